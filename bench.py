@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- LiDAR frames/s of Slam::AddFrame (end to end, from a HOST cloud) on synthetic VLS-128 sequences.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -10,16 +10,27 @@ update) on one VLS-128-shaped scan (128 x 2048 firings, ~260k points) that is ha
 Slam::AddFrames receives it (slam_lib/src/Slam.cxx:230-237): the upload is INSIDE the timed region.  It is a replay:
 the caller holds the next cloud while the current one is registered and announces it (lsa_slam_hint_next_frame), so
 the upload (pinned staging, copy stream) and the extraction of frame f + 1 run beside the registration of frame f.
-Two more legs are reported beside the headline (N = 1): the same replay from scans already resident in HBM
-("replay_resident") and the strictly causal one -- host clouds, nothing announced ahead ("causal_no_lookahead").
 Every rank replays its own independent sequence (seed 1000 + rank) on its own GPU -- the path shards by sequence
 (SURVEY.md 8e), scaling is weak, the only exchange is the all-gather of the 4x4 pose + stamp of every sequence
 after each step (RCCL when there is more than one rank).  Without a launcher, `--gpus N` with N > 1 starts the N
-ranks itself.  Rank 0 prints ONE JSON line with two extra objects:
+ranks itself.  Rank 0 prints ONE JSON line.
+
+A plain run does only what the headline needs: inputs, warm-up, the K timed steps, the result line.
+--dump-outputs DIR  after the timed steps, rank 0 writes what its sequence's last step computed, as a caller of
+                    AddFrame receives it, to DIR/<name>.npy (float64 pose and covariance, float32 world coordinates
+                    of the keypoints of the types in use and of the registered frame; a few MB; empty arrays are
+                    not written)
+--full              everything else as well (N = 1 unless noted):
   roofline      achieved algorithmic GB/s of the dominant kernel FAMILY (summed launch time; HIP events on the
-                context's own stream, live during the timed region) against the 8 TB/s HBM peak
+                context's own stream, live during the timed region) against the 8 TB/s HBM peak, and the per-kernel
+                table (`--no-profile` leaves both out, `--profile-all` times every scope in the timed region)
+  extra legs    the same replay from scans already resident in HBM ("replay_resident"), the strictly causal one --
+                host clouds, nothing announced ahead ("causal_no_lookahead") -- the latter from page-locked buffers,
+                and 8 sequences side by side on the GPU ("batch_replay", over the first 1 000 timed frames at most);
+                `--no-extra-legs` leaves them out
   cpu_baseline  the CPU oracle ("port": restatement of the reference algorithm, OpenMP where the reference has it)
-                on the very frames of the timed region, on the host cores
+                on the very frames of the timed region (the first 500 at most), on the host cores;
+                `--no-cpu-baseline` leaves it out
 """
 import argparse
 import json
@@ -62,6 +73,8 @@ def parse():
     ap.add_argument("--no-numa-bind", action="store_true", help="leave the host threads wherever the scheduler puts them (default: on the GPU's NUMA node)")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"], help="nccl (= RCCL over xGMI, the real run); gloo rehearses the multi-rank path on a box with fewer GPUs than ranks (ranks then share devices)")
     ap.add_argument("--profile-all", action="store_true", help="time every scope in the timed region too (costs ~10 %% of the frame rate)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step computed to DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true", help="also the roofline / per-kernel figures, the extra legs and the CPU baseline (off: the headline only)")
     return ap.parse_args()
 
 
@@ -157,6 +170,7 @@ def main():
     total = args.warmup + args.steps
     per_gpu = max(args.sequences_per_gpu, 1)
     mode = "resident" if args.resident else ("causal" if args.causal else "announced")
+    profile = args.full and not args.no_profile
 
     def make_slam():
         s = L.Slam(local_rank, EgoMotion=3)  # MOTION_EXTRAPOLATION_AND_REGISTRATION: the default mode skips the ego-motion ICP
@@ -165,14 +179,18 @@ def main():
             s.set_param(name, float(value))
         return s
 
-    # ---- inputs: one independent sequence per (rank, sequence), generated on the host, kept as host clouds
+    # ---- inputs: one independent sequence per (rank, sequence), generated on the host, kept as host clouds.  Frames are
+    # independent of each other (the generator is keyed by seed and frame), so they are made on the host cores side by side.
+    from concurrent.futures import ThreadPoolExecutor
+
     sequences = []
     npts = 0
-    for s in range(per_gpu):
-        seed = sequence_seed(rank * per_gpu + s)
-        frames = [L.synth_frame(args.model, seed, f) for f in range(total)]
-        npts += sum(p.size for p, _ in frames)
-        sequences.append((seed, frames))
+    with ThreadPoolExecutor(max_workers=min(16, len(os.sched_getaffinity(0)))) as pool:
+        for s in range(per_gpu):
+            seed = sequence_seed(rank * per_gpu + s)
+            frames = list(pool.map(lambda f: L.synth_frame(args.model, seed, f), range(total)))
+            npts += sum(p.size for p, _ in frames)
+            sequences.append((seed, frames))
 
     class Replay:
         """One sequence on one Slam handle, in one of the three modes."""
@@ -228,7 +246,7 @@ def main():
     followers = [threading.Thread(target=follow, args=(s + 1, rp), daemon=True) for s, rp in enumerate(others)]
 
     # pose table of the north star: every rank ends up with every sequence's pose (a collective only when world > 1)
-    exchange = PoseExchange(world, device="cuda" if args.backend == "nccl" else "cpu", per_rank=per_gpu)
+    exchange = PoseExchange(world, device="cuda" if args.backend == "nccl" else "cpu", per_rank=per_gpu) if distributed else None
 
     def step(f):
         # the last warm-up frame announces nothing: the first timed frame's upload and extraction are inside the timed
@@ -246,13 +264,13 @@ def main():
     # kernel FAMILY (largest summed launch time).  Events cost a few microseconds each on this launch-bound path, so
     # the timed region only keeps them on that family, one step in four (all its launches are counted): the roofline
     # figure is measured live over the timed region without slowing what is being timed.
-    if not args.no_profile:
+    if profile:
         ctx.profile(True)
         ctx.profile_reset()
     for t in followers:
         t.start()
     for f in range(args.warmup):
-        if f == 2 and args.warmup > 4 and not args.no_profile:
+        if f == 2 and args.warmup > 4 and profile:
             # the first launch of every kernel loads its code (milliseconds, once): those frames must not name the family
             ctx.sync()
             ctx.profile_reset()
@@ -260,7 +278,7 @@ def main():
         if h is not None:
             h.wait()
     warm_kernels, dominant = [], None
-    if not args.no_profile and args.warmup > 0:
+    if profile and args.warmup > 0:
         warm_kernels = ctx.profile_stats()
         fams = by_family(warm_kernels)
         if fams:
@@ -268,7 +286,7 @@ def main():
 
     stats_acc, stats_now = np.zeros(16), np.zeros(16)
     stats_ptr = ptr(stats_now)
-    if not args.no_profile:
+    if profile:
         ctx.profile_reset()
         if dominant in FAMILY_PREFIX and not args.profile_all:
             ctx.profile_select(FAMILY_PREFIX[dominant], 4)
@@ -310,9 +328,11 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
 
-    ctx_event_overhead = ctx.profile_event_overhead_us()
-    kernels = [] if args.no_profile else ctx.profile_stats()
-    ctx.profile(False)
+    kernels, ctx_event_overhead = [], None
+    if profile:
+        ctx_event_overhead = ctx.profile_event_overhead_us()
+        kernels = ctx.profile_stats()
+        ctx.profile(False)
     extra = {"uploads_taken_over": slam.get_param("UploadsAdopted"), "extractions_taken_over": slam.get_param("LookaheadAdopted"),
              "device_solve_fallbacks": slam.get_param("DeviceSolveFallbacks") + sum(rp.slam.get_param("DeviceSolveFallbacks") for rp in others_alive),
              "icp_gate_timeouts": slam.get_param("IcpGateTimeouts") + sum(rp.slam.get_param("IcpGateTimeouts") for rp in others_alive)}
@@ -392,9 +412,11 @@ def main():
                 }
                 for k in sorted(table, key=lambda k: -k["total_ms"])
             }
+        if args.dump_outputs:
+            dump_outputs(slam, exchange, args.dump_outputs)
     slam.close()
     if rank == 0:
-        if world == 1 and per_gpu == 1 and not args.no_extra_legs:
+        if args.full and world == 1 and per_gpu == 1 and not args.no_extra_legs:
             for key, m in (("replay_resident", "resident"), ("causal_no_lookahead", "causal"), ("replay_announced", "announced")):
                 if m != mode:
                     out[key] = extra_leg(Replay(sequences[0][1], m), args)
@@ -408,12 +430,37 @@ def main():
                 L.Slam.unpin_cloud(pts)
             if args.batch_sequences > 1:
                 out["batch_replay"] = batch_replay(args, local_rank)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(args, sequences[0])
         print(json.dumps(out), flush=True)
     if distributed:
         dist.barrier()
         dist.destroy_process_group()
+
+
+def dump_outputs(slam, exchange, out_dir):
+    """What a caller of AddFrame receives after the last timed step of this rank's (first) sequence, one .npy per array:
+    pose and covariance (float64), the keypoints of every type the Slam uses and the registered frame, in WORLD
+    coordinates (float32 x, y, z, in the library's order), and with several ranks the all-gathered poses of every sequence
+    (float64).  Empty arrays are not written."""
+    import numpy as np
+
+    import lidarslam_amd as L
+
+    def xyz(pts):
+        return np.stack([pts["x"], pts["y"], pts["z"]], axis=1)
+
+    arrays = {"world_transform": slam.world_transform(), "covariance": slam.covariance()}
+    for k, name, use in ((L.EDGE, "edge", "UseEdges"), (L.PLANE, "plane", "UsePlanes"), (L.BLOB, "blob", "UseBlobs")):
+        if slam.get_param(use):  # a type the Slam does not use has no keypoints (blobs, by default)
+            arrays[f"keypoints_{name}"] = xyz(slam.keypoints(k, 1))
+    arrays["registered_frame"] = xyz(slam.registered_frame())
+    if exchange is not None:
+        arrays["sequence_poses"] = exchange.poses()[0]
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        if a.size:  # an empty array is nothing to compare
+            np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def extra_leg(rp, args):
@@ -430,13 +477,35 @@ def extra_leg(rp, args):
     return {"value": args.steps / dt, "unit": "frames/s", "ms_per_step": 1e3 * dt / args.steps}
 
 
+BATCH_MAX_STEPS = 1000  # timed frames per sequence of the batch leg at most: 8 sequences x 8 MB a frame stay in HBM
+CPU_MAX_STEPS = 500     # timed frames of the CPU baseline at most (~60 ms a frame on 16 host cores)
+
+
 def batch_replay(args, device):
     """Not the headline: the same GPU replaying several independent sequences side by side (seeds 1000, 1001, ...),
-    same frames per sequence as the timed region above, aggregate frames/s between a common start and the last end."""
+    the same warm-up and the frames of the timed region above (the first BATCH_MAX_STEPS of them at most) per sequence,
+    aggregate frames/s between a common start and the last end."""
+    import numpy as np
+
+    import lidarslam_amd as L
+    from concurrent.futures import ThreadPoolExecutor
     from lidarslam_amd.replay import ConcurrentReplay, sequence_seed
 
     n = args.batch_sequences
-    rep = ConcurrentReplay(device, args.model, [sequence_seed(s) for s in range(n)], args.warmup + args.steps, lookahead=True, EgoMotion=3)
+    steps = min(args.steps, BATCH_MAX_STEPS)
+    total = args.warmup + steps
+    rep = ConcurrentReplay(device, args.model, [sequence_seed(s) for s in range(n)], 0, lookahead=True, EgoMotion=3)
+    # the frame stores are filled here rather than by ConcurrentReplay: the frames are made on the host cores side by side,
+    # a bounded batch at a time
+    with ThreadPoolExecutor(max_workers=min(16, len(os.sched_getaffinity(0)))) as pool:
+        for s, slam in enumerate(rep.slams):
+            seed = sequence_seed(s)
+            for f0 in range(0, total, 64):
+                for f, (pts, stamp) in zip(range(f0, total), pool.map(lambda f: L.synth_frame(args.model, seed, f), range(f0, min(total, f0 + 64)))):
+                    slam.store_frame(f, pts)
+                    rep.stamps[s].append(stamp)
+    rep.frames = total
+    rep.poses = np.zeros((n, total, 4, 4))
     for kv in args.param:
         name, value = kv.split("=")
         for s in rep.slams:
@@ -446,7 +515,7 @@ def batch_replay(args, device):
     fallbacks = [int(s.get_param("DeviceSolveFallbacks")) for s in rep.slams]  # of EVERY sequence: solves side by side compete for the CUs
     timeouts = [int(s.get_param("IcpGateTimeouts")) for s in rep.slams]
     rep.close()
-    return {"sequences_on_one_gpu": n, "value": fps, "device_solve_fallbacks": fallbacks, "icp_gate_timeouts": timeouts, "unit": "frames/s", "per_sequence": fps / n, "steps": args.steps, "warmup": args.warmup,
+    return {"sequences_on_one_gpu": n, "value": fps, "device_solve_fallbacks": fallbacks, "icp_gate_timeouts": timeouts, "unit": "frames/s", "per_sequence": fps / n, "steps": steps, "warmup": args.warmup,
             "frames_from": "frame store in HBM, look-ahead extraction", "rolling_maps": maps}
 
 
@@ -495,7 +564,7 @@ def cpu_baseline(args, sequence):
     frames of the timed region: it registers the warm-up frames too (the maps have to exist) but only the timed ones
     count, exactly as on the GPU.  SURVEY.md 8d asks for NbThreads = 1, 4 (the reference's recommended setting,
     ros_wrapping/lidar_slam/params/slam_config_outdoor.yaml:93) and all cores: the headline figure is the all-cores run over
-    the whole timed region; 1 and 4 threads run a bounded sample of it (the first frames of the timed region, ~10 s each)."""
+    the timed region (its first CPU_MAX_STEPS frames at most); 1 and 4 threads run a bounded sample of it (the first frames of the timed region, ~10 s each)."""
     import numpy as np
 
     from oracle import oracle as O
@@ -518,7 +587,7 @@ def cpu_baseline(args, sequence):
             times.append(time.perf_counter() - t)
         return np.array(times[args.warmup:])
 
-    t = run(threads, args.steps)
+    t = run(threads, min(args.steps, CPU_MAX_STEPS))
     out = {
         "value": float(len(t) / t.sum()),
         "unit": "frames/s",

@@ -3,7 +3,7 @@
 # busy (does the clock state of a mostly idle GPU explain in-pipeline kernel times twice those of back-to-back launches?)
 out=gpurun_out/r2c
 mkdir -p $out
-run() { timeout -k 10 300 python bench.py --no-cpu-baseline --no-extra-legs "$@"; }
+run() { timeout -k 10 300 python bench.py --full --no-cpu-baseline --no-extra-legs "$@"; }
 show() { python - "$1" <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

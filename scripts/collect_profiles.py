@@ -1,11 +1,11 @@
-"""Copy the judged summaries of scripts/round_measure.sh from gpurun_out/<round>/ (scratch) into
+"""Copy the judged summaries of scripts/round_measure.sh from OUT/<round>/ (scratch) into
 profiles/ (tracked): kernel stats of the rocprofv3 --kernel-trace --stats run, the PMC per-kernel
-traffic table, the bench JSON lines and the CPU sweep logs.  usage: collect_profiles.py r01"""
+traffic table, the bench JSON lines and the CPU sweep logs.  usage: collect_profiles.py r01 OUT"""
 import glob, json, os, shutil, subprocess, sys
 rnd = sys.argv[1] if len(sys.argv) > 1 else "r03"
-src, dst = os.path.join("gpurun_out", rnd), "profiles"
+src, dst = os.path.join(sys.argv[2], rnd), "profiles"
 os.makedirs(dst, exist_ok=True)
-newest = lambda pattern: sorted(glob.glob(pattern), key=os.path.getmtime, reverse=True)  # gpurun_out keeps earlier runs too
+newest = lambda pattern: sorted(glob.glob(pattern), key=os.path.getmtime, reverse=True)  # OUT may keep earlier runs too
 ks = newest(os.path.join(src, "trace", "*", "*kernel_stats.csv"))
 if ks: shutil.copy(ks[0], os.path.join(dst, f"{rnd}_vls128_kernel_stats.csv"))
 f = newest(os.path.join(src, "pmc_fetch", "*", "*counter_collection.csv"))

@@ -6,7 +6,7 @@ mkdir -p $O
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 timeout -k 10 900 python -m pytest tests -m gpu -x -q "$@" > $O/tests.log 2>&1; rc=$?; tail -3 $O/tests.log; echo "tests rc=$rc"
 [ $rc -ne 0 ] && exit $rc
-timeout -k 10 300 python bench.py --steps 40 --warmup 8 --no-cpu-baseline --batch-sequences 0 > $O/bench.json 2> $O/bench.err; echo "bench rc=$?"
+timeout -k 10 300 python bench.py --full --steps 40 --warmup 8 --no-cpu-baseline --batch-sequences 0 > $O/bench.json 2> $O/bench.err; echo "bench rc=$?"
 python - $O/bench.json <<'PY'
 import json,sys
 try:

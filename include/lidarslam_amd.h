@@ -578,6 +578,31 @@ int lsa_transform_frame_at(lsa_ctx* ctx, int interpolate, const double H0[16], c
  * inputs.  fn: 0 lsa_sin(x) 1 lsa_cos(x) 2 lsa_atan2(y, x) 3 (float)sqrt((float)x)
  * 4 (float)x / (float)y  5 sqrt(x)  6 x / y.  Results as doubles. */
 int lsa_selftest_math(lsa_ctx* ctx, int fn, const double* x, const double* y, int n, double* out);
+/* Device self-test of the fixed-size solvers the kernels inline, evaluated by the same templates: n records of
+ * doubles, one thread per record, record i at in + i * IN and out + i * OUT.  Points are rounded to float, Sym3 and
+ * eigen33 of fn 0 and 2 work in float; Sym3 = xx xy xz yy yz zz; e0 e1 e2 = eigenvectors of l0 <= l1 <= l2; pose
+ * matrices are R row-major (9) then t (3); quaternions w x y z.
+ *   fn  IN  OUT
+ *    0  49  15  PCA_F   CovAccum<float> + eigen33<float>. in: k (1..16), k points x y z (48 slots).
+ *                       out: mean[3] l0 l1 l2 e0[3] e1[3] e2[3]
+ *    1  49  15  PCA_D   the same with CovAccum<double> + eigen33<double> (float points)
+ *    2   6  12  EIG33_F eigen33<float> of a Sym3. out: l0 l1 l2 e0[3] e1[3] e2[3]
+ *    3   6  12  EIG33_D eigen33<double>
+ *    4  12   4  SPD3    solve_spd<3>. in: A[9] row-major, b[3]. out: ok (1/0), x[3] (0 where not reached)
+ *    5  42   7  SPD6    solve_spd<6>. in: A[36], b[6]. out: ok, x[6]
+ *    6  23  28  ACCUM   rotation_and_derivatives + accumulate_one of one residual block at pose w.
+ *                       in: A[9] P[3] X[3] weight sat w[6] (x y z rx ry rz; Tukey a^2 = sat * sat).
+ *                       out: cost, g[6], H upper triangle row-major[21]
+ *    7  42  39  POSE    in: M0[12] M1[12] w[6] qa[4] qb[4] s t t0 t1.  out: FromXYZRPY(w)[12], ToXYZRPY(M0)[6],
+ *                       ToQuaternion(M0)[4], Slerp(qa, qb, s)[4], RotationAngle(M0), interp_eval of
+ *                       MakeInterpConst(M0, M1, t0, t1) at t [12]
+ *    8  12   4  SPD3_HOST   SolveSPD of the host LM loop (host/lsa_lm.cpp), layout of fn 4
+ *    9  42   7  SPD6_HOST   layout of fn 5
+ *   10   9  12  JACOBI3_HOST  the host's cyclic Jacobi eigen-solver. in: A[9]. out: evals[3] ascending, V[9] row-major
+ *                            (columns = eigenvectors)
+ *   11  36  42  JACOBI6_HOST  in: A[36]. out: evals[6], V[36]
+ * fn 8-11 run on the CPU and accept ctx == NULL. */
+int lsa_selftest_numerics(lsa_ctx* ctx, int fn, const double* in, int n, double* out);
 /* Diagnostic: `blocks` single-wave workgroups sleep-spinning for `ms` (<= 2000) milliseconds on a side stream. */
 int lsa_selftest_keep_busy(lsa_ctx* ctx, int ms, int blocks);
 

@@ -115,6 +115,10 @@ void SymEigen(int n, const double* Ain, double* evals, double* evecs)
 
 }  // namespace
 
+// lsa_selftest_numerics, fn 8-11: the two file-local solvers above on one record (layouts: include/lidarslam_amd.h)
+bool ProbeSolveSPD(int n, const double* A, const double* b, double* x) { return SolveSPD(n, A, b, x); }
+void ProbeSymEigen(int n, const double* A, double* evals, double* evecs) { SymEigen(n, A, evals, evecs); }
+
 void LocalOptimizer::TakeResult(const lsa_solve_result_t& r, SolveSummary& sum)
 {
   sum = SolveSummary();

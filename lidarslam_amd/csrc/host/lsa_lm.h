@@ -80,5 +80,9 @@ private:
   void TakeResult(const lsa_solve_result_t& r, SolveSummary& summary);
 };
 
+// SolveSPD / SymEigen of lsa_lm.cpp for the self-test (lsa_selftest_numerics)
+bool ProbeSolveSPD(int n, const double* A, const double* b, double* x);
+void ProbeSymEigen(int n, const double* A, double* evals, double* evecs);
+
 }  // namespace host
 }  // namespace lsa

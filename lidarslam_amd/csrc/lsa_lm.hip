@@ -227,57 +227,6 @@ __device__ __forceinline__ bool lm_evaluate(const LmParams& p, unsigned epoch, u
   return true;
 }
 
-// dense symmetric positive definite solve, as SolveSPD of host/lsa_lm.cpp: Cholesky, forward, backward
-template <int N>
-__device__ __forceinline__ bool solve_spd(const double A[N * N], const double b[N], double x[N])
-{
-  // (every division by a diagonal element is a multiplication by its reciprocal, taken once: 6 divisions instead of 27
-  // on the one thread that runs the step; host/lsa_lm.cpp and the oracle do the same, operation for operation)
-  double L[N * N], rinv[N];
-#pragma unroll
-  for (int i = 0; i < N * N; ++i) L[i] = 0.;
-  bool ok = true;
-#pragma unroll
-  for (int i = 0; i < N; ++i)
-#pragma unroll
-    for (int j = 0; j <= i; ++j)
-    {
-      double s = A[i * N + j];
-#pragma unroll
-      for (int k = 0; k < j; ++k) s -= L[i * N + k] * L[j * N + k];
-      if (i == j)
-      {
-        if (!(s > 0.0) || !isfinite(s)) ok = false;
-        L[i * N + i] = __builtin_sqrt(s);
-        rinv[i] = 1.0 / L[i * N + i];
-      }
-      else
-        L[i * N + j] = s * rinv[j];
-    }
-  if (!ok) return false;
-  double y[N];
-#pragma unroll
-  for (int i = 0; i < N; ++i)
-  {
-    double s = b[i];
-#pragma unroll
-    for (int k = 0; k < i; ++k) s -= L[i * N + k] * y[k];
-    y[i] = s * rinv[i];
-  }
-#pragma unroll
-  for (int i = N - 1; i >= 0; --i)
-  {
-    double s = y[i];
-#pragma unroll
-    for (int k = i + 1; k < N; ++k) s -= L[k * N + i] * x[k];
-    x[i] = s * rinv[i];
-  }
-#pragma unroll
-  for (int i = 0; i < N; ++i)
-    if (!isfinite(x[i])) ok = false;
-  return ok;
-}
-
 enum LmCode
 {
   kCodeNone = 0, kCodeNotEnoughMatches, kCodeGradient0, kCodeMaxIterations, kCodeGradient, kCodeMinRadius, kCodeInvalidSteps, kCodeParameterTolerance,

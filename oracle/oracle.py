@@ -54,6 +54,7 @@ def lib():
         L.orc_lm_solve.argtypes = [vp, vp, i32, f64, vp, i32, i32, vp, vp, vp, vp]
         L.orc_covariance.argtypes = [vp, vp, i32, f64, vp, vp, vp]
         L.orc_math.argtypes = [i32, vp, vp, i32, vp]
+        L.orc_numerics.argtypes = [i32, vp, i32, vp]
         L.orc_undistort.argtypes = [vp, i32, vp, vp, f64, f64]
         L.orc_icp_link.argtypes = [vp, i32, i32, f64, f64, f64, vp, vp, vp, vp]
         L.orc_transform.argtypes = [vp, i32, vp]
@@ -222,6 +223,19 @@ def math(fn, x, y=None):
     y = np.ascontiguousarray(x if y is None else y, np.float64)
     out = np.zeros_like(x)
     lib().orc_math(fn, ptr(x), ptr(y), x.size, ptr(out))
+    return out
+
+
+NUMERICS_WIDTHS = [(49, 15), (49, 15), (6, 12), (6, 12), (12, 4), (42, 7), (23, 28), (42, 39), (12, 4), (42, 7), (9, 12), (36, 42)]
+
+
+def numerics(fn, records):
+    """Same fn ids and record layouts as lsa_selftest_numerics, evaluated by the restatement: records (n, IN) -> (n, OUT)"""
+    win, wout = NUMERICS_WIDTHS[fn]
+    rec = np.ascontiguousarray(records, np.float64).reshape(-1, win)
+    out = np.zeros((rec.shape[0], wout))
+    if lib().orc_numerics(int(fn), ptr(rec), rec.shape[0], ptr(out)) != 0:
+        raise ValueError(f"orc_numerics: bad fn {fn}")
     return out
 
 

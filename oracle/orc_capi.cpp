@@ -248,6 +248,118 @@ int orc_math(int fn, const double* x, const double* y, int n, double* out)
   return 0;
 }
 
+// ---- fixed-size solvers (same fn ids and record layouts as lsa_selftest_numerics, include/lidarslam_amd.h) ----
+}  // extern "C"
+namespace
+{
+const int kNumIn[12] = {49, 49, 6, 6, 12, 42, 23, 42, 12, 42, 9, 36};
+const int kNumOut[12] = {15, 15, 12, 12, 4, 7, 28, 39, 4, 7, 12, 42};
+
+template <typename T> void put_eig(const M3<T>& v, const T l[3], double* o)
+{
+  for (int i = 0; i < 3; ++i) o[i] = l[i];
+  for (int c = 0; c < 3; ++c)
+    for (int r = 0; r < 3; ++r) o[3 + 3 * c + r] = v(r, c);
+}
+template <typename T> void numerics_pca(const double* in, double* o)
+{
+  int k = (int)in[0];
+  k = k < 1 ? 1 : (k > 16 ? 16 : k);
+  V3<T> mean;
+  M3<T> cov, v;
+  T l[3];
+  mean_and_cov<T>(k, [&](int i, float& x, float& y, float& z) { x = (float)in[1 + 3 * i]; y = (float)in[2 + 3 * i]; z = (float)in[3 + 3 * i]; }, mean, cov);
+  eigen33(cov, v, l);
+  o[0] = mean.x; o[1] = mean.y; o[2] = mean.z;
+  put_eig(v, l, o + 3);
+}
+template <typename T> void numerics_eig33(const double* in, double* o)
+{
+  M3<T> m, v;
+  const int map[9] = {0, 1, 2, 1, 3, 4, 2, 4, 5};
+  for (int i = 0; i < 9; ++i) m.m[i] = (T)in[map[i]];
+  T l[3];
+  eigen33(m, v, l);
+  put_eig(v, l, o);
+}
+void numerics_spd(int n, const double* in, double* o)
+{
+  double x[6] = {0, 0, 0, 0, 0, 0};
+  o[0] = CholeskySolve(n, in, in + n * n, x) ? 1. : 0.;
+  for (int i = 0; i < n; ++i) o[1 + i] = x[i];
+}
+void numerics_accum(const double* in, double* o)
+{
+  Residual r;
+  r.valid = true;
+  std::memcpy(r.A, in, sizeof(r.A));
+  std::memcpy(r.P, in + 9, sizeof(r.P));
+  std::memcpy(r.X, in + 12, sizeof(r.X));
+  r.weight = in[15];
+  r.sat = in[16];
+  NormalEq e;
+  EvaluateResiduals(&r, 1, in + 17, true, e);
+  o[0] = e.cost;
+  for (int a = 0; a < 6; ++a) o[1 + a] = e.g[a];
+  int h = 7;
+  for (int a = 0; a < 6; ++a)
+    for (int b = a; b < 6; ++b) o[h++] = e.H[a * 6 + b];
+}
+Iso iso_from12(const double* v)
+{
+  Iso r;
+  std::memcpy(r.R, v, sizeof(r.R));
+  std::memcpy(r.t, v + 9, sizeof(r.t));
+  return r;
+}
+void iso_to12(const Iso& a, double* o)
+{
+  std::memcpy(o, a.R, sizeof(a.R));
+  std::memcpy(o + 9, a.t, sizeof(a.t));
+}
+void numerics_pose(const double* in, double* o)
+{
+  const Iso M0 = iso_from12(in), M1 = iso_from12(in + 12);
+  iso_to12(xyzrpy_to_iso(in + 24), o);
+  iso_to_xyzrpy(M0, o + 12);
+  const Quat q = quat_from_matrix(M0.R);
+  o[18] = q.w; o[19] = q.x; o[20] = q.y; o[21] = q.z;
+  const Quat qa = {in[30], in[31], in[32], in[33]}, qb = {in[34], in[35], in[36], in[37]};
+  const Quat qs = slerp_eval(slerp_prepare(qa, qb), in[38]);
+  o[22] = qs.w; o[23] = qs.x; o[24] = qs.y; o[25] = qs.z;
+  o[26] = rotation_angle(M0.R);
+  Interpolator it;
+  it.SetTimes(in[40], in[41]);
+  it.SetTransforms(M0, M1);
+  iso_to12(it(in[39]), o + 27);
+}
+}  // namespace
+extern "C" {
+
+int orc_numerics(int fn, const double* in, int n, double* out)
+{
+  if (fn < 0 || fn >= 12 || n < 0) return -1;
+  for (int i = 0; i < n; ++i)
+  {
+    const double* a = in + (size_t)i * kNumIn[fn];
+    double* o = out + (size_t)i * kNumOut[fn];
+    switch (fn)
+    {
+      case 0: numerics_pca<float>(a, o); break;
+      case 1: numerics_pca<double>(a, o); break;
+      case 2: numerics_eig33<float>(a, o); break;
+      case 3: numerics_eig33<double>(a, o); break;
+      case 4: case 8: numerics_spd(3, a, o); break;
+      case 5: case 9: numerics_spd(6, a, o); break;
+      case 6: numerics_accum(a, o); break;
+      case 7: numerics_pose(a, o); break;
+      case 10: JacobiEigen(3, a, o, o + 3); break;
+      case 11: JacobiEigen(6, a, o, o + 6); break;
+    }
+  }
+  return 0;
+}
+
 // ---- undistortion ------------------------------------------------------------------
 int orc_undistort(lsa_point_t* pts, int n, const double H0[16], const double H1[16], double t0, double t1)
 {

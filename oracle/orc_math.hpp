@@ -415,6 +415,14 @@ inline Quat slerp_eval(const SlerpConst& c, double t)
   return {s0 * c.a.w + s1 * c.b.w, s0 * c.a.x + s1 * c.b.x, s0 * c.a.y + s1 * c.b.y, s0 * c.a.z + s1 * c.b.z};
 }
 
+// Eigen::AngleAxisd(R).angle(): 2 atan2(|q.vec|, |q.w|)
+inline double rotation_angle(const double R[9])
+{
+  Quat q = quat_from_matrix(R);
+  double n = std::sqrt((q.x * q.x + q.y * q.y) + q.z * q.z);
+  return (n != 0.) ? 2. * t_atan2(n, std::abs(q.w)) : 0.;
+}
+
 // ---------------------------------------------------------------------------
 // RPY <-> matrix (slam_lib/src/Utilities.cxx:33-77)
 inline void rpy_to_matrix(double roll, double pitch, double yaw, double R[9])

@@ -417,10 +417,7 @@ void Slam::UpdateMapsUsingTworld()
   Iso motionSinceLastKf = iso_mul(iso_inverse(KfLastPose), Tworld);
   double transSinceLastKf = std::sqrt((motionSinceLastKf.t[0] * motionSinceLastKf.t[0] + motionSinceLastKf.t[1] * motionSinceLastKf.t[1]) +
                                       motionSinceLastKf.t[2] * motionSinceLastKf.t[2]);
-  // Eigen::AngleAxisd(R).angle(): 2 atan2(|q.vec|, |q.w|)
-  Quat q = quat_from_matrix(motionSinceLastKf.R);
-  double n = std::sqrt((q.x * q.x + q.y * q.y) + q.z * q.z);
-  double rotSinceLastKf = (n != 0.) ? 2. * t_atan2(n, std::abs(q.w)) : 0.;
+  double rotSinceLastKf = rotation_angle(motionSinceLastKf.R);
 
   constexpr double MIN_KF_NB = 10.;
   double thresholdCoef = std::min(KfCounter / MIN_KF_NB, 1.);

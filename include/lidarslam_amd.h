@@ -506,6 +506,48 @@ int lsa_solve_device_interlude(lsa_ctx* ctx, void (*fn)(void*), void* arg);
 int lsa_registration_error(lsa_ctx* ctx, unsigned type_mask, const double pose[16], int two_d_mode, double cov[36], double err[2]);
 
 /* ------------------------------------------------------------------------- */
+/* External sensor constraints of the localization problem (Slam.cxx:1123-1131, CeresCostFunctions.h:255-341).
+ * Both act on the world pose w = (X, Y, Z, rX, rY, rZ) under ScaledLoss(NULL, weight):
+ *   wheel    r = |t - p| - d           (|t - p| replaced by 0, and its Jacobian by 0, where |t - p|^2 < 1e-6)
+ *   gravity  r = R(rX, rY, rZ) g_cur - g_ref
+ * cost += 1/2 weight |r|^2, g += weight J^T r, H += weight J^T J; the match count is not touched. */
+typedef struct lsa_sensor_terms_t
+{
+  int wheel;          /* 1: the odometer term is in the problem */
+  double wheel_weight;
+  double p[3];        /* origin the travelled distance is measured from (the reference's PreviousPose: identity) */
+  double d;           /* distance travelled since the first frame with a measurement */
+  int gravity;        /* 1: the gravity alignment term is in the problem */
+  double gravity_weight;
+  double g_ref[3];    /* reference gravity direction (unit) */
+  double g_cur[3];    /* gravity direction measured at the frame's time (unit) */
+} lsa_sensor_terms_t;
+/* The terms enter every lsa_accumulate, lsa_solve, lsa_solve_device(_begin / _linked) and lsa_registration_error of the
+ * context from now on (a solve enqueued ahead carries the terms of the moment it was enqueued); NULL clears them. */
+int lsa_set_sensor_terms(lsa_ctx* ctx, const lsa_sensor_terms_t* terms);
+/* Host evaluation of the terms at w (rotation from libm sin / cos): sums[29] = cost, g[6], H upper triangle row by row
+ * (21), count -- the layout of the device's normal equations; sums are overwritten, not added to. */
+int lsa_sensor_terms_eval(const lsa_sensor_terms_t* terms, const double w[6], double sums[29]);
+
+/* The reference's measurement managers (SensorConstraints.h / .cxx: WheelOdometryManager absolute mode, ImuManager) on
+ * the host, without a device: what Slam::ComputeSensorConstraints makes of the measurements at one LiDAR time.
+ * lsa_sensors_compute applies the whole rule of Slam::AddFrames: when neither manager is usable (weight > 1e-6 and at
+ * least one measurement) nothing is computed and the previous terms are returned again. */
+typedef struct lsa_sensors lsa_sensors;
+lsa_sensors* lsa_sensors_create(void);
+void lsa_sensors_destroy(lsa_sensors* s);
+int lsa_sensors_add_wheel_odom(lsa_sensors* s, double time, double distance);
+int lsa_sensors_add_gravity(lsa_sensors* s, double time, const double acc[3]);
+int lsa_sensors_set_weights(lsa_sensors* s, double wheel_weight, double gravity_weight);
+int lsa_sensors_set_time_offset(lsa_sensors* s, double offset);
+/* ClearSensorMeasurements: measurements and terms cleared, time offset 0; the gravity reference and the odometer
+ * baseline are kept */
+int lsa_sensors_clear(lsa_sensors* s);
+int lsa_sensors_compute(lsa_sensors* s, double lidar_time, lsa_sensor_terms_t* out);
+/* the gravity reference (zero until first needed); returns 1 when it has been computed */
+int lsa_sensors_gravity_ref(const lsa_sensors* s, double g[3]);
+
+/* ------------------------------------------------------------------------- */
 /* Seam 4: undistortion / transforms.                                         */
 
 /* CurrentUndistortedKeypoints = CurrentRawKeypoints (Slam.cxx:984). */
@@ -706,6 +748,13 @@ int lsa_slam_get_debug_information(lsa_slam* s, double out[10]);
 int lsa_slam_get_map(lsa_slam* s, int type, int clean, lsa_point_t* out, int capacity);
 int lsa_slam_get_target_submap(lsa_slam* s, int type, lsa_point_t* out, int capacity);
 lsa_ctx* lsa_slam_context(lsa_slam* s);
+/* Slam::AddWheelOdomMeasurement / AddGravityMeasurement / ClearSensorMeasurements (Slam.cxx:1582-1598).  Weights and the
+ * time offset are the parameters "WheelOdomWeight", "GravityWeight" and "SensorTimeOffset" of lsa_slam_set_param. */
+int lsa_slam_add_wheel_odom_measurement(lsa_slam* s, double time, double distance);
+int lsa_slam_add_gravity_measurement(lsa_slam* s, double time, const double acc[3]);
+int lsa_slam_clear_sensor_measurements(lsa_slam* s);
+/* the sensor terms the last frame's localization solved with (both flags 0: none) */
+int lsa_slam_sensor_terms(const lsa_slam* s, lsa_sensor_terms_t* out);
 
 
 /* ------------------------------------------------------------------------- */

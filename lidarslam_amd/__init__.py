@@ -73,6 +73,10 @@ ABI_SYMBOLS = [
     "lsa_rolling_grid_create", "lsa_rolling_grid_destroy", "lsa_rolling_grid_set", "lsa_rolling_grid_reset", "lsa_rolling_grid_clear",
     "lsa_rolling_grid_size", "lsa_rolling_grid_roll", "lsa_rolling_grid_add", "lsa_rolling_grid_clear_old_points", "lsa_rolling_grid_get",
     "lsa_rolling_grid_build_submap", "lsa_rolling_grid_submap_valid", "lsa_rolling_grid_submap",
+    "lsa_set_sensor_terms", "lsa_sensor_terms_eval", "lsa_sensors_create", "lsa_sensors_destroy", "lsa_sensors_add_wheel_odom",
+    "lsa_sensors_add_gravity", "lsa_sensors_set_weights", "lsa_sensors_set_time_offset", "lsa_sensors_clear", "lsa_sensors_compute",
+    "lsa_sensors_gravity_ref", "lsa_slam_add_wheel_odom_measurement", "lsa_slam_add_gravity_measurement",
+    "lsa_slam_clear_sensor_measurements", "lsa_slam_sensor_terms",
 ]
 
 
@@ -100,6 +104,93 @@ class SolveResult(C.Structure):
         ("num_evaluations", C.c_int), ("num_matches", C.c_int), ("skipped", C.c_int), ("termination", C.c_int),
         ("message", C.c_char_p),
     ]
+
+
+class SensorTerms(C.Structure):
+    """lsa_sensor_terms_t (include/lidarslam_amd.h): the wheel odometer and gravity terms of the localization problem.
+    ``SensorTerms(wheel_weight=1.0, d=3.0)`` turns the odometer term on, ``gravity_weight=...`` the gravity term."""
+
+    _fields_ = [
+        ("wheel", C.c_int), ("wheel_weight", C.c_double), ("p", C.c_double * 3), ("d", C.c_double),
+        ("gravity", C.c_int), ("gravity_weight", C.c_double), ("g_ref", C.c_double * 3), ("g_cur", C.c_double * 3),
+    ]
+
+    def __init__(self, wheel_weight=None, p=(0.0, 0.0, 0.0), d=0.0, gravity_weight=None, g_ref=(0.0, 0.0, 1.0), g_cur=(0.0, 0.0, 1.0)):
+        super().__init__()
+        if wheel_weight is not None:
+            self.wheel, self.wheel_weight, self.d = 1, float(wheel_weight), float(d)
+            self.p[:] = [float(v) for v in p]
+        if gravity_weight is not None:
+            self.gravity, self.gravity_weight = 1, float(gravity_weight)
+            self.g_ref[:] = [float(v) for v in g_ref]
+            self.g_cur[:] = [float(v) for v in g_cur]
+
+    def as_tuple(self):
+        """every field, in order (the flags as ints): equal tuples are equal terms, bit for bit"""
+        return (self.wheel, self.wheel_weight, *self.p, self.d, self.gravity, self.gravity_weight, *self.g_ref, *self.g_cur)
+
+
+def sensor_terms_eval(terms, w):
+    """lsa_sensor_terms_eval: the terms' 29 sums (cost, g[6], H upper triangle, count) at w, on the host (libm)"""
+    w = np.ascontiguousarray(w, np.float64)
+    out = np.zeros(29)
+    if lib().lsa_sensor_terms_eval(C.byref(terms), ptr(w), ptr(out)) != 0:
+        raise LsaError("lsa_sensor_terms_eval")
+    return out
+
+
+def sums_to_normal_equations(sums):
+    """29 sums -> (cost, g[6], H 6x6, count)"""
+    g = np.array(sums[1:7])
+    H = np.zeros((6, 6))
+    h = 7
+    for a in range(6):
+        for b in range(a, 6):
+            H[a, b] = H[b, a] = sums[h]
+            h += 1
+    return float(sums[0]), g, H, int(sums[28])
+
+
+class Sensors:
+    """The wheel odometer / IMU managers of LidarSlam::Slam without a device (lsa_sensors_*)."""
+
+    def __init__(self):
+        self.L = lib()
+        self.h = self.L.lsa_sensors_create()
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.L.lsa_sensors_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        self.close()
+
+    def add_wheel_odom(self, time, distance):
+        self.L.lsa_sensors_add_wheel_odom(self.h, float(time), float(distance))
+
+    def add_gravity(self, time, acc):
+        a = np.ascontiguousarray(acc, np.float64)
+        self.L.lsa_sensors_add_gravity(self.h, float(time), ptr(a))
+
+    def set_weights(self, wheel, gravity):
+        self.L.lsa_sensors_set_weights(self.h, float(wheel), float(gravity))
+
+    def set_time_offset(self, offset):
+        self.L.lsa_sensors_set_time_offset(self.h, float(offset))
+
+    def clear(self):
+        self.L.lsa_sensors_clear(self.h)
+
+    def compute(self, lidar_time):
+        t = SensorTerms()
+        self.L.lsa_sensors_compute(self.h, float(lidar_time), C.byref(t))
+        return t
+
+    def gravity_ref(self):
+        g = np.zeros(3)
+        have = self.L.lsa_sensors_gravity_ref(self.h, ptr(g))
+        return g, bool(have)
 
 
 def icp_link_expected(x6, skipped, successful_steps, link):
@@ -259,6 +350,23 @@ def lib():
     L.lsa_rolling_grid_build_submap.argtypes = [vp, vp, vp, i32]
     L.lsa_rolling_grid_submap_valid.argtypes = [vp]
     L.lsa_rolling_grid_submap.argtypes = [vp, vp, i32]
+    L.lsa_set_sensor_terms.argtypes = [vp, vp]
+    L.lsa_sensor_terms_eval.argtypes = [vp, vp, vp]
+    L.lsa_sensors_create.restype = vp
+    L.lsa_sensors_create.argtypes = []
+    L.lsa_sensors_destroy.restype = None
+    L.lsa_sensors_destroy.argtypes = [vp]
+    L.lsa_sensors_add_wheel_odom.argtypes = [vp, f64, f64]
+    L.lsa_sensors_add_gravity.argtypes = [vp, f64, vp]
+    L.lsa_sensors_set_weights.argtypes = [vp, f64, f64]
+    L.lsa_sensors_set_time_offset.argtypes = [vp, f64]
+    L.lsa_sensors_clear.argtypes = [vp]
+    L.lsa_sensors_compute.argtypes = [vp, f64, vp]
+    L.lsa_sensors_gravity_ref.argtypes = [vp, vp]
+    L.lsa_slam_add_wheel_odom_measurement.argtypes = [vp, f64, f64]
+    L.lsa_slam_add_gravity_measurement.argtypes = [vp, f64, vp]
+    L.lsa_slam_clear_sensor_measurements.argtypes = [vp]
+    L.lsa_slam_sensor_terms.argtypes = [vp, vp]
     _lib = L
     return L
 
@@ -592,6 +700,10 @@ class Context:
     def solve_device_fallbacks(self):
         return self.L.lsa_solve_device_fallbacks(self.h)
 
+    def set_sensor_terms(self, terms=None):
+        """lsa_set_sensor_terms: a SensorTerms enters every accumulate / solve / registration error from now on; None clears"""
+        self._check(self.L.lsa_set_sensor_terms(self.h, C.byref(terms) if terms is not None else None), "lsa_set_sensor_terms")
+
     def registration_error(self, type_mask, pose, two_d=False):
         cov = np.zeros((6, 6))
         err = np.zeros(2)
@@ -737,6 +849,24 @@ class Slam:
 
     def reset(self, reset_log=True):
         self.L.lsa_slam_reset(self.h, int(reset_log))
+
+    # external sensors (Slam::AddWheelOdomMeasurement / AddGravityMeasurement / ClearSensorMeasurements); the weights and
+    # the time offset are the parameters WheelOdomWeight, GravityWeight and SensorTimeOffset
+    def add_wheel_odom(self, time, distance):
+        self._check(self.L.lsa_slam_add_wheel_odom_measurement(self.h, float(time), float(distance)), "lsa_slam_add_wheel_odom_measurement")
+
+    def add_gravity(self, time, acc):
+        a = np.ascontiguousarray(acc, np.float64)
+        self._check(self.L.lsa_slam_add_gravity_measurement(self.h, float(time), ptr(a)), "lsa_slam_add_gravity_measurement")
+
+    def clear_sensor_measurements(self):
+        self._check(self.L.lsa_slam_clear_sensor_measurements(self.h), "lsa_slam_clear_sensor_measurements")
+
+    def sensor_terms(self):
+        """the SensorTerms the last frame's localization solved with"""
+        t = SensorTerms()
+        self._check(self.L.lsa_slam_sensor_terms(self.h, C.byref(t)), "lsa_slam_sensor_terms")
+        return t
 
     def add_frame(self, pts, stamp_us, seq=0):
         """Slam::AddFrame: host scan -> pose."""

@@ -46,6 +46,34 @@ int lsa_slam_get_param(const lsa_slam* s, const char* name, double* value)
   return s->core.GetParam(name, value);
 }
 
+int lsa_slam_add_wheel_odom_measurement(lsa_slam* s, double time, double distance)
+{
+  if (!s) return LSA_E_ARG;
+  s->core.Sensors().AddWheelOdom(time, distance);
+  return LSA_OK;
+}
+
+int lsa_slam_add_gravity_measurement(lsa_slam* s, double time, const double acc[3])
+{
+  if (!s || !acc) return LSA_E_ARG;
+  s->core.Sensors().AddGravity(time, acc);
+  return LSA_OK;
+}
+
+int lsa_slam_clear_sensor_measurements(lsa_slam* s)
+{
+  if (!s) return LSA_E_ARG;
+  s->core.Sensors().Clear();
+  return LSA_OK;
+}
+
+int lsa_slam_sensor_terms(const lsa_slam* s, lsa_sensor_terms_t* out)
+{
+  if (!s || !out) return LSA_E_ARG;
+  *out = s->core.LocalizationSensorTerms();
+  return LSA_OK;
+}
+
 void lsa_slam_reset(lsa_slam* s, int reset_log)
 {
   if (s) s->core.Reset(reset_log != 0);

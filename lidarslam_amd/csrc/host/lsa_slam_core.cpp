@@ -496,6 +496,9 @@ int SlamCore::ProcessCurrentFrame(uint64_t stampUs)
   }
   int rc = ComputeEgoMotion();
   if (rc < 0) return rc;
+  // Slam::ComputeSensorConstraints (Slam.cxx:256-261): the managers compute at the first frame's time when either one is
+  // usable; otherwise the previous frame's terms stay, with their weights
+  LocSensorTerms = SensorManagers.Compute(CurrentTime);
   rc = Localization();
   if (rc < 0) return rc;
   Tick tail;
@@ -884,6 +887,11 @@ int SlamCore::Localization()
 {
   Tick tloc;
   struct AtExit { SlamCore* c; Tick* t; ~AtExit() { c->DbgAcc[5] += t->Stop() - (c->Stats.loc_icp + c->Stats.loc_lm + c->Stats.submap + c->Stats.undistort); } } atExit{this, &tloc};
+  // the sensor terms enter this frame's localization problem only (Slam.cxx:1123-1131): every solve and the registration
+  // error below; cleared on every way out, so that neither the next ego-motion nor anything else sees them
+  const bool sensorTerms = LocSensorTerms.wheel || LocSensorTerms.gravity;
+  if (sensorTerms) lsa_set_sensor_terms(Ctx, &LocSensorTerms);
+  struct SensorTermsGuard { lsa_ctx* ctx; bool on; ~SensorTermsGuard() { if (on) lsa_set_sensor_terms(ctx, nullptr); } } sensorGuard{Ctx, sensorTerms};
   PreviousTworld = Tworld;
   Tworld = PreviousTworld * Trelative;
   // With the maps on the device the reset, the first undistortion and the keypoints' boxes under the pose guess (which the
@@ -1883,6 +1891,9 @@ int SlamCore::SetParamValue(const std::string& name, double v)
 #define X(NAME, MEMBER, TYPE) if (name == NAME) { MEMBER = static_cast<TYPE>(v); return LSA_OK; }
   LSA_PARAMS(X)
 #undef X
+  if (name == "WheelOdomWeight") { SensorManagers.SetWheelOdomWeight(v); return LSA_OK; }
+  if (name == "GravityWeight") { SensorManagers.SetGravityWeight(v); return LSA_OK; }
+  if (name == "SensorTimeOffset") { SensorManagers.SetTimeOffset(v); return LSA_OK; }
   if (name == "NbThreads") return LSA_OK;  // OpenMP thread count of the reference: no meaning on the device path
   if (name == "Verbosity") return LSA_OK;
   if (name == "EgoMotion") { EgoMotion = static_cast<EgoMotionMode>(static_cast<int>(v)); return LSA_OK; }
@@ -1927,6 +1938,9 @@ int SlamCore::GetParam(const std::string& name, double* v) const
   if (name == "EgoMotion") { *v = static_cast<int>(EgoMotion); return LSA_OK; }
   if (name == "Undistortion") { *v = static_cast<int>(Undistortion); return LSA_OK; }
   if (name == "MapUpdate") { *v = static_cast<int>(MapUpdate); return LSA_OK; }
+  if (name == "WheelOdomWeight") { *v = SensorManagers.GetWheelOdomWeight(); return LSA_OK; }
+  if (name == "GravityWeight") { *v = SensorManagers.GetGravityWeight(); return LSA_OK; }
+  if (name == "SensorTimeOffset") { *v = SensorManagers.GetTimeOffset(); return LSA_OK; }
   if (name == "AzimuthalResolution") { *v = Ctx ? lsa_get_azimuthal_resolution(Ctx) : 0.; return LSA_OK; }
   if (name == "VoxelGridLeafSizeEdges") { *v = LocalMaps[LSA_EDGE]->GetLeafSize(); return LSA_OK; }
   if (name == "VoxelGridLeafSizePlanes") { *v = LocalMaps[LSA_PLANE]->GetLeafSize(); return LSA_OK; }

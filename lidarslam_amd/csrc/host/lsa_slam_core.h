@@ -23,6 +23,7 @@
 #include "lsa_hostmath.h"
 #include "lsa_lm.h"
 #include "lsa_rolling_grid.h"
+#include "lsa_sensor_constraints.h"
 
 namespace lsa
 {
@@ -147,6 +148,11 @@ public:
 
   int SetParam(const std::string& name, double v);
   int GetParam(const std::string& name, double* v) const;
+  // Slam::AddWheelOdomMeasurement / AddGravityMeasurement / ClearSensorMeasurements (Slam.cxx:1582-1598); the weights and
+  // the time offset are the parameters WheelOdomWeight, GravityWeight, SensorTimeOffset.  Slam::Reset leaves them alone.
+  SensorConstraints& Sensors() { return SensorManagers; }
+  // the terms the last frame's localization solved with
+  const lsa_sensor_terms_t& LocalizationSensorTerms() const { return LocSensorTerms; }
   // LocalMaps[k] after every pending insertion has landed (Slam::GetMap reads through this)
   RollingGrid& Map(int k) { WaitMaps(); return *LocalMaps[k]; }
 
@@ -255,6 +261,8 @@ private:
   int ExtractKeypoints();
   int ComputeEgoMotion();
   int Localization();
+  SensorConstraints SensorManagers;
+  lsa_sensor_terms_t LocSensorTerms = {};
   int UpdateMapsUsingTworld();
   int EstimateOverlap();
   void CheckMotionLimits();

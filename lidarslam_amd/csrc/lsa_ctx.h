@@ -263,6 +263,7 @@ struct lsa_ctx
   int lm_records = 512;   // residual blocks per workgroup of the solve kernel the launch aims at (LSA_LM_RECORDS)
   int lm_cache_slots = 0;         // layers of residual blocks the solve kernel keeps in LDS (LSA_LM_CACHE caps it)
   int lm_fallbacks = 0;           // solves that timed out on the device and were redone by the host-driven loop
+  lsa_sensor_terms_t sensor_terms = {};  // lsa_set_sensor_terms: added to every evaluation of the normal equations (both flags 0: none)
   // per match type a ring of kHistRing blocks of 16 ints ([8] rejection histogram + 2 hand-over counters of the kNN
   // cascade): every match takes the next block, the ring is zeroed once per turn instead of one memset per match
   int* hist_dev = nullptr;

@@ -24,6 +24,7 @@
 #include <cmath>
 #include "lsa_accum.h"
 #include "lsa_device_math.h"
+#include "lsa_sensor_terms.h"
 #include "../../include/lsa_pmath.h"
 
 using namespace lsa;
@@ -57,6 +58,10 @@ struct LmParams
   Rigid previous_world;       // PreviousTworld
   double motion0[16];         // Time0, Time1, Rot0 (w x y z), Rot1, Trans0, Trans1
   double* motion_dev;         // the same 16 values between the solves of one loop
+  // wheel odometer / gravity terms of the localization problem (lsa_set_sensor_terms), by value: a solve enqueued ahead
+  // carries the terms of the moment it was enqueued
+  lsa_sensor_terms_t sensors;
+  int sensors_on;
 };
 
 // result layout (doubles): [0..5] pose, [6] initial cost, [7] final cost, [8..36] the 29 sums at the final
@@ -116,6 +121,14 @@ __device__ __forceinline__ void lm_lap(Shared& sh, int slot)
     sh.lap[slot] += now - sh.tk;
     sh.tk = now;
   }
+}
+
+// The sensor terms (lsa_sensor_terms.h) on top of the sums of the evaluation just folded, at sh.w / sh.rot.  Not inlined:
+// inlined, its ~80 live doubles raised the kernel's VGPR count (229 -> 242) and SGPR spills (81 -> 114); as a call the
+// kernel keeps 229 VGPRs, no scratch memory and the same LDS, and a solve without terms never makes the call.
+__device__ __noinline__ void lm_sensor_terms(const lsa_sensor_terms_t* terms, Shared& sh)
+{
+  sensor_terms_add(*terms, sh.w, sh.rot, sh.rot + 9, sh.rot + 18, sh.rot + 27, true, sh.sums[1 - sh.lm.cur_buf]);
 }
 
 __device__ __forceinline__ bool lm_evaluate(const LmParams& p, unsigned epoch, u64* __restrict__ xchg, Shared& sh, double* __restrict__ cache, bool trace)
@@ -223,6 +236,16 @@ __device__ __forceinline__ bool lm_evaluate(const LmParams& p, unsigned epoch, u
     sh.sums[1 - sh.lm.cur_buf][threadIdx.x] = s;
   }
   __syncthreads();
+  // the sensor terms on top of the fold, the same arithmetic in every block; lane 0 of the first wavefront, which is the
+  // one that reads the sums next (lm_step: its LDS operations are served in order).  One uniform branch.
+  if (p.sensors_on && threadIdx.x == 0)
+  {
+    // the callee reads the terms straight from the kernel arguments (LmParams is the first one): taking the address of
+    // `p` would copy all of it to scratch memory
+    const char* args = (const char*)__builtin_amdgcn_kernarg_segment_ptr();
+    const lsa_sensor_terms_t* terms = reinterpret_cast<const lsa_sensor_terms_t*>(args + offsetof(LmParams, sensors));
+    lm_sensor_terms(terms, sh);
+  }
   if (trace) lm_lap(sh, 2);
   return true;
 }
@@ -772,6 +795,8 @@ static int solve_device_begin(lsa_ctx* ctx, unsigned type_mask, const double pri
     row_major_to_rt(link->previous_world, p.previous_world.R, p.previous_world.t);
     std::memcpy(p.motion0, link->motion, sizeof(p.motion0));
   }
+  p.sensors = ctx->sensor_terms;
+  p.sensors_on = (ctx->sensor_terms.wheel || ctx->sensor_terms.gravity) ? 1 : 0;
   p.two_d = two_d_mode ? 1 : 0;
   p.max_iter = lm_max_iter < 0 ? 0 : lm_max_iter;
   p.min_matches = min_matches;
@@ -1105,6 +1130,14 @@ int lsa_debug_set(lsa_ctx* ctx, const char* name, int value)
 }
 
 int lsa_solve_device_fallbacks(const lsa_ctx* ctx) { return ctx ? ctx->lm_fallbacks : 0; }
+
+int lsa_set_sensor_terms(lsa_ctx* ctx, const lsa_sensor_terms_t* terms)
+{
+  if (!ctx) return LSA_E_ARG;
+  if (terms) ctx->sensor_terms = *terms;
+  else std::memset(&ctx->sensor_terms, 0, sizeof(ctx->sensor_terms));
+  return LSA_OK;
+}
 
 int lsa_solve_device_interlude(lsa_ctx* ctx, void (*fn)(void*), void* arg)
 {

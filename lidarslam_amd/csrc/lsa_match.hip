@@ -28,6 +28,7 @@
 #include "lsa_ctx.h"
 #include "lsa_device_math.h"
 #include "lsa_accum.h"
+#include "lsa_sensor_terms.h"
 #include "lsa_knn.h"
 #include "lsa_match_internal.h"
 
@@ -1644,6 +1645,9 @@ int lsa_accumulate(lsa_ctx* ctx, unsigned type_mask, const double w[6], int want
     // LSA_MAILBOX_CHECK: what came through the mailbox must be bit for bit what the device folds from its own partials
     if (got && std::memcmp(dst, hp, kAccumVals * sizeof(double)) != 0) return ctx->fail(LSA_E_STATE, "lsa_accumulate: mailbox and device fold disagree");
   }
+  // the wheel odometer / gravity terms (lsa_set_sensor_terms) on top of the reduction, at the same rotation
+  if (ctx->sensor_terms.wheel || ctx->sensor_terms.gravity)
+    sensor_terms_add(ctx->sensor_terms, w, c.rot.R, c.rot.dRx, c.rot.dRy, c.rot.dRz, want_jacobian != 0, hp);
   *cost = hp[0];
   if (n_valid) *n_valid = (int)hp[28];
   if (g) for (int a = 0; a < 6; ++a) g[a] = hp[1 + a];

@@ -103,7 +103,7 @@ struct Transform
 enum PCDFormat { ASCII = 0, BINARY = 1, BINARY_COMPRESSED = 2 };
 enum PointCloudStorageType { PCL_CLOUD = 0, OCTREE_COMPRESSED = 1, PCD_ASCII = 2, PCD_BINARY = 3, PCD_BINARY_COMPRESSED = 4 };
 
-// slam_lib/include/LidarSlam/SensorConstraints.h:13-23 (external sensors: accepted, not used -- see the Slam methods)
+// slam_lib/include/LidarSlam/SensorConstraints.h:13-23 (external sensors: constraints of the localization solve -- see the Slam methods)
 namespace SensorConstraints
 {
 struct WheelOdomMeasurement
@@ -300,22 +300,25 @@ public:
   // keypoint logging feeds the pose-graph optimisation only: the value is remembered, nothing is logged
   void SetLoggingStorage(PointCloudStorageType s) { this->LoggingStorage = s; }
   PointCloudStorageType GetLoggingStorage() const { return this->LoggingStorage; }
-  // wheel odometer / IMU constraints: weights and time offset are remembered, measurements are dropped
-  void SetWheelOdomWeight(double w) { this->WheelOdomWeight = w; }
-  double GetWheelOdomWeight() const { return this->WheelOdomWeight; }
-  void SetGravityWeight(double w) { this->GravityWeight = w; }
-  double GetGravityWeight() const { return this->GravityWeight; }
-  void SetSensorTimeOffset(double t) { this->SensorTimeOffset = t; }
-  double GetSensorTimeOffset() const { return this->SensorTimeOffset; }
-  void AddGravityMeasurement(const SensorConstraints::GravityMeasurement&)
+  // ---- wheel odometer / IMU gravity constraints (Slam.h:331-343, Slam.cxx:223-227, 1582-1598): the terms enter every ICP
+  // iteration of the localization solve and its covariance; the weights and the time offset are the library's
+  // parameters WheelOdomWeight, GravityWeight, SensorTimeOffset
+  LSA_SLAM_PARAM(WheelOdomWeight, double)
+  LSA_SLAM_PARAM(GravityWeight, double)
+  LSA_SLAM_PARAM(SensorTimeOffset, double)  // both sensors' offset: the LiDAR time minus it is the sensors' time
+  void AddGravityMeasurement(const SensorConstraints::GravityMeasurement& m)
   {
-    this->NotSupported("AddGravityMeasurement", "IMU gravity constraints are not part of this build: the measurement is ignored");
+    const double acc[3] = {m.Acceleration[0], m.Acceleration[1], m.Acceleration[2]};
+    lsa_slam_add_gravity_measurement(this->Handle, m.Time, acc);
+    if (this->GetGravityWeight() <= 1e-6) this->WarnOnce("AddGravityMeasurement", "stored; no constraint while the weight is 0");
   }
-  void AddWheelOdomMeasurement(const SensorConstraints::WheelOdomMeasurement&)
+  void AddWheelOdomMeasurement(const SensorConstraints::WheelOdomMeasurement& m)
   {
-    this->NotSupported("AddWheelOdomMeasurement", "wheel odometry constraints are not part of this build: the measurement is ignored");
+    lsa_slam_add_wheel_odom_measurement(this->Handle, m.Time, m.Distance);
+    if (this->GetWheelOdomWeight() <= 1e-6) this->WarnOnce("AddWheelOdomMeasurement", "stored; no constraint while the weight is 0");
   }
-  void ClearSensorMeasurements() {}
+  // measurements and the current terms cleared, time offset 0; the gravity reference and the odometer's baseline stay
+  void ClearSensorMeasurements() { lsa_slam_clear_sensor_measurements(this->Handle); }
 
   // ---- general parameters (Slam.h:201-232)
   void SetNbThreads(int) {}  // OpenMP thread count of the reference: meaningless on the device path
@@ -479,16 +482,16 @@ private:
     return pc;
   }
 
-  void NotSupported(const char* what, const char* why) const
+  void WarnOnce(const char* what, const char* why) const
   {
     if (this->Warned.insert(what).second) std::fprintf(stderr, "\033[1;33m[WARNING] LidarSlam::Slam::%s: %s\033[0m\n", what, why);
   }
+  void NotSupported(const char* what, const char* why) const { this->WarnOnce(what, why); }
 
   lsa_slam* Handle = nullptr;
   mutable std::set<std::string> Warned;
   std::vector<lsa_point_t> Staging;  // Fetch
   PointCloudStorageType LoggingStorage = PointCloudStorageType::PCL_CLOUD;
-  double WheelOdomWeight = 0., GravityWeight = 0., SensorTimeOffset = 0.;
   std::map<std::uint8_t, KeypointExtractorPtr> KeyPointsExtractors;
   std::uint64_t CurrentStamp = 0;
   std::string WorldFrameId = "world", BaseFrameId = "base", LastError;

@@ -764,12 +764,21 @@ int lsa_slam_sensor_terms(const lsa_slam* s, lsa_sensor_terms_t* out);
  * kernels on the context's look-ahead stream (runs of the batch sorted in LDS and merged by rank, one thread per voxel
  * folding the batch's points for it in arrival order through the reference's per-point rule, old and new voxels merged
  * by rank, stable compactions), ordered by events against the context's stream wherever the two share data; the sub-map is written straight into a kNN target of the context.
- * One grid is driven by one host thread at a time (not necessarily the context's).  Points come out in KEY ORDER (outer index, then leaf index) where the reference
- * hands them out in its hash containers' iteration order -- a defined order in place of an accidental one, adopted by
- * the oracle and the host grid as well ("OrderedMaps").  Sampling modes FIRST, LAST, MAX_INTENSITY, CENTER_POINT;
- * CENTROID (whose reference loop is quadratic in the batch size, RollingGrid.cxx:282-297) is refused: lsa_slam keeps
- * that mode on the host grid.  Parameters by the reference's setter names: "GridSize", "VoxelResolution", "LeafSize",
- * "MinFramesPerVoxel", "Sampling", "DecayingThreshold". */
+ * One grid is driven by one host thread at a time (not necessarily the context's).  The order in which Get and the
+ * sub-maps hand the points out is "Ordered" (the host grid's SetOrdered, lsa_slam's "OrderedMaps"):
+ *   1 (default) KEY ORDER (outer index, then leaf index) -- a defined order in place of the reference's accidental one,
+ *               adopted by the oracle and the host grid as well;
+ *   0           the reference's own: the iteration order of its unordered_map<int, unordered_map<int, Voxel>>.  Every
+ *               modification's effect on the key set goes to the host behind it (a few thousand keys per keyframe, an
+ *               async copy and an event); the host replays it on a keys-only copy of those containers and uploads the
+ *               keys in their iteration order before the next extraction.  The points never leave the device.
+ *   Set on an empty grid, the order is exact from the first insertion on (from containers never used: set it before
+ *   the first insertion).  Set while the grid holds points, the grid puts its points back in, in the order it hands
+ *   them out now, the way the geometry setters do (Get, Clear, Add: counts start again, the points come back with
+ *   time -1 and not fixed, so a map with a "DecayingThreshold" drops them at its next ClearOldPoints -- the host grid,
+ *   whose SetOrdered only changes the order, keeps them).
+ * Sampling modes FIRST, LAST, MAX_INTENSITY, CENTER_POINT, CENTROID.  Parameters by the reference's setter names:
+ * "GridSize", "VoxelResolution", "LeafSize", "MinFramesPerVoxel", "Sampling", "DecayingThreshold", and "Ordered". */
 typedef struct lsa_device_grid lsa_device_grid;
 int lsa_device_grid_create(lsa_ctx* ctx, lsa_device_grid** out);
 void lsa_device_grid_destroy(lsa_device_grid* g); /* before lsa_ctx_destroy of its context */

@@ -1099,6 +1099,8 @@ class DeviceGrid:
         self.L.lsa_device_grid_create.argtypes = [vp, C.POINTER(vp)]
         self.L.lsa_device_grid_destroy.argtypes = [vp]
         self.L.lsa_device_grid_set.argtypes = [vp, C.c_char_p, f64]
+        self.L.lsa_device_grid_get_param.argtypes = [vp, C.c_char_p]
+        self.L.lsa_device_grid_get_param.restype = f64
         self.L.lsa_device_grid_reset.argtypes = [vp, vp]
         self.L.lsa_device_grid_clear.argtypes = [vp]
         self.L.lsa_device_grid_size.argtypes = [vp]
@@ -1136,6 +1138,9 @@ class DeviceGrid:
 
     def set(self, name, value):
         self._check(self.L.lsa_device_grid_set(self.h, name.encode(), float(value)), f"lsa_device_grid_set({name})")
+
+    def get_param(self, name):
+        return float(self.L.lsa_device_grid_get_param(self.h, name.encode()))
 
     def reset(self, position=None):
         pos = None if position is None else np.ascontiguousarray(position, np.float32)

@@ -1924,7 +1924,17 @@ int SlamCore::SetParamValue(const std::string& name, double v)
   if (name == "VoxelGridMinFramesPerVoxel") { for (int k = 0; k < 3; ++k) { LocalMaps[k]->SetMinFramesPerVoxel(static_cast<unsigned>(v)); dev(k, "MinFramesPerVoxel", v); } return LSA_OK; }
   if (name == "VoxelGridDecayingThreshold") { for (int k = 0; k < 3; ++k) { LocalMaps[k]->SetDecayingThreshold(v); dev(k, "DecayingThreshold", v); } return LSA_OK; }
   if (name == "VoxelGridSamplingMode") { for (int k = 0; k < 3; ++k) { LocalMaps[k]->SetSampling(static_cast<SamplingMode>(static_cast<int>(v))); dev(k, "Sampling", v); } return LSA_OK; }
-  if (name == "OrderedMaps") { OrderedMaps = v != 0; for (auto& m : LocalMaps) m->SetOrdered(OrderedMaps); return LSA_OK; }
+  if (name == "OrderedMaps")
+  {
+    // both homes of the maps: the host grids, and the device grids (which put the points they hold back in, in the order
+    // they hand them out now, the way the geometry setters do: time -1, not fixed, so decaying device maps lose them at
+    // the next ClearOldPoints -- set it before the first frame)
+    OrderedMaps = v != 0;
+    for (auto& m : LocalMaps) m->SetOrdered(OrderedMaps);
+    for (int k = 0; k < 3; ++k)
+      if (DevMaps[k] && lsa_device_grid_set(DevMaps[k], "Ordered", OrderedMaps ? 1. : 0.) != LSA_OK) return Fail(LSA_E_HIP, "lsa_device_grid_set(Ordered)");
+    return LSA_OK;
+  }
   LastError = "unknown parameter " + name;
   return LSA_E_ARG;
 }

@@ -221,7 +221,8 @@ public:
   // The same three maps resident on the device (lsa_device_grid: SURVEY.md 8f-1).  "MapsOnDevice" (default): keyframes
   // are inserted and sub-maps extracted without leaving the device -- no staging of the keypoints in host memory, no map
   // threads, no sub-map upload.  Off: the host containers above.  Both
-  // hand their points out in key order ("OrderedMaps"), so the two give the same sub-maps and the same poses.
+  // hand their points out in the same order ("OrderedMaps": 1 key order, 0 the reference's container order), so the two
+  // give the same sub-maps and the same poses.
   lsa_device_grid* DevMaps[3] = {nullptr, nullptr, nullptr};
   bool MapsOnDevice = true;
   // device maps: sub-maps extracted for the predicted boxes beside the ego-motion ICP ("SubMapsAhead"): the extraction and

@@ -16,9 +16,16 @@
 //   decay    ClearOldPoints: stable compaction
 //   sub-map  voxels whose outer index lies in the box, stable compaction straight into the target's point buffer
 // Iteration order.  The reference's Get / BuildSubMapKdTree hand the points out in libstdc++'s hash iteration order,
-// an accident of the container; the device map hands them out in KEY ORDER (outer index, then leaf index as
-// unsigned), and so do the oracle and the host RollingGrid when "OrderedMaps" is set (the default): a defined order
-// in place of an accidental one, documented with the other deviations in DESIGN.md 4.3.
+// an accident of the container.  Two orders, chosen by "Ordered" (the host RollingGrid's SetOrdered):
+//   1 (default)  KEY ORDER (outer index, then leaf index as unsigned) -- the order of the array itself; the oracle and
+//                the host RollingGrid use it too: a defined order in place of an accidental one
+//   0            the reference's container order.  Every modification leaves a record of what it did to the key set
+//                (the keys an Add created, in first-arrival order; the offset of a roll; the keys ClearOldPoints
+//                erased), copied to the host behind it; the host replays the records on a keys-only copy of the
+//                reference's containers (host/lsa_map_order.h) and uploads the keys in their iteration order before the
+//                next extraction; a kernel turns them into places in the sorted array (binary search), and the
+//                extractions compact over that permutation instead of over the array.  The points never leave the
+//                device.
 // Nothing here waits for the device except the calls that return a size or points to the host.
 #include <algorithm>
 #include <cfloat>
@@ -28,7 +35,9 @@
 #include <cstring>
 #include <limits>
 #include <string.h>
+#include <vector>
 #include "lsa_ctx.h"
+#include "host/lsa_map_order.h"
 #include "lsa_device_math.h"
 
 using namespace lsa;
@@ -49,7 +58,8 @@ struct GridParams
   unsigned min_frames;
 };
 // state the kernels read and write (device memory, kStInts ints)
-enum { kStN = 0, kStNbPoints = 1, kStUpdated = 2, kStPosX = 3, kStGroups = 6, kStNew = 7, kStOff = 8, kStSub = 11, kStTmp = 12 /* 6 ints */, kStSubFirst = 18, kStCompact = 19, kStPred = 20 /* 6 ints: lo[3], hi[3]: outer voxels of the box a sub-map was extracted ahead for */, kStInts = 32 };
+enum { kStN = 0, kStNbPoints = 1, kStUpdated = 2, kStPosX = 3, kStGroups = 6, kStNew = 7, kStOff = 8, kStSub = 11, kStTmp = 12 /* 6 ints */, kStSubFirst = 18, kStCompact = 19, kStPred = 20 /* 6 ints: lo[3], hi[3]: outer voxels of the box a sub-map was extracted ahead for */,
+       kStRec = 26 /* keys ClearOldPoints erased ("Ordered" = 0) */, kStInts = 32 };
 
 __device__ __forceinline__ float ordered_to_float(unsigned u) { return __uint_as_float((u & 0x80000000u) ? (u & 0x7fffffffu) : ~u); }
 
@@ -756,7 +766,8 @@ __device__ __forceinline__ void d_add_fold(int bx, const float4* __restrict__ ba
 // of both arrays for itself (dynamic LDS: ochunks + fchunks + 2 ints).
 __device__ __forceinline__ void d_add_merge(int bx, GridParams p, int* __restrict__ st, int use_box, MapView old, const int* __restrict__ old_local,
                                                    const int* __restrict__ old_chunks, int ochunks, int oblocks, const u64* __restrict__ skeys, int n, MapView fresh,
-                                                   const int* __restrict__ fresh_flag, const int* __restrict__ fresh_chunks, int fchunks, MapView dst)
+                                                   const int* __restrict__ fresh_flag, const int* __restrict__ fresh_chunks, int fchunks, MapView dst,
+                                                   u64* __restrict__ rec = nullptr, const unsigned* __restrict__ sorder = nullptr)
 {
   extern __shared__ int scan[];  // [ochunks + 1] exclusive scan of the survivors per chunk, then [fchunks + 1] of the new voxels per block
   __shared__ int carry;
@@ -826,6 +837,14 @@ __device__ __forceinline__ void d_add_merge(int bx, GridParams p, int* __restric
   dst.pts[2 * (size_t)at] = fresh.pts[2 * (size_t)j];
   dst.pts[2 * (size_t)at + 1] = fresh.pts[2 * (size_t)j + 1];
   dst.count[at] = fresh.count[j];
+  if (rec)
+  {
+    // "Ordered" = 0: the new voxel's key and its first point's place in the batch (the head of its run: the run is sorted by
+    // arrival), at the voxel's rank among the new ones
+    const int r = fresh_before(j);
+    rec[2 * (size_t)r] = key;
+    rec[2 * (size_t)r + 1] = sorder[j];
+  }
 }
 // launch 7: the move and the counts become the grid's state (Roll recounts the points when the grid moved, :155)
 __device__ __forceinline__ void d_add_commit(int bx, GridParams p, int* __restrict__ st, int use_box)
@@ -858,6 +877,7 @@ struct AddOne
   MapView map, fresh, dst;
   int *old_local, *old_chunks, *fresh_flag, *fresh_chunks;
   int* vrank;
+  u64* rec;  // "Ordered" = 0: {key, first arrival} of every voxel the Add creates
   int ochunks;
 };
 struct AddBatch
@@ -916,7 +936,7 @@ __global__ __launch_bounds__(256) void k_add_merge(AddBatch b)
 {
   const AddOne& A = b.a[blockIdx.y];
   d_add_merge(blockIdx.x, A.p, A.st, A.use_box, A.map, A.old_local, A.old_chunks, A.ochunks, b.oblocks, A.skeys, A.n, A.fresh, A.fresh_flag, A.fresh_chunks, (A.n + 255) / 256,
-              A.dst);
+              A.dst, A.rec, A.sorder);
 }
 __global__ void k_add_commit(AddBatch b) { const AddOne& A = b.a[blockIdx.y]; d_add_commit(blockIdx.x, A.p, A.st, A.use_box); }
 
@@ -943,6 +963,46 @@ struct CopyEmit
     dst.pts[2 * (size_t)at + 1] = src.pts[2 * (size_t)i + 1];
     dst.count[at] = src.count[i];
   }
+};
+// "Ordered" = 0: the keys ClearOldPoints erases, for the host's copy of the containers
+struct ErasedPred
+{
+  DecayPred keep;
+  __device__ bool operator()(int i) const { return !keep(i); }
+};
+struct KeyEmit
+{
+  const u64* keys;
+  u64* out;
+  __device__ void operator()(int i, int at) const { out[at] = keys[i]; }
+};
+
+// ---- the reference's container order ("Ordered" = 0) -------------------------------------------------------------------
+// The host uploads the keys in the iteration order of its copy of the containers; every one becomes its place in the
+// sorted array.  The extractions then compact over r = 0 .. n-1 and read voxel perm[r]: the same predicates, the same
+// emitters, another order.
+__global__ __launch_bounds__(256) void k_order_perm(const u64* __restrict__ okeys, int n, const u64* __restrict__ keys, const int* __restrict__ st,
+                                                    int* __restrict__ perm)
+{
+  const int r = blockIdx.x * 256 + threadIdx.x;
+  if (r >= n) return;
+  const int N = st[kStN];
+  const int at = lower_bound_u64(keys, N, okeys[r]);
+  perm[r] = at < N ? at : (N > 0 ? N - 1 : 0);  // (never taken: the host's key set is the map's)
+}
+template <typename P>
+struct PermPred
+{
+  P p;
+  const int* perm;
+  __device__ bool operator()(int r) const { return p(perm[r]); }
+};
+template <typename E>
+struct PermEmit
+{
+  E e;
+  const int* perm;
+  __device__ void operator()(int r, int at) const { e(perm[r], at); }
 };
 
 // ---- Get / BuildSubMapKdTree (RollingGrid.cxx:95-114, 353-442) ---------------------------------------------------------
@@ -1096,6 +1156,23 @@ struct lsa_device_grid
   int* old_local = nullptr;    // [cap] rank of an old voxel among the survivors of its chunk (Add)
   MapView fresh = {};
   int chunk_cap = 0;
+  // "Ordered" = 0, the reference's container order (see the head of this file)
+  bool Ordered = true;
+  lsa::host::KeyShadow shadow;  // keys-only copy of the reference's containers
+  int rec_kind = 0;             // the record of the last modification on its way to the host: 0 none, kRecAdd, kRecRoll, kRecDecay
+  int rec_grid = 0;             // the grid size it was made under
+  int rec_voxels = 0;           // voxels of the map after the last record replayed: the shadow must hold as many
+  hipEvent_t ev_rec = nullptr;  // behind its copy
+  int* rec_st = nullptr;        // pinned: the state behind the modification (offset of the move, voxels created, keys erased)
+  u64* rec_host = nullptr;      // pinned: the keys
+  u64* rec_dev = nullptr;
+  size_t rec_cap = 0;           // u64 of both
+  bool order_stale = false;     // the shadow changed since the last upload
+  int order_n = 0, order_cap = 0;
+  u64* order_host = nullptr;    // pinned: the keys in the shadow's iteration order
+  u64* order_dev = nullptr;
+  int* perm = nullptr;          // [order_n]: place in the sorted array of the voxel at each rank of that order
+  hipEvent_t ev_order = nullptr;
 };
 
 namespace
@@ -1262,6 +1339,145 @@ int refresh_state(lsa_device_grid* g)
   return LSA_OK;
 }
 
+// ---- "Ordered" = 0: records, the host's copy of the containers, the order on the device ---------------------------------
+enum { kRecAdd = 1, kRecRoll = 2, kRecDecay = 3 };
+
+// the last modification's record replayed on the shadow (waits for that modification)
+int apply_record(lsa_device_grid* g)
+{
+  if (!g->rec_kind) return LSA_OK;
+  G_HIP(hipEventSynchronize(g->ev_rec));
+  const int kind = g->rec_kind;
+  g->rec_kind = 0;
+  g->order_stale = true;
+  const int* s = g->rec_st;
+  g->rec_voxels = s[kStN];
+  if (kind == kRecAdd || kind == kRecRoll)
+  {
+    // Add rolls first (RollingGrid.cxx:166-172): the move it made, then the keys it created
+    const int off[3] = {s[kStOff], s[kStOff + 1], s[kStOff + 2]};
+    g->shadow.Roll(off, g->rec_grid);
+  }
+  if (kind == kRecAdd)
+  {
+    const int created = s[kStNew];
+    if (created < 0 || 2 * (size_t)created > g->rec_cap) return g->ctx->fail(LSA_E_STATE, "lsa_device_grid: bad record of an insertion");
+    // {key, first arrival}: operator[] inserts a key at its first point (:206-212), so the order of insertion is that of arrival
+    std::vector<std::pair<unsigned, u64>> fresh((size_t)created);
+    for (int i = 0; i < created; ++i) fresh[i] = {(unsigned)g->rec_host[2 * (size_t)i + 1], g->rec_host[2 * (size_t)i]};
+    std::sort(fresh.begin(), fresh.end());
+    for (const auto& f : fresh) g->shadow.Insert(f.second);
+  }
+  else if (kind == kRecDecay)
+  {
+    const int erased = s[kStRec];
+    if (erased < 0 || (size_t)erased > g->rec_cap) return g->ctx->fail(LSA_E_STATE, "lsa_device_grid: bad record of a decay");
+    // the keys themselves, now that their number is known (nothing has written the record's buffer since: every
+    // modification replays the record before it is enqueued)
+    if (erased > 0)
+    {
+      G_HIP(hipMemcpyAsync(g->rec_host, g->rec_dev, (size_t)erased * sizeof(u64), hipMemcpyDeviceToHost, g->stream));
+      G_HIP(hipEventRecord(g->ev_rec, g->stream));
+      G_HIP(hipEventSynchronize(g->ev_rec));
+    }
+    std::vector<u64> keys(g->rec_host, g->rec_host + erased);
+    std::sort(keys.begin(), keys.end());
+    g->shadow.Erase(keys);
+  }
+  return LSA_OK;
+}
+
+// RollingGrid::Clear (:51-56) on the shadow: the keys go, the bucket arrays stay.  A record still on its way is replayed
+// first: the tables' bucket counts after the clear -- and with them the order of every later insertion -- are what the
+// modifications before it made of them.
+int forget_records(lsa_device_grid* g)
+{
+  const int rc = apply_record(g);
+  if (rc) return rc;
+  g->shadow.Clear();
+  g->rec_voxels = 0;
+  g->order_stale = true;
+  return LSA_OK;
+}
+
+// room for a record of `entries` keys (the last record has been replayed)
+int ensure_rec(lsa_device_grid* g, size_t entries)
+{
+  if (entries <= g->rec_cap) return LSA_OK;
+  G_HIP(hipEventSynchronize(g->ev_rec));
+  const size_t cap = std::max(2 * entries, (size_t)1 << 16);
+  if (g->rec_host) G_HIP(hipHostFree(g->rec_host));
+  g->rec_host = nullptr;
+  retire_dev(g->ctx, g->rec_dev);
+  g->rec_dev = nullptr;
+  g->rec_cap = 0;
+  G_HIP(hipHostMalloc((void**)&g->rec_host, cap * sizeof(u64), hipHostMallocDefault));
+  G_HIP(hipMalloc((void**)&g->rec_dev, cap * sizeof(u64)));
+  g->rec_cap = cap;
+  return LSA_OK;
+}
+
+// the record of the modification just enqueued goes to the host behind it: the state, then `entries` keys
+int send_record(lsa_device_grid* g, int kind, size_t entries)
+{
+  G_HIP(hipMemcpyAsync(g->rec_st, g->st, kStInts * sizeof(int), hipMemcpyDeviceToHost, g->stream));
+  if (entries > 0) G_HIP(hipMemcpyAsync(g->rec_host, g->rec_dev, entries * sizeof(u64), hipMemcpyDeviceToHost, g->stream));
+  G_HIP(hipEventRecord(g->ev_rec, g->stream));
+  g->rec_kind = kind;
+  g->rec_grid = g->GridSize;
+  return LSA_OK;
+}
+
+// The order of the map as it is now, on the device, before an extraction: the records replayed, the keys in the shadow's
+// iteration order uploaded and turned into places (on the grid's stream; ev_out follows, for extractions on the context's).
+int ensure_order(lsa_device_grid* g)
+{
+  int rc = apply_record(g);
+  if (rc) return rc;
+  if (!g->order_stale) return LSA_OK;
+  const int n = (int)g->shadow.Size();
+  if (n != g->rec_voxels) return g->ctx->fail(LSA_E_STATE, "lsa_device_grid: the host's copy of the containers holds " + std::to_string(n) + " keys, the map " + std::to_string(g->rec_voxels) + " voxels");
+  G_HIP(hipEventSynchronize(g->ev_order));  // the last upload out of order_host is over
+  if (n > g->order_cap)
+  {
+    const int cap = std::max(2 * n, 1 << 16);
+    if (g->order_host) G_HIP(hipHostFree(g->order_host));
+    g->order_host = nullptr;
+    retire_dev(g->ctx, g->order_dev);
+    retire_dev(g->ctx, g->perm);
+    g->order_dev = nullptr;
+    g->perm = nullptr;
+    g->order_cap = 0;
+    G_HIP(hipHostMalloc((void**)&g->order_host, (size_t)cap * sizeof(u64), hipHostMallocDefault));
+    G_HIP(hipMalloc((void**)&g->order_dev, (size_t)cap * sizeof(u64)));
+    G_HIP(hipMalloc((void**)&g->perm, (size_t)cap * sizeof(int)));
+    g->order_cap = cap;
+  }
+  g->shadow.Keys(g->order_host);
+  G_HIP(hipStreamWaitEvent(g->stream, g->ev_sub, 0));  // an extraction on the context's stream may still read the places
+  if (n > 0)
+  {
+    rc = ensure_map(g, std::max(g->n_upper, n));
+    if (rc) return rc;
+    G_HIP(hipMemcpyAsync(g->order_dev, g->order_host, (size_t)n * sizeof(u64), hipMemcpyHostToDevice, g->stream));
+    hipLaunchKernelGGL(k_order_perm, dim3((n + 255) / 256), dim3(256), 0, g->stream, g->order_dev, n, g->buf[g->cur].keys, g->st, g->perm);
+  }
+  G_HIP(hipEventRecord(g->ev_order, g->stream));
+  G_HIP(hipEventRecord(g->ev_out, g->stream));
+  g->order_stale = false;
+  g->order_n = n;
+  return LSA_OK;
+}
+
+// stable compaction of the map's voxels by pred, emit(voxel, position), in the grid's order
+template <typename Pred, typename Emit>
+void compact_map(lsa_device_grid* g, Pred pred, Emit emit, int* total, bool append = false, hipStream_t on = nullptr, u64* host_out = nullptr, unsigned host_tag = 0,
+                 int* clear_flag = nullptr)
+{
+  if (g->Ordered) compact(g, pred, emit, g->st + kStN, g->n_upper, total, append, true, on, host_out, host_tag, clear_flag);
+  else compact(g, PermPred<Pred>{pred, g->perm}, PermEmit<Emit>{emit, g->perm}, nullptr, g->order_n, total, append, true, on, host_out, host_tag, clear_flag);
+}
+
 // Roll (always a pass into the other buffer: the host does not know whether the grid moves)
 int roll(lsa_device_grid* g, bool use_box)
 {
@@ -1294,12 +1510,19 @@ int add_batches(lsa_device_grid* const* gs, const int* ns, int count, bool fixed
     if (rc) return rc;
     rc = ensure_map(gi, gi->n_upper + ns[i]);
     if (rc) return rc;
+    if (!gi->Ordered)
+    {
+      rc = apply_record(gi);
+      if (!rc) rc = ensure_rec(gi, 2 * (size_t)ns[i]);
+      if (rc) return rc;
+    }
     AddOne& A = b.a[i];
     A.batch = gi->batch; A.n = ns[i]; A.use_box = do_roll ? 1 : 0; A.fixed = fixed ? 1 : 0; A.time = time;
     A.p = params_of(gi); A.st = gi->st;
     A.bkeys = gi->bkeys; A.skeys = gi->skeys; A.border = gi->border; A.sorder = gi->sorder;
     A.map = gi->buf[gi->cur]; A.dst = gi->buf[1 - gi->cur]; A.fresh = gi->fresh;
     A.old_local = gi->old_local; A.old_chunks = gi->chunks; A.fresh_flag = gi->fresh_flag; A.fresh_chunks = gi->heads; A.vrank = gi->vrank;
+    A.rec = gi->Ordered ? nullptr : gi->rec_dev;
     A.ochunks = std::max((gi->n_upper + 1023) / 1024, 1);
     kmax = std::max(kmax, (ns[i] + 255) / 256);
     omax = std::max(omax, A.ochunks);
@@ -1333,6 +1556,11 @@ int add_batches(lsa_device_grid* const* gs, const int* ns, int count, bool fixed
   {
     gs[i]->cur = 1 - gs[i]->cur;
     gs[i]->n_upper += ns[i];
+    if (!gs[i]->Ordered)
+    {
+      const int rc = send_record(gs[i], kRecAdd, 2 * (size_t)ns[i]);
+      if (rc) return rc;
+    }
     const int rc = refresh_state(gs[i]);  // whether a point changed (the kd-tree is only dropped then, :315-317) is read by lsa_device_grid_submap_valid
     if (rc) return rc;
   }
@@ -1357,6 +1585,7 @@ int lsa_device_grid_create(lsa_ctx* ctx, lsa_device_grid** out)
   if (ok) *g->host_sub = 0;
   ok = ok && hipHostMalloc((void**)&g->host_ahead, 2 * sizeof(u64), hipHostMallocCoherent | hipHostMallocMapped) == hipSuccess;
   if (ok) g->host_ahead[0] = g->host_ahead[1] = 0;
+  ok = ok && hipHostMalloc((void**)&g->rec_st, kStInts * sizeof(int), hipHostMallocDefault) == hipSuccess;
   {
     // The maps' kernels go on the context's LOOK-AHEAD stream (next frame's extraction, next ego-motion targets): a
     // process has four hardware queues, and the registration's stream, the look-ahead stream and the copy stream are
@@ -1379,7 +1608,7 @@ int lsa_device_grid_create(lsa_ctx* ctx, lsa_device_grid** out)
       if (ok) { ctx->map_stream_users++; g->shared_stream = true; }
     }
   }
-  for (hipEvent_t* e : {&g->ev_state, &g->ev_in, &g->ev_out, &g->ev_sub, &g->ev_ahead}) ok = ok && hipEventCreateWithFlags(e, hipEventDisableTiming) == hipSuccess;
+  for (hipEvent_t* e : {&g->ev_state, &g->ev_in, &g->ev_out, &g->ev_sub, &g->ev_ahead, &g->ev_rec, &g->ev_order}) ok = ok && hipEventCreateWithFlags(e, hipEventDisableTiming) == hipSuccess;
   if (!ok) { lsa_device_grid_destroy(g); return LSA_E_HIP; }
   *out = g;
   return lsa_device_grid_reset(g, nullptr);
@@ -1394,10 +1623,13 @@ void lsa_device_grid_destroy(lsa_device_grid* g)
   free_view(g->buf[0]); free_view(g->buf[1]); free_view(g->fresh);
   auto fr = [](void* p) { if (p) (void)hipFree(p); };
   fr(g->st); fr(g->batch); fr(g->bkeys); fr(g->skeys); fr(g->border); fr(g->sorder); fr(g->heads); fr(g->fresh_flag); fr(g->vrank); fr(g->chunks); fr(g->old_local);
+  fr(g->rec_dev); fr(g->order_dev); fr(g->perm);
+  for (void* h : {(void*)g->rec_st, (void*)g->rec_host, (void*)g->order_host})
+    if (h) (void)hipHostFree(h);
   if (g->host_st) (void)hipHostFree(g->host_st);
   if (g->host_sub) (void)hipHostFree(g->host_sub);
   if (g->host_ahead) (void)hipHostFree(g->host_ahead);
-  for (hipEvent_t e : {g->ev_state, g->ev_in, g->ev_out, g->ev_sub, g->ev_ahead})
+  for (hipEvent_t e : {g->ev_state, g->ev_in, g->ev_out, g->ev_sub, g->ev_ahead, g->ev_rec, g->ev_order})
     if (e) (void)hipEventDestroy(e);
   if (g->stream && g->own_stream) (void)hipStreamDestroy(g->stream);
   if (g->shared_stream && --g->ctx->map_stream_users == 0 && g->ctx->map_stream)
@@ -1428,6 +1660,11 @@ int lsa_device_grid_reset(lsa_device_grid* g, const float position[3])
   std::memcpy(g->host_st, h, sizeof(h));
   g->n_upper = 0;
   g->submap_valid = false;
+  if (!g->Ordered)
+  {
+    const int rc = forget_records(g);  // Reset goes through Clear (RollingGrid.cxx:40-48)
+    if (rc) return rc;
+  }
   return LSA_OK;
 }
 
@@ -1443,10 +1680,15 @@ int lsa_device_grid_clear(lsa_device_grid* g)
   hipLaunchKernelGGL(k_set_int, dim3(1), dim3(64), 0, g->stream, g->st + kStNbPoints, 0);
   g->n_upper = 0;
   g->submap_valid = false;
+  if (!g->Ordered)
+  {
+    const int rc = forget_records(g);
+    if (rc) return rc;
+  }
   return refresh_state(g);
 }
 
-static int readd_everything(lsa_device_grid* g);
+static int readd_everything(lsa_device_grid* g, int ordered = -1);
 
 int lsa_device_grid_set(lsa_device_grid* g, const char* name, double value)
 {
@@ -1456,6 +1698,17 @@ int lsa_device_grid_set(lsa_device_grid* g, const char* name, double value)
   if (n == "MinFramesPerVoxel") { g->MinFramesPerVoxel = (unsigned)value; return LSA_OK; }
   if (n == "Sampling") { g->Sampling = (int)value; return LSA_OK; }
   if (n == "DecayingThreshold") { g->DecayingThreshold = value; return LSA_OK; }
+  if (n == "Ordered")
+  {
+    // RollingGrid::SetOrdered.  On an empty grid, from the first insertion on.  On a grid that holds points, the way the
+    // geometry setters do it: the points, in the order they are handed out now, go back into the emptied grid (time -1,
+    // not fixed, counts start again: a decaying map loses them at the next ClearOldPoints); to the reference's order,
+    // into containers never used before.
+    const int want = value != 0 ? 1 : 0;
+    if ((want != 0) == g->Ordered) return LSA_OK;
+    G_HIP(hipSetDevice(g->ctx->device));
+    return readd_everything(g, want);
+  }
   if (n == "GridSize")
   {
     // RollingGrid::SetGridSize (:59-70): the points are put back into the resized grid
@@ -1494,6 +1747,7 @@ double lsa_device_grid_get_param(const lsa_device_grid* g, const char* name)
   if (n == "DecayingThreshold") return g->DecayingThreshold;
   if (n == "GridSize") return g->GridSize;
   if (n == "VoxelResolution") return g->VoxelResolution;
+  if (n == "Ordered") return g->Ordered ? 1. : 0.;
   return 0.;
 }
 
@@ -1635,8 +1889,18 @@ int lsa_device_grid_roll(lsa_device_grid* g, const float mn[3], const float mx[3
   }
   G_HIP(hipMemcpyAsync(g->st + kStTmp, box, sizeof(box), hipMemcpyHostToDevice, g->stream));
   G_HIP(hipStreamSynchronize(g->stream));
+  if (!g->Ordered)
+  {
+    rc = apply_record(g);
+    if (rc) return rc;
+  }
   rc = roll(g, true);
   if (rc) return rc;
+  if (!g->Ordered)
+  {
+    rc = send_record(g, kRecRoll, 0);
+    if (rc) return rc;
+  }
   return refresh_state(g);
 }
 
@@ -1649,8 +1913,22 @@ int lsa_device_grid_clear_old_points(lsa_device_grid* g, double now)
   rc = ensure_map(g, std::max(g->n_upper, 1));
   if (rc) return rc;
   const MapView src = g->buf[g->cur], dst = g->buf[1 - g->cur];
-  compact(g, DecayPred{src.pts, now, g->DecayingThreshold}, CopyEmit{src, dst}, g->st + kStN, std::max(g->n_upper, 1), g->st + kStN);
+  const DecayPred keep{src.pts, now, g->DecayingThreshold};
+  if (!g->Ordered)
+  {
+    // the keys that go, for the shadow
+    rc = apply_record(g);
+    if (!rc) rc = ensure_rec(g, (size_t)std::max(g->n_upper, 1));
+    if (rc) return rc;
+    compact(g, ErasedPred{keep}, KeyEmit{src.keys, g->rec_dev}, g->st + kStN, std::max(g->n_upper, 1), g->st + kStRec);
+  }
+  compact(g, keep, CopyEmit{src, dst}, g->st + kStN, std::max(g->n_upper, 1), g->st + kStN);
   g->cur = 1 - g->cur;
+  if (!g->Ordered)
+  {
+    rc = send_record(g, kRecDecay, 0);  // (the erased keys follow when their number is known: apply_record)
+    if (rc) return rc;
+  }
   return refresh_state(g);
 }
 
@@ -1665,11 +1943,16 @@ int lsa_device_grid_get(lsa_device_grid* g, int clean, lsa_point_t* out, int cap
   if (rc) return rc;
   rc = ensure_scratch(ctx, (size_t)g->n_upper * sizeof(lsa_point_t));
   if (rc) return rc;
+  if (!g->Ordered)
+  {
+    rc = ensure_order(g);
+    if (rc) return rc;
+  }
   const MapView m = g->buf[g->cur];
   rc = order_after_context(g);  // the scratch buffer is the context's; a sub-map extraction on its stream comes first too
   if (rc) return rc;
   SubMapPred pred{m.keys, m.pts, m.count, g->st, BoxArg{}, nullptr, nullptr, g->GridSize, (float)g->VoxelResolution, g->VoxelResolution, 0, g->MinFramesPerVoxel, -1, clean ? 3 : 0};
-  compact(g, pred, PointEmit{m.pts, reinterpret_cast<float4*>(ctx->scratch_out)}, g->st + kStN, g->n_upper, g->st + kStSub);
+  compact_map(g, pred, PointEmit{m.pts, reinterpret_cast<float4*>(ctx->scratch_out)}, g->st + kStSub);
   int kept = 0;
   G_HIP(hipMemcpyAsync(&kept, g->st + kStSub, sizeof(int), hipMemcpyDeviceToHost, g->stream));
   G_HIP(hipStreamSynchronize(g->stream));
@@ -1699,6 +1982,11 @@ static int build_submap_begin(lsa_device_grid* g, const float mn[3], const float
   if (rc) return rc;
   rc = ensure_target(ctx, ti, g->n_upper);
   if (rc) return rc;
+  if (!g->Ordered)
+  {
+    rc = ensure_order(g);
+    if (rc) return rc;
+  }
   // The extraction runs on the CONTEXT's stream, behind the grid's last modification (ev_out): the box words, the target
   // and the next match are the context's anyway, so nothing else has to be ordered, and the size comes back through
   // coherent host memory -- no copy, no event, no host call between the kernels.
@@ -1723,8 +2011,8 @@ static int build_submap_begin(lsa_device_grid* g, const float mn[3], const float
     ProfScope ps(ctx, "map_submap", (double)g->n_upper * 44, st);
     // the sub-map is of the map as it is now: the changes the Adds before it flagged are in it (the flag goes with the
     // last kernel)
-    compact(g, pred, PointEmit{m.pts, reinterpret_cast<float4*>(t.pts)}, g->st + kStN, g->n_upper, g->st + kStSub, false, true, st, filtered ? nullptr : g->host_sub,
-            tag, filtered ? nullptr : g->st + kStUpdated);
+    compact_map(g, pred, PointEmit{m.pts, reinterpret_cast<float4*>(t.pts)}, g->st + kStSub, false, st, filtered ? nullptr : g->host_sub, tag,
+                filtered ? nullptr : g->st + kStUpdated);
     if (filtered)
     {
       // "Moving objects constraint was too strong, removing constraint": the rejected voxels follow when too few stayed
@@ -1732,7 +2020,7 @@ static int build_submap_begin(lsa_device_grid* g, const float mn[3], const float
       // the second pass appends behind what the first one kept (its predicate reads the first pass's count from a slot
       // of its own: the total moves while it runs)
       hipLaunchKernelGGL(k_copy_int, dim3(1), dim3(64), 0, st, g->st + kStSubFirst, g->st + kStSub);
-      compact(g, pred, PointEmit{m.pts, reinterpret_cast<float4*>(t.pts)}, g->st + kStN, g->n_upper, g->st + kStSub, true, true, st, g->host_sub, tag, g->st + kStUpdated);
+      compact_map(g, pred, PointEmit{m.pts, reinterpret_cast<float4*>(t.pts)}, g->st + kStSub, true, st, g->host_sub, tag, g->st + kStUpdated);
     }
   }
   G_HIP(hipEventRecord(g->ev_sub, st));  // the grid's next modification comes behind the extraction
@@ -1816,6 +2104,12 @@ int lsa_device_grid_submap_ahead_begin(lsa_device_grid* g, int box_type, int min
   if (rc) return rc;
   rc = after_submap(g);
   if (rc) return rc;
+  if (!g->Ordered)
+  {
+    // behind the order of the last insertion, never an older one
+    rc = ensure_order(g);
+    if (rc) return rc;
+  }
   // The box words: enqueued on this very stream by lsa_keypoint_boxes_predicted, or on the context's by
   // lsa_keypoint_bboxes_begin -- then this stream comes behind the context's.  (The spare target's last readers, searches of an
   // earlier frame, have long finished: every frame ends with the host reading its last solve's result.)
@@ -1839,12 +2133,12 @@ int lsa_device_grid_submap_ahead_begin(lsa_device_grid* g, int box_type, int min
   const unsigned tag = ++g->ahead_tag;
   {
     ProfScope ps(ctx, "map_submap_ahead", (double)g->n_upper * 44, st);
-    compact(g, pred, PointEmit{m.pts, reinterpret_cast<float4*>(t.pts)}, g->st + kStN, g->n_upper, g->st + kStSub, false, true, st, filtered ? nullptr : g->host_ahead, tag);
+    compact_map(g, pred, PointEmit{m.pts, reinterpret_cast<float4*>(t.pts)}, g->st + kStSub, false, st, filtered ? nullptr : g->host_ahead, tag);
     if (filtered)
     {
       pred.mode = 2;
       hipLaunchKernelGGL(k_copy_int, dim3(1), dim3(64), 0, st, g->st + kStSubFirst, g->st + kStSub);
-      compact(g, pred, PointEmit{m.pts, reinterpret_cast<float4*>(t.pts)}, g->st + kStN, g->n_upper, g->st + kStSub, true, true, st, g->host_ahead, tag);
+      compact_map(g, pred, PointEmit{m.pts, reinterpret_cast<float4*>(t.pts)}, g->st + kStSub, true, st, g->host_ahead, tag);
     }
   }
   G_HIP(hipEventRecord(g->ev_ahead, st));  // whoever uses the grid's scratch next on another stream comes behind this
@@ -2021,12 +2315,23 @@ int lsa_device_grid_submap_valid(lsa_device_grid* g)
   return g->submap_valid && g->submap_count > 0 ? 1 : 0;  // an empty sub-map counts as invalid (RollingGrid.h:154)
 }
 
-static int readd_everything(lsa_device_grid* g)
+static int readd_everything(lsa_device_grid* g, int ordered)
 {
-  // prevMap = Get(); Clear(); Add(prevMap)
+  // prevMap = Get(); Clear(); Add(prevMap) -- and, for the "Ordered" setter, the new order between the Get and the Clear
   std::vector<lsa_point_t> all(std::max(g->n_upper, 1));
-  const int n = lsa_device_grid_get(g, 0, all.data(), (int)all.size());
+  const int n = g->n_upper > 0 ? lsa_device_grid_get(g, 0, all.data(), (int)all.size()) : 0;
   if (n < 0) return n;
+  if (ordered >= 0)
+  {
+    if (!ordered)
+    {
+      g->shadow.Fresh();
+      g->rec_kind = 0;  // (none: the grid was in key order)
+      g->rec_voxels = 0;
+      g->order_stale = true;
+    }
+    g->Ordered = ordered != 0;
+  }
   int rc = lsa_device_grid_clear(g);
   if (rc) return rc;
   if (n > 0) return lsa_device_grid_add(g, all.data(), n, 0, -1., 1);

@@ -374,6 +374,11 @@ int lsa_overlap(lsa_ctx* ctx, unsigned type_mask, int interpolate, const double 
  * may be NULL) receives 16 doubles per keypoint: A[9] row-major, P[3], X[3],
  * weight; rows of unmatched keypoints are zero. */
 int lsa_download_match(lsa_ctx* ctx, int type, uint8_t* status, double* weights, double* records, int capacity);
+/* Test hook: writes the match buffer of `type` as lsa_match would leave it -- n rows of the layout lsa_download_match
+ * reads (A[9] row-major, P[3], X[3], weight), their status and the Tukey saturation distance -- so that lsa_accumulate
+ * and the solves run on given residual blocks.  Rows whose status is not LSA_MATCH_SUCCESS are stored as given (any
+ * payload, NaN included): the reductions never read them into a sum.  The buffer grows as lsa_match grows it. */
+int lsa_upload_match(lsa_ctx* ctx, int type, const uint8_t* status, const double* records, int n, double saturation);
 
 /* ------------------------------------------------------------------------- */
 /* Seam 3: LocalOptimizer::Solve() -- slam_lib/src/LocalOptimizer.cxx:74-102.
@@ -493,8 +498,17 @@ int lsa_solve_device_trace(lsa_ctx* ctx, unsigned long long out[12]);
 /* Test hooks for the two bounded waits on the device, so that the callers' fall-backs can be exercised:
  *   "gate_give_up_every" n   every n-th gate (lsa_icp_gate) gives up at once, as if the host had not answered in 50 ms
  *   "lm_give_up_block" b     workgroup b of the NEXT one-launch solve abandons the exchange (the others then wait their
- *                            20 ms and give up too: lsa_solve_device reports LSA_E_STATE); one shot, -1 = none */
+ *                            20 ms and give up too: lsa_solve_device reports LSA_E_STATE); one shot, -1 = none
+ * and the launch shapes of the two reductions, as the environment sets them at creation, with the same clamps; a
+ * negative value restores what the context was created with; they take effect at the next launch:
+ *   "lm_blocks" (LSA_LM_BLOCKS 1..128), "lm_records" (LSA_LM_RECORDS 256..4096), "lm_cache" (LSA_LM_CACHE, at most the
+ *   LDS layers the solve kernel has room for), "accum_blocks" (LSA_ACCUM_BLOCKS 1..256), "mailbox_check" (LSA_MAILBOX_CHECK) */
 int lsa_debug_set(lsa_ctx* ctx, const char* name, int value);
+/* The shape of the last one-launch solve (lsa_solve_device_begin): {workgroups, residual blocks per thread, of those kept
+ * in LDS, residual blocks in all}. */
+int lsa_solve_device_shape(const lsa_ctx* ctx, int out[4]);
+/* The shape of the last lsa_accumulate: {workgroups, most residual blocks of one thread, 0, residual blocks in all}. */
+int lsa_accumulate_shape(const lsa_ctx* ctx, int out[4]);
 /* Solves the device gave up on so far (diagnostics; 0 on a healthy run). */
 int lsa_solve_device_fallbacks(const lsa_ctx* ctx);
 /* Host work for the time the next solve runs on the device: `fn(arg)` is called once, on the calling thread, by the

@@ -262,6 +262,11 @@ struct lsa_ctx
   void* solve_hook_arg = nullptr;
   int lm_records = 512;   // residual blocks per workgroup of the solve kernel the launch aims at (LSA_LM_RECORDS)
   int lm_cache_slots = 0;         // layers of residual blocks the solve kernel keeps in LDS (LSA_LM_CACHE caps it)
+  int lm_cache_capacity = 0;      // layers that fit beside the kernel's static LDS (lm_cache_capacity(), probed at creation)
+  // the launch-shape knobs as the context was created with them (lsa_debug_set with a negative value restores them)
+  struct ShapeKnobs { int lm_blocks, lm_records, lm_cache_slots, accum_blocks; bool mailbox_check; } created_knobs = {};
+  int lm_shape[4] = {0, 0, 0, 0};     // {workgroups, residual blocks per thread, LDS layers, total} of the last solve launch
+  int accum_shape[4] = {0, 0, 0, 0};  // {workgroups, most residual blocks of a thread, 0, total} of the last lsa_accumulate
   int lm_fallbacks = 0;           // solves that timed out on the device and were redone by the host-driven loop
   lsa_sensor_terms_t sensor_terms = {};  // lsa_set_sensor_terms: added to every evaluation of the normal equations (both flags 0: none)
   // per match type a ring of kHistRing blocks of 16 ints ([8] rejection histogram + 2 hand-over counters of the kNN

@@ -573,7 +573,8 @@ int lsa_ctx_create(int device_id, lsa_ctx** out)
   ok &= hipMalloc((void**)&ctx->lm_xchg, (size_t)2 * kLmBlocksMax * kMailboxStride * sizeof(unsigned long long)) == hipSuccess;
   if (ok) ok &= hipMemset(ctx->lm_xchg, 0, (size_t)2 * kLmBlocksMax * kMailboxStride * sizeof(unsigned long long)) == hipSuccess;
   if (const char* e = std::getenv("LSA_ACCUM_BLOCKS")) ctx->accum_blocks = std::min(std::max(std::atoi(e), 1), kAccumBlocksMax);
-  ctx->lm_cache_slots = lm_cache_capacity();
+  ctx->lm_cache_capacity = lm_cache_capacity();
+  ctx->lm_cache_slots = ctx->lm_cache_capacity;
   if (const char* e = std::getenv("LSA_LM_CACHE")) ctx->lm_cache_slots = std::min(std::max(std::atoi(e), 0), ctx->lm_cache_slots);
   if (const char* e = std::getenv("LSA_LM_BLOCKS")) ctx->lm_blocks = std::min(std::max(std::atoi(e), 1), kLmBlocksMax);
   if (const char* e = std::getenv("LSA_LM_RECORDS")) ctx->lm_records = std::min(std::max(std::atoi(e), 256), 4096);
@@ -582,6 +583,7 @@ int lsa_ctx_create(int device_id, lsa_ctx** out)
   if (const char* e = std::getenv("LSA_FUSED_MATCH")) ctx->fused_match = std::atoi(e) != 0;
   if (const char* e = std::getenv("LSA_FUSED_MODEL")) ctx->fused_model = std::atoi(e) != 0;
   if (const char* e = std::getenv("LSA_MAILBOX_CHECK")) ctx->mailbox_check = std::atoi(e) != 0;
+  ctx->created_knobs = {ctx->lm_blocks, ctx->lm_records, ctx->lm_cache_slots, ctx->accum_blocks, ctx->mailbox_check};
   if (!ok) { lsa_ctx_destroy(ctx); return LSA_E_HIP; }
   *out = ctx;
   return LSA_OK;

@@ -739,12 +739,25 @@ int lm_blocks_share()
   return std::max(cus / side_by_side, 8);
 }
 InterpConst make_interp_const(const double H0[16], const double H1[16], double t0, double t1);  // lsa_transform.hip
-// how many 256-thread layers of residual blocks (34 KB each) the solve kernel may keep in LDS beside its own data
+// how many layers of residual blocks (a layer: one block per thread, 17 * kLmThreads doubles = 68 KiB) the solve kernel
+// may keep in LDS beside its own static data (Shared, 34 912 B).  A layer is counted only when the runtime accepts it as
+// dynamic LDS AND static + dynamic fit the LDS a workgroup may have (160 KiB on gfx950: one layer): whether the runtime's
+// check counts the static part is not something to rely on.
 int lm_cache_capacity()
 {
+  const size_t layer = (size_t)17 * kLmThreads * sizeof(double);
+  size_t limit = 0, static_bytes = 0;
+  {
+    hipDeviceProp_t prop;
+    int dev = 0;
+    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) limit = std::max(prop.sharedMemPerBlock, (size_t)prop.maxSharedMemoryPerMultiProcessor);
+    hipFuncAttributes attr;
+    if (hipFuncGetAttributes(&attr, reinterpret_cast<const void*>(k_lm_solve)) == hipSuccess) static_bytes = attr.sharedSizeBytes;
+  }
   int slots = 0;
   for (int want = 3; want >= 1 && slots == 0; --want)
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(k_lm_solve), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(want * 17 * kLmThreads * sizeof(double))) == hipSuccess)
+    if ((limit == 0 || static_bytes + want * layer <= limit) &&
+        hipFuncSetAttribute(reinterpret_cast<const void*>(k_lm_solve), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(want * layer)) == hipSuccess)
       slots = want;
   (void)hipGetLastError();
   return slots;
@@ -815,6 +828,7 @@ static int solve_device_begin(lsa_ctx* ctx, unsigned type_mask, const double pri
   const int per_thread = (total + nb * kLmThreads - 1) / (nb * kLmThreads);
   const size_t slot_bytes = (size_t)17 * kLmThreads * sizeof(double);
   p.cslots = std::min(per_thread, std::max(ctx->lm_cache_slots, 0));
+  ctx->lm_shape[0] = nb; ctx->lm_shape[1] = per_thread; ctx->lm_shape[2] = p.cslots; ctx->lm_shape[3] = total;
   {
     ProfScope ps(ctx, "lm_solve", 0.);
     hipLaunchKernelGGL(k_lm_solve, dim3(nb), dim3(kLmThreads), p.cslots * slot_bytes, ctx->stream, p, ctx->lm_xchg, ctx->lm_mailbox + (size_t)(out_tag % kLmMailRing) * 2 * kLmOut, out_tag,
@@ -1123,9 +1137,30 @@ int lsa_debug_set(lsa_ctx* ctx, const char* name, int value)
 {
   if (!ctx || !name) return LSA_E_ARG;
   const std::string n(name);
+  const lsa_ctx::ShapeKnobs& c = ctx->created_knobs;
+  // the launch-shape knobs: the clamps of the environment variables read at creation (lsa_ctx.hip); negative restores
   if (n == "gate_give_up_every") ctx->debug_gate_give_up_every = value;
   else if (n == "lm_give_up_block") ctx->debug_lm_give_up_block = value;
+  else if (n == "lm_blocks") ctx->lm_blocks = value < 0 ? c.lm_blocks : std::min(std::max(value, 1), kLmBlocksMax);
+  else if (n == "lm_records") ctx->lm_records = value < 0 ? c.lm_records : std::min(std::max(value, 256), 4096);
+  else if (n == "lm_cache") ctx->lm_cache_slots = value < 0 ? c.lm_cache_slots : std::min(value, ctx->lm_cache_capacity);
+  else if (n == "accum_blocks") ctx->accum_blocks = value < 0 ? c.accum_blocks : std::min(std::max(value, 1), kAccumBlocksMax);
+  else if (n == "mailbox_check") ctx->mailbox_check = value < 0 ? c.mailbox_check : value != 0;
   else return ctx->fail(LSA_E_ARG, "lsa_debug_set: no such knob");
+  return LSA_OK;
+}
+
+int lsa_solve_device_shape(const lsa_ctx* ctx, int out[4])
+{
+  if (!ctx || !out) return LSA_E_ARG;
+  std::memcpy(out, ctx->lm_shape, sizeof(ctx->lm_shape));
+  return LSA_OK;
+}
+
+int lsa_accumulate_shape(const lsa_ctx* ctx, int out[4])
+{
+  if (!ctx || !out) return LSA_E_ARG;
+  std::memcpy(out, ctx->accum_shape, sizeof(ctx->accum_shape));
   return LSA_OK;
 }
 

@@ -1527,6 +1527,31 @@ int lsa_download_match(lsa_ctx* ctx, int type, uint8_t* status, double* weights,
   return n;
 }
 
+int lsa_upload_match(lsa_ctx* ctx, int type, const uint8_t* status, const double* records, int n, double saturation)
+{
+  if (!ctx || type < 0 || type > 2 || n < 0 || (n > 0 && (!status || !records)) || !std::isfinite(saturation))
+    return ctx ? ctx->fail(LSA_E_ARG, "lsa_upload_match: bad argument") : LSA_E_ARG;
+  LSA_HIP(ctx, hipSetDevice(ctx->device));
+  MatchBuf& mb = ctx->match[type];
+  int rc = ensure_match(ctx, type, n);  // (outgrown buffers are retired: launches in flight keep them)
+  if (rc) return rc;
+  if (n > 0)
+  {
+    // rows as lsa_download_match hands them out -> the SoA layout of the match buffer, rejected rows as given
+    std::vector<double> soa((size_t)16 * n);
+    for (int i = 0; i < n; ++i)
+      for (int f = 0; f < 16; ++f) soa[(size_t)f * n + i] = records[(size_t)i * 16 + f];
+    LSA_HIP(ctx, hipMemcpy2DAsync(mb.rec, (size_t)mb.cap * sizeof(double), soa.data(), (size_t)n * sizeof(double), (size_t)n * sizeof(double), 16,
+                                  hipMemcpyHostToDevice, ctx->stream));
+    LSA_HIP(ctx, hipMemcpyAsync(mb.status, status, (size_t)n, hipMemcpyHostToDevice, ctx->stream));
+    LSA_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  }
+  mb.k = n;
+  mb.sat = saturation;
+  mb.valid = true;
+  return LSA_OK;
+}
+
 long long lsa_match_serial(const lsa_ctx* ctx, int type)
 {
   if (!ctx || type < 0 || type > 2) return LSA_E_ARG;
@@ -1598,6 +1623,10 @@ int lsa_accumulate(lsa_ctx* ctx, unsigned type_mask, const double w[6], int want
     total += c.set.count[k];
   }
   c.jac = want_jacobian;
+  ctx->accum_shape[0] = ctx->accum_blocks;
+  ctx->accum_shape[1] = (total + ctx->accum_blocks * 256 - 1) / (ctx->accum_blocks * 256);
+  ctx->accum_shape[2] = 0;
+  ctx->accum_shape[3] = total;
   hipStream_t st = ctx->stream;
   const unsigned want = (unsigned)(++ctx->mailbox_seq);
   {

@@ -8,6 +8,7 @@ import time
 import numpy as np
 import pytest
 
+import reduction_cases as RC
 from conftest import bits, pose_diff
 
 pytestmark = pytest.mark.gpu
@@ -181,6 +182,15 @@ def test_normal_equations_match_the_oracle(gpu_ctx, O, L, kps, model):
         assert np.abs(g - go).max() <= 1e-11 * np.abs(go).max()
         assert np.abs(H - Ho).max() <= 1e-12 * np.abs(Ho).max()
         assert np.array_equal(H, H.T)
+        # every entry, not just the largest: within the summation bound of tests/reduction_cases.py of the exactly
+        # rounded sum of the per-block values the kernel adds, at the depth of the shape that ran
+        ab, per_thread, _, total = gpu_ctx.accumulate_shape()
+        assert total == rec.shape[0]
+        rs = RC.RSet("MATCHED", f"model {model}", [st, np.zeros(0), np.zeros(0)], [rec, np.zeros((0, 16)), np.zeros((0, 16))], [5.0, 5.0, 5.0], [w6])
+        ref = RC.Reference(O, rs, w6)
+        assert ref.count == nv
+        bad = ref.violations(RC.sums_of(cost, g, H), RC.depth_accum(ab, per_thread))
+        assert bad.size == 0, f"entries {bad.tolist()} outside the per-entry bound"
         c2, _, _, _ = gpu_ctx.accumulate(7, w6, jac=False)
         assert c2 == cost  # the cost does not depend on whether the Jacobian is asked for
 

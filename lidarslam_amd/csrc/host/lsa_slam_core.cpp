@@ -639,6 +639,303 @@ lsa_match_params_t SlamCore::LocMatchParams() const
   return p;
 }
 
+// ---- the ICP loop of ComputeEgoMotion() and Localization() ---------------------------------------------------------------
+// What the two tell RunIcpLoop about their loop; what only one of them does at some point of an iteration is a callable.
+struct SlamCore::IcpLoopSpec
+{
+  const char* name;                        // "ego" / "loc" (trace lines)
+  int target, set;                         // the LSA_TARGET_* searched, the LSA_SET_* matched against it
+  unsigned matchMask, solveMask;           // keypoint types matched / whose residual blocks the solves take
+  unsigned maxIter, lmMaxIter;
+  double initSaturation, finalSaturation;  // the saturation distance goes from one to the other over the loop
+  lsa_match_params_t match;
+  int loopBit;                             // this loop's bit of LSA_ICP_AHEAD_LOOPS
+  bool linksOk, gatesOk;                   // this loop's iterations can wait behind links / behind gates at all
+  int undistortAhead;                      // `undistort` of lsa_match_types_gated: a search enqueued ahead starts with RefineUndistortion
+  lsa_icp_link_t link;                     // what the loop's solves need to leave a link (`first` is the driver's)
+  long long* matchSerial;                  // lsa_match_serial per type, of the iteration whose result was read last
+  double FrameStats::*icpSeconds;          // stage timers: an iteration's enqueueing, the wait for its solve
+  double FrameStats::*lmSeconds;
+  int FrameStats::*iterations;
+  bool countSkippedEvals;                  // Stats.lm_evals takes in the evaluation of a skipped solve
+};
+// A RefineUndistortion between two iterations that is not applied by a launch of its own
+struct SlamCore::IcpUndistortion
+{
+  Pose d0 = Pose::Identity(), d1 = Pose::Identity();
+  bool pending = false;  // the undistortion the last iteration ended with has not been applied yet
+  bool posted = false;   // ... it was handed to the gate of the iteration enqueued ahead
+};
+
+namespace
+{
+constexpr auto kNothing = [](auto&&...) { return LSA_OK; };  // the callable of a loop that does nothing at that point
+// diagnostics, read once
+const bool kAheadWithHostMaps = std::getenv("LSA_ICP_AHEAD_HOSTMAPS") != nullptr;  // gates in the ego-motion loop with the maps on the host too (see RunIcpLoop)
+const int kAheadLoops = std::getenv("LSA_ICP_AHEAD_LOOPS") ? std::atoi(std::getenv("LSA_ICP_AHEAD_LOOPS")) : 3;  // the loops that enqueue ahead at all: 1 ego-motion only, 2 localization only
+const bool kGateDebug = std::getenv("LSA_GATE_DEBUG") != nullptr;
+}  // namespace
+
+// How an ICP loop's iterations reach the device: the one place where that is written down.  `pose` is the pose the loop
+// iterates (prior of every solve, replaced by every accepted result).  The callables, all returning an LSA_* code:
+//   top(icpIter)                      before anything of the iteration is enqueued
+//   enqueued(icpIter)                 between the iteration's enqueueing and the wait for its solve
+//   solved()                          the solve's result is there
+//   skipped()                         ... with too few matches: the loop ends
+//   accepted(last, undistortion)      `pose` is the solve's; what was enqueued ahead has been called off if `last`.  A
+//                                     RefineUndistortion left in `undistortion` (pending) rides in the next search
+//   finished(optimizer)               after the last accepted iteration
+// In line (ICPAhead = 0, and the fall-back of the other two): match, solve, and the next match once the pose is known.
+// Gates (ICPAhead = 1, and loops longer than kChainMax): iteration i + 1 is enqueued behind a gate (lsa_icp_gate) while
+// iteration i runs: when the solve's result arrives its launches are in the queue already, and all that is between the
+// solve and the next search is one store the gate polls for (or the call that calls them off: Slam.cxx:919-923, 950).
+// Links (ICPAhead = 2): the WHOLE loop is enqueued at once, every solve leaving pose and start point for the iteration
+// behind it on the device (lsa_icp_link) -- no gate, no host between two iterations, nothing spins; this thread reads the
+// results as they arrive, takes the decisions the device has taken already and does its own pose algebra beside the running
+// device.
+// (spec.gatesOk of the ego-motion loop: with the maps on the HOST it stays in line.  Between its iterations this thread then
+// hands sub-maps the map workers have extracted to the look-ahead stream (StageSpeculativeSubMaps: a copy out of pinned
+// memory and a grid build).  With a gate waiting on the registration's stream at that moment the device delivered no result
+// for two seconds in some assignments of the streams to the hardware queues (seen with a second context alive in the
+// process), the solve was then redone on the host with the NEXT iteration's saturation distance already in force: 1.5e-5 m
+// beside the oracle.  The hang is not understood (LSA_ICP_AHEAD_HOSTMAPS=1 + LSA_ICP_TRACE=1 reproduce it); the fall-back's
+// wrong distance is fixed (the solve on the host takes the distances the device solve was enqueued with).)
+template <class Top, class Enqueued, class Solved, class Skipped, class Accepted, class Finished>
+int SlamCore::RunIcpLoop(const IcpLoopSpec& spec, Pose& pose, const Top& top, const Enqueued& enqueued, const Solved& solved, const Skipped& skipped,
+                         const Accepted& accepted, const Finished& finished)
+{
+  TotalMatchedKeypoints = 0;
+  lsa_match_params_t mp = spec.match;
+  auto saturation = [&](unsigned icpIter) {
+    const double iterRatio = icpIter / static_cast<double>(spec.maxIter - 1);
+    return (1 - iterRatio) * spec.initSaturation + iterRatio * spec.finalSaturation;
+  };
+  const bool aheadOk = ICPAhead >= 1 && DeviceLM && FusedMatch && (kAheadLoops & spec.loopBit);
+  bool chain = aheadOk && ICPAhead >= 2 && spec.maxIter <= kChainMax && spec.linksOk;
+  bool ahead = aheadOk && !chain && spec.gatesOk;
+  if (ahead || chain) lsa_icp_abandon(Ctx);
+  unsigned chained = 0;            // iterations 0 .. chained - 1 are in the queue (links)
+  long long chainSerial[kChainMax][3] = {};
+  bool enqueuedAhead = false;      // this iteration's launches are in the queue (their gate has been answered)
+  long long aheadSerial[3] = {0, 0, 0};
+  int ticket = -1;                 // the gate the next iteration waits behind
+  IcpUndistortion undistortion;
+  unsigned icpIter = 0;
+
+  // Every way out calls off what is still in the queue: the gate's iteration, and the links' when the loop ends in front
+  // of them (the device has taken the same decision from the same result -- the iterations behind do nothing; what their
+  // matches announced on the host is taken back).  After an error nobody will end the solves begun: all of it goes.
+  auto callOffRest = [&](bool all) {
+    if (ticket >= 0)
+    {
+      lsa_icp_cancel(Ctx, ticket);
+      lsa_solve_device_drop(Ctx);
+      ticket = -1;
+    }
+    if (all || icpIter + 1 < chained)
+    {
+      lsa_icp_abandon(Ctx);
+      chained = 0;
+    }
+  };
+  struct AtExit { decltype(callOffRest)& callOffRest; bool failed; ~AtExit() { callOffRest(failed); } } atExit{callOffRest, true};
+
+  auto takeSerials = [&](long long* serial) {
+    for (int k = 0; k < 3; ++k)
+      if ((spec.matchMask >> k) & 1u) serial[k] = lsa_match_serial(Ctx, k);
+  };
+  auto setSerials = [&](const long long* serial) {
+    for (int k = 0; k < 3; ++k)
+      if ((spec.matchMask >> k) & 1u) spec.matchSerial[k] = serial[k];
+  };
+  auto matchInLine = [&]() -> int {
+    // all keypoint types are matched concurrently and nothing is read back: the number of matches arrives with the
+    // optimizer's first evaluation.  A pending undistortion (of the working keypoints: the localization's) rides in this
+    // iteration's search kernel (same keypoints, one launch less)
+    if (undistortion.pending)
+      LSA_TRY(lsa_match_types_undistorted(Ctx, spec.target, spec.matchMask, &mp, pose.m, nullptr, undistortion.d0.m, undistortion.d1.m, Motion.Time0, Motion.Time1));
+    else
+      LSA_TRY(lsa_match_types(Ctx, spec.target, spec.matchMask, spec.set, &mp, pose.m, nullptr));
+    undistortion.pending = false;
+    takeSerials(spec.matchSerial);
+    return LSA_OK;
+  };
+  // iteration `iter` behind the link or the gate enqueued last; 1 (and nothing enqueued) when it cannot wait there
+  auto matchAhead = [&](unsigned iter, long long* serial) -> int {
+    lsa_match_params_t next = mp;
+    next.saturation_distance = saturation(iter);
+    const int rc = lsa_match_types_gated(Ctx, spec.target, spec.matchMask, spec.set, &next, spec.undistortAhead);
+    if (rc == 0) takeSerials(serial);
+    return rc;
+  };
+
+  for (; icpIter < spec.maxIter; ++icpIter)
+  {
+    Tick ticp;
+    if (const int rc = top(icpIter); rc < 0) return rc;
+    mp.saturation_distance = saturation(icpIter);
+    LocalOptimizer optimizer(Ctx);
+    optimizer.SetDeviceLoop(DeviceLM);
+    optimizer.SetTwoDMode(TwoDMode);
+    optimizer.SetLMMaxIter(spec.lmMaxIter);
+    optimizer.SetMinMatches(MinNbMatchedKeypoints);
+    optimizer.UseDeviceResiduals(spec.solveMask);
+    optimizer.SetPosePrior(pose);
+    bool begun = enqueuedAhead;  // the solve of this iteration is in flight
+    if (icpIter < chained)
+    {
+      begun = true;
+      setSerials(chainSerial[icpIter]);
+    }
+    else if (!enqueuedAhead)
+    {
+      if (const int rc = matchInLine(); rc < 0) return rc;
+      if (chain)
+      {
+        // this iteration's solve and every iteration behind it, as far as they can ride behind links
+        double prior[6];
+        ToXYZRPY(pose, prior);
+        lsa_icp_link_t link = spec.link;
+        for (unsigned j = icpIter; j < spec.maxIter; ++j)
+        {
+          int leave = j + 1 < spec.maxIter ? lsa_icp_link(Ctx) : -1;
+          if (leave < 0) leave = -1;
+          link.first = j == icpIter ? 1 : 0;
+          const int rc = lsa_solve_device_begin_linked(Ctx, spec.solveMask, j == icpIter ? prior : nullptr, TwoDMode ? 1 : 0, static_cast<int>(spec.lmMaxIter), static_cast<int>(MinNbMatchedKeypoints), leave,
+                                                       leave >= 0 ? &link : nullptr);
+          if (rc < 0) return Fail(rc, "lsa_solve_device_begin_linked");
+          chained = j + 1;
+          if (leave < 0) break;
+          const int mrc = matchAhead(j + 1, chainSerial[j + 1]);
+          if (mrc < 0) return Fail(mrc, "lsa_match_types_gated");
+          if (mrc != 0) { lsa_icp_cancel(Ctx, leave); break; }  // this match cannot wait behind a link: the loop goes on in line from there
+        }
+        chain = false;  // (enqueued once; whatever is not in the queue now runs in line)
+        begun = true;
+      }
+      else if (ahead)
+      {
+        LSA_TRY(optimizer.Begin(false));
+        begun = true;
+      }
+    }
+    else
+      setSerials(aheadSerial);
+    ICP_TRACE("[%s %u] top: ahead %d begun %d enqueued %d\n", spec.name, icpIter, (int)ahead, (int)begun, (int)enqueuedAhead);
+    enqueuedAhead = false;
+    if (ahead && begun && icpIter + 1 < spec.maxIter)
+    {
+      ticket = lsa_icp_gate(Ctx);
+      ICP_TRACE("[%s %u] gate ticket %d\n", spec.name, icpIter, ticket);
+      if (ticket < 0) { ticket = -1; ahead = false; }
+      else
+      {
+        const char* call = "lsa_match_types_gated";
+        int rc = matchAhead(icpIter + 1, aheadSerial);
+        if (rc == 0)
+        {
+          call = "lsa_solve_device_begin";
+          rc = lsa_solve_device_begin(Ctx, spec.solveMask, nullptr, TwoDMode ? 1 : 0, static_cast<int>(spec.lmMaxIter), static_cast<int>(MinNbMatchedKeypoints));
+        }
+        if (rc != 0)
+        {
+          // nothing waits behind this gate: the loop goes on without gates
+          lsa_icp_cancel(Ctx, ticket);
+          ticket = -1;
+          ahead = false;
+          if (rc < 0) return Fail(rc, call);
+        }
+      }
+    }
+    if (const int rc = enqueued(icpIter); rc < 0) return rc;
+    if (!begun) ArmLookaheadInterlude();
+    Stats.*spec.icpSeconds += ticp.Stop();
+    (Stats.*spec.iterations)++;
+
+    Tick tlm;
+    SolveSummary summary;
+    if (begun)
+    {
+      Tick tdbg;
+      const int irc = InterludeWork();
+      const double dbgInterlude = tdbg.Stop();
+      int rc = optimizer.End(summary);
+      ICP_TRACE("[%s %u] End rc %d irc %d ticket %d\n", spec.name, icpIter, rc, irc, ticket);
+      if (kGateDebug && tdbg.Stop() > 0.01)
+        std::fprintf(stderr, "[gate debug] %s iteration %u: enqueue %.3f ms, interlude %.3f ms, until the result %.3f ms, rc %d\n", spec.name, icpIter, 1e3 * Stats.*spec.icpSeconds, 1e3 * dbgInterlude,
+                     1e3 * tdbg.Stop(), rc);
+      if (rc == LSA_E_GATE)
+      {
+        // the gate gave up waiting for this thread (it was held up for 50 ms): nothing of the iteration ran.  Whatever
+        // waits behind it is called off, the iteration is done again in line, the rest of the loop without gates.
+        callOffRest(true);
+        ahead = false;
+        IcpGateTimeouts++;
+        undistortion.pending = undistortion.posted;  // (it was to ride in the search that did not run)
+        rc = matchInLine();
+        if (rc < 0) return rc;
+        rc = optimizer.Solve(summary);
+      }
+      if (rc < 0) return Fail(rc, "LocalOptimizer::End / Solve");
+      if (rc == 1) { ticket = -1; ahead = false; chained = 0; }  // solved on the host: what was enqueued ahead has been called off
+      if (irc < 0) return irc;
+    }
+    else
+    {
+      LSA_TRY(optimizer.Solve(summary));
+      LSA_TRY(FinishLookaheadInterlude());
+    }
+    TotalMatchedKeypoints = summary.num_matches;
+    if (lsa_icp_trace_on())
+      std::fprintf(stderr, "[icp] frame %u %s %u: matches %d evals %d steps %d cost %.17g -> %.17g%s\n", NbrFrameProcessed, spec.name, icpIter, summary.num_matches, summary.num_evaluations,
+                   summary.num_successful_steps, summary.initial_cost, summary.final_cost, summary.skipped ? " skipped" : "");
+    if (const int rc = solved(); rc < 0) return rc;
+    if (!summary.skipped || spec.countSkippedEvals) Stats.lm_evals += summary.num_evaluations;
+    if (!summary.skipped) pose = optimizer.GetOptimizedPose();
+    // Nothing more to search: called off HERE, in front of whatever `accepted` and `finished` put on the stream (an
+    // undistortion, the registration error), so that it does not wait behind the gate.
+    const bool last = summary.skipped || summary.num_successful_steps == 1 || icpIter + 1 == spec.maxIter;
+    if (last) callOffRest(false);
+    const int rc = summary.skipped ? skipped() : accepted(last, undistortion);
+    Stats.*spec.lmSeconds += tlm.Stop();
+    if (rc < 0) return rc;
+    if (last)
+    {
+      if (const int frc = summary.skipped ? LSA_OK : finished(optimizer); frc < 0) return frc;
+      break;
+    }
+    if (ticket >= 0)
+    {
+      double prior[6];
+      ToXYZRPY(pose, prior);  // LocalOptimizer::SetPosePrior of the next iteration
+      const int prc = lsa_icp_post(Ctx, ticket, pose.m, prior, undistortion.pending ? undistortion.d0.m : nullptr, undistortion.pending ? undistortion.d1.m : nullptr, Motion.Time0, Motion.Time1);
+      if (prc < 0) return Fail(prc, "lsa_icp_post");
+      ticket = -1;
+      undistortion.posted = undistortion.pending;
+      undistortion.pending = false;
+      enqueuedAhead = true;
+    }
+    else if (icpIter + 1 < chained)
+      undistortion.pending = false;  // the next search is in the queue and undistorts with what the device worked out (the same)
+  }
+  atExit.failed = false;
+  return LSA_OK;
+}
+
+// MatchingResults::Rejections / Weights of the loop's last iteration (KeepMatchDebug)
+int SlamCore::DownloadMatchDebug(int set, unsigned typeMask, MatchDebug* debug)
+{
+  for (int k = 0; k < 3; ++k)
+  {
+    if (!((typeMask >> k) & 1u)) continue;
+    const int n = lsa_keypoint_count(Ctx, set, k);
+    debug[k].status.assign(n, LSA_MATCH_UNKOWN);
+    debug[k].weights.assign(n, 0.);
+    if (n > 0) LSA_TRY(lsa_download_match(Ctx, k, debug[k].status.data(), debug[k].weights.data(), nullptr, n));
+  }
+  return LSA_OK;
+}
+
 // Slam::ComputeEgoMotion (Slam.cxx:813-972)
 int SlamCore::ComputeEgoMotion()
 {
@@ -671,132 +968,25 @@ int SlamCore::ComputeEgoMotion()
     lsa_set_target_cell_size(Ctx, LSA_TARGET_PREVIOUS, k, static_cast<float>(k == LSA_EDGE ? KnnCellSizeEgoMotionEdges : KnnCellSizeEgoMotion));
     LSA_TRY(lsa_set_target_from_set(Ctx, LSA_TARGET_PREVIOUS, k, LSA_SET_RAW_PREVIOUS));
   }
-  TotalMatchedKeypoints = 0;
-  lsa_match_params_t mp = EgoMatchParams();
-  const unsigned mask = (1u << LSA_EDGE) | (1u << LSA_PLANE);
-  auto saturation = [&](unsigned icpIter) {
-    const double iterRatio = icpIter / static_cast<double>(EgoMotionICPMaxIter - 1);
-    return (1 - iterRatio) * EgoMotionInitSaturationDistance + iterRatio * EgoMotionFinalSaturationDistance;
-  };
-  auto configure = [&](LocalOptimizer& optimizer) {
-    optimizer.SetDeviceLoop(DeviceLM);
-    optimizer.SetTwoDMode(TwoDMode);
-    optimizer.SetLMMaxIter(EgoMotionLMMaxIter);
-    optimizer.SetMinMatches(MinNbMatchedKeypoints);
-    optimizer.UseDeviceResiduals(mask);
-  };
-  // Iteration i + 1 is enqueued behind a gate (lsa_icp_gate) while iteration i runs: when the solve's result arrives its
-  // launches are in the queue already, and all that is between the solve and the next search is one store the gate polls
-  // for (or the call that calls them off: Slam.cxx:919-923, 950).
-  // (With the maps on the HOST this loop stays as it was.  Between its iterations this thread then hands sub-maps the map
-  // workers have extracted to the look-ahead stream (StageSpeculativeSubMaps: a copy out of pinned memory and a grid build).
-  // With a gate waiting on the registration's stream at that moment the device delivered no result for two seconds in some
-  // assignments of the streams to the hardware queues (seen with a second context alive in the process), the solve was then
-  // redone on the host with the NEXT iteration's saturation distance already in force: 1.5e-5 m beside the oracle.  The
-  // hang is not understood (LSA_ICP_AHEAD_HOSTMAPS=1 + LSA_ICP_TRACE=1 reproduce it); the fall-back's wrong distance is
-  // fixed (the solve on the host takes the distances the device solve was enqueued with).)
-  static const bool aheadWithHostMaps = std::getenv("LSA_ICP_AHEAD_HOSTMAPS") != nullptr;  // (diagnostics)
-  static const int aheadLoops = std::getenv("LSA_ICP_AHEAD_LOOPS") ? std::atoi(std::getenv("LSA_ICP_AHEAD_LOOPS")) : 3;  // (diagnostics: 1 ego-motion only, 2 localization only)
-  // ICPAhead = 2: the WHOLE loop is enqueued at once, every solve leaving pose and start point for the iteration behind it
-  // on the device (lsa_icp_link) -- no gate, no host between two iterations, nothing spins; this thread reads the results as
-  // they arrive, takes the decisions the device has taken already and does its own pose algebra beside the running device.
-  bool chain = ICPAhead >= 2 && DeviceLM && FusedMatch && EgoMotionICPMaxIter <= kChainMax && (aheadLoops & 1);
-  bool ahead = !chain && ICPAhead >= 1 && DeviceLM && FusedMatch && (DeviceMapsInUse() || MapUpdate == MappingMode::NONE || aheadWithHostMaps) && (aheadLoops & 1);
-  if (ahead || chain) lsa_icp_abandon(Ctx);
-  unsigned chained = 0;            // iterations 0 .. chained - 1 are in the queue (links)
-  long long chainSerial[kChainMax][3] = {};
-  bool enqueued = false;           // this iteration's launches are in the queue (their gate has been answered)
-  long long aheadSerial[3] = {0, 0, 0};
-  auto callOff = [&](int& ticket) {
-    if (ticket < 0) return;
-    lsa_icp_cancel(Ctx, ticket);
-    lsa_solve_device_drop(Ctx);
-    ticket = -1;
-  };
-
-  DbgAcc[2] += tpre.Stop();
-  for (unsigned icpIter = 0; icpIter < EgoMotionICPMaxIter; ++icpIter)
-  {
-    Tick ticp;
-    mp.saturation_distance = saturation(icpIter);
-    LocalOptimizer optimizer(Ctx);
-    configure(optimizer);
-    optimizer.SetPosePrior(Trelative);
-    bool begun = enqueued;  // the solve of this iteration is in flight
-    if (icpIter < chained)
-    {
-      begun = true;
-      for (int k : {LSA_EDGE, LSA_PLANE}) EgoMatchSerial[k] = chainSerial[icpIter][k];
-    }
-    else if (!enqueued)
-    {
-      // both keypoint types are matched concurrently and nothing is read back: the number of matches
-      // arrives with the optimizer's first evaluation
-      LSA_TRY(lsa_match_types(Ctx, LSA_TARGET_PREVIOUS, mask, LSA_SET_RAW_CURRENT, &mp, Trelative.m, nullptr));
-      for (int k : {LSA_EDGE, LSA_PLANE}) EgoMatchSerial[k] = lsa_match_serial(Ctx, k);
-      if (chain)
-      {
-        // this iteration's solve and every iteration behind it, as far as they can ride behind links
-        double prior[6];
-        ToXYZRPY(Trelative, prior);
-        lsa_icp_link_t link;
-        std::memset(&link, 0, sizeof(link));
-        for (unsigned j = icpIter; j < EgoMotionICPMaxIter; ++j)
-        {
-          int leave = j + 1 < EgoMotionICPMaxIter ? lsa_icp_link(Ctx) : -1;
-          if (leave < 0) leave = -1;
-          link.first = j == icpIter ? 1 : 0;
-          const int rc = lsa_solve_device_begin_linked(Ctx, mask, j == icpIter ? prior : nullptr, TwoDMode ? 1 : 0, static_cast<int>(EgoMotionLMMaxIter), static_cast<int>(MinNbMatchedKeypoints), leave,
-                                                       leave >= 0 ? &link : nullptr);
-          if (rc < 0) { lsa_icp_abandon(Ctx); return Fail(rc, "lsa_solve_device_begin_linked"); }
-          chained = j + 1;
-          if (leave < 0) break;
-          lsa_match_params_t next = mp;
-          next.saturation_distance = saturation(j + 1);
-          const int mrc = lsa_match_types_gated(Ctx, LSA_TARGET_PREVIOUS, mask, LSA_SET_RAW_CURRENT, &next, 0);
-          if (mrc < 0) { lsa_icp_abandon(Ctx); return Fail(mrc, "lsa_match_types_gated"); }
-          if (mrc != 0) { lsa_icp_cancel(Ctx, leave); break; }  // this match cannot wait behind a link: the loop goes on in line from there
-          for (int k : {LSA_EDGE, LSA_PLANE}) chainSerial[j + 1][k] = lsa_match_serial(Ctx, k);
-        }
-        chain = false;  // (enqueued once; whatever is not in the queue now runs in line)
-        begun = true;
-      }
-      else if (ahead)
-      {
-        LSA_TRY(optimizer.Begin(false));
-        begun = true;
-      }
-    }
-    else
-      for (int k : {LSA_EDGE, LSA_PLANE}) EgoMatchSerial[k] = aheadSerial[k];
-    ICP_TRACE("[ego %u] top: ahead %d begun %d enqueued %d\n", icpIter, (int)ahead, (int)begun, (int)enqueued);
-    enqueued = false;
-    int ticket = -1;
-    if (ahead && begun && icpIter + 1 < EgoMotionICPMaxIter)
-    {
-      ticket = lsa_icp_gate(Ctx);
-      ICP_TRACE("[ego %u] gate ticket %d\n", icpIter, ticket);
-      if (ticket < 0) { ticket = -1; ahead = false; }
-      else
-      {
-        lsa_match_params_t next = mp;
-        next.saturation_distance = saturation(icpIter + 1);
-        int rc = lsa_match_types_gated(Ctx, LSA_TARGET_PREVIOUS, mask, LSA_SET_RAW_CURRENT, &next, 0);
-        if (rc == 0)
-        {
-          for (int k : {LSA_EDGE, LSA_PLANE}) aheadSerial[k] = lsa_match_serial(Ctx, k);
-          rc = lsa_solve_device_begin(Ctx, mask, nullptr, TwoDMode ? 1 : 0, static_cast<int>(EgoMotionLMMaxIter), static_cast<int>(MinNbMatchedKeypoints));
-          if (rc < 0) { lsa_icp_cancel(Ctx, ticket); return Fail(rc, "lsa_solve_device_begin"); }
-        }
-        else
-        {
-          lsa_icp_cancel(Ctx, ticket);
-          ticket = -1;
-          ahead = false;
-          if (rc < 0) return Fail(rc, "lsa_match_types_gated");
-        }
-      }
-    }
+  IcpLoopSpec spec = {};
+  spec.name = "ego";
+  spec.target = LSA_TARGET_PREVIOUS;
+  spec.set = LSA_SET_RAW_CURRENT;
+  spec.matchMask = spec.solveMask = (1u << LSA_EDGE) | (1u << LSA_PLANE);
+  spec.maxIter = EgoMotionICPMaxIter;
+  spec.lmMaxIter = EgoMotionLMMaxIter;
+  spec.initSaturation = EgoMotionInitSaturationDistance;
+  spec.finalSaturation = EgoMotionFinalSaturationDistance;
+  spec.match = EgoMatchParams();
+  spec.loopBit = 1;
+  spec.linksOk = true;
+  spec.gatesOk = DeviceMapsInUse() || MapUpdate == MappingMode::NONE || kAheadWithHostMaps;  // (the host-map stall: RunIcpLoop)
+  spec.matchSerial = EgoMatchSerial;
+  spec.icpSeconds = &FrameStats::ego_icp;
+  spec.lmSeconds = &FrameStats::ego_lm;
+  spec.iterations = &FrameStats::ego_iters;
+  spec.countSkippedEvals = true;
+  auto enqueued = [&](unsigned icpIter) -> int {
     // the targets of the NEXT frame's ego-motion, which are this frame's keypoints, are built beside this registration:
     // enqueued (ten launches and two copies on the look-ahead stream: a host thread of their own issues them, this one
     // goes on to the solve) while the first iteration's kernels -- the solve's included -- are on their way
@@ -807,78 +997,14 @@ int SlamCore::ComputeEgoMotion()
     }
     // while the device is busy with this iteration: sub-maps the workers have finished meanwhile go to the device
     if (!SpecPending) LSA_TRY(StageSpeculativeSubMaps());
-    if (!begun) ArmLookaheadInterlude();
-    Stats.ego_icp += ticp.Stop();
-    Stats.ego_iters++;
-
-    Tick tlm;
-    SolveSummary summary;
-    if (begun)
-    {
-      Tick tdbg;
-      const int irc = InterludeWork();
-      const double dbgInterlude = tdbg.Stop();
-      int rc = optimizer.End(summary);
-      ICP_TRACE("[ego %u] End rc %d irc %d ticket %d\n", icpIter, rc, irc, ticket);
-      static const bool gateDebug = std::getenv("LSA_GATE_DEBUG") != nullptr;
-      if (gateDebug && tdbg.Stop() > 0.01)
-        std::fprintf(stderr, "[gate debug] ego iteration %u: enqueue %.3f ms, interlude %.3f ms, until the result %.3f ms, rc %d\n", icpIter, 1e3 * Stats.ego_icp, 1e3 * dbgInterlude, 1e3 * tdbg.Stop(), rc);
-      if (rc == LSA_E_GATE)
-      {
-        // the gate gave up waiting for this thread (it was held up for 50 ms): nothing of the iteration ran.  Whatever
-        // waits behind it is called off, the iteration is done again in line, the rest of the loop without gates.
-        callOff(ticket);
-        lsa_icp_abandon(Ctx);
-        ahead = false;
-        IcpGateTimeouts++;
-        LSA_TRY(lsa_match_types(Ctx, LSA_TARGET_PREVIOUS, mask, LSA_SET_RAW_CURRENT, &mp, Trelative.m, nullptr));
-        for (int k : {LSA_EDGE, LSA_PLANE}) EgoMatchSerial[k] = lsa_match_serial(Ctx, k);
-        rc = optimizer.Solve(summary);
-      }
-      if (rc < 0) { callOff(ticket); lsa_icp_abandon(Ctx); return Fail(rc, "LocalOptimizer::Solve (ego-motion)"); }
-      if (rc == 1) { ticket = -1; ahead = false; chained = 0; }  // solved on the host: what was enqueued ahead has been called off
-      if (irc < 0) { callOff(ticket); return irc; }
-    }
-    else
-    {
-      LSA_TRY(optimizer.Solve(summary));
-      LSA_TRY(FinishLookaheadInterlude());
-    }
-    TotalMatchedKeypoints = summary.num_matches;
-    if (lsa_icp_trace_on())
-      std::fprintf(stderr, "[icp] frame %u ego %u: matches %d evals %d steps %d cost %.17g -> %.17g%s\n", NbrFrameProcessed, icpIter, summary.num_matches, summary.num_evaluations,
-                   summary.num_successful_steps, summary.initial_cost, summary.final_cost, summary.skipped ? " skipped" : "");
-    if (SpecPending)
-    {
-      // the predicted bounding boxes have long arrived: the map workers extract the sub-maps from here on
-      const int rc = FinishSubMapSpeculation();
-      if (rc < 0) { callOff(ticket); return rc; }
-    }
-    Stats.ego_lm += tlm.Stop();
-    Stats.lm_evals += summary.num_evaluations;
-    // (links: the device has taken the same decision from the same result -- the iterations behind this one do nothing;
-    //  what their matches announced on the host is taken back)
-    const bool more = icpIter + 1 < chained;
-    if (summary.skipped) { callOff(ticket); if (more) lsa_icp_abandon(Ctx); break; }  // "Not enough keypoints, EgoMotion skipped for this frame."
-    Trelative = optimizer.GetOptimizedPose();
-    if (summary.num_successful_steps == 1) { callOff(ticket); if (more) lsa_icp_abandon(Ctx); break; }
-    if (ticket >= 0)
-    {
-      double prior[6];
-      ToXYZRPY(Trelative, prior);  // LocalOptimizer::SetPosePrior of the next iteration
-      const int rc = lsa_icp_post(Ctx, ticket, Trelative.m, prior, nullptr, nullptr, 0., 0.);
-      if (rc < 0) return Fail(rc, "lsa_icp_post");
-      enqueued = true;
-    }
-  }
-  if (KeepMatchDebug)
-    for (int k : {LSA_EDGE, LSA_PLANE})
-    {
-      const int n = lsa_keypoint_count(Ctx, LSA_SET_RAW_CURRENT, k);
-      EgoDebug[k].status.assign(n, LSA_MATCH_UNKOWN);
-      EgoDebug[k].weights.assign(n, 0.);
-      if (n > 0) LSA_TRY(lsa_download_match(Ctx, k, EgoDebug[k].status.data(), EgoDebug[k].weights.data(), nullptr, n));
-    }
+    return LSA_OK;
+  };
+  // the predicted bounding boxes have long arrived: the map workers extract the sub-maps from here on
+  auto solved = [&]() -> int { return SpecPending ? FinishSubMapSpeculation() : LSA_OK; };
+  DbgAcc[2] += tpre.Stop();
+  // ("Not enough keypoints, EgoMotion skipped for this frame." leaves Trelative as it is)
+  if (const int rc = RunIcpLoop(spec, Trelative, kNothing, enqueued, solved, kNothing, kNothing, kNothing); rc < 0) return rc;
+  if (KeepMatchDebug) return DownloadMatchDebug(LSA_SET_RAW_CURRENT, spec.matchMask, EgoDebug);
   return LSA_OK;
 }
 
@@ -1074,247 +1200,74 @@ int SlamCore::Localization()
     Stats.submap += t.Stop();
   }
 
-  TotalMatchedKeypoints = 0;
-  lsa_match_params_t mp = LocMatchParams();
-  Pose pendingD0 = Pose::Identity(), pendingD1 = Pose::Identity();
-  bool pendingUndistort = false;  // the undistortion the last iteration ended with has not been applied yet
-  bool postedUndistort = false;   // ... it was handed to the gate of the iteration enqueued ahead
-  unsigned mask = 0;
+  const bool refined = Undistortion == UNDISTORTION_REFINED;
+  IcpLoopSpec spec = {};
+  spec.name = "loc";
+  spec.target = LSA_TARGET_MAP;
+  spec.set = LSA_SET_WORKING;
   for (int k = 0; k < 3; ++k)
-    if (UseKeypoints[k]) mask |= 1u << k;
-  auto saturation = [&](unsigned icpIter) {
-    const double iterRatio = icpIter / static_cast<double>(LocalizationICPMaxIter - 1);
-    return (1 - iterRatio) * LocalizationInitSaturationDistance + iterRatio * LocalizationFinalSaturationDistance;
-  };
-  auto configure = [&](LocalOptimizer& optimizer) {
-    optimizer.SetDeviceLoop(DeviceLM);
-    optimizer.SetTwoDMode(TwoDMode);
-    optimizer.SetLMMaxIter(LocalizationLMMaxIter);
-    optimizer.SetMinMatches(MinNbMatchedKeypoints);
-    optimizer.UseDeviceResiduals(7u);
-  };
-  // as in the ego-motion loop: iteration i + 1 behind a gate while iteration i runs.  The undistortion between two
-  // iterations has to ride in the next search kernel for that (a launch of its own would have to be enqueued between
-  // the two, when the motion is known).
-  const bool undistortAhead = Undistortion == UNDISTORTION_REFINED;
-  bool ahead = ICPAhead && DeviceLM && FusedMatch && (!undistortAhead || UndistortInSearch);
-  static const int aheadLoops = std::getenv("LSA_ICP_AHEAD_LOOPS") ? std::atoi(std::getenv("LSA_ICP_AHEAD_LOOPS")) : 3;
-  ahead = ahead && (aheadLoops & 2);
-  // (ICPAhead = 2: the whole loop behind links, see ComputeEgoMotion; the device then also refines the undistortion)
-  bool chain = ahead && ICPAhead >= 2 && LocalizationICPMaxIter <= kChainMax;
-  if (chain) ahead = false;
-  if (ahead || chain) lsa_icp_abandon(Ctx);
-  unsigned chained = 0;
-  long long chainSerial[kChainMax][3] = {};
-  bool enqueued = false;
-  long long aheadSerial[3] = {0, 0, 0};
-  auto callOff = [&](int& ticket) {
-    if (ticket < 0) return;
-    lsa_icp_cancel(Ctx, ticket);
-    lsa_solve_device_drop(Ctx);
-    ticket = -1;
-  };
-  auto matchInLine = [&]() -> int {
-    // the undistortion the previous iteration ended with rides in this iteration's search kernel (same keypoints, one launch less)
-    if (pendingUndistort)
-      LSA_TRY(lsa_match_types_undistorted(Ctx, LSA_TARGET_MAP, mask, &mp, Tworld.m, nullptr, pendingD0.m, pendingD1.m, Motion.Time0, Motion.Time1));
-    else
-      LSA_TRY(lsa_match_types(Ctx, LSA_TARGET_MAP, mask, LSA_SET_WORKING, &mp, Tworld.m, nullptr));
-    pendingUndistort = false;
-    for (int k = 0; k < 3; ++k)
-      if ((mask >> k) & 1u) LocMatchSerial[k] = lsa_match_serial(Ctx, k);
-    return LSA_OK;
-  };
-
-  for (unsigned icpIter = 0; icpIter < LocalizationICPMaxIter; ++icpIter)
+    if (UseKeypoints[k]) spec.matchMask |= 1u << k;
+  spec.solveMask = 7u;
+  spec.maxIter = LocalizationICPMaxIter;
+  spec.lmMaxIter = LocalizationLMMaxIter;
+  spec.initSaturation = LocalizationInitSaturationDistance;
+  spec.finalSaturation = LocalizationFinalSaturationDistance;
+  spec.match = LocMatchParams();
+  spec.loopBit = 2;
+  // The undistortion between two iterations has to ride in the next search kernel for an iteration to be enqueued ahead (a
+  // launch of its own would have to be enqueued between the two, when the motion is known); behind a link the device
+  // refines it itself.
+  spec.linksOk = spec.gatesOk = !refined || UndistortInSearch;
+  spec.undistortAhead = refined ? 1 : 0;
+  spec.link.refine_undistortion = refined ? 1 : 0;
+  spec.link.have_log = LogTrajectory.empty() ? 0 : 1;
+  spec.link.prev_time = LogTrajectory.empty() ? 0. : LogTrajectory.back().time;
+  spec.link.cur_time = StampToSec(CurrentStamp);
+  spec.link.max_extrapolation_ratio = MaxExtrapolationRatio;
+  std::memcpy(spec.link.previous_world, PreviousTworld.m, sizeof(spec.link.previous_world));
   {
-    Tick ticp;
+    double* m = spec.link.motion;
+    m[0] = Motion.Time0; m[1] = Motion.Time1;
+    m[2] = Motion.Rot0.w; m[3] = Motion.Rot0.x; m[4] = Motion.Rot0.y; m[5] = Motion.Rot0.z;
+    m[6] = Motion.Rot1.w; m[7] = Motion.Rot1.x; m[8] = Motion.Rot1.y; m[9] = Motion.Rot1.z;
+    for (int i = 0; i < 3; ++i) { m[10 + i] = Motion.Trans0[i]; m[13 + i] = Motion.Trans1[i]; }
+  }
+  spec.matchSerial = LocMatchSerial;
+  spec.icpSeconds = &FrameStats::loc_icp;
+  spec.lmSeconds = &FrameStats::loc_lm;
+  spec.iterations = &FrameStats::loc_iters;
+  spec.countSkippedEvals = false;
+  auto top = [&](unsigned icpIter) -> int {
     // the keyframe's insertion is handed to the maps' thread right after this loop: awake by then (last iteration: ~0.1 ms ahead)
     if (WorkerPrewake && DeviceMapsInUse() && icpIter + 1 == LocalizationICPMaxIter && MapUpdate != MappingMode::NONE) MapWorker[0].Expect(300e-6);
-    mp.saturation_distance = saturation(icpIter);
-    LocalOptimizer optimizer(Ctx);
-    configure(optimizer);
-    optimizer.SetPosePrior(Tworld);
-    bool begun = enqueued;
-    if (icpIter < chained)
-    {
-      begun = true;
-      for (int k = 0; k < 3; ++k)
-        if ((mask >> k) & 1u) LocMatchSerial[k] = chainSerial[icpIter][k];
-    }
-    else if (!enqueued)
-    {
-      LSA_TRY(matchInLine());
-      if (chain)
-      {
-        double prior[6];
-        ToXYZRPY(Tworld, prior);
-        lsa_icp_link_t link;
-        std::memset(&link, 0, sizeof(link));
-        link.refine_undistortion = undistortAhead ? 1 : 0;
-        link.have_log = LogTrajectory.empty() ? 0 : 1;
-        link.prev_time = LogTrajectory.empty() ? 0. : LogTrajectory.back().time;
-        link.cur_time = StampToSec(CurrentStamp);
-        link.max_extrapolation_ratio = MaxExtrapolationRatio;
-        std::memcpy(link.previous_world, PreviousTworld.m, sizeof(link.previous_world));
-        {
-          double* m = link.motion;
-          m[0] = Motion.Time0; m[1] = Motion.Time1;
-          m[2] = Motion.Rot0.w; m[3] = Motion.Rot0.x; m[4] = Motion.Rot0.y; m[5] = Motion.Rot0.z;
-          m[6] = Motion.Rot1.w; m[7] = Motion.Rot1.x; m[8] = Motion.Rot1.y; m[9] = Motion.Rot1.z;
-          for (int i = 0; i < 3; ++i) { m[10 + i] = Motion.Trans0[i]; m[13 + i] = Motion.Trans1[i]; }
-        }
-        for (unsigned j = icpIter; j < LocalizationICPMaxIter; ++j)
-        {
-          int leave = j + 1 < LocalizationICPMaxIter ? lsa_icp_link(Ctx) : -1;
-          if (leave < 0) leave = -1;
-          link.first = j == icpIter ? 1 : 0;
-          const int rc = lsa_solve_device_begin_linked(Ctx, 7u, j == icpIter ? prior : nullptr, TwoDMode ? 1 : 0, static_cast<int>(LocalizationLMMaxIter), static_cast<int>(MinNbMatchedKeypoints), leave,
-                                                       leave >= 0 ? &link : nullptr);
-          if (rc < 0) { lsa_icp_abandon(Ctx); return Fail(rc, "lsa_solve_device_begin_linked"); }
-          chained = j + 1;
-          if (leave < 0) break;
-          lsa_match_params_t next = mp;
-          next.saturation_distance = saturation(j + 1);
-          const int mrc = lsa_match_types_gated(Ctx, LSA_TARGET_MAP, mask, LSA_SET_WORKING, &next, undistortAhead ? 1 : 0);
-          if (mrc < 0) { lsa_icp_abandon(Ctx); return Fail(mrc, "lsa_match_types_gated"); }
-          if (mrc != 0) { lsa_icp_cancel(Ctx, leave); break; }
-          for (int k = 0; k < 3; ++k)
-            if ((mask >> k) & 1u) chainSerial[j + 1][k] = lsa_match_serial(Ctx, k);
-        }
-        chain = false;
-        begun = true;
-      }
-      else if (ahead)
-      {
-        LSA_TRY(optimizer.Begin(false));
-        begun = true;
-      }
-    }
-    else
-      for (int k = 0; k < 3; ++k)
-        if ((mask >> k) & 1u) LocMatchSerial[k] = aheadSerial[k];
-    enqueued = false;
-    int ticket = -1;
-    if (ahead && begun && icpIter + 1 < LocalizationICPMaxIter)
-    {
-      ticket = lsa_icp_gate(Ctx);
-      if (ticket < 0) { ticket = -1; ahead = false; }
-      else
-      {
-        lsa_match_params_t next = mp;
-        next.saturation_distance = saturation(icpIter + 1);
-        int rc = lsa_match_types_gated(Ctx, LSA_TARGET_MAP, mask, LSA_SET_WORKING, &next, undistortAhead ? 1 : 0);
-        if (rc == 0)
-        {
-          for (int k = 0; k < 3; ++k)
-            if ((mask >> k) & 1u) aheadSerial[k] = lsa_match_serial(Ctx, k);
-          rc = lsa_solve_device_begin(Ctx, 7u, nullptr, TwoDMode ? 1 : 0, static_cast<int>(LocalizationLMMaxIter), static_cast<int>(MinNbMatchedKeypoints));
-          if (rc < 0) { lsa_icp_cancel(Ctx, ticket); return Fail(rc, "lsa_solve_device_begin"); }
-        }
-        else
-        {
-          lsa_icp_cancel(Ctx, ticket);
-          ticket = -1;
-          ahead = false;
-          if (rc < 0) return Fail(rc, "lsa_match_types_gated");
-        }
-      }
-    }
-    if (!begun) ArmLookaheadInterlude();
-    Stats.loc_icp += ticp.Stop();
-    Stats.loc_iters++;
-
-    Tick tlm;
-    SolveSummary summary;
-    if (begun)
-    {
-      const int irc = InterludeWork();
-      int rc = optimizer.End(summary);
-      if (rc == LSA_E_GATE)
-      {
-        // (see the ego-motion loop) nothing of the iteration ran: done again in line, the rest of the loop without gates
-        callOff(ticket);
-        lsa_icp_abandon(Ctx);
-        ahead = false;
-        IcpGateTimeouts++;
-        pendingUndistort = postedUndistort;  // (it was to ride in the search that did not run)
-        rc = matchInLine();
-        if (rc == LSA_OK) rc = optimizer.Solve(summary);
-      }
-      if (rc < 0) { callOff(ticket); lsa_icp_abandon(Ctx); return Fail(rc, "LocalOptimizer::Solve (localization)"); }
-      if (rc == 1) { ticket = -1; ahead = false; chained = 0; }
-      if (irc < 0) { callOff(ticket); return irc; }
-    }
-    else
-    {
-      LSA_TRY(optimizer.Solve(summary));
-      LSA_TRY(FinishLookaheadInterlude());
-    }
-    TotalMatchedKeypoints = summary.num_matches;
-    if (lsa_icp_trace_on())
-      std::fprintf(stderr, "[icp] frame %u loc %u: matches %d evals %d steps %d cost %.17g -> %.17g%s\n", NbrFrameProcessed, icpIter, summary.num_matches, summary.num_evaluations,
-                   summary.num_successful_steps, summary.initial_cost, summary.final_cost, summary.skipped ? " skipped" : "");
-    if (summary.skipped)
-    {
-      // reset state to previous one to avoid instability (Slam.cxx:1098-1107)
-      callOff(ticket);
-      if (icpIter + 1 < chained) lsa_icp_abandon(Ctx);  // (the device has left go = 0 for them)
-      Trelative = Pose::Identity();
-      Tworld = PreviousTworld;
-      if (Undistortion) Motion.SetTransforms(Pose::Identity(), Pose::Identity());
-      LastError = "Not enough keypoints matched, Localization skipped for this frame.";
-      Stats.loc_lm += tlm.Stop();
-      break;
-    }
-    Stats.lm_evals += summary.num_evaluations;
-    Tworld = optimizer.GetOptimizedPose();
+    return LSA_OK;
+  };
+  auto skipped = [&]() -> int {
+    // reset state to previous one to avoid instability (Slam.cxx:1098-1107)
+    Trelative = Pose::Identity();
+    Tworld = PreviousTworld;
+    if (Undistortion) Motion.SetTransforms(Pose::Identity(), Pose::Identity());
+    LastError = "Not enough keypoints matched, Localization skipped for this frame.";
+    return LSA_OK;
+  };
+  auto accepted = [&](bool last, IcpUndistortion& undistortion) -> int {
     Trelative = Inverse(PreviousTworld) * Tworld;
-    const bool lastIteration = (summary.num_successful_steps == 1) || (icpIter == LocalizationICPMaxIter - 1);
-    if (lastIteration) callOff(ticket);  // nothing more to search: what follows on the stream does not wait behind the gate
-    if (lastIteration && icpIter + 1 < chained) lsa_icp_abandon(Ctx);  // (links: the device has decided the same)
-    if (Undistortion == UNDISTORTION_REFINED)
+    if (!refined) return LSA_OK;
+    if (UndistortInSearch && !last)
     {
-      if (UndistortInSearch && !lastIteration)
-      {
-        RefineUndistortion(&pendingD0, &pendingD1);
-        pendingUndistort = true;
-      }
-      else
-      {
-        int rc = RefineUndistortion();
-        if (rc < 0) { callOff(ticket); return rc; }
-      }
+      undistortion.pending = true;
+      return RefineUndistortion(&undistortion.d0, &undistortion.d1);
     }
-    Stats.loc_lm += tlm.Stop();
-    if (lastIteration)
-    {
-      Tick terr;
-      LSA_TRY(optimizer.EstimateRegistrationError(LocalizationUncertainty));
-      DbgAcc[4] += terr.Stop();
-      break;
-    }
-    if (ticket >= 0)
-    {
-      double prior[6];
-      ToXYZRPY(Tworld, prior);  // LocalOptimizer::SetPosePrior of the next iteration
-      const int rc = lsa_icp_post(Ctx, ticket, Tworld.m, prior, pendingUndistort ? pendingD0.m : nullptr, pendingUndistort ? pendingD1.m : nullptr, Motion.Time0, Motion.Time1);
-      if (rc < 0) return Fail(rc, "lsa_icp_post");
-      postedUndistort = pendingUndistort;
-      pendingUndistort = false;
-      enqueued = true;
-    }
-    else if (icpIter + 1 < chained)
-      pendingUndistort = false;  // the next search is in the queue and undistorts with what the device worked out (the same)
-  }
-  if (KeepMatchDebug)
-    for (int k = 0; k < 3; ++k)
-    {
-      const int n = lsa_keypoint_count(Ctx, LSA_SET_WORKING, k);
-      LocDebug[k].status.assign(n, LSA_MATCH_UNKOWN);
-      LocDebug[k].weights.assign(n, 0.);
-      if (n > 0) LSA_TRY(lsa_download_match(Ctx, k, LocDebug[k].status.data(), LocDebug[k].weights.data(), nullptr, n));
-    }
+    return RefineUndistortion();
+  };
+  auto finished = [&](LocalOptimizer& optimizer) -> int {
+    Tick terr;
+    LSA_TRY(optimizer.EstimateRegistrationError(LocalizationUncertainty));
+    DbgAcc[4] += terr.Stop();
+    return LSA_OK;
+  };
+  if (const int rc = RunIcpLoop(spec, Tworld, top, kNothing, kNothing, skipped, accepted, finished); rc < 0) return rc;
+  if (KeepMatchDebug) return DownloadMatchDebug(LSA_SET_WORKING, 7u, LocDebug);
   return LSA_OK;
 }
 

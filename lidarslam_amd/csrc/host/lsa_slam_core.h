@@ -262,6 +262,14 @@ private:
   int ExtractKeypoints();
   int ComputeEgoMotion();
   int Localization();
+  // The ICP loop of both, under whichever schedule ICPAhead allows (lsa_slam_core.cpp): the spec says what the loop
+  // matches and solves, the callables what only one of the two does at that point of an iteration.
+  struct IcpLoopSpec;
+  struct IcpUndistortion;
+  template <class Top, class Enqueued, class Solved, class Skipped, class Accepted, class Finished>
+  int RunIcpLoop(const IcpLoopSpec& spec, Pose& pose, const Top& top, const Enqueued& enqueued, const Solved& solved, const Skipped& skipped,
+                 const Accepted& accepted, const Finished& finished);
+  int DownloadMatchDebug(int set, unsigned typeMask, MatchDebug* debug);
   SensorConstraints SensorManagers;
   lsa_sensor_terms_t LocSensorTerms = {};
   int UpdateMapsUsingTworld();

@@ -493,7 +493,11 @@ int lsa_icp_link_peek(lsa_ctx* ctx, int ticket, unsigned long long words[64]);
 int lsa_icp_link_expected(const double x[6], int skipped, int successful_steps, const lsa_icp_link_t* link, unsigned long long words[64], double motion_after[16]);
 
 /* Diagnostics (LSA_ROUTE_STATS=1): 100 MHz ticks block 0 spent evaluating, exchanging, folding, stepping, summed over
- * the solves so far; [4] evaluations, [5] ticks inside the kernel, [6] solves. */
+ * the solves so far; [4] evaluations, [5] ticks inside the kernel, [6] solves, [7] of evaluating: the residual blocks alone,
+ * [8..11] of stepping: decision, scaled system, Cholesky solve, model change and candidate.  All 12 slots keep their
+ * meaning from build to build; a part a later kernel no longer has reads 0.  As k_lm_solve stands: "exchanging" ends when
+ * thread 0 holds its own granules of every workgroup, "folding" is its sums, the 8-lane addition, the one barrier behind them
+ * and the sensor terms; "stepping" no longer holds the rotation derivatives of a point past the end of the solve. */
 int lsa_solve_device_trace(lsa_ctx* ctx, unsigned long long out[12]);
 /* Test hooks for the two bounded waits on the device, so that the callers' fall-backs can be exercised:
  *   "gate_give_up_every" n   every n-th gate (lsa_icp_gate) gives up at once, as if the host had not answered in 50 ms

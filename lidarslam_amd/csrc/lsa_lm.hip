@@ -11,8 +11,10 @@
 //     ONE relaxed agent-scope atomic store / load (MI355X: `sc1`, write-through past the non-coherent per-XCD
 //     L2s): tag and payload are one memory object, so no fence, flag or ordering between locations is needed.
 //     Two parities of slots: a block can be at most one evaluation ahead of the slowest;
-//   * EVERY block folds all partial sums in block order and runs the 6x6 trust-region algebra itself -- same
-//     inputs, same instructions, same result in every block -- so the next candidate needs no broadcast;
+//   * EVERY block folds all partial sums in a fixed order -- 8 partial sums per value over the blocks j, j + 8, ..., then
+//     the 8 in order; wavefront j reads the granules of its blocks and sums them itself: no copy of the granules in LDS,
+//     one barrier between publishing and the step -- and runs the 6x6 trust-region algebra itself: same inputs, same
+//     instructions, same result in every block, so the next candidate needs no broadcast;
 //   * block 0 hands pose, summary and the normal equations at the final point to the host through the same
 //     kind of granules in coherent host memory.
 // The arithmetic of the trust-region step is the host loop's, operation for operation (no FMA contraction, IEEE
@@ -89,8 +91,7 @@ struct LmState
 struct Shared
 {
   double wsum[kLmThreads / 64][kAccumVals];
-  unsigned gat[kLmBlocksMax][2 * kAccumVals];  // halves of every block's partial sums
-  double part[kAccumVals][8];
+  double part[kAccumVals][8];  // the fold's 8 partial sums per value, a wavefront each
   // The sums over ALL residual blocks, twice: at the current point, and of the evaluation under way / just done.  A step that
   // is accepted makes the second the first by flipping LmState::cur_buf (29 values that one thread no longer copies).
   double sums[2][kAccumVals];
@@ -111,8 +112,14 @@ __device__ __forceinline__ double uniform(double v)
   return __longlong_as_double(((long long)hi << 32) | (long long)(unsigned)lo);
 }
 
-// One evaluation at sh.w / sh.rot: sh.sums[1 - cur_buf][] = the 29 sums over ALL residual blocks, identical in every block.
-// Returns false when a spin ran out (uniform over the block).
+// the value another lane of the wavefront holds
+__device__ __forceinline__ double lane_value(double v, int lane)
+{
+  const long long b = __double_as_longlong(v);
+  const int lo = __shfl((int)(b & 0xffffffffll), lane), hi = __shfl((int)(b >> 32), lane);
+  return __longlong_as_double(((long long)hi << 32) | (long long)(unsigned)lo);
+}
+
 __device__ __forceinline__ void lm_lap(Shared& sh, int slot)
 {
   if (threadIdx.x == 0)
@@ -131,6 +138,8 @@ __device__ __noinline__ void lm_sensor_terms(const lsa_sensor_terms_t* terms, Sh
   sensor_terms_add(*terms, sh.w, sh.rot, sh.rot + 9, sh.rot + 18, sh.rot + 27, true, sh.sums[1 - sh.lm.cur_buf]);
 }
 
+// One evaluation at sh.w / sh.rot: sh.sums[1 - cur_buf][] = the 29 sums over ALL residual blocks, identical in every block.
+// Returns false when a spin ran out (uniform over the block).  One barrier between publishing the block's sums and the step.
 __device__ __forceinline__ bool lm_evaluate(const LmParams& p, unsigned epoch, u64* __restrict__ xchg, Shared& sh, double* __restrict__ cache, bool trace)
 {
   {
@@ -167,75 +176,67 @@ __device__ __forceinline__ bool lm_evaluate(const LmParams& p, unsigned epoch, u
     const unsigned word = half ? (unsigned)(bits >> 32) : (unsigned)(bits & 0xffffffffull);
     __hip_atomic_store(slots + (size_t)blockIdx.x * kMailboxStride + threadIdx.x, ((u64)tag << 32) | word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   }
-  // gather: every thread sweeps its granules, a batch of loads in flight together, until every tag matches
-  const int total = nb * 2 * kAccumVals;
+  // gather and fold, straight from the granules.  The fold's order is fixed: 8 partial sums per value, partial j over the
+  // blocks b = j, j + 8, ... in ascending b starting from 0, then the 8 in the order ((p0 + p1) + p2) + ...  Wavefront j
+  // of the 8 works out partial j of all 29 values: its lane s < 58 loads granule s of its blocks -- one load of a wavefront
+  // is one block's 464 contiguous bytes, kFoldBatch of them in flight together -- again and again until every tag
+  // matches; the even lane 2v takes the upper half of value v from its neighbour (a DPP move) and sums.  Only the 8 x 29
+  // partial sums pass through LDS, and the one barrier of the exchange stands behind them.
+  static_assert(kLmThreads / 64 == 8, "a wavefront per partial sum of the fold");
   bool failed = (int)blockIdx.x == p.give_up_block;  // (test hook: as if this workgroup had waited too long)
   {
+    constexpr int kFoldBatch = 8;
+    const int j = threadIdx.x >> 6, s = threadIdx.x & 63;
+    const bool loads = s < 2 * kAccumVals;
+    const u64* mine = slots + s;
+    double sum = 0.;
     const unsigned long long t0 = wall_clock64();
     unsigned spins = 0;
-    for (int base = threadIdx.x; base < total && !failed; base += 8 * kLmThreads)
+    for (int b0 = j; b0 < nb; b0 += 8 * kFoldBatch)
     {
-      while (true)
+      u64 x[kFoldBatch];
+#pragma unroll
+      for (int k = 0; k < kFoldBatch; ++k) x[k] = 0ull;
+      while (loads && !failed)
       {
+#pragma unroll
+        for (int k = 0; k < kFoldBatch; ++k)
+          if (b0 + 8 * k < nb) x[k] = __hip_atomic_load(mine + (size_t)(b0 + 8 * k) * kMailboxStride, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         bool ok = true;
-        u64 x[8];
 #pragma unroll
-        for (int k = 0; k < 8; ++k)
-        {
-          const int g = base + k * kLmThreads;
-          if (g < total)
-          {
-            const int b = g / (2 * kAccumVals), s = g - b * (2 * kAccumVals);
-            x[k] = __hip_atomic_load(slots + (size_t)b * kMailboxStride + s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          }
-        }
-#pragma unroll
-        for (int k = 0; k < 8; ++k)
-        {
-          const int g = base + k * kLmThreads;
-          if (g < total)
-          {
-            if ((unsigned)(x[k] >> 32) == tag)
-            {
-              const int b = g / (2 * kAccumVals), s = g - b * (2 * kAccumVals);
-              sh.gat[b][s] = (unsigned)(x[k] & 0xffffffffull);
-            }
-            else ok = false;
-          }
-        }
+        for (int k = 0; k < kFoldBatch; ++k)
+          if (b0 + 8 * k < nb && (unsigned)(x[k] >> 32) != tag) ok = false;
         if (ok) break;
         // 100 MHz clock: 20 ms without the other blocks' sums (they are not resident, or gave up themselves)
         if ((++spins & 15u) == 0 && wall_clock64() - t0 > 2000000ull) { failed = true; break; }
         __builtin_amdgcn_s_sleep(2);
       }
-      if (failed) break;
+      // all lanes again: lane 2v + 1 holds the upper half of what lane 2v holds the lower half of (quad_perm [1, 1, 3, 3])
+#pragma unroll
+      for (int k = 0; k < kFoldBatch; ++k)
+      {
+        const unsigned lo = (unsigned)(x[k] & 0xffffffffull);
+        const unsigned hi = (unsigned)__builtin_amdgcn_update_dpp(0, (int)lo, 0xF5, 0xf, 0xf, false);
+        if (b0 + 8 * k < nb) sum += __longlong_as_double((long long)(((u64)hi << 32) | lo));
+      }
     }
+    if (trace) lm_lap(sh, 1);
+    // (a lane that gave up, or whose neighbour did, holds no sum -- and no sum is used then)
+    if (loads && (s & 1) == 0) sh.part[s >> 1][j] = sum;
   }
   if (failed) atomicOr(&sh.failed, 1);
   __syncthreads();
-  if (trace) lm_lap(sh, 1);
   if (sh.failed) return false;
-  // fold in a fixed order: 8 partial sums per value over the blocks b = j, j + 8, ..., then the 8 in order
-  if (threadIdx.x < kAccumVals * 8)
-  {
-    const int v = threadIdx.x >> 3, j = threadIdx.x & 7;
-    double s = 0.;
-    for (int b = j; b < nb; b += 8)
-    {
-      const u64 bits = ((u64)sh.gat[b][2 * v + 1] << 32) | sh.gat[b][2 * v];
-      s += __longlong_as_double((long long)bits);
-    }
-    sh.part[v][j] = s;
-  }
-  __syncthreads();
+  // the 8 partial sums of a value in order, by the first wavefront -- the one that reads the sums next (the sensor terms,
+  // lm_step: the LDS operations of one wavefront are served in order), so no barrier follows
   if (threadIdx.x < kAccumVals)
   {
-    double s = sh.part[threadIdx.x][0];
+    double r = sh.part[threadIdx.x][0];
 #pragma unroll
-    for (int j = 1; j < 8; ++j) s += sh.part[threadIdx.x][j];
-    sh.sums[1 - sh.lm.cur_buf][threadIdx.x] = s;
+    for (int i = 1; i < 8; ++i) r += sh.part[threadIdx.x][i];
+    sh.sums[1 - sh.lm.cur_buf][threadIdx.x] = r;
   }
-  __syncthreads();
+  if (threadIdx.x < 64) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
   // the sensor terms on top of the fold, the same arithmetic in every block; lane 0 of the first wavefront, which is the
   // one that reads the sums next (lm_step: its LDS operations are served in order).  One uniform branch.
   if (p.sensors_on && threadIdx.x == 0)
@@ -261,12 +262,6 @@ __device__ __forceinline__ void set_point(Shared& sh, const double w[6])
 {
 #pragma unroll
   for (int a = 0; a < 6; ++a) sh.w[a] = w[a];
-}
-__device__ __forceinline__ double lane_value(double v, int lane)
-{
-  const long long b = __double_as_longlong(v);
-  const int lo = __shfl((int)(b & 0xffffffffll), lane), hi = __shfl((int)(b >> 32), lane);
-  return __longlong_as_double(((long long)hi << 32) | (long long)(unsigned)lo);
 }
 // sh.rot = rotation and derivatives at sh.w (CeresCostFunctions.h:67-79).  The first wavefront runs it, all lanes: the
 // three cosines and three sines -- a few hundred dependent instructions each, the longest part of what lies between two
@@ -631,7 +626,10 @@ __global__ __launch_bounds__(kLmThreads) void k_lm_solve(LmParams p, u64* __rest
       if (threadIdx.x == 0 && tr) sh.st0 = wall_clock64();
       if (p.two_d) lm_step<3>(p, sh, epoch == 1);
       else lm_step<6>(p, sh, epoch == 1);
-      finish_point(sh);
+      // the candidate's rotation and derivatives -- unless the solve is over: nobody evaluates at sh.w then, and neither
+      // the result nor the link reads sh.w or sh.rot (they take the pose from LmState::x)
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // sh.stop was written by lane 0 of this wavefront
+      if (!sh.stop) finish_point(sh);
     }
     __syncthreads();
     if (tr) lm_lap(sh, 3);
@@ -740,9 +738,9 @@ int lm_blocks_share()
 }
 InterpConst make_interp_const(const double H0[16], const double H1[16], double t0, double t1);  // lsa_transform.hip
 // how many layers of residual blocks (a layer: one block per thread, 17 * kLmThreads doubles = 68 KiB) the solve kernel
-// may keep in LDS beside its own static data (Shared, 34 912 B).  A layer is counted only when the runtime accepts it as
-// dynamic LDS AND static + dynamic fit the LDS a workgroup may have (160 KiB on gfx950: one layer): whether the runtime's
-// check counts the static part is not something to rely on.
+// may keep in LDS beside its own static data (Shared, 3 360 B).  A layer is counted only when the runtime accepts it as
+// dynamic LDS AND static + dynamic fit the LDS a workgroup may have (160 KiB on gfx950: two layers, since the fold no
+// longer keeps the granules in LDS): whether the runtime's check counts the static part is not something to rely on.
 int lm_cache_capacity()
 {
   const size_t layer = (size_t)17 * kLmThreads * sizeof(double);
@@ -824,7 +822,7 @@ static int solve_device_begin(lsa_ctx* ctx, unsigned type_mask, const double pri
   // other contexts of this process run beside this one -- as many at once as the process has hardware queues
   const int nb = std::min(std::max((total + ctx->lm_records - 1) / ctx->lm_records, 1), std::min(std::min(ctx->lm_blocks, kLmBlocksMax), lm_blocks_share()));
   // the thread's first residual blocks stay in LDS between the evaluations (17 doubles each): as many per thread as
-  // the block's share needs, as many as the LDS holds beside the kernel's own 34 KB (the rest is read again)
+  // the block's share needs, as many as the LDS holds beside the kernel's own 3 KB (the rest is read again)
   const int per_thread = (total + nb * kLmThreads - 1) / (nb * kLmThreads);
   const size_t slot_bytes = (size_t)17 * kLmThreads * sizeof(double);
   p.cslots = std::min(per_thread, std::max(ctx->lm_cache_slots, 0));

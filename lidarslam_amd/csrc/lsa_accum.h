@@ -1,5 +1,5 @@
 // lsa_accum.h -- what Ceres evaluates per LM step for one residual block, shared by the two kernels
-// that evaluate it: k_accumulate (one evaluation per launch, host-driven trust region, lsa_match.hip)
+// that evaluate it: k_accumulate (one evaluation per launch, host-driven trust region, lsa_accumulate.hip)
 // and k_lm_solve (the whole LocalOptimizer::Solve in one launch, lsa_lm.hip).
 //
 //   residual   r = A (R(rpy) X + t - P)              slam_lib/include/LidarSlam/CeresCostFunctions.h:105-152

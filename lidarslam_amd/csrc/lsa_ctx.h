@@ -279,7 +279,7 @@ struct lsa_ctx
   int knn_lanes[3] = {16, 8, 8};
   int knn_rounds[3] = {2, 2, 2};
   // lsa_match_types as one launch for all types, search and model fit fused (lsa_match_fused.hip); off: the staged
-  // kernels of lsa_match.hip, types side by side on streams (same results, kept for comparison)
+  // kernels of lsa_match_staged.hip, types side by side on streams (same results, kept for comparison)
   bool fused_match = true;
   bool fused_model = true;  // ... and the search kernel fits the models of its own keypoints (one launch instead of two)
   void* trace_dev = nullptr;  // LSA_ROUTE_STATS: 4 x 8 bytes per hardware block of the last fused match (lsa_match_trace)
@@ -371,7 +371,7 @@ int transform_sets_to(lsa_ctx* ctx, const lsa_point_t* const src[3], const int n
 int time_from_advancement(lsa_ctx* ctx, lsa_point_t* frame, int n, double rpm, int first_packet);  // lsa_extract.hip
 int ensure_capacity(lsa_ctx* ctx, int n);
 int ensure_target(lsa_ctx* ctx, int ti, int m);
-int build_target_grids(lsa_ctx* ctx, const int* tis, int count, hipStream_t st);  // lsa_match.hip: the search grids of these targets, one chain of launches
+int build_target_grids(lsa_ctx* ctx, const int* tis, int count, hipStream_t st);  // lsa_target.hip: the search grids of these targets, one chain of launches
 int ensure_match(lsa_ctx* ctx, int type, int k);
 int ensure_scratch(lsa_ctx* ctx, size_t bytes);
 int enqueue_time_range(lsa_ctx* ctx, int set, const int* counts_dev);

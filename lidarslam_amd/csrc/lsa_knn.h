@@ -1,5 +1,5 @@
-// lsa_knn.h -- device-side pieces shared by the matching kernels (lsa_match.hip: staged kNN + model kernels, the
-// overlap estimator; lsa_match_fused.hip: one launch per ICP iteration): the view of a target's search grid, the
+// lsa_knn.h -- device-side pieces shared by the matching kernels (lsa_match_staged.hip: staged kNN + model kernels;
+// lsa_match_fused.hip: one launch per ICP iteration; lsa_target.hip: the grid build): the view of a target's search grid, the
 // 64-bit (distance, index) candidate key and its group minimum, and the per-keypoint model fit.
 #pragma once
 #include <cfloat>
@@ -56,13 +56,6 @@ struct GridPtrs
 // kKnnFar when the search proved that the k-th neighbour lies beyond far_d2 (plane / blob matches only
 // need to know that: KeypointsMatcher.cxx:217, 303 reject them as NEIGHBORS_TOO_FAR whatever they are).
 constexpr int kKnnFar = -1;
-// Selection-based search (k_knn_first / k_knn_second).  G lanes cooperate on one query.  The rows of the
-// block of cells being searched are contiguous runs of the cell-sorted array; their bounds are fetched by
-// as many lanes at once, flattened with a group prefix sum, and the candidates are dealt to the lanes evenly,
-// U per lane and batch, all loads in flight together.  The k best of (previous best + batch) are then PICKED:
-// k rounds of "group minimum by (distance, index), owner retires it".  Every lane executes the same
-// instructions whatever its candidates are -- no per-lane sorted lists, no divergent insertion, no merge
-// tree -- and the result sits in registers that are uniform across the group.
 
 // A candidate is ONE 64-bit key: the squared distance's bits above, the target index below.  Distances are
 // sums of squares (never negative, never NaN for finite points), so unsigned order of the key IS the search's

@@ -4,7 +4,7 @@
 // (KDTreePCLAdaptor::KnnSearch, slam_lib/include/LidarSlam/KDTreePCLAdaptor.h:79-105) and the model fit
 // (KeypointsMatcher.cxx:106-346) of a keypoint in the same kernel, the neighbour lists never leave the chip.
 //
-// Search.  The target is indexed by a dense grid at three resolutions (cell, 4 x, 16 x; lsa_match.hip builds it).
+// Search.  The target is indexed by a dense grid at three resolutions (cell, 4 x, 16 x; lsa_target.hip builds it).
 // A spinning-LiDAR cloud spans three orders of magnitude in density, so no single block size suits every query:
 // G lanes share a query and pick the block to search from the CELL COUNTS alone -- the blocks
 //   shell 0..6 = (level 0, 3^3 cells) (0, 5^3) (1, 3^3) (1, 5^3) (2, 3^3) (2, 5^3) (2, 7^3)

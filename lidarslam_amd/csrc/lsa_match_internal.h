@@ -1,5 +1,6 @@
-// lsa_match_internal.h -- what lsa_match.hip (targets, staged kernels, C ABI) and lsa_match_fused.hip (one launch
-// per ICP iteration) share on the host side.
+// lsa_match_internal.h -- what the files of the matching step share on the host side: lsa_match.hip (C ABI),
+// lsa_match_fused.hip (one launch per ICP iteration), lsa_match_staged.hip (staged cross-check), lsa_target.hip (search
+// grids) and lsa_overlap.hip.
 #pragma once
 #include "lsa_knn.h"
 
@@ -19,10 +20,16 @@ struct MatchPrep
 };
 
 struct InterpConst;
+InterpConst make_interp_const(const double H0[16], const double H1[16], double t0, double t1);  // lsa_transform.hip
 // undistort: every keypoint is first moved by that motion interpolated at its own time, in place (lsa_undistort's step, folded
 // into the search kernel); only when every keypoint of the set is among `preps` and is searched
 // gate >= 0: the launch waits behind that gate (lsa_icp_gate) and takes pose -- and, gate_undistorts, the undistortion -- from it
 int enqueue_fused_match(lsa_ctx* ctx, const MatchPrep* preps, int count, const double pose[16], hipStream_t st, const InterpConst* undistort = nullptr,
                         int gate = -1, bool gate_undistorts = false);
+// lsa_match_staged.hip: one prepared match as the staged kernels; the exact kNN alone (k <= 5, 8, 16: three instantiations)
+void enqueue_staged_match(lsa_ctx* ctx, const MatchPrep& mp, const double pose[16], hipStream_t st);
+void enqueue_staged_knn(lsa_ctx* ctx, const lsa_point_t* q, int nq, const Rigid& pose, int k, float far_d2, int type, int ti, hipStream_t st, int* hist);
+int flush_grids(lsa_ctx* ctx);                                              // lsa_target.hip: builds the grids of every target marked dirty
+int next_hist_block(lsa_ctx* ctx, int type, hipStream_t st, int** hist);    // lsa_match.hip: the type's next block of the histogram ring
 
 }  // namespace lsa

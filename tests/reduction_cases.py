@@ -16,7 +16,7 @@ formed by any tree of floating-point additions in which no term passes through m
 numbers are exact, so underflow adds nothing).  fsum = fl(sum t_i) = (sum t_i) / (1 + delta), |delta| <= u, so
 |fsum - sum t_i| <= u |fsum|, and together
     |S_dev - fsum| <= gamma_d * sum_i |t_i| + u * |fsum|.
-d is read from the code (lsa_accum.h, lsa_match.hip, lsa_lm.hip):
+d is read from the code (lsa_accum.h, lsa_accumulate.hip, lsa_lm.hip):
   k_lm_solve    per_thread (the thread's own blocks, acc starts at 0), 6 (wave_reduce_accum: permlane32 swap, permlane16
                 swap, row_ror:8, row_half_mirror, two quad_perms), 7 (the 8 wavefronts in LDS), ceil(nb / 8) (the
                 strided fold b = j, j + 8, ... from 0), 7 (the 8 partials);

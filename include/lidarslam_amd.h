@@ -773,6 +773,21 @@ int lsa_slam_add_gravity_measurement(lsa_slam* s, double time, const double acc[
 int lsa_slam_clear_sensor_measurements(lsa_slam* s);
 /* the sensor terms the last frame's localization solved with (both flags 0: none) */
 int lsa_slam_sensor_terms(const lsa_slam* s, lsa_sensor_terms_t* out);
+/* The keypoint maps as PCD files (Slam::SaveMapsToPCD / LoadMapsFromPCD, Slam.cxx:504-543; formats: PCDFormat,
+ * PointCloudStorage.h:60-65), one file per keypoint type: <prefix>edges.pcd, <prefix>planes.pcd, <prefix>blobs.pcd.
+ * - lsa_slam_save_maps_pcd writes GetMap(k, filtered) of every keypoint type in use; an empty map writes no file.
+ * - lsa_slam_load_maps_pcd: ClearMaps first when reset_maps != 0; then every file that exists goes into its map as ONE
+ *   RollingGrid::Add(cloud, fixed, time) -- fixed when "MapUpdate" is NONE or ADD_KPTS_TO_FIXED_MAP, time < 0 = the wall
+ *   clock in whole seconds (std::time(nullptr)); a file that does not exist leaves its map alone, a malformed one is an error.
+ * - lsa_slam_add_map_points: that Add for points of the caller's (what the loader sits on).
+ * All wait for the map workers, as the map getters do; the two that change a map drop what the look-ahead had prepared from
+ * the maps as they were.  With the maps on the device (the default) a file is converted on the device
+ * (lsa_device_grid_add_pcd / _save_pcd); with "MapsOnDevice" = 0 on the host.
+ * - lsa_slam_map_io_counts: points per type of the last save / load, -1 where no file was written / found. */
+int lsa_slam_add_map_points(lsa_slam* s, int type, const lsa_point_t* pts, int n, int fixed, double time);
+int lsa_slam_save_maps_pcd(lsa_slam* s, const char* prefix, int format, int filtered);
+int lsa_slam_load_maps_pcd(lsa_slam* s, const char* prefix, int reset_maps, double time);
+int lsa_slam_map_io_counts(const lsa_slam* s, int counts[3]);
 
 
 /* ------------------------------------------------------------------------- */
@@ -853,6 +868,20 @@ int lsa_device_grid_submap_ahead_take(lsa_device_grid* g, int box_type, int min_
  * comparison is on its way, 0 when nothing fits; _take_end waits for it. */
 int lsa_device_grid_submap_ahead_take_begin(lsa_device_grid* g, int box_type, int min_nb_points, int slot, int type);
 int lsa_device_grid_submap_ahead_take_end(lsa_device_grid* g, int* taken);
+/* A PCD file into the map and the map into a PCD file; the conversion between the file's records and LidarPoints runs on
+ * the device (k_pcd_decode / k_pcd_encode), ascii text and the LZF stage on the host.
+ * - lsa_device_grid_add_pcd = RollingGrid::Add(the file's cloud, fixed, time, roll_first), the whole file as ONE Add; the
+ *   data section goes up in pieces through pinned staging on the context's copy stream, piece i is converted while piece
+ *   i + 1 is uploaded.  A malformed file: LSA_E_ARG, lsa_last_error names the file and the line.
+ * - lsa_device_grid_save_pcd writes RollingGrid::Get(clean) in the order lsa_device_grid_get hands it out; returns the
+ *   number of points written: 0, and no file, when there is none (an empty cloud is not saved, PointCloudStorage.h:91-92);
+ *   every failure -- a path that cannot be written among them -- is negative and lsa_last_error names the file.
+ * - lsa_pcd_io_times: seconds of the context's last load / save: [0] file, [1] LZF, [2] text, [3] pieces on their way
+ *   (upload or download + conversion), [4] the grid's Add / Get, [5] bytes moved, [6] points; [3] and [4] wait for the
+ *   device only while profiling is on (scopes "pcd_upload", "pcd_decode", "pcd_encode", "map_add"). */
+int lsa_device_grid_add_pcd(lsa_device_grid* g, const char* path, int fixed, double time, int roll_first);
+int lsa_device_grid_save_pcd(lsa_device_grid* g, const char* path, int format, int clean);
+int lsa_pcd_io_times(const lsa_ctx* ctx, double out[8]);
 
 /* ---- the rolling voxel map (host) ---------------------------
  * LidarSlam::RollingGrid -- slam_lib/include/LidarSlam/RollingGrid.h:63-212,
@@ -883,6 +912,27 @@ int lsa_rolling_grid_build_submap(lsa_rolling_grid* g, const float min_point[3],
 /* IsSubMapKdTreeValid / GetSubMap */
 int lsa_rolling_grid_submap_valid(const lsa_rolling_grid* g);
 int lsa_rolling_grid_submap(const lsa_rolling_grid* g, lsa_point_t* out, int capacity);
+
+/* ------------------------------------------------------------------------- */
+/* PCD v0.7 files of LidarPoint clouds; host only, no GPU.  Written from the format's description (no PCL): header entries
+ * VERSION FIELDS SIZE TYPE COUNT WIDTH HEIGHT VIEWPOINT POINTS DATA and # comments; DATA ascii, binary (packed records),
+ * binary_compressed (two uint32 -- compressed size, raw size -- then an LZF stream of the columns, field after field).
+ * Reading takes any field order, ignores fields a LidarPoint does not have, gives 0 to those the file does not have, and
+ * converts types I / U / F of sizes 1, 2, 4, 8 as C++ converts them; only COUNT 1 fields are used, the others are skipped
+ * by their width; w = 1.  Writing emits x y z time intensity laser_id device_id label (SIZE 4 4 4 8 4 2 1 1, TYPE F F F F
+ * F U U U: 28-byte records); ascii values are printed so that they read back to the same bits.
+ * format: 0 ascii, 1 binary, 2 binary_compressed (PCDFormat, PointCloudStorage.h:60-65).
+ * - lsa_pcd_info: number of points and format.  lsa_pcd_read: returns the file's number of points, writes at most
+ *   `capacity`.  Both: LSA_E_ARG for a malformed file, lsa_pcd_last_error() (of the calling thread) names file and line.
+ * - lsa_pcd_write: 0; -3 and no file for an empty cloud, -4 for an unknown format (savePointCloudToPCD).
+ * - lsa_lzf_compress / _decompress: the LZF stage on its own; *written = bytes produced (_compress: also when they do not
+ *   fit, with LSA_E_CAPACITY); a malformed stream or one that outgrows `capacity` is LSA_E_ARG. */
+int lsa_pcd_info(const char* path, int* n, int* format);
+int lsa_pcd_read(const char* path, lsa_point_t* out, int capacity);
+int lsa_pcd_write(const char* path, const lsa_point_t* pts, int n, int format);
+const char* lsa_pcd_last_error(void);
+int lsa_lzf_compress(const void* in, size_t n, void* out, size_t capacity, size_t* written);
+int lsa_lzf_decompress(const void* in, size_t n, void* out, size_t capacity, size_t* written);
 
 /* ------------------------------------------------------------------------- */
 /* Synthetic spinning-LiDAR sequences; host only, no GPU.      */

@@ -34,7 +34,7 @@ from ._native import (  # noqa: F401
     synth_pose,
 )
 
-__all__ = ["Context", "Slam", "ExtractParams", "MatchParams", "POINT_DTYPE", "lib", "LsaError"]
+__all__ = ["Context", "Slam", "ExtractParams", "MatchParams", "POINT_DTYPE", "lib", "LsaError", "read_pcd", "write_pcd"]
 
 TARGET_MAP, TARGET_PREVIOUS = 0, 1
 
@@ -77,7 +77,13 @@ ABI_SYMBOLS = [
     "lsa_sensors_add_gravity", "lsa_sensors_set_weights", "lsa_sensors_set_time_offset", "lsa_sensors_clear", "lsa_sensors_compute",
     "lsa_sensors_gravity_ref", "lsa_slam_add_wheel_odom_measurement", "lsa_slam_add_gravity_measurement",
     "lsa_slam_clear_sensor_measurements", "lsa_slam_sensor_terms",
+    "lsa_pcd_info", "lsa_pcd_read", "lsa_pcd_write", "lsa_pcd_last_error", "lsa_lzf_compress", "lsa_lzf_decompress",
+    "lsa_device_grid_add_pcd", "lsa_device_grid_save_pcd", "lsa_pcd_io_times",
+    "lsa_slam_add_map_points", "lsa_slam_save_maps_pcd", "lsa_slam_load_maps_pcd", "lsa_slam_map_io_counts",
 ]
+
+PCD_ASCII, PCD_BINARY, PCD_BINARY_COMPRESSED = 0, 1, 2  # PCDFormat (PointCloudStorage.h:60-65)
+PCD_FORMAT_NAMES = ["ascii", "binary", "binary_compressed"]
 
 
 class LsaError(RuntimeError):
@@ -370,6 +376,20 @@ def lib():
     L.lsa_slam_add_gravity_measurement.argtypes = [vp, f64, vp]
     L.lsa_slam_clear_sensor_measurements.argtypes = [vp]
     L.lsa_slam_sensor_terms.argtypes = [vp, vp]
+    L.lsa_pcd_info.argtypes = [C.c_char_p, C.POINTER(i32), C.POINTER(i32)]
+    L.lsa_pcd_read.argtypes = [C.c_char_p, vp, i32]
+    L.lsa_pcd_write.argtypes = [C.c_char_p, vp, i32, i32]
+    L.lsa_pcd_last_error.restype = C.c_char_p
+    L.lsa_pcd_last_error.argtypes = []
+    L.lsa_lzf_compress.argtypes = [vp, C.c_size_t, vp, C.c_size_t, C.POINTER(C.c_size_t)]
+    L.lsa_lzf_decompress.argtypes = [vp, C.c_size_t, vp, C.c_size_t, C.POINTER(C.c_size_t)]
+    L.lsa_device_grid_add_pcd.argtypes = [vp, C.c_char_p, i32, f64, i32]
+    L.lsa_device_grid_save_pcd.argtypes = [vp, C.c_char_p, i32, i32]
+    L.lsa_pcd_io_times.argtypes = [vp, vp]
+    L.lsa_slam_add_map_points.argtypes = [vp, i32, vp, i32, i32, f64]
+    L.lsa_slam_save_maps_pcd.argtypes = [vp, C.c_char_p, i32, i32]
+    L.lsa_slam_load_maps_pcd.argtypes = [vp, C.c_char_p, i32, f64]
+    L.lsa_slam_map_io_counts.argtypes = [vp, vp]
     _lib = L
     return L
 
@@ -381,6 +401,59 @@ def _profile(L, h):
         {"name": buf[i].name.decode(), "launches": buf[i].launches, "total_ms": buf[i].total_ms, "bytes": buf[i].bytes}
         for i in range(max(n, 0))
     ]
+
+
+def pcd_info(path):
+    """(number of points, format) of a PCD file; host only"""
+    L = lib()
+    n, fmt = C.c_int(), C.c_int()
+    if L.lsa_pcd_info(os.fsencode(path), C.byref(n), C.byref(fmt)) != 0:
+        raise LsaError(L.lsa_pcd_last_error().decode())
+    return n.value, fmt.value
+
+
+def read_pcd(path):
+    """A PCD file as LidarPoints (POINT_DTYPE): any field order, missing fields 0, extra fields ignored; host only."""
+    L = lib()
+    n, _ = pcd_info(path)
+    out = np.zeros(max(n, 1), POINT_DTYPE)
+    got = L.lsa_pcd_read(os.fsencode(path), ptr(out), out.size)
+    if got < 0:
+        raise LsaError(L.lsa_pcd_last_error().decode())
+    return out[:got].copy()
+
+
+def write_pcd(path, pts, fmt=PCD_BINARY):
+    """Writes LidarPoints as a PCD file (fmt: 0 ascii, 1 binary, 2 binary_compressed); host only.  Returns False, and
+    writes nothing, for an empty cloud (savePointCloudToPCD's -3)."""
+    L = lib()
+    pts = np.ascontiguousarray(pts, POINT_DTYPE)
+    rc = L.lsa_pcd_write(os.fsencode(path), ptr(pts) if pts.size else None, pts.size, int(fmt))
+    if rc == -3 and pts.size == 0:
+        return False
+    if rc != 0:
+        raise LsaError(f"lsa_pcd_write failed ({rc}): {L.lsa_pcd_last_error().decode()}")
+    return True
+
+
+def lzf_compress(data):
+    L = lib()
+    src = np.frombuffer(bytes(data), np.uint8)
+    out = np.zeros(src.size + src.size // 16 + 64, np.uint8)
+    n = C.c_size_t()
+    if L.lsa_lzf_compress(ptr(src) if src.size else None, src.size, ptr(out), out.size, C.byref(n)) != 0:
+        raise LsaError("lsa_lzf_compress failed")
+    return out[: n.value].tobytes()
+
+
+def lzf_decompress(data, raw_size):
+    L = lib()
+    src = np.frombuffer(bytes(data), np.uint8)
+    out = np.zeros(max(raw_size, 1), np.uint8)
+    n = C.c_size_t()
+    if L.lsa_lzf_decompress(ptr(src) if src.size else None, src.size, ptr(out), raw_size, C.byref(n)) != 0:
+        raise LsaError("lsa_lzf_decompress: malformed stream")
+    return out[: n.value].tobytes()
 
 
 def bind_host_to_device(device=0):
@@ -1014,6 +1087,26 @@ class Slam:
         n = self.L.lsa_slam_get_map(self.h, ktype, int(clean), ptr(out), out.size)
         return out[:n].copy()
 
+    def add_map_points(self, ktype, pts, fixed=False, time=-1.0):
+        """RollingGrid::Add(pts, fixed, time) on the map of one keypoint type"""
+        pts = np.ascontiguousarray(pts, POINT_DTYPE)
+        self._check(self.L.lsa_slam_add_map_points(self.h, ktype, ptr(pts) if pts.size else None, pts.size, int(fixed), float(time)), "lsa_slam_add_map_points")
+
+    def map_io_counts(self):
+        o = np.zeros(3, np.int32)
+        self.L.lsa_slam_map_io_counts(self.h, ptr(o))
+        return o.tolist()
+
+    def save_maps_pcd(self, prefix, fmt=PCD_BINARY, filtered=True):
+        """Slam::SaveMapsToPCD: <prefix>edges.pcd ...; returns the points written per type (-1: no file)"""
+        self._check(self.L.lsa_slam_save_maps_pcd(self.h, os.fsencode(prefix), int(fmt), int(filtered)), "lsa_slam_save_maps_pcd")
+        return self.map_io_counts()
+
+    def load_maps_pcd(self, prefix, reset_maps=True, time=-1.0):
+        """Slam::LoadMapsFromPCD; time < 0: the wall clock.  Returns the points read per type (-1: no file)"""
+        self._check(self.L.lsa_slam_load_maps_pcd(self.h, os.fsencode(prefix), int(reset_maps), float(time)), "lsa_slam_load_maps_pcd")
+        return self.map_io_counts()
+
     def target_submap(self, ktype):
         """Slam::GetTargetSubMap(k)"""
         n = self._check(self.L.lsa_slam_get_target_submap(self.h, ktype, None, 0), "lsa_slam_get_target_submap")
@@ -1192,6 +1285,19 @@ class DeviceGrid:
     def add_staged(self, time):
         """the insertion of what stage_keypoints read; any host thread"""
         self._check(self.L.lsa_device_grid_add_staged(self.h, float(time)), "lsa_device_grid_add_staged")
+
+    def add_pcd(self, path, fixed=False, time=-1.0, roll=True):
+        """RollingGrid::Add of a PCD file's cloud, converted on the device"""
+        self._check(self.L.lsa_device_grid_add_pcd(self.h, os.fsencode(path), int(fixed), float(time), int(roll)), "lsa_device_grid_add_pcd")
+
+    def save_pcd(self, path, fmt=PCD_BINARY, clean=False):
+        """RollingGrid::Get(clean) into a PCD file; returns the points written (0 and no file for an empty map)"""
+        return self._check(self.L.lsa_device_grid_save_pcd(self.h, os.fsencode(path), int(fmt), int(clean)), "lsa_device_grid_save_pcd")
+
+    def pcd_io_times(self):
+        o = np.zeros(8)
+        self.L.lsa_pcd_io_times(self.ctx.h, ptr(o))
+        return o
 
     def build_submap_begin_for_keypoints(self, box_type, min_nb_points, ktype=PLANE, slot=TARGET_MAP):
         """box of the keypoints of `box_type` as Context.keypoint_bboxes_begin left it on the device"""

@@ -12,6 +12,7 @@ struct lsa_slam
   explicit lsa_slam(int device) : core(device) {}
   SlamCore core;
   std::vector<lsa_point_t> scratch;
+  int map_io_counts[3] = {-1, -1, -1};  // points per type of the last lsa_slam_save_maps_pcd / lsa_slam_load_maps_pcd
 };
 
 extern "C" {
@@ -277,6 +278,32 @@ int lsa_slam_get_target_submap(lsa_slam* s, int type, lsa_point_t* out, int capa
 }
 
 lsa_ctx* lsa_slam_context(lsa_slam* s) { return s ? s->core.Context() : nullptr; }
+
+// ---- Slam::SaveMapsToPCD / LoadMapsFromPCD (Slam.cxx:504-543) and the primitive under the loader ----
+int lsa_slam_add_map_points(lsa_slam* s, int type, const lsa_point_t* pts, int n, int fixed, double time)
+{
+  if (!s) return LSA_E_ARG;
+  return s->core.AddMapPoints(type, pts, n, fixed != 0, time);
+}
+
+int lsa_slam_save_maps_pcd(lsa_slam* s, const char* prefix, int format, int filtered)
+{
+  if (!s || !prefix) return LSA_E_ARG;
+  return s->core.SaveMapsToPCD(prefix, format, filtered != 0, s->map_io_counts);
+}
+
+int lsa_slam_load_maps_pcd(lsa_slam* s, const char* prefix, int reset_maps, double time)
+{
+  if (!s || !prefix) return LSA_E_ARG;
+  return s->core.LoadMapsFromPCD(prefix, reset_maps != 0, time, s->map_io_counts);
+}
+
+int lsa_slam_map_io_counts(const lsa_slam* s, int counts[3])
+{
+  if (!s || !counts) return LSA_E_ARG;
+  std::memcpy(counts, s->map_io_counts, sizeof(s->map_io_counts));
+  return LSA_OK;
+}
 
 // ---- LidarSlam::RollingGrid on its own (include/lidarslam_amd.h, "the rolling voxel map") ----
 struct lsa_rolling_grid

@@ -4,7 +4,10 @@
 #include <chrono>
 #include <cmath>
 #include <cstdlib>
+#include <cstdio>
 #include <cstring>
+#include <ctime>
+#include "lsa_pcd.h"
 
 namespace lsa
 {
@@ -1648,6 +1651,98 @@ int SlamCore::GetMap(int k, bool clean, std::vector<lsa_point_t>& out)
   }
   out = Map(k).Get(clean);
   return static_cast<int>(out.size());
+}
+
+void SlamCore::DropMapLookahead()
+{
+  SpecPending = false;
+  for (int k = 0; k < 3; ++k)
+  {
+    SpecBuilt[k] = false;
+    SpecDone[k].store(false);
+    SpecStaged[k] = false;
+    DevSpec[k] = false;
+    if (Ctx) (void)lsa_drop_target_ahead(Ctx, LSA_TARGET_MAP, k);
+  }
+}
+
+int SlamCore::AddMapPoints(int type, const lsa_point_t* pts, int n, bool fixed, double time)
+{
+  if (!Ctx) return LSA_E_NO_DEVICE;
+  if (type < 0 || type > 2 || n < 0 || (n > 0 && !pts)) { LastError = "AddMapPoints: bad argument"; return LSA_E_ARG; }
+  WaitMaps();
+  DropMapLookahead();
+  if (n == 0) return LSA_OK;
+  if (DeviceMapsInUse()) LSA_TRY(lsa_device_grid_add(DevMaps[type], pts, n, fixed ? 1 : 0, time, 1));
+  else LocalMaps[type]->Add(pts, static_cast<std::size_t>(n), fixed, time);
+  return LSA_OK;
+}
+
+int SlamCore::SaveMapsToPCD(const std::string& prefix, int format, bool filtered, int counts[3])
+{
+  if (!Ctx) return LSA_E_NO_DEVICE;
+  if (format < pcd::kAscii || format > pcd::kBinaryCompressed) { LastError = "SaveMapsToPCD: unknown PCD format " + std::to_string(format); return LSA_E_ARG; }
+  WaitMaps();
+  for (int k = 0; k < 3; ++k)
+  {
+    if (counts) counts[k] = -1;
+    if (!UseKeypoints[k]) continue;
+    const std::string path = prefix + pcd::map_file_suffix(k);
+    int n = 0;
+    if (DeviceMapsInUse())
+    {
+      if (lsa_device_grid_size(DevMaps[k]) <= 0) continue;  // an empty cloud is not saved (PointCloudStorage.h:91-92)
+      n = lsa_device_grid_save_pcd(DevMaps[k], path.c_str(), format, filtered ? 1 : 0);
+      if (n < 0) return Fail(n, "lsa_device_grid_save_pcd");  // a file that cannot be written is an error, on either home of the maps
+      if (n == 0) continue;  // (no voxel passed the filter)
+    }
+    else
+    {
+      const RollingGrid::PointCloud pts = LocalMaps[k]->Get(filtered);
+      if (pts.empty()) continue;
+      std::string err;
+      const int rc = pcd::write_points(path, pts.data(), static_cast<long long>(pts.size()), format, err);
+      if (rc < 0) { LastError = "SaveMapsToPCD: " + err; return LSA_E_ARG; }
+      n = static_cast<int>(pts.size());
+    }
+    if (counts) counts[k] = n;
+  }
+  return LSA_OK;
+}
+
+int SlamCore::LoadMapsFromPCD(const std::string& prefix, bool resetMaps, double time, int counts[3])
+{
+  if (!Ctx) return LSA_E_NO_DEVICE;
+  if (resetMaps) ClearMaps();
+  WaitMaps();
+  DropMapLookahead();
+  if (time < 0) time = static_cast<double>(std::time(nullptr));
+  // "If mapping mode is NONE or ADD_DECAYING_KPTS, the first map points are fixed" (Slam.cxx:535-537)
+  const bool fixedMap = MapUpdate == MappingMode::NONE || MapUpdate == MappingMode::ADD_KPTS_TO_FIXED_MAP;
+  for (int k = 0; k < 3; ++k)
+  {
+    if (counts) counts[k] = -1;
+    const std::string path = prefix + pcd::map_file_suffix(k);
+    if (FILE* f = std::fopen(path.c_str(), "rb")) std::fclose(f);
+    else continue;  // pcl::io::loadPCDFile(path) != 0: that map is left alone
+    int n = 0;
+    if (DeviceMapsInUse())
+    {
+      int format = 0;
+      if (lsa_pcd_info(path.c_str(), &n, &format) != LSA_OK) { LastError = lsa_pcd_last_error(); return LSA_E_ARG; }
+      LSA_TRY(lsa_device_grid_add_pcd(DevMaps[k], path.c_str(), fixedMap ? 1 : 0, time, 1));
+    }
+    else
+    {
+      std::vector<lsa_point_t> pts;
+      std::string err;
+      if (pcd::read_points(path, pts, err) != LSA_OK) { LastError = err; return LSA_E_ARG; }
+      n = static_cast<int>(pts.size());
+      if (n > 0) LocalMaps[k]->Add(pts.data(), pts.size(), fixedMap, time);
+    }
+    if (counts) counts[k] = n;
+  }
+  return LSA_OK;
 }
 
 int SlamCore::GetTargetSubMap(int k, std::vector<lsa_point_t>& out)

@@ -111,6 +111,13 @@ public:
     for (auto* g : DevMaps)
       if (g) lsa_device_grid_reset(g, nullptr);
   }
+  // Points put into the map of one keypoint type: RollingGrid::Add(pts, fixed, time) with its default roll = true.  What
+  // the map loader sits on; waits for the map workers and drops what the look-ahead had prepared from the maps as they were.
+  int AddMapPoints(int type, const lsa_point_t* pts, int n, bool fixed, double time);
+  // Slam::SaveMapsToPCD / LoadMapsFromPCD (Slam.cxx:504-543).  counts[k]: points written / read per type, -1 where no file
+  // was written (type not in use, empty map) or found.  time < 0: the wall clock in whole seconds (std::time(nullptr)).
+  int SaveMapsToPCD(const std::string& prefix, int format, bool filtered, int counts[3]);
+  int LoadMapsFromPCD(const std::string& prefix, bool resetMaps, double time, int counts[3]);
   void HintNextStoredFrame(int slot) { NextStoredSlot = slot; }
   // Replay from host clouds: the cloud of the AddFrame call after the next one.  Its upload starts at once (pinned
   // staging, copy stream, a thread of its own), its keypoints are extracted beside the registration of the frame in
@@ -332,6 +339,7 @@ private:
   // the sub-map is extracted again.  Same result either way.
   int BeginSubMapSpeculation(const Pose& predicted);
   int FinishSubMapSpeculation();
+  void DropMapLookahead();  // sub-maps extracted ahead and spare targets made from the maps as they were
   bool SpecPending = false;
   bool SpecBuilt[3] = {false, false, false};  // written by the workers, read after WaitMaps
   // the same news for the thread that runs the ICP: it hands a finished sub-map to the device (upload and search

@@ -303,6 +303,14 @@ struct lsa_ctx
   bool loc_boxes = false;    // the boxes the grids read are the ones lsa_localization_begin made (words of their own)
   bool loc_armed = false;    // ... whose words are armed for the next launch
   bool pred_on_lookahead = false;  // the boxes in the first words were enqueued on the look-ahead stream (lsa_keypoint_boxes_predicted)
+  // lsa_pcd.hip: a map file on its way to or from the device in pieces -- two pinned host pieces the copy stream reads (load)
+  // or k_pcd_encode writes (save), two device pieces the copies land in, an event behind every copy and every kernel
+  void* pcd_pinned[2] = {nullptr, nullptr};
+  void* pcd_dev[2] = {nullptr, nullptr};
+  size_t pcd_piece = 0;  // bytes of each
+  hipEvent_t pcd_ev_copy[2] = {nullptr, nullptr}, pcd_ev_kernel[2] = {nullptr, nullptr};
+  int pcd_lds = -1;      // lsa_debug_set "pcd_lds": 1 / 0 picks the form of k_pcd_decode / k_pcd_encode, -1 the default
+  double pcd_times[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // the last load / save, see lsa_pcd_io_times
   std::mutex prof_mutex;  // stats / pending / event_pool of the profiling scopes
   // Buffers that were outgrown.  hipFree / hipHostFree wait for the whole device -- also for a gate that waits for THIS
   // process (lsa_icp_gate), with the runtime's lock held: a free on a worker thread at the wrong moment stalls the frame

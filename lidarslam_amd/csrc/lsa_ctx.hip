@@ -665,6 +665,13 @@ void lsa_ctx_destroy(lsa_ctx* ctx)
   if (ctx->ev_stage) (void)hipEventDestroy(ctx->ev_stage);
   for (int k = 0; k < 3; ++k)
     if (ctx->stage[k]) (void)hipHostFree(ctx->stage[k]);
+  for (int b = 0; b < 2; ++b)
+  {
+    if (ctx->pcd_pinned[b]) (void)hipHostFree(ctx->pcd_pinned[b]);
+    if (ctx->pcd_dev[b]) (void)hipFree(ctx->pcd_dev[b]);
+    if (ctx->pcd_ev_copy[b]) (void)hipEventDestroy(ctx->pcd_ev_copy[b]);
+    if (ctx->pcd_ev_kernel[b]) (void)hipEventDestroy(ctx->pcd_ev_kernel[b]);
+  }
   for (int k = 0; k < 6; ++k)
     if (ctx->tstage[k]) (void)hipHostFree(ctx->tstage[k]);
   if (ctx->stream) (void)hipStreamDestroy(ctx->stream);

@@ -37,6 +37,7 @@
 #include <string.h>
 #include <vector>
 #include "lsa_ctx.h"
+#include "lsa_device_grid_io.h"
 #include "host/lsa_map_order.h"
 #include "lsa_device_math.h"
 
@@ -1570,6 +1571,56 @@ int add_batch(lsa_device_grid* g, int n, bool fixed, double time, bool do_roll) 
 
 }  // namespace
 
+// ---- what lsa_pcd.hip needs of a grid (lsa_device_grid_io.h) ----
+namespace lsa
+{
+lsa_ctx* grid_context(lsa_device_grid* g) { return g->ctx; }
+hipStream_t grid_stream(lsa_device_grid* g) { return g->stream; }
+
+// room for a batch of n points: the buffer a conversion kernel on the grid's stream fills before grid_add_batch(n)
+int grid_batch(lsa_device_grid* g, int n, lsa_point_t** batch)
+{
+  G_HIP(hipSetDevice(g->ctx->device));
+  const int rc = ensure_batch(g, n);
+  if (rc) return rc;
+  g->staged = 0;
+  *batch = reinterpret_cast<lsa_point_t*>(g->batch);
+  return LSA_OK;
+}
+int grid_add_batch(lsa_device_grid* g, int n, bool fixed, double time, bool do_roll) { return add_batch(g, n, fixed, time, do_roll); }
+
+// RollingGrid::Get(clean) left on the device: the points in the order lsa_device_grid_get hands them out, in the context's
+// scratch buffer, *n of them; the grid's stream has been waited for
+int grid_collect(lsa_device_grid* g, int clean, const lsa_point_t** pts, int* n)
+{
+  lsa_ctx* ctx = g->ctx;
+  G_HIP(hipSetDevice(ctx->device));
+  *pts = nullptr;
+  *n = 0;
+  if (g->n_upper == 0) return LSA_OK;
+  int rc = ensure_map(g, g->n_upper);
+  if (rc) return rc;
+  rc = ensure_scratch(ctx, (size_t)g->n_upper * sizeof(lsa_point_t));
+  if (rc) return rc;
+  if (!g->Ordered)
+  {
+    rc = ensure_order(g);
+    if (rc) return rc;
+  }
+  const MapView m = g->buf[g->cur];
+  rc = order_after_context(g);
+  if (rc) return rc;
+  SubMapPred pred{m.keys, m.pts, m.count, g->st, BoxArg{}, nullptr, nullptr, g->GridSize, (float)g->VoxelResolution, g->VoxelResolution, 0, g->MinFramesPerVoxel, -1, clean ? 3 : 0};
+  compact_map(g, pred, PointEmit{m.pts, reinterpret_cast<float4*>(ctx->scratch_out)}, g->st + kStSub);
+  int kept = 0;
+  G_HIP(hipMemcpyAsync(&kept, g->st + kStSub, sizeof(int), hipMemcpyDeviceToHost, g->stream));
+  G_HIP(hipStreamSynchronize(g->stream));
+  *pts = static_cast<const lsa_point_t*>(ctx->scratch_out);
+  *n = kept;
+  return LSA_OK;
+}
+}  // namespace lsa
+
 extern "C" {
 
 int lsa_device_grid_create(lsa_ctx* ctx, lsa_device_grid** out)
@@ -1936,28 +1987,12 @@ int lsa_device_grid_clear_old_points(lsa_device_grid* g, double now)
 int lsa_device_grid_get(lsa_device_grid* g, int clean, lsa_point_t* out, int capacity)
 {
   if (!g || (!out && capacity > 0)) return LSA_E_ARG;
-  lsa_ctx* ctx = g->ctx;
-  G_HIP(hipSetDevice(ctx->device));
-  if (g->n_upper == 0) return 0;
-  int rc = ensure_map(g, g->n_upper);
-  if (rc) return rc;
-  rc = ensure_scratch(ctx, (size_t)g->n_upper * sizeof(lsa_point_t));
-  if (rc) return rc;
-  if (!g->Ordered)
-  {
-    rc = ensure_order(g);
-    if (rc) return rc;
-  }
-  const MapView m = g->buf[g->cur];
-  rc = order_after_context(g);  // the scratch buffer is the context's; a sub-map extraction on its stream comes first too
-  if (rc) return rc;
-  SubMapPred pred{m.keys, m.pts, m.count, g->st, BoxArg{}, nullptr, nullptr, g->GridSize, (float)g->VoxelResolution, g->VoxelResolution, 0, g->MinFramesPerVoxel, -1, clean ? 3 : 0};
-  compact_map(g, pred, PointEmit{m.pts, reinterpret_cast<float4*>(ctx->scratch_out)}, g->st + kStSub);
+  const lsa_point_t* pts = nullptr;
   int kept = 0;
-  G_HIP(hipMemcpyAsync(&kept, g->st + kStSub, sizeof(int), hipMemcpyDeviceToHost, g->stream));
-  G_HIP(hipStreamSynchronize(g->stream));
+  const int rc = lsa::grid_collect(g, clean, &pts, &kept);  // (the scratch buffer is the context's; a sub-map extraction on its stream comes first too)
+  if (rc) return rc;
   const int n = std::min(kept, capacity);
-  if (n > 0) G_HIP(hipMemcpy(out, ctx->scratch_out, (size_t)n * sizeof(lsa_point_t), hipMemcpyDeviceToHost));
+  if (n > 0) G_HIP(hipMemcpy(out, pts, (size_t)n * sizeof(lsa_point_t), hipMemcpyDeviceToHost));
   return n;
 }
 

@@ -1,0 +1,13 @@
+// lsa_device_grid_io.h -- what the map-file unit (lsa_pcd.hip) needs of a device grid (lsa_device_grid.hip): the batch
+// buffer an insertion reads, the insertion itself, and RollingGrid::Get left on the device.
+#pragma once
+#include "lsa_ctx.h"
+
+namespace lsa
+{
+lsa_ctx* grid_context(lsa_device_grid* g);
+hipStream_t grid_stream(lsa_device_grid* g);
+int grid_batch(lsa_device_grid* g, int n, lsa_point_t** batch);
+int grid_add_batch(lsa_device_grid* g, int n, bool fixed, double time, bool do_roll);
+int grid_collect(lsa_device_grid* g, int clean, const lsa_point_t** pts, int* n);
+}  // namespace lsa

@@ -1144,6 +1144,7 @@ int lsa_debug_set(lsa_ctx* ctx, const char* name, int value)
   else if (n == "lm_cache") ctx->lm_cache_slots = value < 0 ? c.lm_cache_slots : std::min(value, ctx->lm_cache_capacity);
   else if (n == "accum_blocks") ctx->accum_blocks = value < 0 ? c.accum_blocks : std::min(std::max(value, 1), kAccumBlocksMax);
   else if (n == "mailbox_check") ctx->mailbox_check = value < 0 ? c.mailbox_check : value != 0;
+  else if (n == "pcd_lds") ctx->pcd_lds = value < 0 ? -1 : (value != 0);  // lsa_pcd.hip: the form of the two conversion kernels
   else return ctx->fail(LSA_E_ARG, "lsa_debug_set: no such knob");
   return LSA_OK;
 }

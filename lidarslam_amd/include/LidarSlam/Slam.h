@@ -277,9 +277,9 @@ public:
   }
   const std::string& GetLastError() const { return this->LastError; }
 
-  // ---- outside the scan-matching hot path (pose-graph optimisation, PCD map IO, external sensors, keypoint
-  // logging).  Present with the reference's signatures so that LidarSlamNode.cxx / vtkSlam.cxx compile unchanged; each
-  // warns once and does nothing, the way the reference itself answers RunPoseGraphOptimization without g2o
+  // ---- outside the scan-matching hot path (pose-graph optimisation, keypoint logging).  Present with the
+  // reference's signatures so that LidarSlamNode.cxx / vtkSlam.cxx compile unchanged; each warns once and does nothing, the
+  // way the reference itself answers RunPoseGraphOptimization without g2o
   // (slam_lib/src/Slam.cxx:355-366: "SLAM PoseGraphOptimization requires G2O, but it was not found.").
 #ifdef LSA_HAVE_EIGEN
   void RunPoseGraphOptimization(const std::vector<Transform>&, const std::vector<std::array<double, 9>>&, Eigen::Isometry3d&, const std::string& = "")
@@ -289,13 +289,17 @@ public:
   {
     this->NotSupported("RunPoseGraphOptimization", "pose-graph optimisation (g2o) is not part of this build: maps and trajectory are left unchanged");
   }
-  void SaveMapsToPCD(const std::string&, PCDFormat = PCDFormat::BINARY_COMPRESSED, bool = true) const
+  // ---- the keypoint maps as PCD files (Slam.cxx:504-543): <prefix>edges.pcd, <prefix>planes.pcd, <prefix>blobs.pcd.  A
+  // failure is reported through GetLastError(); the first call of each per object says on stderr what it wrote or loaded.
+  void SaveMapsToPCD(const std::string& filePrefix, PCDFormat pcdFormat = PCDFormat::BINARY_COMPRESSED, bool filtered = true) const
   {
-    this->NotSupported("SaveMapsToPCD", "PCD map IO is not part of this build: use GetMap() and the caller's own writer");
+    const int rc = lsa_slam_save_maps_pcd(this->Handle, filePrefix.c_str(), static_cast<int>(pcdFormat), filtered ? 1 : 0);
+    this->ReportMapIO("SaveMapsToPCD", "saved to", filePrefix, rc);
   }
-  void LoadMapsFromPCD(const std::string&, bool = true)
+  void LoadMapsFromPCD(const std::string& filePrefix, bool resetMaps = true)
   {
-    this->NotSupported("LoadMapsFromPCD", "PCD map IO is not part of this build: the maps are left unchanged");
+    const int rc = lsa_slam_load_maps_pcd(this->Handle, filePrefix.c_str(), resetMaps ? 1 : 0, -1.);
+    this->ReportMapIO("LoadMapsFromPCD", "loaded from", filePrefix, rc);
   }
   // keypoint logging feeds the pose-graph optimisation only: the value is remembered, nothing is logged
   void SetLoggingStorage(PointCloudStorageType s) { this->LoggingStorage = s; }
@@ -487,6 +491,21 @@ private:
     if (this->Warned.insert(what).second) std::fprintf(stderr, "\033[1;33m[WARNING] LidarSlam::Slam::%s: %s\033[0m\n", what, why);
   }
   void NotSupported(const char* what, const char* why) const { this->WarnOnce(what, why); }
+  void ReportMapIO(const char* what, const char* verb, const std::string& prefix, int rc) const
+  {
+    // GetLastError() speaks of the last call: a save or load that went well clears what an earlier one left
+    this->LastError = rc < 0 ? std::string(what) + ": " + lsa_slam_last_error(this->Handle) : std::string();
+    if (!this->Warned.insert(what).second) return;
+    static const char* const names[3] = {"edges", "planes", "blobs"};
+    int counts[3] = {-1, -1, -1};
+    lsa_slam_map_io_counts(this->Handle, counts);
+    std::string line;
+    for (int k = 0; k < 3; ++k)
+      if (counts[k] >= 0) line += " " + prefix + names[k] + ".pcd (" + std::to_string(counts[k]) + " points)";
+    if (rc < 0) line = " failed: " + this->LastError;
+    else if (line.empty()) line = " no file";
+    std::fprintf(stderr, "LidarSlam::Slam::%s: keypoint maps %s%s\n", what, verb, line.c_str());
+  }
 
   lsa_slam* Handle = nullptr;
   mutable std::set<std::string> Warned;
@@ -494,7 +513,8 @@ private:
   PointCloudStorageType LoggingStorage = PointCloudStorageType::PCL_CLOUD;
   std::map<std::uint8_t, KeypointExtractorPtr> KeyPointsExtractors;
   std::uint64_t CurrentStamp = 0;
-  std::string WorldFrameId = "world", BaseFrameId = "base", LastError;
+  std::string WorldFrameId = "world", BaseFrameId = "base";
+  mutable std::string LastError;  // mutable: SaveMapsToPCD is const in the reference and reports its failure here
   int Verbosity = 0;
 };
 

@@ -382,6 +382,7 @@ int ensure_target(lsa_ctx* ctx, int ti, int m);
 int build_target_grids(lsa_ctx* ctx, const int* tis, int count, hipStream_t st);  // lsa_target.hip: the search grids of these targets, one chain of launches
 int ensure_match(lsa_ctx* ctx, int type, int k);
 int ensure_scratch(lsa_ctx* ctx, size_t bytes);
+void maybe_estimate_resolution(lsa_ctx* ctx, const lsa_point_t* pts, int n);  // lsa_upload.hip: az_res from a frame on the host, unless the context has one
 int enqueue_time_range(lsa_ctx* ctx, int set, const int* counts_dev);
 void finish_time_range(lsa_ctx* ctx, int set, const unsigned long long bits[2]);
 

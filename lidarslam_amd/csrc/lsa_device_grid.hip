@@ -37,15 +37,20 @@
 #include <string.h>
 #include <vector>
 #include "lsa_ctx.h"
+#include "lsa_compact.h"
 #include "lsa_device_grid_io.h"
 #include "host/lsa_map_order.h"
 #include "lsa_device_math.h"
 
 using namespace lsa;
 
+namespace lsa
+{
+__global__ void k_copy_int(int* __restrict__ dst, const int* __restrict__ src) { if (threadIdx.x == 0 && blockIdx.x == 0) *dst = *src; }  // lsa_compact.h
+}  // namespace lsa
+
 namespace
 {
-typedef unsigned long long u64;
 constexpr u64 kNoKey = ~0ull;  // points outside the grid: sorted behind every voxel
 
 struct GridParams
@@ -69,67 +74,6 @@ __device__ __forceinline__ int round_to_int(float v)
   // Eigen's .round().cast<int>(): round half away from zero, then a C cast (out of range: INT_MIN, as on x86-64)
   const float r = roundf(v);
   return (r >= -2147483648.f && r < 2147483648.f) ? (int)r : (int)0x80000000;
-}
-
-// ---- stable compaction: chunk counts -> scatter (the predicate is evaluated twice) ---------------------------------------
-// Two launches: every scatter block sums the counts of the chunks before it itself (a map of a few hundred thousand voxels
-// is a few hundred chunks), the last block leaves the total.
-template <typename Pred>
-__global__ __launch_bounds__(256) void k_compact_count(Pred pred, const int* __restrict__ n_ptr, int n_fixed, int* __restrict__ chunk_count)
-{
-  __shared__ int cnt[4];
-  const int n = n_ptr ? *n_ptr : n_fixed;
-  if (blockIdx.x * 1024 >= n) { if (threadIdx.x == 0) chunk_count[blockIdx.x] = 0; return; }
-  int mine = 0;
-  for (int q = 0; q < 4; ++q)
-  {
-    const int i = blockIdx.x * 1024 + q * 256 + threadIdx.x;
-    if (i < n && pred(i)) ++mine;
-  }
-  for (int o = 32; o > 0; o >>= 1) mine += __shfl_down(mine, o);
-  if ((threadIdx.x & 63) == 0) cnt[threadIdx.x >> 6] = mine;
-  __syncthreads();
-  if (threadIdx.x == 0) chunk_count[blockIdx.x] = cnt[0] + cnt[1] + cnt[2] + cnt[3];
-}
-// total_out: where the number kept goes (never the word n_ptr points at: the other blocks still read that one);
-// base_ptr: the output starts behind *base_ptr elements (appending), at 0 when null
-template <typename Pred, typename Emit>
-__global__ __launch_bounds__(256) void k_compact_scatter(Pred pred, Emit emit, const int* __restrict__ n_ptr, int n_fixed, const int* __restrict__ chunk_count,
-                                                         const int* __restrict__ base_ptr, int* __restrict__ total_out,
-                                                         u64* __restrict__ host_out = nullptr, unsigned host_tag = 0, int* __restrict__ clear_flag = nullptr)
-{
-  __shared__ int wave_cnt[4];
-  __shared__ int before[4];
-  const int n = n_ptr ? *n_ptr : n_fixed;
-  const bool last = blockIdx.x == gridDim.x - 1;
-  if (blockIdx.x * 1024 >= n && !last) return;
-  int mine = 0;
-  for (int c = threadIdx.x; c < (int)blockIdx.x; c += 256) mine += chunk_count[c];
-  for (int o = 32; o > 0; o >>= 1) mine += __shfl_down(mine, o);
-  if ((threadIdx.x & 63) == 0) before[threadIdx.x >> 6] = mine;
-  __syncthreads();
-  int run = (base_ptr ? *base_ptr : 0) + before[0] + before[1] + before[2] + before[3];
-  for (int q = 0; q < 4; ++q)
-  {
-    const int i = blockIdx.x * 1024 + q * 256 + threadIdx.x;
-    const bool keep = i < n && pred(i);
-    const u64 ballot = __ballot(keep);
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    __syncthreads();  // wave_cnt of the round before has been read
-    if (lane == 0) wave_cnt[wv] = __popcll(ballot);
-    __syncthreads();
-    int base = run;
-    for (int w = 0; w < wv; ++w) base += wave_cnt[w];
-    if (keep) emit(i, base + __popcll(ballot & ((1ull << lane) - 1ull)));
-    run += wave_cnt[0] + wave_cnt[1] + wave_cnt[2] + wave_cnt[3];
-  }
-  if (last && threadIdx.x == 0)
-  {
-    *total_out = run;
-    if (clear_flag) *clear_flag = 0;
-    // the total for the host: tag and count in ONE 8-byte store into coherent host memory (no copy, no event)
-    if (host_out) __hip_atomic_store(host_out, ((u64)host_tag << 32) | (u64)(unsigned)run, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-  }
 }
 
 struct MapView
@@ -1070,7 +1014,6 @@ struct PointEmit
   }
 };
 __global__ void k_set_int(int* __restrict__ p, int v) { if (threadIdx.x == 0 && blockIdx.x == 0) *p = v; }
-__global__ void k_copy_int(int* __restrict__ dst, const int* __restrict__ src) { if (threadIdx.x == 0 && blockIdx.x == 0) *dst = *src; }
 // the outer voxels the box of `words` (ordered unsigned, lsa_keypoint_bboxes_begin) touches: lo[3], hi[3]
 __device__ __forceinline__ void box_voxels(const unsigned* __restrict__ words, int grid_size, float resolution, double resolution_d, const int* __restrict__ st, int lo[3],
                                            int hi[3])
@@ -1313,22 +1256,12 @@ int ensure_batch(lsa_device_grid* g, int n)
   return LSA_OK;
 }
 
-// stable compaction of [0, n) (n on the device when n_ptr is given) by pred, emit(i, position); the number kept lands in
-// *total (added to what is there when `append`)
+// stable compaction of [0, n) on the map's stream (or `on`) with the map's chunk counts: lsa_compact.h
 template <typename Pred, typename Emit>
 void compact(lsa_device_grid* g, Pred pred, Emit emit, const int* n_ptr, int n_bound, int* total, bool append = false, bool copy_back = true,
              hipStream_t on = nullptr, u64* host_out = nullptr, unsigned host_tag = 0, int* clear_flag = nullptr)
 {
-  hipStream_t st = on ? on : g->stream;
-  const int nchunks = std::max((n_bound + 1023) / 1024, 1);
-  hipLaunchKernelGGL((k_compact_count<Pred>), dim3(nchunks), dim3(256), 0, st, pred, n_ptr, n_bound, g->chunks);
-  // compacting in place of the count it reads (Roll, ClearOldPoints), or appending behind it: the blocks of the
-  // scatter still read the old count, the new one waits in a slot of its own until they are through
-  const bool aside = n_ptr == total || append;
-  int* const sum = aside ? g->st + kStCompact : total;
-  hipLaunchKernelGGL((k_compact_scatter<Pred, Emit>), dim3(nchunks), dim3(256), 0, st, pred, emit, n_ptr, n_bound, g->chunks, append ? total : (const int*)nullptr, sum,
-                     host_out, host_tag, clear_flag);
-  if (aside && copy_back) hipLaunchKernelGGL(k_copy_int, dim3(1), dim3(64), 0, st, total, sum);  // otherwise the caller's next kernel takes it from st[kStCompact]
+  stable_compact(on ? on : g->stream, g->chunks, g->st + kStCompact, pred, emit, n_ptr, n_bound, total, append, copy_back, host_out, host_tag, clear_flag);
 }
 
 // the host's copy of the state follows every modification (asynchronously)

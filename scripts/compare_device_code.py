@@ -5,10 +5,13 @@
 
 Every *.hip of both directories is compiled to gfx950 assembly (device side only, with the HIPFLAGS of that
 directory's Makefile).  For each kernel the script takes the code object metadata (VGPRs, AGPRs, SGPRs, LDS bytes,
-scratch bytes, spills) and the instruction stream with comments dropped and the function number taken out of the
-local labels.  It reports kernels that exist on one side only, kernels whose resources differ and kernels whose
-instruction stream differs, and exits 1 when there is any of these.  --table prints the per-kernel resources of NEW
-as a Markdown table.  Meant for refactors that move kernels between files: the expected result is no difference.
+scratch bytes, spills) and the instruction stream with comments and section directives dropped and the function number
+taken out of the local labels and the kernel's own symbol.  It reports kernels that exist on one side only, kernels whose resources differ and kernels whose
+instruction stream differs, and exits 1 when there is any of these.  A kernel that exists on one side only is paired
+with the one of the other side that has the same demangled signature once the namespace qualifiers are taken out (a
+kernel that left an anonymous namespace for a header), and compared like any other.  --table prints the per-kernel
+resources of NEW as a Markdown table.  Meant for refactors that move kernels between files: the expected result is no
+difference.
 """
 import argparse
 import concurrent.futures
@@ -51,19 +54,36 @@ def kernels_of(asm_path):
         body = text.split("\n%s:" % name, 1)[1].split("\n.Lfunc_end", 1)[0]
         lines = []
         for line in body.split("\n")[1:]:
-            line = re.sub(r"\.LBB\d+_", ".LBB_", line.split(";", 1)[0]).strip()
-            if line:
+            line = re.sub(r"\.LBB\d+_", ".LBB_", line.split(";", 1)[0]).replace(name, "<self>").strip()
+            if line and line != ".text" and not line.startswith(".section"):  # (which section the code lands in is linkage, not code)
                 lines.append(line)
         out[name] = (res, lines)
     return out
 
 
 def demangle(names):
+    """{symbol: (name for the report, signature without namespace qualifiers)}"""
     try:
         res = subprocess.run([shutil.which("llvm-cxxfilt") or "c++filt"], input="\n".join(names), capture_output=True, text=True, check=True).stdout.split("\n")
-        return {n: re.sub(r"\(anonymous namespace\)::|\(.*", "", d) for n, d in zip(names, res)}
+        return {n: (re.sub(r"\(anonymous namespace\)::|\(.*", "", d), re.sub(r"(\(anonymous namespace\)|\w+)::", "", d)) for n, d in zip(names, res)}
     except (OSError, subprocess.CalledProcessError):
-        return {n: n for n in names}
+        return {n: (n, n) for n in names}
+
+
+def pair_renamed(old, new, where, plain):
+    """Kernels of one side only whose unqualified signature names exactly one kernel of each side: NEW's takes OLD's symbol."""
+    alone = {side: {} for side in ("old", "new")}
+    for side, mine, other in (("old", old, new), ("new", new, old)):
+        for name in set(mine) - set(other):
+            alone[side].setdefault(plain[name], []).append(name)
+    paired = 0
+    for sig, names in alone["old"].items():
+        if len(names) == 1 and len(alone["new"].get(sig, ())) == 1:
+            was = alone["new"][sig][0]
+            new[names[0]] = new.pop(was)
+            where["new"][names[0]] = where["new"].pop(was)
+            paired += 1
+    return paired
 
 
 def main():
@@ -91,7 +111,9 @@ def main():
                 sides[side][name] = k
                 where[side][name] = os.path.basename(src)
     old, new = sides["old"], sides["new"]
-    pretty = demangle(sorted(set(old) | set(new)))
+    names = demangle(sorted(set(old) | set(new)))
+    pretty = {n: v[0] for n, v in names.items()}
+    paired = pair_renamed(old, new, where, {n: v[1] for n, v in names.items()})
     bad = 0
     for name in sorted(set(old) ^ set(new)):
         print(f"ONLY {'old' if name in old else 'new'}: {pretty[name]}")
@@ -112,7 +134,7 @@ def main():
         for name in sorted(new, key=lambda n: (where["new"][n], pretty[n])):
             r = new[name][0]
             print(f"| `{pretty[name]}` | {where['new'][name]} | {r[0]} | {r[1]} | {r[2]} | {r[3]} | {r[4]} | {r[5] + r[6]} |")
-    print(f"{len(old)} kernels old, {len(new)} kernels new, {moved} in another file, {bad} differences")
+    print(f"{len(old)} kernels old, {len(new)} kernels new, {moved} in another file, {paired} paired across namespaces, {bad} differences")
     return 1 if bad else 0
 
 

@@ -506,7 +506,9 @@ int lsa_solve_device_trace(lsa_ctx* ctx, unsigned long long out[12]);
  * and the launch shapes of the two reductions, as the environment sets them at creation, with the same clamps; a
  * negative value restores what the context was created with; they take effect at the next launch:
  *   "lm_blocks" (LSA_LM_BLOCKS 1..128), "lm_records" (LSA_LM_RECORDS 256..4096), "lm_cache" (LSA_LM_CACHE, at most the
- *   LDS layers the solve kernel has room for), "accum_blocks" (LSA_ACCUM_BLOCKS 1..256), "mailbox_check" (LSA_MAILBOX_CHECK) */
+ *   LDS layers the solve kernel has room for), "accum_blocks" (LSA_ACCUM_BLOCKS 1..256), "mailbox_check" (LSA_MAILBOX_CHECK)
+ * and of the keypoint log: "kplog_chunk_kib" n (chunks made from now on hold n KiB; negative: 32 MiB again), "kplog_fail_alloc"
+ * 1 / 0 (while 1, a chunk allocation fails as if the device were out of memory) */
 int lsa_debug_set(lsa_ctx* ctx, const char* name, int value);
 /* The shape of the last one-launch solve (lsa_solve_device_begin): {workgroups, residual blocks per thread, of those kept
  * in LDS, residual blocks in all}. */
@@ -788,6 +790,25 @@ int lsa_slam_add_map_points(lsa_slam* s, int type, const lsa_point_t* pts, int n
 int lsa_slam_save_maps_pcd(lsa_slam* s, const char* prefix, int format, int filtered);
 int lsa_slam_load_maps_pcd(lsa_slam* s, const char* prefix, int reset_maps, double time);
 int lsa_slam_map_io_counts(const lsa_slam* s, int counts[3]);
+/* A trajectory corrected after the fact -- by GPS, a loop closure, g2o, GTSAM, Ceres, control points: the optimizer is the
+ * caller's -- brought back into the library: everything Slam::RunPoseGraphOptimization does AFTER its optimizer
+ * (Slam.cxx:404-477).  Needs the keypoint log, i.e. "LoggingTimeout" != 0 while the frames were added (lsa_kplog_* above).
+ * - lsa_slam_set_trajectory_and_rebuild_maps(poses17, n): rows as lsa_slam_get_trajectory gives them (row-major 4x4 + time).
+ *   Waits for the map workers and the look-ahead; Reset(false); replaces the logged poses; re-projects every logged frame's
+ *   raw keypoints under them (lsa_kplog_replay: per-point interpolation between consecutive poses unless "Undistortion" is
+ *   NONE); per keypoint type in use ONE RollingGrid::Add(aggregate, fixed = false, time = -1, roll = false) and a Roll onto
+ *   the last frame's box, on the device maps or ("MapsOnDevice" = 0) the host maps; Tworld = pose[n-1], PreviousTworld =
+ *   pose[n-2].  The covariance log is kept.  The next lsa_slam_add_frame goes on as after lsa_slam_reset(s, 0).
+ *   LSA_E_STATE when "LoggingTimeout" is 0, when keypoint logging stopped (a chunk could not be allocated; until
+ *   lsa_slam_reset(s, 1)) or when the keypoint log does not cover the logged poses (logging was switched on in between);
+ *   LSA_E_ARG when n is not the number of logged poses, n < 2, or a row's time is not the logged pose's; LSA_E_CAPACITY
+ *   when the maps are on the device and one type has more than 3 000 000 logged keypoints (what one insertion into a
+ *   device map takes: rebuild with "MapsOnDevice" = 0).  On any of these nothing was changed.
+ * - lsa_slam_logged_frames: frames in the keypoint log; lsa_slam_get_logged_keypoints: one frame's raw keypoints of one
+ *   type (returns their number, writes at most capacity).  Read-only parameter "LoggedKeypointsBytes": device memory held. */
+int lsa_slam_set_trajectory_and_rebuild_maps(lsa_slam* s, const double* poses17, int n);
+int lsa_slam_logged_frames(const lsa_slam* s);
+int lsa_slam_get_logged_keypoints(lsa_slam* s, int frame, int type, lsa_point_t* out, int capacity);
 
 
 /* ------------------------------------------------------------------------- */
@@ -882,6 +903,50 @@ int lsa_device_grid_submap_ahead_take_end(lsa_device_grid* g, int* taken);
 int lsa_device_grid_add_pcd(lsa_device_grid* g, const char* path, int fixed, double time, int roll_first);
 int lsa_device_grid_save_pcd(lsa_device_grid* g, const char* path, int format, int clean);
 int lsa_pcd_io_times(const lsa_ctx* ctx, double out[8]);
+
+/* ------------------------------------------------------------------------- */
+/* The keypoint log (Slam::LogKeypoints, slam_lib/src/Slam.cxx:1225-1255) in the memory of the device, and its replay under
+ * a corrected trajectory (the part of Slam::RunPoseGraphOptimization that comes after the optimizer, Slam.cxx:416-475).
+ * A frame of the log is the three RAW keypoint sets (BASE coordinates, not undistorted) of one logged pose.  Storage:
+ * chunks of 32 MiB; a frame never straddles two, so growth never copies; a chunk whose frames have all been popped is
+ * reused; nothing is freed while work may be in flight (lsa_collect_garbage).  The log is made by the first append: a
+ * context that never logs allocates, enqueues and reads nothing for it.
+ * Slam::LoggingStorage (PointCloudStorageType: PCL_CLOUD, OCTREE_COMPRESSED, PCD_ASCII, PCD_BINARY, PCD_BINARY_COMPRESSED)
+ * is accepted by lsa_slam_set_param("LoggingStorage") and all five values mean the same thing here: uncompressed
+ * LidarPoints in HBM (32 B a keypoint; about 1 MB per VLS-128 frame).  Nothing is compressed.
+ * - lsa_kplog_append: a frame from LSA_SET_RAW_CURRENT, one device-to-device launch on the context's stream.
+ * - lsa_kplog_append_points: a frame of the caller's own keypoints (pts[k] may be NULL where n[k] == 0).
+ * - lsa_kplog_pop_front / _clear: drop the oldest frame / everything (_clear also ends a stop, see below).
+ * - lsa_kplog_size: frames; lsa_kplog_count(frame, type): keypoints; lsa_kplog_get: copies them out, returns the number
+ *   written; lsa_kplog_bytes: bytes of device memory held by the chunks.
+ * When a chunk cannot be allocated the append fails with LSA_E_HIP (lsa_last_error says so), lsa_kplog_stopped turns 1 and
+ * appends and replays answer LSA_E_STATE until lsa_kplog_clear.
+ * - lsa_kplog_replay: ONE launch (k_log_replay) for all n = lsa_kplog_size frames and the types in type_mask, a thread per
+ *   logged point: frame i >= 1 with undistort != 0 is moved by LinearTransformInterpolator(pose[i-1], pose[i]) with
+ *   SetTimes(times[i] - times[i-1], 0.) evaluated at each point's own time, as the reference writes it (Slam.cxx:426-440);
+ *   frame 0, and every frame with undistort == 0, by the rigid pose[i].  The per-point arithmetic is lsa_undistort's /
+ *   lsa_stage_transformed's.  poses: n row-major 4x4.  The result -- frames ascending, inside a frame the logged order --
+ *   is written into pinned host memory of the context (lsa_kplog_replayed returns it and its size; valid until the next
+ *   replay) and copied to out[k] where out and out[k] are not NULL.  last_min / last_max [type][xyz]: the box of the LAST
+ *   frame's moved keypoints (Slam.cxx:472-473); FLT_MAX / -FLT_MAX for a type without keypoints in it.
+ *   LSA_E_ARG unless n == lsa_kplog_size and n >= 2.
+ * - lsa_kplog_replay_to_grids: the same straight into the batch buffers of the device maps grids[k] (types in type_mask),
+ *   followed by RollingGrid::Add(aggregate, fixed = false, time = -1, roll = false) on each (Slam.cxx:474); the caller
+ *   rolls (lsa_device_grid_roll(grids[k], last_min[k], last_max[k]), Slam.cxx:475). */
+int lsa_kplog_append(lsa_ctx* ctx);
+int lsa_kplog_append_points(lsa_ctx* ctx, const lsa_point_t* const pts[3], const int n[3]);
+int lsa_kplog_pop_front(lsa_ctx* ctx);
+int lsa_kplog_clear(lsa_ctx* ctx);
+int lsa_kplog_size(const lsa_ctx* ctx);
+int lsa_kplog_count(const lsa_ctx* ctx, int frame, int type);
+int lsa_kplog_get(lsa_ctx* ctx, int frame, int type, lsa_point_t* out, int capacity);
+unsigned long long lsa_kplog_bytes(const lsa_ctx* ctx);
+int lsa_kplog_stopped(const lsa_ctx* ctx);
+int lsa_kplog_replay(lsa_ctx* ctx, unsigned type_mask, const double* poses, const double* times, int n, int undistort, lsa_point_t* const out[3],
+                     float last_min[3][3], float last_max[3][3]);
+long long lsa_kplog_replayed(const lsa_ctx* ctx, int type, const lsa_point_t** pts);
+int lsa_kplog_replay_to_grids(lsa_ctx* ctx, unsigned type_mask, const double* poses, const double* times, int n, int undistort, lsa_device_grid* const grids[3],
+                              float last_min[3][3], float last_max[3][3]);
 
 /* ---- the rolling voxel map (host) ---------------------------
  * LidarSlam::RollingGrid -- slam_lib/include/LidarSlam/RollingGrid.h:63-212,

@@ -80,6 +80,9 @@ ABI_SYMBOLS = [
     "lsa_pcd_info", "lsa_pcd_read", "lsa_pcd_write", "lsa_pcd_last_error", "lsa_lzf_compress", "lsa_lzf_decompress",
     "lsa_device_grid_add_pcd", "lsa_device_grid_save_pcd", "lsa_pcd_io_times",
     "lsa_slam_add_map_points", "lsa_slam_save_maps_pcd", "lsa_slam_load_maps_pcd", "lsa_slam_map_io_counts",
+    "lsa_kplog_append", "lsa_kplog_append_points", "lsa_kplog_pop_front", "lsa_kplog_clear", "lsa_kplog_size", "lsa_kplog_count", "lsa_kplog_get",
+    "lsa_kplog_bytes", "lsa_kplog_stopped", "lsa_kplog_replay", "lsa_kplog_replayed", "lsa_kplog_replay_to_grids",
+    "lsa_slam_set_trajectory_and_rebuild_maps", "lsa_slam_logged_frames", "lsa_slam_get_logged_keypoints",
 ]
 
 PCD_ASCII, PCD_BINARY, PCD_BINARY_COMPRESSED = 0, 1, 2  # PCDFormat (PointCloudStorage.h:60-65)
@@ -87,7 +90,16 @@ PCD_FORMAT_NAMES = ["ascii", "binary", "binary_compressed"]
 
 
 class LsaError(RuntimeError):
-    pass
+    code = None  # the LSA_E_* value of the call that failed, where there was one
+
+
+E_NO_DEVICE, E_HIP, E_ARG, E_STATE, E_CAPACITY = -1, -2, -3, -4, -5
+
+
+def _error(what, rc, message):
+    e = LsaError(f"{what} failed ({rc}): {message}")
+    e.code = rc
+    return e
 
 
 class IcpLink(C.Structure):
@@ -390,6 +402,23 @@ def lib():
     L.lsa_slam_save_maps_pcd.argtypes = [vp, C.c_char_p, i32, i32]
     L.lsa_slam_load_maps_pcd.argtypes = [vp, C.c_char_p, i32, f64]
     L.lsa_slam_map_io_counts.argtypes = [vp, vp]
+    L.lsa_kplog_append.argtypes = [vp]
+    L.lsa_kplog_append_points.argtypes = [vp, vp, vp]
+    L.lsa_kplog_pop_front.argtypes = [vp]
+    L.lsa_kplog_clear.argtypes = [vp]
+    L.lsa_kplog_size.argtypes = [vp]
+    L.lsa_kplog_count.argtypes = [vp, i32, i32]
+    L.lsa_kplog_get.argtypes = [vp, i32, i32, vp, i32]
+    L.lsa_kplog_bytes.restype = C.c_ulonglong
+    L.lsa_kplog_bytes.argtypes = [vp]
+    L.lsa_kplog_stopped.argtypes = [vp]
+    L.lsa_kplog_replay.argtypes = [vp, C.c_uint, vp, vp, i32, i32, vp, vp, vp]
+    L.lsa_kplog_replayed.restype = C.c_longlong
+    L.lsa_kplog_replayed.argtypes = [vp, i32, vp]
+    L.lsa_kplog_replay_to_grids.argtypes = [vp, C.c_uint, vp, vp, i32, i32, vp, vp, vp]
+    L.lsa_slam_set_trajectory_and_rebuild_maps.argtypes = [vp, vp, i32]
+    L.lsa_slam_logged_frames.argtypes = [vp]
+    L.lsa_slam_get_logged_keypoints.argtypes = [vp, i32, i32, vp, i32]
     _lib = L
     return L
 
@@ -486,7 +515,7 @@ class Context:
 
     def _check(self, rc, what):
         if rc < 0:
-            raise LsaError(f"{what} failed ({rc}): {self.L.lsa_last_error(self.h).decode()}")
+            raise _error(what, rc, self.L.lsa_last_error(self.h).decode())
         return rc
 
     # ---- frame / extraction
@@ -905,6 +934,54 @@ class Context:
     def sync(self):
         self._check(self.L.lsa_sync(self.h), "lsa_sync")
 
+    # ---- the keypoint log (lsa_kplog_*): frames of raw keypoints in device memory, replayed under a trajectory
+    def kplog_append(self):
+        """a frame from the SET_RAW_CURRENT keypoints"""
+        self._check(self.L.lsa_kplog_append(self.h), "lsa_kplog_append")
+
+    def kplog_append_points(self, frame):
+        """a frame of the caller's keypoints: three arrays (edges, planes, blobs), any of them empty"""
+        arrs = [np.ascontiguousarray(a, POINT_DTYPE) for a in frame]
+        ptrs = (C.c_void_p * 3)(*[a.ctypes.data if a.size else None for a in arrs])
+        ns = (C.c_int * 3)(*[a.size for a in arrs])
+        self._check(self.L.lsa_kplog_append_points(self.h, ptrs, ns), "lsa_kplog_append_points")
+
+    def kplog_pop_front(self):
+        self._check(self.L.lsa_kplog_pop_front(self.h), "lsa_kplog_pop_front")
+
+    def kplog_clear(self):
+        self._check(self.L.lsa_kplog_clear(self.h), "lsa_kplog_clear")
+
+    def kplog_size(self):
+        return self.L.lsa_kplog_size(self.h)
+
+    def kplog_count(self, frame, ktype):
+        return self._check(self.L.lsa_kplog_count(self.h, frame, ktype), "lsa_kplog_count")
+
+    def kplog_get(self, frame, ktype):
+        out = np.zeros(max(self.kplog_count(frame, ktype), 1), POINT_DTYPE)
+        n = self._check(self.L.lsa_kplog_get(self.h, frame, ktype, ptr(out), out.size), "lsa_kplog_get")
+        return out[:n].copy()
+
+    def kplog_bytes(self):
+        return int(self.L.lsa_kplog_bytes(self.h))
+
+    def kplog_stopped(self):
+        return bool(self.L.lsa_kplog_stopped(self.h))
+
+    def kplog_replay(self, poses, times, undistort=True, type_mask=7):
+        """every logged frame under poses (n, 4, 4) dated times (n,) -> ([edges, planes, blobs] frames ascending,
+        last frame's min [3][3], max [3][3])"""
+        P = np.ascontiguousarray(np.asarray(poses, np.float64).reshape(-1, 16))
+        t = np.ascontiguousarray(times, np.float64)
+        n = self.kplog_size()
+        outs = [np.zeros(max(sum(self.kplog_count(f, k) for f in range(n)) if (type_mask >> k) & 1 else 0, 1), POINT_DTYPE) for k in range(3)]
+        ptrs = (C.c_void_p * 3)(*[o.ctypes.data for o in outs])
+        mn, mx = np.zeros((3, 3), np.float32), np.zeros((3, 3), np.float32)
+        self._check(self.L.lsa_kplog_replay(self.h, type_mask, ptr(P), ptr(t), P.shape[0], int(bool(undistort)), ptrs, ptr(mn), ptr(mx)), "lsa_kplog_replay")
+        sizes = [int(self.L.lsa_kplog_replayed(self.h, k, C.byref(C.c_void_p()))) for k in range(3)]
+        return [o[:s].copy() for o, s in zip(outs, sizes)], mn, mx
+
 
 class Slam:
     """LidarSlam::Slam on one MI355X.  Parameters use the reference's names (``EgoMotion=3`` ...)."""
@@ -930,7 +1007,7 @@ class Slam:
 
     def _check(self, rc, what):
         if rc < 0:
-            raise LsaError(f"{what} failed ({rc}): {self.L.lsa_slam_last_error(self.h).decode()}")
+            raise _error(what, rc, self.L.lsa_slam_last_error(self.h).decode())
         return rc
 
     def set_param(self, name, value):
@@ -1139,6 +1216,26 @@ class Slam:
 
     def context(self):
         return Context(handle=C.c_void_p(self.L.lsa_slam_context(self.h)))
+
+    # ---- the keypoint log ("LoggingTimeout" != 0) and a corrected trajectory brought back
+    def logged_frames(self):
+        """frames in the keypoint log: one per logged pose while logging is on"""
+        return self._check(self.L.lsa_slam_logged_frames(self.h), "lsa_slam_logged_frames")
+
+    def logged_keypoints(self, frame, ktype):
+        """the raw keypoints (BASE, not undistorted) logged with pose `frame` of the trajectory"""
+        n = self._check(self.L.lsa_slam_get_logged_keypoints(self.h, frame, ktype, None, 0), "lsa_slam_get_logged_keypoints")
+        out = np.zeros(max(n, 1), POINT_DTYPE)
+        n = self._check(self.L.lsa_slam_get_logged_keypoints(self.h, frame, ktype, ptr(out), out.size), "lsa_slam_get_logged_keypoints")
+        return out[:n].copy()
+
+    def set_trajectory(self, poses, times):
+        """what Slam::RunPoseGraphOptimization does after its optimizer: the logged poses replaced by poses (n, 4, 4) dated
+        times (n,) -- those of trajectory() --, the maps rebuilt from the keypoint log under them.  Raises LsaError (its
+        .code is E_STATE or E_ARG) and changes nothing when it cannot."""
+        P = np.asarray(poses, np.float64).reshape(-1, 16)
+        rows = np.ascontiguousarray(np.concatenate([P, np.asarray(times, np.float64).reshape(-1, 1)], axis=1))
+        self._check(self.L.lsa_slam_set_trajectory_and_rebuild_maps(self.h, ptr(rows), rows.shape[0]), "lsa_slam_set_trajectory_and_rebuild_maps")
 
 
 class RollingGrid:

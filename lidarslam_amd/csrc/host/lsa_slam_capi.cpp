@@ -305,6 +305,24 @@ int lsa_slam_map_io_counts(const lsa_slam* s, int counts[3])
   return LSA_OK;
 }
 
+// ---- a corrected trajectory brought back: what Slam::RunPoseGraphOptimization does after its optimizer (Slam.cxx:404-477) ----
+int lsa_slam_set_trajectory_and_rebuild_maps(lsa_slam* s, const double* poses17, int n)
+{
+  if (!s) return LSA_E_ARG;
+  return s->core.SetTrajectoryAndRebuildMaps(poses17, n);
+}
+
+int lsa_slam_logged_frames(const lsa_slam* s) { return s ? s->core.LoggedFrames() : LSA_E_ARG; }
+
+int lsa_slam_get_logged_keypoints(lsa_slam* s, int frame, int type, lsa_point_t* out, int capacity)
+{
+  if (!s || capacity < 0 || (capacity > 0 && !out)) return LSA_E_ARG;
+  const int n = s->core.GetLoggedKeypoints(frame, type, s->scratch);
+  if (n < 0) return n;
+  if (std::min(n, capacity) > 0) std::memcpy(out, s->scratch.data(), static_cast<size_t>(std::min(n, capacity)) * sizeof(lsa_point_t));
+  return n;
+}
+
 // ---- LidarSlam::RollingGrid on its own (include/lidarslam_amd.h, "the rolling voxel map") ----
 struct lsa_rolling_grid
 {

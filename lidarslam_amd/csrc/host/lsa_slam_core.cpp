@@ -207,6 +207,8 @@ void SlamCore::Reset(bool resetLog)
   {
     NbrFrameProcessed = 0;
     LogTrajectory.clear();  // LogCovariances is left alone, as in the reference (Slam.cxx:200-209)
+    if (Ctx) (void)lsa_kplog_clear(Ctx);  // LogKeypoints.clear()
+    KpLogStopped = false;
   }
 }
 
@@ -1527,17 +1529,25 @@ int SlamCore::UpdateMapsUsingTworld()
   return LSA_OK;
 }
 
-// Slam::LogCurrentFrameState (Slam.cxx:1225-1264); the keypoints log feeds the pose-graph optimisation, which is
-// out of scope, so only the poses and their covariances are kept
+// Slam::LogCurrentFrameState (Slam.cxx:1225-1264).  The raw keypoints go into the device's log (lsa_kplog.hip): one
+// launch on the registration stream, nothing of it with LoggingTimeout == 0
 void SlamCore::LogCurrentFrameState(double time)
 {
   LogTrajectory.push_back({Tworld, time});
   if (LoggingTimeout != 0.)
   {
     LogCovariances.push_back(LocalizationUncertainty.Covariance);
+    if (!KpLogStopped && lsa_kplog_append(Ctx) < 0)
+    {
+      // the frame itself is done: the failure is reported, and the log says it no longer covers the trajectory
+      KpLogStopped = true;
+      LastError = std::string("keypoint logging stopped: ") + lsa_last_error(Ctx);
+    }
     if (LoggingTimeout > 0)
       while (time - LogTrajectory.front().time > LoggingTimeout && LogTrajectory.size() > 2)
       {
+        // (the log's frames are those of the newest poses: it drops its oldest only when it covers the oldest pose)
+        if (!KpLogStopped && lsa_kplog_size(Ctx) == static_cast<int>(LogTrajectory.size())) (void)lsa_kplog_pop_front(Ctx);
         LogTrajectory.pop_front();
         LogCovariances.pop_front();
       }
@@ -1742,6 +1752,92 @@ int SlamCore::LoadMapsFromPCD(const std::string& prefix, bool resetMaps, double 
     }
     if (counts) counts[k] = n;
   }
+  return LSA_OK;
+}
+
+int SlamCore::LoggedFrames() const { return Ctx && !KpLogStopped ? lsa_kplog_size(Ctx) : 0; }
+
+int SlamCore::GetLoggedKeypoints(int frame, int type, std::vector<lsa_point_t>& out)
+{
+  if (!Ctx) return LSA_E_NO_DEVICE;
+  out.clear();
+  if (type < 0 || type > 2 || frame < 0 || frame >= LoggedFrames()) { LastError = "GetLoggedKeypoints: no such frame or keypoint type"; return LSA_E_ARG; }
+  const int n = lsa_kplog_count(Ctx, frame, type);
+  out.resize(std::max(n, 0));
+  if (n > 0) LSA_TRY(lsa_kplog_get(Ctx, frame, type, out.data(), n));
+  return n;
+}
+
+// Slam::RunPoseGraphOptimization from "Update SLAM trajectory and maps" on (Slam.cxx:404-477); the optimizer is the caller's
+int SlamCore::SetTrajectoryAndRebuildMaps(const double* poses17, int n)
+{
+  if (!Ctx) return LSA_E_NO_DEVICE;
+  const char* who = "SetTrajectoryAndRebuildMaps: ";
+  if (LoggingTimeout == 0.) { LastError = std::string(who) + "keypoint logging is off (LoggingTimeout = 0): there is nothing to rebuild the maps from"; return LSA_E_STATE; }
+  if (KpLogStopped) { LastError = std::string(who) + "keypoint logging stopped when a chunk could not be allocated; Reset(true) starts it again"; return LSA_E_STATE; }
+  const int logged = static_cast<int>(LogTrajectory.size());
+  if (!poses17 || n != logged) { LastError = std::string(who) + std::to_string(n) + " poses for " + std::to_string(logged) + " logged ones"; return LSA_E_ARG; }
+  if (n < 2) { LastError = std::string(who) + "at least two poses"; return LSA_E_ARG; }
+  for (int i = 0; i < n; ++i)
+    if (!(poses17[17 * i + 16] == LogTrajectory[i].time))
+    {
+      LastError = std::string(who) + "pose " + std::to_string(i) + " is not dated like the logged one";
+      return LSA_E_ARG;
+    }
+  if (lsa_kplog_size(Ctx) != n) { LastError = std::string(who) + "the keypoint log does not cover the logged poses (logging was switched on after the first of them)"; return LSA_E_STATE; }
+  if (DeviceMapsInUse())
+  {
+    // one Add per type: the device maps' insertion takes about three million points at a time (the chunk table of its merge
+    // kernel lives in LDS, lsa_device_grid.hip); a longer log is rebuilt with the maps on the host ("MapsOnDevice" = 0)
+    constexpr long long kDeviceAddLimit = 3000000;
+    for (int k = 0; k < 3; ++k)
+    {
+      long long sum = 0;
+      for (int i = 0; i < n && UseKeypoints[k]; ++i) sum += lsa_kplog_count(Ctx, i, k);
+      if (sum > kDeviceAddLimit)
+      {
+        LastError = std::string(who) + std::to_string(sum) + " logged keypoints of one type are more than one insertion into a device map takes (" +
+                    std::to_string(kDeviceAddLimit) + "): set MapsOnDevice = 0 for the rebuild";
+        return LSA_E_CAPACITY;
+      }
+    }
+  }
+  std::vector<double> poses(static_cast<size_t>(n) * 16), times(n);
+  for (int i = 0; i < n; ++i)
+  {
+    std::memcpy(&poses[16 * static_cast<size_t>(i)], poses17 + 17 * static_cast<size_t>(i), 16 * sizeof(double));
+    times[i] = poses17[17 * static_cast<size_t>(i) + 16];
+  }
+  // the map workers and the look-ahead are waited for, then what Reset(false) does (Slam.cxx:408)
+  Reset(false);
+  for (int i = 0; i < n; ++i) std::memcpy(LogTrajectory[i].pose.m, &poses[16 * static_cast<size_t>(i)], 16 * sizeof(double));
+  unsigned mask = 0;
+  for (int k = 0; k < 3; ++k)
+    if (UseKeypoints[k]) mask |= 1u << k;
+  float mn[3][3], mx[3][3];
+  const int undistort = Undistortion != UNDISTORTION_NONE ? 1 : 0;
+  if (DeviceMapsInUse())
+  {
+    lsa_device_grid* grids[3];
+    for (int k = 0; k < 3; ++k) grids[k] = UseKeypoints[k] ? DevMaps[k] : nullptr;
+    LSA_TRY(lsa_kplog_replay_to_grids(Ctx, mask, poses.data(), times.data(), n, undistort, grids, mn, mx));
+    for (int k = 0; k < 3; ++k)
+      if (UseKeypoints[k]) LSA_TRY(lsa_device_grid_roll(DevMaps[k], mn[k], mx[k]));
+  }
+  else
+  {
+    LSA_TRY(lsa_kplog_replay(Ctx, mask, poses.data(), times.data(), n, undistort, nullptr, mn, mx));
+    for (int k = 0; k < 3; ++k)
+    {
+      if (!UseKeypoints[k]) continue;
+      const lsa_point_t* pts = nullptr;
+      const long long cnt = lsa_kplog_replayed(Ctx, k, &pts);
+      if (cnt > 0) LocalMaps[k]->Add(pts, static_cast<std::size_t>(cnt), false, -1., false);
+      LocalMaps[k]->Roll(mn[k], mx[k]);
+    }
+  }
+  std::memcpy(Tworld.m, &poses[16 * static_cast<size_t>(n - 1)], 16 * sizeof(double));
+  std::memcpy(PreviousTworld.m, &poses[16 * static_cast<size_t>(n - 2)], 16 * sizeof(double));
   return LSA_OK;
 }
 
@@ -1956,7 +2052,20 @@ int SlamCore::SetParamValue(const std::string& name, double v)
   }
   if (name == "MapAddThreads") { LocalMaps[LSA_PLANE]->SetAddThreads(static_cast<int>(v)); return LSA_OK; }
   if (name == "MapAddThreadsEdges") { LocalMaps[LSA_EDGE]->SetAddThreads(static_cast<int>(v)); return LSA_OK; }
-  if (name == "LoggingTimeout") { LoggingTimeout = v; return LSA_OK; }
+  if (name == "LoggingTimeout")
+  {
+    LoggingTimeout = v;
+    // logging off: the poses are trimmed to two at the next frame, and keypoints logged so far would describe none of them
+    if (v == 0. && Ctx) { (void)lsa_kplog_clear(Ctx); KpLogStopped = false; }
+    return LSA_OK;
+  }
+  if (name == "LoggingStorage")
+  {
+    // PointCloudStorageType (PointCloudStorage.h:68-75): all five are accepted and mean the same here, uncompressed in HBM
+    if (!(v >= 0 && v <= 4)) { LastError = "LoggingStorage: a PointCloudStorageType (0..4)"; return LSA_E_ARG; }
+    LoggingStorage = static_cast<int>(v);
+    return LSA_OK;
+  }
   if (name == "TimeWindowDuration") { TimeWindowDuration = static_cast<float>(v); return LSA_OK; }
   if (name == "VelocityLimitLinear") { VelocityLimits[0] = static_cast<float>(v); return LSA_OK; }
   if (name == "VelocityLimitAngular") { VelocityLimits[1] = static_cast<float>(v); return LSA_OK; }
@@ -2024,6 +2133,9 @@ int SlamCore::GetParam(const std::string& name, double* v) const
   if (name == "MapAddThreads") { *v = LocalMaps[LSA_PLANE]->GetAddThreads(); return LSA_OK; }
   if (name == "MapAddThreadsEdges") { *v = LocalMaps[LSA_EDGE]->GetAddThreads(); return LSA_OK; }
   if (name == "LoggingTimeout") { *v = LoggingTimeout; return LSA_OK; }
+  if (name == "LoggingStorage") { *v = LoggingStorage; return LSA_OK; }
+  if (name == "LoggedKeypointsBytes") { *v = Ctx ? static_cast<double>(lsa_kplog_bytes(Ctx)) : 0.; return LSA_OK; }
+  if (name == "LoggedFrames") { *v = LoggedFrames(); return LSA_OK; }
   if (name == "TimeWindowDuration") { *v = TimeWindowDuration; return LSA_OK; }
   if (name == "VelocityLimitLinear") { *v = VelocityLimits[0]; return LSA_OK; }
   if (name == "VelocityLimitAngular") { *v = VelocityLimits[1]; return LSA_OK; }

@@ -118,6 +118,11 @@ public:
   // was written (type not in use, empty map) or found.  time < 0: the wall clock in whole seconds (std::time(nullptr)).
   int SaveMapsToPCD(const std::string& prefix, int format, bool filtered, int counts[3]);
   int LoadMapsFromPCD(const std::string& prefix, bool resetMaps, double time, int counts[3]);
+  // What Slam::RunPoseGraphOptimization does after its optimizer (Slam.cxx:404-477): the logged poses replaced by poses17
+  // (rows of lsa_slam_get_trajectory), the maps rebuilt from the keypoint log under them, Tworld / PreviousTworld set.
+  int SetTrajectoryAndRebuildMaps(const double* poses17, int n);
+  int LoggedFrames() const;
+  int GetLoggedKeypoints(int frame, int type, std::vector<lsa_point_t>& out);
   void HintNextStoredFrame(int slot) { NextStoredSlot = slot; }
   // Replay from host clouds: the cloud of the AddFrame call after the next one.  Its upload starts at once (pinned
   // staging, copy stream, a thread of its own), its keypoints are extracted beside the registration of the frame in
@@ -198,6 +203,8 @@ public:
   bool ComplyMotionLimits = true;
   // Slam::LoggingTimeout (Slam.h:425-438): 0 keeps the last two poses, > 0 the poses of that many seconds, < 0 all
   double LoggingTimeout = 0.;
+  // Slam::LoggingStorage (Slam.h:440-447): accepted and remembered; the keypoint log is uncompressed in HBM whatever it says
+  int LoggingStorage = 0;
   double Latency = 0.;  // duration of the last AddFrame [s] (Slam::GetLatency)
   Pose BaseToLidarOffset = Pose::Identity();  // device 0
   lsa_extract_params_t ExtractParams;         // device 0
@@ -285,6 +292,7 @@ private:
   float PreviousVelocity[2] = {0.f, 0.f};
   long long EgoMatchSerial[3] = {0, 0, 0}, LocMatchSerial[3] = {0, 0, 0};  // lsa_match_serial after the last iteration
   void LogCurrentFrameState(double time);
+  bool KpLogStopped = false;  // a chunk of the keypoint log could not be allocated: nothing more is logged until Reset(true)
   Pose InterpolateScanPose(double time) const;
   int InitUndistortion();
   void InitUndistortion(double t0, double t1);

@@ -10,6 +10,7 @@
 //                (cell_start[ncells+1], cell-sorted float4 xyz|index)
 //   match[k]     SoA residual records rec[16][K] (A 9, P 3, X 3, weight), status[K]
 //   reduce       per-block partials of the normal equations, 29 doubles each
+//   keypoint log AoS lsa_point_t in chunks of 32 MiB, a frame's three types one after the other (lsa_kplog.hip; only with logging on)
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>
@@ -130,6 +131,8 @@ struct PendingEvent
   int stat;
   hipEvent_t a, b;
 };
+
+struct KpLog;  // lsa_kplog.hip
 
 }  // namespace lsa
 
@@ -319,6 +322,10 @@ struct lsa_ctx
   std::mutex grave_mutex;
   std::vector<void*> grave_dev, grave_host;
   int bbox_n[3] = {0, 0, 0};
+  // the keypoint log (lsa_kplog.hip): made by the first append, so a context that never logs holds nothing of it
+  lsa::KpLog* kplog = nullptr;
+  size_t kplog_chunk_bytes = (size_t)32 << 20;  // lsa_debug_set "kplog_chunk_kib"
+  int debug_kplog_fail_alloc = 0;               // lsa_debug_set "kplog_fail_alloc": the next chunk allocations fail (the callers' error path)
 
   // profiling
   bool profiling = false;
@@ -358,6 +365,7 @@ namespace lsa
 int lm_cache_capacity();
 extern std::atomic<int> g_live_contexts;  // contexts of this process (lsa_lm.hip: a solve's share of the chip)
 int lm_blocks_share();
+void kplog_destroy(lsa_ctx* ctx);  // lsa_kplog.hip
 inline void retire_dev(lsa_ctx* ctx, void* p)
 {
   if (!p) return;

@@ -1,5 +1,5 @@
-// lsa_device_grid_io.h -- what the map-file unit (lsa_pcd.hip) needs of a device grid (lsa_device_grid.hip): the batch
-// buffer an insertion reads, the insertion itself, and RollingGrid::Get left on the device.
+// lsa_device_grid_io.h -- what the map-file unit (lsa_pcd.hip) and the keypoint log's replay (lsa_kplog.hip) need of a device
+// grid (lsa_device_grid.hip): the batch buffer an insertion reads, the insertion itself, and RollingGrid::Get left on the device.
 #pragma once
 #include "lsa_ctx.h"
 

@@ -1145,6 +1145,8 @@ int lsa_debug_set(lsa_ctx* ctx, const char* name, int value)
   else if (n == "accum_blocks") ctx->accum_blocks = value < 0 ? c.accum_blocks : std::min(std::max(value, 1), kAccumBlocksMax);
   else if (n == "mailbox_check") ctx->mailbox_check = value < 0 ? c.mailbox_check : value != 0;
   else if (n == "pcd_lds") ctx->pcd_lds = value < 0 ? -1 : (value != 0);  // lsa_pcd.hip: the form of the two conversion kernels
+  else if (n == "kplog_chunk_kib") ctx->kplog_chunk_bytes = value < 0 ? ((size_t)32 << 20) : (size_t)std::max(value, 1) << 10;  // lsa_kplog.hip: chunks made from now on
+  else if (n == "kplog_fail_alloc") ctx->debug_kplog_fail_alloc = value > 0 ? 1 : 0;
   else return ctx->fail(LSA_E_ARG, "lsa_debug_set: no such knob");
   return LSA_OK;
 }

@@ -12,9 +12,10 @@
 // without PCL (such as the build container).  Poses are exchanged as row-major 4x4 doubles; with Eigen
 // present Transform::GetIsometry() is offered as well.
 //
-// Outside the hot path and therefore present as signature-compatible "not supported on this build"
-// members only (they warn once and change nothing): pose-graph optimisation, PCD map IO, wheel odometry / IMU
-// constraints, keypoint logging storage.
+// Beyond the per-frame path the mirror also carries PCD map IO, the wheel odometer / IMU gravity constraints, the keypoint
+// log (SetLoggingTimeout, SetLoggingStorage, GetLoggedKeypoints) and SetTrajectoryAndRebuildMaps, which brings a corrected
+// trajectory back.  The pose-graph OPTIMIZER itself (g2o) is not part of this build: RunPoseGraphOptimization is present
+// with the reference's signature, warns once and changes nothing.
 #pragma once
 #include <algorithm>
 #include <array>
@@ -277,17 +278,41 @@ public:
   }
   const std::string& GetLastError() const { return this->LastError; }
 
-  // ---- outside the scan-matching hot path (pose-graph optimisation, keypoint logging).  Present with the
-  // reference's signatures so that LidarSlamNode.cxx / vtkSlam.cxx compile unchanged; each warns once and does nothing, the
-  // way the reference itself answers RunPoseGraphOptimization without g2o
-  // (slam_lib/src/Slam.cxx:355-366: "SLAM PoseGraphOptimization requires G2O, but it was not found.").
+  // ---- the pose-graph optimizer (g2o) is not part of this build.  Present with the reference's signature so that
+  // LidarSlamNode.cxx / vtkSlam.cxx compile unchanged; it warns once and does nothing, the way the reference itself answers
+  // RunPoseGraphOptimization without g2o (slam_lib/src/Slam.cxx:355-366: "SLAM PoseGraphOptimization requires G2O, but it
+  // was not found.").  What the reference does AFTER its optimizer is SetTrajectoryAndRebuildMaps below: run the optimizer
+  // of your choice on GetTrajectory() / GetCovariances() and bring its result there.
 #ifdef LSA_HAVE_EIGEN
   void RunPoseGraphOptimization(const std::vector<Transform>&, const std::vector<std::array<double, 9>>&, Eigen::Isometry3d&, const std::string& = "")
 #else
   void RunPoseGraphOptimization(const std::vector<Transform>&, const std::vector<std::array<double, 9>>&, std::array<double, 16>&, const std::string& = "")
 #endif
   {
-    this->NotSupported("RunPoseGraphOptimization", "pose-graph optimisation (g2o) is not part of this build: maps and trajectory are left unchanged");
+    this->NotSupported("RunPoseGraphOptimization", "the pose-graph optimizer (g2o) is not part of this build: maps and trajectory are left unchanged; "
+                                                   "bring an optimizer's result with SetTrajectoryAndRebuildMaps");
+  }
+  // ---- a corrected trajectory brought back (Slam.cxx:404-477, everything after the optimizer): the logged poses are
+  // replaced by `poses` (as many as GetTrajectory() gives, each with its logged time), every logged frame's keypoints are
+  // re-projected under them, the maps are rebuilt from the aggregate and rolled onto the last frame, Tworld / PreviousTworld
+  // are set.  Needs SetLoggingTimeout(!= 0) while the frames were added.  A failure goes through GetLastError() and
+  // changes nothing.
+  void SetTrajectoryAndRebuildMaps(const std::vector<Transform>& poses)
+  {
+    std::vector<double> rows(poses.size() * 17);
+    for (std::size_t i = 0; i < poses.size(); ++i)
+    {
+      std::memcpy(rows.data() + 17 * i, poses[i].matrix.data(), 16 * sizeof(double));
+      rows[17 * i + 16] = poses[i].time;
+    }
+    const int rc = lsa_slam_set_trajectory_and_rebuild_maps(this->Handle, rows.data(), static_cast<int>(poses.size()));
+    this->LastError = rc < 0 ? std::string("SetTrajectoryAndRebuildMaps: ") + lsa_slam_last_error(this->Handle) : std::string();
+  }
+  // the raw keypoints (BASE, not undistorted) logged with pose `frame` of GetTrajectory()
+  PointCloud::Ptr GetLoggedKeypoints(Keypoint k, std::size_t frame)
+  {
+    return this->Fetch([&](lsa_point_t* out, int cap) { return std::min(cap, lsa_slam_get_logged_keypoints(this->Handle, static_cast<int>(frame), k, out, cap)); },
+                       this->BaseFrameId);
   }
   // ---- the keypoint maps as PCD files (Slam.cxx:504-543): <prefix>edges.pcd, <prefix>planes.pcd, <prefix>blobs.pcd.  A
   // failure is reported through GetLastError(); the first call of each per object says on stderr what it wrote or loaded.
@@ -301,9 +326,9 @@ public:
     const int rc = lsa_slam_load_maps_pcd(this->Handle, filePrefix.c_str(), resetMaps ? 1 : 0, -1.);
     this->ReportMapIO("LoadMapsFromPCD", "loaded from", filePrefix, rc);
   }
-  // keypoint logging feeds the pose-graph optimisation only: the value is remembered, nothing is logged
-  void SetLoggingStorage(PointCloudStorageType s) { this->LoggingStorage = s; }
-  PointCloudStorageType GetLoggingStorage() const { return this->LoggingStorage; }
+  // the library's parameter "LoggingStorage".  All five values are accepted and mean the same thing here: the keypoint
+  // log is kept uncompressed in the device's memory (32 B a keypoint); nothing is compressed
+  LSA_SLAM_ENUM_PARAM(LoggingStorage, PointCloudStorageType)
   // ---- wheel odometer / IMU gravity constraints (Slam.h:331-343, Slam.cxx:223-227, 1582-1598): the terms enter every ICP
   // iteration of the localization solve and its covariance; the weights and the time offset are the library's
   // parameters WheelOdomWeight, GravityWeight, SensorTimeOffset
@@ -510,7 +535,6 @@ private:
   lsa_slam* Handle = nullptr;
   mutable std::set<std::string> Warned;
   std::vector<lsa_point_t> Staging;  // Fetch
-  PointCloudStorageType LoggingStorage = PointCloudStorageType::PCL_CLOUD;
   std::map<std::uint8_t, KeypointExtractorPtr> KeyPointsExtractors;
   std::uint64_t CurrentStamp = 0;
   std::string WorldFrameId = "world", BaseFrameId = "base";

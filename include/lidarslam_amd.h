@@ -379,6 +379,21 @@ int lsa_download_match(lsa_ctx* ctx, int type, uint8_t* status, double* weights,
  * and the solves run on given residual blocks.  Rows whose status is not LSA_MATCH_SUCCESS are stored as given (any
  * payload, NaN included): the reductions never read them into a sum.  The buffer grows as lsa_match grows it. */
 int lsa_upload_match(lsa_ctx* ctx, int type, const uint8_t* status, const double* records, int n, double saturation);
+#define LSA_KNN_MAX 16 /* slots per query of the neighbour lists (the search holds at most 16 neighbours) */
+/* Test hook: the neighbour lists the last search of `type` left in memory -- the two-launch form (lsa_set_fused_match 2),
+ * the staged form (0) and lsa_overlap's nearest-neighbour search leave them; the one-launch form (1) keeps them on the
+ * chip, and 0 is returned after it.  For the first n = min(capacity, queries) queries, one row of LSA_KNN_MAX slots per
+ * query: idx[q * LSA_KNN_MAX + s] is the index in the target (the order it was given in) of the (s + 1)-th nearest
+ * point, d2[q * LSA_KNN_MAX + s] the float squared distance the search compared, ascending by (distance, index).  A slot
+ * at or beyond the number of neighbours found holds (INT32_MAX, +inf) where the search asked for it and (-1, +inf)
+ * beyond the k it asked for.  cnt[q] as stored:
+ *   >= 0  the number of neighbours found, min(k, target size);
+ *   -1    planes and blobs only: the k-th neighbour is proven to lie beyond the rejection distance
+ *         (NEIGHBORS_TOO_FAR whatever the neighbours are) -- the slots need not hold the nearest points;
+ *   -2    two-launch form only: no block of the grid settled the query, the model kernel searched the whole target for
+ *         it and wrote the answer into the slots -- the count stays as the search kernel left it.
+ * Returns n.  Host code and copies only. */
+int lsa_download_knn(lsa_ctx* ctx, int type, int* idx, float* d2, int* cnt, int capacity);
 
 /* ------------------------------------------------------------------------- */
 /* Seam 3: LocalOptimizer::Solve() -- slam_lib/src/LocalOptimizer.cxx:74-102.

@@ -37,6 +37,7 @@ from ._native import (  # noqa: F401
 __all__ = ["Context", "Slam", "ExtractParams", "MatchParams", "POINT_DTYPE", "lib", "LsaError", "read_pcd", "write_pcd"]
 
 TARGET_MAP, TARGET_PREVIOUS = 0, 1
+KNN_MAX = 16  # LSA_KNN_MAX: slots per query of the neighbour lists (Context.knn_lists)
 
 DEBUG_INFORMATION_NAMES = [
     "EgoMotion: edges used", "EgoMotion: planes used", "Localization: edges used", "Localization: planes used",
@@ -56,7 +57,7 @@ ABI_SYMBOLS = [
     "lsa_set_azimuthal_resolution", "lsa_extract_keypoints", "lsa_extract_keypoints_more", "lsa_extract_prefetch", "lsa_extract_prefetch_adopted", "lsa_transform_frame_at", "lsa_set_keypoint_types", "lsa_download_keypoints", "lsa_keypoint_count",
     "lsa_download_debug", "lsa_nb_laser_rings", "lsa_transform_keypoints", "lsa_set_target", "lsa_set_target_from_set", "lsa_prepare_previous_targets", "lsa_prepared_targets_adopted", "lsa_target_staging", "lsa_set_target_staged", "lsa_stage_target_ahead", "lsa_drop_target_ahead", "lsa_staged_targets_adopted",
     "lsa_target_size", "lsa_download_target", "lsa_set_target_cell_size", "lsa_set_knn_lanes", "lsa_set_fused_match", "lsa_set_knn_rounds", "lsa_match_slow_queries", "lsa_match_exhaustive_queries", "lsa_match_route_stats", "lsa_match_trace", "lsa_set_keypoints", "lsa_match", "lsa_match_types", "lsa_match_types_undistorted",
-    "lsa_download_match", "lsa_upload_match", "lsa_overlap", "lsa_accumulate", "lsa_mailbox_active", "lsa_solve", "lsa_solve_device", "lsa_solve_device_fallbacks", "lsa_solve_device_begin", "lsa_solve_device_end", "lsa_solve_device_drop", "lsa_icp_gate", "lsa_icp_link", "lsa_solve_device_begin_linked", "lsa_icp_link_peek", "lsa_icp_link_expected", "lsa_icp_post", "lsa_icp_cancel", "lsa_icp_abandon", "lsa_debug_set", "lsa_solve_device_shape", "lsa_accumulate_shape", "lsa_match_types_gated", "lsa_solve_device_trace", "lsa_registration_error", "lsa_selftest_math", "lsa_selftest_numerics", "lsa_reset_working_keypoints", "lsa_undistort", "lsa_working_time_range",
+    "lsa_download_match", "lsa_upload_match", "lsa_download_knn", "lsa_overlap", "lsa_accumulate", "lsa_mailbox_active", "lsa_solve", "lsa_solve_device", "lsa_solve_device_fallbacks", "lsa_solve_device_begin", "lsa_solve_device_end", "lsa_solve_device_drop", "lsa_icp_gate", "lsa_icp_link", "lsa_solve_device_begin_linked", "lsa_icp_link_peek", "lsa_icp_link_expected", "lsa_icp_post", "lsa_icp_cancel", "lsa_icp_abandon", "lsa_debug_set", "lsa_solve_device_shape", "lsa_accumulate_shape", "lsa_match_types_gated", "lsa_solve_device_trace", "lsa_registration_error", "lsa_selftest_math", "lsa_selftest_numerics", "lsa_reset_working_keypoints", "lsa_undistort", "lsa_working_time_range",
     "lsa_working_bbox", "lsa_working_bboxes", "lsa_localization_begin", "lsa_arm_localization_boxes", "lsa_keypoint_bboxes_begin", "lsa_keypoint_bboxes_begin_interp", "lsa_keypoint_boxes_predicted_mark", "lsa_keypoint_boxes_predicted", "lsa_keypoint_time_range", "lsa_keypoint_bboxes_end", "lsa_download_transformed", "lsa_stage_transformed", "lsa_staged_transformed", "lsa_transform_frame", "lsa_profile_enable", "lsa_profile_select", "lsa_profile_reset",
     "lsa_profile_get", "lsa_slam_create", "lsa_slam_destroy", "lsa_slam_last_error", "lsa_slam_set_param",
     "lsa_slam_get_param", "lsa_slam_reset", "lsa_slam_clear_maps", "lsa_slam_add_frame", "lsa_slam_store_frame", "lsa_slam_add_stored_frame", "lsa_slam_hint_next_stored_frame", "lsa_slam_hint_next_frame", "lsa_upload_frame_begin", "lsa_upload_frame_ready", "lsa_upload_frame_adopt", "lsa_upload_frame_forget", "lsa_profile_event_overhead_us", "lsa_upload_robosense_frame", "lsa_pin_host_memory", "lsa_unpin_host_memory", "lsa_collect_garbage", "lsa_uploads_adopted", "lsa_extract_prefetch_uploaded",
@@ -286,6 +287,7 @@ def lib():
     L.lsa_match_types_undistorted.argtypes = [vp, i32, C.c_uint, C.POINTER(MatchParams), vp, vp, vp, vp, f64, f64]
     L.lsa_download_match.argtypes = [vp, i32, vp, vp, vp, i32]
     L.lsa_upload_match.argtypes = [vp, i32, vp, vp, i32, f64]
+    L.lsa_download_knn.argtypes = [vp, i32, vp, vp, vp, i32]
     L.lsa_accumulate.argtypes = [vp, C.c_uint, vp, i32, vp, vp, vp, vp]
     L.lsa_solve.argtypes = [vp, C.c_uint, vp, i32, i32, vp, vp, vp]
     L.lsa_registration_error.argtypes = [vp, C.c_uint, vp, i32, vp, vp]
@@ -684,6 +686,15 @@ class Context:
         records = np.ascontiguousarray(records, np.float64).reshape(-1, 16)
         assert records.shape[0] == status.size
         self._check(self.L.lsa_upload_match(self.h, ktype, ptr(status), ptr(records), status.size, C.c_double(saturation)), "lsa_upload_match")
+
+    def knn_lists(self, ktype, capacity):
+        """lsa_download_knn (test hook): (idx (n, 16) int32, d2 (n, 16) float32, cnt (n,) int32) of the first
+        min(capacity, queries) queries of the last search of `ktype` that left its neighbour lists in memory; cnt -1: k-th neighbour beyond the rejection distance, -2: whole-target search"""
+        idx = np.zeros((capacity, KNN_MAX), np.int32)
+        d2 = np.zeros((capacity, KNN_MAX), np.float32)
+        cnt = np.zeros(capacity, np.int32)
+        n = self._check(self.L.lsa_download_knn(self.h, ktype, ptr(idx), ptr(d2), ptr(cnt), capacity), "lsa_download_knn")
+        return idx[:n], d2[:n], cnt[:n]
 
     def match_results(self, ktype, query_set=None, records=True, n=None):
         if n is None:

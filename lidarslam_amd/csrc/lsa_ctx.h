@@ -96,6 +96,8 @@ struct MatchBuf
   int* slow_list = nullptr;    // [cap] queries handed to the second kNN kernel ...
   float4* slow_pts = nullptr;  // [cap] ... in target coordinates, w = upper bound of the k-th squared distance
   int k = 0;                   // number of queries of the last match
+  int knn_n = 0;               // queries whose lists the last search left in knn_* (0: none -- the one-launch form keeps them on the chip)
+  int knn_k = 0;               // ... and the neighbours it was asked for (lsa_download_knn)
   int cap = 0;
   double sat = 1.0;
   bool valid = false;

@@ -113,6 +113,7 @@ int ensure_match(lsa_ctx* ctx, int type, int k)
   LSA_HIP(ctx, dev_alloc(ctx, &b.slow_list, (size_t)cap));
   LSA_HIP(ctx, dev_alloc(ctx, &b.slow_pts, (size_t)cap));
   b.cap = cap;
+  b.knn_n = 0;  // the lists stayed in the outgrown buffers
   return LSA_OK;
 }
 

@@ -88,6 +88,7 @@ static int match_prepare(lsa_ctx* ctx, int slot, int type, int query_set, const 
     if (rc) return rc;
   }
   mb.k = nq;
+  mb.knn_n = 0;  // until a search that leaves its lists in memory is enqueued for it
   mb.sat = p->saturation_distance;
   mb.valid = true;
   ctx->last_match_type = type;
@@ -316,6 +317,33 @@ int lsa_upload_match(lsa_ctx* ctx, int type, const uint8_t* status, const double
   mb.sat = saturation;
   mb.valid = true;
   return LSA_OK;
+}
+
+// Test hook.  The lists live on the device as [kKnnMax][cap] (slot s of query q at s * cap + q): copied as they are,
+// one strided copy each, and turned into rows per query on the host.
+int lsa_download_knn(lsa_ctx* ctx, int type, int* idx, float* d2, int* cnt, int capacity)
+{
+  static_assert(LSA_KNN_MAX == kKnnMax, "the header's row length is the buffers'");
+  if (!ctx || type < 0 || type > 2 || !idx || !d2 || !cnt) return ctx ? ctx->fail(LSA_E_ARG, "lsa_download_knn: bad argument") : LSA_E_ARG;
+  LSA_HIP(ctx, hipSetDevice(ctx->device));
+  const MatchBuf& mb = ctx->match[type];
+  const int n = std::min(capacity, mb.knn_n);
+  if (n <= 0) return 0;
+  std::vector<int> si((size_t)kKnnMax * n);
+  std::vector<float> sd((size_t)kKnnMax * n);
+  LSA_HIP(ctx, hipStreamSynchronize(ctx->stream));  // (the staged form's side streams have been joined into it)
+  LSA_HIP(ctx, hipMemcpy2D(si.data(), (size_t)n * sizeof(int), mb.knn_idx, (size_t)mb.cap * sizeof(int), (size_t)n * sizeof(int), kKnnMax, hipMemcpyDeviceToHost));
+  LSA_HIP(ctx, hipMemcpy2D(sd.data(), (size_t)n * sizeof(float), mb.knn_d2, (size_t)mb.cap * sizeof(float), (size_t)n * sizeof(float), kKnnMax, hipMemcpyDeviceToHost));
+  LSA_HIP(ctx, hipMemcpy(cnt, mb.knn_cnt, (size_t)n * sizeof(int), hipMemcpyDeviceToHost));
+  const int k = std::min(std::max(mb.knn_k, 0), kKnnMax);
+  for (int q = 0; q < n; ++q)
+    for (int s = 0; s < kKnnMax; ++s)
+    {
+      // slots the search was not asked for hold whatever an earlier one left: handed out as "none"
+      idx[(size_t)q * kKnnMax + s] = s < k ? si[(size_t)s * n + q] : -1;
+      d2[(size_t)q * kKnnMax + s] = s < k ? sd[(size_t)s * n + q] : INFINITY;
+    }
+  return n;
 }
 
 long long lsa_match_serial(const lsa_ctx* ctx, int type)

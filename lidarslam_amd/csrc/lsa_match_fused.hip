@@ -1224,6 +1224,13 @@ int enqueue_fused_match(lsa_ctx* ctx, const MatchPrep* preps, int count, const d
   a.fuse_model = ctx->fused_model ? 1 : 0;
   for (int k = 0; k < 3; ++k)
     if (a.t[k].mblocks > 0 && a.t[k].nblocks == 0) a.fuse_model = 0;
+  // the two-launch form leaves the lists of every type it searches in memory (lsa_download_knn)
+  for (int k = 0; k < 3; ++k)
+    if (a.t[k].nblocks > 0)
+    {
+      ctx->match[k].knn_n = a.fuse_model ? 0 : a.t[k].nq;
+      ctx->match[k].knn_k = a.t[k].k;
+    }
   // the list lengths compiled in: the reference's defaults (edges 8 ego-motion / 10 localization, planes 5, no blobs)
   // get kernels of their own -- one kernel has one register budget, the longest list in it sets it for every type
   const int ke = kmax[0], kp = kmax[1];

@@ -496,6 +496,8 @@ namespace lsa
 // k = 1, whose speed depends on it.
 void enqueue_staged_knn(lsa_ctx* ctx, const lsa_point_t* q, int nq, const Rigid& pose, int k, float far_d2, int type, int ti, hipStream_t st, int* hist)
 {
+  ctx->match[type].knn_n = nq;
+  ctx->match[type].knn_k = k;
   if (k <= 5) launch_knn<5>(ctx, q, nq, pose, k, far_d2, type, ti, st, hist);
   else if (k <= 8) launch_knn<8>(ctx, q, nq, pose, k, far_d2, type, ti, st, hist);
   else launch_knn<16>(ctx, q, nq, pose, k, far_d2, type, ti, st, hist);

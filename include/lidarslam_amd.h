@@ -186,7 +186,10 @@ void lsa_set_azimuthal_resolution(lsa_ctx* ctx, float rad);
 /* Runs a3-a8 of SURVEY.md 8a on the current frame.  The previous call's
  * keypoints become LSA_SET_RAW_PREVIOUS (Slam.cxx:751).  counts[k] = number of
  * keypoints of type k; keypoints stay on the device, ordered ring-major /
- * index-ascending as SSKE.cxx:575-589 pushes them. */
+ * index-ascending as SSKE.cxx:575-589 pushes them.  A frame that is refused
+ * (laser_id >= 512, more than 8192 points on one ring: LSA_E_CAPACITY) changes
+ * neither set: the next frame's LSA_SET_RAW_PREVIOUS is the last frame that
+ * was extracted. */
 int lsa_extract_keypoints(lsa_ctx* ctx, const lsa_extract_params_t* params, int counts[3]);
 /* A further frame of the same Slam::AddFrames call (another LiDAR device, Slam.cxx:753-801): the frame in the context
  * is extracted with `params` (and the azimuthal resolution set for that device) and its keypoints are appended to
@@ -680,6 +683,18 @@ int lsa_selftest_math(lsa_ctx* ctx, int fn, const double* x, const double* y, in
  *   11  36  42  JACOBI6_HOST  in: A[36]. out: evals[6], V[36]
  * fn 8-11 run on the CPU and accept ctx == NULL. */
 int lsa_selftest_numerics(lsa_ctx* ctx, int fn, const double* in, int n, double* out);
+/* Device self-test of the keypoint labelling (SetKeyPointsLabels, SSKE.cxx:474-590) on its own: the labelling kernel of
+ * the extraction, launched as the extraction launches it, on scores and validity the caller provides instead of those
+ * the curvature kernels computed.  nrings (1..512) rings of ring_lengths[r] >= 0 points; the four score arrays and
+ * `valid` (bit k = valid for keypoint type k) hold the rings one after the other.  Scores are what the curvature
+ * kernel can produce: non-negative, finite or +inf, no -0.0, no NaN.  Of params, neighbor_width and the five
+ * thresholds are used.  label_out / valid_out: one byte per point (bit k = type k; validity after the labelling, the
+ * bit of a labelled point set back as SSKE.cxx:584 does); ring_counts_out[3 * r + k] = keypoints of type k on ring r.
+ * Returns the number of points, LSA_E_CAPACITY when a ring has more than 8192 points (as the extraction does).  The
+ * per-point arrays of the last extraction (lsa_download_debug) are overwritten; the keypoint sets are not touched. */
+int lsa_selftest_labels(lsa_ctx* ctx, const lsa_extract_params_t* params, const int* ring_lengths, int nrings, const float* sin_angle,
+                        const float* depth_gap, const float* saliency, const float* intensity_gap, const uint8_t* valid,
+                        uint8_t* label_out, uint8_t* valid_out, int* ring_counts_out);
 /* Diagnostic: `blocks` single-wave workgroups sleep-spinning for `ms` (<= 2000) milliseconds on a side stream. */
 int lsa_selftest_keep_busy(lsa_ctx* ctx, int ms, int blocks);
 

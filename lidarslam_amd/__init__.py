@@ -57,7 +57,7 @@ ABI_SYMBOLS = [
     "lsa_set_azimuthal_resolution", "lsa_extract_keypoints", "lsa_extract_keypoints_more", "lsa_extract_prefetch", "lsa_extract_prefetch_adopted", "lsa_transform_frame_at", "lsa_set_keypoint_types", "lsa_download_keypoints", "lsa_keypoint_count",
     "lsa_download_debug", "lsa_nb_laser_rings", "lsa_transform_keypoints", "lsa_set_target", "lsa_set_target_from_set", "lsa_prepare_previous_targets", "lsa_prepared_targets_adopted", "lsa_target_staging", "lsa_set_target_staged", "lsa_stage_target_ahead", "lsa_drop_target_ahead", "lsa_staged_targets_adopted",
     "lsa_target_size", "lsa_download_target", "lsa_set_target_cell_size", "lsa_set_knn_lanes", "lsa_set_fused_match", "lsa_set_knn_rounds", "lsa_match_slow_queries", "lsa_match_exhaustive_queries", "lsa_match_route_stats", "lsa_match_trace", "lsa_set_keypoints", "lsa_match", "lsa_match_types", "lsa_match_types_undistorted",
-    "lsa_download_match", "lsa_upload_match", "lsa_download_knn", "lsa_overlap", "lsa_accumulate", "lsa_mailbox_active", "lsa_solve", "lsa_solve_device", "lsa_solve_device_fallbacks", "lsa_solve_device_begin", "lsa_solve_device_end", "lsa_solve_device_drop", "lsa_icp_gate", "lsa_icp_link", "lsa_solve_device_begin_linked", "lsa_icp_link_peek", "lsa_icp_link_expected", "lsa_icp_post", "lsa_icp_cancel", "lsa_icp_abandon", "lsa_debug_set", "lsa_solve_device_shape", "lsa_accumulate_shape", "lsa_match_types_gated", "lsa_solve_device_trace", "lsa_registration_error", "lsa_selftest_math", "lsa_selftest_numerics", "lsa_reset_working_keypoints", "lsa_undistort", "lsa_working_time_range",
+    "lsa_download_match", "lsa_upload_match", "lsa_download_knn", "lsa_overlap", "lsa_accumulate", "lsa_mailbox_active", "lsa_solve", "lsa_solve_device", "lsa_solve_device_fallbacks", "lsa_solve_device_begin", "lsa_solve_device_end", "lsa_solve_device_drop", "lsa_icp_gate", "lsa_icp_link", "lsa_solve_device_begin_linked", "lsa_icp_link_peek", "lsa_icp_link_expected", "lsa_icp_post", "lsa_icp_cancel", "lsa_icp_abandon", "lsa_debug_set", "lsa_solve_device_shape", "lsa_accumulate_shape", "lsa_match_types_gated", "lsa_solve_device_trace", "lsa_registration_error", "lsa_selftest_math", "lsa_selftest_numerics", "lsa_selftest_labels", "lsa_reset_working_keypoints", "lsa_undistort", "lsa_working_time_range",
     "lsa_working_bbox", "lsa_working_bboxes", "lsa_localization_begin", "lsa_arm_localization_boxes", "lsa_keypoint_bboxes_begin", "lsa_keypoint_bboxes_begin_interp", "lsa_keypoint_boxes_predicted_mark", "lsa_keypoint_boxes_predicted", "lsa_keypoint_time_range", "lsa_keypoint_bboxes_end", "lsa_download_transformed", "lsa_stage_transformed", "lsa_staged_transformed", "lsa_transform_frame", "lsa_profile_enable", "lsa_profile_select", "lsa_profile_reset",
     "lsa_profile_get", "lsa_slam_create", "lsa_slam_destroy", "lsa_slam_last_error", "lsa_slam_set_param",
     "lsa_slam_get_param", "lsa_slam_reset", "lsa_slam_clear_maps", "lsa_slam_add_frame", "lsa_slam_store_frame", "lsa_slam_add_stored_frame", "lsa_slam_hint_next_stored_frame", "lsa_slam_hint_next_frame", "lsa_upload_frame_begin", "lsa_upload_frame_ready", "lsa_upload_frame_adopt", "lsa_upload_frame_forget", "lsa_profile_event_overhead_us", "lsa_upload_robosense_frame", "lsa_pin_host_memory", "lsa_unpin_host_memory", "lsa_collect_garbage", "lsa_uploads_adopted", "lsa_extract_prefetch_uploaded",
@@ -297,6 +297,7 @@ def lib():
     L.lsa_accumulate_shape.argtypes = [vp, vp]
     L.lsa_selftest_math.argtypes = [vp, i32, vp, vp, i32, vp]
     L.lsa_selftest_numerics.argtypes = [vp, i32, vp, i32, vp]
+    L.lsa_selftest_labels.argtypes = [vp, C.POINTER(ExtractParams), vp, i32, vp, vp, vp, vp, vp, vp, vp, vp]
     L.lsa_reset_working_keypoints.argtypes = [vp]
     L.lsa_undistort.argtypes = [vp, vp, vp, f64, f64]
     L.lsa_working_time_range.argtypes = [vp, vp, vp]
@@ -856,6 +857,20 @@ class Context:
     def selftest_numerics(self, fn, records):
         """lsa_selftest_numerics on the device (fn 0-7) or the host twins (fn 8-11): records (n, IN) -> (n, OUT)"""
         return selftest_numerics(fn, records, self)
+
+    def selftest_labels(self, ring_lengths, sin_angle, depth_gap, saliency, intensity_gap, valid, params=None):
+        """lsa_selftest_labels: the labelling kernel alone on the given scores and validity bytes, rings one after the
+        other -> (label, validity afterwards, ring_counts (nrings, 3))"""
+        params = params or ExtractParams()
+        lens = np.ascontiguousarray(ring_lengths, np.int32)
+        n = int(lens.sum())
+        scores = [np.ascontiguousarray(a, np.float32) for a in (sin_angle, depth_gap, saliency, intensity_gap)]
+        valid = np.ascontiguousarray(valid, np.uint8)
+        assert all(a.size == n for a in scores) and valid.size == n
+        label, after, counts = np.zeros(n, np.uint8), np.zeros(n, np.uint8), np.zeros((lens.size, 3), np.int32)
+        self._check(self.L.lsa_selftest_labels(self.h, C.byref(params), ptr(lens), lens.size, *[ptr(a) for a in scores], ptr(valid), ptr(label),
+                                               ptr(after), ptr(counts)), "lsa_selftest_labels")
+        return label, after, counts
 
     # ---- undistortion / transforms
     def reset_working_keypoints(self):

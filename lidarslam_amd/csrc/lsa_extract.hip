@@ -654,6 +654,9 @@ __global__ __launch_bounds__(kCompactThreads) void k_compact(const float4* __res
   const int r = blockIdx.x;
   const int nr = ring_meta[0];
   if (r >= nr) return;
+  // an extraction that fails (a laser id or a ring k_label does not take: its labels and counts are those of an earlier
+  // frame, or none) writes no keypoints: the counts stay 0 and the buffers as they were, extract_frame undoes the rest
+  if (ring_meta[2] != 0) return;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   if (wave < 3)
   {
@@ -777,6 +780,13 @@ ExtractConst make_const(const lsa_extract_params_t* p, float az_res)
 
 }  // namespace
 
+// k_label on the context's per-point arrays: one block per possible ring (the extraction and lsa_selftest_labels)
+static void launch_label(lsa_ctx* ctx, const ExtractConst& c, hipStream_t st, int* ring_meta)
+{
+  hipLaunchKernelGGL(k_label, dim3(kMaxRings), dim3(kLabelThreads), 0, st, ctx->score[0], ctx->score[1], ctx->score[2], ctx->score[3], ctx->ring_start,
+                     ctx->ring_len, ring_meta, c, ctx->valid, ctx->label, ctx->ring_counts);
+}
+
 extern "C" {
 
 // The extraction kernels of one frame on `st`: ring bucketing, validity, curvature scores, labels, compaction into
@@ -811,8 +821,7 @@ static void enqueue_extract(lsa_ctx* ctx, const float4* frame4, int n, const Ext
   }
   {
     ProfScope ps(ctx, "label_nms", (double)n * (16 + 1 + 1 + 1), st);
-    hipLaunchKernelGGL(k_label, dim3(kMaxRings), dim3(kLabelThreads), 0, st, ctx->score[0], ctx->score[1], ctx->score[2], ctx->score[3], ctx->ring_start,
-                       ctx->ring_len, ring_meta, c, ctx->valid, ctx->label, ctx->ring_counts);
+    launch_label(ctx, c, st, ring_meta);
   }
   {
     ProfScope ps(ctx, "compact", (double)n * (1 + 4), st);
@@ -855,6 +864,24 @@ static int extract_frame(lsa_ctx* ctx, const lsa_extract_params_t* params, int c
     else LSA_HIP(ctx, hipStreamSynchronize(ctx->prefetch_stream));
     ctx->prefetch_pending = false;
   }
+  // A frame the kernels refuse leaves the keypoint sets as they were before the call (the caller drops that frame: the
+  // next one is registered on the last frame that was extracted): what the swap below changes is kept to be put back.
+  struct SetState
+  {
+    int n[3];
+    unsigned long long ver[3];
+    bool time_valid;
+    double time[2];
+  } saved[2];
+  const int saved_sets[2] = {LSA_SET_RAW_CURRENT, LSA_SET_RAW_PREVIOUS};
+  for (int i = 0; i < 2; ++i)
+  {
+    const int s = saved_sets[i];
+    for (int k = 0; k < 3; ++k) { saved[i].n[k] = ctx->kp_n[s][k]; saved[i].ver[k] = ctx->kp_ver[s][k]; }
+    saved[i].time_valid = ctx->kp_time_valid[s];
+    saved[i].time[0] = ctx->kp_time[s][0];
+    saved[i].time[1] = ctx->kp_time[s][1];
+  }
   if (!append)
   {
     // Slam::ExtractKeypoints: current keypoints become the previous ones (Slam.cxx:751)
@@ -891,8 +918,24 @@ static int extract_frame(lsa_ctx* ctx, const lsa_extract_params_t* params, int c
   }
   unsigned long long hpt[2];
   std::memcpy(hpt, hp + 12, sizeof(hpt));
-  if (hp[6] & 1) return ctx->fail(LSA_E_CAPACITY, "lsa_extract_keypoints: laser_id >= 512 is not supported");
-  if (hp[6] & 2) return ctx->fail(LSA_E_CAPACITY, "lsa_extract_keypoints: more than 8192 points on one laser ring");
+  if (hp[6] & 3)
+  {
+    // k_compact wrote nothing: the buffers go back where they were, with their counts, versions and time ranges
+    if (adopt)
+      for (int k = 0; k < 3; ++k) std::swap(ctx->kp[LSA_SET_RAW_CURRENT][k], ctx->kp_next[k]);
+    if (!append)
+      for (int k = 0; k < 3; ++k) std::swap(ctx->kp[LSA_SET_RAW_CURRENT][k], ctx->kp[LSA_SET_RAW_PREVIOUS][k]);
+    for (int i = 0; i < 2; ++i)
+    {
+      const int s = saved_sets[i];
+      for (int k = 0; k < 3; ++k) { ctx->kp_n[s][k] = saved[i].n[k]; ctx->kp_ver[s][k] = saved[i].ver[k]; }
+      ctx->kp_time_valid[s] = saved[i].time_valid;
+      ctx->kp_time[s][0] = saved[i].time[0];
+      ctx->kp_time[s][1] = saved[i].time[1];
+    }
+    if (hp[6] & 1) return ctx->fail(LSA_E_CAPACITY, "lsa_extract_keypoints: laser_id >= 512 is not supported");
+    return ctx->fail(LSA_E_CAPACITY, "lsa_extract_keypoints: more than 8192 points on one laser ring");
+  }
   ctx->nb_rings_seen = std::max(ctx->nb_rings_seen, hp[4]);
   for (int k = 0; k < 3; ++k)
   {
@@ -1045,6 +1088,64 @@ int lsa_extract_prefetch_adopted(const lsa_ctx* ctx) { return ctx ? ctx->prefetc
 int lsa_extract_keypoints_more(lsa_ctx* ctx, const lsa_extract_params_t* params, const double base_to_lidar[16], double time_offset, int counts[3])
 {
   return extract_frame(ctx, params, counts, true, base_to_lidar, time_offset);
+}
+
+// k_label alone, on scores and validity the caller made up (the extraction's own launch, its own buffers)
+int lsa_selftest_labels(lsa_ctx* ctx, const lsa_extract_params_t* params, const int* ring_lengths, int nrings, const float* sin_angle,
+                        const float* depth_gap, const float* saliency, const float* intensity_gap, const uint8_t* valid, uint8_t* label_out,
+                        uint8_t* valid_out, int* ring_counts_out)
+{
+  if (!ctx || !params || !ring_lengths || !label_out || !valid_out || !ring_counts_out)
+    return ctx ? ctx->fail(LSA_E_ARG, "lsa_selftest_labels: null argument") : LSA_E_ARG;
+  if (nrings < 1 || nrings > kMaxRings) return ctx->fail(LSA_E_ARG, "lsa_selftest_labels: 1 to 512 rings");
+  if (params->neighbor_width < 1 || params->neighbor_width > 8) return ctx->fail(LSA_E_ARG, "lsa_selftest_labels: NeighborWidth must be in [1, 8]");
+  int start[kMaxRings + 1], len[kMaxRings];
+  long long total = 0;
+  for (int r = 0; r < kMaxRings; ++r)
+  {
+    len[r] = r < nrings ? ring_lengths[r] : 0;
+    if (len[r] < 0) return ctx->fail(LSA_E_ARG, "lsa_selftest_labels: negative ring length");
+    start[r] = (int)total;
+    total += len[r];
+    if (total > (1ll << 24)) return ctx->fail(LSA_E_ARG, "lsa_selftest_labels: more than 2^24 points");
+  }
+  start[kMaxRings] = (int)total;
+  const int n = (int)total;
+  if (n > 0 && (!sin_angle || !depth_gap || !saliency || !intensity_gap || !valid)) return ctx->fail(LSA_E_ARG, "lsa_selftest_labels: null argument");
+  LSA_HIP(ctx, hipSetDevice(ctx->device));
+  int rc = ensure_capacity(ctx, std::max(n, 1));
+  if (rc) return rc;
+  if (ctx->prefetch_pending)
+  {
+    LSA_HIP(ctx, hipStreamSynchronize(ctx->prefetch_stream));  // the per-point buffers are shared with the look-ahead extraction
+  }
+  hipStream_t st = ctx->stream;
+  const ExtractConst c = make_const(params, ctx->az_res);
+  int* ring_meta = ctx->extract_out + 4;
+  hipLaunchKernelGGL(k_extract_init, dim3(1), dim3(64), 0, st, ctx->extract_out);
+  LSA_HIP(ctx, hipMemcpyAsync(ring_meta, &nrings, sizeof(int), hipMemcpyHostToDevice, st));  // NbLaserRings
+  LSA_HIP(ctx, hipMemcpyAsync(ctx->ring_start, start, sizeof(start), hipMemcpyHostToDevice, st));
+  LSA_HIP(ctx, hipMemcpyAsync(ctx->ring_len, len, sizeof(len), hipMemcpyHostToDevice, st));
+  LSA_HIP(ctx, hipMemsetAsync(ctx->ring_counts, 0, kMaxRings * 3 * sizeof(int), st));
+  if (n > 0)
+  {
+    const float* src[4] = {sin_angle, depth_gap, saliency, intensity_gap};  // the order of ctx->score
+    for (int i = 0; i < 4; ++i) LSA_HIP(ctx, hipMemcpyAsync(ctx->score[i], src[i], (size_t)n * sizeof(float), hipMemcpyHostToDevice, st));
+    LSA_HIP(ctx, hipMemcpyAsync(ctx->valid, valid, (size_t)n, hipMemcpyHostToDevice, st));
+    LSA_HIP(ctx, hipMemsetAsync(ctx->label, 0, (size_t)n, st));
+  }
+  launch_label(ctx, c, st, ring_meta);
+  int* hp = reinterpret_cast<int*>(ctx->host_pinned);
+  LSA_HIP(ctx, hipMemcpyAsync(hp, ctx->extract_out, 16 * sizeof(int), hipMemcpyDeviceToHost, st));
+  if (n > 0)
+  {
+    LSA_HIP(ctx, hipMemcpyAsync(label_out, ctx->label, (size_t)n, hipMemcpyDeviceToHost, st));
+    LSA_HIP(ctx, hipMemcpyAsync(valid_out, ctx->valid, (size_t)n, hipMemcpyDeviceToHost, st));
+  }
+  LSA_HIP(ctx, hipMemcpyAsync(ring_counts_out, ctx->ring_counts, (size_t)nrings * 3 * sizeof(int), hipMemcpyDeviceToHost, st));
+  LSA_HIP(ctx, hipStreamSynchronize(st));
+  if (hp[6] & 2) return ctx->fail(LSA_E_CAPACITY, "lsa_selftest_labels: more than 8192 points on one laser ring");
+  return n;
 }
 
 int lsa_keypoint_count(const lsa_ctx* ctx, int set, int type)

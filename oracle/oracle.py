@@ -47,6 +47,7 @@ def lib():
         L.orc_extractor_keypoints.argtypes = [vp, i32, vp, i32]
         L.orc_extractor_debug.argtypes = [vp, i32, vp, i32]
         L.orc_extractor_nb_rings.argtypes = [vp]
+        L.orc_extractor_label.argtypes = [vp, C.POINTER(ExtractParams), vp, i32, vp, vp, vp, vp, vp, vp, vp, vp]
         L.orc_knn.argtypes = [vp, i32, vp, i32, i32, vp, vp, vp]
         L.orc_knn_brute.argtypes = [vp, i32, vp, i32, i32, vp, vp, vp]
         L.orc_match.argtypes = [vp, i32, vp, i32, i32, C.POINTER(MatchParams), vp, i32, vp, vp, vp, vp]
@@ -153,6 +154,20 @@ class Extractor:
 
     def nb_rings(self):
         return lib().orc_extractor_nb_rings(self.h)
+
+    def label(self, ring_lengths, sin_angle, depth_gap, saliency, intensity_gap, valid, params=None):
+        """SetKeyPointsLabels alone on the given scores and validity bytes (rings one after the other) ->
+        (label, validity afterwards, ring_counts (nrings, 3)); the layout of lsa_selftest_labels"""
+        params = params or ExtractParams()
+        lens = np.ascontiguousarray(ring_lengths, np.int32)
+        n = int(lens.sum())
+        scores = [np.ascontiguousarray(a, np.float32) for a in (sin_angle, depth_gap, saliency, intensity_gap)]
+        valid = np.ascontiguousarray(valid, np.uint8)
+        assert all(a.size == n for a in scores) and valid.size == n
+        label, after, counts = np.zeros(n, np.uint8), np.zeros(n, np.uint8), np.zeros((lens.size, 3), np.int32)
+        lib().orc_extractor_label(self.h, C.byref(params), ptr(lens), lens.size, *[ptr(a) for a in scores], ptr(valid), ptr(label), ptr(after),
+                                  ptr(counts))
+        return label, after, counts
 
 
 def knn(target, queries, k, brute=False):

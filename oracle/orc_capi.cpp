@@ -124,6 +124,29 @@ int orc_extractor_debug(void* h, int id, float* out, int capacity)
   return n;
 }
 int orc_extractor_nb_rings(void* h) { return ((ExtractorHandle*)h)->e.NbLaserRings; }
+// SetKeyPointsLabels alone on given per-ring scores and validity (layout of lsa_selftest_labels): labels, validity afterwards
+// and the keypoints per ring and type
+int orc_extractor_label(void* h, const lsa_extract_params_t* p, const int* len, int nrings, const float* angles, const float* depthGap,
+                        const float* saliency, const float* intensityGap, const uint8_t* valid, uint8_t* labelOut, uint8_t* validOut,
+                        int* ringCounts)
+{
+  ExtractorHandle* eh = (ExtractorHandle*)h;
+  ApplyExtractParams(eh->e, p);
+  eh->scan.clear();
+  eh->e.LabelGivenScores(len, nrings, angles, depthGap, saliency, intensityGap, valid);
+  size_t o = 0;
+  for (int r = 0; r < nrings; ++r)
+  {
+    for (int k = 0; k < 3; ++k) ringCounts[3 * r + k] = 0;
+    for (int i = 0; i < len[r]; ++i, ++o)
+    {
+      labelOut[o] = eh->e.Label[r][i];
+      validOut[o] = eh->e.IsPointValid[r][i];
+      for (int k = 0; k < 3; ++k) ringCounts[3 * r + k] += (eh->e.Label[r][i] >> k) & 1;
+    }
+  }
+  return (int)o;
+}
 
 // ---- kNN --------------------------------------------------------------------
 int orc_knn(const lsa_point_t* tgt, int m, const double* queries, int nq, int k, int* idx, float* d2, int* counts)

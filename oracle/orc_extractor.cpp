@@ -350,6 +350,32 @@ void Extractor::SetKeyPointsLabels()
   }
 }
 
+void Extractor::LabelGivenScores(const int* len, int nrings, const float* angles, const float* depthGap, const float* saliency,
+                                 const float* intensityGap, const uint8_t* valid)
+{
+  static const std::vector<Point> noScan;  // DebugArray then has nothing to flatten
+  Scan = &noScan;
+  NbLaserRings = nrings;
+  ScanLines.assign(nrings, {});
+  Angles.assign(nrings, {}); DepthGap.assign(nrings, {}); Saliency.assign(nrings, {}); IntensityGap.assign(nrings, {});
+  IsPointValid.assign(nrings, {}); Label.assign(nrings, {});
+  for (int k = 0; k < 3; ++k) Keypoints[k].clear();
+  size_t o = 0;
+  for (int r = 0; r < nrings; ++r)
+  {
+    const size_t n = len[r];
+    ScanLines[r].assign(n, Point{});
+    Angles[r].assign(angles + o, angles + o + n);
+    DepthGap[r].assign(depthGap + o, depthGap + o + n);
+    Saliency[r].assign(saliency + o, saliency + o + n);
+    IntensityGap[r].assign(intensityGap + o, intensityGap + o + n);
+    IsPointValid[r].assign(valid + o, valid + o + n);
+    Label[r].assign(n, 0);
+    o += n;
+  }
+  SetKeyPointsLabels();
+}
+
 // SSKE.cxx:593-637
 void Extractor::EstimateAzimuthalResolution()
 {

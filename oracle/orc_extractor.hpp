@@ -49,6 +49,12 @@ public:
   // 7..9 {edge,plane,blob}_validity
   std::vector<float> DebugArray(int id) const;
 
+  // SetKeyPointsLabels (SSKE.cxx:474-590) alone, on per-ring arrays the caller provides instead of those the steps
+  // before it compute: nrings rings of len[r] points, the rings one after the other in the flat arrays.  Fills Label,
+  // IsPointValid and (with zeroed points) Keypoints.
+  void LabelGivenScores(const int* len, int nrings, const float* angles, const float* depthGap, const float* saliency,
+                        const float* intensityGap, const uint8_t* valid);
+
 private:
   const std::vector<Point>* Scan = nullptr;
   void ConvertAndSortScanLines();

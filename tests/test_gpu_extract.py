@@ -5,22 +5,9 @@ import numpy as np
 import pytest
 
 from conftest import bits
+from extract_cases import assert_extraction_equal
 
 pytestmark = pytest.mark.gpu
-
-
-def assert_extraction_equal(ctx, ex, O, L, pts, params=None):
-    ctx.upload_frame(pts)
-    counts = ctx.extract_keypoints(params)
-    ref = ex.compute(pts, params)
-    assert counts.tolist() == ref.tolist()
-    for i, name in enumerate(O.DEBUG_NAMES):
-        a, b = ctx.debug_array(i), ex.debug(i)
-        bad = np.flatnonzero(bits(a) != bits(b))
-        assert bad.size == 0, f"{name}: {bad.size} mismatches, first at {bad[:5]}: gpu {a[bad[:5]]} oracle {b[bad[:5]]}"
-    for k in range(3):
-        assert ctx.keypoints(L.SET_RAW_CURRENT, k).tobytes() == ex.keypoints(k).tobytes(), f"keypoint cloud {k}"
-    return counts
 
 
 @pytest.mark.parametrize("model,frames", [(8, 3), (16, 2), (64, 1), (128, 2)])

@@ -1355,6 +1355,9 @@ class DeviceGrid:
         self.L.lsa_device_grid_build_submap_begin.argtypes = [vp, vp, vp, i32, i32, i32]
         self.L.lsa_device_grid_build_submap_begin_for_keypoints.argtypes = [vp, i32, i32, i32, i32]
         self.L.lsa_device_grid_build_submap_end.argtypes = [vp]
+        self.L.lsa_device_grid_submap_ahead_begin.argtypes = [vp, i32, i32, i32]
+        self.L.lsa_device_grid_submap_ahead_wait.argtypes = [vp]
+        self.L.lsa_device_grid_submap_ahead_take.argtypes = [vp, i32, i32, i32, i32, vp]
         if self.L.lsa_device_grid_create(ctx.h, C.byref(h)) != 0:
             raise LsaError("lsa_device_grid_create failed")
         self.h = h
@@ -1428,6 +1431,19 @@ class DeviceGrid:
 
     def build_submap_end(self):
         return self._check(self.L.lsa_device_grid_build_submap_end(self.h), "lsa_device_grid_build_submap_end")
+
+    def submap_ahead_begin(self, box_type, min_nb_points, ktype=PLANE):
+        """the sub-map for the box Context.keypoint_bboxes_begin left on the device, ahead of time, into the spare target"""
+        self._check(self.L.lsa_device_grid_submap_ahead_begin(self.h, box_type, int(min_nb_points), ktype), "lsa_device_grid_submap_ahead_begin")
+
+    def submap_ahead_wait(self):
+        return self._check(self.L.lsa_device_grid_submap_ahead_wait(self.h), "lsa_device_grid_submap_ahead_wait")
+
+    def submap_ahead_take(self, box_type, min_nb_points, ktype=PLANE, slot=TARGET_MAP):
+        """(size, taken): taken == 1 when the sub-map extracted ahead became target (slot, ktype)"""
+        taken = C.c_int(0)
+        n = self._check(self.L.lsa_device_grid_submap_ahead_take(self.h, box_type, int(min_nb_points), slot, ktype, C.byref(taken)), "lsa_device_grid_submap_ahead_take")
+        return n, taken.value
 
     def clear_old_points(self, time):
         self._check(self.L.lsa_device_grid_clear_old_points(self.h, float(time)), "lsa_device_grid_clear_old_points")

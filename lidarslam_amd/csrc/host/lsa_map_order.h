@@ -1,12 +1,12 @@
 // lsa_map_order.h -- the iteration order of LidarSlam::RollingGrid's containers for a map whose points live elsewhere
-// (the device grid, lsa_device_grid.hip, with "Ordered" = 0).
+// (the device grid, lsa_grid_order.hip, with "Ordered" = 0).
 //
 // The reference's Get / BuildSubMapKdTree hand the voxels out in the iteration order of
 // std::unordered_map<int, std::unordered_map<int, Voxel>> (RollingGrid.cxx:95-113, 362-442): an accident of the tables'
 // history -- which keys came in which order, which were erased, when a table rehashed, that clear() keeps the bucket
 // array.  KeyShadow holds the same two levels of tables with the keys alone and applies the same sequence of container
 // operations RollingGrid.cxx applies, so its iteration order IS the reference's, by construction and not by a model of
-// the library.  The device grid records what each of its modifications did to the key set (lsa_device_grid.hip) and
+// the library.  The device grid records what each of its modifications did to the key set (lsa_grid_order.hip) and
 // replays it here.
 #pragma once
 #include <algorithm>

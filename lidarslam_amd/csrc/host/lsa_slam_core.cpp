@@ -1788,7 +1788,7 @@ int SlamCore::SetTrajectoryAndRebuildMaps(const double* poses17, int n)
   if (DeviceMapsInUse())
   {
     // one Add per type: the device maps' insertion takes about three million points at a time (the chunk table of its merge
-    // kernel lives in LDS, lsa_device_grid.hip); a longer log is rebuilt with the maps on the host ("MapsOnDevice" = 0)
+    // kernel lives in LDS, lsa_grid_add.hip); a longer log is rebuilt with the maps on the host ("MapsOnDevice" = 0)
     constexpr long long kDeviceAddLimit = 3000000;
     for (int k = 0; k < 3; ++k)
     {

@@ -1,4 +1,4 @@
-// lsa_compact.h -- the one stable compaction of the library: the device maps' (lsa_device_grid.hip) and the frame
+// lsa_compact.h -- the one stable compaction of the library: the device maps' (lsa_device_grid.hip, lsa_grid_submap.hip) and the frame
 // converters' (lsa_wire.hip).  What stays is a predicate functor bool(int i), what happens to it an emitter functor
 // void(int i, int position).  One (predicate, emitter) pair is launched from ONE translation unit only: the kernel would
 // exist twice in the library otherwise.

@@ -1,5 +1,6 @@
 // lsa_device_grid_io.h -- what the map-file unit (lsa_pcd.hip) and the keypoint log's replay (lsa_kplog.hip) need of a device
-// grid (lsa_device_grid.hip): the batch buffer an insertion reads, the insertion itself, and RollingGrid::Get left on the device.
+// grid: the batch buffer an insertion reads and the insertion itself (lsa_grid_add.hip), RollingGrid::Get left on the device
+// (lsa_grid_submap.hip).  What the grid's own units share is lsa_grid.h.
 #pragma once
 #include "lsa_ctx.h"
 

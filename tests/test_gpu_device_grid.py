@@ -262,3 +262,62 @@ def test_the_two_step_calls_of_the_pipeline(ctx):
         assert ctx.target(k).tobytes() == o.submap().tobytes()
         assert g.submap_valid()
         g.close()
+
+
+def box_on_device(ctx, pose):
+    """lsa_keypoint_bboxes_begin: the boxes of the WORKING keypoints under `pose` stay on the device (nothing read back)"""
+    ctx._check(ctx.L.lsa_keypoint_bboxes_begin(ctx.h, L.SET_WORKING, L.ptr(L.pose16(pose))), "lsa_keypoint_bboxes_begin")
+
+
+@pytest.mark.parametrize("ordered", [1, 0])
+@pytest.mark.parametrize("min_nb", [-1, 0, 10**6])  # unfiltered; first pass only; first pass short, the second appends
+def test_a_sub_map_extracted_ahead_is_taken_over_only_for_the_same_voxels_of_the_same_map(ctx, ordered, min_nb):
+    """lsa_device_grid_submap_ahead_begin / _wait / _take with MinFramesPerVoxel at work (the one- and the two-pass
+    extraction): taken over for a box that touches the same outer voxels -- the oracle's sub-map byte for byte --, left
+    alone for a box two outer voxels further or after a modification, where the usual extraction gives the oracle's."""
+    rng = np.random.default_rng(7)
+    ctx.set_keypoints(L.SET_WORKING, L.PLANE, cloud(rng, 200, 0, spread=9))
+    params = dict(GridSize=12, VoxelResolution=8.0, LeafSize=0.6, MinFramesPerVoxel=3)
+    g, o = L.DeviceGrid(ctx), O.RollingGrid(Ordered=ordered, **params)
+    g.set("Ordered", ordered)  # before the first insertion: exact from then on
+    for k, v in params.items():
+        g.set(k, v)
+    a, b = cloud(rng, 1500, 0, spread=14.0), cloud(rng, 1500, np.array([4.0, 0, 0]), spread=14.0)
+    for pts in (a, a, a, b):
+        g.add(pts), o.add(pts)
+    P, moved = np.eye(4), np.eye(4)
+    P[:3, 3] = [1.0, -2.0, 0.5]
+    moved[:3, 3] = P[:3, 3] + [16.0, 0.0, 0.0]  # two outer voxels along x
+    (mn, mx), (mn2, mx2) = ([v[L.PLANE] for v in ctx.keypoint_bboxes(L.SET_WORKING, T)] for T in (P, moved))
+    # the inputs reach both branches (oracle alone): some voxels have three frames, not all
+    n0, n1, n_all = (o.build_submap(mn, mx, m) for m in (0, 10**6, -1))
+    assert 0 < n0 < n1 == n_all < o.size()
+
+    def ahead(actual, between=None):
+        box_on_device(ctx, P)
+        g.submap_ahead_begin(L.PLANE, min_nb)
+        if between is None:
+            assert g.submap_ahead_wait() == 2
+        else:
+            g.add(between), o.add(between)
+        box_on_device(ctx, actual)
+        return g.submap_ahead_take(L.PLANE, min_nb)
+
+    # (a) the same box: taken over
+    n, taken = ahead(P)
+    assert taken == 1 and n == o.build_submap(mn, mx, min_nb) == (n_all, n0, n1)[(-1, 0, 10**6).index(min_nb)]
+    assert ctx.target(L.PLANE).tobytes() == o.submap().tobytes()
+    assert g.submap_valid() == o.submap_valid()
+    # (b) another range of voxels: everything left as it was, the usual extraction follows
+    before = ctx.target(L.PLANE).tobytes()
+    assert ahead(moved) == (0, 0) and ctx.target(L.PLANE).tobytes() == before
+    g.build_submap_begin_for_keypoints(L.PLANE, min_nb)
+    assert g.build_submap_end() == o.build_submap(mn2, mx2, min_nb) > 0
+    assert ctx.target(L.PLANE).tobytes() == o.submap().tobytes() != before
+    # (c) the map modified in between: not taken over either
+    before = ctx.target(L.PLANE).tobytes()
+    assert ahead(P, between=cloud(rng, 1500, np.array([-4.0, 0, 0]), spread=14.0)) == (0, 0) and ctx.target(L.PLANE).tobytes() == before
+    g.build_submap_begin_for_keypoints(L.PLANE, min_nb)
+    assert g.build_submap_end() == o.build_submap(mn, mx, min_nb) > 0
+    assert ctx.target(L.PLANE).tobytes() == o.submap().tobytes()
+    g.close()

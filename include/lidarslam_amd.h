@@ -831,9 +831,9 @@ int lsa_slam_map_io_counts(const lsa_slam* s, int counts[3]);
  *   pose[n-2].  The covariance log is kept.  The next lsa_slam_add_frame goes on as after lsa_slam_reset(s, 0).
  *   LSA_E_STATE when "LoggingTimeout" is 0, when keypoint logging stopped (a chunk could not be allocated; until
  *   lsa_slam_reset(s, 1)) or when the keypoint log does not cover the logged poses (logging was switched on in between);
- *   LSA_E_ARG when n is not the number of logged poses, n < 2, or a row's time is not the logged pose's; LSA_E_CAPACITY
- *   when the maps are on the device and one type has more than 3 000 000 logged keypoints (what one insertion into a
- *   device map takes: rebuild with "MapsOnDevice" = 0).  On any of these nothing was changed.
+ *   LSA_E_ARG when n is not the number of logged poses, n < 2, or a row's time is not the logged pose's.  On any of these
+ *   nothing was changed.  A log of any length is taken, on the device maps as on the host maps: what remains is what one
+ *   replay and one insertion address, 2^31 - 1 logged keypoints of one type (lsa_kplog_replay_to_grids, LSA_E_CAPACITY).
  * - lsa_slam_logged_frames: frames in the keypoint log; lsa_slam_get_logged_keypoints: one frame's raw keypoints of one
  *   type (returns their number, writes at most capacity).  Read-only parameter "LoggedKeypointsBytes": device memory held. */
 int lsa_slam_set_trajectory_and_rebuild_maps(lsa_slam* s, const double* poses17, int n);
@@ -862,7 +862,13 @@ int lsa_slam_get_logged_keypoints(lsa_slam* s, int frame, int type, lsa_point_t*
  *   time -1 and not fixed, so a map with a "DecayingThreshold" drops them at its next ClearOldPoints -- the host grid,
  *   whose SetOrdered only changes the order, keeps them).
  * Sampling modes FIRST, LAST, MAX_INTENSITY, CENTER_POINT, CENTROID.  Parameters by the reference's setter names:
- * "GridSize", "VoxelResolution", "LeafSize", "MinFramesPerVoxel", "Sampling", "DecayingThreshold", and "Ordered". */
+ * "GridSize", "VoxelResolution", "LeafSize", "MinFramesPerVoxel", "Sampling", "DecayingThreshold", and "Ordered".
+ * lsa_device_grid_set also takes "GlobalScans", a TEST KNOB that changes no result: which of its two forms an insertion
+ * takes is a matter of its size (the chunk tables of the merge in LDS while they fit -- points / 256 + voxels / 1024 + 2 <=
+ * 12 288, every keyframe's insertion --, scanned into global memory by launches of their own otherwise); 1 takes the second
+ * form at any size, 2 takes it with scan blocks of 64 entries instead of 256, so that a further level of the scan is
+ * reached with a million points; 0 (default) goes by size.  lsa_device_grid_get_param also answers "Voxels": the voxels the
+ * map holds (the size of Get(false)) as of the last modification, which it waits for. */
 typedef struct lsa_device_grid lsa_device_grid;
 int lsa_device_grid_create(lsa_ctx* ctx, lsa_device_grid** out);
 void lsa_device_grid_destroy(lsa_device_grid* g); /* before lsa_ctx_destroy of its context */
@@ -873,7 +879,9 @@ int lsa_device_grid_reset(lsa_device_grid* g, const float position[3]);
 int lsa_device_grid_clear(lsa_device_grid* g);
 /* RollingGrid::Size() (waits for the modifications enqueued so far). */
 int lsa_device_grid_size(lsa_device_grid* g);
-/* RollingGrid::Add(pointcloud, fixed, currentTime, roll) from host points ... */
+/* RollingGrid::Add(pointcloud, fixed, currentTime, roll) from host points ...  One call is one Add whatever its size (a
+ * voxel's frame count rises once, the sampling modes see the whole cloud in arrival order).  LSA_E_CAPACITY when the voxels
+ * of the map and the points of the insertion together are more than 2^31 - 8193, what the kernels address. */
 int lsa_device_grid_add(lsa_device_grid* g, const lsa_point_t* pts, int n, int fixed, double time, int roll);
 /* ... and from a keypoint set of the context moved by `pose` (Slam::UpdateMapsUsingTworld, Slam.cxx:1178-1222): nothing
  * leaves the device and nothing is waited for. */
@@ -923,7 +931,8 @@ int lsa_device_grid_submap_ahead_take_end(lsa_device_grid* g, int* taken);
  * the device (k_pcd_decode / k_pcd_encode), ascii text and the LZF stage on the host.
  * - lsa_device_grid_add_pcd = RollingGrid::Add(the file's cloud, fixed, time, roll_first), the whole file as ONE Add; the
  *   data section goes up in pieces through pinned staging on the context's copy stream, piece i is converted while piece
- *   i + 1 is uploaded.  A malformed file: LSA_E_ARG, lsa_last_error names the file and the line.
+ *   i + 1 is uploaded.  A malformed file: LSA_E_ARG, lsa_last_error names the file and the line.  A file of any size the
+ *   format counts (2^31 - 1 points) and lsa_device_grid_add addresses is taken.
  * - lsa_device_grid_save_pcd writes RollingGrid::Get(clean) in the order lsa_device_grid_get hands it out; returns the
  *   number of points written: 0, and no file, when there is none (an empty cloud is not saved, PointCloudStorage.h:91-92);
  *   every failure -- a path that cannot be written among them -- is negative and lsa_last_error names the file.

@@ -1008,6 +1008,18 @@ class Context:
         sizes = [int(self.L.lsa_kplog_replayed(self.h, k, C.byref(C.c_void_p()))) for k in range(3)]
         return [o[:s].copy() for o, s in zip(outs, sizes)], mn, mx
 
+    def kplog_replay_to_grids(self, poses, times, grids, undistort=True):
+        """the same straight into device maps of this context: grids = [edges, planes, blobs], a DeviceGrid or None each;
+        per map ONE Add(aggregate, fixed=False, time=-1, roll=False), nothing comes to the host.  Returns the last
+        frame's min [3][3], max [3][3] (what the caller rolls the maps onto)."""
+        P = np.ascontiguousarray(np.asarray(poses, np.float64).reshape(-1, 16))
+        t = np.ascontiguousarray(times, np.float64)
+        mask = sum(1 << k for k in range(3) if grids[k] is not None)
+        hs = (C.c_void_p * 3)(*[g.h.value if g is not None else None for g in grids])
+        mn, mx = np.zeros((3, 3), np.float32), np.zeros((3, 3), np.float32)
+        self._check(self.L.lsa_kplog_replay_to_grids(self.h, mask, ptr(P), ptr(t), P.shape[0], int(bool(undistort)), hs, ptr(mn), ptr(mx)), "lsa_kplog_replay_to_grids")
+        return mn, mx
+
 
 class Slam:
     """LidarSlam::Slam on one MI355X.  Parameters use the reference's names (``EgoMotion=3`` ...)."""
@@ -1448,7 +1460,10 @@ class DeviceGrid:
     def clear_old_points(self, time):
         self._check(self.L.lsa_device_grid_clear_old_points(self.h, float(time)), "lsa_device_grid_clear_old_points")
 
-    def get(self, clean=False, capacity=1 << 22):
+    def get(self, clean=False, capacity=None):
+        """RollingGrid::Get(clean); capacity: room for so many points (default: the voxels the map holds)"""
+        if capacity is None:
+            capacity = max(int(self.get_param("Voxels")), 1)
         out = np.zeros(capacity, POINT_DTYPE)
         n = self._check(self.L.lsa_device_grid_get(self.h, int(clean), ptr(out), out.size), "lsa_device_grid_get")
         return out[:n].copy()

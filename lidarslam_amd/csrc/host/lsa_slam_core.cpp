@@ -1785,23 +1785,8 @@ int SlamCore::SetTrajectoryAndRebuildMaps(const double* poses17, int n)
       return LSA_E_ARG;
     }
   if (lsa_kplog_size(Ctx) != n) { LastError = std::string(who) + "the keypoint log does not cover the logged poses (logging was switched on after the first of them)"; return LSA_E_STATE; }
-  if (DeviceMapsInUse())
-  {
-    // one Add per type: the device maps' insertion takes about three million points at a time (the chunk table of its merge
-    // kernel lives in LDS, lsa_grid_add.hip); a longer log is rebuilt with the maps on the host ("MapsOnDevice" = 0)
-    constexpr long long kDeviceAddLimit = 3000000;
-    for (int k = 0; k < 3; ++k)
-    {
-      long long sum = 0;
-      for (int i = 0; i < n && UseKeypoints[k]; ++i) sum += lsa_kplog_count(Ctx, i, k);
-      if (sum > kDeviceAddLimit)
-      {
-        LastError = std::string(who) + std::to_string(sum) + " logged keypoints of one type are more than one insertion into a device map takes (" +
-                    std::to_string(kDeviceAddLimit) + "): set MapsOnDevice = 0 for the rebuild";
-        return LSA_E_CAPACITY;
-      }
-    }
-  }
+  // (one Add per type, of any size the replay addresses: a long log takes the form of the device maps' insertion that keeps its
+  //  scans in global memory, lsa_grid_add.hip)
   std::vector<double> poses(static_cast<size_t>(n) * 16), times(n);
   for (int i = 0; i < n; ++i)
   {

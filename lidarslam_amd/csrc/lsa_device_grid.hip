@@ -224,7 +224,7 @@ int ensure_map(lsa_device_grid* g, int want)
 {
   if (want > g->cap)
   {
-    const int cap = std::max(2 * want, 1 << 19);  // 46 MB for both buffers: growth (a device-wide stall) is rare
+    const int cap = (int)std::min(std::max(2ll * want, 1ll << 19), kAddressable);  // 46 MB for both buffers: growth (a device-wide stall) is rare
     G_HIP(hipStreamSynchronize(g->stream));
     MapView nb[2];
     for (int b = 0; b < 2; ++b)
@@ -363,6 +363,7 @@ void lsa_device_grid_destroy(lsa_device_grid* g)
   free_view(g->buf[0]); free_view(g->buf[1]); free_view(g->fresh);
   auto fr = [](void* p) { if (p) (void)hipFree(p); };
   fr(g->st); fr(g->batch); fr(g->bkeys); fr(g->skeys); fr(g->border); fr(g->sorder); fr(g->heads); fr(g->fresh_flag); fr(g->vrank); fr(g->chunks); fr(g->old_local);
+  fr(g->oscan); fr(g->fscan); fr(g->scan_sums);
   fr(g->rec_dev); fr(g->order_dev); fr(g->perm);
   for (void* h : {(void*)g->rec_st, (void*)g->rec_host, (void*)g->order_host})
     if (h) (void)hipHostFree(h);
@@ -448,6 +449,13 @@ int lsa_device_grid_set(lsa_device_grid* g, const char* name, double value)
   if (n == "MinFramesPerVoxel") { g->MinFramesPerVoxel = (unsigned)value; return LSA_OK; }
   if (n == "Sampling") { g->Sampling = (int)value; return LSA_OK; }
   if (n == "DecayingThreshold") { g->DecayingThreshold = value; return LSA_OK; }
+  if (n == "GlobalScans")
+  {
+    // (a test knob: which form an insertion takes is otherwise a matter of its size alone, lsa_grid_add.hip)
+    if (value != 0. && value != 1. && value != 2.) return g->ctx->fail(LSA_E_ARG, "lsa_device_grid_set: GlobalScans is 0, 1 or 2");
+    g->GlobalScans = (int)value;
+    return LSA_OK;
+  }
   if (n == "Ordered")
   {
     // RollingGrid::SetOrdered.  On an empty grid, from the first insertion on.  On a grid that holds points, the way the
@@ -498,6 +506,13 @@ double lsa_device_grid_get_param(const lsa_device_grid* g, const char* name)
   if (n == "GridSize") return g->GridSize;
   if (n == "VoxelResolution") return g->VoxelResolution;
   if (n == "Ordered") return g->Ordered ? 1. : 0.;
+  if (n == "GlobalScans") return g->GlobalScans;
+  if (n == "Voxels")
+  {
+    // the voxels the map holds, Get(false)'s size, as of the last modification that has completed on the device (waits for it)
+    if (hipSetDevice(g->ctx->device) != hipSuccess || hipEventSynchronize(g->ev_state) != hipSuccess) return 0.;
+    return std::max(g->host_st[kStN], 0);
+  }
   return 0.;
 }
 

@@ -102,6 +102,11 @@ struct lsa_device_grid
   int* old_local = nullptr;    // [cap] rank of an old voxel among the survivors of its chunk (Add)
   lsa::MapView fresh = {};
   int chunk_cap = 0;
+  // the form of an insertion that keeps its scans in global memory (lsa_grid_add.hip): the exclusive scans of `chunks`
+  // ([old chunks + 1]) and of `heads` ([blocks of the batch + 1]), and the block sums of every level of a scan
+  int *oscan = nullptr, *fscan = nullptr, *scan_sums = nullptr;
+  int oscan_cap = 0, fscan_cap = 0, scan_sums_cap = 0;
+  int GlobalScans = 0;  // test knob: 0 by size, 1 that form at any size, 2 with scan blocks of 64 entries (levels end 16 times sooner)
   // "Ordered" = 0, the reference's container order (see the head of lsa_device_grid.hip)
   bool Ordered = true;
   lsa::host::KeyShadow shadow;  // keys-only copy of the reference's containers
@@ -144,6 +149,9 @@ int end_modification(lsa_device_grid* g, int record_kind, size_t entries);
 // ---- lsa_grid_add.hip ----
 int ensure_batch(lsa_device_grid* g, int n);
 int add_batches(lsa_device_grid* const* gs, const int* ns, int count, bool fixed, double time, bool do_roll);
+// what one insertion addresses with an int: the voxels of the map and the points of the batch together (the kernels round both up
+// to whole runs of the sort)
+constexpr long long kAddressable = 0x7fffffffLL - 2 * 4096;
 // ---- lsa_grid_order.hip ----
 enum { kRecAdd = 1, kRecRoll = 2, kRecDecay = 3 };
 int apply_record(lsa_device_grid* g);

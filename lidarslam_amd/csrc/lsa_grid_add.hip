@@ -554,27 +554,35 @@ __device__ __forceinline__ void d_add_fold(int bx, const float4* __restrict__ ba
 
 // launch 6: the new map.  Blocks [0, oblocks): 1024 old voxels each -- a survivor's place is its rank among the survivors
 // plus the number of new voxels in front of it; the other blocks: 256 places of the sorted batch each -- a new voxel's
-// place is its rank among the new ones plus the number of survivors in front of it.  Every block scans the chunk counts
-// of both arrays for itself (dynamic LDS: ochunks + fchunks + 2 ints).
+// place is its rank among the new ones plus the number of survivors in front of it.  Two forms.  kGlobal = false: every block scans
+// the chunk counts of both arrays for itself (dynamic LDS: ochunks + fchunks + 2 ints) -- a keyframe's insertion: a few hundred
+// entries, one launch.  kGlobal = true: the launches in front of this one have left the scans in global memory (launch_scans)
+// -- an insertion whose table does not fit LDS: a long log, a prior map; no dynamic LDS.
+template <bool kGlobal>
 __device__ __forceinline__ void d_add_merge(int bx, GridParams p, int* __restrict__ st, int use_box, MapView old, const int* __restrict__ old_local,
                                                    const int* __restrict__ old_chunks, int ochunks, int oblocks, const u64* __restrict__ skeys, int n, MapView fresh,
                                                    const int* __restrict__ fresh_flag, const int* __restrict__ fresh_chunks, int fchunks, MapView dst,
-                                                   u64* __restrict__ rec = nullptr, const unsigned* __restrict__ sorder = nullptr)
+                                                   u64* __restrict__ rec = nullptr, const unsigned* __restrict__ sorder = nullptr,
+                                                   const int* __restrict__ goscan = nullptr, const int* __restrict__ gfscan = nullptr)
 {
-  extern __shared__ int scan[];  // [ochunks + 1] exclusive scan of the survivors per chunk, then [fchunks + 1] of the new voxels per block
-  __shared__ int carry;
   // oblocks: where the launch's blocks for the sorted batch begin (it may be shared with a bigger map)
   if (bx < oblocks ? bx >= ochunks : (bx - oblocks) * 256 >= n) return;
-  int* const oscan = scan;
-  int* const fscan = scan + ochunks + 1;
   const Shift sft = roll_shift(p, st, use_box);
   const int g = p.grid_size;
   const int N = st[kStN];
+  const int *oscan, *fscan;  // [ochunks + 1] exclusive scan of the survivors per chunk, [fchunks + 1] of the new voxels per block
+  if constexpr (kGlobal) { oscan = goscan; fscan = gfscan; }
+  else
+  {
+  extern __shared__ int scan[];  // the one, then the other
+  __shared__ int carry;
+  oscan = scan;
+  fscan = scan + ochunks + 1;
   // both scans, 256 entries at a time
   for (int which = 0; which < 2; ++which)
   {
     const int* src = which ? fresh_chunks : old_chunks;
-    int* out = which ? fscan : oscan;
+    int* out = which ? scan + ochunks + 1 : scan;
     const int cnt = which ? fchunks : ochunks;
     if (threadIdx.x == 0) carry = 0;
     __syncthreads();
@@ -600,6 +608,7 @@ __device__ __forceinline__ void d_add_merge(int bx, GridParams p, int* __restric
     }
     if (threadIdx.x == 0) out[cnt] = carry;
     __syncthreads();
+  }
   }
   const int survivors = oscan[ochunks], created = fscan[fchunks];
   if (bx == 0 && threadIdx.x == 0) { st[kStCompact] = survivors; st[kStNew] = created; }
@@ -727,8 +736,108 @@ __global__ __launch_bounds__(1024) void k_add_vscan(AddBatch b)
 __global__ __launch_bounds__(256) void k_add_merge(AddBatch b)
 {
   const AddOne& A = b.a[blockIdx.y];
-  d_add_merge(blockIdx.x, A.p, A.st, A.use_box, A.map, A.old_local, A.old_chunks, A.ochunks, b.oblocks, A.skeys, A.n, A.fresh, A.fresh_flag, A.fresh_chunks, (A.n + 255) / 256,
-              A.dst, A.rec, A.sorder);
+  d_add_merge<false>(blockIdx.x, A.p, A.st, A.use_box, A.map, A.old_local, A.old_chunks, A.ochunks, b.oblocks, A.skeys, A.n, A.fresh, A.fresh_flag, A.fresh_chunks,
+                     (A.n + 255) / 256, A.dst, A.rec, A.sorder);
+}
+
+// ---- the scans of the other form, in global memory -------------------------------------------------------------------------
+// A plain multi-level exclusive scan, for up to six arrays at a time (blockIdx.y: the old chunks and the batch's blocks of
+// up to three maps).  A level: every block scans `per` entries (its block size) and leaves their sum; the sums are the next
+// level's entries, scanned in place the same way, until one block takes them all; then, from the top level down, every entry
+// gets the scanned sum of its block.  out[cnt] is the total.  A kernel boundary is the only thing a block ever waits for:
+// nothing spins on another block's flag.
+struct ScanLevel
+{
+  const int* src[6];
+  int* out[6];   // (== src from the second level on)
+  int* sums[6];  // [blocks + 1]
+  int cnt[6];    // 0: nothing (left) to do for this array
+  int per;
+};
+__global__ __launch_bounds__(256) void k_scan_blocks(ScanLevel L)
+{
+  __shared__ int wsum[4];
+  const int j = blockIdx.y, cnt = L.cnt[j], per = L.per;
+  if (cnt <= 0) return;
+  const int nb = (cnt + per - 1) / per;
+  if ((int)blockIdx.x >= nb) return;  // (a launch shared with a longer array)
+  const int c = blockIdx.x * per + threadIdx.x;
+  const int v = c < cnt ? L.src[j][c] : 0;
+  int inc = v;
+  for (int o = 1; o < 64; o <<= 1)
+  {
+    const int t = __shfl_up(inc, o);
+    if ((threadIdx.x & 63) >= o) inc += t;
+  }
+  if ((threadIdx.x & 63) == 63) wsum[threadIdx.x >> 6] = inc;
+  __syncthreads();
+  int add = 0;
+  for (int w = 0; w < (int)(threadIdx.x >> 6); ++w) add += wsum[w];
+  if (c < cnt) L.out[j][c] = add + inc - v;
+  if ((int)threadIdx.x == per - 1)
+  {
+    L.sums[j][blockIdx.x] = add + inc;
+    if (nb == 1) L.out[j][cnt] = add + inc;
+  }
+}
+__global__ __launch_bounds__(256) void k_scan_addback(ScanLevel L)
+{
+  const int j = blockIdx.y, cnt = L.cnt[j], per = L.per;
+  if (cnt <= per) return;  // nothing, or one block: complete as it is
+  const int c = blockIdx.x * 256 + threadIdx.x;
+  if (c < cnt) L.out[j][c] += L.sums[j][c / per];
+  else if (c == cnt) L.out[j][cnt] = L.sums[j][(cnt + per - 1) / per];  // the scanned sums' own total
+}
+struct ScanPtrs
+{
+  const int *oscan[3], *fscan[3];
+};
+__global__ __launch_bounds__(256) void k_add_merge_global(AddBatch b, ScanPtrs s)
+{
+  const AddOne& A = b.a[blockIdx.y];
+  d_add_merge<true>(blockIdx.x, A.p, A.st, A.use_box, A.map, A.old_local, A.old_chunks, A.ochunks, b.oblocks, A.skeys, A.n, A.fresh, A.fresh_flag, A.fresh_chunks,
+                    (A.n + 255) / 256, A.dst, A.rec, A.sorder, s.oscan[blockIdx.y], s.fscan[blockIdx.y]);
+}
+struct ScanJob
+{
+  const int* src;
+  int* out;   // [cnt + 1]; may be src
+  int* sums;  // room for sums_room(cnt) ints
+  int cnt;
+};
+size_t sums_room(int cnt) { return (size_t)cnt / 32 + 32; }  // more than the sum over the levels of (blocks + 1), with blocks of 64 entries or more
+void launch_scans(hipStream_t st, const ScanJob* jobs, int nj, int per)
+{
+  ScanLevel lv[8];  // (64^6 entries are more than an int counts)
+  int blocks[8];
+  int depth = 0;
+  ScanLevel cur{};
+  cur.per = per;
+  for (int j = 0; j < nj; ++j) { cur.src[j] = jobs[j].src; cur.out[j] = jobs[j].out; cur.sums[j] = jobs[j].sums; cur.cnt[j] = jobs[j].cnt; }
+  for (;;)
+  {
+    ScanLevel next{};
+    next.per = per;
+    int most = 0;
+    for (int j = 0; j < nj; ++j)
+    {
+      const int nb = cur.cnt[j] > 0 ? (cur.cnt[j] + per - 1) / per : 0;
+      most = std::max(most, nb);
+      if (nb > 1) { next.src[j] = next.out[j] = cur.sums[j]; next.sums[j] = cur.sums[j] + nb + 1; next.cnt[j] = nb; }
+    }
+    if (most == 0) break;
+    lv[depth] = cur;
+    blocks[depth++] = most;
+    if (most == 1 || depth == 8) break;
+    cur = next;
+  }
+  for (int l = 0; l < depth; ++l) hipLaunchKernelGGL(k_scan_blocks, dim3(blocks[l], nj), dim3(per), 0, st, lv[l]);
+  for (int l = depth - 2; l >= 0; --l)
+  {
+    int most = 0;
+    for (int j = 0; j < nj; ++j) most = std::max(most, lv[l].cnt[j]);
+    hipLaunchKernelGGL(k_scan_addback, dim3(most / 256 + 1, nj), dim3(256), 0, st, lv[l]);
+  }
 }
 __global__ void k_add_commit(AddBatch b) { const AddOne& A = b.a[blockIdx.y]; d_add_commit(blockIdx.x, A.p, A.st, A.use_box); }
 }  // namespace
@@ -740,7 +849,7 @@ int ensure_batch(lsa_device_grid* g, int n)
   if (n <= g->bcap) return LSA_OK;
   // (twice what is asked for: outgrowing the batch retires eight buffers, and freeing them at the next frame's start waits for
   //  the device eight times -- 0.2-0.6 ms; a keyframe's keypoint count wanders by a quarter over the first hundred frames)
-  const int cap = std::max(2 * n, 1 << 15);
+  const int cap = (int)std::min(std::max(2ll * n, 1ll << 15), kAddressable);
   auto fr = [g](void* p) { retire_dev(g->ctx, p); };
   fr(g->batch); fr(g->bkeys); fr(g->skeys); fr(g->border); fr(g->sorder); fr(g->heads); fr(g->fresh_flag); fr(g->vrank);
   retire_view(g, g->fresh);
@@ -758,8 +867,29 @@ int ensure_batch(lsa_device_grid* g, int n)
   return LSA_OK;
 }
 
+// room for the scans of the form that keeps them in global memory: grown like the batch scratch, nothing freed while work may be
+// in flight
+static int ensure_scans(lsa_device_grid* g, int ochunks, int fchunks, size_t sums)
+{
+  auto grow = [g](int*& p, int& cap, size_t want) -> int {
+    if (want <= (size_t)cap) return LSA_OK;
+    const size_t to = std::min<size_t>(std::max<size_t>(2 * want, 1 << 12), 0x7fffffff);
+    retire_dev(g->ctx, p);
+    p = nullptr;
+    cap = 0;
+    G_HIP(hipMalloc((void**)&p, to * sizeof(int)));
+    cap = (int)to;
+    return LSA_OK;
+  };
+  int rc = grow(g->oscan, g->oscan_cap, (size_t)ochunks + 1);
+  if (!rc) rc = grow(g->fscan, g->fscan_cap, (size_t)fchunks + 1);
+  if (!rc) rc = grow(g->scan_sums, g->scan_sums_cap, sums);
+  return rc;
+}
+
 // Add of the ns[i] points in gs[i]->batch (device), for up to three maps of one context at a time: seven launches
-// whatever the number of maps
+// whatever the number of maps -- while the chunk tables of the merge fit LDS (every keyframe's do); a few more for the scans in
+// global memory when they do not, or when a map's "GlobalScans" asks for that form
 int add_batches(lsa_device_grid* const* gs, const int* ns, int count, bool fixed, double time, bool do_roll)
 {
   lsa_device_grid* g = gs[0];  // (for the error macro; all maps share the context and the stream)
@@ -771,6 +901,9 @@ int add_batches(lsa_device_grid* const* gs, const int* ns, int count, bool fixed
     lsa_device_grid* gi = gs[i];
     if (gi->ctx != g->ctx || gi->stream != st) return g->ctx->fail(LSA_E_ARG, "lsa_device_grid: the maps of one insertion share a context");
     tighten(gi);
+    if ((long long)gi->n_upper + ns[i] > kAddressable)
+      return g->ctx->fail(LSA_E_CAPACITY, "lsa_device_grid: the voxels of the map (" + std::to_string(gi->n_upper) + ") and the points of the insertion (" + std::to_string(ns[i]) +
+                                              ") together are more than one insertion addresses (2^31 - 8193)");
     const int rc = begin_modification(gi, gi->n_upper + ns[i], 2 * (size_t)ns[i]);
     if (rc) return rc;
     AddOne& A = b.a[i];
@@ -788,7 +921,27 @@ int add_batches(lsa_device_grid* const* gs, const int* ns, int count, bool fixed
   b.kblocks = kmax;
   b.oblocks = omax;
   const size_t lds = (size_t)(omax + kmax + 2) * sizeof(int);
-  if (lds > 48 * 1024) return g->ctx->fail(LSA_E_CAPACITY, "lsa_device_grid: more than twelve million voxels in a map");
+  // the form: the tables in LDS while they fit (12 288 entries: n / 256 + voxels / 1024), in global memory otherwise
+  int knob = 0;
+  for (int i = 0; i < count; ++i) knob = std::max(knob, gs[i]->GlobalScans);
+  const bool global = knob != 0 || lds > 48 * 1024;
+  const int per = knob == 2 ? 64 : 256;  // entries a scan block takes
+  ScanJob tables[6], flags[3];
+  ScanPtrs sp{};
+  if (global)
+    for (int i = 0; i < count; ++i)
+    {
+      lsa_device_grid* gi = gs[i];
+      const int fchunks = (ns[i] + 255) / 256, ochunks = b.a[i].ochunks;
+      // the block sums: of the flags of CENTROID first, then (the flags' scan is over) of the two tables side by side
+      const int rc = ensure_scans(gi, ochunks, fchunks, std::max(sums_room(ns[i]), sums_room(ochunks) + sums_room(fchunks)));
+      if (rc) return rc;
+      tables[2 * i] = ScanJob{gi->chunks, gi->oscan, gi->scan_sums, ochunks};
+      tables[2 * i + 1] = ScanJob{gi->heads, gi->fscan, gi->scan_sums + sums_room(ochunks), fchunks};
+      flags[i] = ScanJob{gi->vrank, gi->vrank, gi->scan_sums, b.a[i].p.sampling == 4 ? ns[i] : 0};
+      sp.oscan[i] = gi->oscan;
+      sp.fscan[i] = gi->fscan;
+    }
   double bytes = 0;
   for (int i = 0; i < count; ++i) bytes += (double)ns[i] * (32 + 12 + 44) + (double)gs[i]->n_upper * 44 * 2;
   {
@@ -803,10 +956,17 @@ int add_batches(lsa_device_grid* const* gs, const int* ns, int count, bool fixed
     if (centroid)
     {
       hipLaunchKernelGGL(k_add_flags, dim3(kmax, y), dim3(256), 0, st, b);
-      hipLaunchKernelGGL(k_add_vscan, dim3(1, y), dim3(1024), 0, st, b);
+      // (one workgroup per map walks the whole batch: linear, but alone -- 10 ms for three million points; the multi-level scan instead)
+      if (global) launch_scans(st, flags, count, per);
+      else hipLaunchKernelGGL(k_add_vscan, dim3(1, y), dim3(1024), 0, st, b);
     }
     hipLaunchKernelGGL(k_add_fold, dim3(kmax, y), dim3(256), 0, st, b);
-    hipLaunchKernelGGL(k_add_merge, dim3(omax + kmax, y), dim3(256), lds, st, b);
+    if (global)
+    {
+      launch_scans(st, tables, 2 * count, per);
+      hipLaunchKernelGGL(k_add_merge_global, dim3(omax + kmax, y), dim3(256), 0, st, b, sp);
+    }
+    else hipLaunchKernelGGL(k_add_merge, dim3(omax + kmax, y), dim3(256), lds, st, b);
     hipLaunchKernelGGL(k_add_commit, dim3(1, y), dim3(64), 0, st, b);
   }
   for (int i = 0; i < count; ++i)

@@ -839,6 +839,60 @@ int lsa_slam_map_io_counts(const lsa_slam* s, int counts[3]);
 int lsa_slam_set_trajectory_and_rebuild_maps(lsa_slam* s, const double* poses17, int n);
 int lsa_slam_logged_frames(const lsa_slam* s);
 int lsa_slam_get_logged_keypoints(lsa_slam* s, int frame, int type, lsa_point_t* out, int capacity);
+/* Loop closure: the registration of a logged frame against the part of the log recorded when the place was first seen -- the
+ * constraint a pose-graph optimizer (the caller's) takes; the corrected trajectory comes back through
+ * lsa_slam_set_trajectory_and_rebuild_maps.  Nothing but the result leaves the device.
+ * - lsa_slam_register_logged_frames(query q, revisited r, params, guess, out), indices into the logged trajectory:
+ *   1. windows R = [r - revisited_half_window, r + ...] and Q = [q - query_half_window, q + ...], clipped to the log;
+ *   2. target: per keypoint type in use the points of R under the logged poses (lsa_kplog_replay_range, rule 2 -- rule 0 when
+ *      "Undistortion" is NONE) as ONE RollingGrid::Add(fixed = false, time = -1, roll = true) into a fresh device grid with
+ *      that type's map parameters; the whole grid, unfiltered, is the kNN target;
+ *   3. query: the points of Q under inv(P[q]) * P[i], same rule -- q's BASE frame;
+ *   4. the ICP loop of Slam::Localization (match parameters, saturation distance interpolated over the iterations, types in
+ *      the order EDGE, PLANE, BLOB, early end when a solve makes no step, skipped below "MinNbMatchedKeypoints", "TwoDMode"
+ *      honoured) without sensor terms and without undistortion between the iterations, then the registration error.
+ *   guess: row-major 4x4 world pose of q's BASE the loop starts from; NULL = the logged pose of q.  params NULL = defaults.
+ *   All of it runs on a scratch context of the handle (made by the first call): the working keypoints, the map targets, the
+ *   sub-maps' validity, the maps and the look-ahead of the frame path are not touched; the call waits for the map workers
+ *   and for the device (it is an offline call).
+ *   LSA_E_STATE when "LoggingTimeout" is 0, keypoint logging stopped, or the keypoint log does not cover the logged poses;
+ *   LSA_E_ARG for an index outside the log, a negative window, or windows that overlap.  A refusal changes nothing.
+ *   Read-only parameters of lsa_slam_get_param, a measurement hook: "LoopClosureReplaySeconds", "LoopClosureMapsSeconds",
+ *   "LoopClosureIcpSeconds", "LoopClosureSeconds" -- the last call's two replays, scratch maps, ICP loop and the whole of it by the
+ *   HOST's clock.  A stage counts what the host waited for in it: the replays are waited for, the insertions behind the first
+ *   are only enqueued there and are waited for through the sub-maps' sizes, so their time is in the "maps" share.
+ * - lsa_loop_closure_params_init: revisited_half_window 5, query_half_window 0, everything else 0.
+ * - lsa_loop_closure_candidate(poses17, n, query, min_travelled, max_distance): host only, no device.  Rows as
+ *   lsa_slam_get_trajectory gives them.  Among the frames i < query at least min_travelled metres back along the trajectory
+ *   (sum of the step lengths between i and query) and at most max_distance metres from query's position, the nearest one,
+ *   the lower index on a tie; -1 when there is none, LSA_E_ARG for a bad argument.  Place recognition proper is the caller's. */
+typedef struct lsa_loop_closure_params_t
+{
+  int32_t revisited_half_window; /* frames on either side of `revisited` that make the target (default 5) */
+  int32_t query_half_window;     /* frames on either side of `query` that are registered together (default 0) */
+  int32_t icp_max_iter;          /* <= 0: "LocalizationICPMaxIter" */
+  int32_t lm_max_iter;           /* <= 0: "LocalizationLMMaxIter" */
+  double init_saturation;        /* <= 0: "LocalizationInitSaturationDistance" */
+  double final_saturation;       /* <= 0: "LocalizationFinalSaturationDistance" */
+} lsa_loop_closure_params_t;
+typedef struct lsa_loop_closure_result_t
+{
+  double world[16];        /* the registered world pose of query's BASE, row-major */
+  double relative[16];     /* inv(P[revisited]) * world: the edge revisited -> query */
+  double covariance[36];   /* LocalOptimizer::EstimateRegistrationError at `world` (DoF order X, Y, Z, rX, rY, rZ) */
+  double position_error;   /* [m] */
+  double orientation_error;/* [deg] */
+  int32_t status;          /* 0 registered; 1 skipped (fewer matches than "MinNbMatchedKeypoints"): world = the guess */
+  int32_t iterations;      /* ICP iterations run */
+  int32_t first_histogram[3][LSA_MATCH_NSTATUS]; /* match rejection histograms of the first ... */
+  int32_t last_histogram[3][LSA_MATCH_NSTATUS];  /* ... and of the last iteration, per keypoint type */
+  int64_t target_points[3];/* size of the target sub-map per keypoint type */
+  int64_t query_points[3]; /* keypoints registered per type */
+} lsa_loop_closure_result_t;
+void lsa_loop_closure_params_init(lsa_loop_closure_params_t* params);
+int lsa_slam_register_logged_frames(lsa_slam* s, int query, int revisited, const lsa_loop_closure_params_t* params, const double guess[16],
+                                    lsa_loop_closure_result_t* out);
+int lsa_loop_closure_candidate(const double* poses17, int n, int query, double min_travelled, double max_distance);
 
 
 /* ------------------------------------------------------------------------- */
@@ -971,7 +1025,18 @@ int lsa_pcd_io_times(const lsa_ctx* ctx, double out[8]);
  *   LSA_E_ARG unless n == lsa_kplog_size and n >= 2.
  * - lsa_kplog_replay_to_grids: the same straight into the batch buffers of the device maps grids[k] (types in type_mask),
  *   followed by RollingGrid::Add(aggregate, fixed = false, time = -1, roll = false) on each (Slam.cxx:474); the caller
- *   rolls (lsa_device_grid_roll(grids[k], last_min[k], last_max[k]), Slam.cxx:475). */
+ *   rolls (lsa_device_grid_roll(grids[k], last_min[k], last_max[k]), Slam.cxx:475).
+ * - lsa_kplog_replay_range: ONE launch (k_log_replay_range) for the frames first..last (inclusive) alone -- their tables, their
+ *   points: a range costs what its points cost, not what the log costs.  poses / times are still those of all n =
+ *   lsa_kplog_size frames (frame `first` >= 1 interpolates from pose[first - 1]); the caller may pass any poses.  rule:
+ *     0  every frame by the rigid pose[i];
+ *     1  the rebuild's rule, lsa_kplog_replay's with undistort != 0: SetTimes(times[i] - times[i-1], 0.);
+ *     2  the sweep rule: SetTimes(-(times[i] - times[i-1]), 0.) -- pose[i-1] one sweep BEFORE pose[i], which is where the
+ *        points of a frame whose times lie in [-sweep, 0] were taken; the geometry a registration wants.
+ *   Frame 0 is rigid under every rule; the per-point arithmetic is lsa_kplog_replay's.  The result goes where lsa_kplog_replay's
+ *   goes (lsa_kplog_replayed; out[k] where given).  box_min / box_max [type][xyz]: the box of ALL replayed points of a type;
+ *   a NaN coordinate takes no part; FLT_MAX / -FLT_MAX for a type without points.
+ *   LSA_E_ARG (nothing written) for a bad range or rule or n != lsa_kplog_size, LSA_E_STATE for a stopped log. */
 int lsa_kplog_append(lsa_ctx* ctx);
 int lsa_kplog_append_points(lsa_ctx* ctx, const lsa_point_t* const pts[3], const int n[3]);
 int lsa_kplog_pop_front(lsa_ctx* ctx);
@@ -986,6 +1051,8 @@ int lsa_kplog_replay(lsa_ctx* ctx, unsigned type_mask, const double* poses, cons
 long long lsa_kplog_replayed(const lsa_ctx* ctx, int type, const lsa_point_t** pts);
 int lsa_kplog_replay_to_grids(lsa_ctx* ctx, unsigned type_mask, const double* poses, const double* times, int n, int undistort, lsa_device_grid* const grids[3],
                               float last_min[3][3], float last_max[3][3]);
+int lsa_kplog_replay_range(lsa_ctx* ctx, unsigned type_mask, const double* poses, const double* times, int n, int first, int last, int rule,
+                           lsa_point_t* const out[3], float box_min[3][3], float box_max[3][3]);
 
 /* ---- the rolling voxel map (host) ---------------------------
  * LidarSlam::RollingGrid -- slam_lib/include/LidarSlam/RollingGrid.h:63-212,

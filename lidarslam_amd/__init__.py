@@ -84,6 +84,7 @@ ABI_SYMBOLS = [
     "lsa_kplog_append", "lsa_kplog_append_points", "lsa_kplog_pop_front", "lsa_kplog_clear", "lsa_kplog_size", "lsa_kplog_count", "lsa_kplog_get",
     "lsa_kplog_bytes", "lsa_kplog_stopped", "lsa_kplog_replay", "lsa_kplog_replayed", "lsa_kplog_replay_to_grids",
     "lsa_slam_set_trajectory_and_rebuild_maps", "lsa_slam_logged_frames", "lsa_slam_get_logged_keypoints",
+    "lsa_kplog_replay_range", "lsa_loop_closure_params_init", "lsa_slam_register_logged_frames", "lsa_loop_closure_candidate",
 ]
 
 PCD_ASCII, PCD_BINARY, PCD_BINARY_COMPRESSED = 0, 1, 2  # PCDFormat (PointCloudStorage.h:60-65)
@@ -123,6 +124,58 @@ class SolveResult(C.Structure):
         ("num_evaluations", C.c_int), ("num_matches", C.c_int), ("skipped", C.c_int), ("termination", C.c_int),
         ("message", C.c_char_p),
     ]
+
+
+class LoopClosureParams(C.Structure):
+    """lsa_loop_closure_params_t (include/lidarslam_amd.h): a value <= 0 of the last four means the Localization parameter
+    of the same meaning."""
+
+    _fields_ = [
+        ("revisited_half_window", C.c_int32), ("query_half_window", C.c_int32), ("icp_max_iter", C.c_int32), ("lm_max_iter", C.c_int32),
+        ("init_saturation", C.c_double), ("final_saturation", C.c_double),
+    ]
+
+    def __init__(self, revisited_half_window=5, query_half_window=0, icp_max_iter=0, lm_max_iter=0, init_saturation=0.0, final_saturation=0.0):
+        super().__init__(revisited_half_window, query_half_window, icp_max_iter, lm_max_iter, init_saturation, final_saturation)
+
+
+class LoopClosureResultStruct(C.Structure):
+    """lsa_loop_closure_result_t (include/lidarslam_amd.h)."""
+
+    _fields_ = [
+        ("world", C.c_double * 16), ("relative", C.c_double * 16), ("covariance", C.c_double * 36),
+        ("position_error", C.c_double), ("orientation_error", C.c_double), ("status", C.c_int32), ("iterations", C.c_int32),
+        ("first_histogram", C.c_int32 * 24), ("last_histogram", C.c_int32 * 24), ("target_points", C.c_int64 * 3), ("query_points", C.c_int64 * 3),
+    ]
+
+
+class LoopClosureResult:
+    """What Slam.register_logged_frames returns: world (4, 4), relative (4, 4) = inv(P[revisited]) @ world, covariance (6, 6),
+    position_error [m], orientation_error [deg], status (0 registered, 1 skipped), iterations, first_histogram /
+    last_histogram (3, 8) and target_points / query_points (3,)."""
+
+    def __init__(self, r):
+        self.world = np.array(r.world).reshape(4, 4)
+        self.relative = np.array(r.relative).reshape(4, 4)
+        self.covariance = np.array(r.covariance).reshape(6, 6)
+        self.position_error, self.orientation_error = r.position_error, r.orientation_error
+        self.status, self.iterations = r.status, r.iterations
+        self.first_histogram = np.array(r.first_histogram, np.int32).reshape(3, 8)
+        self.last_histogram = np.array(r.last_histogram, np.int32).reshape(3, 8)
+        self.target_points = np.array(r.target_points, np.int64)
+        self.query_points = np.array(r.query_points, np.int64)
+
+
+def loop_closure_candidate(poses, times, query, min_travelled, max_distance):
+    """lsa_loop_closure_candidate on a trajectory as Slam.trajectory() gives it (poses (n, 4, 4), times (n,)): among the
+    frames before `query` at least min_travelled metres back along the trajectory and within max_distance metres of
+    query's position, the nearest (the lower index on a tie); -1 when there is none.  Host only."""
+    P = np.asarray(poses, np.float64).reshape(-1, 16)
+    rows = np.ascontiguousarray(np.concatenate([P, np.asarray(times, np.float64).reshape(-1, 1)], axis=1))
+    rc = lib().lsa_loop_closure_candidate(ptr(rows), rows.shape[0], int(query), float(min_travelled), float(max_distance))
+    if rc < -1:
+        raise _error("lsa_loop_closure_candidate", rc, "bad argument")
+    return rc
 
 
 class SensorTerms(C.Structure):
@@ -419,6 +472,11 @@ def lib():
     L.lsa_kplog_replayed.restype = C.c_longlong
     L.lsa_kplog_replayed.argtypes = [vp, i32, vp]
     L.lsa_kplog_replay_to_grids.argtypes = [vp, C.c_uint, vp, vp, i32, i32, vp, vp, vp]
+    L.lsa_kplog_replay_range.argtypes = [vp, C.c_uint, vp, vp, i32, i32, i32, i32, vp, vp, vp]
+    L.lsa_loop_closure_params_init.restype = None
+    L.lsa_loop_closure_params_init.argtypes = [vp]
+    L.lsa_slam_register_logged_frames.argtypes = [vp, i32, i32, vp, vp, vp]
+    L.lsa_loop_closure_candidate.argtypes = [vp, i32, i32, C.c_double, C.c_double]
     L.lsa_slam_set_trajectory_and_rebuild_maps.argtypes = [vp, vp, i32]
     L.lsa_slam_logged_frames.argtypes = [vp]
     L.lsa_slam_get_logged_keypoints.argtypes = [vp, i32, i32, vp, i32]
@@ -1008,6 +1066,21 @@ class Context:
         sizes = [int(self.L.lsa_kplog_replayed(self.h, k, C.byref(C.c_void_p()))) for k in range(3)]
         return [o[:s].copy() for o, s in zip(outs, sizes)], mn, mx
 
+    def kplog_replay_range(self, poses, times, first, last, rule, type_mask=7):
+        """the logged frames first..last (inclusive) under poses (n, 4, 4) dated times (n,) of ALL logged frames; rule 0 rigid,
+        1 the rebuild's times (t[i] - t[i-1], 0), 2 the sweep's (-(t[i] - t[i-1]), 0) -> ([edges, planes, blobs] frames
+        ascending, min [3][3], max [3][3] of all replayed points per type)"""
+        P = np.ascontiguousarray(np.asarray(poses, np.float64).reshape(-1, 16))
+        t = np.ascontiguousarray(times, np.float64)
+        frames = range(max(first, 0), min(last, self.kplog_size() - 1) + 1)
+        outs = [np.zeros(max(sum(self.kplog_count(f, k) for f in frames) if (type_mask >> k) & 1 else 0, 1), POINT_DTYPE) for k in range(3)]
+        ptrs = (C.c_void_p * 3)(*[o.ctypes.data for o in outs])
+        mn, mx = np.zeros((3, 3), np.float32), np.zeros((3, 3), np.float32)
+        self._check(self.L.lsa_kplog_replay_range(self.h, type_mask, ptr(P), ptr(t), P.shape[0], int(first), int(last), int(rule), ptrs, ptr(mn), ptr(mx)),
+                    "lsa_kplog_replay_range")
+        sizes = [int(self.L.lsa_kplog_replayed(self.h, k, C.byref(C.c_void_p()))) for k in range(3)]
+        return [o[:s].copy() for o, s in zip(outs, sizes)], mn, mx
+
     def kplog_replay_to_grids(self, poses, times, grids, undistort=True):
         """the same straight into device maps of this context: grids = [edges, planes, blobs], a DeviceGrid or None each;
         per map ONE Add(aggregate, fixed=False, time=-1, roll=False), nothing comes to the host.  Returns the last
@@ -1274,6 +1347,19 @@ class Slam:
         P = np.asarray(poses, np.float64).reshape(-1, 16)
         rows = np.ascontiguousarray(np.concatenate([P, np.asarray(times, np.float64).reshape(-1, 1)], axis=1))
         self._check(self.L.lsa_slam_set_trajectory_and_rebuild_maps(self.h, ptr(rows), rows.shape[0]), "lsa_slam_set_trajectory_and_rebuild_maps")
+
+
+    def register_logged_frames(self, query, revisited, params=None, guess=None):
+        """Loop closure: logged frame `query` registered against the logged keypoints around logged frame `revisited`
+        (indices into trajectory()) -> LoopClosureResult.  params: a LoopClosureParams (None: its defaults); guess: (4, 4)
+        world pose of query's BASE to start from (None: the logged pose).  The frame path does not notice the call.  Raises
+        LsaError (.code E_STATE or E_ARG) and changes nothing when it cannot."""
+        p = params if params is not None else LoopClosureParams()
+        g = None if guess is None else np.ascontiguousarray(np.asarray(guess, np.float64).reshape(16))
+        r = LoopClosureResultStruct()
+        self._check(self.L.lsa_slam_register_logged_frames(self.h, int(query), int(revisited), C.byref(p), None if g is None else ptr(g), C.byref(r)),
+                    "lsa_slam_register_logged_frames")
+        return LoopClosureResult(r)
 
 
 class RollingGrid:

@@ -323,6 +323,25 @@ int lsa_slam_get_logged_keypoints(lsa_slam* s, int frame, int type, lsa_point_t*
   return n;
 }
 
+void lsa_loop_closure_params_init(lsa_loop_closure_params_t* params)
+{
+  if (!params) return;
+  std::memset(params, 0, sizeof(*params));
+  params->revisited_half_window = 5;
+}
+
+int lsa_slam_register_logged_frames(lsa_slam* s, int query, int revisited, const lsa_loop_closure_params_t* params, const double guess[16],
+                                    lsa_loop_closure_result_t* out)
+{
+  if (!s) return LSA_E_ARG;
+  return s->core.RegisterLoggedFrames(query, revisited, params, guess, out);
+}
+
+int lsa_loop_closure_candidate(const double* poses17, int n, int query, double min_travelled, double max_distance)
+{
+  return lsa::host::LoopClosureCandidate(poses17, n, query, min_travelled, max_distance);
+}
+
 // ---- LidarSlam::RollingGrid on its own (include/lidarslam_amd.h, "the rolling voxel map") ----
 struct lsa_rolling_grid
 {

@@ -8,6 +8,8 @@
 #include <cstring>
 #include <ctime>
 #include "lsa_pcd.h"
+#include "../lsa_device_grid_io.h"
+#include "../lsa_kplog_io.h"
 
 namespace lsa
 {
@@ -146,6 +148,9 @@ SlamCore::~SlamCore()
     std::fprintf(stderr, "[stage debug] per frame, us: garbage+adopt %.1f | wait for the look-ahead thread %.1f | ego-motion before its loop %.1f | after the maps %.1f | registration error %.1f | localization outside its stage timers %.1f | of the first: garbage %.1f, up to the hand-over %.1f (%ld frames)\n",
                  1e6 * DbgAcc[0] / DbgFrames, 1e6 * DbgAcc[1] / DbgFrames, 1e6 * DbgAcc[2] / DbgFrames, 1e6 * DbgAcc[3] / DbgFrames, 1e6 * DbgAcc[4] / DbgFrames, 1e6 * DbgAcc[5] / DbgFrames, 1e6 * DbgAcc[6] / DbgFrames, 1e6 * DbgAcc[7] / DbgFrames, DbgFrames);
   WaitMaps();
+  for (auto* g : LoopMaps)
+    if (g) lsa_device_grid_destroy(g);
+  if (LoopCtx) lsa_ctx_destroy(LoopCtx);
   for (auto* g : DevMaps)
     if (g) lsa_device_grid_destroy(g);
   if (Ctx) lsa_ctx_destroy(Ctx);
@@ -648,7 +653,9 @@ lsa_match_params_t SlamCore::LocMatchParams() const
 // What the two tell RunIcpLoop about their loop; what only one of them does at some point of an iteration is a callable.
 struct SlamCore::IcpLoopSpec
 {
-  const char* name;                        // "ego" / "loc" (trace lines)
+  const char* name;                        // "ego" / "loc" / "reg" (trace lines)
+  lsa_ctx* ctx;                            // the context the loop drives; NULL: the frame path's own
+  bool inLine;                             // strictly in line whatever ICPAhead says: nothing of the loop waits on the device for the host
   int target, set;                         // the LSA_TARGET_* searched, the LSA_SET_* matched against it
   unsigned matchMask, solveMask;           // keypoint types matched / whose residual blocks the solves take
   unsigned maxIter, lmMaxIter;
@@ -690,7 +697,7 @@ const bool kGateDebug = std::getenv("LSA_GATE_DEBUG") != nullptr;
 //   accepted(last, undistortion)      `pose` is the solve's; what was enqueued ahead has been called off if `last`.  A
 //                                     RefineUndistortion left in `undistortion` (pending) rides in the next search
 //   finished(optimizer)               after the last accepted iteration
-// In line (ICPAhead = 0, and the fall-back of the other two): match, solve, and the next match once the pose is known.
+// In line (ICPAhead = 0, spec.inLine, and the fall-back of the other two): match, solve, and the next match once the pose is known.
 // Gates (ICPAhead = 1, and loops longer than kChainMax): iteration i + 1 is enqueued behind a gate (lsa_icp_gate) while
 // iteration i runs: when the solve's result arrives its launches are in the queue already, and all that is between the
 // solve and the next search is one store the gate polls for (or the call that calls them off: Slam.cxx:919-923, 950).
@@ -709,16 +716,18 @@ template <class Top, class Enqueued, class Solved, class Skipped, class Accepted
 int SlamCore::RunIcpLoop(const IcpLoopSpec& spec, Pose& pose, const Top& top, const Enqueued& enqueued, const Solved& solved, const Skipped& skipped,
                          const Accepted& accepted, const Finished& finished)
 {
+  lsa_ctx* const ctx = spec.ctx ? spec.ctx : Ctx;  // the context the loop drives
+  const bool own = ctx == Ctx;                      // ... the frame path's: the look-ahead's interlude rides in its solves
   TotalMatchedKeypoints = 0;
   lsa_match_params_t mp = spec.match;
   auto saturation = [&](unsigned icpIter) {
     const double iterRatio = icpIter / static_cast<double>(spec.maxIter - 1);
     return (1 - iterRatio) * spec.initSaturation + iterRatio * spec.finalSaturation;
   };
-  const bool aheadOk = ICPAhead >= 1 && DeviceLM && FusedMatch && (kAheadLoops & spec.loopBit);
+  const bool aheadOk = !spec.inLine && ICPAhead >= 1 && DeviceLM && FusedMatch && (kAheadLoops & spec.loopBit);
   bool chain = aheadOk && ICPAhead >= 2 && spec.maxIter <= kChainMax && spec.linksOk;
   bool ahead = aheadOk && !chain && spec.gatesOk;
-  if (ahead || chain) lsa_icp_abandon(Ctx);
+  if (ahead || chain) lsa_icp_abandon(ctx);
   unsigned chained = 0;            // iterations 0 .. chained - 1 are in the queue (links)
   long long chainSerial[kChainMax][3] = {};
   bool enqueuedAhead = false;      // this iteration's launches are in the queue (their gate has been answered)
@@ -733,13 +742,13 @@ int SlamCore::RunIcpLoop(const IcpLoopSpec& spec, Pose& pose, const Top& top, co
   auto callOffRest = [&](bool all) {
     if (ticket >= 0)
     {
-      lsa_icp_cancel(Ctx, ticket);
-      lsa_solve_device_drop(Ctx);
+      lsa_icp_cancel(ctx, ticket);
+      lsa_solve_device_drop(ctx);
       ticket = -1;
     }
     if (all || icpIter + 1 < chained)
     {
-      lsa_icp_abandon(Ctx);
+      lsa_icp_abandon(ctx);
       chained = 0;
     }
   };
@@ -747,7 +756,7 @@ int SlamCore::RunIcpLoop(const IcpLoopSpec& spec, Pose& pose, const Top& top, co
 
   auto takeSerials = [&](long long* serial) {
     for (int k = 0; k < 3; ++k)
-      if ((spec.matchMask >> k) & 1u) serial[k] = lsa_match_serial(Ctx, k);
+      if ((spec.matchMask >> k) & 1u) serial[k] = lsa_match_serial(ctx, k);
   };
   auto setSerials = [&](const long long* serial) {
     for (int k = 0; k < 3; ++k)
@@ -758,9 +767,9 @@ int SlamCore::RunIcpLoop(const IcpLoopSpec& spec, Pose& pose, const Top& top, co
     // optimizer's first evaluation.  A pending undistortion (of the working keypoints: the localization's) rides in this
     // iteration's search kernel (same keypoints, one launch less)
     if (undistortion.pending)
-      LSA_TRY(lsa_match_types_undistorted(Ctx, spec.target, spec.matchMask, &mp, pose.m, nullptr, undistortion.d0.m, undistortion.d1.m, Motion.Time0, Motion.Time1));
+      LSA_TRY(lsa_match_types_undistorted(ctx, spec.target, spec.matchMask, &mp, pose.m, nullptr, undistortion.d0.m, undistortion.d1.m, Motion.Time0, Motion.Time1));
     else
-      LSA_TRY(lsa_match_types(Ctx, spec.target, spec.matchMask, spec.set, &mp, pose.m, nullptr));
+      LSA_TRY(lsa_match_types(ctx, spec.target, spec.matchMask, spec.set, &mp, pose.m, nullptr));
     undistortion.pending = false;
     takeSerials(spec.matchSerial);
     return LSA_OK;
@@ -769,7 +778,7 @@ int SlamCore::RunIcpLoop(const IcpLoopSpec& spec, Pose& pose, const Top& top, co
   auto matchAhead = [&](unsigned iter, long long* serial) -> int {
     lsa_match_params_t next = mp;
     next.saturation_distance = saturation(iter);
-    const int rc = lsa_match_types_gated(Ctx, spec.target, spec.matchMask, spec.set, &next, spec.undistortAhead);
+    const int rc = lsa_match_types_gated(ctx, spec.target, spec.matchMask, spec.set, &next, spec.undistortAhead);
     if (rc == 0) takeSerials(serial);
     return rc;
   };
@@ -779,7 +788,7 @@ int SlamCore::RunIcpLoop(const IcpLoopSpec& spec, Pose& pose, const Top& top, co
     Tick ticp;
     if (const int rc = top(icpIter); rc < 0) return rc;
     mp.saturation_distance = saturation(icpIter);
-    LocalOptimizer optimizer(Ctx);
+    LocalOptimizer optimizer(ctx);
     optimizer.SetDeviceLoop(DeviceLM);
     optimizer.SetTwoDMode(TwoDMode);
     optimizer.SetLMMaxIter(spec.lmMaxIter);
@@ -803,17 +812,17 @@ int SlamCore::RunIcpLoop(const IcpLoopSpec& spec, Pose& pose, const Top& top, co
         lsa_icp_link_t link = spec.link;
         for (unsigned j = icpIter; j < spec.maxIter; ++j)
         {
-          int leave = j + 1 < spec.maxIter ? lsa_icp_link(Ctx) : -1;
+          int leave = j + 1 < spec.maxIter ? lsa_icp_link(ctx) : -1;
           if (leave < 0) leave = -1;
           link.first = j == icpIter ? 1 : 0;
-          const int rc = lsa_solve_device_begin_linked(Ctx, spec.solveMask, j == icpIter ? prior : nullptr, TwoDMode ? 1 : 0, static_cast<int>(spec.lmMaxIter), static_cast<int>(MinNbMatchedKeypoints), leave,
+          const int rc = lsa_solve_device_begin_linked(ctx, spec.solveMask, j == icpIter ? prior : nullptr, TwoDMode ? 1 : 0, static_cast<int>(spec.lmMaxIter), static_cast<int>(MinNbMatchedKeypoints), leave,
                                                        leave >= 0 ? &link : nullptr);
           if (rc < 0) return Fail(rc, "lsa_solve_device_begin_linked");
           chained = j + 1;
           if (leave < 0) break;
           const int mrc = matchAhead(j + 1, chainSerial[j + 1]);
           if (mrc < 0) return Fail(mrc, "lsa_match_types_gated");
-          if (mrc != 0) { lsa_icp_cancel(Ctx, leave); break; }  // this match cannot wait behind a link: the loop goes on in line from there
+          if (mrc != 0) { lsa_icp_cancel(ctx, leave); break; }  // this match cannot wait behind a link: the loop goes on in line from there
         }
         chain = false;  // (enqueued once; whatever is not in the queue now runs in line)
         begun = true;
@@ -830,7 +839,7 @@ int SlamCore::RunIcpLoop(const IcpLoopSpec& spec, Pose& pose, const Top& top, co
     enqueuedAhead = false;
     if (ahead && begun && icpIter + 1 < spec.maxIter)
     {
-      ticket = lsa_icp_gate(Ctx);
+      ticket = lsa_icp_gate(ctx);
       ICP_TRACE("[%s %u] gate ticket %d\n", spec.name, icpIter, ticket);
       if (ticket < 0) { ticket = -1; ahead = false; }
       else
@@ -840,12 +849,12 @@ int SlamCore::RunIcpLoop(const IcpLoopSpec& spec, Pose& pose, const Top& top, co
         if (rc == 0)
         {
           call = "lsa_solve_device_begin";
-          rc = lsa_solve_device_begin(Ctx, spec.solveMask, nullptr, TwoDMode ? 1 : 0, static_cast<int>(spec.lmMaxIter), static_cast<int>(MinNbMatchedKeypoints));
+          rc = lsa_solve_device_begin(ctx, spec.solveMask, nullptr, TwoDMode ? 1 : 0, static_cast<int>(spec.lmMaxIter), static_cast<int>(MinNbMatchedKeypoints));
         }
         if (rc != 0)
         {
           // nothing waits behind this gate: the loop goes on without gates
-          lsa_icp_cancel(Ctx, ticket);
+          lsa_icp_cancel(ctx, ticket);
           ticket = -1;
           ahead = false;
           if (rc < 0) return Fail(rc, call);
@@ -853,7 +862,7 @@ int SlamCore::RunIcpLoop(const IcpLoopSpec& spec, Pose& pose, const Top& top, co
       }
     }
     if (const int rc = enqueued(icpIter); rc < 0) return rc;
-    if (!begun) ArmLookaheadInterlude();
+    if (!begun && own) ArmLookaheadInterlude();
     Stats.*spec.icpSeconds += ticp.Stop();
     (Stats.*spec.iterations)++;
 
@@ -888,7 +897,7 @@ int SlamCore::RunIcpLoop(const IcpLoopSpec& spec, Pose& pose, const Top& top, co
     else
     {
       LSA_TRY(optimizer.Solve(summary));
-      LSA_TRY(FinishLookaheadInterlude());
+      if (own) LSA_TRY(FinishLookaheadInterlude());
     }
     TotalMatchedKeypoints = summary.num_matches;
     if (lsa_icp_trace_on())
@@ -913,7 +922,7 @@ int SlamCore::RunIcpLoop(const IcpLoopSpec& spec, Pose& pose, const Top& top, co
     {
       double prior[6];
       ToXYZRPY(pose, prior);  // LocalOptimizer::SetPosePrior of the next iteration
-      const int prc = lsa_icp_post(Ctx, ticket, pose.m, prior, undistortion.pending ? undistortion.d0.m : nullptr, undistortion.pending ? undistortion.d1.m : nullptr, Motion.Time0, Motion.Time1);
+      const int prc = lsa_icp_post(ctx, ticket, pose.m, prior, undistortion.pending ? undistortion.d0.m : nullptr, undistortion.pending ? undistortion.d1.m : nullptr, Motion.Time0, Motion.Time1);
       if (prc < 0) return Fail(prc, "lsa_icp_post");
       ticket = -1;
       undistortion.posted = undistortion.pending;
@@ -1826,6 +1835,186 @@ int SlamCore::SetTrajectoryAndRebuildMaps(const double* poses17, int n)
   return LSA_OK;
 }
 
+// ---- loop closure: a logged frame registered against the log around a revisited pose ---------------------------------------
+int SlamCore::EnsureLoopClosureScratch()
+{
+  if (LoopCtx) return LSA_OK;
+  lsa_ctx* ctx = nullptr;
+  const int rc = lsa_ctx_create(Ctx->device, &ctx);
+  if (rc != LSA_OK) { LastError = "RegisterLoggedFrames: the scratch context could not be created"; return rc; }
+  for (int k = 0; k < 3; ++k)
+    if (const int grc = lsa_device_grid_create(ctx, &LoopMaps[k]); grc != LSA_OK)
+    {
+      LastError = std::string("RegisterLoggedFrames: a scratch map could not be created: ") + lsa_last_error(ctx);
+      for (auto*& g : LoopMaps) { if (g) lsa_device_grid_destroy(g); g = nullptr; }
+      lsa_ctx_destroy(ctx);
+      return grc;
+    }
+  LoopCtx = ctx;
+  return LSA_OK;
+}
+
+int SlamCore::RegisterLoggedFrames(int query, int revisited, const lsa_loop_closure_params_t* params, const double* guess16, lsa_loop_closure_result_t* out)
+{
+  if (!Ctx) return LSA_E_NO_DEVICE;
+  const std::string who = "RegisterLoggedFrames: ";
+  if (!out) { LastError = who + "no place for the result"; return LSA_E_ARG; }
+  if (LoggingTimeout == 0.) { LastError = who + "keypoint logging is off (LoggingTimeout = 0): there are no logged keypoints to register against"; return LSA_E_STATE; }
+  if (KpLogStopped) { LastError = who + "keypoint logging stopped when a chunk could not be allocated; Reset(true) starts it again"; return LSA_E_STATE; }
+  const int n = static_cast<int>(LogTrajectory.size());
+  if (lsa_kplog_size(Ctx) != n) { LastError = who + "the keypoint log does not cover the logged poses (logging was switched on after the first of them)"; return LSA_E_STATE; }
+  lsa_loop_closure_params_t p;
+  std::memset(&p, 0, sizeof(p));
+  p.revisited_half_window = 5;
+  if (params) p = *params;
+  LoopClosureWindows w;
+  {
+    std::string why;
+    if (const int rc = LoopClosureWindowsOf(n, query, revisited, p.revisited_half_window, p.query_half_window, &w, &why); rc != LSA_OK) { LastError = who + why; return rc; }
+  }
+  if (!DevMaps[0] || !DevMaps[1] || !DevMaps[2]) { LastError = who + "no device maps to take the scratch maps' parameters from"; return LSA_E_STATE; }
+  // from here on the device works: the map workers and the look-ahead have enqueued what they had (nothing of theirs is changed)
+  Tick tall;
+  double seconds[3] = {0., 0., 0.};  // replays, scratch maps, ICP
+  WaitMaps();
+  if (const int rc = EnsureLoopClosureScratch(); rc < 0) return rc;
+  (void)lsa_collect_garbage(LoopCtx);  // what the last call outgrew (nothing on the device waits for the host here)
+  auto failOn = [&](lsa_ctx* ctx, int rc, const char* where) {
+    LastError = who + where + ": " + lsa_last_error(ctx);
+    return rc;
+  };
+
+  unsigned mask = 0;
+  for (int k = 0; k < 3; ++k)
+    if (UseKeypoints[k]) mask |= 1u << k;
+  const int rule = Undistortion != UNDISTORTION_NONE ? 2 : 0;
+  std::vector<double> poses(static_cast<size_t>(n) * 16), times(n);
+  for (int i = 0; i < n; ++i)
+  {
+    std::memcpy(&poses[16 * static_cast<size_t>(i)], LogTrajectory[i].pose.m, 16 * sizeof(double));
+    times[i] = LogTrajectory[i].time;
+  }
+  std::memset(out, 0, sizeof(*out));
+  float mn[3][3], mx[3][3];
+  long long counts[3] = {0, 0, 0};
+
+  // the target: the revisited frames under the logged trajectory, ONE Add(fixed = false, time = -1, roll = true) per type
+  // into a fresh grid with that type's map parameters; the whole grid, unfiltered, is the sub-map
+  for (int k = 0; k < 3; ++k)
+    if (const int rc = grid_adopt_parameters(LoopMaps[k], DevMaps[k]); rc < 0) return failOn(LoopCtx, rc, "the scratch maps' parameters");
+  {
+    // (the replay waits for the log's stream; the insertions behind it are only enqueued: the sub-maps' sizes wait for them)
+    const KpLogRange range{mask, poses.data(), times.data(), n, w.r0, w.r1, rule};
+    Tick t;
+    if (const int rc = kplog_replay_range_to_grids(Ctx, range, LoopMaps, false, -1., true, counts, mn, mx); rc < 0) return failOn(Ctx, rc, "the replay of the revisited frames");
+    seconds[0] += t.Stop();
+  }
+  Tick tmaps;
+  for (int k = 0; k < 3; ++k)
+  {
+    if (!UseKeypoints[k]) continue;
+    lsa_set_target_cell_size(LoopCtx, LSA_TARGET_MAP, k, static_cast<float>((k == LSA_EDGE ? KnnCellScaleMapsEdges : KnnCellScaleMaps) * LocalMaps[k]->GetLeafSize()));
+    if (const int rc = lsa_device_grid_build_submap_begin(LoopMaps[k], nullptr, nullptr, -1, LSA_TARGET_MAP, k); rc < 0) return failOn(LoopCtx, rc, "lsa_device_grid_build_submap_begin");
+  }
+  for (int k = 0; k < 3; ++k)
+  {
+    if (!UseKeypoints[k]) continue;
+    const int size = lsa_device_grid_build_submap_end(LoopMaps[k]);
+    if (size < 0) return failOn(LoopCtx, size, "lsa_device_grid_build_submap_end");
+    out->target_points[k] = size;
+  }
+  seconds[1] += tmaps.Stop();
+
+  // the query: its frames under inv(P[q]) * P[i] -- q's BASE frame -- into the scratch context's working keypoints
+  const Pose logged = LogTrajectory[query].pose;
+  {
+    const Pose inv = Inverse(logged);
+    std::vector<double> rel(static_cast<size_t>(n) * 16, 0.);
+    for (int i = std::max(w.q0 - 1, 0); i <= w.q1; ++i)
+    {
+      const Pose r = inv * LogTrajectory[i].pose;
+      std::memcpy(&rel[16 * static_cast<size_t>(i)], r.m, 16 * sizeof(double));
+    }
+    const KpLogRange range{mask, rel.data(), times.data(), n, w.q0, w.q1, rule};
+    Tick t;
+    if (const int rc = kplog_replay_range_to_set(Ctx, range, LoopCtx, LSA_SET_WORKING, counts, mn, mx); rc < 0) return failOn(Ctx, rc, "the replay of the query frames");
+    seconds[0] += t.Stop();
+    for (int k = 0; k < 3; ++k) out->query_points[k] = counts[k];
+  }
+  Tick ticp;
+
+  // the ICP loop of Localization() on the scratch context, strictly in line: no sensor terms, no undistortion in between
+  Pose world = logged;
+  if (guess16) std::memcpy(world.m, guess16, 16 * sizeof(double));
+  // the search's form and tuning as the frame path has them (results do not depend on either)
+  lsa_set_fused_match(LoopCtx, FusedMatch ? 1 : 0);
+  lsa_set_knn_lanes(LoopCtx, LSA_EDGE, KnnLanesEdges);
+  lsa_set_knn_lanes(LoopCtx, LSA_PLANE, KnnLanesPlanes);
+  lsa_set_knn_lanes(LoopCtx, LSA_BLOB, KnnLanesBlobs);
+  lsa_set_knn_rounds(LoopCtx, LSA_EDGE, KnnRoundsEdges);
+  lsa_set_knn_rounds(LoopCtx, LSA_PLANE, KnnRoundsPlanes);
+  lsa_set_knn_rounds(LoopCtx, LSA_BLOB, KnnRoundsBlobs);
+  long long serial[3] = {0, 0, 0};
+  IcpLoopSpec spec = {};
+  spec.name = "reg";
+  spec.ctx = LoopCtx;
+  spec.inLine = true;
+  spec.target = LSA_TARGET_MAP;
+  spec.set = LSA_SET_WORKING;
+  spec.matchMask = spec.solveMask = mask;
+  spec.maxIter = p.icp_max_iter > 0 ? static_cast<unsigned>(p.icp_max_iter) : LocalizationICPMaxIter;
+  spec.lmMaxIter = p.lm_max_iter > 0 ? static_cast<unsigned>(p.lm_max_iter) : LocalizationLMMaxIter;
+  spec.initSaturation = p.init_saturation > 0. ? p.init_saturation : LocalizationInitSaturationDistance;
+  spec.finalSaturation = p.final_saturation > 0. ? p.final_saturation : LocalizationFinalSaturationDistance;
+  spec.match = LocMatchParams();
+  spec.matchSerial = serial;
+  spec.icpSeconds = &FrameStats::loc_icp;
+  spec.lmSeconds = &FrameStats::loc_lm;
+  spec.iterations = &FrameStats::loc_iters;
+  int iterations = 0;
+  RegistrationError uncertainty;
+  auto solved = [&]() -> int {
+    // the rejection histograms of this iteration's matches (the first iteration's are kept, the last one's stay)
+    for (int k = 0; k < 3; ++k)
+    {
+      if (!((mask >> k) & 1u)) continue;
+      int h[LSA_MATCH_NSTATUS];
+      if (const int rc = lsa_match_histogram(LoopCtx, k, serial[k], h); rc < 0) return failOn(LoopCtx, rc, "lsa_match_histogram");
+      for (int s = 0; s < LSA_MATCH_NSTATUS; ++s)
+      {
+        if (iterations == 0) out->first_histogram[k][s] = h[s];
+        out->last_histogram[k][s] = h[s];
+      }
+    }
+    ++iterations;
+    return LSA_OK;
+  };
+  auto skipped = [&]() -> int { out->status = 1; return LSA_OK; };
+  auto finished = [&](LocalOptimizer& optimizer) -> int { return optimizer.EstimateRegistrationError(uncertainty); };
+  // (the loop's counters are the frame path's: they are put back, the frame's statistics do not notice either)
+  const FrameStats stats = Stats;
+  const unsigned matched = TotalMatchedKeypoints;
+  const std::string error = LastError;
+  const int rc = RunIcpLoop(spec, world, kNothing, kNothing, solved, skipped, kNothing, finished);
+  Stats = stats;
+  TotalMatchedKeypoints = matched;
+  if (rc < 0) return LastError.rfind(who, 0) == 0 ? rc : failOn(LoopCtx, rc, "the ICP loop");
+  LastError = error;
+  if (const int src = lsa_sync(LoopCtx); src < 0) return failOn(LoopCtx, src, "lsa_sync");
+  seconds[2] = ticp.Stop();
+  for (int i = 0; i < 3; ++i) LoopClosureSeconds[i] = seconds[i];
+  LoopClosureSeconds[3] = tall.Stop();
+
+  std::memcpy(out->world, world.m, sizeof(out->world));
+  const Pose relative = Inverse(LogTrajectory[revisited].pose) * world;
+  std::memcpy(out->relative, relative.m, sizeof(out->relative));
+  std::memcpy(out->covariance, uncertainty.Covariance.data(), sizeof(out->covariance));
+  out->position_error = uncertainty.PositionError;
+  out->orientation_error = uncertainty.OrientationError;
+  out->iterations = iterations;
+  return LSA_OK;
+}
+
 int SlamCore::GetTargetSubMap(int k, std::vector<lsa_point_t>& out)
 {
   if (!Ctx) return LSA_E_NO_DEVICE;
@@ -2119,6 +2308,12 @@ int SlamCore::GetParam(const std::string& name, double* v) const
   if (name == "MapAddThreadsEdges") { *v = LocalMaps[LSA_EDGE]->GetAddThreads(); return LSA_OK; }
   if (name == "LoggingTimeout") { *v = LoggingTimeout; return LSA_OK; }
   if (name == "LoggingStorage") { *v = LoggingStorage; return LSA_OK; }
+  // the last RegisterLoggedFrames by the host's clock (every stage ends in a wait for the device): the two replays, the
+  // scratch maps' insertions and sub-maps, the ICP loop with the registration error, the whole call
+  if (name == "LoopClosureReplaySeconds") { *v = LoopClosureSeconds[0]; return LSA_OK; }
+  if (name == "LoopClosureMapsSeconds") { *v = LoopClosureSeconds[1]; return LSA_OK; }
+  if (name == "LoopClosureIcpSeconds") { *v = LoopClosureSeconds[2]; return LSA_OK; }
+  if (name == "LoopClosureSeconds") { *v = LoopClosureSeconds[3]; return LSA_OK; }
   if (name == "LoggedKeypointsBytes") { *v = Ctx ? static_cast<double>(lsa_kplog_bytes(Ctx)) : 0.; return LSA_OK; }
   if (name == "LoggedFrames") { *v = LoggedFrames(); return LSA_OK; }
   if (name == "TimeWindowDuration") { *v = TimeWindowDuration; return LSA_OK; }

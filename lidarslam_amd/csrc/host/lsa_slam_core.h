@@ -22,6 +22,7 @@
 #include "../../../include/lidarslam_amd.h"
 #include "lsa_hostmath.h"
 #include "lsa_lm.h"
+#include "lsa_loop_closure.h"
 #include "lsa_rolling_grid.h"
 #include "lsa_sensor_constraints.h"
 
@@ -121,6 +122,10 @@ public:
   // What Slam::RunPoseGraphOptimization does after its optimizer (Slam.cxx:404-477): the logged poses replaced by poses17
   // (rows of lsa_slam_get_trajectory), the maps rebuilt from the keypoint log under them, Tworld / PreviousTworld set.
   int SetTrajectoryAndRebuildMaps(const double* poses17, int n);
+  // Loop closure: logged frame `query` registered against the logged keypoints around `revisited` (lsa_slam_register_logged_frames
+  // in lidarslam_amd.h says what it computes).  Everything runs on a scratch context of this object's: the frame path's
+  // keypoint sets, targets, maps and look-ahead do not notice.  A refusal changes nothing and leaves its reason in Error().
+  int RegisterLoggedFrames(int query, int revisited, const lsa_loop_closure_params_t* params, const double* guess16, lsa_loop_closure_result_t* out);
   int LoggedFrames() const;
   int GetLoggedKeypoints(int frame, int type, std::vector<lsa_point_t>& out);
   void HintNextStoredFrame(int slot) { NextStoredSlot = slot; }
@@ -332,6 +337,12 @@ private:
   bool HoldLookahead = false;     // ... and must not start yet: the sub-maps extracted ahead of time for THIS frame's localization go onto the look-ahead stream first
   int TryStartLookahead();        // starts it as soon as the upload has been enqueued
   lsa_ctx* Ctx = nullptr;
+  // RegisterLoggedFrames' own context on the same device, made by its first call: the query keypoints (its working set), a
+  // scratch map per keypoint type and the targets their sub-maps become
+  lsa_ctx* LoopCtx = nullptr;
+  lsa_device_grid* LoopMaps[3] = {nullptr, nullptr, nullptr};
+  int EnsureLoopClosureScratch();
+  double LoopClosureSeconds[4] = {0., 0., 0., 0.};  // the last call by the host's clock: replays, scratch maps, ICP loop, all of it
   std::string LastError;
   uint64_t CurrentStamp = 0;
   bool HaveFrame = false;

@@ -293,6 +293,19 @@ int end_modification(lsa_device_grid* g, int record_kind, size_t entries)
 // ---- what lsa_pcd.hip needs of a grid (lsa_device_grid_io.h) ----
 lsa_ctx* grid_context(lsa_device_grid* g) { return g->ctx; }
 hipStream_t grid_stream(lsa_device_grid* g) { return g->stream; }
+// A fresh grid with another grid's geometry, sampling mode and order: the values as `src` holds them, not put through the
+// setters again (SetVoxelResolution snaps to the leaf size of the moment it is called at).  `dst` is emptied.
+int grid_adopt_parameters(lsa_device_grid* dst, const lsa_device_grid* src)
+{
+  int rc = lsa_device_grid_reset(dst, nullptr);
+  if (!rc) rc = lsa_device_grid_set(dst, "Ordered", src->Ordered ? 1. : 0.);
+  if (rc) return rc;
+  dst->GridSize = src->GridSize;
+  dst->VoxelResolution = src->VoxelResolution;
+  dst->LeafSize = src->LeafSize;
+  dst->Sampling = src->Sampling;
+  return lsa_device_grid_reset(dst, nullptr);  // (the grid's position, snapped to the resolution it has now)
+}
 }  // namespace lsa
 
 // Roll (always a pass into the other buffer: the host does not know whether the grid moves)

@@ -5,6 +5,9 @@
 //                  under the new poses, frame i >= 1 with the LinearTransformInterpolator between pose[i-1] and pose[i]
 //                  (SetTimes(t[i] - t[i-1], 0.), evaluated at the point's own time) when undistortion is on, frame 0 and
 //                  everything otherwise with the rigid pose[i]; and the box of the LAST frame's points (:472-475)
+//   k_log_replay_range  the same for a range of frames, under one of three time rules, with the box of ALL replayed points:
+//                  what the registration of logged frames (host/lsa_slam_core.cpp, RegisterLoggedFrames) makes its target
+//                  sub-map and its query keypoints of
 // Storage: an arena of fixed-size chunks.  A frame (its three types, one after the other) never straddles two chunks, so
 // growth never copies; a chunk whose frames have all been popped goes to a free list; nothing is freed while work may be in
 // flight (the context's graveyard, lsa_ctx.h).  The host keeps the frame table {device pointer, count} per frame and type.
@@ -14,6 +17,7 @@
 #include "lsa_ctx.h"
 #include "lsa_device_math.h"
 #include "lsa_device_grid_io.h"
+#include "lsa_kplog_io.h"
 
 using namespace lsa;
 
@@ -181,6 +185,74 @@ __global__ __launch_bounds__(256) void k_log_replay(ReplayArgs a, unsigned* __re
       atomicMin(&bits[6 * t + d], blo[d]);
       atomicMax(&bits[6 * t + 3 + d], bhi[d]);
     }
+}
+
+// The replay of a RANGE of frames (lsa_kplog_replay_range): the tables hold the range's frames only, the point's arithmetic
+// is k_log_replay's, and the box is that of ALL the points of a type (what a sub-map made of the range is rolled onto), not
+// of the last frame's.  Every wavefront reduces its points by shuffles, the workgroup's four through LDS, and one thread
+// sends the workgroup's box: six atomics a workgroup.
+__global__ __launch_bounds__(256) void k_log_replay_range(ReplayArgs a, unsigned* __restrict__ bits)
+{
+  __shared__ unsigned s_box[4][6];
+  const int t = blockIdx.y;
+  const long long total = a.total[t];
+  if ((long long)blockIdx.x * 256 >= total) return;  // (the whole workgroup: nobody is left waiting at the barrier)
+  const long long first = (long long)blockIdx.x * 256 + (threadIdx.x & ~63u);  // of this wavefront
+  const long long i = first + (threadIdx.x & 63u);
+  unsigned blo[3] = {~0u, ~0u, ~0u}, bhi[3] = {0u, 0u, 0u};
+  if (i < total)
+  {
+    const long long* __restrict__ off = a.off[t];
+    int lo = 0, hi = a.nframes - 1;  // the largest f with off[f] <= first (off[0] = 0): its frame is not empty
+    while (lo < hi)
+    {
+      const int mid = (lo + hi + 1) >> 1;
+      if (off[mid] <= first) lo = mid;
+      else hi = mid - 1;
+    }
+    int f = lo;
+    while (off[f + 1] <= i) ++f;  // off[nframes] = total > i
+    const float4* __restrict__ src = a.src[t][f];
+    const size_t j = (size_t)(i - off[f]);
+    float4 p = src[2 * j];
+    const float4 q = src[2 * j + 1];
+    const FrameMotion& m = a.motion[f];
+    Rigid T;
+    if (m.interp) interp_eval(m.c, point_time(q), T);
+    else T = m.R;
+    double ox, oy, oz;
+    rigid_apply(T, (double)p.x, (double)p.y, (double)p.z, ox, oy, oz);
+    p.x = (float)ox; p.y = (float)oy; p.z = (float)oz;
+    a.out[t][2 * (size_t)i] = p;
+    a.out[t][2 * (size_t)i + 1] = q;
+    const float v[3] = {p.x, p.y, p.z};
+    // a NaN coordinate takes no part, as in a min / max loop written with comparisons
+    for (int d = 0; d < 3; ++d)
+      if (v[d] == v[d]) blo[d] = bhi[d] = f2ou(v[d]);
+  }
+  for (int d = 0; d < 3; ++d)
+    for (int s = 32; s > 0; s >>= 1)
+    {
+      const unsigned l2 = __shfl_down(blo[d], s), h2 = __shfl_down(bhi[d], s);
+      blo[d] = l2 < blo[d] ? l2 : blo[d];
+      bhi[d] = h2 > bhi[d] ? h2 : bhi[d];
+    }
+  if ((threadIdx.x & 63u) == 0)
+    for (int d = 0; d < 3; ++d)
+    {
+      s_box[threadIdx.x >> 6][d] = blo[d];
+      s_box[threadIdx.x >> 6][3 + d] = bhi[d];
+    }
+  __syncthreads();
+  if (threadIdx.x < 6)
+  {
+    const int d = threadIdx.x;
+    unsigned v = s_box[0][d];
+    for (int w = 1; w < 4; ++w) v = d < 3 ? (s_box[w][d] < v ? s_box[w][d] : v) : (s_box[w][d] > v ? s_box[w][d] : v);
+    // (a word still as it was armed changes nothing: no atomic for it)
+    if (d < 3) { if (v != ~0u) atomicMin(&bits[6 * t + d], v); }
+    else if (v != 0u) atomicMax(&bits[6 * t + d], v);
+  }
 }
 
 KpLog* log_of(lsa_ctx* ctx, bool create)
@@ -383,7 +455,184 @@ int run_replay(lsa_ctx* ctx, KpLog* log, Replay* r, float last_min[3][3], float 
       }
   return LSA_OK;
 }
+// ---- the replay of a range of frames (lsa_kplog_replay_range and the library's own destinations, lsa_kplog_io.h) ----
+int check_range(lsa_ctx* ctx, const char* who, const KpLogRange& q, float box_min[3][3], float box_max[3][3])
+{
+  if (!ctx) return LSA_E_ARG;
+  if (!q.poses || !q.times || !box_min || !box_max || (q.type_mask & ~7u) || q.rule < 0 || q.rule > 2) return ctx->fail(LSA_E_ARG, std::string(who) + ": bad argument");
+  KpLog* log = ctx->kplog;
+  if (log && log->stopped) return ctx->fail(LSA_E_STATE, std::string(who) + ": keypoint logging stopped when a chunk could not be allocated");
+  const int have = log ? (int)log->frames.size() : 0;
+  if (q.n != have) return ctx->fail(LSA_E_ARG, std::string(who) + ": " + std::to_string(q.n) + " poses for " + std::to_string(have) + " logged frames");
+  if (q.first < 0 || q.last < q.first || q.last >= q.n)
+    return ctx->fail(LSA_E_ARG, std::string(who) + ": frames " + std::to_string(q.first) + ".." + std::to_string(q.last) + " of " + std::to_string(q.n) + " logged ones");
+  return LSA_OK;
+}
+
+// the tables of the range's frames alone (entry f is frame first + f): what a range costs is what its frames cost
+int prepare_range(lsa_ctx* ctx, KpLog* log, const KpLogRange& q, Replay* r)
+{
+  const int n = q.last - q.first + 1;
+  const size_t nf = (size_t)n;
+  const size_t motion_bytes = aligned(nf * sizeof(FrameMotion));
+  const size_t off_bytes = aligned((nf + 1) * sizeof(long long));
+  const size_t src_bytes = aligned(nf * sizeof(const float4*));
+  const size_t bytes = motion_bytes + 3 * (off_bytes + src_bytes);
+  std::vector<char> host(bytes, 0);
+  FrameMotion* motion = reinterpret_cast<FrameMotion*>(host.data());
+  for (int f = 0; f < n; ++f)
+  {
+    const size_t i = (size_t)(q.first + f);
+    FrameMotion& m = motion[f];
+    m.interp = (q.rule != 0 && i >= 1) ? 1 : 0;
+    if (m.interp)
+    {
+      // rule 1: SetTimes(t[i] - t[i - 1], 0.), the rebuild's (Slam.cxx:431); rule 2: pose[i - 1] one sweep BEFORE pose[i]
+      const double dt = q.times[i] - q.times[i - 1];
+      m.c = make_interp_const(q.poses + 16 * (i - 1), q.poses + 16 * i, q.rule == 1 ? dt : -dt, 0.);
+    }
+    row_major_to_rt(q.poses + 16 * i, m.R.R, m.R.t);
+  }
+  if (bytes > log->table_cap)
+  {
+    retire_dev(ctx, log->table);
+    log->table = nullptr;
+    log->table_cap = 0;
+    LSA_HIP(ctx, hipMalloc(&log->table, bytes + bytes / 2));
+    log->table_cap = bytes + bytes / 2;
+  }
+  if (!log->box_dev) LSA_HIP(ctx, hipMalloc((void**)&log->box_dev, 18 * sizeof(unsigned)));
+  char* dev = static_cast<char*>(log->table);
+  r->args.motion = reinterpret_cast<const FrameMotion*>(dev);
+  r->args.nframes = n;
+  for (int k = 0; k < 3; ++k)
+  {
+    const size_t at_off = motion_bytes + (size_t)k * (off_bytes + src_bytes), at_src = at_off + off_bytes;
+    long long* off = reinterpret_cast<long long*>(host.data() + at_off);
+    const float4** src = reinterpret_cast<const float4**>(host.data() + at_src);
+    const bool used = (q.type_mask >> k) & 1u;
+    long long sum = 0;
+    for (int f = 0; f < n; ++f)
+    {
+      const KpLogFrame& fr = log->frames[(size_t)(q.first + f)];
+      off[f] = sum;
+      src[f] = reinterpret_cast<const float4*>(fr.pts[k]);
+      if (used) sum += fr.n[k];
+    }
+    off[n] = sum;
+    r->total[k] = r->args.total[k] = sum;
+    r->last_n[k] = 0;
+    r->args.off[k] = reinterpret_cast<const long long*>(dev + at_off);
+    r->args.src[k] = reinterpret_cast<const float4* const*>(dev + at_src);
+    r->args.out[k] = nullptr;
+  }
+  LSA_HIP(ctx, hipMemcpyAsync(log->table, host.data(), bytes, hipMemcpyHostToDevice, ctx->stream));
+  LSA_HIP(ctx, hipStreamSynchronize(ctx->stream));  // `host` goes away
+  return LSA_OK;
+}
+
+// launches the range's replay (the outputs are set) and reads the boxes of all its points back; waits for the context's stream
+int run_range(lsa_ctx* ctx, KpLog* log, Replay* r, float box_min[3][3], float box_max[3][3])
+{
+  long long nmax = 0, all = 0;
+  for (int k = 0; k < 3; ++k) { nmax = std::max(nmax, r->total[k]); all += r->total[k]; }
+  for (int k = 0; k < 3; ++k)
+    for (int d = 0; d < 3; ++d) { box_min[k][d] = FLT_MAX; box_max[k][d] = -FLT_MAX; }
+  if (nmax <= 0) return LSA_OK;
+  if ((nmax + 255) / 256 > 0x7fffffffLL) return ctx->fail(LSA_E_CAPACITY, "lsa_kplog_replay_range: more points than one launch addresses");
+  unsigned box[18];
+  {
+    ProfScope ps(ctx, "log_replay_range", (double)all * 64 + (double)r->args.nframes * (sizeof(FrameMotion) + 3 * 16));
+    hipLaunchKernelGGL(k_log_box_init, dim3(1), dim3(64), 0, ctx->stream, log->box_dev);
+    hipLaunchKernelGGL(k_log_replay_range, dim3((unsigned)((nmax + 255) / 256), 3), dim3(256), 0, ctx->stream, r->args, log->box_dev);
+  }
+  LSA_HIP(ctx, hipGetLastError());  // (a launch that failed: the outputs may feed another context, which would read them unwritten)
+  LSA_HIP(ctx, hipMemcpyAsync(box, log->box_dev, sizeof(box), hipMemcpyDeviceToHost, ctx->stream));
+  LSA_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  for (int k = 0; k < 3; ++k)
+    for (int d = 0; d < 3; ++d)
+    {
+      // (a word as it was armed: no point of the type, or that coordinate NaN in all of them)
+      if (box[6 * k + d] != ~0u) box_min[k][d] = ou2f_host(box[6 * k + d]);
+      if (box[6 * k + 3 + d] != 0u) box_max[k][d] = ou2f_host(box[6 * k + 3 + d]);
+    }
+  return LSA_OK;
+}
 }  // namespace
+
+namespace lsa
+{
+// The range straight into a keypoint set of `dst`, a context on the same device (the log's own or another one): nothing of
+// the set's survives, the types outside the mask come out empty.  Waits for the stream of the log's context, so whatever
+// `dst` enqueues afterwards on its own streams finds the points written.
+int kplog_replay_range_to_set(lsa_ctx* ctx, const KpLogRange& q, lsa_ctx* dst, int set, long long counts[3], float box_min[3][3], float box_max[3][3])
+{
+  const char* who = "lsa_kplog_replay_range (to a keypoint set)";
+  int rc = check_range(ctx, who, q, box_min, box_max);
+  if (rc) return rc;
+  if (!dst || dst->device != ctx->device || set < 0 || set > 2) return ctx->fail(LSA_E_ARG, std::string(who) + ": bad argument");
+  KpLog* log = ctx->kplog;
+  LSA_HIP(ctx, hipSetDevice(ctx->device));
+  Replay r;
+  rc = prepare_range(ctx, log, q, &r);
+  if (rc) return rc;
+  long long nmax = 0;
+  for (int k = 0; k < 3; ++k) nmax = std::max(nmax, r.total[k]);
+  if (nmax > 0x7fffffffLL - (0x7fffffffLL >> 3)) return ctx->fail(LSA_E_CAPACITY, std::string(who) + ": more points than a keypoint set holds");
+  rc = ensure_capacity(dst, (int)nmax);  // (grows the set; waits for the destination's streams when it does)
+  if (rc) return dst == ctx ? rc : ctx->fail(rc, std::string(who) + ": " + dst->error);
+  LSA_HIP(ctx, hipStreamSynchronize(dst->stream));  // nothing in flight still reads the set
+  for (int k = 0; k < 3; ++k) r.args.out[k] = reinterpret_cast<float4*>(dst->kp[set][k]);
+  rc = run_range(ctx, log, &r, box_min, box_max);
+  if (rc) return rc;
+  for (int k = 0; k < 3; ++k)
+  {
+    dst->kp_n[set][k] = (int)r.total[k];
+    dst->kp_ver[set][k] = ++dst->kp_clock;
+    if (counts) counts[k] = r.total[k];
+  }
+  dst->kp_time_valid[set] = false;
+  return LSA_OK;
+}
+
+// ... and into the batch buffers of device grids (of one context on the same device, the log's own or another one), followed by
+// ONE RollingGrid::Add(range, fixed, time, roll) on each: lsa_kplog_replay_to_grids for a range.
+int kplog_replay_range_to_grids(lsa_ctx* ctx, const KpLogRange& q, lsa_device_grid* const grids[3], bool fixed, double time, bool roll, long long counts[3],
+                                float box_min[3][3], float box_max[3][3])
+{
+  const char* who = "lsa_kplog_replay_range (to device grids)";
+  int rc = check_range(ctx, who, q, box_min, box_max);
+  if (rc) return rc;
+  if (!grids) return ctx->fail(LSA_E_ARG, std::string(who) + ": bad argument");
+  for (int k = 0; k < 3; ++k)
+    if (((q.type_mask >> k) & 1u) && (!grids[k] || grid_context(grids[k])->device != ctx->device)) return ctx->fail(LSA_E_ARG, std::string(who) + ": a map on this device for every type asked for");
+  KpLog* log = ctx->kplog;
+  LSA_HIP(ctx, hipSetDevice(ctx->device));
+  Replay r;
+  rc = prepare_range(ctx, log, q, &r);
+  if (rc) return rc;
+  for (int k = 0; k < 3; ++k)
+  {
+    if (counts) counts[k] = r.total[k];
+    if (r.total[k] <= 0) continue;
+    if (r.total[k] > 0x7fffffffLL) return ctx->fail(LSA_E_CAPACITY, std::string(who) + ": more points than one insertion takes");
+    LSA_HIP(ctx, hipStreamSynchronize(grid_stream(grids[k])));  // nothing in flight uses the batch buffer
+    lsa_point_t* batch = nullptr;
+    rc = grid_batch(grids[k], (int)r.total[k], &batch);
+    if (rc) return grid_context(grids[k]) == ctx ? rc : ctx->fail(rc, std::string(who) + ": " + grid_context(grids[k])->error);
+    r.args.out[k] = reinterpret_cast<float4*>(batch);
+  }
+  rc = run_range(ctx, log, &r, box_min, box_max);  // (waits for the context's stream: the batches are written)
+  if (rc) return rc;
+  for (int k = 0; k < 3; ++k)
+    if (r.total[k] > 0)
+    {
+      rc = grid_add_batch(grids[k], (int)r.total[k], fixed, time, roll);
+      if (rc) return grid_context(grids[k]) == ctx ? rc : ctx->fail(rc, std::string(who) + ": " + grid_context(grids[k])->error);
+    }
+  return LSA_OK;
+}
+}  // namespace lsa
 
 extern "C" {
 
@@ -532,6 +781,42 @@ long long lsa_kplog_replayed(const lsa_ctx* ctx, int type, const lsa_point_t** p
   if (!ctx || type < 0 || type > 2 || !pts || !ctx->kplog) return LSA_E_ARG;
   *pts = ctx->kplog->stage[type];
   return ctx->kplog->stage_n[type];
+}
+
+int lsa_kplog_replay_range(lsa_ctx* ctx, unsigned type_mask, const double* poses, const double* times, int n, int first, int last, int rule, lsa_point_t* const out[3],
+                           float box_min[3][3], float box_max[3][3])
+{
+  const KpLogRange q{type_mask, poses, times, n, first, last, rule};
+  int rc = check_range(ctx, "lsa_kplog_replay_range", q, box_min, box_max);
+  if (rc) return rc;
+  KpLog* log = ctx->kplog;
+  LSA_HIP(ctx, hipSetDevice(ctx->device));
+  Replay r;
+  rc = prepare_range(ctx, log, q, &r);
+  if (rc) return rc;
+  // into the pinned staging of the whole-log replay (lsa_kplog_replayed reads either)
+  for (int k = 0; k < 3; ++k)
+  {
+    log->stage_n[k] = 0;
+    if (r.total[k] > log->stage_cap[k])
+    {
+      retire_host(ctx, log->stage[k]);
+      log->stage[k] = nullptr;
+      log->stage_cap[k] = 0;
+      const long long cap = r.total[k] + r.total[k] / 4;
+      LSA_HIP(ctx, hipHostMalloc((void**)&log->stage[k], (size_t)cap * sizeof(lsa_point_t), hipHostMallocDefault));
+      log->stage_cap[k] = cap;
+    }
+    r.args.out[k] = reinterpret_cast<float4*>(log->stage[k]);
+  }
+  rc = run_range(ctx, log, &r, box_min, box_max);
+  if (rc) return rc;
+  for (int k = 0; k < 3; ++k)
+  {
+    log->stage_n[k] = r.total[k];
+    if (out && out[k] && r.total[k] > 0) std::memcpy(out[k], log->stage[k], (size_t)r.total[k] * sizeof(lsa_point_t));
+  }
+  return LSA_OK;
 }
 
 int lsa_kplog_replay_to_grids(lsa_ctx* ctx, unsigned type_mask, const double* poses, const double* times, int n, int undistort, lsa_device_grid* const grids[3],

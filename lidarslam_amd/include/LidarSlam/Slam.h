@@ -14,7 +14,8 @@
 //
 // Beyond the per-frame path the mirror also carries PCD map IO, the wheel odometer / IMU gravity constraints, the keypoint
 // log (SetLoggingTimeout, SetLoggingStorage, GetLoggedKeypoints) and SetTrajectoryAndRebuildMaps, which brings a corrected
-// trajectory back.  The pose-graph OPTIMIZER itself (g2o) is not part of this build: RunPoseGraphOptimization is present
+// trajectory back, and the loop-closure constraint an optimizer needs as input: FindLoopClosureCandidate and
+// RegisterLoggedFrames.  The pose-graph OPTIMIZER itself (g2o) is not part of this build: RunPoseGraphOptimization is present
 // with the reference's signature, warns once and changes nothing.
 #pragma once
 #include <algorithm>
@@ -281,8 +282,9 @@ public:
   // ---- the pose-graph optimizer (g2o) is not part of this build.  Present with the reference's signature so that
   // LidarSlamNode.cxx / vtkSlam.cxx compile unchanged; it warns once and does nothing, the way the reference itself answers
   // RunPoseGraphOptimization without g2o (slam_lib/src/Slam.cxx:355-366: "SLAM PoseGraphOptimization requires G2O, but it
-  // was not found.").  What the reference does AFTER its optimizer is SetTrajectoryAndRebuildMaps below: run the optimizer
-  // of your choice on GetTrajectory() / GetCovariances() and bring its result there.
+  // was not found.").  What the reference does AFTER its optimizer is SetTrajectoryAndRebuildMaps below, and the
+  // loop-closure constraints an optimizer wants as input come from RegisterLoggedFrames: run the optimizer of your choice
+  // on GetTrajectory() / GetCovariances() and those edges, and bring its result there.
 #ifdef LSA_HAVE_EIGEN
   void RunPoseGraphOptimization(const std::vector<Transform>&, const std::vector<std::array<double, 9>>&, Eigen::Isometry3d&, const std::string& = "")
 #else
@@ -307,6 +309,43 @@ public:
     }
     const int rc = lsa_slam_set_trajectory_and_rebuild_maps(this->Handle, rows.data(), static_cast<int>(poses.size()));
     this->LastError = rc < 0 ? std::string("SetTrajectoryAndRebuildMaps: ") + lsa_slam_last_error(this->Handle) : std::string();
+  }
+  // ---- loop closure: the constraint an optimizer takes.  Logged frame `query` is registered against the logged keypoints
+  // around logged frame `revisited` (indices into GetTrajectory()): a sub-map from the frames revisited -+
+  // params.revisited_half_window under the logged poses, the ICP-LM loop of the localization from `guess` (the world pose of
+  // query's BASE; nullptr = its logged pose) on the device, nothing but the result coming back.  The frame path does not
+  // notice the call.  result.relative = inv(pose[revisited]) * result.world is the pose-graph edge revisited -> query,
+  // result.covariance its uncertainty; result.status is 0 (registered) or 1 (too few matches: world = the guess).  When it
+  // cannot -- no keypoint log, windows that overlap, an index outside the log -- nothing is changed, GetLastError() says
+  // why and result.status is the negative LSA_E_* code.
+  using LoopClosureParameters = lsa_loop_closure_params_t;
+  using LoopClosureRegistration = lsa_loop_closure_result_t;
+  static LoopClosureParameters DefaultLoopClosureParameters()
+  {
+    LoopClosureParameters p;
+    lsa_loop_closure_params_init(&p);
+    return p;
+  }
+  LoopClosureRegistration RegisterLoggedFrames(std::size_t query, std::size_t revisited, const LoopClosureParameters& params = DefaultLoopClosureParameters(),
+                                               const Transform* guess = nullptr)
+  {
+    LoopClosureRegistration result;
+    std::memset(&result, 0, sizeof(result));
+    const int rc = lsa_slam_register_logged_frames(this->Handle, static_cast<int>(query), static_cast<int>(revisited), &params, guess ? guess->matrix.data() : nullptr, &result);
+    this->LastError = rc < 0 ? std::string("RegisterLoggedFrames: ") + lsa_slam_last_error(this->Handle) : std::string();
+    if (rc < 0) result.status = rc;
+    return result;
+  }
+  // The logged frame to try a loop closure of `query` against: among the frames at least minTravelled metres back along
+  // GetTrajectory() and within maxDistance metres of query's position, the nearest; -1 when there is none.  Host only;
+  // place recognition proper (descriptors) is the caller's.
+  int FindLoopClosureCandidate(std::size_t query, double minTravelled, double maxDistance) const
+  {
+    const int n = lsa_slam_get_trajectory(this->Handle, nullptr, nullptr, 0);
+    std::vector<double> rows(static_cast<std::size_t>(n > 0 ? n : 0) * 17);
+    if (n > 0) lsa_slam_get_trajectory(this->Handle, rows.data(), nullptr, n);
+    const int found = lsa_loop_closure_candidate(rows.data(), n, static_cast<int>(query), minTravelled, maxDistance);
+    return found < 0 ? -1 : found;
   }
   // the raw keypoints (BASE, not undistorted) logged with pose `frame` of GetTrajectory()
   PointCloud::Ptr GetLoggedKeypoints(Keypoint k, std::size_t frame)

@@ -865,7 +865,8 @@ int lsa_slam_get_logged_keypoints(lsa_slam* s, int frame, int type, lsa_point_t*
  * - lsa_loop_closure_candidate(poses17, n, query, min_travelled, max_distance): host only, no device.  Rows as
  *   lsa_slam_get_trajectory gives them.  Among the frames i < query at least min_travelled metres back along the trajectory
  *   (sum of the step lengths between i and query) and at most max_distance metres from query's position, the nearest one,
- *   the lower index on a tie; -1 when there is none, LSA_E_ARG for a bad argument.  Place recognition proper is the caller's. */
+ *   the lower index on a tie; -1 when there is none, LSA_E_ARG for a bad argument.  It decides by position alone; by
+ *   appearance, drift or no drift, and with a yaw to start the registration from: lsa_slam_recognize_place below. */
 typedef struct lsa_loop_closure_params_t
 {
   int32_t revisited_half_window; /* frames on either side of `revisited` that make the target (default 5) */
@@ -893,6 +894,64 @@ void lsa_loop_closure_params_init(lsa_loop_closure_params_t* params);
 int lsa_slam_register_logged_frames(lsa_slam* s, int query, int revisited, const lsa_loop_closure_params_t* params, const double guess[16],
                                     lsa_loop_closure_result_t* out);
 int lsa_loop_closure_candidate(const double* poses17, int n, int query, double min_travelled, double max_distance);
+
+/* Place recognition on the keypoint log: which logged frame looks like this one, wherever the drifted trajectory puts it.
+ * Every logged frame gets a descriptor made of its raw keypoints in its own coordinates (Scan Context, Kim & Kim, IROS
+ * 2018): `rings` x `sectors` polar cells around the sensor, each the largest z + height_offset of the keypoints in it
+ * (0 when empty or not positive), followed by the `sectors` column norms.  Two descriptors are compared column by column
+ * under every column shift; the best shift is the yaw between the frames.  The definition, to the order of every float
+ * operation, is lidarslam_amd/csrc/lsa_scan_descriptor.h, compiled for the host and the device alike.
+ * - lsa_place_params_t: rings 1..32 (default 20), sectors 1..120 (60), type_mask a non-empty subset of the three types (EDGE
+ *   and PLANE), min_range (0) < max_range (80), height_offset finite (2.0), min_common_sectors (15; <= 0: max(1, sectors / 4)):
+ *   under a shift with fewer columns occupied in both descriptors the distance is 1.  Anything else: LSA_E_ARG.
+ * - host statement, no device: lsa_scan_descriptor_host (n points already filtered by type -> rings * sectors + sectors
+ *   floats), lsa_place_distance_host (query a, candidate b -> distance in [0, 2] and shift in [0, sectors)),
+ *   lsa_place_select_host: from a table of (distance, shift) for the frames 0..query-1 and the trajectory (rows of 17 doubles)
+ *   the admissible frames -- at least min_travelled back along the trajectory (lsa_loop_closure_candidate's rule), within
+ *   max_distance of query's position if max_distance > 0, distance <= max_descriptor_distance if that is > 0 -- ranked by
+ *   (distance, index); a frame within exclusion_half_window of one already picked is passed over.  Returns how many of at
+ *   most `capacity` were written.  yaw = shift * 2 pi / sectors in (-pi, pi]: a start guess for
+ *   lsa_slam_register_logged_frames is P[frame] * Rz(yaw).
+ * - lsa_slam_recognize_place(query, search, out, capacity): describes the logged frames that have no descriptor yet
+ *   (k_log_describe, a workgroup per frame), compares frame `query` with every frame before it (k_place_search, a workgroup per
+ *   candidate, exhaustive and exact), copies the table out and selects on the host.  Returns the number of candidates.
+ *   Runs on the log's context; waits for the map workers and the device (an offline call); changes nothing the frame path
+ *   reads.  search NULL = defaults.  LSA_E_STATE when "LoggingTimeout" is 0, keypoint logging stopped, or the keypoint
+ *   log does not cover the logged poses; LSA_E_ARG for a query outside the log or bad parameters. */
+typedef struct lsa_place_params_t
+{
+  int32_t rings;
+  int32_t sectors;
+  uint32_t type_mask;          /* bit k: keypoints of type k take part */
+  int32_t min_common_sectors;
+  double min_range;            /* [m] horizontal range r with min_range <= r < max_range */
+  double max_range;
+  double height_offset;        /* [m] added to z: the sensor's height above the lowest thing worth describing */
+} lsa_place_params_t;
+typedef struct lsa_place_search_t
+{
+  lsa_place_params_t descriptor;
+  double min_travelled;           /* [m] (default 20) */
+  double max_distance;            /* [m] <= 0: no position gate (default 0) */
+  double max_descriptor_distance; /* <= 0: no descriptor gate (default 0) */
+  int32_t exclusion_half_window;  /* frames (default 5) */
+  int32_t reserved;
+} lsa_place_search_t;
+typedef struct lsa_place_candidate_t
+{
+  int32_t frame;
+  int32_t shift;
+  float distance;
+  float reserved;
+  double yaw;                     /* [rad] */
+} lsa_place_candidate_t;
+void lsa_place_params_init(lsa_place_params_t* params);
+void lsa_place_search_init(lsa_place_search_t* search);
+int lsa_scan_descriptor_host(const lsa_place_params_t* params, const lsa_point_t* pts, int n, float* out);
+int lsa_place_distance_host(const lsa_place_params_t* params, const float* a, const float* b, float* distance, int* shift);
+int lsa_place_select_host(const float* distance, const int32_t* shift, const double* poses17, int n, int query, int sectors, double min_travelled,
+                          double max_distance, double max_descriptor_distance, int exclusion_half_window, lsa_place_candidate_t* out, int capacity);
+int lsa_slam_recognize_place(lsa_slam* s, int query, const lsa_place_search_t* search, lsa_place_candidate_t* out, int capacity);
 
 
 /* ------------------------------------------------------------------------- */
@@ -1036,7 +1095,25 @@ int lsa_pcd_io_times(const lsa_ctx* ctx, double out[8]);
  *   Frame 0 is rigid under every rule; the per-point arithmetic is lsa_kplog_replay's.  The result goes where lsa_kplog_replay's
  *   goes (lsa_kplog_replayed; out[k] where given).  box_min / box_max [type][xyz]: the box of ALL replayed points of a type;
  *   a NaN coordinate takes no part; FLT_MAX / -FLT_MAX for a type without points.
- *   LSA_E_ARG (nothing written) for a bad range or rule or n != lsa_kplog_size, LSA_E_STATE for a stopped log. */
+ *   LSA_E_ARG (nothing written) for a bad range or rule or n != lsa_kplog_size, LSA_E_STATE for a stopped log.
+ * The descriptor store (lsa_place.hip; lsa_place_params_t and the descriptor: "Place recognition" above): a slot of
+ * rings * sectors + sectors floats per logged frame, owned by the log, filled lazily.  It follows _append, _pop_front and
+ * _clear; a change of any parameter invalidates all of it; poses are no part of it.
+ * - lsa_kplog_describe(params, first, last): describes the frames of the range that have no valid descriptor (ONE launch of
+ *   k_log_describe).  Returns how many it described.
+ * - lsa_kplog_descriptors(first, last, out): copies the range's descriptors out, (last - first + 1) x (rings * sectors +
+ *   sectors) floats; LSA_E_STATE when one of them has not been described.  lsa_kplog_descriptor_length: the floats of one
+ *   under the parameters the store holds now (0: none yet).
+ * - lsa_kplog_place_search(params, query, first, last, distance_out, shift_out): describes what is missing among `query`
+ *   and first..last, ONE launch of k_place_search, ONE copy of the table (last - first + 1 entries) to pinned memory.
+ * - lsa_kplog_described: how many frames the last of these calls described (a test's view of the laziness).
+ * The three: LSA_E_STATE for a stopped log, LSA_E_ARG for a bad range, a query outside the log or parameters out of
+ * limits, with nothing written.  lsa_debug_set "place_max_blocks" n: at most n workgroups a search launch (<= 0: the default). */
+int lsa_kplog_describe(lsa_ctx* ctx, const lsa_place_params_t* params, int first, int last);
+int lsa_kplog_descriptors(lsa_ctx* ctx, int first, int last, float* out);
+int lsa_kplog_place_search(lsa_ctx* ctx, const lsa_place_params_t* params, int query, int first, int last, float* distance_out, int32_t* shift_out);
+int lsa_kplog_described(const lsa_ctx* ctx);
+int lsa_kplog_descriptor_length(const lsa_ctx* ctx);
 int lsa_kplog_append(lsa_ctx* ctx);
 int lsa_kplog_append_points(lsa_ctx* ctx, const lsa_point_t* const pts[3], const int n[3]);
 int lsa_kplog_pop_front(lsa_ctx* ctx);

@@ -85,6 +85,8 @@ ABI_SYMBOLS = [
     "lsa_kplog_bytes", "lsa_kplog_stopped", "lsa_kplog_replay", "lsa_kplog_replayed", "lsa_kplog_replay_to_grids",
     "lsa_slam_set_trajectory_and_rebuild_maps", "lsa_slam_logged_frames", "lsa_slam_get_logged_keypoints",
     "lsa_kplog_replay_range", "lsa_loop_closure_params_init", "lsa_slam_register_logged_frames", "lsa_loop_closure_candidate",
+    "lsa_place_params_init", "lsa_place_search_init", "lsa_scan_descriptor_host", "lsa_place_distance_host", "lsa_place_select_host",
+    "lsa_slam_recognize_place", "lsa_kplog_describe", "lsa_kplog_descriptors", "lsa_kplog_place_search", "lsa_kplog_described", "lsa_kplog_descriptor_length",
 ]
 
 PCD_ASCII, PCD_BINARY, PCD_BINARY_COMPRESSED = 0, 1, 2  # PCDFormat (PointCloudStorage.h:60-65)
@@ -176,6 +178,99 @@ def loop_closure_candidate(poses, times, query, min_travelled, max_distance):
     if rc < -1:
         raise _error("lsa_loop_closure_candidate", rc, "bad argument")
     return rc
+
+
+class PlaceParams(C.Structure):
+    """lsa_place_params_t (include/lidarslam_amd.h): the shape of a frame's descriptor.  min_common_sectors None: the default
+    of the shape, max(1, sectors // 4)."""
+
+    _fields_ = [
+        ("rings", C.c_int32), ("sectors", C.c_int32), ("type_mask", C.c_uint32), ("min_common_sectors", C.c_int32),
+        ("min_range", C.c_double), ("max_range", C.c_double), ("height_offset", C.c_double),
+    ]
+
+    def __init__(self, rings=20, sectors=60, type_mask=(1 << EDGE) | (1 << PLANE), min_range=0.0, max_range=80.0, height_offset=2.0, min_common_sectors=None):
+        if min_common_sectors is None:
+            min_common_sectors = max(1, int(sectors) // 4)
+        super().__init__(rings, sectors, type_mask, min_common_sectors, min_range, max_range, height_offset)
+
+    @property
+    def length(self):
+        """floats of a descriptor: rings * sectors cells, row-major [ring][sector], then the sectors column norms"""
+        return self.rings * self.sectors + self.sectors
+
+
+class PlaceSearch(C.Structure):
+    """lsa_place_search_t: the descriptor's parameters and the selection's."""
+
+    _fields_ = [
+        ("descriptor", PlaceParams), ("min_travelled", C.c_double), ("max_distance", C.c_double), ("max_descriptor_distance", C.c_double),
+        ("exclusion_half_window", C.c_int32), ("reserved", C.c_int32),
+    ]
+
+    def __init__(self, min_travelled=20.0, max_distance=0.0, max_descriptor_distance=0.0, exclusion_half_window=5, **descriptor):
+        super().__init__(PlaceParams(**descriptor), min_travelled, max_distance, max_descriptor_distance, exclusion_half_window, 0)
+
+
+class PlaceCandidateStruct(C.Structure):
+    """lsa_place_candidate_t."""
+
+    _fields_ = [("frame", C.c_int32), ("shift", C.c_int32), ("distance", C.c_float), ("reserved", C.c_float), ("yaw", C.c_double)]
+
+
+def _candidates(out, n):
+    """[(frame, distance, shift, yaw)]: distance a numpy float32, yaw a float [rad]"""
+    return [(int(c.frame), np.float32(c.distance), int(c.shift), float(c.yaw)) for c in out[:n]]
+
+
+def scan_descriptor(points, **params):
+    """The host statement of a frame's descriptor (lsa_scan_descriptor_host): points a POINT_DTYPE array, or (n, 3) xyz,
+    already filtered by type -> float32 (rings * sectors + sectors,).  params: PlaceParams' fields."""
+    p = PlaceParams(**params)
+    pts = np.asarray(points)
+    if pts.dtype != POINT_DTYPE:
+        xyz = np.asarray(points, np.float32).reshape(-1, 3)
+        pts = np.zeros(xyz.shape[0], POINT_DTYPE)
+        pts["x"], pts["y"], pts["z"] = xyz[:, 0], xyz[:, 1], xyz[:, 2]
+    pts = np.ascontiguousarray(pts)
+    out = np.zeros(max(p.rings, 0) * max(p.sectors, 0) + max(p.sectors, 0), np.float32)
+    rc = lib().lsa_scan_descriptor_host(C.byref(p), ptr(pts) if pts.size else None, pts.size, ptr(out))
+    if rc < 0:
+        raise _error("lsa_scan_descriptor_host", rc, "parameters out of limits")
+    return out
+
+
+def place_distance(a, b, **params):
+    """The host statement of the distance of query descriptor a to candidate descriptor b (lsa_place_distance_host) ->
+    (distance float32, shift): the smallest distance over the column shifts, the lowest shift on a tie."""
+    p = PlaceParams(**params)
+    a = np.ascontiguousarray(np.asarray(a, np.float32).reshape(-1))
+    b = np.ascontiguousarray(np.asarray(b, np.float32).reshape(-1))
+    if p.rings < 1 or p.sectors < 1 or a.size != p.length or b.size != p.length:
+        raise _error("lsa_place_distance_host", E_ARG, "descriptors of another shape than the parameters'")
+    d, s = C.c_float(), C.c_int()
+    rc = lib().lsa_place_distance_host(C.byref(p), ptr(a), ptr(b), C.byref(d), C.byref(s))
+    if rc < 0:
+        raise _error("lsa_place_distance_host", rc, "parameters out of limits")
+    return np.float32(d.value), int(s.value)
+
+
+def place_select(distance, shift, poses, times, query, sectors=60, min_travelled=20.0, max_distance=0.0, max_descriptor_distance=0.0,
+                 exclusion_half_window=5, capacity=5):
+    """The host statement of the selection (lsa_place_select_host): distance / shift the table of the frames 0..query-1,
+    poses (n, 4, 4) and times (n,) as Slam.trajectory() gives them -> [(frame, distance, shift, yaw)], best first."""
+    P = np.asarray(poses, np.float64).reshape(-1, 16)
+    rows = np.ascontiguousarray(np.concatenate([P, np.asarray(times, np.float64).reshape(-1, 1)], axis=1))
+    d = np.ascontiguousarray(np.asarray(distance, np.float32).reshape(-1))
+    s = np.ascontiguousarray(np.asarray(shift, np.int32).reshape(-1))
+    if d.size < max(int(query), 0) or s.size < max(int(query), 0):
+        raise _error("lsa_place_select_host", E_ARG, "a table shorter than the frames before query")
+    out = (PlaceCandidateStruct * max(int(capacity), 1))()
+    rc = lib().lsa_place_select_host(ptr(d) if d.size else None, ptr(s) if s.size else None, ptr(rows), rows.shape[0], int(query), int(sectors), float(min_travelled),
+                                     float(max_distance), float(max_descriptor_distance), int(exclusion_half_window), out, int(capacity))
+    if rc < 0:
+        raise _error("lsa_place_select_host", rc, "bad argument")
+    return _candidates(out, rc)
 
 
 class SensorTerms(C.Structure):
@@ -477,6 +572,19 @@ def lib():
     L.lsa_loop_closure_params_init.argtypes = [vp]
     L.lsa_slam_register_logged_frames.argtypes = [vp, i32, i32, vp, vp, vp]
     L.lsa_loop_closure_candidate.argtypes = [vp, i32, i32, C.c_double, C.c_double]
+    L.lsa_place_params_init.restype = None
+    L.lsa_place_params_init.argtypes = [vp]
+    L.lsa_place_search_init.restype = None
+    L.lsa_place_search_init.argtypes = [vp]
+    L.lsa_scan_descriptor_host.argtypes = [vp, vp, i32, vp]
+    L.lsa_place_distance_host.argtypes = [vp, vp, vp, vp, vp]
+    L.lsa_place_select_host.argtypes = [vp, vp, vp, i32, i32, i32, C.c_double, C.c_double, C.c_double, i32, vp, i32]
+    L.lsa_slam_recognize_place.argtypes = [vp, i32, vp, vp, i32]
+    L.lsa_kplog_describe.argtypes = [vp, vp, i32, i32]
+    L.lsa_kplog_descriptors.argtypes = [vp, i32, i32, vp]
+    L.lsa_kplog_place_search.argtypes = [vp, vp, i32, i32, i32, vp, vp]
+    L.lsa_kplog_described.argtypes = [vp]
+    L.lsa_kplog_descriptor_length.argtypes = [vp]
     L.lsa_slam_set_trajectory_and_rebuild_maps.argtypes = [vp, vp, i32]
     L.lsa_slam_logged_frames.argtypes = [vp]
     L.lsa_slam_get_logged_keypoints.argtypes = [vp, i32, i32, vp, i32]
@@ -1081,6 +1189,34 @@ class Context:
         sizes = [int(self.L.lsa_kplog_replayed(self.h, k, C.byref(C.c_void_p()))) for k in range(3)]
         return [o[:s].copy() for o, s in zip(outs, sizes)], mn, mx
 
+    # ---- the log's descriptor store (lsa_kplog_describe / _descriptors / _place_search): place recognition
+    def kplog_describe(self, first, last, **params):
+        """describes the frames first..last that have no valid descriptor under these PlaceParams -> how many it described"""
+        p = PlaceParams(**params)
+        return self._check(self.L.lsa_kplog_describe(self.h, C.byref(p), int(first), int(last)), "lsa_kplog_describe")
+
+    def kplog_descriptors(self, first, last, **params):
+        """the described frames' descriptors -> float32 (last - first + 1, PlaceParams(**params).length)"""
+        length = PlaceParams(**params).length
+        if self.L.lsa_kplog_descriptor_length(self.h) not in (0, length):
+            raise _error("lsa_kplog_descriptors", E_STATE, "the store holds descriptors of another shape")
+        out = np.zeros((max(int(last) - int(first) + 1, 1), max(length, 1)), np.float32)
+        self._check(self.L.lsa_kplog_descriptors(self.h, int(first), int(last), ptr(out)), "lsa_kplog_descriptors")
+        return out
+
+    def kplog_place_search(self, query, first, last, out=None, **params):
+        """frame `query` against the frames first..last -> (distance float32 (count,), shift int32 (count,)), written into
+        out = (distance, shift) where given"""
+        p = PlaceParams(**params)
+        count = max(int(last) - int(first) + 1, 1)
+        d, s = out if out is not None else (np.zeros(count, np.float32), np.zeros(count, np.int32))
+        self._check(self.L.lsa_kplog_place_search(self.h, C.byref(p), int(query), int(first), int(last), ptr(d), ptr(s)), "lsa_kplog_place_search")
+        return d, s
+
+    def kplog_described(self):
+        """frames described by the last kplog_describe / kplog_place_search"""
+        return self.L.lsa_kplog_described(self.h)
+
     def kplog_replay_to_grids(self, poses, times, grids, undistort=True):
         """the same straight into device maps of this context: grids = [edges, planes, blobs], a DeviceGrid or None each;
         per map ONE Add(aggregate, fixed=False, time=-1, roll=False), nothing comes to the host.  Returns the last
@@ -1360,6 +1496,16 @@ class Slam:
         self._check(self.L.lsa_slam_register_logged_frames(self.h, int(query), int(revisited), C.byref(p), None if g is None else ptr(g), C.byref(r)),
                     "lsa_slam_register_logged_frames")
         return LoopClosureResult(r)
+
+    def recognize_place(self, query, capacity=5, **params):
+        """Place recognition: the logged frames before `query` that look like it -> [(frame, distance, shift, yaw)], best
+        first.  params: PlaceSearch's fields (min_travelled, max_distance, max_descriptor_distance, exclusion_half_window)
+        and PlaceParams' (rings, sectors, ...).  A start guess for register_logged_frames(query, frame) is
+        P[frame] @ Rz(yaw).  The frame path does not notice the call.  Raises LsaError (.code E_STATE or E_ARG) when it cannot."""
+        p = PlaceSearch(**params)
+        out = (PlaceCandidateStruct * max(int(capacity), 1))()
+        n = self._check(self.L.lsa_slam_recognize_place(self.h, int(query), C.byref(p), out, int(capacity)), "lsa_slam_recognize_place")
+        return _candidates(out, n)
 
 
 class RollingGrid:

@@ -337,6 +337,12 @@ int lsa_slam_register_logged_frames(lsa_slam* s, int query, int revisited, const
   return s->core.RegisterLoggedFrames(query, revisited, params, guess, out);
 }
 
+int lsa_slam_recognize_place(lsa_slam* s, int query, const lsa_place_search_t* search, lsa_place_candidate_t* out, int capacity)
+{
+  if (!s) return LSA_E_ARG;
+  return s->core.RecognizePlace(query, search, out, capacity);
+}
+
 int lsa_loop_closure_candidate(const double* poses17, int n, int query, double min_travelled, double max_distance)
 {
   return lsa::host::LoopClosureCandidate(poses17, n, query, min_travelled, max_distance);

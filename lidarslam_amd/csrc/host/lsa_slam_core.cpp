@@ -1835,6 +1835,48 @@ int SlamCore::SetTrajectoryAndRebuildMaps(const double* poses17, int n)
   return LSA_OK;
 }
 
+// ---- place recognition: which logged frame looks like this one (descriptors of the keypoint log, lsa_place.hip) -------------
+int SlamCore::RecognizePlace(int query, const lsa_place_search_t* search, lsa_place_candidate_t* out, int capacity)
+{
+  if (!Ctx) return LSA_E_NO_DEVICE;
+  const std::string who = "RecognizePlace: ";
+  if (capacity < 0 || (capacity > 0 && !out)) { LastError = who + "no place for the candidates"; return LSA_E_ARG; }
+  if (LoggingTimeout == 0.) { LastError = who + "keypoint logging is off (LoggingTimeout = 0): there are no logged keypoints to describe"; return LSA_E_STATE; }
+  if (KpLogStopped) { LastError = who + "keypoint logging stopped when a chunk could not be allocated; Reset(true) starts it again"; return LSA_E_STATE; }
+  const int n = static_cast<int>(LogTrajectory.size());
+  if (lsa_kplog_size(Ctx) != n) { LastError = who + "the keypoint log does not cover the logged poses (logging was switched on after the first of them)"; return LSA_E_STATE; }
+  lsa_place_search_t p;
+  lsa_place_search_init(&p);
+  if (search) p = *search;
+  if (query < 0 || query >= n) { LastError = who + "query frame " + std::to_string(query) + " is not one of the " + std::to_string(n) + " logged ones"; return LSA_E_ARG; }
+  if (!place::params_ok(p.descriptor) || !(p.min_travelled >= 0.) || p.exclusion_half_window < 0 || p.max_distance != p.max_distance ||
+      p.max_descriptor_distance != p.max_descriptor_distance)
+  {
+    LastError = who + "parameters out of limits";
+    return LSA_E_ARG;
+  }
+  if (query == 0) return 0;  // no frame before it
+  // the device works from here on: the map workers and the look-ahead have enqueued what they had (nothing of theirs is changed)
+  WaitMaps();
+  std::vector<float> distance(static_cast<size_t>(query));
+  std::vector<int32_t> shift(static_cast<size_t>(query));
+  if (const int rc = lsa_kplog_place_search(Ctx, &p.descriptor, query, 0, query - 1, distance.data(), shift.data()); rc < 0)
+  {
+    LastError = who + lsa_last_error(Ctx);
+    return rc;
+  }
+  std::vector<double> rows(static_cast<size_t>(n) * 17);
+  for (int i = 0; i < n; ++i)
+  {
+    std::memcpy(&rows[17 * static_cast<size_t>(i)], LogTrajectory[i].pose.m, 16 * sizeof(double));
+    rows[17 * static_cast<size_t>(i) + 16] = LogTrajectory[i].time;
+  }
+  const int found = PlaceSelect(distance.data(), shift.data(), rows.data(), n, query, p.descriptor.sectors, p.min_travelled, p.max_distance, p.max_descriptor_distance,
+                                p.exclusion_half_window, out, capacity);
+  if (found < 0) LastError = who + "bad argument";
+  return found;
+}
+
 // ---- loop closure: a logged frame registered against the log around a revisited pose ---------------------------------------
 int SlamCore::EnsureLoopClosureScratch()
 {

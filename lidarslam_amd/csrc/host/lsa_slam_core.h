@@ -23,6 +23,7 @@
 #include "lsa_hostmath.h"
 #include "lsa_lm.h"
 #include "lsa_loop_closure.h"
+#include "lsa_place.h"
 #include "lsa_rolling_grid.h"
 #include "lsa_sensor_constraints.h"
 
@@ -126,6 +127,10 @@ public:
   // in lidarslam_amd.h says what it computes).  Everything runs on a scratch context of this object's: the frame path's
   // keypoint sets, targets, maps and look-ahead do not notice.  A refusal changes nothing and leaves its reason in Error().
   int RegisterLoggedFrames(int query, int revisited, const lsa_loop_closure_params_t* params, const double* guess16, lsa_loop_closure_result_t* out);
+  // Place recognition: the logged frames before `query` that look like it, by the descriptors of the keypoint log
+  // (lsa_slam_recognize_place in lidarslam_amd.h).  Runs on the log's context after the map workers; reads the log, writes
+  // the log's descriptor store and nothing else.  Returns the number of candidates written.
+  int RecognizePlace(int query, const lsa_place_search_t* search, lsa_place_candidate_t* out, int capacity);
   int LoggedFrames() const;
   int GetLoggedKeypoints(int frame, int type, std::vector<lsa_point_t>& out);
   void HintNextStoredFrame(int slot) { NextStoredSlot = slot; }

@@ -11,6 +11,7 @@
 //   match[k]     SoA residual records rec[16][K] (A 9, P 3, X 3, weight), status[K]
 //   reduce       per-block partials of the normal equations, 29 doubles each
 //   keypoint log AoS lsa_point_t in chunks of 32 MiB, a frame's three types one after the other (lsa_kplog.hip; only with logging on)
+//   descriptors  a ring of slots of rings * sectors + sectors floats, one per logged frame (lsa_place.hip; only once asked for)
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>
@@ -135,6 +136,7 @@ struct PendingEvent
 };
 
 struct KpLog;  // lsa_kplog.hip
+struct PlaceStore;  // lsa_place.hip
 
 }  // namespace lsa
 
@@ -328,6 +330,9 @@ struct lsa_ctx
   lsa::KpLog* kplog = nullptr;
   size_t kplog_chunk_bytes = (size_t)32 << 20;  // lsa_debug_set "kplog_chunk_kib"
   int debug_kplog_fail_alloc = 0;               // lsa_debug_set "kplog_fail_alloc": the next chunk allocations fail (the callers' error path)
+  // the log's descriptor store (lsa_place.hip): made by the first describe, follows the log's appends, pops and clears
+  lsa::PlaceStore* place = nullptr;
+  int place_max_blocks = 0;                     // lsa_debug_set "place_max_blocks": 0 = the default
 
   // profiling
   bool profiling = false;

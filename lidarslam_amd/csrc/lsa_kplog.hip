@@ -56,6 +56,7 @@ struct KpLog
 void kplog_destroy(lsa_ctx* ctx)
 {
   KpLog* log = ctx->kplog;
+  place_destroy(ctx);
   if (!log) return;
   for (KpLogChunk& c : log->chunks)
     if (c.base) (void)hipFree(c.base);
@@ -65,6 +66,14 @@ void kplog_destroy(lsa_ctx* ctx)
     if (log->stage[k]) (void)hipHostFree(log->stage[k]);
   delete log;
   ctx->kplog = nullptr;
+}
+
+bool kplog_frame(const lsa_ctx* ctx, int frame, const lsa_point_t* pts[3], int n[3])
+{
+  const KpLog* log = ctx ? ctx->kplog : nullptr;
+  if (!log || frame < 0 || frame >= (int)log->frames.size()) return false;
+  for (int k = 0; k < 3; ++k) { pts[k] = log->frames[frame].pts[k]; n[k] = log->frames[frame].n[k]; }
+  return true;
 }
 }  // namespace lsa
 
@@ -692,6 +701,7 @@ int lsa_kplog_pop_front(lsa_ctx* ctx)
   const KpLogFrame fr = log->frames.front();
   log->frames.pop_front();
   release_frame(ctx, log, fr);
+  place_pop_front(ctx);
   return LSA_OK;
 }
 
@@ -709,6 +719,7 @@ int lsa_kplog_clear(lsa_ctx* ctx)
   log->cur = -1;
   log->held = 0;
   log->stopped = false;
+  place_clear(ctx);
   return LSA_OK;
 }
 

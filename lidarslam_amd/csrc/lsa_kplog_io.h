@@ -19,4 +19,12 @@ struct KpLogRange
 int kplog_replay_range_to_set(lsa_ctx* ctx, const KpLogRange& range, lsa_ctx* dst, int set, long long counts[3], float box_min[3][3], float box_max[3][3]);
 int kplog_replay_range_to_grids(lsa_ctx* ctx, const KpLogRange& range, lsa_device_grid* const grids[3], bool fixed, double time, bool roll, long long counts[3],
                                 float box_min[3][3], float box_max[3][3]);
+
+// The log's frame table for its other unit, the descriptor store (lsa_place.hip): frame `frame`'s device pointers and counts.
+// false: no such frame.
+bool kplog_frame(const lsa_ctx* ctx, int frame, const lsa_point_t* pts[3], int n[3]);
+// ... and what the log tells the store (each does nothing while there is no store)
+void place_pop_front(lsa_ctx* ctx);
+void place_clear(lsa_ctx* ctx);
+void place_destroy(lsa_ctx* ctx);
 }  // namespace lsa

@@ -336,9 +336,30 @@ public:
     if (rc < 0) result.status = rc;
     return result;
   }
-  // The logged frame to try a loop closure of `query` against: among the frames at least minTravelled metres back along
-  // GetTrajectory() and within maxDistance metres of query's position, the nearest; -1 when there is none.  Host only;
-  // place recognition proper (descriptors) is the caller's.
+  // ---- place recognition: the logged frames before `query` that LOOK like it, whatever the drifted trajectory says about
+  // where they are -- polar height descriptors of the logged keypoints, built and compared on the device, exhaustively
+  // (lsa_slam_recognize_place).  Best first; candidate.yaw is the turn about z between the two frames, so a start guess for
+  // RegisterLoggedFrames(query, candidate.frame, ...) is pose[candidate.frame] * Rz(candidate.yaw).  Empty when there is
+  // none or when it cannot (GetLastError() says why).
+  using PlaceSearchParameters = lsa_place_search_t;
+  using PlaceCandidate = lsa_place_candidate_t;
+  static PlaceSearchParameters DefaultPlaceSearchParameters()
+  {
+    PlaceSearchParameters p;
+    lsa_place_search_init(&p);
+    return p;
+  }
+  std::vector<PlaceCandidate> RecognizePlace(std::size_t query, const PlaceSearchParameters& params = DefaultPlaceSearchParameters(), std::size_t maxCandidates = 5)
+  {
+    std::vector<PlaceCandidate> found(maxCandidates);
+    const int rc = lsa_slam_recognize_place(this->Handle, static_cast<int>(query), &params, found.data(), static_cast<int>(maxCandidates));
+    this->LastError = rc < 0 ? std::string("RecognizePlace: ") + lsa_slam_last_error(this->Handle) : std::string();
+    found.resize(static_cast<std::size_t>(rc > 0 ? rc : 0));
+    return found;
+  }
+  // The logged frame to try a loop closure of `query` against BY POSITION: among the frames at least minTravelled metres
+  // back along GetTrajectory() and within maxDistance metres of query's position, the nearest; -1 when there is none.  Host
+  // only.  By appearance: RecognizePlace above.
   int FindLoopClosureCandidate(std::size_t query, double minTravelled, double maxDistance) const
   {
     const int n = lsa_slam_get_trajectory(this->Handle, nullptr, nullptr, 0);

@@ -820,8 +820,8 @@ int lsa_slam_add_map_points(lsa_slam* s, int type, const lsa_point_t* pts, int n
 int lsa_slam_save_maps_pcd(lsa_slam* s, const char* prefix, int format, int filtered);
 int lsa_slam_load_maps_pcd(lsa_slam* s, const char* prefix, int reset_maps, double time);
 int lsa_slam_map_io_counts(const lsa_slam* s, int counts[3]);
-/* A trajectory corrected after the fact -- by GPS, a loop closure, g2o, GTSAM, Ceres, control points: the optimizer is the
- * caller's -- brought back into the library: everything Slam::RunPoseGraphOptimization does AFTER its optimizer
+/* A trajectory corrected after the fact -- by GPS, a loop closure, g2o, GTSAM, Ceres, control points: any optimizer of the
+ * caller's, or lsa_slam_optimize_logged_trajectory below for loop-closure edges -- brought back into the library: everything Slam::RunPoseGraphOptimization does AFTER its optimizer
  * (Slam.cxx:404-477).  Needs the keypoint log, i.e. "LoggingTimeout" != 0 while the frames were added (lsa_kplog_* above).
  * - lsa_slam_set_trajectory_and_rebuild_maps(poses17, n): rows as lsa_slam_get_trajectory gives them (row-major 4x4 + time).
  *   Waits for the map workers and the look-ahead; Reset(false); replaces the logged poses; re-projects every logged frame's
@@ -840,8 +840,8 @@ int lsa_slam_set_trajectory_and_rebuild_maps(lsa_slam* s, const double* poses17,
 int lsa_slam_logged_frames(const lsa_slam* s);
 int lsa_slam_get_logged_keypoints(lsa_slam* s, int frame, int type, lsa_point_t* out, int capacity);
 /* Loop closure: the registration of a logged frame against the part of the log recorded when the place was first seen -- the
- * constraint a pose-graph optimizer (the caller's) takes; the corrected trajectory comes back through
- * lsa_slam_set_trajectory_and_rebuild_maps.  Nothing but the result leaves the device.
+ * constraint a pose-graph optimizer (the caller's, or lsa_slam_optimize_logged_trajectory) takes; the corrected trajectory
+ * comes back through lsa_slam_set_trajectory_and_rebuild_maps.  Nothing but the result leaves the device.
  * - lsa_slam_register_logged_frames(query q, revisited r, params, guess, out), indices into the logged trajectory:
  *   1. windows R = [r - revisited_half_window, r + ...] and Q = [q - query_half_window, q + ...], clipped to the log;
  *   2. target: per keypoint type in use the points of R under the logged poses (lsa_kplog_replay_range, rule 2 -- rule 0 when
@@ -1130,6 +1130,107 @@ int lsa_kplog_replay_to_grids(lsa_ctx* ctx, unsigned type_mask, const double* po
                               float last_min[3][3], float last_max[3][3]);
 int lsa_kplog_replay_range(lsa_ctx* ctx, unsigned type_mask, const double* poses, const double* times, int n, int first, int last, int rule,
                            lsa_point_t* const out[3], float box_min[3][3], float box_max[3][3]);
+
+/* ------------------------------------------------------------------------- */
+/* Pose-graph optimization of relative-pose edges: the odometry chain of a logged trajectory plus the loop-closure edges
+ * lsa_slam_register_logged_frames produces.  The whole definition -- retraction t += R rho, R = R Exp(phi); the error
+ * e = [Rz^T (Ri^T (tj - ti) - tz) ; Log(Rz^T Ri^T Rj)]; its exact Jacobians; the order of every sum; the rules for small angles
+ * and angles near pi; the Levenberg-Marquardt loop with a preconditioned conjugate gradient inside -- is
+ * lidarslam_amd/csrc/lsa_pose_graph.h, compiled for the host and the device alike.  No GPS, no robust kernels.
+ * - lsa_pgo_edge_t: from -> to, `relative` the measured inv(P[from]) * P[to] (row-major 4x4), `information` its 6x6 weight
+ *   over (translation, rotation) in the tangent of the retraction, row-major.  from != to.
+ * - fixed[n]: non-zero = the pose is held.  At least one pose must be fixed and every free pose needs an edge; an index
+ *   out of range, from == to or a non-finite entry: all LSA_E_ARG, nothing written.
+ * - lsa_pgo_params_init: max_iterations 50, pcg_max_iter 500, pcg_tolerance 1e-8, initial_lambda 1e-6, lambda_shrink 0.25,
+ *   lambda_grow 8, lambda_min 1e-12, lambda_max 1e12, gradient_tolerance 1e-12, step_tolerance 1e-10, cost_tolerance 1e-13,
+ *   preconditioner 0 (block tridiagonal; 1 = its diagonal blocks alone, a knob for measurements), apply 0,
+ *   odometry_information 0, odometry_sigma {0.05 m x 3, 0.01 rad x 3}.
+ * - lsa_pgo_result_t.termination: LSA_PGO_* below; `message` names it (a static string).
+ * - lsa_pgo_solve_host: the host statement, no device (ctx-free).  lsa_pgo_solve: the device solver (lsa_pose_graph.hip):
+ *   k_pgo_linearize (a thread per edge), k_pgo_assemble (a thread per pose), a block parallel cyclic reduction of the
+ *   tridiagonal preconditioner (ceil(log2 n) launches per factorization and per application, alpha / gamma of every level
+ *   kept: LSA_E_CAPACITY above 262144 poses), k_pgo_spmv, two-level fixed-order dot products, no floating-point atomics: two
+ *   runs give the same bits.  The host drives LM and PCG and reads one small status block per PCG iteration; alpha and beta
+ *   stay on the device.  poses_out may be poses.  A refusal writes nothing.
+ * - seams (one call each: copies plus the kernel named, or its host twin): lsa_pgo_linearize[_host] -> e[6 m], blocks[120 m]
+ *   (Haa Hab Hbb ga gb per edge), chi2[m]; lsa_pgo_assemble[_host] at lambda -> D[36 n] (damped), g[6 n], L[36 n] = block
+ *   (i, i-1), U[36 n] = block (i, i+1); lsa_pgo_tridiagonal_solve[_host] (device: cyclic reduction; host: block Thomas):
+ *   returns 1 and leaves x untouched when a block is not positive definite; lsa_pgo_spmv[_host]: q = H_lambda p with the
+ *   blocks beyond the chain.
+ *   lsa_pgo_retract[_host]: out[i] = the retraction of pose i by delta[6 i .. 6 i + 5] (k_pgo_retract / its host twin);
+ *   lsa_pgo_edge_jacobians_host: e[6], A[36], B[36] of ONE edge (row-major 6x6), host only -- the device's are held through the
+ *   block records, which are made of them.
+ * - lsa_pgo_information_from_covariance: the inverse of a symmetric positive definite 6x6 (host); LSA_E_ARG otherwise.
+ * - lsa_slam_optimize_logged_trajectory(loop_edges, m, params, poses17_out, capacity, result): the graph of the logged
+ *   trajectory.  Vertices: the n logged poses, pose 0 fixed.  Odometry edge i-1 -> i: Z = inv(P[i-1]) * P[i], information by
+ *   params->odometry_information: 0 (the default, a choice: it works in "TwoDMode" and for a log whose covariances were
+ *   popped) = diag(1 / odometry_sigma^2), default sigma 0.05 m and 0.01 rad, a choice too; 1 = the reference's rule
+ *   (PoseGraphOptimization.cxx:237-244), the inverse of logged covariance i, LSA_E_ARG naming the frame when that is not
+ *   positive definite.  loop_edges: from = revisited, to = query, relative = lsa_loop_closure_result_t.relative, information
+ *   e.g. lsa_pgo_information_from_covariance(its covariance).  That a covariance over (X, Y, Z, rX, rY, rZ) serves as the
+ *   information of this tangent (translation in the body frame, rotation vector) is the reference's own simplification.
+ *   Writes n rows of 17 doubles as lsa_slam_get_trajectory gives them (capacity >= n rows) and returns n.  With
+ *   params->apply != 0 the result goes straight into lsa_slam_set_trajectory_and_rebuild_maps; with 0 nothing the frame path
+ *   reads is touched.  Waits for the map workers (an offline call); runs lsa_pgo_solve on the handle's scratch context.
+ *   LSA_E_STATE when "LoggingTimeout" is 0, keypoint logging stopped or the keypoint log does not cover the logged poses
+ *   (mode 1: or the covariance log does not); LSA_E_ARG for fewer than two poses, an edge outside the log or bad parameters;
+ *   nothing changed.  Read-only parameter "PoseGraphSeconds": the last call's solve by the host's clock. */
+#define LSA_PGO_MAX_ITERATIONS 0
+#define LSA_PGO_GRADIENT 1
+#define LSA_PGO_STEP 2
+#define LSA_PGO_COST 3
+#define LSA_PGO_LAMBDA_CEILING 4
+#define LSA_PGO_LINEAR_SOLVER_FAILED 5
+typedef struct lsa_pgo_edge_t
+{
+  int32_t from, to;
+  double relative[16];
+  double information[36];
+} lsa_pgo_edge_t;
+typedef struct lsa_pgo_params_t
+{
+  int32_t max_iterations;
+  int32_t pcg_max_iter;
+  int32_t preconditioner;
+  int32_t apply;                /* lsa_slam_optimize_logged_trajectory: hand the result to ..._set_trajectory_and_rebuild_maps */
+  int32_t odometry_information; /* lsa_slam_optimize_logged_trajectory: 0 diag(1 / odometry_sigma^2), 1 inverse logged covariance */
+  int32_t reserved;
+  double pcg_tolerance;
+  double initial_lambda, lambda_shrink, lambda_grow, lambda_min, lambda_max;
+  double gradient_tolerance, step_tolerance, cost_tolerance;
+  double odometry_sigma[6];
+} lsa_pgo_params_t;
+typedef struct lsa_pgo_result_t
+{
+  double initial_cost, final_cost; /* F = 1/2 sum chi2 */
+  double largest_step;             /* the largest max |delta| of an accepted step */
+  double final_lambda;
+  int32_t iterations, accepted_steps, rejected_steps;
+  int32_t pcg_iterations, last_pcg_iterations, pcg_truncated;
+  int32_t termination, reserved;
+  const char* message;
+} lsa_pgo_result_t;
+void lsa_pgo_params_init(lsa_pgo_params_t* params);
+int lsa_pgo_solve_host(const double* poses16, int n, const uint8_t* fixed, const lsa_pgo_edge_t* edges, int m, const lsa_pgo_params_t* params, double* poses_out,
+                       lsa_pgo_result_t* result);
+int lsa_pgo_solve(lsa_ctx* ctx, const double* poses16, int n, const uint8_t* fixed, const lsa_pgo_edge_t* edges, int m, const lsa_pgo_params_t* params, double* poses_out,
+                  lsa_pgo_result_t* result);
+int lsa_pgo_linearize_host(const double* poses16, int n, const lsa_pgo_edge_t* edges, int m, double* e_out, double* blocks_out, double* chi2_out);
+int lsa_pgo_linearize(lsa_ctx* ctx, const double* poses16, int n, const lsa_pgo_edge_t* edges, int m, double* e_out, double* blocks_out, double* chi2_out);
+int lsa_pgo_assemble_host(const double* poses16, int n, const uint8_t* fixed, const lsa_pgo_edge_t* edges, int m, double lambda, double* D_out, double* g_out,
+                          double* L_out, double* U_out);
+int lsa_pgo_assemble(lsa_ctx* ctx, const double* poses16, int n, const uint8_t* fixed, const lsa_pgo_edge_t* edges, int m, double lambda, double* D_out, double* g_out,
+                     double* L_out, double* U_out);
+int lsa_pgo_tridiagonal_solve_host(int n, const double* D, const double* L, const double* U, const double* b, double* x);
+int lsa_pgo_tridiagonal_solve(lsa_ctx* ctx, int n, const double* D, const double* L, const double* U, const double* b, double* x);
+int lsa_pgo_spmv_host(const double* poses16, int n, const uint8_t* fixed, const lsa_pgo_edge_t* edges, int m, double lambda, const double* p, double* q);
+int lsa_pgo_spmv(lsa_ctx* ctx, const double* poses16, int n, const uint8_t* fixed, const lsa_pgo_edge_t* edges, int m, double lambda, const double* p, double* q);
+int lsa_pgo_retract_host(const double* poses16, int n, const double* delta, double* poses_out);
+int lsa_pgo_retract(lsa_ctx* ctx, const double* poses16, int n, const double* delta, double* poses_out);
+int lsa_pgo_edge_jacobians_host(const double* poses16, int n, const lsa_pgo_edge_t* edge, double* e6, double* A36, double* B36);
+int lsa_pgo_information_from_covariance(const double* cov36, double* info36);
+int lsa_slam_optimize_logged_trajectory(lsa_slam* s, const lsa_pgo_edge_t* loop_edges, int m, const lsa_pgo_params_t* params, double* poses17_out, int capacity,
+                                        lsa_pgo_result_t* result);
 
 /* ---- the rolling voxel map (host) ---------------------------
  * LidarSlam::RollingGrid -- slam_lib/include/LidarSlam/RollingGrid.h:63-212,

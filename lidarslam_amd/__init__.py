@@ -87,6 +87,9 @@ ABI_SYMBOLS = [
     "lsa_kplog_replay_range", "lsa_loop_closure_params_init", "lsa_slam_register_logged_frames", "lsa_loop_closure_candidate",
     "lsa_place_params_init", "lsa_place_search_init", "lsa_scan_descriptor_host", "lsa_place_distance_host", "lsa_place_select_host",
     "lsa_slam_recognize_place", "lsa_kplog_describe", "lsa_kplog_descriptors", "lsa_kplog_place_search", "lsa_kplog_described", "lsa_kplog_descriptor_length",
+    "lsa_pgo_params_init", "lsa_pgo_solve_host", "lsa_pgo_solve", "lsa_pgo_linearize_host", "lsa_pgo_linearize", "lsa_pgo_assemble_host", "lsa_pgo_assemble",
+    "lsa_pgo_tridiagonal_solve_host", "lsa_pgo_tridiagonal_solve", "lsa_pgo_spmv_host", "lsa_pgo_spmv", "lsa_pgo_information_from_covariance",
+    "lsa_pgo_retract_host", "lsa_pgo_retract", "lsa_pgo_edge_jacobians_host", "lsa_slam_optimize_logged_trajectory",
 ]
 
 PCD_ASCII, PCD_BINARY, PCD_BINARY_COMPRESSED = 0, 1, 2  # PCDFormat (PointCloudStorage.h:60-65)
@@ -271,6 +274,195 @@ def place_select(distance, shift, poses, times, query, sectors=60, min_travelled
     if rc < 0:
         raise _error("lsa_place_select_host", rc, "bad argument")
     return _candidates(out, rc)
+
+
+# lsa_pgo_edge_t as a numpy record: from -> to, the measured inv(P[from]) @ P[to] (row-major 4x4), its 6x6 information
+PGO_EDGE_DTYPE = np.dtype([("from", np.int32), ("to", np.int32), ("relative", np.float64, (16,)), ("information", np.float64, (36,))])
+PGO_EDGE_BLOCK = 120  # doubles of an edge's block record: Haa[36] Hab[36] Hbb[36] ga[6] gb[6]
+PGO_MAX_ITERATIONS, PGO_GRADIENT, PGO_STEP, PGO_COST, PGO_LAMBDA_CEILING, PGO_LINEAR_SOLVER_FAILED = range(6)
+
+
+class PoseGraphParams(C.Structure):
+    """lsa_pgo_params_t (include/lidarslam_amd.h); the defaults are lsa_pgo_params_init's."""
+
+    _fields_ = [
+        ("max_iterations", C.c_int32), ("pcg_max_iter", C.c_int32), ("preconditioner", C.c_int32), ("apply", C.c_int32), ("odometry_information", C.c_int32),
+        ("reserved", C.c_int32), ("pcg_tolerance", C.c_double), ("initial_lambda", C.c_double), ("lambda_shrink", C.c_double), ("lambda_grow", C.c_double),
+        ("lambda_min", C.c_double), ("lambda_max", C.c_double), ("gradient_tolerance", C.c_double), ("step_tolerance", C.c_double), ("cost_tolerance", C.c_double),
+        ("odometry_sigma", C.c_double * 6),
+    ]
+
+    def __init__(self, **kw):
+        super().__init__()
+        lib().lsa_pgo_params_init(C.byref(self))
+        for k, v in kw.items():
+            if k == "odometry_sigma":
+                v = (C.c_double * 6)(*[float(a) for a in v])
+            elif k not in dict(self._fields_):
+                raise TypeError(f"PoseGraphParams has no field {k!r}")
+            setattr(self, k, v)
+
+
+class PoseGraphResultStruct(C.Structure):
+    """lsa_pgo_result_t."""
+
+    _fields_ = [
+        ("initial_cost", C.c_double), ("final_cost", C.c_double), ("largest_step", C.c_double), ("final_lambda", C.c_double),
+        ("iterations", C.c_int32), ("accepted_steps", C.c_int32), ("rejected_steps", C.c_int32), ("pcg_iterations", C.c_int32),
+        ("last_pcg_iterations", C.c_int32), ("pcg_truncated", C.c_int32), ("termination", C.c_int32), ("reserved", C.c_int32), ("message", C.c_char_p),
+    ]
+
+
+class PoseGraphResult:
+    """What a pose-graph solve reports: initial_cost / final_cost (1/2 sum chi2), largest_step, final_lambda, iterations,
+    accepted_steps, rejected_steps, pcg_iterations, last_pcg_iterations, pcg_truncated, termination (PGO_*), message."""
+
+    def __init__(self, r):
+        for name, _ in PoseGraphResultStruct._fields_:
+            if name != "reserved":
+                setattr(self, name, getattr(r, name))
+        self.message = (r.message or b"").decode()
+
+    def __repr__(self):
+        return f"PoseGraphResult({self.__dict__})"
+
+
+def pose_graph_edges(edges):
+    """A PGO_EDGE_DTYPE array from one, or from an iterable of (from, to, relative (4, 4), information (6, 6))."""
+    if isinstance(edges, np.ndarray) and edges.dtype == PGO_EDGE_DTYPE:
+        return np.ascontiguousarray(edges)
+    edges = list(edges)
+    out = np.zeros(len(edges), PGO_EDGE_DTYPE)
+    for k, (a, b, Z, W) in enumerate(edges):
+        out[k]["from"], out[k]["to"] = int(a), int(b)
+        out[k]["relative"] = np.asarray(Z, np.float64).reshape(16)
+        out[k]["information"] = np.asarray(W, np.float64).reshape(36)
+    return out
+
+
+def _pgo_graph(poses, fixed, edges):
+    P = np.ascontiguousarray(np.asarray(poses, np.float64).reshape(-1, 16))
+    E = pose_graph_edges(edges)
+    f = None if fixed is None else np.ascontiguousarray(np.asarray(fixed).astype(np.uint8).reshape(-1))
+    if f is not None and f.size != P.shape[0]:
+        raise _error("pose graph", E_ARG, "as many fixed flags as poses")
+    return P, f, E
+
+
+def _pgo_run(what, ctx, poses, fixed, edges, make_out, *extra):
+    """One of the lsa_pgo_* calls that take (poses, n, [fixed,] edges, m, extra..., outputs...); ctx None: the _host twin."""
+    P, f, E = _pgo_graph(poses, fixed, edges)
+    L = lib()
+    fn = getattr(L, what if ctx is not None else what + "_host")
+    outs = make_out(P.shape[0], E.size)
+    args = ([ctx.h] if ctx is not None else []) + [ptr(P), P.shape[0]] + ([] if f is None else [ptr(f)]) + [ptr(E) if E.size else None, E.size]
+    rc = fn(*args, *extra, *[ptr(o) if isinstance(o, np.ndarray) else o for o in outs])
+    if rc < 0:
+        raise _error(fn.__name__, rc, L.lsa_last_error(ctx.h).decode() if ctx is not None else "the graph is outside the definition")
+    return outs
+
+
+def pose_graph_solve(poses, fixed, edges, ctx=None, params=None, **kw):
+    """Levenberg-Marquardt on the pose graph (lidarslam_amd/csrc/lsa_pose_graph.h): poses (n, 4, 4), fixed (n,) flags, edges as
+    pose_graph_edges takes them -> (poses (n, 4, 4), PoseGraphResult).  ctx None: the host statement (lsa_pgo_solve_host); a
+    Context: the device solver (lsa_pgo_solve).  params: a PoseGraphParams, or its fields as keywords."""
+    p = params if params is not None else PoseGraphParams(**kw)
+    r = PoseGraphResultStruct()
+    P, f, E = _pgo_graph(poses, fixed, edges)
+    if f is None:
+        raise _error("lsa_pgo_solve", E_ARG, "fixed flags are needed")
+    out = np.zeros((P.shape[0], 4, 4))
+    L = lib()
+    if ctx is None:
+        rc = L.lsa_pgo_solve_host(ptr(P), P.shape[0], ptr(f), ptr(E) if E.size else None, E.size, C.byref(p), ptr(out), C.byref(r))
+        if rc < 0:
+            raise _error("lsa_pgo_solve_host", rc, "the graph or the parameters are outside the definition")
+    else:
+        rc = L.lsa_pgo_solve(ctx.h, ptr(P), P.shape[0], ptr(f), ptr(E) if E.size else None, E.size, C.byref(p), ptr(out), C.byref(r))
+        if rc < 0:
+            raise _error("lsa_pgo_solve", rc, L.lsa_last_error(ctx.h).decode())
+    return out, PoseGraphResult(r)
+
+
+def pose_graph_solve_host(poses, fixed, edges, params=None, **kw):
+    """pose_graph_solve without a device."""
+    return pose_graph_solve(poses, fixed, edges, None, params, **kw)
+
+
+def pose_graph_linearize(poses, edges, ctx=None):
+    """-> e (m, 6), blocks (m, 120), chi2 (m,): k_pgo_linearize with a Context, its host twin without."""
+    e, b, c = _pgo_run("lsa_pgo_linearize", ctx, poses, None, edges, lambda n, m: [np.zeros((m, 6)), np.zeros((m, PGO_EDGE_BLOCK)), np.zeros(m)])
+    return e, b, c
+
+
+def pose_graph_assemble(poses, fixed, edges, lam=0.0, ctx=None):
+    """-> D (n, 6, 6) damped by lam, g (n, 6), L (n, 6, 6) = block (i, i-1), U (n, 6, 6) = block (i, i+1)."""
+    D, g, Lo, U = _pgo_run("lsa_pgo_assemble", ctx, poses, fixed, edges, lambda n, m: [np.zeros((n, 6, 6)), np.zeros((n, 6)), np.zeros((n, 6, 6)), np.zeros((n, 6, 6))],
+                           C.c_double(lam))
+    return D, g, Lo, U
+
+
+def pose_graph_spmv(poses, fixed, edges, lam, p, ctx=None):
+    """q = H_lambda p (n, 6), the blocks beyond the chain included."""
+    pv = np.ascontiguousarray(np.asarray(p, np.float64).reshape(-1, 6))
+    if pv.shape[0] != np.asarray(poses).reshape(-1, 16).shape[0]:
+        raise _error("lsa_pgo_spmv", E_ARG, "a vector of another length than the poses")
+    q, = _pgo_run("lsa_pgo_spmv", ctx, poses, fixed, edges, lambda n, m: [np.zeros((n, 6))], C.c_double(lam), ptr(pv))
+    return q
+
+
+def pose_graph_tridiagonal_solve(D, L, U, b, ctx=None):
+    """x (n, 6) with T x = b for the block-tridiagonal T = (D, L, U), each (n, 6, 6): cyclic reduction on the device with a
+    Context, block Thomas on the host without.  None when a block is not positive definite."""
+    D, L, U = [np.ascontiguousarray(np.asarray(a, np.float64).reshape(-1, 36)) for a in (D, L, U)]
+    b = np.ascontiguousarray(np.asarray(b, np.float64).reshape(-1, 6))
+    n = D.shape[0]
+    if not (L.shape[0] == U.shape[0] == b.shape[0] == n):
+        raise _error("lsa_pgo_tridiagonal_solve", E_ARG, "arrays of different lengths")
+    x = np.full((n, 6), np.nan)
+    lb = lib()
+    if ctx is None:
+        rc = lb.lsa_pgo_tridiagonal_solve_host(n, ptr(D), ptr(L), ptr(U), ptr(b), ptr(x))
+    else:
+        rc = lb.lsa_pgo_tridiagonal_solve(ctx.h, n, ptr(D), ptr(L), ptr(U), ptr(b), ptr(x))
+    if rc < 0:
+        raise _error("lsa_pgo_tridiagonal_solve", rc, lb.lsa_last_error(ctx.h).decode() if ctx is not None else "bad argument")
+    return None if rc == 1 else x
+
+
+def pose_graph_retract(poses, delta, ctx=None):
+    """poses (n, 4, 4) moved by delta (n, 6) = (rho, phi): t += R rho, R = R Exp(phi) (k_pgo_retract with a Context)."""
+    P = np.ascontiguousarray(np.asarray(poses, np.float64).reshape(-1, 16))
+    d = np.ascontiguousarray(np.asarray(delta, np.float64).reshape(-1, 6))
+    if d.shape[0] != P.shape[0]:
+        raise _error("lsa_pgo_retract", E_ARG, "as many steps as poses")
+    out = np.zeros((P.shape[0], 4, 4))
+    lb = lib()
+    rc = lb.lsa_pgo_retract_host(ptr(P), P.shape[0], ptr(d), ptr(out)) if ctx is None else lb.lsa_pgo_retract(ctx.h, ptr(P), P.shape[0], ptr(d), ptr(out))
+    if rc < 0:
+        raise _error("lsa_pgo_retract", rc, lb.lsa_last_error(ctx.h).decode() if ctx is not None else "bad argument")
+    return out
+
+
+def pose_graph_edge_jacobians(poses, edge):
+    """e (6,), A = de/ddelta_from (6, 6), B = de/ddelta_to (6, 6) of one edge; the host statement."""
+    P = np.ascontiguousarray(np.asarray(poses, np.float64).reshape(-1, 16))
+    E = pose_graph_edges([edge] if isinstance(edge, tuple) else edge)
+    e, A, B = np.zeros(6), np.zeros((6, 6)), np.zeros((6, 6))
+    rc = lib().lsa_pgo_edge_jacobians_host(ptr(P), P.shape[0], ptr(E), ptr(e), ptr(A), ptr(B))
+    if rc < 0:
+        raise _error("lsa_pgo_edge_jacobians_host", rc, "the edge is outside the definition")
+    return e, A, B
+
+
+def information_from_covariance(cov):
+    """The inverse of a symmetric positive definite 6x6 (lsa_pgo_information_from_covariance); raises for anything else."""
+    c = np.ascontiguousarray(np.asarray(cov, np.float64).reshape(36))
+    out = np.zeros((6, 6))
+    rc = lib().lsa_pgo_information_from_covariance(ptr(c), ptr(out))
+    if rc < 0:
+        raise _error("lsa_pgo_information_from_covariance", rc, "not a symmetric positive definite matrix")
+    return out
 
 
 class SensorTerms(C.Structure):
@@ -585,6 +777,23 @@ def lib():
     L.lsa_kplog_place_search.argtypes = [vp, vp, i32, i32, i32, vp, vp]
     L.lsa_kplog_described.argtypes = [vp]
     L.lsa_kplog_descriptor_length.argtypes = [vp]
+    L.lsa_pgo_params_init.restype = None
+    L.lsa_pgo_params_init.argtypes = [vp]
+    L.lsa_pgo_solve_host.argtypes = [vp, i32, vp, vp, i32, vp, vp, vp]
+    L.lsa_pgo_solve.argtypes = [vp, vp, i32, vp, vp, i32, vp, vp, vp]
+    L.lsa_pgo_linearize_host.argtypes = [vp, i32, vp, i32, vp, vp, vp]
+    L.lsa_pgo_linearize.argtypes = [vp, vp, i32, vp, i32, vp, vp, vp]
+    L.lsa_pgo_assemble_host.argtypes = [vp, i32, vp, vp, i32, f64, vp, vp, vp, vp]
+    L.lsa_pgo_assemble.argtypes = [vp, vp, i32, vp, vp, i32, f64, vp, vp, vp, vp]
+    L.lsa_pgo_tridiagonal_solve_host.argtypes = [i32, vp, vp, vp, vp, vp]
+    L.lsa_pgo_tridiagonal_solve.argtypes = [vp, i32, vp, vp, vp, vp, vp]
+    L.lsa_pgo_spmv_host.argtypes = [vp, i32, vp, vp, i32, f64, vp, vp]
+    L.lsa_pgo_spmv.argtypes = [vp, vp, i32, vp, vp, i32, f64, vp, vp]
+    L.lsa_pgo_information_from_covariance.argtypes = [vp, vp]
+    L.lsa_pgo_retract_host.argtypes = [vp, i32, vp, vp]
+    L.lsa_pgo_retract.argtypes = [vp, vp, i32, vp, vp]
+    L.lsa_pgo_edge_jacobians_host.argtypes = [vp, i32, vp, vp, vp, vp]
+    L.lsa_slam_optimize_logged_trajectory.argtypes = [vp, vp, i32, vp, vp, i32, vp]
     L.lsa_slam_set_trajectory_and_rebuild_maps.argtypes = [vp, vp, i32]
     L.lsa_slam_logged_frames.argtypes = [vp]
     L.lsa_slam_get_logged_keypoints.argtypes = [vp, i32, i32, vp, i32]
@@ -1190,6 +1399,25 @@ class Context:
         return [o[:s].copy() for o, s in zip(outs, sizes)], mn, mx
 
     # ---- the log's descriptor store (lsa_kplog_describe / _descriptors / _place_search): place recognition
+    # ---- pose graph (lsa_pose_graph.hip); the module functions of the same names without a Context are the host statement
+    def pose_graph_solve(self, poses, fixed, edges, params=None, **kw):
+        return pose_graph_solve(poses, fixed, edges, self, params, **kw)
+
+    def pose_graph_linearize(self, poses, edges):
+        return pose_graph_linearize(poses, edges, self)
+
+    def pose_graph_assemble(self, poses, fixed, edges, lam=0.0):
+        return pose_graph_assemble(poses, fixed, edges, lam, self)
+
+    def pose_graph_spmv(self, poses, fixed, edges, lam, p):
+        return pose_graph_spmv(poses, fixed, edges, lam, p, self)
+
+    def pose_graph_tridiagonal_solve(self, D, L, U, b):
+        return pose_graph_tridiagonal_solve(D, L, U, b, self)
+
+    def pose_graph_retract(self, poses, delta):
+        return pose_graph_retract(poses, delta, self)
+
     def kplog_describe(self, first, last, **params):
         """describes the frames first..last that have no valid descriptor under these PlaceParams -> how many it described"""
         p = PlaceParams(**params)
@@ -1496,6 +1724,22 @@ class Slam:
         self._check(self.L.lsa_slam_register_logged_frames(self.h, int(query), int(revisited), C.byref(p), None if g is None else ptr(g), C.byref(r)),
                     "lsa_slam_register_logged_frames")
         return LoopClosureResult(r)
+
+    def optimize_trajectory(self, loop_edges, apply=False, params=None, **kw):
+        """Pose-graph optimization of the logged trajectory on the device (lsa_slam_optimize_logged_trajectory): the odometry
+        chain of the log, pose 0 fixed, plus loop_edges -- (revisited, query, relative (4, 4), information (6, 6)) each, e.g.
+        from register_logged_frames: (r, q, res.relative, information_from_covariance(res.covariance)).  apply=True hands the
+        result to set_trajectory.  kw: PoseGraphParams' fields (odometry_information, odometry_sigma, ...).
+        -> (poses (n, 4, 4), times (n,), PoseGraphResult)"""
+        p = params if params is not None else PoseGraphParams(**kw)
+        p.apply = int(bool(apply))
+        E = pose_graph_edges(loop_edges)
+        n = self._check(self.L.lsa_slam_logged_frames(self.h), "lsa_slam_logged_frames")
+        rows = np.zeros((max(n, 1), 17))
+        r = PoseGraphResultStruct()
+        got = self._check(self.L.lsa_slam_optimize_logged_trajectory(self.h, ptr(E) if E.size else None, E.size, C.byref(p), ptr(rows), rows.shape[0], C.byref(r)),
+                          "lsa_slam_optimize_logged_trajectory")
+        return rows[:got, :16].reshape(-1, 4, 4).copy(), rows[:got, 16].copy(), PoseGraphResult(r)
 
     def recognize_place(self, query, capacity=5, **params):
         """Place recognition: the logged frames before `query` that look like it -> [(frame, distance, shift, yaw)], best

@@ -343,6 +343,13 @@ int lsa_slam_recognize_place(lsa_slam* s, int query, const lsa_place_search_t* s
   return s->core.RecognizePlace(query, search, out, capacity);
 }
 
+int lsa_slam_optimize_logged_trajectory(lsa_slam* s, const lsa_pgo_edge_t* loop_edges, int m, const lsa_pgo_params_t* params, double* poses17_out, int capacity,
+                                        lsa_pgo_result_t* result)
+{
+  if (!s) return LSA_E_ARG;
+  return s->core.OptimizeLoggedTrajectory(loop_edges, m, params, poses17_out, capacity, result);
+}
+
 int lsa_loop_closure_candidate(const double* poses17, int n, int query, double min_travelled, double max_distance)
 {
   return lsa::host::LoopClosureCandidate(poses17, n, query, min_travelled, max_distance);

@@ -10,6 +10,7 @@
 #include "lsa_pcd.h"
 #include "../lsa_device_grid_io.h"
 #include "../lsa_kplog_io.h"
+#include "lsa_pose_graph.h"
 
 namespace lsa
 {
@@ -1877,6 +1878,87 @@ int SlamCore::RecognizePlace(int query, const lsa_place_search_t* search, lsa_pl
   return found;
 }
 
+// ---- pose-graph optimization of the logged trajectory (lsa_pose_graph.hip) ---------------------------------------------------
+int SlamCore::OptimizeLoggedTrajectory(const lsa_pgo_edge_t* loopEdges, int m, const lsa_pgo_params_t* params, double* poses17, int capacity, lsa_pgo_result_t* result)
+{
+  if (!Ctx) return LSA_E_NO_DEVICE;
+  const std::string who = "OptimizeLoggedTrajectory: ";
+  if (!result || !poses17 || m < 0 || (m > 0 && !loopEdges)) { LastError = who + "bad argument"; return LSA_E_ARG; }
+  if (LoggingTimeout == 0.) { LastError = who + "keypoint logging is off (LoggingTimeout = 0): there is no logged trajectory to optimize"; return LSA_E_STATE; }
+  if (KpLogStopped) { LastError = who + "keypoint logging stopped when a chunk could not be allocated; Reset(true) starts it again"; return LSA_E_STATE; }
+  const int n = static_cast<int>(LogTrajectory.size());
+  if (lsa_kplog_size(Ctx) != n) { LastError = who + "the keypoint log does not cover the logged poses (logging was switched on after the first of them)"; return LSA_E_STATE; }
+  lsa_pgo_params_t p;
+  lsa_pgo_params_init(&p);
+  if (params) p = *params;
+  if (!pg::params_ok(p)) { LastError = who + "parameters out of limits"; return LSA_E_ARG; }
+  if (n < 2) { LastError = who + "at least two logged poses"; return LSA_E_ARG; }
+  if (capacity < n) { LastError = who + "room for " + std::to_string(capacity) + " of " + std::to_string(n) + " poses"; return LSA_E_ARG; }
+  for (int k = 0; k < m; ++k)
+    if (loopEdges[k].from < 0 || loopEdges[k].from >= n || loopEdges[k].to < 0 || loopEdges[k].to >= n || loopEdges[k].from == loopEdges[k].to)
+    {
+      LastError = who + "loop edge " + std::to_string(k) + " does not join two of the " + std::to_string(n) + " logged poses";
+      return LSA_E_ARG;
+    }
+  std::vector<lsa_pgo_edge_t> edges(static_cast<size_t>(n - 1 + m));
+  double diagonal[36];
+  std::memset(diagonal, 0, sizeof(diagonal));
+  if (p.odometry_information == 0)
+    for (int k = 0; k < 6; ++k)
+    {
+      const double sigma = p.odometry_sigma[k];
+      if (!(sigma > 0.) || !pg::finite_d(1. / (sigma * sigma))) { LastError = who + "odometry_sigma must be positive"; return LSA_E_ARG; }
+      diagonal[k * 7] = 1. / (sigma * sigma);
+    }
+  else if (static_cast<int>(LogCovariances.size()) != n) { LastError = who + "the covariance log does not cover the logged poses (odometry_information 0 needs none)"; return LSA_E_STATE; }
+  for (int i = 1; i < n; ++i)
+  {
+    lsa_pgo_edge_t& ed = edges[static_cast<size_t>(i - 1)];
+    ed.from = i - 1;
+    ed.to = i;
+    const Pose z = Inverse(LogTrajectory[i - 1].pose) * LogTrajectory[i].pose;
+    std::memcpy(ed.relative, z.m, sizeof(ed.relative));
+    if (p.odometry_information == 0) std::memcpy(ed.information, diagonal, sizeof(diagonal));
+    else if (lsa_pgo_information_from_covariance(LogCovariances[i].data(), ed.information) != LSA_OK)
+    {
+      LastError = who + "the logged covariance of frame " + std::to_string(i) + " is not positive definite (odometry_information 0 needs none)";
+      return LSA_E_ARG;
+    }
+  }
+  for (int k = 0; k < m; ++k) edges[static_cast<size_t>(n - 1 + k)] = loopEdges[k];
+  std::vector<double> in(static_cast<size_t>(n) * 16), out(static_cast<size_t>(n) * 16);
+  std::vector<unsigned char> fixed(static_cast<size_t>(n), 0);
+  fixed[0] = 1;
+  for (int i = 0; i < n; ++i) std::memcpy(&in[16 * static_cast<size_t>(i)], LogTrajectory[i].pose.m, 16 * sizeof(double));
+  {
+    std::string why;
+    if (const int rc = PgoCheckEdges(in.data(), n, edges.data(), static_cast<int>(edges.size()), &why); rc != LSA_OK) { LastError = who + why; return rc; }
+  }
+  // from here on the device works: the map workers and the look-ahead have enqueued what they had (nothing of theirs is changed)
+  WaitMaps();
+  if (const int rc = EnsureLoopClosureScratch(); rc < 0) return rc;
+  (void)lsa_collect_garbage(LoopCtx);
+  Tick t;
+  lsa_pgo_result_t r;
+  if (const int rc = lsa_pgo_solve(LoopCtx, in.data(), n, fixed.data(), edges.data(), static_cast<int>(edges.size()), &p, out.data(), &r); rc < 0)
+  {
+    LastError = who + lsa_last_error(LoopCtx);
+    return rc;
+  }
+  PoseGraphSeconds = t.Stop();
+  std::vector<double> rows(static_cast<size_t>(n) * 17);
+  for (int i = 0; i < n; ++i)
+  {
+    std::memcpy(&rows[17 * static_cast<size_t>(i)], &out[16 * static_cast<size_t>(i)], 16 * sizeof(double));
+    rows[17 * static_cast<size_t>(i) + 16] = LogTrajectory[i].time;
+  }
+  if (p.apply != 0)
+    if (const int rc = SetTrajectoryAndRebuildMaps(rows.data(), n); rc < 0) return rc;
+  std::memcpy(poses17, rows.data(), rows.size() * sizeof(double));
+  *result = r;
+  return n;
+}
+
 // ---- loop closure: a logged frame registered against the log around a revisited pose ---------------------------------------
 int SlamCore::EnsureLoopClosureScratch()
 {
@@ -2356,6 +2438,7 @@ int SlamCore::GetParam(const std::string& name, double* v) const
   if (name == "LoopClosureMapsSeconds") { *v = LoopClosureSeconds[1]; return LSA_OK; }
   if (name == "LoopClosureIcpSeconds") { *v = LoopClosureSeconds[2]; return LSA_OK; }
   if (name == "LoopClosureSeconds") { *v = LoopClosureSeconds[3]; return LSA_OK; }
+  if (name == "PoseGraphSeconds") { *v = PoseGraphSeconds; return LSA_OK; }
   if (name == "LoggedKeypointsBytes") { *v = Ctx ? static_cast<double>(lsa_kplog_bytes(Ctx)) : 0.; return LSA_OK; }
   if (name == "LoggedFrames") { *v = LoggedFrames(); return LSA_OK; }
   if (name == "TimeWindowDuration") { *v = TimeWindowDuration; return LSA_OK; }

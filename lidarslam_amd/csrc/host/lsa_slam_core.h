@@ -131,6 +131,10 @@ public:
   // (lsa_slam_recognize_place in lidarslam_amd.h).  Runs on the log's context after the map workers; reads the log, writes
   // the log's descriptor store and nothing else.  Returns the number of candidates written.
   int RecognizePlace(int query, const lsa_place_search_t* search, lsa_place_candidate_t* out, int capacity);
+  // Pose-graph optimization of the logged trajectory with the caller's loop edges (lsa_slam_optimize_logged_trajectory in
+  // lidarslam_amd.h): the solve runs on the scratch context; with params->apply the result goes through
+  // SetTrajectoryAndRebuildMaps, without it nothing of the frame path is touched.  Returns the number of poses.
+  int OptimizeLoggedTrajectory(const lsa_pgo_edge_t* loopEdges, int m, const lsa_pgo_params_t* params, double* poses17, int capacity, lsa_pgo_result_t* result);
   int LoggedFrames() const;
   int GetLoggedKeypoints(int frame, int type, std::vector<lsa_point_t>& out);
   void HintNextStoredFrame(int slot) { NextStoredSlot = slot; }
@@ -347,6 +351,7 @@ private:
   lsa_ctx* LoopCtx = nullptr;
   lsa_device_grid* LoopMaps[3] = {nullptr, nullptr, nullptr};
   int EnsureLoopClosureScratch();
+  double PoseGraphSeconds = 0.;   // the last OptimizeLoggedTrajectory's solve by the host's clock
   double LoopClosureSeconds[4] = {0., 0., 0., 0.};  // the last call by the host's clock: replays, scratch maps, ICP loop, all of it
   std::string LastError;
   uint64_t CurrentStamp = 0;

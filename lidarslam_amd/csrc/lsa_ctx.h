@@ -12,6 +12,7 @@
 //   reduce       per-block partials of the normal equations, 29 doubles each
 //   keypoint log AoS lsa_point_t in chunks of 32 MiB, a frame's three types one after the other (lsa_kplog.hip; only with logging on)
 //   descriptors  a ring of slots of rings * sectors + sectors floats, one per logged frame (lsa_place.hip; only once asked for)
+//   pose graph   poses, edges, per-edge block records, block rows D / L / U, the cyclic reduction's levels, PCG vectors (lsa_pose_graph.hip; only once asked for)
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>
@@ -137,6 +138,7 @@ struct PendingEvent
 
 struct KpLog;  // lsa_kplog.hip
 struct PlaceStore;  // lsa_place.hip
+struct PgoBuffers;  // lsa_pose_graph.hip
 
 }  // namespace lsa
 
@@ -333,6 +335,8 @@ struct lsa_ctx
   // the log's descriptor store (lsa_place.hip): made by the first describe, follows the log's appends, pops and clears
   lsa::PlaceStore* place = nullptr;
   int place_max_blocks = 0;                     // lsa_debug_set "place_max_blocks": 0 = the default
+  // the pose-graph solver's buffers (lsa_pose_graph.hip): made by the first call, grown through the graveyard
+  lsa::PgoBuffers* pgo = nullptr;
 
   // profiling
   bool profiling = false;
@@ -373,6 +377,7 @@ int lm_cache_capacity();
 extern std::atomic<int> g_live_contexts;  // contexts of this process (lsa_lm.hip: a solve's share of the chip)
 int lm_blocks_share();
 void kplog_destroy(lsa_ctx* ctx);  // lsa_kplog.hip
+void pgo_destroy(lsa_ctx* ctx);    // lsa_pose_graph.hip
 inline void retire_dev(lsa_ctx* ctx, void* p)
 {
   if (!p) return;

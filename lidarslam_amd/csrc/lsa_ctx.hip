@@ -299,6 +299,7 @@ void lsa_ctx_destroy(lsa_ctx* ctx)
     fr(ctx->match[k].rec); fr(ctx->match[k].status); fr(ctx->match[k].knn_idx); fr(ctx->match[k].knn_d2); fr(ctx->match[k].knn_cnt); fr(ctx->match[k].slow_list); fr(ctx->match[k].slow_pts);
   }
   kplog_destroy(ctx);
+  pgo_destroy(ctx);
   fr(ctx->partials); fr(ctx->reduce_out); fr(ctx->hist_dev); fr(ctx->scratch_out); fr(ctx->range_bits);
   for (auto& s : ctx->store) fr(s.first);
   if (ctx->host_pinned) (void)hipHostFree(ctx->host_pinned);

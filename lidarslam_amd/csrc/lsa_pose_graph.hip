@@ -1,0 +1,756 @@
+// lsa_pose_graph.hip -- the pose-graph solve on the device.  The definition -- error, Jacobians, the order of
+// every sum, the LM loop -- is lsa_pose_graph.h, the text the host statement (host/lsa_pose_graph.cpp) compiles too; the kernels
+// below decide only who computes what.  All double precision, no floating-point atomics, every sum in a fixed order: two runs
+// give the same bits.  No kernel waits for the host or for another workgroup; every launch is finite whatever the data.
+//   k_pgo_linearize   a thread per edge: e, A, B, the edge's block record, chi2
+//   k_pgo_assemble    a thread per pose: walks its incidence list ascending; D (damped), diag(H), g, the tridiagonal L / U
+//   k_pgo_pcr_level   block parallel cyclic reduction of the preconditioner T, one launch per stride s = 1, 2, 4, .. < n, a
+//                     thread per row: alpha = -L_i D_{i-s}^-1, gamma = -U_i D_{i+s}^-1, D' = D + alpha U_{i-s} + gamma L_{i+s},
+//                     L' = alpha L_{i-s}, U' = gamma U_{i+s}; alpha and gamma of every level are KEPT, so that an application
+//                     of T^-1 is ceil(log2 n) light launches (k_pgo_pcr_apply) plus one (k_pgo_pcr_solve with the inverses
+//                     of the last level's diagonal blocks).  36 n doubles twice per level: 262144 poses is the limit
+//                     (LSA_E_CAPACITY), 2.7 GB there.  A block that is not positive definite raises a flag.
+//   k_pgo_spmv        row i = D_i p_i + L_i p_{i-1} + U_i p_{i+1} + the blocks beyond the chain in the order of the row's list,
+//                     and the workgroup's partial sum of p.q
+//   PCG's vector updates and dot products: a partial sum per workgroup by a fixed tree, the partial sums added in order by
+//   one thread, which also forms alpha and beta -- they stay on the device; the host reads one status block per iteration
+//   to decide whether to enqueue the next.
+//   k_pgo_retract, k_pgo_chi2 and the sums for the candidate.
+// Buffers belong to the context and grow through its graveyard; everything runs on the context's stream.
+#include <algorithm>
+#include <cstring>
+#include <string>
+#include <vector>
+#include "lsa_ctx.h"
+#include "lsa_pose_graph.h"
+#include "host/lsa_pose_graph.h"
+
+using namespace lsa;
+
+namespace lsa
+{
+struct PgoState
+{
+  double rz, rz0, pq, alpha, beta;
+  double stat[4];  // model decrease, max |delta|, max |g|, sum of chi2
+  int iters, converged, failed, notspd;
+};
+struct PgoBuf
+{
+  void* p = nullptr;
+  size_t cap = 0;
+};
+struct PgoBuffers
+{
+  PgoBuf poses, cand, edges, fixed, row_start, inc, loop_start, loop_edge, loop_col, e, blocks, chi2, D, dg, g, L, U, work[2], alpha, gamma, Dinv, vec, partials, state;
+  PgoState* host = nullptr;  // pinned
+};
+void pgo_destroy(lsa_ctx* ctx)
+{
+  PgoBuffers* b = ctx->pgo;
+  if (!b) return;
+  PgoBuf* all[] = {&b->poses, &b->cand, &b->edges, &b->fixed, &b->row_start, &b->inc, &b->loop_start, &b->loop_edge, &b->loop_col, &b->e, &b->blocks, &b->chi2, &b->D,
+                   &b->dg, &b->g, &b->L, &b->U, &b->work[0], &b->work[1], &b->alpha, &b->gamma, &b->Dinv, &b->vec, &b->partials, &b->state};
+  for (PgoBuf* x : all)
+    if (x->p) (void)hipFree(x->p);
+  if (b->host) (void)hipHostFree(b->host);
+  delete b;
+  ctx->pgo = nullptr;
+}
+}  // namespace lsa
+
+namespace
+{
+constexpr int kThreads = 256;
+constexpr int kMaxPoses = 262144;
+inline unsigned blocks_for(long long n) { return (unsigned)std::max<long long>(1, (n + kThreads - 1) / kThreads); }
+
+__global__ __launch_bounds__(kThreads) void k_pgo_linearize(const double* __restrict__ poses, const lsa_pgo_edge_t* __restrict__ edges, int m, double* __restrict__ e,
+                                                            double* __restrict__ blocks, double* __restrict__ chi2)
+{
+  const int k = blockIdx.x * kThreads + threadIdx.x;
+  if (k >= m) return;
+  pg::linearize_edge(poses, edges[k], e + 6LL * k, blocks + (long long)k * pg::kEdgeBlock, chi2 + k);
+}
+
+__global__ __launch_bounds__(kThreads) void k_pgo_chi2(const double* __restrict__ poses, const lsa_pgo_edge_t* __restrict__ edges, int m, double* __restrict__ chi2)
+{
+  const int k = blockIdx.x * kThreads + threadIdx.x;
+  if (k >= m) return;
+  chi2[k] = pg::edge_chi2(poses, edges[k]);
+}
+
+__global__ __launch_bounds__(kThreads) void k_pgo_assemble(int n, const unsigned char* __restrict__ fixed, pg::Graph G, const lsa_pgo_edge_t* __restrict__ edges,
+                                                           const double* __restrict__ blocks, double lambda, double* __restrict__ D, double* __restrict__ dg,
+                                                           double* __restrict__ g, double* __restrict__ L, double* __restrict__ U)
+{
+  const int i = blockIdx.x * kThreads + threadIdx.x;
+  if (i >= n) return;
+  pg::assemble_row(i, n, fixed, G, edges, blocks, lambda, D + 36LL * i, dg + 6LL * i, g + 6LL * i, L + 36LL * i, U + 36LL * i);
+}
+
+// one level of the cyclic reduction at stride s
+__global__ __launch_bounds__(kThreads) void k_pgo_pcr_level(int n, int s, const double* __restrict__ Din, const double* __restrict__ Lin, const double* __restrict__ Uin,
+                                                            double* __restrict__ Dout, double* __restrict__ Lout, double* __restrict__ Uout, double* __restrict__ alpha,
+                                                            double* __restrict__ gamma, PgoState* st)
+{
+  const int i = blockIdx.x * kThreads + threadIdx.x;
+  if (i >= n) return;
+  const long long at = 36LL * i;
+  double Dn[36], X[36], T[36];
+  for (int k = 0; k < 36; ++k) Dn[k] = Din[at + k];
+  bool ok = true;
+  pg::Chol6 c;
+  if (i - s >= 0)
+  {
+    const long long lo = 36LL * (i - s);
+    ok = pg::chol6(Din + lo, c) && ok;
+    pg::chol6_right(c, Lin + at, X);
+    for (int k = 0; k < 36; ++k) X[k] = -X[k];
+    pg::mul6(X, Uin + lo, T);
+    for (int k = 0; k < 36; ++k) Dn[k] += T[k];
+    pg::mul6(X, Lin + lo, T);
+    for (int k = 0; k < 36; ++k) { alpha[at + k] = X[k]; Lout[at + k] = T[k]; }
+  }
+  else
+    for (int k = 0; k < 36; ++k) { alpha[at + k] = 0.; Lout[at + k] = 0.; }
+  if (i + s < n)
+  {
+    const long long hi = 36LL * (i + s);
+    ok = pg::chol6(Din + hi, c) && ok;
+    pg::chol6_right(c, Uin + at, X);
+    for (int k = 0; k < 36; ++k) X[k] = -X[k];
+    pg::mul6(X, Lin + hi, T);
+    for (int k = 0; k < 36; ++k) Dn[k] += T[k];
+    pg::mul6(X, Uin + hi, T);
+    for (int k = 0; k < 36; ++k) { gamma[at + k] = X[k]; Uout[at + k] = T[k]; }
+  }
+  else
+    for (int k = 0; k < 36; ++k) { gamma[at + k] = 0.; Uout[at + k] = 0.; }
+  for (int k = 0; k < 36; ++k) Dout[at + k] = Dn[k];
+  if (!ok) st->notspd = 1;  // every writer writes the same word
+}
+
+// the inverses of the last level's diagonal blocks
+__global__ __launch_bounds__(kThreads) void k_pgo_pcr_invert(int n, const double* __restrict__ D, double* __restrict__ Dinv, PgoState* st)
+{
+  const int i = blockIdx.x * kThreads + threadIdx.x;
+  if (i >= n) return;
+  pg::Chol6 c;
+  const bool ok = pg::chol6(D + 36LL * i, c);
+  for (int k = 0; k < 6; ++k)
+  {
+    double unit[6], col[6];
+    for (int j = 0; j < 6; ++j) unit[j] = j == k ? 1. : 0.;
+    pg::chol6_solve(c, unit, col);
+    for (int j = 0; j < 6; ++j) Dinv[36LL * i + j * 6 + k] = col[j];
+  }
+  if (!ok) st->notspd = 1;
+}
+
+__global__ __launch_bounds__(kThreads) void k_pgo_pcr_apply(int n, int s, const double* __restrict__ alpha, const double* __restrict__ gamma, const double* __restrict__ bin,
+                                                            double* __restrict__ bout)
+{
+  const int i = blockIdx.x * kThreads + threadIdx.x;
+  if (i >= n) return;
+  double acc[6], y[6];
+  for (int k = 0; k < 6; ++k) acc[k] = bin[6LL * i + k];
+  if (i - s >= 0)
+  {
+    pg::mulv6(alpha + 36LL * i, bin + 6LL * (i - s), y);
+    for (int k = 0; k < 6; ++k) acc[k] += y[k];
+  }
+  if (i + s < n)
+  {
+    pg::mulv6(gamma + 36LL * i, bin + 6LL * (i + s), y);
+    for (int k = 0; k < 6; ++k) acc[k] += y[k];
+  }
+  for (int k = 0; k < 6; ++k) bout[6LL * i + k] = acc[k];
+}
+
+__global__ __launch_bounds__(kThreads) void k_pgo_pcr_solve(int n, const double* __restrict__ Dinv, const double* __restrict__ b, double* __restrict__ x)
+{
+  const int i = blockIdx.x * kThreads + threadIdx.x;
+  if (i >= n) return;
+  double y[6];
+  pg::mulv6(Dinv + 36LL * i, b + 6LL * i, y);
+  for (int k = 0; k < 6; ++k) x[6LL * i + k] = y[k];
+}
+
+// the workgroup's sum by a fixed tree; every thread of the workgroup must call it
+__device__ double block_sum(double v, double* lds)
+{
+  lds[threadIdx.x] = v;
+  __syncthreads();
+  for (int off = kThreads / 2; off > 0; off >>= 1)
+  {
+    if ((int)threadIdx.x < off) lds[threadIdx.x] = lds[threadIdx.x] + lds[threadIdx.x + off];
+    __syncthreads();
+  }
+  const double r = lds[0];
+  __syncthreads();
+  return r;
+}
+__device__ double block_max(double v, double* lds)
+{
+  lds[threadIdx.x] = v;
+  __syncthreads();
+  for (int off = kThreads / 2; off > 0; off >>= 1)
+  {
+    if ((int)threadIdx.x < off) lds[threadIdx.x] = lds[threadIdx.x + off] > lds[threadIdx.x] ? lds[threadIdx.x + off] : lds[threadIdx.x];
+    __syncthreads();
+  }
+  const double r = lds[0];
+  __syncthreads();
+  return r;
+}
+
+__global__ __launch_bounds__(kThreads) void k_pgo_spmv(int n, pg::Graph G, const double* __restrict__ blocks, const double* __restrict__ D, const double* __restrict__ L,
+                                                       const double* __restrict__ U, const double* __restrict__ p, double* __restrict__ q, double* __restrict__ partials)
+{
+  __shared__ double lds[kThreads];
+  const int i = blockIdx.x * kThreads + threadIdx.x;
+  double d = 0.;
+  if (i < n)
+  {
+    double y[6];
+    pg::spmv_row(i, n, G, blocks, D, L, U, p, y);
+    for (int k = 0; k < 6; ++k) q[6LL * i + k] = y[k];
+    d = pg::dot6(p + 6LL * i, y);
+  }
+  const double s = block_sum(d, lds);
+  if (threadIdx.x == 0 && partials) partials[blockIdx.x] = s;
+}
+
+// partial sums of a.b over the rows of six
+__global__ __launch_bounds__(kThreads) void k_pgo_dot(int n, const double* __restrict__ a, const double* __restrict__ b, double* __restrict__ partials)
+{
+  __shared__ double lds[kThreads];
+  const int i = blockIdx.x * kThreads + threadIdx.x;
+  const double s = block_sum(i < n ? pg::dot6(a + 6LL * i, b + 6LL * i) : 0., lds);
+  if (threadIdx.x == 0) partials[blockIdx.x] = s;
+}
+// partial sums of v[0..m)
+__global__ __launch_bounds__(kThreads) void k_pgo_sum(int m, const double* __restrict__ v, double* __restrict__ partials)
+{
+  __shared__ double lds[kThreads];
+  const int i = blockIdx.x * kThreads + threadIdx.x;
+  const double s = block_sum(i < m ? v[i] : 0., lds);
+  if (threadIdx.x == 0) partials[blockIdx.x] = s;
+}
+// per workgroup: the model decrease's terms, max |delta|, max |g| (delta may be NULL: the gradient alone)
+__global__ __launch_bounds__(kThreads) void k_pgo_row_stats(int n, double lambda, const double* __restrict__ delta, const double* __restrict__ dg, const double* __restrict__ g,
+                                                            double* __restrict__ partials)
+{
+  __shared__ double lds[kThreads];
+  const int i = blockIdx.x * kThreads + threadIdx.x;
+  double model = 0., md = 0., mg = 0.;
+  if (i < n)
+    for (int k = 0; k < 6; ++k)
+    {
+      const double gk = g[6LL * i + k];
+      mg = __builtin_fabs(gk) > mg ? __builtin_fabs(gk) : mg;
+      if (delta)
+      {
+        const double dk = delta[6LL * i + k];
+        md = __builtin_fabs(dk) > md ? __builtin_fabs(dk) : md;
+        const double t = dk * (lambda * dg[6LL * i + k] * dk - gk);
+        model = k == 0 ? t : model + t;
+      }
+    }
+  const double a = block_sum(model, lds), b = block_max(md, lds), c = block_max(mg, lds);
+  if (threadIdx.x == 0)
+  {
+    partials[3LL * blockIdx.x] = a;
+    partials[3LL * blockIdx.x + 1] = b;
+    partials[3LL * blockIdx.x + 2] = c;
+  }
+}
+
+// the second level: one thread adds the partial sums in order and takes PCG's decisions
+enum { FIN_INIT = 0, FIN_PQ = 1, FIN_RZ = 2, FIN_STATS = 3, FIN_CHI2 = 4 };
+__global__ void k_pgo_finish(int what, int nb, const double* __restrict__ partials, double tol2, PgoState* st)
+{
+  if (blockIdx.x != 0 || threadIdx.x != 0) return;
+  if (what == FIN_STATS)
+  {
+    double model = 0., md = 0., mg = 0.;
+    for (int b = 0; b < nb; ++b)
+    {
+      model += partials[3LL * b];
+      md = partials[3LL * b + 1] > md ? partials[3LL * b + 1] : md;
+      mg = partials[3LL * b + 2] > mg ? partials[3LL * b + 2] : mg;
+    }
+    st->stat[0] = 0.5 * model;
+    st->stat[1] = md;
+    st->stat[2] = mg;
+    return;
+  }
+  double s = 0.;
+  for (int b = 0; b < nb; ++b) s += partials[b];
+  if (what == FIN_CHI2) { st->stat[3] = s; return; }
+  if (what == FIN_INIT)
+  {
+    st->rz = s;
+    st->rz0 = s;
+    st->iters = 0;
+    st->converged = s == 0. ? 1 : 0;
+    st->failed = (pg::finite_d(s) && s >= 0.) ? 0 : 1;
+    return;
+  }
+  if (st->failed || st->converged) return;
+  if (what == FIN_PQ)
+  {
+    st->pq = s;
+    st->iters = st->iters + 1;
+    if (!(s > 0.) || !pg::finite_d(s)) { st->failed = 1; st->alpha = 0.; }
+    else st->alpha = st->rz / s;
+    return;
+  }
+  // FIN_RZ
+  if (!pg::finite_d(s)) { st->failed = 1; st->beta = 0.; return; }
+  if (s <= tol2 * st->rz0) { st->converged = 1; st->beta = 0.; return; }
+  st->beta = s / st->rz;
+  st->rz = s;
+}
+
+__global__ __launch_bounds__(kThreads) void k_pgo_pcg_start(long long nv, const double* __restrict__ g, double* __restrict__ delta, double* __restrict__ r)
+{
+  const long long k = (long long)blockIdx.x * kThreads + threadIdx.x;
+  if (k >= nv) return;
+  delta[k] = 0.;
+  r[k] = -g[k];
+}
+__global__ __launch_bounds__(kThreads) void k_pgo_axpy(long long nv, const PgoState* __restrict__ st, const double* __restrict__ p, const double* __restrict__ q,
+                                                       double* __restrict__ delta, double* __restrict__ r)
+{
+  const long long k = (long long)blockIdx.x * kThreads + threadIdx.x;
+  if (k >= nv || st->failed || st->converged) return;
+  const double a = st->alpha;
+  delta[k] += a * p[k];
+  r[k] -= a * q[k];
+}
+__global__ __launch_bounds__(kThreads) void k_pgo_update_p(long long nv, const PgoState* __restrict__ st, const double* __restrict__ z, double* __restrict__ p)
+{
+  const long long k = (long long)blockIdx.x * kThreads + threadIdx.x;
+  if (k >= nv || st->failed || st->converged) return;
+  p[k] = z[k] + st->beta * p[k];
+}
+__global__ __launch_bounds__(kThreads) void k_pgo_retract(int n, const double* __restrict__ poses, const double* __restrict__ delta, double* __restrict__ cand)
+{
+  const int i = blockIdx.x * kThreads + threadIdx.x;
+  if (i >= n) return;
+  pg::store(pg::retract(pg::load(poses + 16LL * i), delta + 6LL * i), cand + 16LL * i);
+}
+
+int ensure(lsa_ctx* ctx, PgoBuf& b, size_t bytes)
+{
+  if (bytes <= b.cap) return LSA_OK;
+  retire_dev(ctx, b.p);
+  b.p = nullptr;
+  b.cap = 0;
+  const size_t cap = bytes + bytes / 2;
+  LSA_HIP(ctx, hipMalloc(&b.p, cap));
+  b.cap = cap;
+  return LSA_OK;
+}
+template <typename T> T* ptr_of(const PgoBuf& b) { return static_cast<T*>(b.p); }
+
+int levels_of(int n)
+{
+  int nl = 0;
+  for (long long s = 1; s < n; s *= 2) ++nl;
+  return nl;
+}
+
+// the vectors of PCG, 6 n doubles each
+enum { V_DELTA = 0, V_R, V_Z, V_P, V_Q, V_T0, V_T1, V_COUNT };
+
+struct Problem
+{
+  lsa_ctx* ctx;
+  PgoBuffers* B;
+  int n = 0, m = 0, nl = 0, nb = 0;
+  bool haveGraph = false;
+  pg::Graph G{};
+  double* vec(int k) const { return ptr_of<double>(B->vec) + 6LL * n * k; }
+  PgoState* state() const { return ptr_of<PgoState>(B->state); }
+};
+
+#define PGO_TRY(call)                \
+  do                                 \
+  {                                  \
+    const int rc__ = (call);         \
+    if (rc__ != LSA_OK) return rc__; \
+  } while (0)
+
+// buffers for n poses and m edges; poses, edges (and the graph, when given) uploaded
+int setup(Problem& P, lsa_ctx* ctx, const double* poses16, int n, const unsigned char* fixed, const lsa_pgo_edge_t* edges, int m, const host::PoseGraph* G)
+{
+  LSA_HIP(ctx, hipSetDevice(ctx->device));
+  if (!ctx->pgo) ctx->pgo = new PgoBuffers;
+  PgoBuffers* B = ctx->pgo;
+  P.ctx = ctx;
+  P.B = B;
+  P.n = n;
+  P.m = m;
+  P.nl = levels_of(n);
+  P.nb = (int)blocks_for(std::max(n, m));
+  const size_t n36 = (size_t)n * 36 * sizeof(double), n6 = (size_t)n * 6 * sizeof(double);
+  PGO_TRY(ensure(ctx, B->poses, (size_t)n * 16 * sizeof(double)));
+  PGO_TRY(ensure(ctx, B->cand, (size_t)n * 16 * sizeof(double)));
+  PGO_TRY(ensure(ctx, B->edges, std::max<size_t>(1, (size_t)m) * sizeof(lsa_pgo_edge_t)));
+  PGO_TRY(ensure(ctx, B->fixed, (size_t)n));
+  PGO_TRY(ensure(ctx, B->row_start, ((size_t)n + 1) * sizeof(int)));
+  PGO_TRY(ensure(ctx, B->loop_start, ((size_t)n + 1) * sizeof(int)));
+  PGO_TRY(ensure(ctx, B->inc, std::max<size_t>(1, (size_t)2 * m) * sizeof(int)));
+  PGO_TRY(ensure(ctx, B->loop_edge, std::max<size_t>(1, (size_t)2 * m) * sizeof(int)));
+  PGO_TRY(ensure(ctx, B->loop_col, std::max<size_t>(1, (size_t)2 * m) * sizeof(int)));
+  PGO_TRY(ensure(ctx, B->e, std::max<size_t>(1, (size_t)m) * 6 * sizeof(double)));
+  PGO_TRY(ensure(ctx, B->blocks, std::max<size_t>(1, (size_t)m) * pg::kEdgeBlock * sizeof(double)));
+  PGO_TRY(ensure(ctx, B->chi2, std::max<size_t>(1, (size_t)m) * sizeof(double)));
+  PGO_TRY(ensure(ctx, B->D, n36));
+  PGO_TRY(ensure(ctx, B->L, n36));
+  PGO_TRY(ensure(ctx, B->U, n36));
+  PGO_TRY(ensure(ctx, B->dg, n6));
+  PGO_TRY(ensure(ctx, B->g, n6));
+  PGO_TRY(ensure(ctx, B->work[0], 3 * n36));
+  PGO_TRY(ensure(ctx, B->work[1], 3 * n36));
+  PGO_TRY(ensure(ctx, B->alpha, std::max(1, P.nl) * n36));
+  PGO_TRY(ensure(ctx, B->gamma, std::max(1, P.nl) * n36));
+  PGO_TRY(ensure(ctx, B->Dinv, n36));
+  PGO_TRY(ensure(ctx, B->vec, V_COUNT * n6));
+  PGO_TRY(ensure(ctx, B->partials, (size_t)3 * P.nb * sizeof(double)));
+  PGO_TRY(ensure(ctx, B->state, sizeof(PgoState)));
+  if (!B->host) LSA_HIP(ctx, hipHostMalloc((void**)&B->host, sizeof(PgoState), hipHostMallocDefault));
+  hipStream_t st = ctx->stream;
+  LSA_HIP(ctx, hipMemsetAsync(B->state.p, 0, sizeof(PgoState), st));
+  if (poses16) LSA_HIP(ctx, hipMemcpyAsync(B->poses.p, poses16, (size_t)n * 16 * sizeof(double), hipMemcpyHostToDevice, st));
+  if (m > 0 && edges) LSA_HIP(ctx, hipMemcpyAsync(B->edges.p, edges, (size_t)m * sizeof(lsa_pgo_edge_t), hipMemcpyHostToDevice, st));
+  if (fixed) LSA_HIP(ctx, hipMemcpyAsync(B->fixed.p, fixed, (size_t)n, hipMemcpyHostToDevice, st));
+  P.haveGraph = G != nullptr;
+  if (G)
+  {
+    LSA_HIP(ctx, hipMemcpyAsync(B->row_start.p, G->row_start.data(), ((size_t)n + 1) * sizeof(int), hipMemcpyHostToDevice, st));
+    LSA_HIP(ctx, hipMemcpyAsync(B->loop_start.p, G->loop_start.data(), ((size_t)n + 1) * sizeof(int), hipMemcpyHostToDevice, st));
+    if (!G->inc.empty()) LSA_HIP(ctx, hipMemcpyAsync(B->inc.p, G->inc.data(), G->inc.size() * sizeof(int), hipMemcpyHostToDevice, st));
+    if (!G->loop_edge.empty())
+    {
+      LSA_HIP(ctx, hipMemcpyAsync(B->loop_edge.p, G->loop_edge.data(), G->loop_edge.size() * sizeof(int), hipMemcpyHostToDevice, st));
+      LSA_HIP(ctx, hipMemcpyAsync(B->loop_col.p, G->loop_col.data(), G->loop_col.size() * sizeof(int), hipMemcpyHostToDevice, st));
+    }
+    P.G = pg::Graph{ptr_of<int>(B->row_start), ptr_of<int>(B->inc), ptr_of<int>(B->loop_start), ptr_of<int>(B->loop_edge), ptr_of<int>(B->loop_col)};
+  }
+  return LSA_OK;
+}
+
+int launch_linearize(const Problem& P, const double* poses)
+{
+  if (P.m == 0) return LSA_OK;
+  ProfScope ps(P.ctx, "pgo_linearize", (double)P.m * (sizeof(lsa_pgo_edge_t) + (pg::kEdgeBlock + 7) * 8.));
+  hipLaunchKernelGGL(k_pgo_linearize, dim3(blocks_for(P.m)), dim3(kThreads), 0, P.ctx->stream, poses, ptr_of<lsa_pgo_edge_t>(P.B->edges), P.m, ptr_of<double>(P.B->e),
+                     ptr_of<double>(P.B->blocks), ptr_of<double>(P.B->chi2));
+  LSA_HIP(P.ctx, hipGetLastError());
+  return LSA_OK;
+}
+// sum of chi2 into stat[3]
+int launch_cost(const Problem& P)
+{
+  const int nb = (int)blocks_for(P.m);
+  hipLaunchKernelGGL(k_pgo_sum, dim3(nb), dim3(kThreads), 0, P.ctx->stream, P.m, ptr_of<double>(P.B->chi2), ptr_of<double>(P.B->partials));
+  hipLaunchKernelGGL(k_pgo_finish, dim3(1), dim3(64), 0, P.ctx->stream, (int)FIN_CHI2, nb, ptr_of<double>(P.B->partials), 0., P.state());
+  LSA_HIP(P.ctx, hipGetLastError());
+  return LSA_OK;
+}
+int launch_assemble(const Problem& P, double lambda)
+{
+  ProfScope ps(P.ctx, "pgo_assemble", (double)P.n * (36 * 3 + 12) * 8. + (double)P.m * 2 * pg::kEdgeBlock * 8.);
+  hipLaunchKernelGGL(k_pgo_assemble, dim3(blocks_for(P.n)), dim3(kThreads), 0, P.ctx->stream, P.n, ptr_of<unsigned char>(P.B->fixed), P.G, ptr_of<lsa_pgo_edge_t>(P.B->edges),
+                     ptr_of<double>(P.B->blocks), lambda, ptr_of<double>(P.B->D), ptr_of<double>(P.B->dg), ptr_of<double>(P.B->g), ptr_of<double>(P.B->L),
+                     ptr_of<double>(P.B->U));
+  LSA_HIP(P.ctx, hipGetLastError());
+  return LSA_OK;
+}
+// the cyclic reduction of (D, L, U): alpha / gamma per level and the last level's inverses; diagonalOnly: T = the D blocks
+int launch_factor(const Problem& P, bool diagonalOnly)
+{
+  const int n = P.n;
+  const long long n36 = 36LL * n;
+  ProfScope ps(P.ctx, "pgo_factor", (double)(diagonalOnly ? 0 : P.nl) * n36 * 8. * 8 + n36 * 16.);
+  const double* D = ptr_of<double>(P.B->D);
+  const double* L = ptr_of<double>(P.B->L);
+  const double* U = ptr_of<double>(P.B->U);
+  int level = 0;
+  if (!diagonalOnly)
+    for (long long s = 1; s < n; s *= 2, ++level)
+    {
+      double* out = ptr_of<double>(P.B->work[level & 1]);
+      hipLaunchKernelGGL(k_pgo_pcr_level, dim3(blocks_for(n)), dim3(kThreads), 0, P.ctx->stream, n, (int)s, D, L, U, out, out + n36, out + 2 * n36,
+                         ptr_of<double>(P.B->alpha) + level * n36, ptr_of<double>(P.B->gamma) + level * n36, P.state());
+      D = out;
+      L = out + n36;
+      U = out + 2 * n36;
+    }
+  hipLaunchKernelGGL(k_pgo_pcr_invert, dim3(blocks_for(n)), dim3(kThreads), 0, P.ctx->stream, n, D, ptr_of<double>(P.B->Dinv), P.state());
+  LSA_HIP(P.ctx, hipGetLastError());
+  return LSA_OK;
+}
+// x = T^-1 b (b is kept)
+int launch_apply(const Problem& P, bool diagonalOnly, const double* b, double* x)
+{
+  const int n = P.n;
+  const long long n36 = 36LL * n;
+  ProfScope ps(P.ctx, "pgo_apply", (double)((diagonalOnly ? 0 : P.nl) * 2 + 1) * (n36 + 12LL * n) * 8.);
+  const double* in = b;
+  int level = 0;
+  if (!diagonalOnly)
+    for (long long s = 1; s < n; s *= 2, ++level)
+    {
+      double* out = P.vec(V_T0 + (level & 1));
+      hipLaunchKernelGGL(k_pgo_pcr_apply, dim3(blocks_for(n)), dim3(kThreads), 0, P.ctx->stream, n, (int)s, ptr_of<double>(P.B->alpha) + level * n36,
+                         ptr_of<double>(P.B->gamma) + level * n36, in, out);
+      in = out;
+    }
+  hipLaunchKernelGGL(k_pgo_pcr_solve, dim3(blocks_for(n)), dim3(kThreads), 0, P.ctx->stream, n, ptr_of<double>(P.B->Dinv), in, x);
+  LSA_HIP(P.ctx, hipGetLastError());
+  return LSA_OK;
+}
+int launch_spmv(const Problem& P, const double* p, double* q, double* partials)
+{
+  ProfScope ps(P.ctx, "pgo_spmv", (double)P.n * (36 * 3 + 12) * 8.);
+  hipLaunchKernelGGL(k_pgo_spmv, dim3(blocks_for(P.n)), dim3(kThreads), 0, P.ctx->stream, P.n, P.G, ptr_of<double>(P.B->blocks), ptr_of<double>(P.B->D),
+                     ptr_of<double>(P.B->L), ptr_of<double>(P.B->U), p, q, partials);
+  LSA_HIP(P.ctx, hipGetLastError());
+  return LSA_OK;
+}
+int finish(const Problem& P, int what, int nb, double tol2)
+{
+  hipLaunchKernelGGL(k_pgo_finish, dim3(1), dim3(64), 0, P.ctx->stream, what, nb, ptr_of<double>(P.B->partials), tol2, P.state());
+  LSA_HIP(P.ctx, hipGetLastError());
+  return LSA_OK;
+}
+int read_state(const Problem& P, PgoState* out)
+{
+  LSA_HIP(P.ctx, hipMemcpyAsync(P.B->host, P.B->state.p, sizeof(PgoState), hipMemcpyDeviceToHost, P.ctx->stream));
+  LSA_HIP(P.ctx, hipStreamSynchronize(P.ctx->stream));
+  *out = *P.B->host;
+  return LSA_OK;
+}
+int download(lsa_ctx* ctx, void* dst, const void* src, size_t bytes)
+{
+  if (bytes) LSA_HIP(ctx, hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, ctx->stream));
+  return LSA_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int lsa_pgo_linearize(lsa_ctx* ctx, const double* poses16, int n, const lsa_pgo_edge_t* edges, int m, double* e_out, double* blocks_out, double* chi2_out)
+{
+  if (!ctx) return LSA_E_ARG;
+  std::string why = "bad argument";
+  if (!e_out || !blocks_out || !chi2_out || host::PgoCheckEdges(poses16, n, edges, m, &why) != LSA_OK) return ctx->fail(LSA_E_ARG, "lsa_pgo_linearize: " + why);
+  if (n > kMaxPoses) return ctx->fail(LSA_E_CAPACITY, "lsa_pgo_linearize: more than 262144 poses");
+  Problem P;
+  PGO_TRY(setup(P, ctx, poses16, n, nullptr, edges, m, nullptr));
+  PGO_TRY(launch_linearize(P, ptr_of<double>(P.B->poses)));
+  PGO_TRY(download(ctx, e_out, P.B->e.p, (size_t)m * 6 * sizeof(double)));
+  PGO_TRY(download(ctx, blocks_out, P.B->blocks.p, (size_t)m * pg::kEdgeBlock * sizeof(double)));
+  PGO_TRY(download(ctx, chi2_out, P.B->chi2.p, (size_t)m * sizeof(double)));
+  LSA_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return LSA_OK;
+}
+
+int lsa_pgo_assemble(lsa_ctx* ctx, const double* poses16, int n, const uint8_t* fixed, const lsa_pgo_edge_t* edges, int m, double lambda, double* D_out, double* g_out,
+                     double* L_out, double* U_out)
+{
+  if (!ctx) return LSA_E_ARG;
+  std::string why = "bad argument";
+  host::PoseGraph G;
+  if (!D_out || !g_out || !L_out || !U_out || !(lambda >= 0.) || !pg::finite_d(lambda) || host::PgoBuild(poses16, n, fixed, edges, m, &G, &why) != LSA_OK)
+    return ctx->fail(LSA_E_ARG, "lsa_pgo_assemble: " + why);
+  if (n > kMaxPoses) return ctx->fail(LSA_E_CAPACITY, "lsa_pgo_assemble: more than 262144 poses");
+  Problem P;
+  PGO_TRY(setup(P, ctx, poses16, n, fixed, edges, m, &G));
+  PGO_TRY(launch_linearize(P, ptr_of<double>(P.B->poses)));
+  PGO_TRY(launch_assemble(P, lambda));
+  const size_t n36 = (size_t)n * 36 * sizeof(double);
+  PGO_TRY(download(ctx, D_out, P.B->D.p, n36));
+  PGO_TRY(download(ctx, g_out, P.B->g.p, (size_t)n * 6 * sizeof(double)));
+  PGO_TRY(download(ctx, L_out, P.B->L.p, n36));
+  PGO_TRY(download(ctx, U_out, P.B->U.p, n36));
+  LSA_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return LSA_OK;
+}
+
+int lsa_pgo_spmv(lsa_ctx* ctx, const double* poses16, int n, const uint8_t* fixed, const lsa_pgo_edge_t* edges, int m, double lambda, const double* p, double* q)
+{
+  if (!ctx) return LSA_E_ARG;
+  std::string why = "bad argument";
+  host::PoseGraph G;
+  if (!p || !q || !(lambda >= 0.) || !pg::finite_d(lambda) || host::PgoBuild(poses16, n, fixed, edges, m, &G, &why) != LSA_OK)
+    return ctx->fail(LSA_E_ARG, "lsa_pgo_spmv: " + why);
+  if (n > kMaxPoses) return ctx->fail(LSA_E_CAPACITY, "lsa_pgo_spmv: more than 262144 poses");
+  Problem P;
+  PGO_TRY(setup(P, ctx, poses16, n, fixed, edges, m, &G));
+  PGO_TRY(launch_linearize(P, ptr_of<double>(P.B->poses)));
+  PGO_TRY(launch_assemble(P, lambda));
+  LSA_HIP(ctx, hipMemcpyAsync(P.vec(V_P), p, (size_t)n * 6 * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+  PGO_TRY(launch_spmv(P, P.vec(V_P), P.vec(V_Q), nullptr));
+  PGO_TRY(download(ctx, q, P.vec(V_Q), (size_t)n * 6 * sizeof(double)));
+  LSA_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return LSA_OK;
+}
+
+int lsa_pgo_retract(lsa_ctx* ctx, const double* poses16, int n, const double* delta, double* poses_out)
+{
+  if (!ctx) return LSA_E_ARG;
+  if (!poses16 || !delta || !poses_out || n < 1) return ctx->fail(LSA_E_ARG, "lsa_pgo_retract: bad argument");
+  if (n > kMaxPoses) return ctx->fail(LSA_E_CAPACITY, "lsa_pgo_retract: more than 262144 poses");
+  Problem P;
+  PGO_TRY(setup(P, ctx, poses16, n, nullptr, nullptr, 0, nullptr));
+  LSA_HIP(ctx, hipMemcpyAsync(P.vec(V_DELTA), delta, (size_t)n * 6 * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+  hipLaunchKernelGGL(k_pgo_retract, dim3(blocks_for(n)), dim3(kThreads), 0, ctx->stream, n, ptr_of<double>(P.B->poses), P.vec(V_DELTA), ptr_of<double>(P.B->cand));
+  LSA_HIP(ctx, hipGetLastError());
+  std::vector<double> out((size_t)n * 16);
+  PGO_TRY(download(ctx, out.data(), P.B->cand.p, out.size() * sizeof(double)));
+  LSA_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  std::memcpy(poses_out, out.data(), out.size() * sizeof(double));
+  return LSA_OK;
+}
+
+int lsa_pgo_tridiagonal_solve(lsa_ctx* ctx, int n, const double* D, const double* L, const double* U, const double* b, double* x)
+{
+  if (!ctx) return LSA_E_ARG;
+  if (n < 1 || !D || !L || !U || !b || !x) return ctx->fail(LSA_E_ARG, "lsa_pgo_tridiagonal_solve: bad argument");
+  if (n > kMaxPoses) return ctx->fail(LSA_E_CAPACITY, "lsa_pgo_tridiagonal_solve: more than 262144 rows");
+  Problem P;
+  PGO_TRY(setup(P, ctx, nullptr, n, nullptr, nullptr, 0, nullptr));
+  const size_t n36 = (size_t)n * 36 * sizeof(double);
+  hipStream_t st = ctx->stream;
+  LSA_HIP(ctx, hipMemcpyAsync(P.B->D.p, D, n36, hipMemcpyHostToDevice, st));
+  LSA_HIP(ctx, hipMemcpyAsync(P.B->L.p, L, n36, hipMemcpyHostToDevice, st));
+  LSA_HIP(ctx, hipMemcpyAsync(P.B->U.p, U, n36, hipMemcpyHostToDevice, st));
+  LSA_HIP(ctx, hipMemcpyAsync(P.vec(V_R), b, (size_t)n * 6 * sizeof(double), hipMemcpyHostToDevice, st));
+  PGO_TRY(launch_factor(P, false));
+  PGO_TRY(launch_apply(P, false, P.vec(V_R), P.vec(V_Z)));
+  PgoState s;
+  PGO_TRY(read_state(P, &s));
+  if (s.notspd) return 1;
+  std::vector<double> out((size_t)n * 6);
+  PGO_TRY(download(ctx, out.data(), P.vec(V_Z), out.size() * sizeof(double)));
+  LSA_HIP(ctx, hipStreamSynchronize(st));
+  for (double v : out)
+    if (!pg::finite_d(v)) return 1;
+  std::memcpy(x, out.data(), out.size() * sizeof(double));
+  return LSA_OK;
+}
+
+int lsa_pgo_solve(lsa_ctx* ctx, const double* poses16, int n, const uint8_t* fixed, const lsa_pgo_edge_t* edges, int m, const lsa_pgo_params_t* params, double* poses_out,
+                  lsa_pgo_result_t* result)
+{
+  if (!ctx) return LSA_E_ARG;
+  lsa_pgo_params_t p;
+  lsa_pgo_params_init(&p);
+  if (params) p = *params;
+  if (!poses_out || !result || !pg::params_ok(p)) return ctx->fail(LSA_E_ARG, "lsa_pgo_solve: bad argument or parameters out of limits");
+  std::string why;
+  host::PoseGraph G;
+  if (const int rc = host::PgoBuild(poses16, n, fixed, edges, m, &G, &why); rc != LSA_OK) return ctx->fail(rc, "lsa_pgo_solve: " + why);
+  if (n > kMaxPoses) return ctx->fail(LSA_E_CAPACITY, "lsa_pgo_solve: more than 262144 poses (the cyclic reduction keeps every level)");
+  Problem P;
+  PGO_TRY(setup(P, ctx, poses16, n, fixed, edges, m, &G));
+  hipStream_t st = ctx->stream;
+  const long long nv = 6LL * n;
+  const bool diag = p.preconditioner == 1;
+  double* x = ptr_of<double>(P.B->poses);
+  double* cand = ptr_of<double>(P.B->cand);
+  double* partials = ptr_of<double>(P.B->partials);
+  const int nbn = (int)blocks_for(n);
+  PgoState s;
+  lsa_pgo_result_t R;
+  std::memset(&R, 0, sizeof(R));
+  PGO_TRY(launch_linearize(P, x));
+  PGO_TRY(launch_cost(P));
+  PGO_TRY(read_state(P, &s));
+  double F = 0.5 * s.stat[3];
+  R.initial_cost = F;
+  double lambda = p.initial_lambda;
+  int term = LSA_PGO_MAX_ITERATIONS;
+  for (int it = 0; it < p.max_iterations; ++it)
+  {
+    R.iterations = it + 1;
+    LSA_HIP(ctx, hipMemsetAsync(P.B->state.p, 0, sizeof(PgoState), st));
+    PGO_TRY(launch_assemble(P, lambda));
+    hipLaunchKernelGGL(k_pgo_row_stats, dim3(nbn), dim3(kThreads), 0, st, n, lambda, (const double*)nullptr, ptr_of<double>(P.B->dg), ptr_of<double>(P.B->g), partials);
+    PGO_TRY(finish(P, FIN_STATS, nbn, 0.));
+    // the factorization and PCG's start are enqueued behind the gradient's norm: one wait for all of them
+    PGO_TRY(launch_factor(P, diag));
+    hipLaunchKernelGGL(k_pgo_pcg_start, dim3(blocks_for(nv)), dim3(kThreads), 0, st, nv, ptr_of<double>(P.B->g), P.vec(V_DELTA), P.vec(V_R));
+    PGO_TRY(launch_apply(P, diag, P.vec(V_R), P.vec(V_Z)));
+    LSA_HIP(ctx, hipMemcpyAsync(P.vec(V_P), P.vec(V_Z), (size_t)nv * sizeof(double), hipMemcpyDeviceToDevice, st));
+    hipLaunchKernelGGL(k_pgo_dot, dim3(nbn), dim3(kThreads), 0, st, n, P.vec(V_R), P.vec(V_Z), partials);
+    PGO_TRY(finish(P, FIN_INIT, nbn, 0.));
+    PGO_TRY(read_state(P, &s));
+    if (s.stat[2] <= p.gradient_tolerance) { term = LSA_PGO_GRADIENT; break; }
+    if (s.notspd) { term = LSA_PGO_LINEAR_SOLVER_FAILED; break; }
+    int iters = 0;
+    while (!s.converged && !s.failed && iters < p.pcg_max_iter)
+    {
+      ++iters;
+      PGO_TRY(launch_spmv(P, P.vec(V_P), P.vec(V_Q), partials));
+      PGO_TRY(finish(P, FIN_PQ, nbn, 0.));
+      hipLaunchKernelGGL(k_pgo_axpy, dim3(blocks_for(nv)), dim3(kThreads), 0, st, nv, P.state(), P.vec(V_P), P.vec(V_Q), P.vec(V_DELTA), P.vec(V_R));
+      PGO_TRY(launch_apply(P, diag, P.vec(V_R), P.vec(V_Z)));
+      hipLaunchKernelGGL(k_pgo_dot, dim3(nbn), dim3(kThreads), 0, st, n, P.vec(V_R), P.vec(V_Z), partials);
+      PGO_TRY(finish(P, FIN_RZ, nbn, p.pcg_tolerance * p.pcg_tolerance));
+      hipLaunchKernelGGL(k_pgo_update_p, dim3(blocks_for(nv)), dim3(kThreads), 0, st, nv, P.state(), P.vec(V_Z), P.vec(V_P));
+      PGO_TRY(read_state(P, &s));
+    }
+    R.pcg_iterations += iters;
+    R.last_pcg_iterations = iters;
+    if (s.failed) { term = LSA_PGO_LINEAR_SOLVER_FAILED; break; }
+    if (!s.converged) ++R.pcg_truncated;
+    hipLaunchKernelGGL(k_pgo_row_stats, dim3(nbn), dim3(kThreads), 0, st, n, lambda, P.vec(V_DELTA), ptr_of<double>(P.B->dg), ptr_of<double>(P.B->g), partials);
+    PGO_TRY(finish(P, FIN_STATS, nbn, 0.));
+    hipLaunchKernelGGL(k_pgo_retract, dim3(nbn), dim3(kThreads), 0, st, n, x, P.vec(V_DELTA), cand);
+    if (m > 0) hipLaunchKernelGGL(k_pgo_chi2, dim3(blocks_for(m)), dim3(kThreads), 0, st, cand, ptr_of<lsa_pgo_edge_t>(P.B->edges), m, ptr_of<double>(P.B->chi2));
+    PGO_TRY(launch_cost(P));
+    PGO_TRY(read_state(P, &s));
+    const double model = s.stat[0], step = s.stat[1], Fn = 0.5 * s.stat[3];
+    if (model > 0. && pg::finite_d(Fn) && F - Fn > 0.)
+    {
+      const double dec = F - Fn;
+      std::swap(x, cand);
+      const bool small = dec <= p.cost_tolerance * F;
+      PGO_TRY(launch_linearize(P, x));
+      PGO_TRY(launch_cost(P));
+      PGO_TRY(read_state(P, &s));
+      F = 0.5 * s.stat[3];
+      ++R.accepted_steps;
+      R.largest_step = step > R.largest_step ? step : R.largest_step;
+      lambda = lambda * p.lambda_shrink > p.lambda_min ? lambda * p.lambda_shrink : p.lambda_min;
+      if (step <= p.step_tolerance) { term = LSA_PGO_STEP; break; }
+      if (small) { term = LSA_PGO_COST; break; }
+    }
+    else
+    {
+      ++R.rejected_steps;
+      lambda *= p.lambda_grow;
+      if (step <= p.step_tolerance) { term = LSA_PGO_STEP; break; }
+      if (lambda > p.lambda_max) { term = LSA_PGO_LAMBDA_CEILING; break; }
+    }
+  }
+  R.final_cost = F;
+  R.final_lambda = lambda;
+  R.termination = term;
+  R.message = host::PgoMessage(term);
+  std::vector<double> out((size_t)n * 16);
+  PGO_TRY(download(ctx, out.data(), x, out.size() * sizeof(double)));
+  LSA_HIP(ctx, hipStreamSynchronize(st));
+  std::memcpy(poses_out, out.data(), out.size() * sizeof(double));
+  *result = R;
+  return LSA_OK;
+}
+
+}  // extern "C"

@@ -15,7 +15,8 @@
 // Beyond the per-frame path the mirror also carries PCD map IO, the wheel odometer / IMU gravity constraints, the keypoint
 // log (SetLoggingTimeout, SetLoggingStorage, GetLoggedKeypoints) and SetTrajectoryAndRebuildMaps, which brings a corrected
 // trajectory back, and the loop-closure constraint an optimizer needs as input: FindLoopClosureCandidate and
-// RegisterLoggedFrames.  The pose-graph OPTIMIZER itself (g2o) is not part of this build: RunPoseGraphOptimization is present
+// RegisterLoggedFrames.  OptimizeLoggedTrajectory optimizes the logged trajectory with such edges on the device.  The reference's
+// pose-graph OPTIMIZER with GPS positions (g2o) is not part of this build: RunPoseGraphOptimization is present
 // with the reference's signature, warns once and changes nothing.
 #pragma once
 #include <algorithm>
@@ -356,6 +357,46 @@ public:
     this->LastError = rc < 0 ? std::string("RecognizePlace: ") + lsa_slam_last_error(this->Handle) : std::string();
     found.resize(static_cast<std::size_t>(rc > 0 ? rc : 0));
     return found;
+  }
+  // ---- pose-graph optimization of the logged trajectory on the device (lsa_slam_optimize_logged_trajectory): the odometry
+  // chain of the log, pose 0 fixed, plus the loop edges given -- LoopClosureEdge(revisited, query, registration) makes one from
+  // what RegisterLoggedFrames returned.  Returns the optimized poses with their logged times (empty when it cannot:
+  // GetLastError() says why and summary->termination is the negative LSA_E_* code); with params.apply != 0 they have gone through
+  // SetTrajectoryAndRebuildMaps as well, with 0 nothing the frame path reads is touched.  RunPoseGraphOptimization above, the
+  // reference's entry point with GPS positions, is not this and stays as it is.
+  using PoseGraphEdge = lsa_pgo_edge_t;
+  using PoseGraphParameters = lsa_pgo_params_t;
+  using PoseGraphSummary = lsa_pgo_result_t;
+  static PoseGraphParameters DefaultPoseGraphParameters()
+  {
+    PoseGraphParameters p;
+    lsa_pgo_params_init(&p);
+    return p;
+  }
+  // information = inverse(registration.covariance); false when that is not positive definite (the edge is left zeroed)
+  static bool LoopClosureEdge(std::size_t revisited, std::size_t query, const LoopClosureRegistration& registration, PoseGraphEdge& edge)
+  {
+    std::memset(&edge, 0, sizeof(edge));
+    edge.from = static_cast<int>(revisited);
+    edge.to = static_cast<int>(query);
+    std::memcpy(edge.relative, registration.relative, sizeof(edge.relative));
+    return lsa_pgo_information_from_covariance(registration.covariance, edge.information) == 0;
+  }
+  std::vector<Transform> OptimizeLoggedTrajectory(const std::vector<PoseGraphEdge>& loopEdges, const PoseGraphParameters& params = DefaultPoseGraphParameters(),
+                                                  PoseGraphSummary* summary = nullptr)
+  {
+    std::vector<Transform> poses = this->GetTrajectory();
+    std::vector<double> rows((poses.size() + 1) * 17);
+    PoseGraphSummary result;
+    std::memset(&result, 0, sizeof(result));
+    const int rc = lsa_slam_optimize_logged_trajectory(this->Handle, loopEdges.empty() ? nullptr : loopEdges.data(), static_cast<int>(loopEdges.size()), &params, rows.data(),
+                                                       static_cast<int>(poses.size()), &result);
+    this->LastError = rc < 0 ? std::string("OptimizeLoggedTrajectory: ") + lsa_slam_last_error(this->Handle) : std::string();
+    if (rc < 0) result.termination = rc;
+    if (summary) *summary = result;
+    if (rc < 0) return {};
+    for (std::size_t i = 0; i < poses.size(); ++i) std::memcpy(poses[i].matrix.data(), rows.data() + 17 * i, 16 * sizeof(double));
+    return poses;
   }
   // The logged frame to try a loop closure of `query` against BY POSITION: among the frames at least minTravelled metres
   // back along GetTrajectory() and within maxDistance metres of query's position, the nearest; -1 when there is none.  Host

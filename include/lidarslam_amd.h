@@ -32,7 +32,6 @@ extern "C" {
 #define LSA_E_ARG (-3)
 #define LSA_E_STATE (-4)
 #define LSA_E_CAPACITY (-5)
-#define LSA_E_GATE (-6) /* an ICP iteration enqueued ahead did not run: its gate gave up waiting for the host (lsa_icp_gate) */
 
 /* Keypoint types -- slam_lib/include/LidarSlam/Enums.h:30-36 */
 #define LSA_EDGE 0
@@ -223,8 +222,9 @@ int lsa_unpin_host_memory(void* ptr);
  * sample of its contents is compared (lsa_upload_frame_adopt then returns 0 and the caller uploads). */
 int lsa_upload_frame_forget(lsa_ctx* ctx);
 /* Frees the buffers the context has outgrown since the last call.  Growth never frees on the spot: hipFree waits for the
- * whole device, also for an ICP iteration that waits on the device for this very process (lsa_icp_gate).  Call it where
- * nothing of the context waits on the device for the host -- the pipeline does at the start of every AddFrame. */
+ * whole device with the runtime's lock held, which stalls every thread that enqueues, and retiring a buffer instead lets
+ * growth go without a stream synchronise (launches in flight keep the old buffer).  The pipeline calls it at the start of
+ * every AddFrame. */
 int lsa_collect_garbage(lsa_ctx* ctx);
 int lsa_uploads_adopted(const lsa_ctx* ctx);
 int lsa_extract_prefetch_uploaded(lsa_ctx* ctx, const lsa_extract_params_t* params);
@@ -448,46 +448,39 @@ typedef struct lsa_solve_result
 } lsa_solve_result_t;
 int lsa_solve_device(lsa_ctx* ctx, unsigned type_mask, const double prior[6], int two_d_mode, int lm_max_iter, int min_matches,
                      lsa_solve_result_t* out);
-/* lsa_solve_device in two halves: _begin enqueues the solve (prior == NULL: the start point is the one the gate in
- * front of it will hand over, see lsa_icp_gate), _end waits for the result of the oldest solve begun and not ended.
- * _drop forgets the solve begun last without waiting (its gate was called off: it will never run). */
+/* lsa_solve_device in two halves: _begin enqueues the solve (prior == NULL: the start point is the one the link in
+ * front of it will hold, see lsa_icp_link), _end waits for the result of the oldest solve begun and not ended.
+ * _drop forgets the solve begun last without waiting (its link was called off: it will never run). */
 int lsa_solve_device_begin(lsa_ctx* ctx, unsigned type_mask, const double prior[6], int two_d_mode, int lm_max_iter, int min_matches);
 int lsa_solve_device_end(lsa_ctx* ctx, lsa_solve_result_t* out);
 int lsa_solve_device_drop(lsa_ctx* ctx);
 
 /* ICP iterations enqueued AHEAD of their inputs (the `for icpIter` loops of Slam::ComputeEgoMotion / Localization,
- * slam_lib/src/Slam.cxx:892-950, 1071-1145: iteration i + 1 needs the pose iteration i ends with).
- *   ticket = lsa_icp_gate(ctx)              a gate on the context's stream; the launches enqueued next with
- *   lsa_match_types_gated(...)              gated inputs -- this match and lsa_solve_device_begin(prior = NULL) -- wait
- *   lsa_solve_device_begin(ctx, .., NULL)   behind it ON THE DEVICE
- *   lsa_icp_post(ctx, ticket, pose, prior, H0, H1, t0, t1)   hands over the pose to search under, the optimiser's start
- *                                           point and (H0 / H1 not NULL) the undistortion the match starts with: they run
- *   lsa_icp_cancel(ctx, ticket)             or calls them off: they do nothing, nobody waits for them
- * so that the kernel-launch path is not between the end of a solve and the next search.  A gate waits 50 ms at most; after
- * that the launches behind it do nothing and lsa_solve_device_end reports LSA_E_GATE.  At most 8 gates in flight.
- * lsa_icp_abandon calls off every gate still waiting and forgets the solves begun behind them (error paths, Reset).
- * lsa_match_types_gated returns 1 (and enqueues nothing) when this match cannot wait behind a gate: the two-launch or
- * staged forms, an empty target, an undistortion that would not reach every keypoint. */
-int lsa_icp_gate(lsa_ctx* ctx);
-int lsa_icp_post(lsa_ctx* ctx, int ticket, const double pose[16], const double prior[6], const double H0[16], const double H1[16], double t0, double t1);
-int lsa_icp_cancel(lsa_ctx* ctx, int ticket);
-int lsa_icp_abandon(lsa_ctx* ctx);
-int lsa_match_types_gated(lsa_ctx* ctx, int slot, unsigned type_mask, int query_set, const lsa_match_params_t* p, int undistort);
-
-/* The same loops WITHOUT the host between two iterations: a LINK is a gate's block on the device that the solve in front
- * of it fills in itself -- whether the next iteration runs (Slam.cxx:919-923, 950 / 1098-1107, 1151: the solve was not
- * skipped and made a step), the pose from the solve's parameters (Utils::XYZRPYtoIsometry), the next start point
- * (LocalOptimizer::SetPosePrior's IsometryToXYZRPY of that pose) and, localization, Slam::RefineUndistortion under the new
- * pose (Slam.cxx:1322-1352) -- with the arithmetic the host uses on the same result when it arrives (lsa_posemath.h over
- * lsa_pmath.h: the same bits).  A whole loop is enqueued at once:
+ * slam_lib/src/Slam.cxx:892-950, 1071-1145: iteration i + 1 needs the pose iteration i ends with), without the host
+ * between two iterations.  A LINK is a block of 64 words on the device that the solve in front of it fills in itself: word
+ * 0 = go -- whether the next iteration runs (Slam.cxx:919-923, 950 / 1098-1107, 1151: the solve was not skipped and made
+ * a step) -- then the pose from the solve's parameters (Utils::XYZRPYtoIsometry), the next start point
+ * (LocalOptimizer::SetPosePrior's IsometryToXYZRPY of that pose) and, localization, the constants of
+ * Slam::RefineUndistortion under the new pose (Slam.cxx:1322-1352) -- with the arithmetic the host uses on the same result
+ * when it arrives (lsa_posemath.h over lsa_pmath.h: the same bits).  The launches enqueued behind a link -- a match with
+ * lsa_match_types_linked, a solve with prior == NULL -- read their inputs from it ON THE DEVICE, or do nothing when go is
+ * not 1.  A whole loop is enqueued at once:
  *   lsa_match_types(...)                                       iteration 0, pose from the host
  *   t1 = lsa_icp_link(ctx)                                     reserves a block (at most 7 at a time)
  *   lsa_solve_device_begin_linked(.., prior, .., t1, &link)    solve 0 leaves block t1; what is enqueued next waits behind it
- *   lsa_match_types_gated(...)                                 iteration 1: searches under the pose in t1, or does nothing
+ *   lsa_match_types_linked(...)                                 iteration 1: searches under the pose in t1, or does nothing
  *   t2 = lsa_icp_link(ctx); lsa_solve_device_begin_linked(.., NULL, .., t2, &link); ...
  *   lsa_solve_device_begin_linked(.., NULL, .., -1, NULL)      the last one leaves nothing
  * then lsa_solve_device_end once per iteration, in order; the host takes the same decision from every result and, where
- * the device stopped, forgets the rest with lsa_icp_abandon.  Between two iterations there is one kernel boundary. */
+ * the device stopped, forgets the rest with lsa_icp_abandon.  Between two iterations there is one kernel boundary.
+ * lsa_icp_cancel(ctx, ticket) takes back what the match behind that link announced on the host (the device has called the
+ * iteration off itself, or will never reach it); lsa_icp_abandon does so for every link still reserved, the youngest
+ * first, and forgets the solves begun behind them (error paths, Reset).
+ * lsa_match_types_linked returns 1 (and enqueues nothing) when this match cannot wait behind a link: the two-launch or
+ * staged forms, an empty target, an undistortion that would not reach every keypoint. */
+int lsa_icp_cancel(lsa_ctx* ctx, int ticket);
+int lsa_icp_abandon(lsa_ctx* ctx);
+int lsa_match_types_linked(lsa_ctx* ctx, int slot, unsigned type_mask, int query_set, const lsa_match_params_t* p, int undistort);
 typedef struct lsa_icp_link
 {
   int refine_undistortion;         /* localization: Slam::RefineUndistortion between two iterations (Undistortion = REFINED) */
@@ -517,8 +510,7 @@ int lsa_icp_link_expected(const double x[6], int skipped, int successful_steps, 
  * thread 0 holds its own granules of every workgroup, "folding" is its sums, the 8-lane addition, the one barrier behind them
  * and the sensor terms; "stepping" no longer holds the rotation derivatives of a point past the end of the solve. */
 int lsa_solve_device_trace(lsa_ctx* ctx, unsigned long long out[12]);
-/* Test hooks for the two bounded waits on the device, so that the callers' fall-backs can be exercised:
- *   "gate_give_up_every" n   every n-th gate (lsa_icp_gate) gives up at once, as if the host had not answered in 50 ms
+/* Test hook for the bounded wait on the device, so that the callers' fall-back can be exercised:
  *   "lm_give_up_block" b     workgroup b of the NEXT one-launch solve abandons the exchange (the others then wait their
  *                            20 ms and give up too: lsa_solve_device reports LSA_E_STATE); one shot, -1 = none
  * and the launch shapes of the two reductions, as the environment sets them at creation, with the same clamps; a

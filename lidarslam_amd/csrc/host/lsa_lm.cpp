@@ -156,12 +156,6 @@ int LocalOptimizer::Solve(SolveSummary& sum)
   return SolveOnHost(sum);
 }
 
-int LocalOptimizer::Begin(bool gated)
-{
-  HaveFinal = false;
-  return lsa_solve_device_begin(Ctx, TypeMask, gated ? nullptr : PoseArray, TwoDMode ? 1 : 0, static_cast<int>(LMMaxIter), static_cast<int>(MinMatches));
-}
-
 int LocalOptimizer::End(SolveSummary& sum)
 {
   HaveFinal = false;
@@ -173,7 +167,7 @@ int LocalOptimizer::End(SolveSummary& sum)
     TakeResult(r, sum);
     return LSA_OK;
   }
-  if (rc != LSA_E_STATE) return rc;  // LSA_E_GATE: neither the match nor the solve ran, the caller redoes both
+  if (rc != LSA_E_STATE) return rc;
   // the solve gave up: the residual blocks are there, the loop runs here.  Whatever was enqueued ahead has been called off
   // (lsa_solve_device_end): 1 tells the caller
   const int hrc = SolveOnHost(sum);

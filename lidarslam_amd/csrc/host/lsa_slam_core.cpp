@@ -656,15 +656,15 @@ struct SlamCore::IcpLoopSpec
 {
   const char* name;                        // "ego" / "loc" / "reg" (trace lines)
   lsa_ctx* ctx;                            // the context the loop drives; NULL: the frame path's own
-  bool inLine;                             // strictly in line whatever ICPAhead says: nothing of the loop waits on the device for the host
+  bool inLine;                             // strictly in line whatever ICPAhead says
   int target, set;                         // the LSA_TARGET_* searched, the LSA_SET_* matched against it
   unsigned matchMask, solveMask;           // keypoint types matched / whose residual blocks the solves take
   unsigned maxIter, lmMaxIter;
   double initSaturation, finalSaturation;  // the saturation distance goes from one to the other over the loop
   lsa_match_params_t match;
   int loopBit;                             // this loop's bit of LSA_ICP_AHEAD_LOOPS
-  bool linksOk, gatesOk;                   // this loop's iterations can wait behind links / behind gates at all
-  int undistortAhead;                      // `undistort` of lsa_match_types_gated: a search enqueued ahead starts with RefineUndistortion
+  bool linksOk;                            // this loop's iterations can wait behind links at all
+  int undistortAhead;                      // `undistort` of lsa_match_types_linked: a search enqueued ahead starts with RefineUndistortion
   lsa_icp_link_t link;                     // what the loop's solves need to leave a link (`first` is the driver's)
   long long* matchSerial;                  // lsa_match_serial per type, of the iteration whose result was read last
   double FrameStats::*icpSeconds;          // stage timers: an iteration's enqueueing, the wait for its solve
@@ -677,16 +677,13 @@ struct SlamCore::IcpUndistortion
 {
   Pose d0 = Pose::Identity(), d1 = Pose::Identity();
   bool pending = false;  // the undistortion the last iteration ended with has not been applied yet
-  bool posted = false;   // ... it was handed to the gate of the iteration enqueued ahead
 };
 
 namespace
 {
 constexpr auto kNothing = [](auto&&...) { return LSA_OK; };  // the callable of a loop that does nothing at that point
 // diagnostics, read once
-const bool kAheadWithHostMaps = std::getenv("LSA_ICP_AHEAD_HOSTMAPS") != nullptr;  // gates in the ego-motion loop with the maps on the host too (see RunIcpLoop)
 const int kAheadLoops = std::getenv("LSA_ICP_AHEAD_LOOPS") ? std::atoi(std::getenv("LSA_ICP_AHEAD_LOOPS")) : 3;  // the loops that enqueue ahead at all: 1 ego-motion only, 2 localization only
-const bool kGateDebug = std::getenv("LSA_GATE_DEBUG") != nullptr;
 }  // namespace
 
 // How an ICP loop's iterations reach the device: the one place where that is written down.  `pose` is the pose the loop
@@ -698,21 +695,16 @@ const bool kGateDebug = std::getenv("LSA_GATE_DEBUG") != nullptr;
 //   accepted(last, undistortion)      `pose` is the solve's; what was enqueued ahead has been called off if `last`.  A
 //                                     RefineUndistortion left in `undistortion` (pending) rides in the next search
 //   finished(optimizer)               after the last accepted iteration
-// In line (ICPAhead = 0, spec.inLine, and the fall-back of the other two): match, solve, and the next match once the pose is known.
-// Gates (ICPAhead = 1, and loops longer than kChainMax): iteration i + 1 is enqueued behind a gate (lsa_icp_gate) while
-// iteration i runs: when the solve's result arrives its launches are in the queue already, and all that is between the
-// solve and the next search is one store the gate polls for (or the call that calls them off: Slam.cxx:919-923, 950).
-// Links (ICPAhead = 2): the WHOLE loop is enqueued at once, every solve leaving pose and start point for the iteration
-// behind it on the device (lsa_icp_link) -- no gate, no host between two iterations, nothing spins; this thread reads the
-// results as they arrive, takes the decisions the device has taken already and does its own pose algebra beside the running
-// device.
-// (spec.gatesOk of the ego-motion loop: with the maps on the HOST it stays in line.  Between its iterations this thread then
-// hands sub-maps the map workers have extracted to the look-ahead stream (StageSpeculativeSubMaps: a copy out of pinned
-// memory and a grid build).  With a gate waiting on the registration's stream at that moment the device delivered no result
-// for two seconds in some assignments of the streams to the hardware queues (seen with a second context alive in the
-// process), the solve was then redone on the host with the NEXT iteration's saturation distance already in force: 1.5e-5 m
-// beside the oracle.  The hang is not understood (LSA_ICP_AHEAD_HOSTMAPS=1 + LSA_ICP_TRACE=1 reproduce it); the fall-back's
-// wrong distance is fixed (the solve on the host takes the distances the device solve was enqueued with).)
+// In line (ICPAhead = 0, spec.inLine, and the fall-back of the other): match, solve, and the next match once the pose is known.
+// Links (any other ICPAhead): the WHOLE loop is enqueued at once, every solve leaving pose and start point for the iteration
+// behind it on the device (lsa_icp_link) -- no host between two iterations, nothing spins; this thread reads the results as
+// they arrive, takes the decisions the device has taken already and does its own pose algebra beside the running device.
+// What cannot be linked -- a loop longer than kChainMax, !spec.linksOk, a match lsa_match_types_linked refuses -- runs in
+// line from there on.
+// (There is no third schedule with iteration i + 1 behind a gate kernel that polls host memory for the pose.  It was here
+// once and gained nothing measurable over links (0.0985 against 0.0976 ms an iteration); with host maps and a second
+// context alive a waiting gate once kept the device from delivering any result for two seconds, which was never
+// explained.  It was removed rather than fenced off.)
 template <class Top, class Enqueued, class Solved, class Skipped, class Accepted, class Finished>
 int SlamCore::RunIcpLoop(const IcpLoopSpec& spec, Pose& pose, const Top& top, const Enqueued& enqueued, const Solved& solved, const Skipped& skipped,
                          const Accepted& accepted, const Finished& finished)
@@ -725,28 +717,17 @@ int SlamCore::RunIcpLoop(const IcpLoopSpec& spec, Pose& pose, const Top& top, co
     const double iterRatio = icpIter / static_cast<double>(spec.maxIter - 1);
     return (1 - iterRatio) * spec.initSaturation + iterRatio * spec.finalSaturation;
   };
-  const bool aheadOk = !spec.inLine && ICPAhead >= 1 && DeviceLM && FusedMatch && (kAheadLoops & spec.loopBit);
-  bool chain = aheadOk && ICPAhead >= 2 && spec.maxIter <= kChainMax && spec.linksOk;
-  bool ahead = aheadOk && !chain && spec.gatesOk;
-  if (ahead || chain) lsa_icp_abandon(ctx);
+  bool chain = !spec.inLine && ICPAhead != 0 && DeviceLM && FusedMatch && (kAheadLoops & spec.loopBit) && spec.maxIter <= kChainMax && spec.linksOk;
+  if (chain) lsa_icp_abandon(ctx);
   unsigned chained = 0;            // iterations 0 .. chained - 1 are in the queue (links)
   long long chainSerial[kChainMax][3] = {};
-  bool enqueuedAhead = false;      // this iteration's launches are in the queue (their gate has been answered)
-  long long aheadSerial[3] = {0, 0, 0};
-  int ticket = -1;                 // the gate the next iteration waits behind
   IcpUndistortion undistortion;
   unsigned icpIter = 0;
 
-  // Every way out calls off what is still in the queue: the gate's iteration, and the links' when the loop ends in front
-  // of them (the device has taken the same decision from the same result -- the iterations behind do nothing; what their
-  // matches announced on the host is taken back).  After an error nobody will end the solves begun: all of it goes.
+  // Every way out calls off what is still in the queue: the links' iterations when the loop ends in front of them (the
+  // device has taken the same decision from the same result -- the iterations behind do nothing; what their matches
+  // announced on the host is taken back).  After an error nobody will end the solves begun: all of it goes.
   auto callOffRest = [&](bool all) {
-    if (ticket >= 0)
-    {
-      lsa_icp_cancel(ctx, ticket);
-      lsa_solve_device_drop(ctx);
-      ticket = -1;
-    }
     if (all || icpIter + 1 < chained)
     {
       lsa_icp_abandon(ctx);
@@ -775,11 +756,11 @@ int SlamCore::RunIcpLoop(const IcpLoopSpec& spec, Pose& pose, const Top& top, co
     takeSerials(spec.matchSerial);
     return LSA_OK;
   };
-  // iteration `iter` behind the link or the gate enqueued last; 1 (and nothing enqueued) when it cannot wait there
+  // iteration `iter` behind the link reserved last; 1 (and nothing enqueued) when it cannot wait there
   auto matchAhead = [&](unsigned iter, long long* serial) -> int {
     lsa_match_params_t next = mp;
     next.saturation_distance = saturation(iter);
-    const int rc = lsa_match_types_gated(ctx, spec.target, spec.matchMask, spec.set, &next, spec.undistortAhead);
+    const int rc = lsa_match_types_linked(ctx, spec.target, spec.matchMask, spec.set, &next, spec.undistortAhead);
     if (rc == 0) takeSerials(serial);
     return rc;
   };
@@ -796,13 +777,13 @@ int SlamCore::RunIcpLoop(const IcpLoopSpec& spec, Pose& pose, const Top& top, co
     optimizer.SetMinMatches(MinNbMatchedKeypoints);
     optimizer.UseDeviceResiduals(spec.solveMask);
     optimizer.SetPosePrior(pose);
-    bool begun = enqueuedAhead;  // the solve of this iteration is in flight
+    bool begun = false;  // the solve of this iteration is in flight
     if (icpIter < chained)
     {
       begun = true;
       setSerials(chainSerial[icpIter]);
     }
-    else if (!enqueuedAhead)
+    else
     {
       if (const int rc = matchInLine(); rc < 0) return rc;
       if (chain)
@@ -822,46 +803,14 @@ int SlamCore::RunIcpLoop(const IcpLoopSpec& spec, Pose& pose, const Top& top, co
           chained = j + 1;
           if (leave < 0) break;
           const int mrc = matchAhead(j + 1, chainSerial[j + 1]);
-          if (mrc < 0) return Fail(mrc, "lsa_match_types_gated");
+          if (mrc < 0) return Fail(mrc, "lsa_match_types_linked");
           if (mrc != 0) { lsa_icp_cancel(ctx, leave); break; }  // this match cannot wait behind a link: the loop goes on in line from there
         }
         chain = false;  // (enqueued once; whatever is not in the queue now runs in line)
         begun = true;
       }
-      else if (ahead)
-      {
-        LSA_TRY(optimizer.Begin(false));
-        begun = true;
-      }
     }
-    else
-      setSerials(aheadSerial);
-    ICP_TRACE("[%s %u] top: ahead %d begun %d enqueued %d\n", spec.name, icpIter, (int)ahead, (int)begun, (int)enqueuedAhead);
-    enqueuedAhead = false;
-    if (ahead && begun && icpIter + 1 < spec.maxIter)
-    {
-      ticket = lsa_icp_gate(ctx);
-      ICP_TRACE("[%s %u] gate ticket %d\n", spec.name, icpIter, ticket);
-      if (ticket < 0) { ticket = -1; ahead = false; }
-      else
-      {
-        const char* call = "lsa_match_types_gated";
-        int rc = matchAhead(icpIter + 1, aheadSerial);
-        if (rc == 0)
-        {
-          call = "lsa_solve_device_begin";
-          rc = lsa_solve_device_begin(ctx, spec.solveMask, nullptr, TwoDMode ? 1 : 0, static_cast<int>(spec.lmMaxIter), static_cast<int>(MinNbMatchedKeypoints));
-        }
-        if (rc != 0)
-        {
-          // nothing waits behind this gate: the loop goes on without gates
-          lsa_icp_cancel(ctx, ticket);
-          ticket = -1;
-          ahead = false;
-          if (rc < 0) return Fail(rc, call);
-        }
-      }
-    }
+    ICP_TRACE("[%s %u] top: begun %d chained %u\n", spec.name, icpIter, (int)begun, chained);
     if (const int rc = enqueued(icpIter); rc < 0) return rc;
     if (!begun && own) ArmLookaheadInterlude();
     Stats.*spec.icpSeconds += ticp.Stop();
@@ -871,28 +820,11 @@ int SlamCore::RunIcpLoop(const IcpLoopSpec& spec, Pose& pose, const Top& top, co
     SolveSummary summary;
     if (begun)
     {
-      Tick tdbg;
       const int irc = InterludeWork();
-      const double dbgInterlude = tdbg.Stop();
-      int rc = optimizer.End(summary);
-      ICP_TRACE("[%s %u] End rc %d irc %d ticket %d\n", spec.name, icpIter, rc, irc, ticket);
-      if (kGateDebug && tdbg.Stop() > 0.01)
-        std::fprintf(stderr, "[gate debug] %s iteration %u: enqueue %.3f ms, interlude %.3f ms, until the result %.3f ms, rc %d\n", spec.name, icpIter, 1e3 * Stats.*spec.icpSeconds, 1e3 * dbgInterlude,
-                     1e3 * tdbg.Stop(), rc);
-      if (rc == LSA_E_GATE)
-      {
-        // the gate gave up waiting for this thread (it was held up for 50 ms): nothing of the iteration ran.  Whatever
-        // waits behind it is called off, the iteration is done again in line, the rest of the loop without gates.
-        callOffRest(true);
-        ahead = false;
-        IcpGateTimeouts++;
-        undistortion.pending = undistortion.posted;  // (it was to ride in the search that did not run)
-        rc = matchInLine();
-        if (rc < 0) return rc;
-        rc = optimizer.Solve(summary);
-      }
-      if (rc < 0) return Fail(rc, "LocalOptimizer::End / Solve");
-      if (rc == 1) { ticket = -1; ahead = false; chained = 0; }  // solved on the host: what was enqueued ahead has been called off
+      const int rc = optimizer.End(summary);
+      ICP_TRACE("[%s %u] End rc %d irc %d\n", spec.name, icpIter, rc, irc);
+      if (rc < 0) return Fail(rc, "LocalOptimizer::End");
+      if (rc == 1) chained = 0;  // solved on the host: what was enqueued ahead has been called off
       if (irc < 0) return irc;
     }
     else
@@ -908,7 +840,7 @@ int SlamCore::RunIcpLoop(const IcpLoopSpec& spec, Pose& pose, const Top& top, co
     if (!summary.skipped || spec.countSkippedEvals) Stats.lm_evals += summary.num_evaluations;
     if (!summary.skipped) pose = optimizer.GetOptimizedPose();
     // Nothing more to search: called off HERE, in front of whatever `accepted` and `finished` put on the stream (an
-    // undistortion, the registration error), so that it does not wait behind the gate.
+    // undistortion, the registration error), so that what the links' matches announced on the host is taken back first.
     const bool last = summary.skipped || summary.num_successful_steps == 1 || icpIter + 1 == spec.maxIter;
     if (last) callOffRest(false);
     const int rc = summary.skipped ? skipped() : accepted(last, undistortion);
@@ -919,18 +851,7 @@ int SlamCore::RunIcpLoop(const IcpLoopSpec& spec, Pose& pose, const Top& top, co
       if (const int frc = summary.skipped ? LSA_OK : finished(optimizer); frc < 0) return frc;
       break;
     }
-    if (ticket >= 0)
-    {
-      double prior[6];
-      ToXYZRPY(pose, prior);  // LocalOptimizer::SetPosePrior of the next iteration
-      const int prc = lsa_icp_post(ctx, ticket, pose.m, prior, undistortion.pending ? undistortion.d0.m : nullptr, undistortion.pending ? undistortion.d1.m : nullptr, Motion.Time0, Motion.Time1);
-      if (prc < 0) return Fail(prc, "lsa_icp_post");
-      ticket = -1;
-      undistortion.posted = undistortion.pending;
-      undistortion.pending = false;
-      enqueuedAhead = true;
-    }
-    else if (icpIter + 1 < chained)
+    if (icpIter + 1 < chained)
       undistortion.pending = false;  // the next search is in the queue and undistorts with what the device worked out (the same)
   }
   atExit.failed = false;
@@ -995,7 +916,6 @@ int SlamCore::ComputeEgoMotion()
   spec.match = EgoMatchParams();
   spec.loopBit = 1;
   spec.linksOk = true;
-  spec.gatesOk = DeviceMapsInUse() || MapUpdate == MappingMode::NONE || kAheadWithHostMaps;  // (the host-map stall: RunIcpLoop)
   spec.matchSerial = EgoMatchSerial;
   spec.icpSeconds = &FrameStats::ego_icp;
   spec.lmSeconds = &FrameStats::ego_lm;
@@ -1232,7 +1152,7 @@ int SlamCore::Localization()
   // The undistortion between two iterations has to ride in the next search kernel for an iteration to be enqueued ahead (a
   // launch of its own would have to be enqueued between the two, when the motion is known); behind a link the device
   // refines it itself.
-  spec.linksOk = spec.gatesOk = !refined || UndistortInSearch;
+  spec.linksOk = !refined || UndistortInSearch;
   spec.undistortAhead = refined ? 1 : 0;
   spec.link.refine_undistortion = refined ? 1 : 0;
   spec.link.have_log = LogTrajectory.empty() ? 0 : 1;
@@ -2425,7 +2345,7 @@ int SlamCore::GetParam(const std::string& name, double* v) const
   if (name == "DeviceMapsInUse") { *v = DeviceMapsInUse() ? 1. : 0.; return LSA_OK; }
   if (name == "UploadsAdopted") { *v = Ctx ? lsa_uploads_adopted(Ctx) : 0; return LSA_OK; }
   if (name == "DeviceSolveFallbacks") { *v = Ctx ? lsa_solve_device_fallbacks(Ctx) : 0; return LSA_OK; }
-  if (name == "IcpGateTimeouts") { *v = IcpGateTimeouts; return LSA_OK; }
+  if (name == "IcpGateTimeouts") { *v = 0; return LSA_OK; }  // nothing counts them any more: the benchmark still reads the name
   if (name == "TargetsBuiltAheadAdopted") { *v = Ctx ? lsa_prepared_targets_adopted(Ctx) : 0; return LSA_OK; }
   if (name == "SubMapsStagedAheadAdopted") { *v = Ctx ? lsa_staged_targets_adopted(Ctx) : 0; return LSA_OK; }
   if (name == "MapAddThreads") { *v = LocalMaps[LSA_PLANE]->GetAddThreads(); return LSA_OK; }

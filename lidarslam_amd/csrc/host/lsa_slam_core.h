@@ -260,8 +260,7 @@ public:
   bool SubMapsAhead = true;
   bool SubMapsAheadAdaptive = true;  // give it up for a while when the localization had to wait for it twice in a row
   bool LocalizationStartFused = true;  // reset + first undistortion + keypoint boxes of the localization as one launch (device maps)
-  int IcpGateTimeouts = 0;        // ICP iterations enqueued ahead whose gate gave up (diagnostics; 0 on a healthy run)
-  int ICPAhead = 2;               // ICP iterations enqueued ahead of their inputs.  2: the whole loop at once, every solve leaving the next iteration's pose on the device (lsa_icp_link); 1: iteration i + 1 behind a gate the host answers (lsa_icp_gate); 0: off
+  int ICPAhead = 2;               // ICP iterations enqueued ahead of their inputs.  0: off (in line); anything else: the whole loop at once, every solve leaving the next iteration's pose on the device (lsa_icp_link).  1 once selected another schedule and stays accepted as a synonym of 2
   bool UndistortInSearch = true;  // RefineUndistortion between two localization iterations inside the next iteration's search kernel
   bool SpecBoxesOnLookahead = true;  // the predicted boxes of the sub-maps ahead of time on the look-ahead stream, not the context's
   bool SpecGridsTogether = true;  // the search grids of the sub-maps extracted ahead of time built by one sequence of launches

@@ -48,9 +48,8 @@ constexpr int kLmOut = 48;                // doubles the LM kernel hands to the 
 constexpr int kLmMailRing = 8;            // result mailboxes: solves enqueued one behind the other (lsa_icp_link) each write their own
 constexpr int kHistRing = 256;  // half of it is cleared at a time (two fills on the ICP's stream): once in 128 matches
 constexpr int kAccumVals = 29;            // cost, g[6], H upper[21], nvalid
-constexpr int kGateRing = 8;              // gates (ICP iterations enqueued ahead of their inputs) a context can have in flight
-constexpr int kGateWords = 64;            // 8-byte words of a gate block on the device
-constexpr int kGateGranules = 128;        // 8-byte granules {sequence number, half a word} of a gate block in host memory
+constexpr int kLinkRing = 8;              // links (ICP iterations enqueued ahead of their inputs) a context can have in flight
+constexpr int kLinkWords = 64;            // 8-byte words of a link block on the device
 
 struct GridDesc
 {
@@ -251,20 +250,16 @@ struct lsa_ctx
   unsigned lm_tag = 0;            // tags handed out so far (every launch takes max evaluations + 2)
   unsigned long long lm_seq = 0;  // launches so far
   int lm_blocks = lsa::kLmBlocks;
-  // lsa_icp_gate: ICP iterations enqueued ahead of their inputs.  The host's side, in coherent host memory:
-  // [kGateRing][kGateGranules] granules {sequence number of the gate, half of word i / 2} -- every 8-byte granule carries
-  // its own tag, so ONE sweep of loads over the bus that finds all the tags in place has the whole block, whatever order
-  // the reads were served in.  The device's side, which the launches read: [kGateRing][kGateWords] words, word 0 = go
-  unsigned long long* gate_host = nullptr;
-  unsigned long long* gate_dev = nullptr;
-  unsigned gate_seq = 0;                 // gates enqueued so far
-  int gate_current = -1;                 // ticket the launches enqueued next wait behind (lsa_match_types_gated, lsa_solve_device_begin)
-  struct GateSaved { double sat[3]; int hist_pos[3]; long long hist_serial[3]; int k[3]; bool valid[3]; unsigned mask; bool used; bool link; unsigned seq; } gate_saved[lsa::kGateRing] = {};
+  // lsa_icp_link: ICP iterations enqueued ahead of their inputs.  The blocks the solves leave and the launches behind
+  // them read, on the device: [kLinkRing][kLinkWords] words, word 0 = go
+  unsigned long long* link_dev = nullptr;
+  unsigned link_seq = 0;                 // links reserved so far
+  int link_current = -1;                 // ticket the launches enqueued next wait behind (lsa_match_types_linked, lsa_solve_device_begin)
+  struct LinkSaved { double sat[3]; int hist_pos[3]; long long hist_serial[3]; int k[3]; bool valid[3]; unsigned mask; bool used; unsigned seq; } link_saved[lsa::kLinkRing] = {};
   double* motion_dev = nullptr;          // [16] the motion within the frame (LinearTransformInterpolator) between the linked solves of one localization loop
-  int debug_gate_give_up_every = 0;      // lsa_debug_set: every n-th gate gives up at once (exercises the callers' fall-back)
   int debug_lm_give_up_block = -1;       // lsa_debug_set: that workgroup of the NEXT solve abandons the exchange (one shot)
   std::deque<unsigned> lm_pending;       // result tags of the solves begun and not ended yet, oldest first
-  std::deque<int> lm_pending_wait;       // ... and the gate / link each of them waits behind (-1: none)
+  std::deque<int> lm_pending_wait;       // ... and the link each of them waits behind (-1: none)
   hipStream_t map_stream = nullptr;     // shared by the device maps of this context (lsa_device_grid.hip), created with the first of them
   int map_stream_users = 0;
   void (*solve_hook)(void*) = nullptr;  // lsa_solve_device_interlude
@@ -321,10 +316,10 @@ struct lsa_ctx
   int pcd_lds = -1;      // lsa_debug_set "pcd_lds": 1 / 0 picks the form of k_pcd_decode / k_pcd_encode, -1 the default
   double pcd_times[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // the last load / save, see lsa_pcd_io_times
   std::mutex prof_mutex;  // stats / pending / event_pool of the profiling scopes
-  // Buffers that were outgrown.  hipFree / hipHostFree wait for the whole device -- also for a gate that waits for THIS
-  // process (lsa_icp_gate), with the runtime's lock held: a free on a worker thread at the wrong moment stalls the frame
-  // until the gate gives up.  Outgrown buffers are therefore only noted here and freed at the start of the next frame
-  // (lsa_collect_garbage), when nothing on the device waits for the host; kernels in flight keep the old buffer valid.
+  // Buffers that were outgrown.  hipFree / hipHostFree wait for the whole device with the runtime's lock held: a free on
+  // a worker thread at the wrong moment stalls every thread that enqueues.  Outgrown buffers are therefore only noted
+  // here and freed at the start of the next frame (lsa_collect_garbage); kernels in flight keep the old buffer valid, so
+  // growth needs no stream synchronise.
   std::mutex grave_mutex;
   std::vector<void*> grave_dev, grave_host;
   int bbox_n[3] = {0, 0, 0};
@@ -356,7 +351,7 @@ struct lsa_ctx
   }
 };
 
-// LSA_ICP_TRACE=1: every step of the gated ICP loops on stderr (diagnostics; read once)
+// LSA_ICP_TRACE=1: every step of the ICP loops enqueued ahead on stderr (diagnostics; read once)
 inline bool lsa_icp_trace_on()
 {
   static const bool on = std::getenv("LSA_ICP_TRACE") != nullptr;

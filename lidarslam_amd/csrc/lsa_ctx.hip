@@ -88,7 +88,7 @@ int ensure_target(lsa_ctx* ctx, int ti, int m)
   // with a floor of 16 k a map's first hundred keyframes crossed it for every target, 15 us a frame over bench.py's window)
   int cap = std::max(2 * m, 65536);
   // (no synchronisation: the outgrown buffers are retired, launches in flight keep them; the new ones are filled before
-  // they are read.  This runs on worker threads too, beside ICP iterations that wait behind a gate)
+  // they are read.  This runs on worker threads too, beside ICP iterations enqueued ahead)
   LSA_HIP(ctx, dev_alloc(ctx, &t.pts, (size_t)cap));
   LSA_HIP(ctx, dev_alloc(ctx, &t.xyzl, (size_t)cap));
   for (int l = 0; l < kGridLevels; ++l)
@@ -208,21 +208,11 @@ int lsa_ctx_create(int device_id, lsa_ctx** out)
     std::memset(ctx->lm_mailbox, 0, (size_t)kLmMailRing * 2 * kLmOut * sizeof(unsigned long long));
   else
     ctx->lm_mailbox = nullptr;  // optional: lsa_solve_device then reports LSA_E_STATE and the host-driven loop is used
-  // gates of ICP iterations enqueued ahead (lsa_icp_gate): optional like the result mailbox
-  if (ctx->lm_mailbox && hipHostMalloc((void**)&ctx->gate_host, (size_t)kGateRing * kGateGranules * sizeof(unsigned long long), hipHostMallocCoherent | hipHostMallocMapped) == hipSuccess)
-  {
-    std::memset(ctx->gate_host, 0, (size_t)kGateRing * kGateGranules * sizeof(unsigned long long));
-    if (hipMalloc((void**)&ctx->gate_dev, (size_t)kGateRing * kGateWords * sizeof(unsigned long long)) != hipSuccess ||
-        hipMemset(ctx->gate_dev, 0, (size_t)kGateRing * kGateWords * sizeof(unsigned long long)) != hipSuccess)
-    {
-      (void)hipHostFree(ctx->gate_host);
-      ctx->gate_host = nullptr;
-      ctx->gate_dev = nullptr;
-    }
-  }
-  else
-    ctx->gate_host = nullptr;
-  if (ctx->gate_dev && (hipMalloc((void**)&ctx->motion_dev, 16 * sizeof(double)) != hipSuccess || hipMemset(ctx->motion_dev, 0, 16 * sizeof(double)) != hipSuccess))
+  // link blocks of ICP iterations enqueued ahead (lsa_icp_link): optional like the result mailbox
+  if (ctx->lm_mailbox && (hipMalloc((void**)&ctx->link_dev, (size_t)kLinkRing * kLinkWords * sizeof(unsigned long long)) != hipSuccess ||
+                          hipMemset(ctx->link_dev, 0, (size_t)kLinkRing * kLinkWords * sizeof(unsigned long long)) != hipSuccess))
+    ctx->link_dev = nullptr;
+  if (ctx->link_dev && (hipMalloc((void**)&ctx->motion_dev, 16 * sizeof(double)) != hipSuccess || hipMemset(ctx->motion_dev, 0, 16 * sizeof(double)) != hipSuccess))
     ctx->motion_dev = nullptr;  // optional: no links then (lsa_icp_link says so)
   ok &= hipMalloc((void**)&ctx->lm_xchg, (size_t)2 * kLmBlocksMax * kMailboxStride * sizeof(unsigned long long)) == hipSuccess;
   if (ok) ok &= hipMemset(ctx->lm_xchg, 0, (size_t)2 * kLmBlocksMax * kMailboxStride * sizeof(unsigned long long)) == hipSuccess;
@@ -305,8 +295,7 @@ void lsa_ctx_destroy(lsa_ctx* ctx)
   if (ctx->host_pinned) (void)hipHostFree(ctx->host_pinned);
   if (ctx->mailbox) (void)hipHostFree(ctx->mailbox);
   if (ctx->lm_mailbox) (void)hipHostFree(ctx->lm_mailbox);
-  if (ctx->gate_host) (void)hipHostFree(ctx->gate_host);
-  fr(ctx->gate_dev);
+  fr(ctx->link_dev);
   fr(ctx->motion_dev);
   fr(ctx->lm_xchg);
   fr(ctx->trace_dev);

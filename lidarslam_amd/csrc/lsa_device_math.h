@@ -227,7 +227,7 @@ template <typename T> struct CovAccum
   }
 };
 
-// (Rigid, InterpConst, IcpGate: lsa_posemath.h)
+// (Rigid, InterpConst, IcpLinkBlock: lsa_posemath.h)
 LSA_DEV void rigid_apply(const Rigid& a, double x, double y, double z, double& ox, double& oy, double& oz)
 {
   ox = ((a.R[0] * x + a.R[1] * y) + a.R[2] * z) + a.t[0];

@@ -50,10 +50,10 @@ struct LmParams
   unsigned tag_base;
   int cslots;  // residual blocks per thread kept in LDS between the evaluations
   int give_up_block;    // test hook: this workgroup abandons the exchange at its first evaluation (-1: none)
-  const IcpGate* gate;  // not null: the launch was enqueued ahead of its start point (lsa_icp_gate / lsa_icp_link) -- x0 comes from there, or nothing is done
+  const IcpLinkBlock* link;  // not null: the launch was enqueued ahead of its start point (lsa_icp_link) -- x0 comes from there, or nothing is done
   // What this solve leaves for the ICP iteration enqueued behind it (lsa_icp_link; Slam.cxx:907, 940-950 and 1086, 1134-1151):
   // whether it runs at all, the pose its keypoints are searched under, its start point and -- localization -- the undistortion.
-  IcpGate* leave;             // null: nothing is left (no iteration behind this one)
+  IcpLinkBlock* leave;             // null: nothing is left (no iteration behind this one)
   int link_refine;            // localization with Slam::RefineUndistortion between two iterations
   int motion_from_args;       // the motion within the frame as the loop starts with it: motion0 (first solve of the loop) or motion_dev
   posemath::ScanPoseClock clock;
@@ -493,7 +493,7 @@ __device__ __forceinline__ void lm_step(const LmParams& p, Shared& sh, bool firs
 __device__ void leave_link(const LmParams& p, const LmState& lm, bool failed, int part)
 {
   using namespace posemath;
-  IcpGate* g = p.leave;
+  IcpLinkBlock* g = p.leave;
   const int lane = threadIdx.x & 63;
   const bool go = !failed && !lm.skipped && lm.successful != 1;
   if (!go)
@@ -566,20 +566,12 @@ __global__ __launch_bounds__(kLmThreads) void k_lm_solve(LmParams p, u64* __rest
   // the thread's first residual block: on its way from memory while the launch finds out whether it runs and where it starts
   RecordRegs pre;
   if (kRecordPrefetch && p.cslots > 0) record_load(p.set, blockIdx.x * blockDim.x + threadIdx.x, pre);
-  if (p.gate)
+  if (p.link)
   {
-    // enqueued ahead of its start point: the gate in front of this launch has left it (go == 1), or the iteration was
-    // called off (0: nobody waits for a result) or the gate gave up waiting for the host (2: the host is told)
-    const unsigned long long go = p.gate->go;
-    if (go != 1ull)
+    // enqueued ahead of its start point: the solve in front of this launch has left it (go == 1), or the iteration was
+    // called off (0: nobody waits for a result)
+    if (p.link->go != 1ull)
     {
-      if (go == 2ull && blockIdx.x == 0 && threadIdx.x < 2 * kResCount)
-      {
-        const double r = (threadIdx.x >> 1) == kResFailed ? 2. : 0.;
-        const u64 bits = (u64)__double_as_longlong(r);
-        const unsigned word = (threadIdx.x & 1) ? (unsigned)(bits >> 32) : (unsigned)(bits & 0xffffffffull);
-        __hip_atomic_store(mailbox + threadIdx.x, ((u64)out_tag << 32) | word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-      }
       // an iteration that does not run leaves the same for the one behind it
       if (p.leave && blockIdx.x == 0 && threadIdx.x == 0) p.leave->go = 0ull;
       return;
@@ -596,14 +588,14 @@ __global__ __launch_bounds__(kLmThreads) void k_lm_solve(LmParams p, u64* __rest
 #pragma unroll
     for (int v = 0; v < kAccumVals; ++v) sh.sums[0][v] = 0.;
     lm.cur_buf = 0;
-    // the start point: the launch's own argument, or what the gate brought over (read into LDS, the arguments stay untouched)
+    // the start point: the launch's own argument, or what the link brought over (read into LDS, the arguments stay untouched)
     double x0[6];
 #pragma unroll
     for (int a = 0; a < 6; ++a) x0[a] = p.x0[a];
-    if (p.gate)
+    if (p.link)
     {
 #pragma unroll
-      for (int a = 0; a < 6; ++a) x0[a] = p.gate->in.x0[a];
+      for (int a = 0; a < 6; ++a) x0[a] = p.link->in.x0[a];
     }
 #pragma unroll
     for (int a = 0; a < 6; ++a) { lm.x[a] = x0[a]; lm.scale[a] = 1.; lm.diag[a] = 0.; }
@@ -671,46 +663,6 @@ __global__ __launch_bounds__(kLmThreads) void k_lm_solve(LmParams p, u64* __rest
   }
 }
 
-// Waits for the host to release gate `seq`, then leaves what the host posted in the device block the launches behind the
-// gate read.  The host's block is 128 granules {seq, half of word i / 2}; the two wavefronts sweep all of them with one
-// load each, again and again, until every tag is `seq`: one trip over the bus after the host's last store, and no
-// assumption on the order the reads are served in.  Word 0 of the block is go (1 run, 0 called off); the wait is bounded
-// (50 ms of the 100 MHz clock): a host that does not answer makes the launches behind it do nothing and say so (go = 2).
-__global__ __launch_bounds__(kGateGranules) void k_icp_gate(const u64* __restrict__ host_granules, u64* __restrict__ dev_words, unsigned seq, int give_up)
-{
-  __shared__ unsigned halves[kGateGranules];
-  __shared__ int state;  // 0 waiting, 1 all there, 2 gave up
-  const int t = threadIdx.x;
-  if (t == 0) state = give_up ? 2 : 0;  // (test hook: as if the host had not answered in time)
-  __syncthreads();
-  const unsigned long long t0 = wall_clock64();
-  while (state == 0)
-  {
-    const u64 g = __hip_atomic_load(host_granules + t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    const bool mine = (unsigned)(g >> 32) == seq;
-    if (mine) halves[t] = (unsigned)(g & 0xffffffffull);
-    const int all = __syncthreads_and(mine ? 1 : 0);
-    if (t == 0)
-    {
-      if (all) state = 1;
-      else if (wall_clock64() - t0 > 5000000ull) state = 2;
-    }
-    __syncthreads();
-    if (state == 0) __builtin_amdgcn_s_sleep(1);
-  }
-  if (state == 1)
-  {
-    if (t < kGateWords)
-    {
-      const u64 w = ((u64)halves[2 * t + 1] << 32) | halves[2 * t];
-      // called off (go == 0): only the first word matters
-      if (t == 0 || (halves[0] | halves[1]) != 0u) dev_words[t] = w;
-    }
-  }
-  else if (t == 0)
-    dev_words[0] = 2ull;
-}
-
 const char* const kMessages[] = {"", "not enough matches", "gradient tolerance (iteration 0)", "max iterations", "gradient tolerance",
                                  "min trust region radius", "too many invalid steps", "parameter tolerance", "function tolerance"};
 
@@ -736,7 +688,6 @@ int lm_blocks_share()
   const int side_by_side = std::max(1, std::min(g_live_contexts.load(std::memory_order_relaxed), queues));
   return std::max(cus / side_by_side, 8);
 }
-InterpConst make_interp_const(const double H0[16], const double H1[16], double t0, double t1);  // lsa_transform.hip
 // how many layers of residual blocks (a layer: one block per thread, 17 * kLmThreads doubles = 68 KiB) the solve kernel
 // may keep in LDS beside its own static data (Shared, 3 360 B).  A layer is counted only when the runtime accepts it as
 // dynamic LDS AND static + dynamic fit the LDS a workgroup may have (160 KiB on gfx950: two layers, since the fold no
@@ -767,9 +718,9 @@ extern "C" {
 static int solve_device_begin(lsa_ctx* ctx, unsigned type_mask, const double prior[6], int two_d_mode, int lm_max_iter, int min_matches, int leave_ticket, const lsa_icp_link_t* link)
 {
   if (!ctx) return LSA_E_ARG;
-  if (leave_ticket >= 0 && (leave_ticket >= kGateRing || !link || !ctx->gate_dev || !ctx->gate_saved[leave_ticket].used || !ctx->gate_saved[leave_ticket].link))
+  if (leave_ticket >= 0 && (leave_ticket >= kLinkRing || !link || !ctx->link_dev || !ctx->link_saved[leave_ticket].used))
     return ctx->fail(LSA_E_ARG, "lsa_solve_device_begin_linked: no such link (lsa_icp_link)");
-  if (!prior && ctx->gate_current < 0) return ctx->fail(LSA_E_ARG, "lsa_solve_device_begin: no start point and no gate to wait behind");
+  if (!prior && ctx->link_current < 0) return ctx->fail(LSA_E_ARG, "lsa_solve_device_begin: no start point and no link to wait behind");
   if (!ctx->lm_mailbox) return ctx->fail(LSA_E_STATE, "lsa_solve_device: no coherent host memory for the result");
   LSA_HIP(ctx, hipSetDevice(ctx->device));
   LmParams p;
@@ -786,7 +737,7 @@ static int solve_device_begin(lsa_ctx* ctx, unsigned type_mask, const double pri
   for (int a = 0; a < 6; ++a) p.x0[a] = prior ? prior[a] : 0.;
   p.give_up_block = ctx->debug_lm_give_up_block;
   ctx->debug_lm_give_up_block = -1;
-  p.gate = prior ? nullptr : reinterpret_cast<const IcpGate*>(ctx->gate_dev + (size_t)ctx->gate_current * kGateWords);
+  p.link = prior ? nullptr : reinterpret_cast<const IcpLinkBlock*>(ctx->link_dev + (size_t)ctx->link_current * kLinkWords);
   p.leave = nullptr;
   p.link_refine = 0;
   p.motion_from_args = 0;
@@ -796,7 +747,7 @@ static int solve_device_begin(lsa_ctx* ctx, unsigned type_mask, const double pri
   std::memset(p.motion0, 0, sizeof(p.motion0));
   if (leave_ticket >= 0)
   {
-    p.leave = reinterpret_cast<IcpGate*>(ctx->gate_dev + (size_t)leave_ticket * kGateWords);
+    p.leave = reinterpret_cast<IcpLinkBlock*>(ctx->link_dev + (size_t)leave_ticket * kLinkWords);
     p.link_refine = link->refine_undistortion ? 1 : 0;
     p.motion_from_args = link->first ? 1 : 0;
     p.clock.have_log = link->have_log ? 1 : 0;
@@ -833,10 +784,10 @@ static int solve_device_begin(lsa_ctx* ctx, unsigned type_mask, const double pri
                        ctx->route_stats && ctx->trace_dev ? reinterpret_cast<unsigned long long*>(ctx->trace_dev) + (size_t)8192 * 12 : nullptr);
   }
   ctx->lm_pending.push_back(out_tag);
-  ctx->lm_pending_wait.push_back(prior ? -1 : ctx->gate_current);
+  ctx->lm_pending_wait.push_back(prior ? -1 : ctx->link_current);
   // what is enqueued next waits behind the link this solve leaves
-  if (leave_ticket >= 0) ctx->gate_current = leave_ticket;
-  if (lsa_icp_trace_on()) std::fprintf(stderr, "[lm begin] tag %u gated %d leaves %d sat2 %.6g %.6g counts %d %d\n", out_tag, prior ? 0 : 1, leave_ticket, p.set.sat2[0], p.set.sat2[1], p.set.count[0], p.set.count[1]);
+  if (leave_ticket >= 0) ctx->link_current = leave_ticket;
+  if (lsa_icp_trace_on()) std::fprintf(stderr, "[lm begin] tag %u linked %d leaves %d sat2 %.6g %.6g counts %d %d\n", out_tag, prior ? 0 : 1, leave_ticket, p.set.sat2[0], p.set.sat2[1], p.set.count[0], p.set.count[1]);
   return LSA_OK;
 }
 
@@ -854,7 +805,7 @@ int lsa_solve_device_begin_linked(lsa_ctx* ctx, unsigned type_mask, const double
 int lsa_solve_device_drop(lsa_ctx* ctx)
 {
   if (!ctx || ctx->lm_pending.empty()) return LSA_E_ARG;
-  ctx->lm_pending.pop_back();  // the solve begun last will never run (its gate was called off): nobody waits for it
+  ctx->lm_pending.pop_back();  // the solve begun last will never run (its link was called off): nobody waits for it
   ctx->lm_pending_wait.pop_back();
   return LSA_OK;
 }
@@ -882,9 +833,8 @@ int lsa_solve_device_end(lsa_ctx* ctx, lsa_solve_result_t* out)
         {
           if ((++spins & 0x3ff) == 0 && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(2000))
           {
-            // whatever was enqueued ahead is called off first: its gates wait for this thread (the stream would not
-            // drain), and what its matches announced on the host -- the NEXT iteration's saturation distance -- must not
-            // be what the caller's fall-back solves with
+            // whatever was enqueued ahead is called off first: what its matches announced on the host -- the NEXT
+            // iteration's saturation distance -- must not be what the caller's fall-back solves with
             (void)lsa_icp_abandon(ctx);
             LSA_HIP(ctx, hipStreamSynchronize(ctx->stream));
             return ctx->fail(LSA_E_STATE, "lsa_solve_device: no result from the device");
@@ -898,18 +848,16 @@ int lsa_solve_device_end(lsa_ctx* ctx, lsa_solve_result_t* out)
     }
   }
   if (lsa_icp_trace_on()) std::fprintf(stderr, "[lm end] tag %u: failed %g code %g evals %g matches %g\n", out_tag, res[kResFailed], res[kResCode], res[kResEvaluations], res[kResMatches]);
-  // (the gate's case first and without waiting for the stream: the next iteration's gate may be waiting there for this thread)
-  if (res[kResFailed] == 2.) return ctx->fail(LSA_E_GATE, "lsa_solve_device: the gate in front of the solve gave up waiting for the host");
   if (res[kResFailed] != 0.)
   {
-    // iterations enqueued ahead are called off first (their gates wait for this thread, the stream would not drain)
+    // iterations enqueued ahead are called off first
     (void)lsa_icp_abandon(ctx);
     LSA_HIP(ctx, hipStreamSynchronize(ctx->stream));  // every block has given up or finished: the slots are quiet again
     ctx->lm_fallbacks++;
     return ctx->fail(LSA_E_STATE, "lsa_solve_device: a block waited too long for the others");
   }
   // the link this solve waited behind has served: its iteration ran, what its match announced stands
-  if (waited_behind >= 0 && waited_behind < kGateRing && ctx->gate_saved[waited_behind].link) ctx->gate_saved[waited_behind].used = false;
+  if (waited_behind >= 0 && waited_behind < kLinkRing) ctx->link_saved[waited_behind].used = false;
   std::memset(out, 0, sizeof(*out));
   for (int a = 0; a < 6; ++a) out->pose[a] = res[kResPose + a];
   out->initial_cost = res[kResInitial];
@@ -951,44 +899,24 @@ int lsa_solve_device(lsa_ctx* ctx, unsigned type_mask, const double prior[6], in
 }
 
 // ---- ICP iterations enqueued ahead of their inputs ------------------------------------------------------------------
-// A gate is one small launch that waits, on the device, for the host to post what the launches behind it need (the pose
-// the solve before it ended with: slam_lib/src/Slam.cxx:907, 940-946 and 1086, 1134-1142), or to call them off.  The
-// kernel-launch path (a dozen microseconds a launch) is then not between the end of a solve and the next search: the
-// launches are in the queue already and what remains is one store to coherent host memory and the gate's poll.
-int lsa_icp_gate(lsa_ctx* ctx)
-{
-  if (!ctx) return LSA_E_ARG;
-  if (!ctx->gate_host || !ctx->gate_dev) return ctx->fail(LSA_E_STATE, "lsa_icp_gate: no coherent host memory for the gates");
-  LSA_HIP(ctx, hipSetDevice(ctx->device));
-  const unsigned seq = ++ctx->gate_seq;
-  const int ticket = (int)(seq % kGateRing);
-  lsa_ctx::GateSaved& sv = ctx->gate_saved[ticket];
-  sv = lsa_ctx::GateSaved();
-  sv.used = true;
-  sv.seq = seq;
-  hipLaunchKernelGGL(k_icp_gate, dim3(1), dim3(kGateGranules), 0, ctx->stream, ctx->gate_host + (size_t)ticket * kGateGranules, ctx->gate_dev + (size_t)ticket * kGateWords, seq,
-                     (ctx->debug_gate_give_up_every > 0 && seq % (unsigned)ctx->debug_gate_give_up_every == 0) ? 1 : 0);
-  ctx->gate_current = ticket;
-  return ticket;
-}
-
-// A link is a gate without the kernel and without the host: the block on the device is written by the SOLVE in front of it
-// (k_lm_solve's leave_link: lsa_posemath.h's arithmetic, which the host repeats on the same result when it arrives), so that
-// between two iterations there is one kernel boundary -- no trip over the bus, no host thread on the path.  The ticket is
+// A link is a block on the device that carries what the launches of the next iteration need (the pose the solve before it
+// ended with: slam_lib/src/Slam.cxx:907, 940-946 and 1086, 1134-1142), or calls them off.  It is written by the SOLVE in
+// front of it (k_lm_solve's leave_link: lsa_posemath.h's arithmetic, which the host repeats on the same result when it
+// arrives), so that between two iterations there is one kernel boundary -- no kernel-launch path (a dozen microseconds a
+// launch), no trip over the bus, no host thread on the path.  The ticket is
 // reserved here, handed to lsa_solve_device_begin_linked as the block to leave, and what is enqueued after that solve
-// (lsa_match_types_gated, the next solve) waits behind it.
+// (lsa_match_types_linked, the next solve) waits behind it.
 int lsa_icp_link(lsa_ctx* ctx)
 {
   if (!ctx) return LSA_E_ARG;
-  if (!ctx->gate_dev || !ctx->motion_dev) return ctx->fail(LSA_E_STATE, "lsa_icp_link: no device memory for the links");
-  const unsigned seq = ctx->gate_seq + 1;
-  const int ticket = (int)(seq % kGateRing);
-  if (ctx->gate_saved[ticket].used) return ctx->fail(LSA_E_STATE, "lsa_icp_link: too many iterations enqueued ahead");
-  ctx->gate_seq = seq;
-  lsa_ctx::GateSaved& sv = ctx->gate_saved[ticket];
-  sv = lsa_ctx::GateSaved();
+  if (!ctx->link_dev || !ctx->motion_dev) return ctx->fail(LSA_E_STATE, "lsa_icp_link: no device memory for the links");
+  const unsigned seq = ctx->link_seq + 1;
+  const int ticket = (int)(seq % kLinkRing);
+  if (ctx->link_saved[ticket].used) return ctx->fail(LSA_E_STATE, "lsa_icp_link: too many iterations enqueued ahead");
+  ctx->link_seq = seq;
+  lsa_ctx::LinkSaved& sv = ctx->link_saved[ticket];
+  sv = lsa_ctx::LinkSaved();
   sv.used = true;
-  sv.link = true;
   sv.seq = seq;
   return ticket;
 }
@@ -1000,9 +928,9 @@ int lsa_icp_link_expected(const double x[6], int skipped, int successful_steps, 
 {
   if (!x || !link || !words) return LSA_E_ARG;
   using namespace posemath;
-  IcpGate g;
+  IcpLinkBlock g;
   std::memset(&g, 0, sizeof(g));
-  std::memset(words, 0, kGateWords * sizeof(unsigned long long));
+  std::memset(words, 0, kLinkWords * sizeof(unsigned long long));
   if (motion_after) std::memcpy(motion_after, link->motion, 16 * sizeof(double));
   if (skipped || successful_steps == 1) return LSA_OK;  // go = 0: nothing else of the block means anything
   const Pose T = FromXYZRPY(x);
@@ -1043,64 +971,22 @@ int lsa_icp_link_expected(const double x[6], int skipped, int successful_steps, 
 
 int lsa_icp_link_peek(lsa_ctx* ctx, int ticket, unsigned long long words[64])
 {
-  if (!ctx || !words || ticket < 0 || ticket >= kGateRing || !ctx->gate_dev) return ctx ? ctx->fail(LSA_E_ARG, "lsa_icp_link_peek: bad argument") : LSA_E_ARG;
+  if (!ctx || !words || ticket < 0 || ticket >= kLinkRing || !ctx->link_dev) return ctx ? ctx->fail(LSA_E_ARG, "lsa_icp_link_peek: bad argument") : LSA_E_ARG;
   LSA_HIP(ctx, hipSetDevice(ctx->device));
   LSA_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  LSA_HIP(ctx, hipMemcpy(words, ctx->gate_dev + (size_t)ticket * kGateWords, kGateWords * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+  LSA_HIP(ctx, hipMemcpy(words, ctx->link_dev + (size_t)ticket * kLinkWords, kLinkWords * sizeof(unsigned long long), hipMemcpyDeviceToHost));
   return LSA_OK;
-}
-
-static int gate_release(lsa_ctx* ctx, int ticket, const IcpGate* block)
-{
-  if (!ctx || ticket < 0 || ticket >= kGateRing || !ctx->gate_host || !ctx->gate_saved[ticket].used)
-    return ctx ? ctx->fail(LSA_E_ARG, "lsa_icp_post / lsa_icp_cancel: no such gate") : LSA_E_ARG;
-  unsigned long long* g = ctx->gate_host + (size_t)ticket * kGateGranules;
-  // which gate this slot serves now: the newest one enqueued with this ticket
-  unsigned seq = ctx->gate_seq;
-  while ((int)(seq % kGateRing) != ticket) --seq;
-  unsigned long long words[kGateWords] = {};
-  if (block) std::memcpy(words, block, sizeof(IcpGate));  // (word 0 = go = 1; called off: all zero)
-  // every granule carries the gate's number: the device has the block once it has seen it in all of them
-  for (int i = 0; i < kGateWords; ++i)
-  {
-    __atomic_store_n(g + 2 * i, ((unsigned long long)seq << 32) | (words[i] & 0xffffffffull), __ATOMIC_RELAXED);
-    __atomic_store_n(g + 2 * i + 1, ((unsigned long long)seq << 32) | (words[i] >> 32), __ATOMIC_RELAXED);
-  }
-  if (lsa_icp_trace_on()) std::fprintf(stderr, "[gate] ticket %d seq %u %s\n", ticket, seq, block ? "posted" : "called off");
-  ctx->gate_saved[ticket].used = false;
-  if (ctx->gate_current == ticket) ctx->gate_current = -1;
-  return LSA_OK;
-}
-
-int lsa_icp_post(lsa_ctx* ctx, int ticket, const double pose[16], const double prior[6], const double H0[16], const double H1[16], double t0, double t1)
-{
-  if (!ctx || !pose || !prior || ((H0 == nullptr) != (H1 == nullptr))) return ctx ? ctx->fail(LSA_E_ARG, "lsa_icp_post: bad argument") : LSA_E_ARG;
-  IcpGate g;
-  std::memset(&g, 0, sizeof(g));
-  g.go = 1;
-  row_major_to_rt(pose, g.in.pose.R, g.in.pose.t);
-  for (int a = 0; a < 6; ++a) g.in.x0[a] = prior[a];
-  if (H0) g.in.ic = make_interp_const(H0, H1, t0, t1);
-  return gate_release(ctx, ticket, &g);
 }
 
 int lsa_icp_cancel(lsa_ctx* ctx, int ticket)
 {
-  if (!ctx || ticket < 0 || ticket >= kGateRing) return LSA_E_ARG;
-  // what the launches behind the gate had announced on the host is taken back: they will not run
-  const lsa_ctx::GateSaved sv = ctx->gate_saved[ticket];
-  if (sv.link)
-  {
-    // (the device has called it off itself -- the solve in front left go = 0 -- or will never reach it)
-    if (!sv.used) return ctx->fail(LSA_E_ARG, "lsa_icp_cancel: no such link");
-    ctx->gate_saved[ticket].used = false;
-    if (ctx->gate_current == ticket) ctx->gate_current = -1;
-  }
-  else
-  {
-    const int rc = gate_release(ctx, ticket, nullptr);
-    if (rc) return rc;
-  }
+  if (!ctx || ticket < 0 || ticket >= kLinkRing) return LSA_E_ARG;
+  // what the launches behind the link had announced on the host is taken back: they will not run
+  // (the device has called it off itself -- the solve in front left go = 0 -- or will never reach it)
+  const lsa_ctx::LinkSaved sv = ctx->link_saved[ticket];
+  if (!sv.used) return ctx->fail(LSA_E_ARG, "lsa_icp_cancel: no such link");
+  ctx->link_saved[ticket].used = false;
+  if (ctx->link_current == ticket) ctx->link_current = -1;
   for (int k = 0; k < 3; ++k)
     if ((sv.mask >> k) & 1u)
     {
@@ -1120,14 +1006,14 @@ int lsa_icp_abandon(lsa_ctx* ctx)
   while (true)
   {
     int youngest = -1;
-    for (int t = 0; t < kGateRing; ++t)
-      if (ctx->gate_saved[t].used && (youngest < 0 || (int)(ctx->gate_saved[t].seq - ctx->gate_saved[youngest].seq) > 0)) youngest = t;
+    for (int t = 0; t < kLinkRing; ++t)
+      if (ctx->link_saved[t].used && (youngest < 0 || (int)(ctx->link_saved[t].seq - ctx->link_saved[youngest].seq) > 0)) youngest = t;
     if (youngest < 0) break;
-    if (lsa_icp_cancel(ctx, youngest) != LSA_OK) ctx->gate_saved[youngest].used = false;
+    if (lsa_icp_cancel(ctx, youngest) != LSA_OK) ctx->link_saved[youngest].used = false;
   }
   ctx->lm_pending.clear();
   ctx->lm_pending_wait.clear();
-  ctx->gate_current = -1;
+  ctx->link_current = -1;
   return LSA_OK;
 }
 
@@ -1137,8 +1023,7 @@ int lsa_debug_set(lsa_ctx* ctx, const char* name, int value)
   const std::string n(name);
   const lsa_ctx::ShapeKnobs& c = ctx->created_knobs;
   // the launch-shape knobs: the clamps of the environment variables read at creation (lsa_ctx.hip); negative restores
-  if (n == "gate_give_up_every") ctx->debug_gate_give_up_every = value;
-  else if (n == "lm_give_up_block") ctx->debug_lm_give_up_block = value;
+  if (n == "lm_give_up_block") ctx->debug_lm_give_up_block = value;
   else if (n == "lm_blocks") ctx->lm_blocks = value < 0 ? c.lm_blocks : std::min(std::max(value, 1), kLmBlocksMax);
   else if (n == "lm_records") ctx->lm_records = value < 0 ? c.lm_records : std::min(std::max(value, 256), 4096);
   else if (n == "lm_cache") ctx->lm_cache_slots = value < 0 ? c.lm_cache_slots : std::min(value, ctx->lm_cache_capacity);

@@ -147,9 +147,9 @@ int lsa_match(lsa_ctx* ctx, int slot, int type, int query_set, const lsa_match_p
 }
 
 static int match_types_impl(lsa_ctx* ctx, int slot, unsigned type_mask, int query_set, const lsa_match_params_t* p, const double pose[16], int* histograms,
-                            const InterpConst* undistort, int gate = -1, bool gate_undistorts = false)
+                            const InterpConst* undistort, int link = -1, bool link_undistorts = false)
 {
-  if (!ctx || !p || (!pose && gate < 0) || slot < 0 || slot > 1 || (type_mask & ~7u) || query_set < 0 || query_set > 2)
+  if (!ctx || !p || (!pose && link < 0) || slot < 0 || slot > 1 || (type_mask & ~7u) || query_set < 0 || query_set > 2)
     return ctx ? ctx->fail(LSA_E_ARG, "lsa_match_types: bad argument") : LSA_E_ARG;
   LSA_HIP(ctx, hipSetDevice(ctx->device));
   if (histograms) std::memset(histograms, 0, 3 * LSA_MATCH_NSTATUS * sizeof(int));
@@ -175,10 +175,10 @@ static int match_types_impl(lsa_ctx* ctx, int slot, unsigned type_mask, int quer
     int np = 0;
     for (int i = 0; i < nt; ++i)
     {
-      if (gate >= 0)
+      if (link >= 0)
       {
         // should the iteration be called off, what it announces here is taken back (lsa_icp_cancel)
-        lsa_ctx::GateSaved& sv = ctx->gate_saved[gate];
+        lsa_ctx::LinkSaved& sv = ctx->link_saved[link];
         const int k = types[i];
         sv.mask |= 1u << k;
         sv.sat[k] = ctx->match[k].sat; sv.k[k] = ctx->match[k].k; sv.valid[k] = ctx->match[k].valid;
@@ -190,7 +190,7 @@ static int match_types_impl(lsa_ctx* ctx, int slot, unsigned type_mask, int quer
     }
     if (np > 0)
     {
-      const int rc = enqueue_fused_match(ctx, preps, np, pose, ctx->stream, undistort, gate, gate_undistorts);
+      const int rc = enqueue_fused_match(ctx, preps, np, pose, ctx->stream, undistort, link, link_undistorts);
       if (rc) return rc;
     }
   }
@@ -260,18 +260,18 @@ int lsa_match_types_undistorted(lsa_ctx* ctx, int slot, unsigned type_mask, cons
   return match_types_impl(ctx, slot, type_mask, LSA_SET_WORKING, p, pose, histograms, &ic);
 }
 
-int lsa_match_types_gated(lsa_ctx* ctx, int slot, unsigned type_mask, int query_set, const lsa_match_params_t* p, int undistort)
+int lsa_match_types_linked(lsa_ctx* ctx, int slot, unsigned type_mask, int query_set, const lsa_match_params_t* p, int undistort)
 {
   if (!ctx || !p || slot < 0 || slot > 1 || (type_mask & ~7u) || query_set < 0 || query_set > 2)
-    return ctx ? ctx->fail(LSA_E_ARG, "lsa_match_types_gated: bad argument") : LSA_E_ARG;
-  if (ctx->gate_current < 0) return ctx->fail(LSA_E_STATE, "lsa_match_types_gated: no gate to wait behind (lsa_icp_gate)");
-  // only the one-launch form reads a gate; an undistortion must reach every keypoint of the working set (otherwise it is a
+    return ctx ? ctx->fail(LSA_E_ARG, "lsa_match_types_linked: bad argument") : LSA_E_ARG;
+  if (ctx->link_current < 0) return ctx->fail(LSA_E_STATE, "lsa_match_types_linked: no link to wait behind (lsa_icp_link)");
+  // only the one-launch form reads a link; an undistortion must reach every keypoint of the working set (otherwise it is a
   // launch of its own, which the caller has to enqueue once the motion is known)
   if (!ctx->fused_match || !ctx->fused_model) return 1;
   if (undistort && (query_set != LSA_SET_WORKING || !search_reaches_every_keypoint(ctx, slot, type_mask, p))) return 1;
   for (int k = 0; k < 3; ++k)
     if (((type_mask >> k) & 1u) && ctx->kp_n[query_set][k] > 0 && ctx->target[slot * 3 + k].m <= 0) return 1;  // (an empty target is answered by a fill, not by the search)
-  return match_types_impl(ctx, slot, type_mask, query_set, p, nullptr, nullptr, nullptr, ctx->gate_current, undistort != 0);
+  return match_types_impl(ctx, slot, type_mask, query_set, p, nullptr, nullptr, nullptr, ctx->link_current, undistort != 0);
 }
 
 int lsa_download_match(lsa_ctx* ctx, int type, uint8_t* status, double* weights, double* records, int capacity)

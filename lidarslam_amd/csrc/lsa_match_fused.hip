@@ -597,7 +597,7 @@ struct FusedArgs
   int fuse_model;  // the search kernel fits the models of its own keypoints (no second launch)
   int undistort;   // ... and first moves every keypoint by the motion `ic` interpolated at its own time (lsa_undistort), in place
   InterpConst ic;
-  const IcpGate* gate;  // not null: enqueued ahead of its inputs (lsa_icp_gate) -- pose and `ic` come from there, or nothing is done
+  const IcpLinkBlock* link;  // not null: enqueued ahead of its inputs (lsa_icp_link) -- pose and `ic` come from there, or nothing is done
 };
 
 struct SearchShared
@@ -849,7 +849,7 @@ __device__ __forceinline__ void search_whole_target(const float4* __restrict__ s
   merge_lists<KMAX, 64>(L, k, best);
 }
 
-// Pose and motion of the launch, into LDS: the launch's own arguments, or what the link / gate in front of it left on the
+// Pose and motion of the launch, into LDS: the launch's own arguments, or what the link in front of it left on the
 // device (enqueued ahead of its inputs: go == 1, or the iteration was called off and the workgroup returns false).  They
 // always go through ONE copy in LDS, whichever source they have: a pointer that may lead into the kernel's arguments or
 // elsewhere, and even a choice between the two value by value, makes the compiler move pose and motion (or all 1.4 KB of
@@ -858,11 +858,11 @@ __device__ __forceinline__ void search_whole_target(const float4* __restrict__ s
 __device__ __forceinline__ bool load_inputs(const FusedArgs& a, IcpInputs& gin)
 {
   __shared__ unsigned long long go;
-  if (a.gate)
+  if (a.link)
   {
     constexpr int words = (int)(sizeof(IcpInputs) / 8);
-    static_assert(words + 1 <= 256 && offsetof(IcpGate, in) == 8, "one word per thread, go in front");
-    const unsigned long long* src = reinterpret_cast<const unsigned long long*>(a.gate);
+    static_assert(words + 1 <= 256 && offsetof(IcpLinkBlock, in) == 8, "one word per thread, go in front");
+    const unsigned long long* src = reinterpret_cast<const unsigned long long*>(a.link);
     if ((int)threadIdx.x < words) reinterpret_cast<unsigned long long*>(&gin)[threadIdx.x] = src[1 + threadIdx.x];
     else if ((int)threadIdx.x == words) go = src[0];
   }
@@ -886,8 +886,8 @@ __device__ __forceinline__ void search_type(const FusedArgs& a, IcpInputs& gin, 
   const int tid = threadIdx.x, gl = tid % G, ql = tid / G;
   const int q = block * QB + ql;
   const bool active = q < t.nq;
-  // the keypoint first, on its way while the launch's inputs arrive: they do not depend on each other, and behind a link or a
-  // gate the inputs are a trip to memory of their own
+  // the keypoint first, on its way while the launch's inputs arrive: they do not depend on each other, and behind a link
+  // the inputs are a trip to memory of their own
   float4 q4 = {0.f, 0.f, 0.f, 0.f}, b4 = {0.f, 0.f, 0.f, 0.f};
   if (active)
   {
@@ -1136,7 +1136,7 @@ template <int KE, int KP, int KB>
 __global__ __launch_bounds__(kModelBlock) void k_model_all(FusedArgs a)
 {
   __shared__ ModelShared<KE, kModelBlock> sh;
-  if (a.gate && a.gate->go != 1ull) return;  // (only reached with a gate when a type's parameters are invalid: nothing is searched for it)
+  if (a.link && a.link->go != 1ull) return;  // (only reached with a link when a type's parameters are invalid: nothing is searched for it)
   int b = blockIdx.x;
   if (b < a.t[0].mblocks) { model_type<KE, LSA_EDGE, kModelBlock>(a.pose, a.t[0], b, sh); return; }
   b -= a.t[0].mblocks;
@@ -1172,11 +1172,11 @@ namespace lsa
 
 // Enqueues the matches `preps` describes (at most one per keypoint type, every one with a non-empty target and at
 // least one keypoint) as two launches on `st`: the searches of all types, then their model fits.
-int enqueue_fused_match(lsa_ctx* ctx, const MatchPrep* preps, int count, const double pose[16], hipStream_t st, const InterpConst* undistort, int gate, bool gate_undistorts)
+int enqueue_fused_match(lsa_ctx* ctx, const MatchPrep* preps, int count, const double pose[16], hipStream_t st, const InterpConst* undistort, int link, bool link_undistorts)
 {
   FusedArgs a;
   std::memset(&a, 0, sizeof(a));
-  if (gate >= 0) a.gate = reinterpret_cast<const IcpGate*>(ctx->gate_dev + (size_t)gate * kGateWords);
+  if (link >= 0) a.link = reinterpret_cast<const IcpLinkBlock*>(ctx->link_dev + (size_t)link * kLinkWords);
   else row_major_to_rt(pose, a.pose.R, a.pose.t);
   int kmax[3] = {1, 1, 1};
   const int lanes[3] = {kGE, kGP, kGB};
@@ -1220,7 +1220,7 @@ int enqueue_fused_match(lsa_ctx* ctx, const MatchPrep* preps, int count, const d
     a.undistort = 1;
     a.ic = *undistort;
   }
-  if (gate >= 0 && gate_undistorts) a.undistort = 1;
+  if (link >= 0 && link_undistorts) a.undistort = 1;
   a.fuse_model = ctx->fused_model ? 1 : 0;
   for (int k = 0; k < 3; ++k)
     if (a.t[k].mblocks > 0 && a.t[k].nblocks == 0) a.fuse_model = 0;

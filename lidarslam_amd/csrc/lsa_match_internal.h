@@ -23,9 +23,9 @@ struct InterpConst;
 InterpConst make_interp_const(const double H0[16], const double H1[16], double t0, double t1);  // lsa_transform.hip
 // undistort: every keypoint is first moved by that motion interpolated at its own time, in place (lsa_undistort's step, folded
 // into the search kernel); only when every keypoint of the set is among `preps` and is searched
-// gate >= 0: the launch waits behind that gate (lsa_icp_gate) and takes pose -- and, gate_undistorts, the undistortion -- from it
+// link >= 0: the launch waits behind that link (lsa_icp_link) and takes pose -- and, link_undistorts, the undistortion -- from it
 int enqueue_fused_match(lsa_ctx* ctx, const MatchPrep* preps, int count, const double pose[16], hipStream_t st, const InterpConst* undistort = nullptr,
-                        int gate = -1, bool gate_undistorts = false);
+                        int link = -1, bool link_undistorts = false);
 // lsa_match_staged.hip: one prepared match as the staged kernels; the exact kNN alone (k <= 5, 8, 16: three instantiations)
 void enqueue_staged_match(lsa_ctx* ctx, const MatchPrep& mp, const double pose[16], hipStream_t st);
 void enqueue_staged_knn(lsa_ctx* ctx, const lsa_point_t* q, int nq, const Rigid& pose, int k, float far_d2, int type, int ti, hipStream_t st, int* hist);

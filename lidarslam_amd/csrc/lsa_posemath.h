@@ -40,22 +40,21 @@ struct InterpConst
   int invalid;           // Time0 == Time1 or H0 ~ H1
 };
 
-// What an ICP iteration that was enqueued ahead of its inputs reads on the device once they are there -- handed over by
-// the host through a gate (lsa_icp_gate) or left by the solve in front of it (a link, lsa_icp_link): the pose the keypoints
-// are searched under, the optimiser's start point, the undistortion of the iteration before.  `go` comes first: 1 = run,
-// anything else = the launch does nothing (0 called off, 2 the gate gave up).
+// What an ICP iteration that was enqueued ahead of its inputs reads on the device once they are there -- left by the solve
+// in front of it (a link, lsa_icp_link): the pose the keypoints are searched under, the optimiser's start point, the
+// undistortion of the iteration before.  `go` comes first: 1 = run, anything else = the launch does nothing (0 called off).
 struct IcpInputs
 {
   Rigid pose;
   double x0[6];
   InterpConst ic;
 };
-struct IcpGate
+struct IcpLinkBlock
 {
   unsigned long long go;
   IcpInputs in;
 };
-static_assert(sizeof(IcpGate) % 8 == 0 && sizeof(IcpGate) <= 64 * 8, "a gate block is at most 64 words");
+static_assert(sizeof(IcpLinkBlock) % 8 == 0 && sizeof(IcpLinkBlock) <= 64 * 8, "a link block is at most 64 words");
 
 namespace posemath
 {

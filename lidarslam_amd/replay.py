@@ -127,7 +127,7 @@ class ConcurrentReplay:
         # 1810 against 2210 frames/s), where the host cores are there (2.6 per sequence against 1.4).
         params.setdefault("MapsOnDevice", 1 if len(seeds) == 1 else 0)
         # ICP loops enqueued whole, every solve leaving the next iteration's pose on the device (links: nothing spins on a
-        # hardware queue, unlike the gates of ICPAhead = 1, which side by side held up the other sequences' kernels)
+        # hardware queue and holds up the other sequences' kernels)
         params.setdefault("ICPAhead", 2)
         # worker threads woken ahead of their jobs poll for them: worth a core for one or two sequences, not for eight
         params.setdefault("WorkerPrewake", 1 if len(seeds) <= 2 else 0)

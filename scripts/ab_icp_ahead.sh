@@ -1,8 +1,8 @@
 #!/bin/bash
-# ICP loops in line (0), behind gates (1), enqueued whole behind links (2): one box, three alternations, then 8 sequences side by side
+# ICP loops in line (0), enqueued whole behind links (2): one box, three alternations, then 8 sequences side by side
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 for round in 1 2 3; do
-  for v in 0 1 2; do
+  for v in 0 2; do
     timeout -k 10 200 python bench.py --no-cpu-baseline --no-extra-legs --no-profile --param ICPAhead=$v 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); s=d['stage_ms_per_frame']

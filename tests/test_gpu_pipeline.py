@@ -108,7 +108,7 @@ def run_both(L, O, model, nframes, seed=1000, check_keypoints=True, **params):
         dp, da = pose_diff(To, Tg)
         worst = (max(worst[0], dp), max(worst[1], da))
         assert dp < 1e-4 and da < 1e-4, f"frame {f}: north-star tolerance exceeded ({dp} m, {da} rad)"
-        assert dp < 1e-7 and da < 1e-6, f"frame {f}: poses drift apart ({dp} m, {da} rad; gates that gave up: {sg.get_param('IcpGateTimeouts')}, solves redone on the host: {sg.get_param('DeviceSolveFallbacks')})"
+        assert dp < 1e-7 and da < 1e-6, f"frame {f}: poses drift apart ({dp} m, {da} rad; solves redone on the host: {sg.get_param('DeviceSolveFallbacks')})"
         if check_keypoints:
             for k in range(3):
                 assert sg.keypoints(k, which=2).tobytes() == so.keypoints(k, which=2).tobytes(), f"frame {f}: raw keypoints {k}"
@@ -865,9 +865,7 @@ def test_a_cloud_rewritten_after_it_was_announced_is_not_taken_over(L):
 @pytest.mark.gpu
 @pytest.mark.parametrize("model,nframes", [(16, 14), (64, 6)])
 def test_icp_iterations_enqueued_ahead_change_nothing_but_the_schedule(L, model, nframes):
-    """ICPAhead = 1: iteration i + 1 of both ICP loops waits behind a gate on the device while iteration i runs
-    (lsa_icp_gate / lsa_icp_post / lsa_icp_cancel).  ICPAhead = 2 (the default): the whole loop is enqueued at once and
-    every solve leaves the pose, the start point and the undistortion of the iteration behind it on the device
+    """ICPAhead = 2 (the default): the whole ICP loop is enqueued at once and every solve leaves the pose, the start point and the undistortion of the iteration behind it on the device
     (lsa_icp_link: lsa_posemath.h's arithmetic on the device, the host repeats it on the same results).  Same launches,
     same inputs, same order: poses, match counts and match statuses are those of the loop that enqueues every iteration
     when its pose is known, bit for bit."""
@@ -881,36 +879,32 @@ def test_icp_iterations_enqueued_ahead_change_nothing_but_the_schedule(L, model,
             poses.append(s.world_transform())
             used.append(s.get_param("TotalMatchedKeypoints"))
             status.append([s.match_status(loc, k)[0].tobytes() for loc in (0, 1) for k in (L.EDGE, L.PLANE)])
-        fb, gt = s.get_param("DeviceSolveFallbacks"), s.get_param("IcpGateTimeouts")
+        fb = s.get_param("DeviceSolveFallbacks")
         cov = s.covariance()
         s.close()
-        return np.array(poses), used, status, cov, fb, gt
+        return np.array(poses), used, status, cov, fb
 
     inline = run(ICPAhead=0)
-    for mode in (1, 2):
-        ahead = run(ICPAhead=mode)
-        assert ahead[4] == 0 and ahead[5] == 0
-        assert np.array_equal(inline[0], ahead[0]) and inline[1] == ahead[1] and inline[2] == ahead[2], mode
-        assert np.array_equal(inline[3], ahead[3]), mode
+    ahead = run(ICPAhead=2)
+    assert ahead[4] == 0
+    assert np.array_equal(inline[0], ahead[0]) and inline[1] == ahead[1] and inline[2] == ahead[2]
+    assert np.array_equal(inline[3], ahead[3])
     # ... also without the refined undistortion (nothing rides in the search kernel), with a single LM iteration allowed, with
-    # more iterations than one loop enqueues behind links, in 2D, with the maps on the host and without any map update
+    # more iterations than one loop enqueues behind links (it falls back to the in-line loop), in 2D, with the maps on the host
+    # and without any map update
     for extra in ({"Undistortion": 1}, {"Undistortion": 0}, {"LocalizationICPMaxIter": 1, "EgoMotionICPMaxIter": 2}, {"LocalizationICPMaxIter": 8, "EgoMotionICPMaxIter": 6},
                   {"TwoDMode": 1}, {"MapsOnDevice": 0}, {"UndistortInSearch": 0}):
         a = run(ICPAhead=0, **extra)
-        for mode in (1, 2):
-            b = run(ICPAhead=mode, **extra)
-            assert np.array_equal(a[0], b[0]) and a[1] == b[1] and a[2] == b[2], (extra, mode)
-            assert b[4] == 0 and b[5] == 0
+        b = run(ICPAhead=2, **extra)
+        assert np.array_equal(a[0], b[0]) and a[1] == b[1] and a[2] == b[2], extra
+        assert b[4] == 0
 
 
 @pytest.mark.gpu
 def test_the_fall_backs_of_the_bounded_device_waits_are_exercised(L, O):
-    """Two waits on the device are bounded and have a fall-back on the host that a healthy run never takes:
-    (a) the gate of an ICP iteration enqueued ahead gives up after 50 ms without an answer -- nothing of the iteration ran,
-        the caller does it again in line (LSA_E_GATE);
-    (b) a workgroup of the one-launch solve that waits 20 ms for the others' sums abandons the exchange, all give up, the
-        trust-region loop runs on the host (LSA_E_STATE, DeviceSolveFallbacks).
-    lsa_debug_set provokes both; the results must be those of the undisturbed run / of the oracle."""
+    """One wait on the device is bounded and has a fall-back on the host that a healthy run never takes: a workgroup of the
+    one-launch solve that waits 20 ms for the others' sums abandons the exchange, all give up, the trust-region loop runs on
+    the host (LSA_E_STATE, DeviceSolveFallbacks).  lsa_debug_set provokes it; the results must be those of the oracle."""
     frames = [L.synth_frame(16, 1000, f) for f in range(8)]
 
     def run(prepare=None, **params):
@@ -921,27 +915,23 @@ def test_the_fall_backs_of_the_bounded_device_waits_are_exercised(L, O):
                 prepare(s, f)
             s.add_frame(pts, stamp, f)
             poses.append(s.world_transform())
-        out = np.array(poses), s.get_param("IcpGateTimeouts"), s.get_param("DeviceSolveFallbacks"), s.get_param("TotalMatchedKeypoints")
+        out = np.array(poses), s.get_param("DeviceSolveFallbacks")
         s.close()
         return out
 
     plain = run()
-    assert plain[1] == 0 and plain[2] == 0
-    # (a) every third gate gives up
-    gates = run(lambda s, f: s.context().debug_set("gate_give_up_every", 3) if f == 0 else None, ICPAhead=1)
-    assert gates[1] >= 4 and gates[2] == 0
-    assert np.array_equal(plain[0], gates[0]) and plain[3] == gates[3]
-    # (b) one solve of frames 2 and 5 is abandoned by its second workgroup (or by its only one)
+    assert plain[1] == 0
+    # one solve of frames 2 and 5 is abandoned by its second workgroup (or by its only one)
     so = O.Slam(EgoMotion=3)
     ref = []
     for f, (pts, stamp) in enumerate(frames):
         so.add_frame(pts, stamp, f)
         ref.append(so.world_transform())
     # (with the loops enqueued whole -- ICPAhead = 2, the default -- the solve that gives up leaves "do not run" for the
-    #  iterations behind it, the host redoes it and goes on in line; with gates; with nothing enqueued ahead)
-    for block, mode in ((1, 2), (0, 2), (1, 1), (0, 0)):
+    #  iterations behind it, the host redoes it and goes on in line; with nothing enqueued ahead)
+    for block, mode in ((1, 2), (0, 2), (0, 0)):
         lm = run(lambda s, f: s.context().debug_set("lm_give_up_block", block) if f in (2, 5) else None, ICPAhead=mode)
-        assert lm[2] == 2 and lm[1] == 0
+        assert lm[1] == 2
         for f in range(len(frames)):
             dp, da = pose_diff(ref[f], lm[0][f])
             assert dp < 1e-7 and da < 1e-6, (block, f, dp, da)

@@ -1,6 +1,6 @@
 """Wheel odometer and IMU gravity terms in the localization solve, on the device: lsa_accumulate and the one-launch
 solve (k_lm_solve) with the terms against the host-driven loop and the host evaluation of the terms, an optimum
-worked out here by a damped Newton iteration, and the pipeline (in-line, gated and linked ICP iterations) fed with
+worked out here by a damped Newton iteration, and the pipeline (in-line and linked ICP iterations) fed with
 measurement streams built from the generator's ground truth."""
 import math
 
@@ -229,7 +229,7 @@ def feed_both():
 def test_pipeline_forms_agree_with_the_terms_on(L, model, nframes):
     params = dict(EgoMotion=3, WheelOdomWeight=20.0, GravityWeight=50.0)
     runs = {name: run(L, model, nframes, dict(params, **extra), feed_both()) for name, extra in
-            (("inline", {"DeviceLM": 0}), ("links", {}), ("gates", {"ICPAhead": 1}))}
+            (("inline", {"DeviceLM": 0}), ("links", {}))}
     for name, r in runs.items():
         assert r["fallbacks"] == 0, name
         assert np.abs(r["poses"][:, :3, 3] - runs["links"]["poses"][:, :3, 3]).max() < 1e-9, name

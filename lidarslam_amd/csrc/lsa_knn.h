@@ -66,16 +66,50 @@ __device__ __forceinline__ knn_key make_key(float d2, int idx) { return ((knn_ke
 __device__ __forceinline__ float key_d2(knn_key k) { return __uint_as_float((unsigned)(k >> 32)); }
 __device__ __forceinline__ int key_idx(knn_key k) { return (int)(unsigned)(k & 0xffffffffu); }
 
-// minimum of the key over the G lanes of a group; result in every lane
+// A/B switches of the list keeping (default on; -DLSA_...=0 builds the integer forms for comparison)
+#ifndef LSA_KEY_F64
+#define LSA_KEY_F64 1   // compare-swaps of the lanes' sorted lists by v_min_f64 / v_max_f64
+#endif
+#ifndef LSA_GMIN_F64
+#define LSA_GMIN_F64 1  // group_min's stages by v_min_f64
+#endif
+
+// Minimum / maximum of two keys through the f64 pipe.  A key at or below kKeyEmpty has sign bit 0 and an upper word of
+// at most 0x7f800000: read as a double its exponent field is at most 0x7f8 -- finite, never NaN -- and the IEEE order of
+// such doubles is the unsigned order of their bits (tests/test_knn_key_order.py).  Keys whose distance bits are below
+// 0x00100000 (distance 0 among them) are f64 DENORMALS: the kernels are compiled with float_denorm_mode_16_64 = 3, so
+// v_min_f64 / v_max_f64 hand them through unchanged (no flush) -- tests/test_gpu_knn_list_keeping.py covers the range.
+// Plain instructions: __builtin_fmin / fmax add a canonicalising v_max_f64 each under IEEE mode.
+__device__ __forceinline__ knn_key key_min_f64(knn_key a, knn_key b)
+{
+  double r;
+  asm("v_min_f64 %0, %1, %2" : "=v"(r) : "v"(__longlong_as_double((long long)a)), "v"(__longlong_as_double((long long)b)));
+  return (knn_key)__double_as_longlong(r);
+}
+__device__ __forceinline__ knn_key key_max_f64(knn_key a, knn_key b)
+{
+  double r;
+  asm("v_max_f64 %0, %1, %2" : "=v"(r) : "v"(__longlong_as_double((long long)a)), "v"(__longlong_as_double((long long)b)));
+  return (knn_key)__double_as_longlong(r);
+}
+
+// minimum of the key over the G lanes of a group; result in every lane.  Keys with sign bit 0 only (distances are sums of
+// squares): one v_min_f64 per stage instead of a 64-bit compare and two selects.
 template <int G>
 __device__ __forceinline__ void group_min(knn_key& m)
 {
+  auto lower = [](knn_key a, knn_key b) {
+#if LSA_GMIN_F64
+    return key_min_f64(a, b);
+#else
+    return b < a ? b : a;
+#endif
+  };
   auto dpp = [&](auto ctrl) {
     constexpr int c = decltype(ctrl)::value;
     const unsigned lo = (unsigned)__builtin_amdgcn_update_dpp(0, (int)(unsigned)(m & 0xffffffffu), c, 0xF, 0xF, true);
     const unsigned hi = (unsigned)__builtin_amdgcn_update_dpp(0, (int)(unsigned)(m >> 32), c, 0xF, 0xF, true);
-    const knn_key o = ((knn_key)hi << 32) | lo;
-    m = o < m ? o : m;
+    m = lower(m, ((knn_key)hi << 32) | lo);
   };
   // inside a row of 16 lanes the exchange is a DPP operand modifier (no LDS round trip):
   // quad_perm [1,0,3,2], quad_perm [2,3,0,1], row_half_mirror, row_mirror
@@ -91,15 +125,13 @@ __device__ __forceinline__ void group_min(knn_key& m)
   {
     const auto lo = __builtin_amdgcn_permlane16_swap((unsigned)(m & 0xffffffffu), (unsigned)(m & 0xffffffffu), false, false);
     const auto hi = __builtin_amdgcn_permlane16_swap((unsigned)(m >> 32), (unsigned)(m >> 32), false, false);
-    const knn_key a = ((knn_key)hi[0] << 32) | lo[0], b = ((knn_key)hi[1] << 32) | lo[1];
-    m = b < a ? b : a;
+    m = lower(((knn_key)hi[0] << 32) | lo[0], ((knn_key)hi[1] << 32) | lo[1]);
   }
   if (G >= 64)
   {
     const auto lo = __builtin_amdgcn_permlane32_swap((unsigned)(m & 0xffffffffu), (unsigned)(m & 0xffffffffu), false, false);
     const auto hi = __builtin_amdgcn_permlane32_swap((unsigned)(m >> 32), (unsigned)(m >> 32), false, false);
-    const knn_key a = ((knn_key)hi[0] << 32) | lo[0], b = ((knn_key)hi[1] << 32) | lo[1];
-    m = b < a ? b : a;
+    m = lower(((knn_key)hi[0] << 32) | lo[0], ((knn_key)hi[1] << 32) | lo[1]);
   }
 }
 

@@ -20,9 +20,10 @@
 // device list to the tail kernel: one wavefront per query over the whole target.  Same (distance, index) total
 // order everywhere => the result does not depend on the route taken.
 //
-// Model.  The leaders of a block's groups leave their neighbour lists in LDS; after one barrier the first 256 / G
-// threads fit the models of the block's keypoints, one thread each, dense -- the other wavefronts are gone and
-// their SIMDs take the next block's search.
+// Model.  One-launch form: the G lanes that searched a keypoint gather its neighbours' points, filter them and sum up
+// their covariance side by side (group_stage: the lists stay in registers, nine sums per keypoint go to LDS); after one
+// barrier the workgroup's first wavefront finishes the 256 / G matches, one lane each (finish_model).  Two-launch form:
+// the lists go to memory and k_model_all fits one keypoint per thread.
 #include <cmath>
 #include "lsa_knn.h"
 #include "lsa_match_internal.h"
@@ -69,23 +70,33 @@ struct LaneList
 #pragma unroll
     for (int s = 0; s < KMAX; ++s) v[s] = kKeyEmpty;
   }
+  // one compare-swap: lo <- the smaller, hi <- the larger.  Both at or below kKeyEmpty (what a list holds, and what the
+  // guards in front let through): v_min_f64 + v_max_f64 on the bits instead of a 64-bit compare and four selects
+  static __device__ __forceinline__ void order2(knn_key& lo, knn_key& hi)
+  {
+#if LSA_KEY_F64
+    const knn_key a = key_min_f64(lo, hi), b = key_max_f64(lo, hi);
+    lo = a;
+    hi = b;
+#else
+    const knn_key a = lo, b = hi;
+    const bool sw = b < a;
+    lo = sw ? b : a;
+    hi = sw ? a : b;
+#endif
+  }
   __device__ __forceinline__ void insert(knn_key key)
   {
 #ifdef LSA_ABLATE_INSERT
     if (key < v[0]) v[0] = key;  // (timing experiment only: wrong results)
     return;
 #endif
+    // the guard stays an integer compare: a key above kKeyEmpty (a NaN distance, whatever its sign) is never inserted
     if (key < v[KMAX - 1])
     {
       v[KMAX - 1] = key;
 #pragma unroll
-      for (int s = KMAX - 1; s > 0; --s)
-      {
-        const knn_key a = v[s - 1], b = v[s];
-        const bool sw = b < a;
-        v[s - 1] = sw ? b : a;
-        v[s] = sw ? a : b;
-      }
+      for (int s = KMAX - 1; s > 0; --s) order2(v[s - 1], v[s]);
     }
   }
 };
@@ -255,9 +266,9 @@ __device__ __forceinline__ unsigned store_rows(const RowTable& tb, int base, int
 
 // The scan of a block: its `total` candidates, in the order of the table, are dealt to the G lanes of the group ROUND
 // ROBIN (candidate c -> lane c mod G): the lanes of a group read neighbouring addresses of the cell-sorted array -- one
-// or two cache lines per load instruction and group where contiguous per-lane runs touched G (the kernel is bound by
-// the gathers' cache-line throughput in the vector memory pipeline, not by arithmetic) -- and the k nearest spread over
-// the lanes.  Every lane walks U candidates per turn, the loads of the next turn in flight while the current one is
+// or two cache lines per load instruction and group where contiguous per-lane runs touched G -- and the k nearest spread
+// over the lanes (the kernel is bound by its vector instructions, two thirds of them list keeping, not by the gathers:
+// DESIGN 3.2).  Every lane walks U candidates per turn, the loads of the next turn in flight while the current one is
 // compared, and follows the table's runs by itself (one entry = start, end, candidates in front; all rows non-empty, a
 // (0, 0, total) sentinel behind them).  It keeps its k best in a sorted list in registers.  base: the group's table of
 // the block, nent: its entries.

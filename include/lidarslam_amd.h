@@ -1128,11 +1128,12 @@ int lsa_kplog_replay_range(lsa_ctx* ctx, unsigned type_mask, const double* poses
  * lsa_slam_register_logged_frames produces.  The whole definition -- retraction t += R rho, R = R Exp(phi); the error
  * e = [Rz^T (Ri^T (tj - ti) - tz) ; Log(Rz^T Ri^T Rj)]; its exact Jacobians; the order of every sum; the rules for small angles
  * and angles near pi; the Levenberg-Marquardt loop with a preconditioned conjugate gradient inside -- is
- * lidarslam_amd/csrc/lsa_pose_graph.h, compiled for the host and the device alike.  No GPS, no robust kernels.
+ * lidarslam_amd/csrc/lsa_pose_graph.h, compiled for the host and the device alike.  No robust kernels.  Position
+ * priors (GPS fixes) and the reference's RunPoseGraphOptimization on top of them: the next comment.
  * - lsa_pgo_edge_t: from -> to, `relative` the measured inv(P[from]) * P[to] (row-major 4x4), `information` its 6x6 weight
  *   over (translation, rotation) in the tangent of the retraction, row-major.  from != to.
- * - fixed[n]: non-zero = the pose is held.  At least one pose must be fixed and every free pose needs an edge; an index
- *   out of range, from == to or a non-finite entry: all LSA_E_ARG, nothing written.
+ * - fixed[n]: non-zero = the pose is held.  At least one pose must be fixed (or, in the calls with priors, a prior given) and
+ *   every free pose needs an edge; an index out of range, from == to or a non-finite entry: all LSA_E_ARG, nothing written.
  * - lsa_pgo_params_init: max_iterations 50, pcg_max_iter 500, pcg_tolerance 1e-8, initial_lambda 1e-6, lambda_shrink 0.25,
  *   lambda_grow 8, lambda_min 1e-12, lambda_max 1e12, gradient_tolerance 1e-12, step_tolerance 1e-10, cost_tolerance 1e-13,
  *   preconditioner 0 (block tridiagonal; 1 = its diagonal blocks alone, a knob for measurements), apply 0,
@@ -1202,6 +1203,43 @@ typedef struct lsa_pgo_result_t
   int32_t termination, reserved;
   const char* message;
 } lsa_pgo_result_t;
+/* Position priors in the pose graph.
+ * - lsa_pgo_prior_t: the measured `position` of a point carried by pose `pose`, `information` its 3x3 weight (row-major).  All
+ *   priors of a solve share offset16 = (Ro, to), a row-major 4x4 (may be NULL when k is 0): d = Ri^T (g - ti),
+ *   e = Ro^T (d - to), A = de/ddelta_i = [-Ro^T, Ro^T [d]x].  For GPS fixes offset16 = inverse(gpsToSensor), as the reference
+ *   sets it.  A graph needs a fixed pose or a prior; every free pose still needs an edge; a prior on a fixed pose counts in the
+ *   cost alone; an index out of range, a non-finite entry or k < 0: LSA_E_ARG, nothing written.  The cost is 1/2 sum chi2 over
+ *   the m edge values followed by the k prior values.
+ * - lsa_pgo_solve_priors[_host], lsa_pgo_assemble_priors[_host], lsa_pgo_spmv_priors[_host]: the calls above with priors; with
+ *   k = 0 they are those calls, bit for bit (which are now their k = 0 case).  lsa_pgo_linearize_priors[_host] -> e[3 k],
+ *   blocks[42 k] (Haa[36] ga[6] per prior), chi2[k] (k_pgo_linearize_priors / its host twin).  lsa_pgo_prior_jacobian_host:
+ *   e[3], A[18] (3x6 row-major) of ONE prior.  lsa_pgo_premultiply[_host]: out[i] = W * P[i]; lsa_pgo_reanchor[_host]:
+ *   out[i] = inv(P[0]) * P[i] (k_pgo_premultiply, k_pgo_reanchor / their host twins; poses_out may be poses16).
+ * - lsa_pgo_information_from_covariance3: the inverse of a symmetric positive definite 3x3 (host); LSA_E_ARG otherwise.
+ * - lsa_gps_match_trajectory (host): per GPS fix, in order, match_out[f] = the index of the logged pose, dated
+ *   slam_times[j] + time_offset, nearest in time to gps_times[f] within max_time_diff (inclusive; the reference uses 0.1 s), the
+ *   earlier of two equally near; -1 when there is none, and for a fix whose pose is the pose of the fix accepted before it.
+ *   Times finite and ascending, else LSA_E_ARG.
+ * - lsa_trajectory_alignment (host): the rigid T (row-major 4x4) minimising sum |T from_i - to_i|^2 over `pairs` pairs of
+ *   points (xyz each), Horn's closed form; for fewer than three pairs, or when the two largest eigenvalues of Horn's matrix are
+ *   within 1e-9 of the largest (collinear tracks), x -> R x + (to_0 - from_0) with R the least rotation carrying the chord
+ *   from_last - from_0 onto to_last - to_0 (the identity when a chord vanishes).
+ * - lsa_slam_run_pose_graph_optimization(gps_times, gps_xyz, gps_cov9, G, gps_to_sensor16, time_offset, params, poses17_out,
+ *   capacity, result): Slam::RunPoseGraphOptimization.  Fixes are matched to the logged poses (above, 0.1 s); W = the alignment
+ *   of the matched antenna positions (P_i * inverse(gps_to_sensor)).t onto their fixes; the graph: the logged poses premultiplied
+ *   by W, all free, the odometry chain as lsa_slam_optimize_logged_trajectory builds it (params->odometry_information), a prior
+ *   per matched fix with the inverse of its covariance; solved by lsa_pgo_solve_priors on the handle's scratch context.  Out:
+ *   gps_to_sensor16 = the optimized pose 0 (in the GPS frame), rows i = inv(opt[0]) * opt[i] with the logged times; returns n.
+ *   params->apply as above.  LSA_E_STATE as lsa_slam_optimize_logged_trajectory; LSA_E_ARG, the text naming the case, for fewer
+ *   than two logged poses or fixes, time intervals that do not overlap (closed intervals, logged times + time_offset), no fix
+ *   matched, a covariance that is not positive definite (the fix is named), bad parameters; nothing changed.
+ *   "PoseGraphSeconds" is updated. */
+typedef struct lsa_pgo_prior_t
+{
+  int32_t pose, reserved;
+  double position[3];
+  double information[9];
+} lsa_pgo_prior_t;
 void lsa_pgo_params_init(lsa_pgo_params_t* params);
 int lsa_pgo_solve_host(const double* poses16, int n, const uint8_t* fixed, const lsa_pgo_edge_t* edges, int m, const lsa_pgo_params_t* params, double* poses_out,
                        lsa_pgo_result_t* result);
@@ -1223,6 +1261,32 @@ int lsa_pgo_edge_jacobians_host(const double* poses16, int n, const lsa_pgo_edge
 int lsa_pgo_information_from_covariance(const double* cov36, double* info36);
 int lsa_slam_optimize_logged_trajectory(lsa_slam* s, const lsa_pgo_edge_t* loop_edges, int m, const lsa_pgo_params_t* params, double* poses17_out, int capacity,
                                         lsa_pgo_result_t* result);
+int lsa_pgo_solve_priors_host(const double* poses16, int n, const uint8_t* fixed, const lsa_pgo_edge_t* edges, int m, const lsa_pgo_prior_t* priors, int k,
+                              const double* offset16, const lsa_pgo_params_t* params, double* poses_out, lsa_pgo_result_t* result);
+int lsa_pgo_solve_priors(lsa_ctx* ctx, const double* poses16, int n, const uint8_t* fixed, const lsa_pgo_edge_t* edges, int m, const lsa_pgo_prior_t* priors, int k,
+                         const double* offset16, const lsa_pgo_params_t* params, double* poses_out, lsa_pgo_result_t* result);
+int lsa_pgo_linearize_priors_host(const double* poses16, int n, const lsa_pgo_prior_t* priors, int k, const double* offset16, double* e_out, double* blocks_out,
+                                  double* chi2_out);
+int lsa_pgo_linearize_priors(lsa_ctx* ctx, const double* poses16, int n, const lsa_pgo_prior_t* priors, int k, const double* offset16, double* e_out, double* blocks_out,
+                             double* chi2_out);
+int lsa_pgo_assemble_priors_host(const double* poses16, int n, const uint8_t* fixed, const lsa_pgo_edge_t* edges, int m, const lsa_pgo_prior_t* priors, int k,
+                                 const double* offset16, double lambda, double* D_out, double* g_out, double* L_out, double* U_out);
+int lsa_pgo_assemble_priors(lsa_ctx* ctx, const double* poses16, int n, const uint8_t* fixed, const lsa_pgo_edge_t* edges, int m, const lsa_pgo_prior_t* priors, int k,
+                            const double* offset16, double lambda, double* D_out, double* g_out, double* L_out, double* U_out);
+int lsa_pgo_spmv_priors_host(const double* poses16, int n, const uint8_t* fixed, const lsa_pgo_edge_t* edges, int m, const lsa_pgo_prior_t* priors, int k,
+                             const double* offset16, double lambda, const double* p, double* q);
+int lsa_pgo_spmv_priors(lsa_ctx* ctx, const double* poses16, int n, const uint8_t* fixed, const lsa_pgo_edge_t* edges, int m, const lsa_pgo_prior_t* priors, int k,
+                        const double* offset16, double lambda, const double* p, double* q);
+int lsa_pgo_prior_jacobian_host(const double* poses16, int n, const lsa_pgo_prior_t* prior, const double* offset16, double* e3, double* A18);
+int lsa_pgo_premultiply_host(const double* poses16, int n, const double* W16, double* poses_out);
+int lsa_pgo_premultiply(lsa_ctx* ctx, const double* poses16, int n, const double* W16, double* poses_out);
+int lsa_pgo_reanchor_host(const double* poses16, int n, double* poses_out);
+int lsa_pgo_reanchor(lsa_ctx* ctx, const double* poses16, int n, double* poses_out);
+int lsa_pgo_information_from_covariance3(const double* cov9, double* info9);
+int lsa_gps_match_trajectory(const double* slam_times, int n, const double* gps_times, int G, double time_offset, double max_time_diff, int32_t* match_out);
+int lsa_trajectory_alignment(const double* from_xyz, const double* to_xyz, int pairs, double* T16_out);
+int lsa_slam_run_pose_graph_optimization(lsa_slam* s, const double* gps_times, const double* gps_xyz, const double* gps_cov9, int G, double* gps_to_sensor16,
+                                         double time_offset, const lsa_pgo_params_t* params, double* poses17_out, int capacity, lsa_pgo_result_t* result);
 
 /* ---- the rolling voxel map (host) ---------------------------
  * LidarSlam::RollingGrid -- slam_lib/include/LidarSlam/RollingGrid.h:63-212,

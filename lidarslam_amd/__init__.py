@@ -90,6 +90,10 @@ ABI_SYMBOLS = [
     "lsa_pgo_params_init", "lsa_pgo_solve_host", "lsa_pgo_solve", "lsa_pgo_linearize_host", "lsa_pgo_linearize", "lsa_pgo_assemble_host", "lsa_pgo_assemble",
     "lsa_pgo_tridiagonal_solve_host", "lsa_pgo_tridiagonal_solve", "lsa_pgo_spmv_host", "lsa_pgo_spmv", "lsa_pgo_information_from_covariance",
     "lsa_pgo_retract_host", "lsa_pgo_retract", "lsa_pgo_edge_jacobians_host", "lsa_slam_optimize_logged_trajectory",
+    "lsa_pgo_solve_priors_host", "lsa_pgo_solve_priors", "lsa_pgo_linearize_priors_host", "lsa_pgo_linearize_priors", "lsa_pgo_assemble_priors_host",
+    "lsa_pgo_assemble_priors", "lsa_pgo_spmv_priors_host", "lsa_pgo_spmv_priors", "lsa_pgo_prior_jacobian_host", "lsa_pgo_premultiply_host", "lsa_pgo_premultiply",
+    "lsa_pgo_reanchor_host", "lsa_pgo_reanchor", "lsa_pgo_information_from_covariance3", "lsa_gps_match_trajectory", "lsa_trajectory_alignment",
+    "lsa_slam_run_pose_graph_optimization",
 ]
 
 PCD_ASCII, PCD_BINARY, PCD_BINARY_COMPRESSED = 0, 1, 2  # PCDFormat (PointCloudStorage.h:60-65)
@@ -279,6 +283,9 @@ def place_select(distance, shift, poses, times, query, sectors=60, min_travelled
 # lsa_pgo_edge_t as a numpy record: from -> to, the measured inv(P[from]) @ P[to] (row-major 4x4), its 6x6 information
 PGO_EDGE_DTYPE = np.dtype([("from", np.int32), ("to", np.int32), ("relative", np.float64, (16,)), ("information", np.float64, (36,))])
 PGO_EDGE_BLOCK = 120  # doubles of an edge's block record: Haa[36] Hab[36] Hbb[36] ga[6] gb[6]
+# lsa_pgo_prior_t: a measured position of the point carried by `pose` behind the solve's offset, and its 3x3 information
+PGO_PRIOR_DTYPE = np.dtype([("pose", np.int32), ("reserved", np.int32), ("position", np.float64, (3,)), ("information", np.float64, (9,))])
+PGO_PRIOR_BLOCK = 42  # doubles of a prior's block record: Haa[36] ga[6]
 PGO_MAX_ITERATIONS, PGO_GRADIENT, PGO_STEP, PGO_COST, PGO_LAMBDA_CEILING, PGO_LINEAR_SOLVER_FAILED = range(6)
 
 
@@ -340,6 +347,19 @@ def pose_graph_edges(edges):
     return out
 
 
+def pose_graph_priors(priors):
+    """A PGO_PRIOR_DTYPE array from one, or from an iterable of (pose, position (3,), information (3, 3)); None: no prior."""
+    if isinstance(priors, np.ndarray) and priors.dtype == PGO_PRIOR_DTYPE:
+        return np.ascontiguousarray(priors)
+    priors = [] if priors is None else list(priors)
+    out = np.zeros(len(priors), PGO_PRIOR_DTYPE)
+    for k, (i, g, W) in enumerate(priors):
+        out[k]["pose"] = int(i)
+        out[k]["position"] = np.asarray(g, np.float64).reshape(3)
+        out[k]["information"] = np.asarray(W, np.float64).reshape(9)
+    return out
+
+
 def _pgo_graph(poses, fixed, edges):
     P = np.ascontiguousarray(np.asarray(poses, np.float64).reshape(-1, 16))
     E = pose_graph_edges(edges)
@@ -349,23 +369,35 @@ def _pgo_graph(poses, fixed, edges):
     return P, f, E
 
 
-def _pgo_run(what, ctx, poses, fixed, edges, make_out, *extra):
-    """One of the lsa_pgo_* calls that take (poses, n, [fixed,] edges, m, extra..., outputs...); ctx None: the _host twin."""
+def _pgo_priors(priors, offset):
+    """-> the arguments (priors, k, offset16) of a lsa_pgo_*_priors call and the arrays they point into"""
+    R = pose_graph_priors(priors)
+    O = np.ascontiguousarray(np.asarray(np.eye(4) if offset is None else offset, np.float64).reshape(16))
+    return [ptr(R) if R.size else None, R.size, ptr(O)], (R, O)
+
+
+def _pgo_run(what, ctx, poses, fixed, edges, make_out, *extra, priors=None, offset=None):
+    """One of the lsa_pgo_* calls that take (poses, n, [fixed,] edges, m, extra..., outputs...); ctx None: the _host twin.
+    With priors the call is its _priors form, which takes (priors, k, offset16) behind the edges."""
     P, f, E = _pgo_graph(poses, fixed, edges)
     L = lib()
+    pa, keep = ([], None) if priors is None else _pgo_priors(priors, offset)
+    if priors is not None:
+        what += "_priors"
     fn = getattr(L, what if ctx is not None else what + "_host")
     outs = make_out(P.shape[0], E.size)
-    args = ([ctx.h] if ctx is not None else []) + [ptr(P), P.shape[0]] + ([] if f is None else [ptr(f)]) + [ptr(E) if E.size else None, E.size]
+    args = ([ctx.h] if ctx is not None else []) + [ptr(P), P.shape[0]] + ([] if f is None else [ptr(f)]) + [ptr(E) if E.size else None, E.size] + pa
     rc = fn(*args, *extra, *[ptr(o) if isinstance(o, np.ndarray) else o for o in outs])
     if rc < 0:
         raise _error(fn.__name__, rc, L.lsa_last_error(ctx.h).decode() if ctx is not None else "the graph is outside the definition")
     return outs
 
 
-def pose_graph_solve(poses, fixed, edges, ctx=None, params=None, **kw):
+def pose_graph_solve(poses, fixed, edges, ctx=None, params=None, priors=None, offset=None, **kw):
     """Levenberg-Marquardt on the pose graph (lidarslam_amd/csrc/lsa_pose_graph.h): poses (n, 4, 4), fixed (n,) flags, edges as
     pose_graph_edges takes them -> (poses (n, 4, 4), PoseGraphResult).  ctx None: the host statement (lsa_pgo_solve_host); a
-    Context: the device solver (lsa_pgo_solve).  params: a PoseGraphParams, or its fields as keywords."""
+    Context: the device solver (lsa_pgo_solve).  params: a PoseGraphParams, or its fields as keywords.  priors: position
+    priors as pose_graph_priors takes them, behind the (4, 4) offset (None: the identity) -- lsa_pgo_solve_priors[_host]."""
     p = params if params is not None else PoseGraphParams(**kw)
     r = PoseGraphResultStruct()
     P, f, E = _pgo_graph(poses, fixed, edges)
@@ -373,20 +405,18 @@ def pose_graph_solve(poses, fixed, edges, ctx=None, params=None, **kw):
         raise _error("lsa_pgo_solve", E_ARG, "fixed flags are needed")
     out = np.zeros((P.shape[0], 4, 4))
     L = lib()
-    if ctx is None:
-        rc = L.lsa_pgo_solve_host(ptr(P), P.shape[0], ptr(f), ptr(E) if E.size else None, E.size, C.byref(p), ptr(out), C.byref(r))
-        if rc < 0:
-            raise _error("lsa_pgo_solve_host", rc, "the graph or the parameters are outside the definition")
-    else:
-        rc = L.lsa_pgo_solve(ctx.h, ptr(P), P.shape[0], ptr(f), ptr(E) if E.size else None, E.size, C.byref(p), ptr(out), C.byref(r))
-        if rc < 0:
-            raise _error("lsa_pgo_solve", rc, L.lsa_last_error(ctx.h).decode())
+    name = "lsa_pgo_solve" + ("" if priors is None else "_priors") + ("_host" if ctx is None else "")
+    pa, keep = ([], None) if priors is None else _pgo_priors(priors, offset)
+    args = ([] if ctx is None else [ctx.h]) + [ptr(P), P.shape[0], ptr(f), ptr(E) if E.size else None, E.size] + pa + [C.byref(p), ptr(out), C.byref(r)]
+    rc = getattr(L, name)(*args)
+    if rc < 0:
+        raise _error(name, rc, "the graph or the parameters are outside the definition" if ctx is None else L.lsa_last_error(ctx.h).decode())
     return out, PoseGraphResult(r)
 
 
-def pose_graph_solve_host(poses, fixed, edges, params=None, **kw):
+def pose_graph_solve_host(poses, fixed, edges, params=None, priors=None, offset=None, **kw):
     """pose_graph_solve without a device."""
-    return pose_graph_solve(poses, fixed, edges, None, params, **kw)
+    return pose_graph_solve(poses, fixed, edges, None, params, priors, offset, **kw)
 
 
 def pose_graph_linearize(poses, edges, ctx=None):
@@ -395,20 +425,70 @@ def pose_graph_linearize(poses, edges, ctx=None):
     return e, b, c
 
 
-def pose_graph_assemble(poses, fixed, edges, lam=0.0, ctx=None):
+def pose_graph_linearize_priors(poses, priors, offset=None, ctx=None):
+    """-> e (k, 3), blocks (k, 42), chi2 (k,) of the position priors: k_pgo_linearize_priors with a Context, its host twin without."""
+    P = np.ascontiguousarray(np.asarray(poses, np.float64).reshape(-1, 16))
+    pa, keep = _pgo_priors(priors, offset)
+    k = pa[1]
+    e, b, c = np.zeros((k, 3)), np.zeros((k, PGO_PRIOR_BLOCK)), np.zeros(k)
+    L = lib()
+    if ctx is None:
+        rc = L.lsa_pgo_linearize_priors_host(ptr(P), P.shape[0], *pa, ptr(e), ptr(b), ptr(c))
+    else:
+        rc = L.lsa_pgo_linearize_priors(ctx.h, ptr(P), P.shape[0], *pa, ptr(e), ptr(b), ptr(c))
+    if rc < 0:
+        raise _error("lsa_pgo_linearize_priors", rc, L.lsa_last_error(ctx.h).decode() if ctx is not None else "a prior is outside the definition")
+    return e, b, c
+
+
+def pose_graph_prior_jacobian(poses, prior, offset=None):
+    """e (3,) and A = de/ddelta (3, 6) of one prior (pose, position, information); the host statement."""
+    P = np.ascontiguousarray(np.asarray(poses, np.float64).reshape(-1, 16))
+    pa, keep = _pgo_priors([prior] if isinstance(prior, tuple) else prior, offset)
+    e, A = np.zeros(3), np.zeros((3, 6))
+    rc = lib().lsa_pgo_prior_jacobian_host(ptr(P), P.shape[0], pa[0], pa[2], ptr(e), ptr(A))
+    if rc < 0:
+        raise _error("lsa_pgo_prior_jacobian_host", rc, "the prior is outside the definition")
+    return e, A
+
+
+def pose_graph_assemble(poses, fixed, edges, lam=0.0, ctx=None, priors=None, offset=None):
     """-> D (n, 6, 6) damped by lam, g (n, 6), L (n, 6, 6) = block (i, i-1), U (n, 6, 6) = block (i, i+1)."""
     D, g, Lo, U = _pgo_run("lsa_pgo_assemble", ctx, poses, fixed, edges, lambda n, m: [np.zeros((n, 6, 6)), np.zeros((n, 6)), np.zeros((n, 6, 6)), np.zeros((n, 6, 6))],
-                           C.c_double(lam))
+                           C.c_double(lam), priors=priors, offset=offset)
     return D, g, Lo, U
 
 
-def pose_graph_spmv(poses, fixed, edges, lam, p, ctx=None):
+def pose_graph_spmv(poses, fixed, edges, lam, p, ctx=None, priors=None, offset=None):
     """q = H_lambda p (n, 6), the blocks beyond the chain included."""
     pv = np.ascontiguousarray(np.asarray(p, np.float64).reshape(-1, 6))
     if pv.shape[0] != np.asarray(poses).reshape(-1, 16).shape[0]:
         raise _error("lsa_pgo_spmv", E_ARG, "a vector of another length than the poses")
-    q, = _pgo_run("lsa_pgo_spmv", ctx, poses, fixed, edges, lambda n, m: [np.zeros((n, 6))], C.c_double(lam), ptr(pv))
+    q, = _pgo_run("lsa_pgo_spmv", ctx, poses, fixed, edges, lambda n, m: [np.zeros((n, 6))], C.c_double(lam), ptr(pv), priors=priors, offset=offset)
     return q
+
+
+def pose_graph_premultiply(poses, W, ctx=None):
+    """W @ poses[i] for every pose (k_pgo_premultiply with a Context, its host twin without)."""
+    P = np.ascontiguousarray(np.asarray(poses, np.float64).reshape(-1, 16))
+    Wm = np.ascontiguousarray(np.asarray(W, np.float64).reshape(16))
+    out = np.zeros((P.shape[0], 4, 4))
+    lb = lib()
+    rc = lb.lsa_pgo_premultiply_host(ptr(P), P.shape[0], ptr(Wm), ptr(out)) if ctx is None else lb.lsa_pgo_premultiply(ctx.h, ptr(P), P.shape[0], ptr(Wm), ptr(out))
+    if rc < 0:
+        raise _error("lsa_pgo_premultiply", rc, lb.lsa_last_error(ctx.h).decode() if ctx is not None else "bad argument")
+    return out
+
+
+def pose_graph_reanchor(poses, ctx=None):
+    """inv(poses[0]) @ poses[i] for every pose (k_pgo_reanchor with a Context, its host twin without)."""
+    P = np.ascontiguousarray(np.asarray(poses, np.float64).reshape(-1, 16))
+    out = np.zeros((P.shape[0], 4, 4))
+    lb = lib()
+    rc = lb.lsa_pgo_reanchor_host(ptr(P), P.shape[0], ptr(out)) if ctx is None else lb.lsa_pgo_reanchor(ctx.h, ptr(P), P.shape[0], ptr(out))
+    if rc < 0:
+        raise _error("lsa_pgo_reanchor", rc, lb.lsa_last_error(ctx.h).decode() if ctx is not None else "bad argument")
+    return out
 
 
 def pose_graph_tridiagonal_solve(D, L, U, b, ctx=None):
@@ -463,6 +543,44 @@ def information_from_covariance(cov):
     if rc < 0:
         raise _error("lsa_pgo_information_from_covariance", rc, "not a symmetric positive definite matrix")
     return out
+
+
+def information_from_covariance3(cov):
+    """The inverse of a symmetric positive definite 3x3 (lsa_pgo_information_from_covariance3); raises for anything else."""
+    c = np.ascontiguousarray(np.asarray(cov, np.float64).reshape(9))
+    out = np.zeros((3, 3))
+    rc = lib().lsa_pgo_information_from_covariance3(ptr(c), ptr(out))
+    if rc < 0:
+        raise _error("lsa_pgo_information_from_covariance3", rc, "not a symmetric positive definite matrix")
+    return out
+
+
+def gps_match_trajectory(slam_times, gps_times, time_offset=0.0, max_time_diff=0.1):
+    """Per GPS fix the index of the logged pose (dated slam_times + time_offset) nearest in time within max_time_diff, the
+    earlier of two equally near; -1 for none and for a fix whose pose the fix accepted before it already took
+    (lsa_gps_match_trajectory).  Times ascending."""
+    s = np.ascontiguousarray(np.asarray(slam_times, np.float64).reshape(-1))
+    g = np.ascontiguousarray(np.asarray(gps_times, np.float64).reshape(-1))
+    out = np.full(g.size, -2, np.int32)
+    rc = lib().lsa_gps_match_trajectory(ptr(s) if s.size else None, s.size, ptr(g) if g.size else None, g.size, float(time_offset), float(max_time_diff),
+                                        ptr(out) if g.size else None)
+    if rc < 0:
+        raise _error("lsa_gps_match_trajectory", rc, "times that are not finite and ascending, or a negative bound")
+    return out
+
+
+def trajectory_alignment(from_xyz, to_xyz):
+    """The rigid (4, 4) T minimising sum |T from_i - to_i|^2 over the pairs (Horn's closed form; the reference's rough
+    estimate for fewer than three pairs or collinear tracks) -- lsa_trajectory_alignment."""
+    a = np.ascontiguousarray(np.asarray(from_xyz, np.float64).reshape(-1, 3))
+    b = np.ascontiguousarray(np.asarray(to_xyz, np.float64).reshape(-1, 3))
+    if a.shape != b.shape:
+        raise _error("lsa_trajectory_alignment", E_ARG, "as many points from as to")
+    T = np.zeros((4, 4))
+    rc = lib().lsa_trajectory_alignment(ptr(a) if a.size else None, ptr(b) if b.size else None, a.shape[0], ptr(T))
+    if rc < 0:
+        raise _error("lsa_trajectory_alignment", rc, "no pair, or a non-finite coordinate")
+    return T
 
 
 class SensorTerms(C.Structure):
@@ -793,6 +911,23 @@ def lib():
     L.lsa_pgo_retract_host.argtypes = [vp, i32, vp, vp]
     L.lsa_pgo_retract.argtypes = [vp, vp, i32, vp, vp]
     L.lsa_pgo_edge_jacobians_host.argtypes = [vp, i32, vp, vp, vp, vp]
+    L.lsa_pgo_solve_priors_host.argtypes = [vp, i32, vp, vp, i32, vp, i32, vp, vp, vp, vp]
+    L.lsa_pgo_solve_priors.argtypes = [vp, vp, i32, vp, vp, i32, vp, i32, vp, vp, vp, vp]
+    L.lsa_pgo_linearize_priors_host.argtypes = [vp, i32, vp, i32, vp, vp, vp, vp]
+    L.lsa_pgo_linearize_priors.argtypes = [vp, vp, i32, vp, i32, vp, vp, vp, vp]
+    L.lsa_pgo_assemble_priors_host.argtypes = [vp, i32, vp, vp, i32, vp, i32, vp, f64, vp, vp, vp, vp]
+    L.lsa_pgo_assemble_priors.argtypes = [vp, vp, i32, vp, vp, i32, vp, i32, vp, f64, vp, vp, vp, vp]
+    L.lsa_pgo_spmv_priors_host.argtypes = [vp, i32, vp, vp, i32, vp, i32, vp, f64, vp, vp]
+    L.lsa_pgo_spmv_priors.argtypes = [vp, vp, i32, vp, vp, i32, vp, i32, vp, f64, vp, vp]
+    L.lsa_pgo_prior_jacobian_host.argtypes = [vp, i32, vp, vp, vp, vp]
+    L.lsa_pgo_premultiply_host.argtypes = [vp, i32, vp, vp]
+    L.lsa_pgo_premultiply.argtypes = [vp, vp, i32, vp, vp]
+    L.lsa_pgo_reanchor_host.argtypes = [vp, i32, vp]
+    L.lsa_pgo_reanchor.argtypes = [vp, vp, i32, vp]
+    L.lsa_pgo_information_from_covariance3.argtypes = [vp, vp]
+    L.lsa_gps_match_trajectory.argtypes = [vp, i32, vp, i32, f64, f64, vp]
+    L.lsa_trajectory_alignment.argtypes = [vp, vp, i32, vp]
+    L.lsa_slam_run_pose_graph_optimization.argtypes = [vp, vp, vp, vp, i32, vp, f64, vp, vp, i32, vp]
     L.lsa_slam_optimize_logged_trajectory.argtypes = [vp, vp, i32, vp, vp, i32, vp]
     L.lsa_slam_set_trajectory_and_rebuild_maps.argtypes = [vp, vp, i32]
     L.lsa_slam_logged_frames.argtypes = [vp]
@@ -1391,17 +1526,26 @@ class Context:
 
     # ---- the log's descriptor store (lsa_kplog_describe / _descriptors / _place_search): place recognition
     # ---- pose graph (lsa_pose_graph.hip); the module functions of the same names without a Context are the host statement
-    def pose_graph_solve(self, poses, fixed, edges, params=None, **kw):
-        return pose_graph_solve(poses, fixed, edges, self, params, **kw)
+    def pose_graph_solve(self, poses, fixed, edges, params=None, priors=None, offset=None, **kw):
+        return pose_graph_solve(poses, fixed, edges, self, params, priors, offset, **kw)
+
+    def pose_graph_linearize_priors(self, poses, priors, offset=None):
+        return pose_graph_linearize_priors(poses, priors, offset, self)
+
+    def pose_graph_premultiply(self, poses, W):
+        return pose_graph_premultiply(poses, W, self)
+
+    def pose_graph_reanchor(self, poses):
+        return pose_graph_reanchor(poses, self)
 
     def pose_graph_linearize(self, poses, edges):
         return pose_graph_linearize(poses, edges, self)
 
-    def pose_graph_assemble(self, poses, fixed, edges, lam=0.0):
-        return pose_graph_assemble(poses, fixed, edges, lam, self)
+    def pose_graph_assemble(self, poses, fixed, edges, lam=0.0, priors=None, offset=None):
+        return pose_graph_assemble(poses, fixed, edges, lam, self, priors, offset)
 
-    def pose_graph_spmv(self, poses, fixed, edges, lam, p):
-        return pose_graph_spmv(poses, fixed, edges, lam, p, self)
+    def pose_graph_spmv(self, poses, fixed, edges, lam, p, priors=None, offset=None):
+        return pose_graph_spmv(poses, fixed, edges, lam, p, self, priors, offset)
 
     def pose_graph_tridiagonal_solve(self, D, L, U, b):
         return pose_graph_tridiagonal_solve(D, L, U, b, self)
@@ -1731,6 +1875,32 @@ class Slam:
         got = self._check(self.L.lsa_slam_optimize_logged_trajectory(self.h, ptr(E) if E.size else None, E.size, C.byref(p), ptr(rows), rows.shape[0], C.byref(r)),
                           "lsa_slam_optimize_logged_trajectory")
         return rows[:got, :16].reshape(-1, 4, 4).copy(), rows[:got, 16].copy(), PoseGraphResult(r)
+
+    def run_pose_graph_optimization(self, gps_times, gps_xyz, gps_cov, gps_to_sensor=None, apply=True, time_offset=0.0, params=None, **kw):
+        """Slam::RunPoseGraphOptimization (lsa_slam_run_pose_graph_optimization): the odometry chain of the log, every pose free,
+        plus a position prior per GPS fix matched to a logged pose by time; solved on the device from the track laid onto the
+        fixes, then brought back onto logged pose 0.  gps_times (G,), gps_xyz (G, 3), gps_cov (G, 3, 3); gps_to_sensor (4, 4):
+        the antenna's pose in BASE (None: the identity).  apply=True hands the result to set_trajectory.  kw: PoseGraphParams'
+        fields; odometry_information defaults to 1, the reference's rule.
+        -> (poses (n, 4, 4), times (n,), gps_to_sensor (4, 4) = the optimized pose 0 in the GPS frame, PoseGraphResult, matches (G,))"""
+        if params is None:
+            kw.setdefault("odometry_information", 1)
+        p = params if params is not None else PoseGraphParams(**kw)
+        p.apply = int(bool(apply))
+        t = np.ascontiguousarray(np.asarray(gps_times, np.float64).reshape(-1))
+        x = np.ascontiguousarray(np.asarray(gps_xyz, np.float64).reshape(-1, 3))
+        c = np.ascontiguousarray(np.asarray(gps_cov, np.float64).reshape(-1, 9))
+        if not (x.shape[0] == c.shape[0] == t.size):
+            raise _error("lsa_slam_run_pose_graph_optimization", E_ARG, "as many positions and covariances as times")
+        cal = np.ascontiguousarray(np.asarray(np.eye(4) if gps_to_sensor is None else gps_to_sensor, np.float64).reshape(4, 4).copy())
+        n = self._check(self.L.lsa_slam_logged_frames(self.h), "lsa_slam_logged_frames")
+        rows = np.zeros((max(n, 1), 17))
+        r = PoseGraphResultStruct()
+        got = self._check(self.L.lsa_slam_run_pose_graph_optimization(self.h, ptr(t) if t.size else None, ptr(x) if t.size else None, ptr(c) if t.size else None, t.size,
+                                                                      ptr(cal), float(time_offset), C.byref(p), ptr(rows), rows.shape[0], C.byref(r)),
+                          "lsa_slam_run_pose_graph_optimization")
+        times = rows[:got, 16].copy()
+        return rows[:got, :16].reshape(-1, 4, 4).copy(), times, cal, PoseGraphResult(r), gps_match_trajectory(times, t, time_offset)
 
     def recognize_place(self, query, capacity=5, **params):
         """Place recognition: the logged frames before `query` that look like it -> [(frame, distance, shift, yaw)], best

@@ -81,25 +81,33 @@ double Dot(const std::vector<double>& a, const std::vector<double>& b)
 
 struct System
 {
-  std::vector<double> e, blocks, chi2, D, dg, g, L, U;
-  void Size(int n, int m)
+  std::vector<double> e, blocks, chi2, pe, pblocks, D, dg, g, L, U;  // chi2: the m edge values, then the k prior values
+  void Size(int n, int m, int k = 0)
   {
     e.resize(static_cast<size_t>(m) * 6);
     blocks.resize(static_cast<size_t>(m) * pg::kEdgeBlock);
-    chi2.resize(static_cast<size_t>(m));
+    chi2.resize(static_cast<size_t>(m) + static_cast<size_t>(k));
+    pe.resize(static_cast<size_t>(k) * 3);
+    pblocks.resize(static_cast<size_t>(k) * pg::kPriorBlock);
     D.resize(static_cast<size_t>(n) * 36);
     L.resize(D.size());
     U.resize(D.size());
     dg.resize(static_cast<size_t>(n) * 6);
     g.resize(dg.size());
   }
-  double Linearize(const double* poses, const lsa_pgo_edge_t* edges, int m)
+  double Linearize(const double* poses, const lsa_pgo_edge_t* edges, int m, const lsa_pgo_prior_t* priors = nullptr, int np = 0, const pg::Pose* O = nullptr)
   {
     double F = 0.;
     for (int k = 0; k < m; ++k)
     {
       pg::linearize_edge(poses, edges[k], &e[6 * static_cast<size_t>(k)], &blocks[static_cast<size_t>(k) * pg::kEdgeBlock], &chi2[static_cast<size_t>(k)]);
       F += chi2[static_cast<size_t>(k)];
+    }
+    for (int k = 0; k < np; ++k)
+    {
+      const size_t at = static_cast<size_t>(m) + static_cast<size_t>(k);
+      pg::linearize_prior(poses, priors[k], *O, &pe[3 * static_cast<size_t>(k)], &pblocks[static_cast<size_t>(k) * pg::kPriorBlock], &chi2[at]);
+      F += chi2[at];
     }
     return 0.5 * F;
   }
@@ -109,7 +117,7 @@ struct System
     for (int i = 0; i < G.n; ++i)
     {
       const size_t b = 36 * static_cast<size_t>(i), c = 6 * static_cast<size_t>(i);
-      pg::assemble_row(i, G.n, fixed, v, edges, blocks.data(), lambda, &D[b], &dg[c], &g[c], &L[b], &U[b]);
+      pg::assemble_row(i, G.n, fixed, v, edges, blocks.data(), pblocks.data(), lambda, &D[b], &dg[c], &g[c], &L[b], &U[b]);
     }
   }
 };
@@ -147,9 +155,29 @@ int PgoCheckEdges(const double* poses16, int n, const lsa_pgo_edge_t* edges, int
   return LSA_OK;
 }
 
-int PgoBuild(const double* poses16, int n, const unsigned char* fixed, const lsa_pgo_edge_t* edges, int m, PoseGraph* g, std::string* why)
+int PgoCheckPriors(const double* poses16, int n, const lsa_pgo_prior_t* priors, int k, const double* offset16, std::string* why)
+{
+  auto no = [&](const std::string& w) {
+    if (why) *why = w;
+    return LSA_E_ARG;
+  };
+  if (!poses16 || n < 1 || k < 0 || (k > 0 && (!priors || !offset16))) return no("bad argument");
+  if (k == 0) return LSA_OK;
+  if (!all_finite(poses16, 16 * n)) return no("a pose has a non-finite entry");
+  if (!all_finite(offset16, 16)) return no("the priors' offset has a non-finite entry");
+  for (int a = 0; a < k; ++a)
+  {
+    if (priors[a].pose < 0 || priors[a].pose >= n) return no("prior " + std::to_string(a) + " names a pose outside 0.." + std::to_string(n - 1));
+    if (!all_finite(priors[a].position, 3) || !all_finite(priors[a].information, 9)) return no("prior " + std::to_string(a) + " has a non-finite entry");
+  }
+  return LSA_OK;
+}
+
+int PgoBuild(const double* poses16, int n, const unsigned char* fixed, const lsa_pgo_edge_t* edges, int m, PoseGraph* g, std::string* why, const lsa_pgo_prior_t* priors,
+             int np, const double* offset16)
 {
   if (const int rc = PgoCheckEdges(poses16, n, edges, m, why); rc != LSA_OK) return rc;
+  if (const int rc = PgoCheckPriors(poses16, n, priors, np, offset16, why); rc != LSA_OK) return rc;
   auto no = [&](const std::string& w) {
     if (why) *why = w;
     return LSA_E_ARG;
@@ -157,9 +185,18 @@ int PgoBuild(const double* poses16, int n, const unsigned char* fixed, const lsa
   if (!fixed) return no("bad argument");
   bool anyFixed = false;
   for (int i = 0; i < n; ++i) anyFixed = anyFixed || fixed[i] != 0;
-  if (!anyFixed) return no("no pose is fixed");
+  if (!anyFixed && np == 0) return no("no pose is fixed and there is no prior");
   g->n = n;
   g->m = m;
+  g->k = np;
+  g->prior_start.assign(static_cast<size_t>(n) + 1, 0);
+  for (int a = 0; a < np; ++a) ++g->prior_start[static_cast<size_t>(priors[a].pose) + 1];
+  for (int i = 0; i < n; ++i) g->prior_start[static_cast<size_t>(i) + 1] += g->prior_start[static_cast<size_t>(i)];
+  g->prior_of.assign(static_cast<size_t>(np), 0);
+  {
+    std::vector<int> pat(g->prior_start.begin(), g->prior_start.end() - 1);
+    for (int a = 0; a < np; ++a) g->prior_of[static_cast<size_t>(pat[static_cast<size_t>(priors[a].pose)]++)] = a;
+  }
   g->row_start.assign(static_cast<size_t>(n) + 1, 0);
   g->loop_start.assign(static_cast<size_t>(n) + 1, 0);
   auto beyond = [&](int a, int b) { return !fixed[a] && !fixed[b] && a - b != 1 && b - a != 1; };
@@ -210,8 +247,8 @@ bool PgoTridiagonalSolve(int n, const double* D, const double* L, const double* 
   return true;
 }
 
-int PgoSolve(const double* poses16, int n, const unsigned char* fixed, const lsa_pgo_edge_t* edges, int m, const lsa_pgo_params_t* params, double* poses_out,
-             lsa_pgo_result_t* result, std::string* why)
+int PgoSolve(const double* poses16, int n, const unsigned char* fixed, const lsa_pgo_edge_t* edges, int m, const lsa_pgo_prior_t* priors, int np, const double* offset16,
+             const lsa_pgo_params_t* params, double* poses_out, lsa_pgo_result_t* result, std::string* why)
 {
   lsa_pgo_params_t p;
   lsa_pgo_params_init(&p);
@@ -222,16 +259,18 @@ int PgoSolve(const double* poses16, int n, const unsigned char* fixed, const lsa
     return LSA_E_ARG;
   }
   PoseGraph G;
-  if (const int rc = PgoBuild(poses16, n, fixed, edges, m, &G, why); rc != LSA_OK) return rc;
+  if (const int rc = PgoBuild(poses16, n, fixed, edges, m, &G, why, priors, np, offset16); rc != LSA_OK) return rc;
   const pg::Graph view = G.view();
+  pg::Pose O = pg::load(poses16);  // unused without priors
+  if (np > 0) O = pg::load(offset16);
   const size_t nv = static_cast<size_t>(n) * 6;
   std::vector<double> x(poses16, poses16 + 16 * static_cast<size_t>(n)), cand(x.size());
   System S;
-  S.Size(n, m);
+  S.Size(n, m, np);
   std::vector<double> delta(nv), r(nv), z(nv), pv(nv), q(nv), zeros;
   lsa_pgo_result_t R;
   std::memset(&R, 0, sizeof(R));
-  double F = S.Linearize(x.data(), edges, m);
+  double F = S.Linearize(x.data(), edges, m, priors, np, &O);
   R.initial_cost = F;
   double lambda = p.initial_lambda;
   int term = LSA_PGO_MAX_ITERATIONS;
@@ -287,13 +326,14 @@ int PgoSolve(const double* poses16, int n, const unsigned char* fixed, const lsa
     for (int i = 0; i < n; ++i) pg::store(pg::retract(pg::load(&x[16 * static_cast<size_t>(i)]), &delta[6 * static_cast<size_t>(i)]), &cand[16 * static_cast<size_t>(i)]);
     double Fn = 0.;
     for (int k = 0; k < m; ++k) Fn += pg::edge_chi2(cand.data(), edges[k]);
+    for (int k = 0; k < np; ++k) Fn += pg::prior_chi2(cand.data(), priors[k], O);
     Fn *= 0.5;
     if (model > 0. && pg::finite_d(Fn) && F - Fn > 0.)
     {
       const double dec = F - Fn;
       x = cand;
       const bool small = dec <= p.cost_tolerance * F;
-      F = S.Linearize(x.data(), edges, m);
+      F = S.Linearize(x.data(), edges, m, priors, np, &O);
       ++R.accepted_steps;
       R.largest_step = step > R.largest_step ? step : R.largest_step;
       lambda = lambda * p.lambda_shrink > p.lambda_min ? lambda * p.lambda_shrink : p.lambda_min;
@@ -344,7 +384,48 @@ void lsa_pgo_params_init(lsa_pgo_params_t* p)
 int lsa_pgo_solve_host(const double* poses16, int n, const uint8_t* fixed, const lsa_pgo_edge_t* edges, int m, const lsa_pgo_params_t* params, double* poses_out,
                        lsa_pgo_result_t* result)
 {
-  return host::PgoSolve(poses16, n, fixed, edges, m, params, poses_out, result, nullptr);
+  return host::PgoSolve(poses16, n, fixed, edges, m, nullptr, 0, nullptr, params, poses_out, result, nullptr);
+}
+
+int lsa_pgo_solve_priors_host(const double* poses16, int n, const uint8_t* fixed, const lsa_pgo_edge_t* edges, int m, const lsa_pgo_prior_t* priors, int k,
+                              const double* offset16, const lsa_pgo_params_t* params, double* poses_out, lsa_pgo_result_t* result)
+{
+  return host::PgoSolve(poses16, n, fixed, edges, m, priors, k, offset16, params, poses_out, result, nullptr);
+}
+
+int lsa_pgo_linearize_priors_host(const double* poses16, int n, const lsa_pgo_prior_t* priors, int k, const double* offset16, double* e_out, double* blocks_out,
+                                  double* chi2_out)
+{
+  if (!e_out || !blocks_out || !chi2_out) return LSA_E_ARG;
+  if (const int rc = host::PgoCheckPriors(poses16, n, priors, k, offset16, nullptr); rc != LSA_OK) return rc;
+  if (k == 0) return LSA_OK;
+  const pg::Pose O = pg::load(offset16);
+  for (int a = 0; a < k; ++a) pg::linearize_prior(poses16, priors[a], O, e_out + 3 * static_cast<size_t>(a), blocks_out + static_cast<size_t>(a) * pg::kPriorBlock, chi2_out + a);
+  return LSA_OK;
+}
+
+int lsa_pgo_prior_jacobian_host(const double* poses16, int n, const lsa_pgo_prior_t* prior, const double* offset16, double* e3, double* A18)
+{
+  if (!e3 || !A18 || !prior) return LSA_E_ARG;
+  if (const int rc = host::PgoCheckPriors(poses16, n, prior, 1, offset16, nullptr); rc != LSA_OK) return rc;
+  pg::prior_eval(pg::load(poses16 + 16 * static_cast<size_t>(prior->pose)), pg::load(offset16), prior->position, e3, A18);
+  return LSA_OK;
+}
+
+int lsa_pgo_premultiply_host(const double* poses16, int n, const double* W16, double* poses_out)
+{
+  if (!poses16 || !W16 || !poses_out || n < 1) return LSA_E_ARG;
+  const pg::Pose W = pg::load(W16);
+  for (int i = 0; i < n; ++i) pg::store(pg::compose(W, pg::load(poses16 + 16 * static_cast<size_t>(i))), poses_out + 16 * static_cast<size_t>(i));
+  return LSA_OK;
+}
+
+int lsa_pgo_reanchor_host(const double* poses16, int n, double* poses_out)
+{
+  if (!poses16 || !poses_out || n < 1) return LSA_E_ARG;
+  const pg::Pose A = pg::load(poses16);  // read before pose 0 is written: poses_out may be poses16
+  for (int i = 0; i < n; ++i) pg::store(pg::inverse_compose(A, pg::load(poses16 + 16 * static_cast<size_t>(i))), poses_out + 16 * static_cast<size_t>(i));
+  return LSA_OK;
 }
 
 int lsa_pgo_linearize_host(const double* poses16, int n, const lsa_pgo_edge_t* edges, int m, double* e_out, double* blocks_out, double* chi2_out)
@@ -358,12 +439,19 @@ int lsa_pgo_linearize_host(const double* poses16, int n, const lsa_pgo_edge_t* e
 int lsa_pgo_assemble_host(const double* poses16, int n, const uint8_t* fixed, const lsa_pgo_edge_t* edges, int m, double lambda, double* D_out, double* g_out,
                           double* L_out, double* U_out)
 {
+  return lsa_pgo_assemble_priors_host(poses16, n, fixed, edges, m, nullptr, 0, nullptr, lambda, D_out, g_out, L_out, U_out);
+}
+
+int lsa_pgo_assemble_priors_host(const double* poses16, int n, const uint8_t* fixed, const lsa_pgo_edge_t* edges, int m, const lsa_pgo_prior_t* priors, int k,
+                                 const double* offset16, double lambda, double* D_out, double* g_out, double* L_out, double* U_out)
+{
   if (!D_out || !g_out || !L_out || !U_out || !(lambda >= 0.) || !pg::finite_d(lambda)) return LSA_E_ARG;
   host::PoseGraph G;
-  if (const int rc = host::PgoBuild(poses16, n, fixed, edges, m, &G, nullptr); rc != LSA_OK) return rc;
+  if (const int rc = host::PgoBuild(poses16, n, fixed, edges, m, &G, nullptr, priors, k, offset16); rc != LSA_OK) return rc;
   host::System S;
-  S.Size(n, m);
-  S.Linearize(poses16, edges, m);
+  S.Size(n, m, k);
+  const pg::Pose O = pg::load(k > 0 ? offset16 : poses16);
+  S.Linearize(poses16, edges, m, priors, k, &O);
   S.Assemble(G, fixed, edges, lambda);
   std::memcpy(D_out, S.D.data(), S.D.size() * sizeof(double));
   std::memcpy(g_out, S.g.data(), S.g.size() * sizeof(double));
@@ -380,12 +468,19 @@ int lsa_pgo_tridiagonal_solve_host(int n, const double* D, const double* L, cons
 
 int lsa_pgo_spmv_host(const double* poses16, int n, const uint8_t* fixed, const lsa_pgo_edge_t* edges, int m, double lambda, const double* p, double* q)
 {
+  return lsa_pgo_spmv_priors_host(poses16, n, fixed, edges, m, nullptr, 0, nullptr, lambda, p, q);
+}
+
+int lsa_pgo_spmv_priors_host(const double* poses16, int n, const uint8_t* fixed, const lsa_pgo_edge_t* edges, int m, const lsa_pgo_prior_t* priors, int k,
+                             const double* offset16, double lambda, const double* p, double* q)
+{
   if (!p || !q || !(lambda >= 0.) || !pg::finite_d(lambda)) return LSA_E_ARG;
   host::PoseGraph G;
-  if (const int rc = host::PgoBuild(poses16, n, fixed, edges, m, &G, nullptr); rc != LSA_OK) return rc;
+  if (const int rc = host::PgoBuild(poses16, n, fixed, edges, m, &G, nullptr, priors, k, offset16); rc != LSA_OK) return rc;
   host::System S;
-  S.Size(n, m);
-  S.Linearize(poses16, edges, m);
+  S.Size(n, m, k);
+  const pg::Pose O = pg::load(k > 0 ? offset16 : poses16);
+  S.Linearize(poses16, edges, m, priors, k, &O);
   S.Assemble(G, fixed, edges, lambda);
   std::vector<double> out(static_cast<size_t>(n) * 6);
   const pg::Graph view = G.view();
@@ -438,6 +533,58 @@ int lsa_pgo_information_from_covariance(const double* cov36, double* info36)
     if (!pg::finite_d(out[i])) return LSA_E_ARG;
   for (int i = 0; i < 6; ++i)
     for (int j = 0; j <= i; ++j) info36[i * 6 + j] = info36[j * 6 + i] = 0.5 * (out[i * 6 + j] + out[j * 6 + i]);
+  return LSA_OK;
+}
+
+int lsa_pgo_information_from_covariance3(const double* cov9, double* info9)
+{
+  if (!cov9 || !info9) return LSA_E_ARG;
+  for (int i = 0; i < 9; ++i)
+    if (!pg::finite_d(cov9[i])) return LSA_E_ARG;
+  for (int i = 0; i < 3; ++i)
+    for (int j = 0; j < i; ++j)
+    {
+      const double a = cov9[i * 3 + j], b = cov9[j * 3 + i];
+      if (std::fabs(a - b) > 1e-9 * (std::fabs(a) + std::fabs(b))) return LSA_E_ARG;
+    }
+  // Cholesky of the lower triangle; a pivot that rounding alone left positive is singular to working precision (as the 6x6 rule)
+  double L[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}, rinv[3];
+  for (int i = 0; i < 3; ++i)
+    for (int j = 0; j <= i; ++j)
+    {
+      double s = cov9[i * 3 + j];
+      for (int k = 0; k < j; ++k) s -= L[i * 3 + k] * L[j * 3 + k];
+      if (i == j)
+      {
+        if (!(s > 1e-12 * cov9[i * 4]) || !(s <= 1.79769313486231570815e308)) return LSA_E_ARG;
+        L[i * 4] = std::sqrt(s);
+        rinv[i] = 1.0 / L[i * 4];
+      }
+      else
+        L[i * 3 + j] = s * rinv[j];
+    }
+  double out[9];
+  for (int c = 0; c < 3; ++c)
+  {
+    double y[3], x[3];
+    for (int i = 0; i < 3; ++i)
+    {
+      double s = i == c ? 1. : 0.;
+      for (int k = 0; k < i; ++k) s -= L[i * 3 + k] * y[k];
+      y[i] = s * rinv[i];
+    }
+    for (int i = 2; i >= 0; --i)
+    {
+      double s = y[i];
+      for (int k = i + 1; k < 3; ++k) s -= L[k * 3 + i] * x[k];
+      x[i] = s * rinv[i];
+    }
+    for (int i = 0; i < 3; ++i) out[i * 3 + c] = x[i];
+  }
+  for (int i = 0; i < 9; ++i)
+    if (!pg::finite_d(out[i])) return LSA_E_ARG;
+  for (int i = 0; i < 3; ++i)
+    for (int j = 0; j <= i; ++j) info9[i * 3 + j] = info9[j * 3 + i] = 0.5 * (out[i * 3 + j] + out[j * 3 + i]);
   return LSA_OK;
 }
 

@@ -17,15 +17,20 @@ struct PoseGraph
   int n = 0, m = 0;
   std::vector<int> row_start, inc;                    // incidence lists, CSR, ascending edge index
   std::vector<int> loop_start, loop_edge, loop_col;   // couplings beyond the chain between free poses (pg::Graph)
-  pg::Graph view() const { return pg::Graph{row_start.data(), inc.data(), loop_start.data(), loop_edge.data(), loop_col.data()}; }
+  int k = 0;
+  std::vector<int> prior_start, prior_of;             // the priors of the poses, CSR, ascending prior index
+  pg::Graph view() const { return pg::Graph{row_start.data(), inc.data(), loop_start.data(), loop_edge.data(), loop_col.data(), prior_start.data(), prior_of.data()}; }
 };
 // LSA_E_ARG (and why) unless the graph is within the definition; fixed may be NULL where none is needed (linearization)
 int PgoCheckEdges(const double* poses16, int n, const lsa_pgo_edge_t* edges, int m, std::string* why);
-int PgoBuild(const double* poses16, int n, const unsigned char* fixed, const lsa_pgo_edge_t* edges, int m, PoseGraph* g, std::string* why);
+// priors: k of them behind one offset (offset16 may be NULL when k is 0); a graph needs a fixed pose or a prior
+int PgoCheckPriors(const double* poses16, int n, const lsa_pgo_prior_t* priors, int k, const double* offset16, std::string* why);
+int PgoBuild(const double* poses16, int n, const unsigned char* fixed, const lsa_pgo_edge_t* edges, int m, PoseGraph* g, std::string* why,
+             const lsa_pgo_prior_t* priors = nullptr, int k = 0, const double* offset16 = nullptr);
 // block Thomas on the block-tridiagonal (D, L, U); false when a pivot block is not positive definite (x untouched)
 bool PgoTridiagonalSolve(int n, const double* D, const double* L, const double* U, const double* b, double* x);
 const char* PgoMessage(int termination);
-int PgoSolve(const double* poses16, int n, const unsigned char* fixed, const lsa_pgo_edge_t* edges, int m, const lsa_pgo_params_t* params, double* poses_out,
-             lsa_pgo_result_t* result, std::string* why);
+int PgoSolve(const double* poses16, int n, const unsigned char* fixed, const lsa_pgo_edge_t* edges, int m, const lsa_pgo_prior_t* priors, int k, const double* offset16,
+             const lsa_pgo_params_t* params, double* poses_out, lsa_pgo_result_t* result, std::string* why);
 }  // namespace host
 }  // namespace lsa

@@ -350,6 +350,13 @@ int lsa_slam_optimize_logged_trajectory(lsa_slam* s, const lsa_pgo_edge_t* loop_
   return s->core.OptimizeLoggedTrajectory(loop_edges, m, params, poses17_out, capacity, result);
 }
 
+int lsa_slam_run_pose_graph_optimization(lsa_slam* s, const double* gps_times, const double* gps_xyz, const double* gps_cov9, int G, double* gps_to_sensor16,
+                                         double time_offset, const lsa_pgo_params_t* params, double* poses17_out, int capacity, lsa_pgo_result_t* result)
+{
+  if (!s) return LSA_E_ARG;
+  return s->core.RunPoseGraphOptimization(gps_times, gps_xyz, gps_cov9, G, gps_to_sensor16, time_offset, params, poses17_out, capacity, result);
+}
+
 int lsa_loop_closure_candidate(const double* poses17, int n, int query, double min_travelled, double max_distance)
 {
   return lsa::host::LoopClosureCandidate(poses17, n, query, min_travelled, max_distance);

@@ -1799,28 +1799,10 @@ int SlamCore::RecognizePlace(int query, const lsa_place_search_t* search, lsa_pl
 }
 
 // ---- pose-graph optimization of the logged trajectory (lsa_pose_graph.hip) ---------------------------------------------------
-int SlamCore::OptimizeLoggedTrajectory(const lsa_pgo_edge_t* loopEdges, int m, const lsa_pgo_params_t* params, double* poses17, int capacity, lsa_pgo_result_t* result)
+// the odometry chain of the log: edge i-1 -> i with Z = inv(P[i-1]) P[i], weighted by p.odometry_information (n - 1 edges)
+int SlamCore::LoggedChainEdges(const lsa_pgo_params_t& p, const std::string& who, lsa_pgo_edge_t* edges)
 {
-  if (!Ctx) return LSA_E_NO_DEVICE;
-  const std::string who = "OptimizeLoggedTrajectory: ";
-  if (!result || !poses17 || m < 0 || (m > 0 && !loopEdges)) { LastError = who + "bad argument"; return LSA_E_ARG; }
-  if (LoggingTimeout == 0.) { LastError = who + "keypoint logging is off (LoggingTimeout = 0): there is no logged trajectory to optimize"; return LSA_E_STATE; }
-  if (KpLogStopped) { LastError = who + "keypoint logging stopped when a chunk could not be allocated; Reset(true) starts it again"; return LSA_E_STATE; }
   const int n = static_cast<int>(LogTrajectory.size());
-  if (lsa_kplog_size(Ctx) != n) { LastError = who + "the keypoint log does not cover the logged poses (logging was switched on after the first of them)"; return LSA_E_STATE; }
-  lsa_pgo_params_t p;
-  lsa_pgo_params_init(&p);
-  if (params) p = *params;
-  if (!pg::params_ok(p)) { LastError = who + "parameters out of limits"; return LSA_E_ARG; }
-  if (n < 2) { LastError = who + "at least two logged poses"; return LSA_E_ARG; }
-  if (capacity < n) { LastError = who + "room for " + std::to_string(capacity) + " of " + std::to_string(n) + " poses"; return LSA_E_ARG; }
-  for (int k = 0; k < m; ++k)
-    if (loopEdges[k].from < 0 || loopEdges[k].from >= n || loopEdges[k].to < 0 || loopEdges[k].to >= n || loopEdges[k].from == loopEdges[k].to)
-    {
-      LastError = who + "loop edge " + std::to_string(k) + " does not join two of the " + std::to_string(n) + " logged poses";
-      return LSA_E_ARG;
-    }
-  std::vector<lsa_pgo_edge_t> edges(static_cast<size_t>(n - 1 + m));
   double diagonal[36];
   std::memset(diagonal, 0, sizeof(diagonal));
   if (p.odometry_information == 0)
@@ -1845,6 +1827,32 @@ int SlamCore::OptimizeLoggedTrajectory(const lsa_pgo_edge_t* loopEdges, int m, c
       return LSA_E_ARG;
     }
   }
+  return LSA_OK;
+}
+
+int SlamCore::OptimizeLoggedTrajectory(const lsa_pgo_edge_t* loopEdges, int m, const lsa_pgo_params_t* params, double* poses17, int capacity, lsa_pgo_result_t* result)
+{
+  if (!Ctx) return LSA_E_NO_DEVICE;
+  const std::string who = "OptimizeLoggedTrajectory: ";
+  if (!result || !poses17 || m < 0 || (m > 0 && !loopEdges)) { LastError = who + "bad argument"; return LSA_E_ARG; }
+  if (LoggingTimeout == 0.) { LastError = who + "keypoint logging is off (LoggingTimeout = 0): there is no logged trajectory to optimize"; return LSA_E_STATE; }
+  if (KpLogStopped) { LastError = who + "keypoint logging stopped when a chunk could not be allocated; Reset(true) starts it again"; return LSA_E_STATE; }
+  const int n = static_cast<int>(LogTrajectory.size());
+  if (lsa_kplog_size(Ctx) != n) { LastError = who + "the keypoint log does not cover the logged poses (logging was switched on after the first of them)"; return LSA_E_STATE; }
+  lsa_pgo_params_t p;
+  lsa_pgo_params_init(&p);
+  if (params) p = *params;
+  if (!pg::params_ok(p)) { LastError = who + "parameters out of limits"; return LSA_E_ARG; }
+  if (n < 2) { LastError = who + "at least two logged poses"; return LSA_E_ARG; }
+  if (capacity < n) { LastError = who + "room for " + std::to_string(capacity) + " of " + std::to_string(n) + " poses"; return LSA_E_ARG; }
+  for (int k = 0; k < m; ++k)
+    if (loopEdges[k].from < 0 || loopEdges[k].from >= n || loopEdges[k].to < 0 || loopEdges[k].to >= n || loopEdges[k].from == loopEdges[k].to)
+    {
+      LastError = who + "loop edge " + std::to_string(k) + " does not join two of the " + std::to_string(n) + " logged poses";
+      return LSA_E_ARG;
+    }
+  std::vector<lsa_pgo_edge_t> edges(static_cast<size_t>(n - 1 + m));
+  if (const int rc = LoggedChainEdges(p, who, edges.data()); rc != LSA_OK) return rc;
   for (int k = 0; k < m; ++k) edges[static_cast<size_t>(n - 1 + k)] = loopEdges[k];
   std::vector<double> in(static_cast<size_t>(n) * 16), out(static_cast<size_t>(n) * 16);
   std::vector<unsigned char> fixed(static_cast<size_t>(n), 0);
@@ -1875,6 +1883,112 @@ int SlamCore::OptimizeLoggedTrajectory(const lsa_pgo_edge_t* loopEdges, int m, c
   if (p.apply != 0)
     if (const int rc = SetTrajectoryAndRebuildMaps(rows.data(), n); rc < 0) return rc;
   std::memcpy(poses17, rows.data(), rows.size() * sizeof(double));
+  *result = r;
+  return n;
+}
+
+// ---- Slam::RunPoseGraphOptimization (Slam.cxx:355-477, PoseGraphOptimization::Process): GPS positions as priors -------------
+int SlamCore::RunPoseGraphOptimization(const double* gpsTimes, const double* gpsXyz, const double* gpsCov9, int G, double* gpsToSensor16, double timeOffset,
+                                       const lsa_pgo_params_t* params, double* poses17, int capacity, lsa_pgo_result_t* result)
+{
+  if (!Ctx) return LSA_E_NO_DEVICE;
+  const std::string who = "RunPoseGraphOptimization: ";
+  if (!result || !poses17 || !gpsToSensor16 || G < 0 || (G > 0 && (!gpsTimes || !gpsXyz || !gpsCov9)) || !pg::finite_d(timeOffset)) { LastError = who + "bad argument"; return LSA_E_ARG; }
+  if (LoggingTimeout == 0.) { LastError = who + "keypoint logging is off (LoggingTimeout = 0): there is no logged trajectory to optimize"; return LSA_E_STATE; }
+  if (KpLogStopped) { LastError = who + "keypoint logging stopped when a chunk could not be allocated; Reset(true) starts it again"; return LSA_E_STATE; }
+  const int n = static_cast<int>(LogTrajectory.size());
+  if (lsa_kplog_size(Ctx) != n) { LastError = who + "the keypoint log does not cover the logged poses (logging was switched on after the first of them)"; return LSA_E_STATE; }
+  lsa_pgo_params_t p;
+  lsa_pgo_params_init(&p);
+  if (params) p = *params;
+  if (!pg::params_ok(p)) { LastError = who + "parameters out of limits"; return LSA_E_ARG; }
+  if (n < 2 || G < 2)
+  {
+    LastError = who + "the SLAM and GPS trajectories must have at least 2 points (got " + std::to_string(n) + " logged poses and " + std::to_string(G) + " GPS positions)";
+    return LSA_E_ARG;
+  }
+  if (capacity < n) { LastError = who + "room for " + std::to_string(capacity) + " of " + std::to_string(n) + " poses"; return LSA_E_ARG; }
+  for (int k = 0; k < 16; ++k)
+    if (!pg::finite_d(gpsToSensor16[k])) { LastError = who + "the GPS to sensor calibration has a non-finite entry"; return LSA_E_ARG; }
+  for (int f = 0; f < G; ++f)
+    for (int k = 0; k < 3; ++k)
+      if (!pg::finite_d(gpsXyz[3 * static_cast<size_t>(f) + k]) || !pg::finite_d(gpsTimes[f])) { LastError = who + "GPS fix " + std::to_string(f) + " has a non-finite entry"; return LSA_E_ARG; }
+  // the two tracks must overlap in time (PoseGraphOptimization.cxx:130-143; the logged times carry the offset here, and the
+  // intervals are closed: the reference's strict comparison refuses two tracks that begin at the same instant, an accident)
+  std::vector<double> times(static_cast<size_t>(n));
+  for (int i = 0; i < n; ++i) times[static_cast<size_t>(i)] = LogTrajectory[i].time;
+  {
+    const double g0 = gpsTimes[0], g1 = gpsTimes[G - 1], s0 = times[0] + timeOffset, s1 = times[static_cast<size_t>(n) - 1] + timeOffset;
+    auto inside = [](double t, double lo, double hi) { return lo <= t && t <= hi; };
+    if (!inside(g0, s0, s1) && !inside(s0, g0, g1))
+    {
+      LastError = who + "SLAM time and GPS time do not match: GPS = (" + std::to_string(g0) + ", " + std::to_string(g1) + "), SLAM = (" + std::to_string(s0) + ", " +
+                  std::to_string(s1) + "); please indicate the time offset";
+      return LSA_E_ARG;
+    }
+  }
+  std::vector<int32_t> match(static_cast<size_t>(G));
+  if (lsa_gps_match_trajectory(times.data(), n, gpsTimes, G, timeOffset, 0.1, match.data()) != LSA_OK) { LastError = who + "the logged or the GPS times are not ascending"; return LSA_E_ARG; }
+  // O = inverse(gpsToSensor) is what the reference hands g2o's ParameterSE3Offset (PoseGraphOptimization.cxx:102-106): the fix of
+  // pose P is expected at the translation of P O
+  Pose cal;
+  std::memcpy(cal.m, gpsToSensor16, sizeof(cal.m));
+  const Pose offset = Inverse(cal);
+  std::vector<lsa_pgo_prior_t> priors;
+  std::vector<double> from, to;
+  for (int f = 0; f < G; ++f)
+  {
+    if (match[static_cast<size_t>(f)] < 0) continue;
+    lsa_pgo_prior_t pr;
+    std::memset(&pr, 0, sizeof(pr));
+    pr.pose = match[static_cast<size_t>(f)];
+    std::memcpy(pr.position, gpsXyz + 3 * static_cast<size_t>(f), sizeof(pr.position));
+    if (lsa_pgo_information_from_covariance3(gpsCov9 + 9 * static_cast<size_t>(f), pr.information) != LSA_OK)
+    {
+      LastError = who + "the covariance of GPS fix " + std::to_string(f) + " is not positive definite";
+      return LSA_E_ARG;
+    }
+    priors.push_back(pr);
+    const Pose antenna = LogTrajectory[pr.pose].pose * offset;  // its translation: t_i + R_i t_o
+    for (int k = 0; k < 3; ++k) { from.push_back(antenna.m[4 * k + 3]); to.push_back(pr.position[k]); }
+  }
+  if (priors.empty()) { LastError = who + "no GPS fix is within 0.1 s of a logged pose"; return LSA_E_ARG; }
+  double W[16];
+  if (lsa_trajectory_alignment(from.data(), to.data(), static_cast<int>(priors.size()), W) != LSA_OK) { LastError = who + "the two tracks could not be aligned"; return LSA_E_ARG; }
+  std::vector<lsa_pgo_edge_t> edges(static_cast<size_t>(n - 1));
+  if (const int rc = LoggedChainEdges(p, who, edges.data()); rc != LSA_OK) return rc;
+  std::vector<double> in(static_cast<size_t>(n) * 16), start(in.size()), opt(in.size()), out(in.size());
+  std::vector<unsigned char> fixed(static_cast<size_t>(n), 0);
+  for (int i = 0; i < n; ++i) std::memcpy(&in[16 * static_cast<size_t>(i)], LogTrajectory[i].pose.m, 16 * sizeof(double));
+  {
+    std::string why;
+    if (const int rc = PgoCheckEdges(in.data(), n, edges.data(), n - 1, &why); rc != LSA_OK) { LastError = who + why; return rc; }
+  }
+  // from here on the device works: the map workers and the look-ahead have enqueued what they had (nothing of theirs is changed)
+  WaitMaps();
+  if (const int rc = EnsureLoopClosureScratch(); rc < 0) return rc;
+  (void)lsa_collect_garbage(LoopCtx);
+  Tick t;
+  lsa_pgo_result_t r;
+  int rc = lsa_pgo_premultiply(LoopCtx, in.data(), n, W, start.data());
+  if (rc == LSA_OK) rc = lsa_pgo_solve_priors(LoopCtx, start.data(), n, fixed.data(), edges.data(), n - 1, priors.data(), static_cast<int>(priors.size()), offset.m, &p, opt.data(), &r);
+  if (rc == LSA_OK) rc = lsa_pgo_reanchor(LoopCtx, opt.data(), n, out.data());
+  if (rc < 0)
+  {
+    LastError = who + lsa_last_error(LoopCtx);
+    return rc;
+  }
+  PoseGraphSeconds = t.Stop();
+  std::vector<double> rows(static_cast<size_t>(n) * 17);
+  for (int i = 0; i < n; ++i)
+  {
+    std::memcpy(&rows[17 * static_cast<size_t>(i)], &out[16 * static_cast<size_t>(i)], 16 * sizeof(double));
+    rows[17 * static_cast<size_t>(i) + 16] = LogTrajectory[i].time;
+  }
+  if (p.apply != 0)
+    if (const int rc2 = SetTrajectoryAndRebuildMaps(rows.data(), n); rc2 < 0) return rc2;
+  std::memcpy(poses17, rows.data(), rows.size() * sizeof(double));
+  std::memcpy(gpsToSensor16, opt.data(), 16 * sizeof(double));  // the optimized pose 0 in the GPS frame (Slam.cxx:404)
   *result = r;
   return n;
 }

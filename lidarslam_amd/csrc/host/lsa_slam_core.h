@@ -135,6 +135,12 @@ public:
   // lidarslam_amd.h): the solve runs on the scratch context; with params->apply the result goes through
   // SetTrajectoryAndRebuildMaps, without it nothing of the frame path is touched.  Returns the number of poses.
   int OptimizeLoggedTrajectory(const lsa_pgo_edge_t* loopEdges, int m, const lsa_pgo_params_t* params, double* poses17, int capacity, lsa_pgo_result_t* result);
+  // Slam::RunPoseGraphOptimization (lsa_slam_run_pose_graph_optimization in lidarslam_amd.h): GPS fixes matched to the logged
+  // poses by time become position priors on a graph of free poses; solved on the scratch context from the track laid onto
+  // the fixes, brought back onto logged pose 0.  gpsToSensor16: in the calibration, out the optimized pose 0 in the GPS frame.
+  int RunPoseGraphOptimization(const double* gpsTimes, const double* gpsXyz, const double* gpsCov9, int G, double* gpsToSensor16, double timeOffset,
+                               const lsa_pgo_params_t* params, double* poses17, int capacity, lsa_pgo_result_t* result);
+  int LoggedChainEdges(const lsa_pgo_params_t& p, const std::string& who, lsa_pgo_edge_t* edges);
   int LoggedFrames() const;
   int GetLoggedKeypoints(int frame, int type, std::vector<lsa_point_t>& out);
   void HintNextStoredFrame(int slot) { NextStoredSlot = slot; }
@@ -350,7 +356,7 @@ private:
   lsa_ctx* LoopCtx = nullptr;
   lsa_device_grid* LoopMaps[3] = {nullptr, nullptr, nullptr};
   int EnsureLoopClosureScratch();
-  double PoseGraphSeconds = 0.;   // the last OptimizeLoggedTrajectory's solve by the host's clock
+  double PoseGraphSeconds = 0.;   // the last OptimizeLoggedTrajectory's or RunPoseGraphOptimization's solve by the host's clock
   double LoopClosureSeconds[4] = {0., 0., 0., 0.};  // the last call by the host's clock: replays, scratch maps, ICP loop, all of it
   std::string LastError;
   uint64_t CurrentStamp = 0;

@@ -1,4 +1,4 @@
-// lsa_pose_graph.h -- the pose graph of relative-pose edges and its Levenberg-Marquardt solve, ONE definition for the host
+// lsa_pose_graph.h -- the pose graph of relative-pose edges and position priors and its Levenberg-Marquardt solve, ONE definition for the host
 // statement (host/lsa_pose_graph.cpp) and the device (lsa_pose_graph.hip); DESIGN.md 3.9.  Plain C++ in double precision (no
 // HIP header, no libm): sines, cosines and atan2 are lsa_pmath.h's, sqrt and / the IEEE ones, nothing may be contracted or
 // re-associated (-ffp-contract=off), so the same inputs give the same bits wherever this text is compiled.
@@ -10,6 +10,13 @@
 //   A = de/ddelta_i = [ -Rz^T , Rz^T [d]x ; 0 , -J Rij^T ]      B = de/ddelta_j = [ RE , 0 ; 0 , J ]
 //   J = Jr^-1(e_rot) = I + 1/2 [phi]x + c(theta) [phi]x^2,   c = 1/theta^2 - (1 + cos theta) / (2 theta sin theta).
 // A rotation error of exactly pi is outside the definition (Log has no unique value there, c has a pole at 2 pi).
+//
+// PRIOR (i, g, Omega 3x3): a measured position g of a point carried by pose i (a GPS antenna).  All priors of a solve share one
+//   offset O = (Ro, to), the inverse of the antenna's pose in the body (what the reference gives g2o's ParameterSE3Offset).
+//   d = Ri^T (g - ti)      e = Ro^T (d - to)      A = de/ddelta_i = [ -Ro^T , Ro^T [d]x ]  (3x6)
+//   (g2o's EdgeSE3PointXYZ with a zero measurement.  Omega weighs e in this antenna frame although a GPS covariance is given
+//   in the world frame: the reference's letter, kept.)  With no fixed pose and fewer than three non-collinear priors the
+//   minimum is not unique: outside the definition, as a rotation error of pi is.
 //
 // SMALL ANGLES AND ANGLES NEAR PI
 //   Exp:  R = I + a [phi]x + b [phi]x^2.  theta^2 < 1e-8: a = 1 - theta^2/6, b = 1/2 - theta^2/24 (the next terms are below
@@ -23,16 +30,18 @@
 // ORDER OF THE SUMS.  A product of two 3x3 or 6x6 matrices, and of a matrix and a vector, sums over the inner index
 // ascending, left to right, starting from the first product.  Per edge: OA = Omega A, OB = Omega B, Oe = Omega e; then
 // Haa = A^T OA, Hab = A^T OB, Hbb = B^T OB, ga = A^T Oe, gb = B^T Oe, chi2 = e^T Oe -- the 120 doubles of an edge's block
-// record in that order (kEdgeBlock), 6x6 row-major.
+// record in that order (kEdgeBlock), 6x6 row-major.  Per prior: OA = Omega A (3x6), Oe = Omega e; Haa = A^T OA, ga = A^T Oe,
+// chi2 = e^T Oe -- the 42 doubles of a prior's block record (kPriorBlock).
 // ASSEMBLY.  Diagonal block D_i and gradient g_i of a free pose i: the sums of Haa / ga (i = from) or Hbb / gb (i = to) over
 // its incident edges in ascending edge index, starting from the first.  Off-diagonal block (i, j): the sum over the edges
-// joining i and j in ascending edge index of Hab (i = from) or Hab^T (i = to).  A fixed pose: delta = 0, its row is the
-// identity, g = 0, couplings to it are dropped.  H_lambda = H + lambda diag(H): on the diagonal h + lambda * h.
+// joining i and j in ascending edge index of Hab (i = from) or Hab^T (i = to).  The priors of pose i follow its edges in D_i and
+// g_i, in ascending prior index (a second list, prior_start / prior_of); they touch no other block.  A fixed pose: delta = 0, its
+// row is the identity, g = 0, couplings to it are dropped, a prior on it counts in the cost alone.  H_lambda = H + lambda diag(H): on the diagonal h + lambda * h.
 // PRECONDITIONER  T = the blocks of H_lambda with |i - j| <= 1 (SPD whenever H_lambda is: chain edges enter whole, other edges by
 // their diagonal blocks, the damping is positive); every other block is PCG's.
 //
 // THE LM LOOP (the host and the device follow this text; p = lsa_pgo_params_t)
-//   x = poses; linearize; F = 1/2 sum chi2 (edge order); F0 = F; lambda = p.initial_lambda
+//   x = poses; linearize; F = 1/2 sum chi2 (the edges' values in edge order, then the priors' in prior order); F0 = F; lambda = p.initial_lambda
 //   for it = 0 .. p.max_iterations - 1:
 //     assemble at lambda;  if max |g| <= p.gradient_tolerance: GRADIENT
 //     factor T;  a block that is not SPD: LINEAR_SOLVER_FAILED (poses as they were before this iteration)
@@ -56,6 +65,7 @@ namespace lsa
 namespace pg
 {
 constexpr int kEdgeBlock = 120;  // Haa[36] Hab[36] Hbb[36] ga[6] gb[6]
+constexpr int kPriorBlock = 42;  // Haa[36] ga[6]
 constexpr double kExpSeries2 = 1e-8, kLogSeries2 = 1e-10, kJrSeries2 = 0.0625;
 
 struct Pose
@@ -313,6 +323,73 @@ LSA_HD double edge_chi2(const double* poses16, const lsa_pgo_edge_t& ed)
   return dot6(e, Oe);
 }
 
+// e[3] and A[18] (3x6 row-major) of one prior: the measured position g on pose Pi behind the offset O
+LSA_HD void prior_eval(const Pose& Pi, const Pose& O, const double* g, double* e, double* A)
+{
+  double dt[3], d[3], dz[3], S[9], M[9];
+  for (int k = 0; k < 3; ++k) dt[k] = g[k] - Pi.t[k];
+  tmulv3(Pi.R, dt, d);
+  for (int k = 0; k < 3; ++k) dz[k] = d[k] - O.t[k];
+  tmulv3(O.R, dz, e);
+  hat(d, S);
+  tmul3(O.R, S, M);  // Ro^T [d]x
+  for (int r = 0; r < 3; ++r)
+    for (int c = 0; c < 3; ++c)
+    {
+      A[r * 6 + c] = -O.R[c * 3 + r];
+      A[r * 6 + 3 + c] = M[r * 3 + c];
+    }
+}
+// the block record and chi2 of a prior from e, A and its information
+LSA_HD void prior_blocks(const double* e, const double* A, const double* Om, double* blk, double* chi2)
+{
+  double OA[18], Oe[3];
+  for (int i = 0; i < 3; ++i)
+    for (int j = 0; j < 6; ++j) OA[i * 6 + j] = (Om[i * 3] * A[j] + Om[i * 3 + 1] * A[6 + j]) + Om[i * 3 + 2] * A[12 + j];
+  mulv3(Om, e, Oe);
+  for (int i = 0; i < 6; ++i)
+  {
+    for (int j = 0; j < 6; ++j) blk[i * 6 + j] = (A[i] * OA[j] + A[6 + i] * OA[6 + j]) + A[12 + i] * OA[12 + j];
+    blk[36 + i] = (A[i] * Oe[0] + A[6 + i] * Oe[1]) + A[12 + i] * Oe[2];
+  }
+  *chi2 = (e[0] * Oe[0] + e[1] * Oe[1]) + e[2] * Oe[2];
+}
+// everything of one prior: e[3], blk[kPriorBlock], chi2
+LSA_HD void linearize_prior(const double* poses16, const lsa_pgo_prior_t& pr, const Pose& O, double* e, double* blk, double* chi2)
+{
+  double A[18];
+  prior_eval(load(poses16 + 16 * (long long)pr.pose), O, pr.position, e, A);
+  prior_blocks(e, A, pr.information, blk, chi2);
+}
+// chi2 alone (a candidate's cost)
+LSA_HD double prior_chi2(const double* poses16, const lsa_pgo_prior_t& pr, const Pose& O)
+{
+  double e[3], A[18], Oe[3];
+  prior_eval(load(poses16 + 16 * (long long)pr.pose), O, pr.position, e, A);
+  mulv3(pr.information, e, Oe);
+  return (e[0] * Oe[0] + e[1] * Oe[1]) + e[2] * Oe[2];
+}
+
+// W P and inv(A) P of rigid poses: what brings a trajectory into the frame of the measured positions and back onto its pose 0
+LSA_HD Pose compose(const Pose& W, const Pose& P)
+{
+  Pose r;
+  double Wt[3];
+  mul3(W.R, P.R, r.R);
+  mulv3(W.R, P.t, Wt);
+  for (int k = 0; k < 3; ++k) r.t[k] = Wt[k] + W.t[k];
+  return r;
+}
+LSA_HD Pose inverse_compose(const Pose& A, const Pose& P)
+{
+  Pose r;
+  double dt[3];
+  tmul3(A.R, P.R, r.R);
+  for (int k = 0; k < 3; ++k) dt[k] = P.t[k] - A.t[k];
+  tmulv3(A.R, dt, r.t);
+  return r;
+}
+
 // The incidence lists of the poses (CSR, ascending edge index) and, per pose, its couplings beyond the chain: entry k of
 // row i names the edge and whether pose i is its `to` end (the block is then Hab^T).
 struct Graph
@@ -322,11 +399,13 @@ struct Graph
   const int* loop_start;  // [n + 1]
   const int* loop_edge;   // edge index * 2 + (1 when pose i is the edge's `to`)
   const int* loop_col;    // the other pose
+  const int* prior_start; // [n + 1] the priors of the poses, ascending prior index (all zero without priors)
+  const int* prior_of;    // prior indices
 };
 
 // Row i of the assembly at lambda: D (damped), dg = diag(H) (undamped), g, L = block (i, i-1), U = block (i, i+1)
-LSA_HD void assemble_row(int i, int n, const unsigned char* fixed, const Graph& G, const lsa_pgo_edge_t* edges, const double* blocks, double lambda, double* D, double* dg,
-                         double* g, double* L, double* U)
+LSA_HD void assemble_row(int i, int n, const unsigned char* fixed, const Graph& G, const lsa_pgo_edge_t* edges, const double* blocks, const double* pblocks, double lambda,
+                         double* D, double* dg, double* g, double* L, double* U)
 {
   for (int k = 0; k < 36; ++k) { D[k] = 0.; L[k] = 0.; U[k] = 0.; }
   for (int k = 0; k < 6; ++k) { g[k] = 0.; dg[k] = 0.; }
@@ -359,6 +438,13 @@ LSA_HD void assemble_row(int i, int n, const unsigned char* fixed, const Graph& 
         T[r * 6 + c] = firstT ? v : T[r * 6 + c] + v;
       }
     firstT = false;
+  }
+  for (int a = G.prior_start[i]; a < G.prior_start[i + 1]; ++a)
+  {
+    const double* blk = pblocks + (long long)G.prior_of[a] * kPriorBlock;
+    for (int k = 0; k < 36; ++k) D[k] = first ? blk[k] : D[k] + blk[k];
+    for (int k = 0; k < 6; ++k) g[k] = first ? blk[36 + k] : g[k] + blk[36 + k];
+    first = false;
   }
   for (int k = 0; k < 6; ++k)
   {

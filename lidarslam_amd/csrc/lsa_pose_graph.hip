@@ -3,7 +3,9 @@
 // below decide only who computes what.  All double precision, no floating-point atomics, every sum in a fixed order: two runs
 // give the same bits.  No kernel waits for the host or for another workgroup; every launch is finite whatever the data.
 //   k_pgo_linearize   a thread per edge: e, A, B, the edge's block record, chi2
-//   k_pgo_assemble    a thread per pose: walks its incidence list ascending; D (damped), diag(H), g, the tridiagonal L / U
+//   k_pgo_linearize_priors   a thread per position prior: e, the prior's block record, chi2 behind the edges' values
+//   k_pgo_assemble    a thread per pose: walks its incidence list ascending, then its priors; D (damped), diag(H), g, the
+//                     tridiagonal L / U
 //   k_pgo_pcr_level   block parallel cyclic reduction of the preconditioner T, one launch per stride s = 1, 2, 4, .. < n, a
 //                     thread per row: alpha = -L_i D_{i-s}^-1, gamma = -U_i D_{i+s}^-1, D' = D + alpha U_{i-s} + gamma L_{i+s},
 //                     L' = alpha L_{i-s}, U' = gamma U_{i+s}; alpha and gamma of every level are KEPT, so that an application
@@ -15,7 +17,9 @@
 //   PCG's vector updates and dot products: a partial sum per workgroup by a fixed tree, the partial sums added in order by
 //   one thread, which also forms alpha and beta -- they stay on the device; the host reads one status block per iteration
 //   to decide whether to enqueue the next.
-//   k_pgo_retract, k_pgo_chi2 and the sums for the candidate.
+//   k_pgo_retract, k_pgo_chi2, k_pgo_chi2_priors and the sums for the candidate.
+//   k_pgo_premultiply, k_pgo_reanchor   a thread per pose: W P_i, and inv(P_0) P_i (a trajectory into the frame of the measured
+//                     positions and back onto its first pose).
 // Buffers belong to the context and grow through its graveyard; everything runs on the context's stream.
 #include <algorithm>
 #include <cstring>
@@ -42,7 +46,8 @@ struct PgoBuf
 };
 struct PgoBuffers
 {
-  PgoBuf poses, cand, edges, fixed, row_start, inc, loop_start, loop_edge, loop_col, e, blocks, chi2, D, dg, g, L, U, work[2], alpha, gamma, Dinv, vec, partials, state;
+  PgoBuf poses, cand, edges, fixed, row_start, inc, loop_start, loop_edge, loop_col, e, blocks, chi2, D, dg, g, L, U, work[2], alpha, gamma, Dinv, vec, partials, state, priors, prior_start, prior_of,
+      pe, pblocks;
   PgoState* host = nullptr;  // pinned
 };
 void pgo_destroy(lsa_ctx* ctx)
@@ -50,7 +55,8 @@ void pgo_destroy(lsa_ctx* ctx)
   PgoBuffers* b = ctx->pgo;
   if (!b) return;
   PgoBuf* all[] = {&b->poses, &b->cand, &b->edges, &b->fixed, &b->row_start, &b->inc, &b->loop_start, &b->loop_edge, &b->loop_col, &b->e, &b->blocks, &b->chi2, &b->D,
-                   &b->dg, &b->g, &b->L, &b->U, &b->work[0], &b->work[1], &b->alpha, &b->gamma, &b->Dinv, &b->vec, &b->partials, &b->state};
+                   &b->dg, &b->g, &b->L, &b->U, &b->work[0], &b->work[1], &b->alpha, &b->gamma, &b->Dinv, &b->vec, &b->partials, &b->state, &b->priors, &b->prior_start,
+                   &b->prior_of, &b->pe, &b->pblocks};
   for (PgoBuf* x : all)
     if (x->p) (void)hipFree(x->p);
   if (b->host) (void)hipHostFree(b->host);
@@ -80,13 +86,30 @@ __global__ __launch_bounds__(kThreads) void k_pgo_chi2(const double* __restrict_
   chi2[k] = pg::edge_chi2(poses, edges[k]);
 }
 
+// the priors' values go behind the m edge values of chi2
+__global__ __launch_bounds__(kThreads) void k_pgo_linearize_priors(const double* __restrict__ poses, const lsa_pgo_prior_t* __restrict__ priors, int k, pg::Pose O,
+                                                                   double* __restrict__ e, double* __restrict__ blocks, double* __restrict__ chi2)
+{
+  const int a = blockIdx.x * kThreads + threadIdx.x;
+  if (a >= k) return;
+  pg::linearize_prior(poses, priors[a], O, e + 3LL * a, blocks + (long long)a * pg::kPriorBlock, chi2 + a);
+}
+
+__global__ __launch_bounds__(kThreads) void k_pgo_chi2_priors(const double* __restrict__ poses, const lsa_pgo_prior_t* __restrict__ priors, int k, pg::Pose O,
+                                                              double* __restrict__ chi2)
+{
+  const int a = blockIdx.x * kThreads + threadIdx.x;
+  if (a >= k) return;
+  chi2[a] = pg::prior_chi2(poses, priors[a], O);
+}
+
 __global__ __launch_bounds__(kThreads) void k_pgo_assemble(int n, const unsigned char* __restrict__ fixed, pg::Graph G, const lsa_pgo_edge_t* __restrict__ edges,
-                                                           const double* __restrict__ blocks, double lambda, double* __restrict__ D, double* __restrict__ dg,
-                                                           double* __restrict__ g, double* __restrict__ L, double* __restrict__ U)
+                                                           const double* __restrict__ blocks, const double* __restrict__ pblocks, double lambda, double* __restrict__ D,
+                                                           double* __restrict__ dg, double* __restrict__ g, double* __restrict__ L, double* __restrict__ U)
 {
   const int i = blockIdx.x * kThreads + threadIdx.x;
   if (i >= n) return;
-  pg::assemble_row(i, n, fixed, G, edges, blocks, lambda, D + 36LL * i, dg + 6LL * i, g + 6LL * i, L + 36LL * i, U + 36LL * i);
+  pg::assemble_row(i, n, fixed, G, edges, blocks, pblocks, lambda, D + 36LL * i, dg + 6LL * i, g + 6LL * i, L + 36LL * i, U + 36LL * i);
 }
 
 // one level of the cyclic reduction at stride s
@@ -343,6 +366,21 @@ __global__ __launch_bounds__(kThreads) void k_pgo_retract(int n, const double* _
   pg::store(pg::retract(pg::load(poses + 16LL * i), delta + 6LL * i), cand + 16LL * i);
 }
 
+// out_i = W P_i
+__global__ __launch_bounds__(kThreads) void k_pgo_premultiply(int n, pg::Pose W, const double* __restrict__ poses, double* __restrict__ out)
+{
+  const int i = blockIdx.x * kThreads + threadIdx.x;
+  if (i >= n) return;
+  pg::store(pg::compose(W, pg::load(poses + 16LL * i)), out + 16LL * i);
+}
+// out_i = inv(P_0) P_i (out is another buffer than poses: every thread reads pose 0)
+__global__ __launch_bounds__(kThreads) void k_pgo_reanchor(int n, const double* __restrict__ poses, double* __restrict__ out)
+{
+  const int i = blockIdx.x * kThreads + threadIdx.x;
+  if (i >= n) return;
+  pg::store(pg::inverse_compose(pg::load(poses), pg::load(poses + 16LL * i)), out + 16LL * i);
+}
+
 int ensure(lsa_ctx* ctx, PgoBuf& b, size_t bytes)
 {
   if (bytes <= b.cap) return LSA_OK;
@@ -370,9 +408,10 @@ struct Problem
 {
   lsa_ctx* ctx;
   PgoBuffers* B;
-  int n = 0, m = 0, nl = 0, nb = 0;
+  int n = 0, m = 0, k = 0, nl = 0, nb = 0;
   bool haveGraph = false;
   pg::Graph G{};
+  pg::Pose O{};  // the priors' offset
   double* vec(int k) const { return ptr_of<double>(B->vec) + 6LL * n * k; }
   PgoState* state() const { return ptr_of<PgoState>(B->state); }
 };
@@ -384,8 +423,9 @@ struct Problem
     if (rc__ != LSA_OK) return rc__; \
   } while (0)
 
-// buffers for n poses and m edges; poses, edges (and the graph, when given) uploaded
-int setup(Problem& P, lsa_ctx* ctx, const double* poses16, int n, const unsigned char* fixed, const lsa_pgo_edge_t* edges, int m, const host::PoseGraph* G)
+// buffers for n poses, m edges and k priors; poses, edges, priors (and the graph, when given) uploaded
+int setup(Problem& P, lsa_ctx* ctx, const double* poses16, int n, const unsigned char* fixed, const lsa_pgo_edge_t* edges, int m, const host::PoseGraph* G,
+          const lsa_pgo_prior_t* priors = nullptr, int k = 0, const double* offset16 = nullptr)
 {
   LSA_HIP(ctx, hipSetDevice(ctx->device));
   if (!ctx->pgo) ctx->pgo = new PgoBuffers;
@@ -394,8 +434,10 @@ int setup(Problem& P, lsa_ctx* ctx, const double* poses16, int n, const unsigned
   P.B = B;
   P.n = n;
   P.m = m;
+  P.k = k;
+  if (k > 0) P.O = pg::load(offset16);
   P.nl = levels_of(n);
-  P.nb = (int)blocks_for(std::max(n, m));
+  P.nb = (int)blocks_for(std::max((long long)n, (long long)m + k));
   const size_t n36 = (size_t)n * 36 * sizeof(double), n6 = (size_t)n * 6 * sizeof(double);
   PGO_TRY(ensure(ctx, B->poses, (size_t)n * 16 * sizeof(double)));
   PGO_TRY(ensure(ctx, B->cand, (size_t)n * 16 * sizeof(double)));
@@ -408,7 +450,12 @@ int setup(Problem& P, lsa_ctx* ctx, const double* poses16, int n, const unsigned
   PGO_TRY(ensure(ctx, B->loop_col, std::max<size_t>(1, (size_t)2 * m) * sizeof(int)));
   PGO_TRY(ensure(ctx, B->e, std::max<size_t>(1, (size_t)m) * 6 * sizeof(double)));
   PGO_TRY(ensure(ctx, B->blocks, std::max<size_t>(1, (size_t)m) * pg::kEdgeBlock * sizeof(double)));
-  PGO_TRY(ensure(ctx, B->chi2, std::max<size_t>(1, (size_t)m) * sizeof(double)));
+  PGO_TRY(ensure(ctx, B->chi2, std::max<size_t>(1, (size_t)m + (size_t)k) * sizeof(double)));
+  PGO_TRY(ensure(ctx, B->priors, std::max<size_t>(1, (size_t)k) * sizeof(lsa_pgo_prior_t)));
+  PGO_TRY(ensure(ctx, B->prior_start, ((size_t)n + 1) * sizeof(int)));
+  PGO_TRY(ensure(ctx, B->prior_of, std::max<size_t>(1, (size_t)k) * sizeof(int)));
+  PGO_TRY(ensure(ctx, B->pe, std::max<size_t>(1, (size_t)k) * 3 * sizeof(double)));
+  PGO_TRY(ensure(ctx, B->pblocks, std::max<size_t>(1, (size_t)k) * pg::kPriorBlock * sizeof(double)));
   PGO_TRY(ensure(ctx, B->D, n36));
   PGO_TRY(ensure(ctx, B->L, n36));
   PGO_TRY(ensure(ctx, B->U, n36));
@@ -428,6 +475,7 @@ int setup(Problem& P, lsa_ctx* ctx, const double* poses16, int n, const unsigned
   if (poses16) LSA_HIP(ctx, hipMemcpyAsync(B->poses.p, poses16, (size_t)n * 16 * sizeof(double), hipMemcpyHostToDevice, st));
   if (m > 0 && edges) LSA_HIP(ctx, hipMemcpyAsync(B->edges.p, edges, (size_t)m * sizeof(lsa_pgo_edge_t), hipMemcpyHostToDevice, st));
   if (fixed) LSA_HIP(ctx, hipMemcpyAsync(B->fixed.p, fixed, (size_t)n, hipMemcpyHostToDevice, st));
+  if (k > 0 && priors) LSA_HIP(ctx, hipMemcpyAsync(B->priors.p, priors, (size_t)k * sizeof(lsa_pgo_prior_t), hipMemcpyHostToDevice, st));
   P.haveGraph = G != nullptr;
   if (G)
   {
@@ -439,25 +487,40 @@ int setup(Problem& P, lsa_ctx* ctx, const double* poses16, int n, const unsigned
       LSA_HIP(ctx, hipMemcpyAsync(B->loop_edge.p, G->loop_edge.data(), G->loop_edge.size() * sizeof(int), hipMemcpyHostToDevice, st));
       LSA_HIP(ctx, hipMemcpyAsync(B->loop_col.p, G->loop_col.data(), G->loop_col.size() * sizeof(int), hipMemcpyHostToDevice, st));
     }
-    P.G = pg::Graph{ptr_of<int>(B->row_start), ptr_of<int>(B->inc), ptr_of<int>(B->loop_start), ptr_of<int>(B->loop_edge), ptr_of<int>(B->loop_col)};
+    LSA_HIP(ctx, hipMemcpyAsync(B->prior_start.p, G->prior_start.data(), ((size_t)n + 1) * sizeof(int), hipMemcpyHostToDevice, st));
+    if (!G->prior_of.empty()) LSA_HIP(ctx, hipMemcpyAsync(B->prior_of.p, G->prior_of.data(), G->prior_of.size() * sizeof(int), hipMemcpyHostToDevice, st));
+    P.G = pg::Graph{ptr_of<int>(B->row_start), ptr_of<int>(B->inc), ptr_of<int>(B->loop_start), ptr_of<int>(B->loop_edge), ptr_of<int>(B->loop_col),
+                    ptr_of<int>(B->prior_start), ptr_of<int>(B->prior_of)};
   }
   return LSA_OK;
 }
 
-int launch_linearize(const Problem& P, const double* poses)
+int launch_linearize_priors(const Problem& P, const double* poses)
 {
-  if (P.m == 0) return LSA_OK;
-  ProfScope ps(P.ctx, "pgo_linearize", (double)P.m * (sizeof(lsa_pgo_edge_t) + (pg::kEdgeBlock + 7) * 8.));
-  hipLaunchKernelGGL(k_pgo_linearize, dim3(blocks_for(P.m)), dim3(kThreads), 0, P.ctx->stream, poses, ptr_of<lsa_pgo_edge_t>(P.B->edges), P.m, ptr_of<double>(P.B->e),
-                     ptr_of<double>(P.B->blocks), ptr_of<double>(P.B->chi2));
+  if (P.k == 0) return LSA_OK;
+  ProfScope ps(P.ctx, "pgo_linearize_priors", (double)P.k * (sizeof(lsa_pgo_prior_t) + (pg::kPriorBlock + 4) * 8.));
+  hipLaunchKernelGGL(k_pgo_linearize_priors, dim3(blocks_for(P.k)), dim3(kThreads), 0, P.ctx->stream, poses, ptr_of<lsa_pgo_prior_t>(P.B->priors), P.k, P.O,
+                     ptr_of<double>(P.B->pe), ptr_of<double>(P.B->pblocks), ptr_of<double>(P.B->chi2) + P.m);
   LSA_HIP(P.ctx, hipGetLastError());
   return LSA_OK;
 }
-// sum of chi2 into stat[3]
+// edges and priors
+int launch_linearize(const Problem& P, const double* poses)
+{
+  if (P.m > 0)
+  {
+    ProfScope ps(P.ctx, "pgo_linearize", (double)P.m * (sizeof(lsa_pgo_edge_t) + (pg::kEdgeBlock + 7) * 8.));
+    hipLaunchKernelGGL(k_pgo_linearize, dim3(blocks_for(P.m)), dim3(kThreads), 0, P.ctx->stream, poses, ptr_of<lsa_pgo_edge_t>(P.B->edges), P.m, ptr_of<double>(P.B->e),
+                       ptr_of<double>(P.B->blocks), ptr_of<double>(P.B->chi2));
+    LSA_HIP(P.ctx, hipGetLastError());
+  }
+  return launch_linearize_priors(P, poses);
+}
+// sum of chi2 (the m edge values, then the k prior values) into stat[3]
 int launch_cost(const Problem& P)
 {
-  const int nb = (int)blocks_for(P.m);
-  hipLaunchKernelGGL(k_pgo_sum, dim3(nb), dim3(kThreads), 0, P.ctx->stream, P.m, ptr_of<double>(P.B->chi2), ptr_of<double>(P.B->partials));
+  const int nb = (int)blocks_for((long long)P.m + P.k);
+  hipLaunchKernelGGL(k_pgo_sum, dim3(nb), dim3(kThreads), 0, P.ctx->stream, P.m + P.k, ptr_of<double>(P.B->chi2), ptr_of<double>(P.B->partials));
   hipLaunchKernelGGL(k_pgo_finish, dim3(1), dim3(64), 0, P.ctx->stream, (int)FIN_CHI2, nb, ptr_of<double>(P.B->partials), 0., P.state());
   LSA_HIP(P.ctx, hipGetLastError());
   return LSA_OK;
@@ -466,7 +529,7 @@ int launch_assemble(const Problem& P, double lambda)
 {
   ProfScope ps(P.ctx, "pgo_assemble", (double)P.n * (36 * 3 + 12) * 8. + (double)P.m * 2 * pg::kEdgeBlock * 8.);
   hipLaunchKernelGGL(k_pgo_assemble, dim3(blocks_for(P.n)), dim3(kThreads), 0, P.ctx->stream, P.n, ptr_of<unsigned char>(P.B->fixed), P.G, ptr_of<lsa_pgo_edge_t>(P.B->edges),
-                     ptr_of<double>(P.B->blocks), lambda, ptr_of<double>(P.B->D), ptr_of<double>(P.B->dg), ptr_of<double>(P.B->g), ptr_of<double>(P.B->L),
+                     ptr_of<double>(P.B->blocks), ptr_of<double>(P.B->pblocks), lambda, ptr_of<double>(P.B->D), ptr_of<double>(P.B->dg), ptr_of<double>(P.B->g), ptr_of<double>(P.B->L),
                      ptr_of<double>(P.B->U));
   LSA_HIP(P.ctx, hipGetLastError());
   return LSA_OK;
@@ -564,14 +627,21 @@ int lsa_pgo_linearize(lsa_ctx* ctx, const double* poses16, int n, const lsa_pgo_
 int lsa_pgo_assemble(lsa_ctx* ctx, const double* poses16, int n, const uint8_t* fixed, const lsa_pgo_edge_t* edges, int m, double lambda, double* D_out, double* g_out,
                      double* L_out, double* U_out)
 {
+  return lsa_pgo_assemble_priors(ctx, poses16, n, fixed, edges, m, nullptr, 0, nullptr, lambda, D_out, g_out, L_out, U_out);
+}
+
+int lsa_pgo_assemble_priors(lsa_ctx* ctx, const double* poses16, int n, const uint8_t* fixed, const lsa_pgo_edge_t* edges, int m, const lsa_pgo_prior_t* priors, int k,
+                            const double* offset16, double lambda, double* D_out, double* g_out, double* L_out, double* U_out)
+{
   if (!ctx) return LSA_E_ARG;
   std::string why = "bad argument";
   host::PoseGraph G;
-  if (!D_out || !g_out || !L_out || !U_out || !(lambda >= 0.) || !pg::finite_d(lambda) || host::PgoBuild(poses16, n, fixed, edges, m, &G, &why) != LSA_OK)
+  if (!D_out || !g_out || !L_out || !U_out || !(lambda >= 0.) || !pg::finite_d(lambda) ||
+      host::PgoBuild(poses16, n, fixed, edges, m, &G, &why, priors, k, offset16) != LSA_OK)
     return ctx->fail(LSA_E_ARG, "lsa_pgo_assemble: " + why);
   if (n > kMaxPoses) return ctx->fail(LSA_E_CAPACITY, "lsa_pgo_assemble: more than 262144 poses");
   Problem P;
-  PGO_TRY(setup(P, ctx, poses16, n, fixed, edges, m, &G));
+  PGO_TRY(setup(P, ctx, poses16, n, fixed, edges, m, &G, priors, k, offset16));
   PGO_TRY(launch_linearize(P, ptr_of<double>(P.B->poses)));
   PGO_TRY(launch_assemble(P, lambda));
   const size_t n36 = (size_t)n * 36 * sizeof(double);
@@ -585,14 +655,20 @@ int lsa_pgo_assemble(lsa_ctx* ctx, const double* poses16, int n, const uint8_t* 
 
 int lsa_pgo_spmv(lsa_ctx* ctx, const double* poses16, int n, const uint8_t* fixed, const lsa_pgo_edge_t* edges, int m, double lambda, const double* p, double* q)
 {
+  return lsa_pgo_spmv_priors(ctx, poses16, n, fixed, edges, m, nullptr, 0, nullptr, lambda, p, q);
+}
+
+int lsa_pgo_spmv_priors(lsa_ctx* ctx, const double* poses16, int n, const uint8_t* fixed, const lsa_pgo_edge_t* edges, int m, const lsa_pgo_prior_t* priors, int k,
+                        const double* offset16, double lambda, const double* p, double* q)
+{
   if (!ctx) return LSA_E_ARG;
   std::string why = "bad argument";
   host::PoseGraph G;
-  if (!p || !q || !(lambda >= 0.) || !pg::finite_d(lambda) || host::PgoBuild(poses16, n, fixed, edges, m, &G, &why) != LSA_OK)
+  if (!p || !q || !(lambda >= 0.) || !pg::finite_d(lambda) || host::PgoBuild(poses16, n, fixed, edges, m, &G, &why, priors, k, offset16) != LSA_OK)
     return ctx->fail(LSA_E_ARG, "lsa_pgo_spmv: " + why);
   if (n > kMaxPoses) return ctx->fail(LSA_E_CAPACITY, "lsa_pgo_spmv: more than 262144 poses");
   Problem P;
-  PGO_TRY(setup(P, ctx, poses16, n, fixed, edges, m, &G));
+  PGO_TRY(setup(P, ctx, poses16, n, fixed, edges, m, &G, priors, k, offset16));
   PGO_TRY(launch_linearize(P, ptr_of<double>(P.B->poses)));
   PGO_TRY(launch_assemble(P, lambda));
   LSA_HIP(ctx, hipMemcpyAsync(P.vec(V_P), p, (size_t)n * 6 * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
@@ -649,6 +725,56 @@ int lsa_pgo_tridiagonal_solve(lsa_ctx* ctx, int n, const double* D, const double
 int lsa_pgo_solve(lsa_ctx* ctx, const double* poses16, int n, const uint8_t* fixed, const lsa_pgo_edge_t* edges, int m, const lsa_pgo_params_t* params, double* poses_out,
                   lsa_pgo_result_t* result)
 {
+  return lsa_pgo_solve_priors(ctx, poses16, n, fixed, edges, m, nullptr, 0, nullptr, params, poses_out, result);
+}
+
+int lsa_pgo_linearize_priors(lsa_ctx* ctx, const double* poses16, int n, const lsa_pgo_prior_t* priors, int k, const double* offset16, double* e_out, double* blocks_out,
+                             double* chi2_out)
+{
+  if (!ctx) return LSA_E_ARG;
+  std::string why = "bad argument";
+  if (!e_out || !blocks_out || !chi2_out || host::PgoCheckPriors(poses16, n, priors, k, offset16, &why) != LSA_OK)
+    return ctx->fail(LSA_E_ARG, "lsa_pgo_linearize_priors: " + why);
+  if (n > kMaxPoses) return ctx->fail(LSA_E_CAPACITY, "lsa_pgo_linearize_priors: more than 262144 poses");
+  if (k == 0) return LSA_OK;
+  Problem P;
+  PGO_TRY(setup(P, ctx, poses16, n, nullptr, nullptr, 0, nullptr, priors, k, offset16));
+  PGO_TRY(launch_linearize_priors(P, ptr_of<double>(P.B->poses)));
+  PGO_TRY(download(ctx, e_out, P.B->pe.p, (size_t)k * 3 * sizeof(double)));
+  PGO_TRY(download(ctx, blocks_out, P.B->pblocks.p, (size_t)k * pg::kPriorBlock * sizeof(double)));
+  PGO_TRY(download(ctx, chi2_out, P.B->chi2.p, (size_t)k * sizeof(double)));
+  LSA_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return LSA_OK;
+}
+
+// the two transforms around a solve with priors; what = 0: W P_i, 1: inv(P_0) P_i
+static int pgo_transform(lsa_ctx* ctx, const char* who, int what, const double* poses16, int n, const double* W16, double* poses_out)
+{
+  if (!ctx) return LSA_E_ARG;
+  if (!poses16 || !poses_out || n < 1 || (what == 0 && !W16)) return ctx->fail(LSA_E_ARG, std::string(who) + ": bad argument");
+  if (n > kMaxPoses) return ctx->fail(LSA_E_CAPACITY, std::string(who) + ": more than 262144 poses");
+  Problem P;
+  PGO_TRY(setup(P, ctx, poses16, n, nullptr, nullptr, 0, nullptr));
+  if (what == 0)
+    hipLaunchKernelGGL(k_pgo_premultiply, dim3(blocks_for(n)), dim3(kThreads), 0, ctx->stream, n, pg::load(W16), ptr_of<double>(P.B->poses), ptr_of<double>(P.B->cand));
+  else
+    hipLaunchKernelGGL(k_pgo_reanchor, dim3(blocks_for(n)), dim3(kThreads), 0, ctx->stream, n, ptr_of<double>(P.B->poses), ptr_of<double>(P.B->cand));
+  LSA_HIP(ctx, hipGetLastError());
+  std::vector<double> out((size_t)n * 16);
+  PGO_TRY(download(ctx, out.data(), P.B->cand.p, out.size() * sizeof(double)));
+  LSA_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  std::memcpy(poses_out, out.data(), out.size() * sizeof(double));
+  return LSA_OK;
+}
+int lsa_pgo_premultiply(lsa_ctx* ctx, const double* poses16, int n, const double* W16, double* poses_out)
+{
+  return pgo_transform(ctx, "lsa_pgo_premultiply", 0, poses16, n, W16, poses_out);
+}
+int lsa_pgo_reanchor(lsa_ctx* ctx, const double* poses16, int n, double* poses_out) { return pgo_transform(ctx, "lsa_pgo_reanchor", 1, poses16, n, nullptr, poses_out); }
+
+int lsa_pgo_solve_priors(lsa_ctx* ctx, const double* poses16, int n, const uint8_t* fixed, const lsa_pgo_edge_t* edges, int m, const lsa_pgo_prior_t* priors, int k,
+                         const double* offset16, const lsa_pgo_params_t* params, double* poses_out, lsa_pgo_result_t* result)
+{
   if (!ctx) return LSA_E_ARG;
   lsa_pgo_params_t p;
   lsa_pgo_params_init(&p);
@@ -656,10 +782,10 @@ int lsa_pgo_solve(lsa_ctx* ctx, const double* poses16, int n, const uint8_t* fix
   if (!poses_out || !result || !pg::params_ok(p)) return ctx->fail(LSA_E_ARG, "lsa_pgo_solve: bad argument or parameters out of limits");
   std::string why;
   host::PoseGraph G;
-  if (const int rc = host::PgoBuild(poses16, n, fixed, edges, m, &G, &why); rc != LSA_OK) return ctx->fail(rc, "lsa_pgo_solve: " + why);
+  if (const int rc = host::PgoBuild(poses16, n, fixed, edges, m, &G, &why, priors, k, offset16); rc != LSA_OK) return ctx->fail(rc, "lsa_pgo_solve: " + why);
   if (n > kMaxPoses) return ctx->fail(LSA_E_CAPACITY, "lsa_pgo_solve: more than 262144 poses (the cyclic reduction keeps every level)");
   Problem P;
-  PGO_TRY(setup(P, ctx, poses16, n, fixed, edges, m, &G));
+  PGO_TRY(setup(P, ctx, poses16, n, fixed, edges, m, &G, priors, k, offset16));
   hipStream_t st = ctx->stream;
   const long long nv = 6LL * n;
   const bool diag = p.preconditioner == 1;
@@ -715,6 +841,8 @@ int lsa_pgo_solve(lsa_ctx* ctx, const double* poses16, int n, const uint8_t* fix
     PGO_TRY(finish(P, FIN_STATS, nbn, 0.));
     hipLaunchKernelGGL(k_pgo_retract, dim3(nbn), dim3(kThreads), 0, st, n, x, P.vec(V_DELTA), cand);
     if (m > 0) hipLaunchKernelGGL(k_pgo_chi2, dim3(blocks_for(m)), dim3(kThreads), 0, st, cand, ptr_of<lsa_pgo_edge_t>(P.B->edges), m, ptr_of<double>(P.B->chi2));
+    if (k > 0)
+      hipLaunchKernelGGL(k_pgo_chi2_priors, dim3(blocks_for(k)), dim3(kThreads), 0, st, cand, ptr_of<lsa_pgo_prior_t>(P.B->priors), k, P.O, ptr_of<double>(P.B->chi2) + m);
     PGO_TRY(launch_cost(P));
     PGO_TRY(read_state(P, &s));
     const double model = s.stat[0], step = s.stat[1], Fn = 0.5 * s.stat[3];

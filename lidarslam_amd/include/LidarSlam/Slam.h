@@ -15,9 +15,9 @@
 // Beyond the per-frame path the mirror also carries PCD map IO, the wheel odometer / IMU gravity constraints, the keypoint
 // log (SetLoggingTimeout, SetLoggingStorage, GetLoggedKeypoints) and SetTrajectoryAndRebuildMaps, which brings a corrected
 // trajectory back, and the loop-closure constraint an optimizer needs as input: FindLoopClosureCandidate and
-// RegisterLoggedFrames.  OptimizeLoggedTrajectory optimizes the logged trajectory with such edges on the device.  The reference's
-// pose-graph OPTIMIZER with GPS positions (g2o) is not part of this build: RunPoseGraphOptimization is present
-// with the reference's signature, warns once and changes nothing.
+// RegisterLoggedFrames.  OptimizeLoggedTrajectory optimizes the logged trajectory with such edges on the device, and
+// RunPoseGraphOptimization, the reference's entry point with GPS positions, runs on the same device solver with the positions
+// as priors (no g2o).
 #pragma once
 #include <algorithm>
 #include <array>
@@ -280,20 +280,69 @@ public:
   }
   const std::string& GetLastError() const { return this->LastError; }
 
-  // ---- the pose-graph optimizer (g2o) is not part of this build.  Present with the reference's signature so that
-  // LidarSlamNode.cxx / vtkSlam.cxx compile unchanged; it warns once and does nothing, the way the reference itself answers
-  // RunPoseGraphOptimization without g2o (slam_lib/src/Slam.cxx:355-366: "SLAM PoseGraphOptimization requires G2O, but it
-  // was not found.").  What the reference does AFTER its optimizer is SetTrajectoryAndRebuildMaps below, and the
-  // loop-closure constraints an optimizer wants as input come from RegisterLoggedFrames: run the optimizer of your choice
-  // on GetTrajectory() / GetCovariances() and those edges, and bring its result there.
+  // ---- Slam::RunPoseGraphOptimization (Slam.cxx:355-477) on the device solver (lsa_slam_run_pose_graph_optimization): the
+  // odometry chain of the log weighted by the inverse logged covariances, every pose free, plus a position prior per GPS fix
+  // matched to a logged pose by time, behind inverse(gpsToSensorOffset).  As the reference: gpsToSensorOffset comes back as
+  // the optimized first pose in the GPS frame, the trajectory comes back re-anchored on that pose and goes through
+  // SetTrajectoryAndRebuildMaps.  Needs SetLoggingTimeout(!= 0) while the frames were added.  When it cannot -- no keypoint
+  // log, fewer than two poses or fixes, times that do not overlap, no fix within 0.1 s of a pose, a covariance that is not
+  // positive definite -- it says why once on stderr and in GetLastError(), and changes nothing.  A g2o file is not written.
+  // The third form takes the solver's parameters (params.apply decides whether the maps are rebuilt), a time offset added to
+  // the logged times before they are compared with the fixes', and gives the solver's summary and the optimized poses.
 #ifdef LSA_HAVE_EIGEN
-  void RunPoseGraphOptimization(const std::vector<Transform>&, const std::vector<std::array<double, 9>>&, Eigen::Isometry3d&, const std::string& = "")
-#else
-  void RunPoseGraphOptimization(const std::vector<Transform>&, const std::vector<std::array<double, 9>>&, std::array<double, 16>&, const std::string& = "")
-#endif
+  void RunPoseGraphOptimization(const std::vector<Transform>& gpsPositions, const std::vector<std::array<double, 9>>& gpsCovariances, Eigen::Isometry3d& gpsToSensorOffset,
+                                const std::string& g2oFileName = "")
   {
-    this->NotSupported("RunPoseGraphOptimization", "the pose-graph optimizer (g2o) is not part of this build: maps and trajectory are left unchanged; "
-                                                   "bring an optimizer's result with SetTrajectoryAndRebuildMaps");
+    std::array<double, 16> offset = Transform(gpsToSensorOffset).matrix;
+    this->RunPoseGraphOptimization(gpsPositions, gpsCovariances, offset, g2oFileName);
+    gpsToSensorOffset = Transform(offset).GetIsometry();
+  }
+#endif
+  void RunPoseGraphOptimization(const std::vector<Transform>& gpsPositions, const std::vector<std::array<double, 9>>& gpsCovariances, std::array<double, 16>& gpsToSensorOffset,
+                                const std::string& g2oFileName = "")
+  {
+    if (!g2oFileName.empty()) this->WarnOnce("RunPoseGraphOptimization (g2o file)", "no g2o file is written: the graph is solved on the device");
+    lsa_pgo_params_t params;
+    lsa_pgo_params_init(&params);
+    params.odometry_information = 1;  // the reference's rule: the inverse of the logged covariance
+    params.apply = 1;
+    this->RunPoseGraphOptimization(gpsPositions, gpsCovariances, gpsToSensorOffset, params, 0., nullptr);
+  }
+  std::vector<Transform> RunPoseGraphOptimization(const std::vector<Transform>& gpsPositions, const std::vector<std::array<double, 9>>& gpsCovariances,
+                                                  std::array<double, 16>& gpsToSensorOffset, const lsa_pgo_params_t& params, double timeOffset = 0.,
+                                                  lsa_pgo_result_t* summary = nullptr)
+  {
+    std::vector<Transform> poses = this->GetTrajectory();
+    std::vector<double> rows((poses.size() + 1) * 17), times(gpsPositions.size()), xyz(gpsPositions.size() * 3), cov(gpsPositions.size() * 9);
+    lsa_pgo_result_t result;
+    std::memset(&result, 0, sizeof(result));
+    int rc = LSA_E_ARG;
+    if (gpsCovariances.size() != gpsPositions.size()) this->LastError = "RunPoseGraphOptimization: as many covariances as GPS positions";
+    else
+    {
+      for (std::size_t f = 0; f < gpsPositions.size(); ++f)
+      {
+        times[f] = gpsPositions[f].time;
+        xyz[3 * f] = gpsPositions[f].x(); xyz[3 * f + 1] = gpsPositions[f].y(); xyz[3 * f + 2] = gpsPositions[f].z();
+        std::memcpy(cov.data() + 9 * f, gpsCovariances[f].data(), 9 * sizeof(double));
+      }
+      std::array<double, 16> offset = gpsToSensorOffset;
+      rc = lsa_slam_run_pose_graph_optimization(this->Handle, times.data(), xyz.data(), cov.data(), static_cast<int>(gpsPositions.size()), offset.data(), timeOffset, &params,
+                                                rows.data(), static_cast<int>(poses.size()), &result);
+      this->LastError = rc < 0 ? std::string("RunPoseGraphOptimization: ") + lsa_slam_last_error(this->Handle) : std::string();
+      if (rc >= 0) gpsToSensorOffset = offset;
+    }
+    if (rc < 0)
+    {
+      result.termination = rc;
+      const std::size_t colon = this->LastError.find(": ");
+      std::fprintf(stderr, "\033[1;33m[WARNING] LidarSlam::Slam::RunPoseGraphOptimization: %s; maps and trajectory are left unchanged\033[0m\n",
+                   this->LastError.substr(colon == std::string::npos ? 0 : colon + 2).c_str());
+    }
+    if (summary) *summary = result;
+    if (rc < 0) return {};
+    for (std::size_t i = 0; i < poses.size(); ++i) std::memcpy(poses[i].matrix.data(), rows.data() + 17 * i, 16 * sizeof(double));
+    return poses;
   }
   // ---- a corrected trajectory brought back (Slam.cxx:404-477, everything after the optimizer): the logged poses are
   // replaced by `poses` (as many as GetTrajectory() gives, each with its logged time), every logged frame's keypoints are
@@ -363,7 +412,7 @@ public:
   // what RegisterLoggedFrames returned.  Returns the optimized poses with their logged times (empty when it cannot:
   // GetLastError() says why and summary->termination is the negative LSA_E_* code); with params.apply != 0 they have gone through
   // SetTrajectoryAndRebuildMaps as well, with 0 nothing the frame path reads is touched.  RunPoseGraphOptimization above, the
-  // reference's entry point with GPS positions, is not this and stays as it is.
+  // reference's entry point with GPS positions, runs on the same solver with every pose free and the positions as priors.
   using PoseGraphEdge = lsa_pgo_edge_t;
   using PoseGraphParameters = lsa_pgo_params_t;
   using PoseGraphSummary = lsa_pgo_result_t;

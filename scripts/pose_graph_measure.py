@@ -2,7 +2,10 @@
 circle, --poses poses in all, noisy odometry, --loops true loop edges between the laps.  Records the device's wall time, LM
 iterations and PCG iterations per LM step; the share of factor / apply / spmv with the profiling scopes on; the host
 statement's time for the same graph; and the device solver with the preconditioner reduced to its diagonal blocks
-(preconditioner = 1), so that the file itself shows what the cyclic reduction buys.  Appends to profiles/pose_graph.jsonl."""
+(preconditioner = 1), so that the file itself shows what the cyclic reduction buys.  Appends to profiles/pose_graph.jsonl.
+--gps: the GPS case instead -- every pose free, a position prior every --gps_every poses behind a lever arm, in a frame a known
+world transform away, the start laid onto the fixes by trajectory_alignment; without loop edges and with --loops of them.
+Appends to profiles/pose_graph_gps.jsonl: the device's wall time, LM and PCG iterations, and the host statement's time."""
 import argparse, json, os, sys, time
 import numpy as np
 sys.path.insert(0, os.getcwd())
@@ -14,8 +17,11 @@ ap.add_argument("--laps", type=int, default=2)
 ap.add_argument("--loops", type=int, default=5)
 ap.add_argument("--runs", type=int, default=3)
 ap.add_argument("--diag_pcg_max_iter", type=int, default=20000)
-ap.add_argument("--out", default="profiles/pose_graph.jsonl")
+ap.add_argument("--gps", action="store_true")
+ap.add_argument("--gps_every", type=int, default=10)
+ap.add_argument("--out", default=None)
 a = ap.parse_args()
+a.out = a.out or ("profiles/pose_graph_gps.jsonl" if a.gps else "profiles/pose_graph.jsonl")
 out = open(a.out, "a")
 
 
@@ -36,7 +42,7 @@ def pose(angle):
     return T
 
 
-def graph(n, laps, loops, seed=1):
+def graph(n, laps, loops, seed=1, gps=0):
     rng = np.random.default_rng(seed)
     truth = [pose(2 * np.pi * laps * i / n) for i in range(n)]
     W = np.diag([1e4] * 3 + [2.5e5] * 3)
@@ -56,10 +62,35 @@ def graph(n, laps, loops, seed=1):
         edges.append((a0, b0, np.linalg.inv(truth[a0]) @ truth[b0], W))
     fixed = np.zeros(n, np.uint8)
     fixed[0] = 1
+    if gps:
+        # fixes of 0.03 m at every gps-th pose, seen through a lever arm from a frame 100 m and 0.8 rad away
+        Wt, O = np.eye(4), np.eye(4)
+        Wt[:3, :3], Wt[:3, 3] = rot(np.array([0, 0, 0.8])) @ rot(np.array([0.02, -0.03, 0])), [100, -50, 10]
+        O[:3, :3], O[:3, 3] = rot(np.array([0.1, -0.2, 0.3])), [0.4, -0.3, 1.2]
+        priors = [(i, (Wt @ truth[i] @ O)[:3, 3] + 0.03 * rng.standard_normal(3), np.eye(3) / 0.03**2) for i in range(0, n, gps)]
+        A = L.trajectory_alignment([(init[i] @ O)[:3, 3] for i, _, _ in priors], [g for _, g, _ in priors])
+        return L.pose_graph_premultiply(np.array(init), A), np.zeros(n, np.uint8), L.pose_graph_edges(edges), L.pose_graph_priors(priors), O
     return np.array(init), fixed, L.pose_graph_edges(edges)
 
 
 ctx = L.Context(0)
+if a.gps:
+    for n in a.poses:
+        for loops in (0, a.loops):
+            P, fixed, E, R, O = graph(n, a.laps, loops, gps=a.gps_every)
+            case = dict(poses=n, laps=a.laps, loops=loops, edges=int(E.size), priors=int(R.size))
+            ctx.pose_graph_solve(P, fixed, E, priors=R, offset=O)  # buffers
+            for run in range(a.runs):
+                t0 = time.perf_counter()
+                dev, r = ctx.pose_graph_solve(P, fixed, E, priors=R, offset=O)
+                emit(what="device_gps", run=run, **case, wall_s=time.perf_counter() - t0, lm_iterations=r.iterations, pcg_iterations=r.pcg_iterations,
+                     pcg_per_lm=r.pcg_iterations / max(r.iterations, 1), termination=r.termination, initial_cost=r.initial_cost, final_cost=r.final_cost)
+            t0 = time.perf_counter()
+            host, hr = L.pose_graph_solve_host(P, fixed, E, priors=R, offset=O)
+            emit(what="host_statement_gps", **case, wall_s=time.perf_counter() - t0, lm_iterations=hr.iterations, pcg_iterations=hr.pcg_iterations, termination=hr.termination,
+                 final_cost=hr.final_cost, max_position_difference_m=float(np.abs(host[:, :3, 3] - dev[:, :3, 3]).max()))
+    ctx.close()
+    sys.exit(0)
 for n in a.poses:
     P, fixed, E = graph(n, a.laps, a.loops)
     case = dict(poses=n, laps=a.laps, loops=a.loops, edges=int(E.size))

@@ -6,20 +6,21 @@
 // Host keeps what SURVEY.md 8 leaves on the host: frame checks, pose bookkeeping, the
 // 6-dof trust-region control flow, the rolling voxel maps.  Everything per point / per
 // keypoint runs on the device through lidarslam_amd.h.
+//
+// One class, one unit per job: lsa_slam_core.cpp (construction, the frame path, the look-ahead, the getters),
+// lsa_slam_icp.cpp (the two registrations; their loop is lsa_slam_icp_loop.h), lsa_slam_maps.cpp (sub-maps, speculation,
+// insertion, load / save), lsa_slam_log.cpp (the keypoint log and the calls on it), lsa_slam_params.cpp (parameters by name).
 #pragma once
 #include <array>
 #include <atomic>
-#include <condition_variable>
 #include <deque>
 #include <limits>
 #include <map>
-#include <functional>
 #include <memory>
-#include <mutex>
 #include <string>
-#include <thread>
 #include <vector>
 #include "../../../include/lidarslam_amd.h"
+#include "lsa_host_worker.h"
 #include "lsa_hostmath.h"
 #include "lsa_lm.h"
 #include "lsa_loop_closure.h"
@@ -55,36 +56,6 @@ struct MatchDebug
 {
   std::vector<uint8_t> status;
   std::vector<double> weights;
-};
-
-// One persistent host thread that runs jobs in submission order.  Each map has one: the keyframe's
-// insertion (RollingGrid::Add, hash-map bound) is handed to it at the end of AddFrame and overlaps the next
-// frame's keypoint extraction and ego-motion ICP on the device, and the sub-maps of the three keypoint
-// types are extracted side by side.  Wait() is called before anything else reads a map.
-// Same operations in the same order on the same containers: results do not depend on the overlap.
-class HostWorker
-{
-public:
-  HostWorker();
-  ~HostWorker();
-  void Submit(std::function<void()> job);
-  void Wait();
-  // A job is about to be submitted (within `seconds`): the thread wakes up now and polls for it instead of sleeping, so that
-  // the job starts within a microsecond of Submit instead of a scheduler's wake-up later (tens of microseconds on an idle
-  // host, a fifth of a frame and more on a busy one: a map insertion enqueued late runs INTO the next frame's ICP kernels
-  // instead of in front of them).  Costs the polling time on one core, bounded by `seconds`.
-  void Expect(double seconds);
-
-private:
-  void Run();
-  std::mutex M;
-  std::condition_variable Cv, Idle;
-  std::deque<std::function<void()>> Jobs;
-  bool Busy = false, Quit = false;
-  std::atomic<int> Posted{0};           // jobs in the queue (read without the lock by the polling thread)
-  std::atomic<long long> PollUntil{0};  // steady-clock nanoseconds
-  std::atomic<bool> Leaving{false};
-  std::thread T;
 };
 
 class SlamCore
@@ -140,7 +111,6 @@ public:
   // the fixes, brought back onto logged pose 0.  gpsToSensor16: in the calibration, out the optimized pose 0 in the GPS frame.
   int RunPoseGraphOptimization(const double* gpsTimes, const double* gpsXyz, const double* gpsCov9, int G, double* gpsToSensor16, double timeOffset,
                                const lsa_pgo_params_t* params, double* poses17, int capacity, lsa_pgo_result_t* result);
-  int LoggedChainEdges(const lsa_pgo_params_t& p, const std::string& who, lsa_pgo_edge_t* edges);
   int LoggedFrames() const;
   int GetLoggedKeypoints(int frame, int type, std::vector<lsa_point_t>& out);
   void HintNextStoredFrame(int slot) { NextStoredSlot = slot; }
@@ -291,35 +261,19 @@ public:
   int KeypointCounts[3] = {0, 0, 0};
 
 private:
+  int Fail(int rc, const char* where);
+  lsa_ctx* Ctx = nullptr;
+  std::string LastError;
+
+  // ---- frame path (lsa_slam_core.cpp) ----
   int ProcessCurrentFrame(uint64_t stampUs);
   int ExtractKeypoints();
-  int ComputeEgoMotion();
-  int Localization();
-  // The ICP loop of both, under whichever schedule ICPAhead allows (lsa_slam_core.cpp): the spec says what the loop
-  // matches and solves, the callables what only one of the two does at that point of an iteration.
-  struct IcpLoopSpec;
-  struct IcpUndistortion;
-  template <class Top, class Enqueued, class Solved, class Skipped, class Accepted, class Finished>
-  int RunIcpLoop(const IcpLoopSpec& spec, Pose& pose, const Top& top, const Enqueued& enqueued, const Solved& solved, const Skipped& skipped,
-                 const Accepted& accepted, const Finished& finished);
-  int DownloadMatchDebug(int set, unsigned typeMask, MatchDebug* debug);
-  SensorConstraints SensorManagers;
-  lsa_sensor_terms_t LocSensorTerms = {};
-  int UpdateMapsUsingTworld();
+  int ExtractFrames();
+  int PrepareNextEgoMotionTargets();
   int EstimateOverlap();
   void CheckMotionLimits();
-  float PreviousVelocity[2] = {0.f, 0.f};
-  long long EgoMatchSerial[3] = {0, 0, 0}, LocMatchSerial[3] = {0, 0, 0};  // lsa_match_serial after the last iteration
-  void LogCurrentFrameState(double time);
-  bool KpLogStopped = false;  // a chunk of the keypoint log could not be allocated: nothing more is logged until Reset(true)
-  Pose InterpolateScanPose(double time) const;
-  int InitUndistortion();
-  void InitUndistortion(double t0, double t1);
-  int RefineUndistortion(Pose* outD0 = nullptr, Pose* outD1 = nullptr);
-  int Fail(int rc, const char* where);
-  lsa_match_params_t EgoMatchParams() const;
-  lsa_match_params_t LocMatchParams() const;
-
+  unsigned UsedTypesMask() const { return (UseKeypoints[0] ? 1u : 0u) | (UseKeypoints[1] ? 2u : 0u) | (UseKeypoints[2] ? 4u : 0u); }  // bit k: type k is in use
+  void ApplySearchTuning(lsa_ctx* ctx);  // the search's form and tuning (results do not depend on either)
   // the frames of the current AddFrames call when there are several (device-resident, in the last slots of the
   // context's frame store); empty for the single-frame calls, whose frame is the context's current one
   struct HeldFrame
@@ -331,41 +285,42 @@ private:
   };
   std::vector<HeldFrame> CurrentFrames;
   float Device0AzimuthalResolution = 0.f;  // parked here while another device's frame is extracted
-  int ExtractFrames();
-  int PrepareNextEgoMotionTargets();
-  void ArmLookaheadInterlude();
-  int InterludeWork();
-  int DevSpecStatus = 0;   // written by the look-ahead thread, read once DevSpecRunning is false
-  std::atomic<bool> DevSpecRunning{false};
-  int DevSpecBackoff = 0;  // frames the sub-maps ahead of time are not tried for (they were late)
-  int DevSpecLate = 0;     // frames in a row the localization had to wait for them
-  int DevSpecGood = 0, DevSpecPenalty = 4;
-  int FinishLookaheadInterlude();
-  bool InterludeRan = true;
-  int InterludeStatus = 0;
-  int NextStoredSlot = -1;
-  bool NextFrameHinted = false;   // a cloud was announced (HintNextFrame) and its look-ahead extraction not started yet
-  double DbgAcc[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // (diagnostics, LSA_STAGE_DEBUG=1: seconds outside the stage timers, printed when the object goes)
-  long DbgFrames = 0;
-  bool WorkerPrewake = true;      // the worker threads are woken ahead of the jobs whose time is known (HostWorker::Expect)
-  bool HoldLookahead = false;     // ... and must not start yet: the sub-maps extracted ahead of time for THIS frame's localization go onto the look-ahead stream first
-  int TryStartLookahead();        // starts it as soon as the upload has been enqueued
-  lsa_ctx* Ctx = nullptr;
-  // RegisterLoggedFrames' own context on the same device, made by its first call: the query keypoints (its working set), a
-  // scratch map per keypoint type and the targets their sub-maps become
-  lsa_ctx* LoopCtx = nullptr;
-  lsa_device_grid* LoopMaps[3] = {nullptr, nullptr, nullptr};
-  int EnsureLoopClosureScratch();
-  double PoseGraphSeconds = 0.;   // the last OptimizeLoggedTrajectory's or RunPoseGraphOptimization's solve by the host's clock
-  double LoopClosureSeconds[4] = {0., 0., 0., 0.};  // the last call by the host's clock: replays, scratch maps, ICP loop, all of it
-  std::string LastError;
   uint64_t CurrentStamp = 0;
   bool HaveFrame = false;
   double CurrentTime = 0.;
-  WithinFrameMotion Motion;
   Pose KfLastPose;
-  MatchDebug EgoDebug[3], LocDebug[3];
+  float PreviousVelocity[2] = {0.f, 0.f};
   std::vector<lsa_point_t> Scratch;
+  SensorConstraints SensorManagers;
+  lsa_sensor_terms_t LocSensorTerms = {};
+
+  // ---- ICP loops and undistortion (lsa_slam_icp.cpp; the loop is lsa_slam_icp_loop.h) ----
+  int ComputeEgoMotion();
+  int Localization();
+  // The ICP loop of both, and of RegisterLoggedFrames, under whichever schedule ICPAhead allows: the spec says what the loop
+  // matches and solves, the callables what only one of them does at that point of an iteration.
+  struct IcpLoopSpec;
+  struct IcpUndistortion;
+  template <class Top, class Enqueued, class Solved, class Skipped, class Accepted, class Finished>
+  int RunIcpLoop(const IcpLoopSpec& spec, Pose& pose, const Top& top, const Enqueued& enqueued, const Solved& solved, const Skipped& skipped,
+                 const Accepted& accepted, const Finished& finished);
+  lsa_match_params_t EgoMatchParams() const;
+  lsa_match_params_t LocMatchParams() const;
+  int DownloadMatchDebug(int set, unsigned typeMask, MatchDebug* debug);
+  Pose InterpolateScanPose(double time) const;
+  int InitUndistortion();
+  void InitUndistortion(double t0, double t1);
+  int RefineUndistortion(Pose* outD0 = nullptr, Pose* outD1 = nullptr);
+  WithinFrameMotion Motion;
+  long long EgoMatchSerial[3] = {0, 0, 0}, LocMatchSerial[3] = {0, 0, 0};  // lsa_match_serial after the last iteration
+  MatchDebug EgoDebug[3], LocDebug[3];
+
+  // ---- sub-maps and speculation (lsa_slam_maps.cpp) ----
+  // What Localization() searches: which sub-maps are stale, what the speculation left is taken or dropped, the rest extracted
+  int PrepareLocalizationSubMaps(bool boxesEnqueued);
+  int UpdateMapsUsingTworld();
+  // edge length of the search cells of map k's target: the map holds one point per leaf voxel, a cell of about one leaf keeps a handful of candidates
+  float MapSearchCell(int k) const { return static_cast<float>((k == LSA_EDGE ? KnnCellScaleMapsEdges : KnnCellScaleMaps) * LocalMaps[k]->GetLeafSize()); }
   // Sub-maps are extracted ahead of time: as soon as the keypoints exist, their bounding box under the
   // PREDICTED pose is reduced on the device (asynchronously) and the map workers extract the sub-maps for it
   // while the ego-motion ICP runs.  Localization() checks the box under the actual pose: the sub-map only
@@ -373,6 +328,7 @@ private:
   // the sub-map is extracted again.  Same result either way.
   int BeginSubMapSpeculation(const Pose& predicted);
   int FinishSubMapSpeculation();
+  int StageSpeculativeSubMaps();
   void DropMapLookahead();  // sub-maps extracted ahead and spare targets made from the maps as they were
   bool SpecPending = false;
   bool SpecBuilt[3] = {false, false, false};  // written by the workers, read after WaitMaps
@@ -380,13 +336,62 @@ private:
   // grid on the look-ahead stream) at its next stop between two kernels' results
   std::atomic<bool> SpecDone[3];
   bool SpecStaged[3] = {false, false, false};
-  int StageSpeculativeSubMaps();
+  // ... with the maps on the device (DevSpec[k] above: a sub-map of map k was asked for ahead of time)
+  int DevSpecStatus = 0;   // written by the look-ahead thread, read once DevSpecRunning is false
+  std::atomic<bool> DevSpecRunning{false};
+  int DevSpecBackoff = 0;  // frames the sub-maps ahead of time are not tried for (they were late)
+  int DevSpecLate = 0;     // frames in a row the localization had to wait for them
+  int DevSpecGood = 0, DevSpecPenalty = 4;
   double MapJobSeconds[3] = {0., 0., 0.};  // written by the workers, read after WaitMaps
-  HostWorker AheadWorker;                   // enqueues the next frame's ego-motion targets beside the first solve
-  int AheadStatus = 0;                  // result of the work done between a solve's launch and its wait
-  int MapJobFailed[3] = {0, 0, 0};          // a device-map insertion that failed on its worker (read after WaitMaps)
-  HostWorker MapWorker[3];                  // one per map: the three rolling grids are independent
+  int MapJobFailed[3] = {0, 0, 0};         // a device-map insertion that failed on its worker (read after WaitMaps)
+
+  // ---- look-ahead and interlude (lsa_slam_core.cpp) ----
+  int TryStartLookahead();        // starts the announced cloud's extraction as soon as its upload has been enqueued
+  void ArmLookaheadInterlude();
+  int InterludeWork();
+  int FinishLookaheadInterlude();
+  bool InterludeRan = true;
+  int InterludeStatus = 0;
+  int NextStoredSlot = -1;
+  bool NextFrameHinted = false;   // a cloud was announced (HintNextFrame) and its look-ahead extraction not started yet
+  bool HoldLookahead = false;     // ... and must not start yet: the sub-maps extracted ahead of time for THIS frame's localization go onto the look-ahead stream first
+  int AheadStatus = 0;            // result of the work the look-ahead thread did beside the first ego-motion solve
+
+  // ---- keypoint log and the scratch context (lsa_slam_log.cpp) ----
+  void LogCurrentFrameState(double time);
+  bool KpLogStopped = false;  // a chunk of the keypoint log could not be allocated: nothing more is logged until Reset(true)
+  // What every call on the log refuses first: logging off (`whatIsMissing` ends that sentence), logging stopped and, with
+  // `covering`, LogCovers.  Returns the number of logged poses, or the refusal's code with its text in LastError.
+  int LogReady(const std::string& who, const char* whatIsMissing, bool covering = true);
+  int LogCovers(const std::string& who);  // refuses a keypoint log that has fewer frames than there are logged poses
+  void LoggedPoses16(std::vector<double>& poses, std::vector<double>* times) const;  // the logged trajectory, 16 doubles a pose
+  std::vector<double> RowsOf(const double* poses16, int n) const;  // rows of lsa_slam_get_trajectory: the poses dated like the log
+  // the two pose-graph calls: what both refuse and pack before their own part, and everything from the solve on
+  struct PoseGraphProblem;
+  int PoseGraphBegin(const std::string& who, const lsa_pgo_params_t* params, const std::string& tooFew, int capacity, PoseGraphProblem& pb);
+  int PoseGraphEdges(const std::string& who, const lsa_pgo_edge_t* loopEdges, int m, PoseGraphProblem& pb);
+  template <class Solve>
+  int PoseGraphSolve(const std::string& who, const PoseGraphProblem& pb, const Solve& solve, double* poses17, lsa_pgo_result_t* result);
+  int LoggedChainEdges(const lsa_pgo_params_t& p, const std::string& who, lsa_pgo_edge_t* edges);
+  // RegisterLoggedFrames' and the pose-graph solves' own context on the same device, made by the first call: the query
+  // keypoints (its working set), a scratch map per keypoint type and the targets their sub-maps become
+  lsa_ctx* LoopCtx = nullptr;
+  lsa_device_grid* LoopMaps[3] = {nullptr, nullptr, nullptr};
+  int EnsureLoopClosureScratch();
+
+  // ---- diagnostics ----
+  double DbgAcc[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // (LSA_STAGE_DEBUG=1: seconds outside the stage timers, printed when the object goes)
+  long DbgFrames = 0;
+  double PoseGraphSeconds = 0.;   // the last OptimizeLoggedTrajectory's or RunPoseGraphOptimization's solve by the host's clock
+  double LoopClosureSeconds[4] = {0., 0., 0., 0.};  // the last call by the host's clock: replays, scratch maps, ICP loop, all of it
+
+  // ---- workers ----
+  // These stay the LAST data members: members are destroyed in reverse order of declaration, so the threads are joined
+  // before any state their jobs touch goes away (and they start after all of it exists).
+  bool WorkerPrewake = true;  // the worker threads are woken ahead of the jobs whose time is known (HostWorker::Expect)
   void WaitMaps() { for (auto& w : MapWorker) w.Wait(); AheadWorker.Wait(); }
+  HostWorker AheadWorker;     // enqueues the sub-maps ahead of time and the next frame's ego-motion targets beside the first solve
+  HostWorker MapWorker[3];    // one per map: the three rolling grids are independent
 };
 
 }  // namespace host

@@ -6,7 +6,7 @@
 //                  (SetTimes(t[i] - t[i-1], 0.), evaluated at the point's own time) when undistortion is on, frame 0 and
 //                  everything otherwise with the rigid pose[i]; and the box of the LAST frame's points (:472-475)
 //   k_log_replay_range  the same for a range of frames, under one of three time rules, with the box of ALL replayed points:
-//                  what the registration of logged frames (host/lsa_slam_core.cpp, RegisterLoggedFrames) makes its target
+//                  what the registration of logged frames (host/lsa_slam_log.cpp, RegisterLoggedFrames) makes its target
 //                  sub-map and its query keypoints of
 // Storage: an arena of fixed-size chunks.  A frame (its three types, one after the other) never straddles two chunks, so
 // growth never copies; a chunk whose frames have all been popped goes to a free list; nothing is freed while work may be in

@@ -1,5 +1,5 @@
 // lsa_kplog_io.h -- the keypoint log's replay of a RANGE of frames into destinations on the device (lsa_kplog.hip), for the
-// library's own callers: the registration of logged frames (host/lsa_slam_core.cpp) replays the frames around a revisited
+// library's own callers: the registration of logged frames (host/lsa_slam_log.cpp) replays the frames around a revisited
 // pose into the batch buffers of scratch maps and the query frames into a keypoint set.  lsa_kplog_replay_range (the C ABI)
 // is the same replay into pinned host memory.
 #pragma once

@@ -484,7 +484,7 @@ __device__ __forceinline__ void lm_step(const LmParams& p, Shared& sh, bool firs
   if (threadIdx.x == 0) sh.stop = lm_take_step<N>(p, sh) ? 1 : 0;
 }
 
-// What the host's loop does between two ICP iterations (host/lsa_slam_core.cpp, Slam.cxx:940-950 / 1134-1151), for the
+// What the host's loop does between two ICP iterations (host/lsa_slam_icp.cpp, Slam.cxx:940-950 / 1134-1151), for the
 // iteration enqueued behind this solve: does it run (the solve was not skipped and made a step), the pose from the solve's
 // parameters, the next start point (the round trip through the matrix, as LocalOptimizer::SetPosePrior makes it) and,
 // localization, Slam::RefineUndistortion under the new pose.  lsa_posemath.h is the host's arithmetic: the host works
@@ -922,7 +922,7 @@ int lsa_icp_link(lsa_ctx* ctx)
 }
 
 // What the HOST works out between two iterations from a solve's result (lsa_posemath.h compiled for this side: the loops
-// of host/lsa_slam_core.cpp call the same functions), laid out as the device's block: a test holds lsa_icp_link_peek
+// of host/lsa_slam_icp.cpp call the same functions), laid out as the device's block: a test holds lsa_icp_link_peek
 // against it, word for word.
 int lsa_icp_link_expected(const double x[6], int skipped, int successful_steps, const lsa_icp_link_t* link, unsigned long long words[64], double motion_after[16])
 {

@@ -1,5 +1,5 @@
 // lsa_posemath.h -- the 6-dof pose algebra between two ICP iterations, ONE source for the host (the loops of
-// host/lsa_slam_core.cpp) and the device (the link a solve leaves for the iteration enqueued behind it, lsa_lm.hip); the
+// host/lsa_slam_icp.cpp) and the device (the link a solve leaves for the iteration enqueued behind it, lsa_lm.hip); the
 // elementary functions are include/lsa_pmath.h's, which the tests' CPU restatement evaluates as well.
 // Restates the Eigen operations the reference performs on Eigen::Isometry3d:
 //   Utils::XYZRPYtoIsometry / IsometryToXYZRPY   slam_lib/src/Utilities.cxx:33-77

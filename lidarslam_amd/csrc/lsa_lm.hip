@@ -13,8 +13,9 @@
 //     Two parities of slots: a block can be at most one evaluation ahead of the slowest;
 //   * EVERY block folds all partial sums in a fixed order -- 8 partial sums per value over the blocks j, j + 8, ..., then
 //     the 8 in order; wavefront j reads the granules of its blocks and sums them itself: no copy of the granules in LDS,
-//     one barrier between publishing and the step -- and runs the 6x6 trust-region algebra itself: same inputs, same
-//     instructions, same result in every block, so the next candidate needs no broadcast;
+//     one barrier between publishing and the step -- and runs the 6x6 trust-region algebra itself, its first wavefront
+//     with a row of the system per lane (lm_step): same inputs, same instructions, same result in every block, so the
+//     next candidate needs no broadcast;
 //   * block 0 hands pose, summary and the normal equations at the final point to the host through the same
 //     kind of granules in coherent host memory.
 // The arithmetic of the trust-region step is the host loop's, operation for operation (no FMA contraction, IEEE
@@ -77,8 +78,8 @@ static_assert(kResCount <= kLmOut, "result does not fit the mailbox");
 __device__ __forceinline__ constexpr int hidx(int a, int b) { return 7 + a * 6 - (a * (a - 1)) / 2 + (b - a); }
 __device__ __forceinline__ constexpr int hsym(int a, int b) { return a <= b ? hidx(a, b) : hidx(b, a); }
 
-// trust-region state between two evaluations (thread 0 of every block keeps its own copy in LDS: nothing of it is
-// live in registers while the residual blocks are evaluated)
+// trust-region state between two evaluations (every block keeps its own copy in LDS: nothing of it is live in registers
+// while the residual blocks are evaluated; lm_step loads it into the first wavefront's lanes and lane 0 writes it back)
 struct LmState
 {
   int cur_buf;             // which of Shared::sums holds the sums at the current point x (the other one takes the next evaluation's)
@@ -95,7 +96,7 @@ struct Shared
   // The sums over ALL residual blocks, twice: at the current point, and of the evaluation under way / just done.  A step that
   // is accepted makes the second the first by flipping LmState::cur_buf (29 values that one thread no longer copies).
   double sums[2][kAccumVals];
-  double Hs[36], gs[6];     // the scaled system of the step under way (lm_scale_system: a lane per entry)
+  double Hs[36], gs[6];     // the scaled system at the current point (lm_step: written when a point is accepted, lane a its row)
   double w[6];              // the point to evaluate next
   double rot[39];           // R, dR/drx, dR/dry, dR/drz, t at w
   LmState lm;
@@ -117,6 +118,14 @@ __device__ __forceinline__ double lane_value(double v, int lane)
 {
   const long long b = __double_as_longlong(v);
   const int lo = __shfl((int)(b & 0xffffffffll), lane), hi = __shfl((int)(b >> 32), lane);
+  return __longlong_as_double(((long long)hi << 32) | (long long)(unsigned)lo);
+}
+
+// the value lane `src` of the wavefront holds (the same src in all lanes: v_readlane), the same value in every lane afterwards
+__device__ __forceinline__ double lane_bcast(double v, int src)
+{
+  const long long b = __double_as_longlong(v);
+  const int lo = __builtin_amdgcn_readlane((int)(b & 0xffffffffll), src), hi = __builtin_amdgcn_readlane((int)(b >> 32), src);
   return __longlong_as_double(((long long)hi << 32) | (long long)(unsigned)lo);
 }
 
@@ -257,23 +266,23 @@ enum LmCode
   kCodeFunctionTolerance
 };
 
-// sh.w = the point to evaluate next (one thread); its rotation and derivatives follow in finish_point
-__device__ __forceinline__ void set_point(Shared& sh, const double w[6])
+// sh.w = the point to evaluate next, sh.rot = rotation and derivatives there (CeresCostFunctions.h:67-79).  The first
+// wavefront runs it, all lanes; every lane holds the point (the same six values in all of them: lm_step works the
+// candidate out that way), so the six lanes that work out the three cosines and three sines -- a few hundred dependent
+// instructions each, side by side instead of one lane six times -- take their angle from their own registers and do not
+// wait for sh.w to make the round trip through LDS.
+// (The point comes by value: a lane's choice among values is a select, among the elements of an array in memory it would
+// be an indexed load from scratch memory.)
+__device__ __forceinline__ void finish_point(Shared& sh, double x, double y, double z, double rx, double ry, double rz)
 {
-#pragma unroll
-  for (int a = 0; a < 6; ++a) sh.w[a] = w[a];
-}
-// sh.rot = rotation and derivatives at sh.w (CeresCostFunctions.h:67-79).  The first wavefront runs it, all lanes: the
-// three cosines and three sines -- a few hundred dependent instructions each, the longest part of what lies between two
-// evaluations -- are worked out by six lanes side by side instead of one lane six times.
-__device__ __forceinline__ void finish_point(Shared& sh)
-{
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // sh.w was written by lane 0 of this wavefront
-  const int lane = threadIdx.x & 63;
-  const double angle = sh.w[3 + (lane < 6 ? lane % 3 : 0)];
+  const double w[6] = {x, y, z, rx, ry, rz};
+  int lane = threadIdx.x & 63;
+  asm volatile("" : "+v"(lane));  // (as in lm_step: no lane masks kept in scalar registers across the evaluation)
+  const int k = lane < 6 ? lane % 3 : 0;
+  const double angle = k == 0 ? rx : (k == 1 ? ry : rz);
   const double v = lane < 3 ? lsa_cos(angle) : lsa_sin(angle);
-  const double cx = lane_value(v, 0), cy = lane_value(v, 1), cz = lane_value(v, 2);
-  const double sx = lane_value(v, 3), sy = lane_value(v, 4), sz = lane_value(v, 5);
+  const double cx = lane_bcast(v, 0), cy = lane_bcast(v, 1), cz = lane_bcast(v, 2);
+  const double sx = lane_bcast(v, 3), sy = lane_bcast(v, 4), sz = lane_bcast(v, 5);
   if (lane == 0)
   {
     double R[9], dRx[9], dRy[9], dRz[9];
@@ -281,207 +290,309 @@ __device__ __forceinline__ void finish_point(Shared& sh)
 #pragma unroll
     for (int i = 0; i < 9; ++i) { sh.rot[i] = R[i]; sh.rot[9 + i] = dRx[i]; sh.rot[18 + i] = dRy[i]; sh.rot[27 + i] = dRz[i]; }
 #pragma unroll
-    for (int i = 0; i < 3; ++i) sh.rot[36 + i] = sh.w[i];
+    for (int i = 0; i < 3; ++i) sh.rot[36 + i] = w[i];
+#pragma unroll
+    for (int a = 0; a < 6; ++a) sh.w[a] = w[a];
   }
 }
 
 // What the trust-region loop of host/lsa_lm.cpp (LocalOptimizer::Solve) does between two evaluations, N active
 // parameters: all 6, or (x, y, rz) in 2D mode (SubsetParameterization(6, {2, 3, 4}), LocalOptimizer.cxx:89-90).
-// In: sh.sums[1 - cur_buf] = the sums at sh.w (the start point when first, a candidate afterwards).  Out: sh.w / sh.rot =
-// the next candidate, or true = the solve is over.  Three parts, the first wavefront runs them: lm_decide (one lane: what
-// became of the candidate), lm_scale_system (a lane per entry of the Jacobi-scaled normal equations), lm_take_step (one lane:
-// the damped solve and the next candidate).  The arithmetic of every value is the host loop's, operation for operation.
+// In: sh.sums[1 - cur_buf] = the sums at sh.w (the start point when first, a candidate afterwards).  Out: cand = the next
+// candidate, or true = the solve is over (sh.stop says so to the other wavefronts behind the barrier).
+//
+// The first wavefront runs it, ALL lanes through the same instructions.  What is one value -- the decision on the
+// candidate, the radius, the pivots, the step, the next candidate -- every lane works out for itself from the same
+// operands (no more instructions than one lane alone would issue, and nothing to hand round afterwards); what is a row
+// of the 6 x 6 system belongs to lane a < N, and lane N carries the right-hand side as one more row:
+//   * the Jacobi scales 1 / (1 + sqrt(H_aa)), the row of the scaled system, the clamped diagonal and M_aa: lane a;
+//   * the Cholesky factor column by column: the pivot goes round (v_readlane), lane i > j works out L_ij, and lane N the
+//     forward substitution's y_j by the same formula -- every entry subtracts its products in the order k = 0, 1, ...
+//     (each as soon as column k exists), and multiplies by the reciprocal of the pivot, as solve_spd<N> does;
+//   * back substitution row by row (its sums run over k ascending while x_k arrive descending: nothing to spread);
+//   * the rows t_a = sum_b Hs_ab step_b of the model's cost change: lane a; s.g and s.Hs are added in order.
+// The scaled system of the current point stays in sh.Hs / sh.gs from the accepted step (or the start) that made it; a
+// rejected step only loads it.  The system of the point just evaluated is formed before it is known whether the
+// candidate is accepted -- its loads and products are independent of the decision's divisions and run in their shadow --
+// and stored only if it is.  Everything the step reads from LDS is loaded at its head, one latency for all of it.
+// The arithmetic of every value is the host loop's, operation for operation, every sum in the host's order.
 template <int N> __device__ __forceinline__ constexpr int lm_act(int a) { return N == 6 ? a : (a == 2 ? 5 : a); }
 template <int N>
-__device__ __forceinline__ double lm_grad_max(const double* cur)
+__device__ __forceinline__ double lm_grad_max(const double g[N])
 {
   double m = 0;
 #pragma unroll
-  for (int a = 0; a < N; ++a) { const double v = __builtin_fabs(cur[1 + lm_act<N>(a)]); m = m > v ? m : v; }  // std::max(m, v)
+  for (int a = 0; a < N; ++a) { const double v = __builtin_fabs(g[a]); m = m > v ? m : v; }  // std::max(m, v)
   return m;
 }
 template <int N>
-__device__ bool lm_decide(const LmParams& p, Shared& sh, bool first)
+__device__ __forceinline__ double lm_x_norm(const double x[6])
+{
+  double s = 0;
+#pragma unroll
+  for (int a = 0; a < N; ++a) s += x[lm_act<N>(a)] * x[lm_act<N>(a)];
+  return __builtin_sqrt(s);
+}
+template <int N>
+__device__ __forceinline__ bool lm_step(const LmParams& p, Shared& sh, bool first, double cand[6])
 {
   const double function_tolerance = 1e-6, gradient_tolerance = 1e-10, parameter_tolerance = 1e-8;
-  const double min_relative_decrease = 1e-3, max_radius = 1e16;
+  const double min_relative_decrease = 1e-3, max_radius = 1e16, min_trust_region_radius = 1e-32;
+  const double min_diagonal = 1e-6, max_diagonal = 1e32;
+  const int max_consecutive_invalid = 5;
+  // (The lane number passes through an empty asm statement: the lane masks made from it -- a pair of scalar registers
+  // for every `row == j` -- would otherwise be worked out once, ahead of the loop over the evaluations, and stay live
+  // through the residual blocks, whose rotation constants then no longer fit the scalar registers.)
+  int lane = threadIdx.x & 63;
+  asm volatile("" : "+v"(lane));
+  const bool l0 = lane == 0;
+  const int row = lane < N ? lane : 0;  // (the lanes behind the rows work row 0 out again: nobody reads what they hold)
+  const int fr = N == 6 ? row : (row == 2 ? 5 : row);  // lm_act<N>(row)
   LmState& lm = sh.lm;
-  const double* cur = sh.sums[lm.cur_buf];
-  const double* tot = sh.sums[1 - lm.cur_buf];
-  auto xnorm = [&]() {
-    double s = 0;
-#pragma unroll
-    for (int a = 0; a < N; ++a) s += lm.x[lm_act<N>(a)] * lm.x[lm_act<N>(a)];
-    return __builtin_sqrt(s);
+  unsigned long long t0 = sh.st0;  // tracing (block 0): the clock at the head of the part under way
+  auto stamp = [&](int part) {
+    if (t0 && l0) { const unsigned long long n = wall_clock64(); sh.sub[part] += n - t0; t0 = n; }
   };
 
+  // ---- everything the step reads
+  int cur_buf = lm.cur_buf;
+  const double* tot = sh.sums[1 - cur_buf];  // at the point just evaluated
+  const double* old = sh.sums[cur_buf];      // at the current point
+  const double tot_cost = tot[0], old_cost = old[0], tot_count = tot[28];
+  double tot_g[N], old_g[N], tot_row[N], kept_row[N], kept_gs[N], scale[N], x_old[6], x_w[6];
+#pragma unroll
+  for (int a = 0; a < N; ++a)
+  {
+    const int fb = lm_act<N>(a);
+    const int lo = fr <= fb ? fr : fb, hi = fr <= fb ? fb : fr;
+    tot_g[a] = tot[1 + fb];
+    old_g[a] = old[1 + fb];
+    tot_row[a] = tot[7 + lo * 6 - (lo * (lo - 1)) / 2 + (hi - lo)];  // hsym(fr, fb)
+    kept_row[a] = sh.Hs[row * N + a];
+    kept_gs[a] = sh.gs[a];
+    scale[a] = lm.scale[a];
+  }
+#pragma unroll
+  for (int a = 0; a < 6; ++a) { x_old[a] = lm.x[a]; x_w[a] = sh.w[a]; }
+  double scale_row = lm.scale[row], diag_row = lm.diag[row];
+  double radius = lm.radius, decrease_factor = lm.decrease_factor, x_norm = lm.x_norm, model_cost_change = lm.model_cost_change, delta_norm = lm.delta_norm;
+  int reuse_diagonal = lm.reuse_diagonal, consecutive_invalid = lm.consecutive_invalid, iter = lm.iter;
+  int successful = lm.successful, unsuccessful = lm.unsuccessful, evaluations = lm.evaluations;
+  double tot_diag = tot_row[0];  // H(fr, fr)
+#pragma unroll
+  for (int b = 1; b < N; ++b)
+    if (row == b) tot_diag = tot_row[b];
+
+  // ---- what became of the candidate; use_tot: the sums just folded are the current ones from now on
+  bool use_tot;
   if (first)
   {
-    lm.matches = (int)tot[28];
-    if (lm.matches < p.min_matches)
+    const int matches = (int)tot_count;
+    if (l0) lm.matches = matches;
+    if (matches < p.min_matches)
     {
-      lm.skipped = 1;
-      lm.code = kCodeNotEnoughMatches;
+      if (l0) { lm.skipped = 1; lm.code = kCodeNotEnoughMatches; sh.stop = 1; }
       return true;
     }
-    lm.cur_buf ^= 1;  // the sums at the start point are the current ones
-    cur = tot;
-    lm.initial_cost = cur[0];
-    lm.successful = 1;  // iteration 0 is reported as a successful step by Ceres
+    use_tot = true;  // the sums at the start point are the current ones
+    successful = 1;  // iteration 0 is reported as a successful step by Ceres
+    scale_row = 1.0 / (1.0 + __builtin_sqrt(tot_diag));  // Jacobi scaling, once
 #pragma unroll
-    for (int a = 0; a < N; ++a) lm.scale[a] = 1.0 / (1.0 + __builtin_sqrt(cur[hidx(lm_act<N>(a), lm_act<N>(a))]));  // Jacobi scaling, once
-    if (lm_grad_max<N>(cur) <= gradient_tolerance) { lm.code = kCodeGradient0; return true; }
-    lm.x_norm = xnorm();
+    for (int a = 0; a < N; ++a) scale[a] = lane_bcast(scale_row, a);
+    if (lane < N) lm.scale[lane] = scale_row;
+    if (l0) { lm.initial_cost = tot_cost; lm.cur_buf = cur_buf ^ 1; lm.successful = 1; }
+    if (lm_grad_max<N>(tot_g) <= gradient_tolerance)
+    {
+      if (l0) { lm.code = kCodeGradient0; sh.stop = 1; }
+      return true;
+    }
+    x_norm = lm_x_norm<N>(x_old);  // (sh.w is the start point, and so is LmState::x)
   }
   else
   {
     // parameter / function tolerance terminate WITHOUT taking the candidate step
-    if (lm.delta_norm <= parameter_tolerance * (lm.x_norm + parameter_tolerance)) { lm.code = kCodeParameterTolerance; return true; }
-    const double cost_change = cur[0] - tot[0];
-    if (__builtin_fabs(cost_change) <= function_tolerance * cur[0]) { lm.code = kCodeFunctionTolerance; return true; }
-    const double relative_decrease = cost_change / lm.model_cost_change;
-    if (relative_decrease > min_relative_decrease)
+    if (delta_norm <= parameter_tolerance * (x_norm + parameter_tolerance))
     {
-#pragma unroll
-      for (int a = 0; a < 6; ++a) lm.x[a] = sh.w[a];
-      lm.x_norm = xnorm();
+      if (l0) { lm.code = kCodeParameterTolerance; sh.stop = 1; }
+      return true;
+    }
+    const double cost_change = old_cost - tot_cost;
+    if (__builtin_fabs(cost_change) <= function_tolerance * old_cost)
+    {
+      if (l0) { lm.code = kCodeFunctionTolerance; sh.stop = 1; }
+      return true;
+    }
+    const double relative_decrease = cost_change / model_cost_change;
+    use_tot = relative_decrease > min_relative_decrease;
+    if (use_tot)
+    {
       // cost AND Jacobian were evaluated at the candidate (Ceres evaluates the Jacobian again on acceptance, at the
       // same point: same arithmetic, one evaluation less): its sums become the current ones
-      lm.cur_buf ^= 1;
-      ++lm.successful;
+      x_norm = lm_x_norm<N>(x_w);
+      ++successful;
       const double t = 2.0 * relative_decrease - 1.0;
       const double q = 1.0 - t * t * t;
       const double d = (1.0 / 3.0) < q ? q : (1.0 / 3.0);  // std::max(1.0 / 3.0, q)
-      const double r = lm.radius / d;
-      lm.radius = r < max_radius ? r : max_radius;          // std::min(max_radius, r)
-      lm.decrease_factor = 2.0;
-      lm.reuse_diagonal = 0;
+      const double r = radius / d;
+      radius = r < max_radius ? r : max_radius;            // std::min(max_radius, r)
+      decrease_factor = 2.0;
+      reuse_diagonal = 0;
     }
     else
     {
-      ++lm.unsuccessful;
-      lm.radius /= lm.decrease_factor; lm.decrease_factor *= 2.0; lm.reuse_diagonal = 1;
+      ++unsuccessful;
+      radius /= decrease_factor; decrease_factor *= 2.0; reuse_diagonal = 1;
     }
   }
-  if (sh.st0) { const unsigned long long n = wall_clock64(); sh.sub[0] += n - sh.st0; sh.st0 = n; }
-  return false;
-}
-// sh.Hs / sh.gs = the normal equations at the current point, scaled: lane l < N * N the entry l, the next N lanes the gradient
-template <int N>
-__device__ __forceinline__ void lm_scale_system(Shared& sh)
-{
-  const int l = threadIdx.x & 63;
-  const LmState& lm = sh.lm;
-  const double* cur = sh.sums[lm.cur_buf];
-  if (l < N * N)
-  {
-    const int a = l / N, b = l - a * N;
-    const int fa = lm_act<N>(a), fb = lm_act<N>(b);
-    const int lo = fa <= fb ? fa : fb, hi = fa <= fb ? fb : fa;
-    sh.Hs[l] = cur[7 + lo * 6 - (lo * (lo - 1)) / 2 + (hi - lo)] * lm.scale[a] * lm.scale[b];  // hsym(fa, fb)
-  }
-  else if (l < N * N + N)
-  {
-    const int a = l - N * N;
-    sh.gs[a] = cur[1 + lm_act<N>(a)] * lm.scale[a];
-  }
-}
-template <int N>
-__device__ bool lm_take_step(const LmParams& p, Shared& sh)
-{
-  const double gradient_tolerance = 1e-10, min_trust_region_radius = 1e-32;
-  const double min_diagonal = 1e-6, max_diagonal = 1e32;
-  const int max_consecutive_invalid = 5;
-  LmState& lm = sh.lm;
-  const double* cur = sh.sums[lm.cur_buf];
-  double Hs[N * N], gs[N];
+  if (use_tot) cur_buf ^= 1;
+  stamp(0);
+
+  // ---- the normal equations at the current point, scaled: lane a its row, every lane the gradient
+  double x[6], g[N], Hrow[N], gs[N];
 #pragma unroll
-  for (int i = 0; i < N * N; ++i) Hs[i] = sh.Hs[i];
+  for (int a = 0; a < 6; ++a) x[a] = use_tot ? x_w[a] : x_old[a];
 #pragma unroll
-  for (int a = 0; a < N; ++a) gs[a] = sh.gs[a];
+  for (int a = 0; a < N; ++a)
+  {
+    g[a] = use_tot ? tot_g[a] : old_g[a];
+    const double h = tot_row[a] * scale_row * scale[a];
+    const double gsa = tot_g[a] * scale[a];
+    Hrow[a] = use_tot ? h : kept_row[a];
+    gs[a] = use_tot ? gsa : kept_gs[a];
+  }
+  if (use_tot)
+  {
+    // kept for the rejected steps that may follow
+    if (lane < N)
+    {
+#pragma unroll
+      for (int a = 0; a < N; ++a) sh.Hs[lane * N + a] = Hrow[a];
+    }
+    if (l0)
+    {
+#pragma unroll
+      for (int a = 0; a < N; ++a) sh.gs[a] = gs[a];
+    }
+  }
+  const double grad_max = lm_grad_max<N>(g);
+  double Hdiag = Hrow[0];  // Hs(row, row)
+#pragma unroll
+  for (int b = 1; b < N; ++b)
+    if (row == b) Hdiag = Hrow[b];
+
+  // ---- the damped solve and the next candidate; again with a smaller radius while the step is invalid
+  int code = kCodeNone;
   while (true)
   {
-    if (lm.iter >= p.max_iter) { lm.code = kCodeMaxIterations; return true; }
-    if (lm_grad_max<N>(cur) <= gradient_tolerance) { lm.code = kCodeGradient; return true; }
-    if (lm.radius < min_trust_region_radius) { lm.code = kCodeMinRadius; return true; }
-    ++lm.iter;
-    lm.iterations = lm.iter;
-    if (!lm.reuse_diagonal)
+    if (iter >= p.max_iter) { code = kCodeMaxIterations; break; }
+    if (grad_max <= gradient_tolerance) { code = kCodeGradient; break; }
+    if (radius < min_trust_region_radius) { code = kCodeMinRadius; break; }
+    ++iter;
+    if (!reuse_diagonal)
+    {
+      const double lo = Hdiag < min_diagonal ? min_diagonal : Hdiag;  // std::max(h, min_diagonal)
+      diag_row = max_diagonal < lo ? max_diagonal : lo;               // std::min(lo, max_diagonal)
+    }
+    // M = Hs + diag / radius: lane i < N holds the row i (its entries j <= i are the ones the factor reads), lane N the
+    // right-hand side gs
+    double s[N];
+    const double damped = Hdiag + diag_row / radius;
+#pragma unroll
+    for (int j = 0; j < N; ++j) s[j] = row == j ? damped : Hrow[j];
+    if (lane == N)
     {
 #pragma unroll
-      for (int a = 0; a < N; ++a)
-      {
-        const double h = Hs[a * N + a];
-        const double lo = h < min_diagonal ? min_diagonal : h;  // std::max(h, min_diagonal)
-        lm.diag[a] = max_diagonal < lo ? max_diagonal : lo;     // std::min(lo, max_diagonal)
-      }
+      for (int j = 0; j < N; ++j) s[j] = gs[j];
     }
-    double M[N * N], y[N], step[N];
+    stamp(1);
+    // Cholesky and the forward substitution, column by column.  s[jj] of lane i has lost the products of the columns
+    // before j, in their order, when column j comes: s[j] of lane j is the pivot's square.  Lu[i][j] = L_ij for
+    // j < i < N, Lu[N][j] = y_j, the same value in every lane.
+    bool ok = true;
+    double rinv[N], Lu[N + 1][N];
 #pragma unroll
-    for (int i = 0; i < N * N; ++i) M[i] = Hs[i];
-#pragma unroll
-    for (int a = 0; a < N; ++a) M[a * N + a] += lm.diag[a] / lm.radius;
-#pragma unroll
-    for (int a = 0; a < N; ++a) y[a] = 0.;
-    if (sh.st0) { const unsigned long long n = wall_clock64(); sh.sub[1] += n - sh.st0; sh.st0 = n; }
-    bool ok = solve_spd<N>(M, gs, y);
-    if (sh.st0) { const unsigned long long n = wall_clock64(); sh.sub[2] += n - sh.st0; sh.st0 = n; }
-    lm.reuse_diagonal = 1;
-    double model_cost_change = 0;
-    if (ok)
+    for (int j = 0; j < N; ++j)
     {
+      const double d = lane_bcast(s[j], j);
+      if (!(d > 0.0) || !isfinite(d)) ok = false;
+      rinv[j] = 1.0 / __builtin_sqrt(d);
+      const double lij = s[j] * rinv[j];
 #pragma unroll
-      for (int a = 0; a < N; ++a) step[a] = -y[a];
-      double sg = 0, sHs = 0;
+      for (int jj = j + 1; jj <= N; ++jj) Lu[jj][j] = lane_bcast(lij, jj);
 #pragma unroll
-      for (int a = 0; a < N; ++a)
-      {
-        sg += step[a] * gs[a];
-        double t = 0;
-#pragma unroll
-        for (int b = 0; b < N; ++b) t += Hs[a * N + b] * step[b];
-        sHs += step[a] * t;
-      }
-      model_cost_change = -sg - 0.5 * sHs;
-      if (model_cost_change < 0.0) ok = false;
+      for (int jj = j + 1; jj < N; ++jj) s[jj] -= lij * Lu[jj][j];
     }
-    if (!ok)
+    double y[N];
+#pragma unroll
+    for (int i = N - 1; i >= 0; --i)
     {
-      ++lm.unsuccessful;
-      if (++lm.consecutive_invalid >= max_consecutive_invalid) { lm.code = kCodeInvalidSteps; return true; }
-      lm.radius /= lm.decrease_factor; lm.decrease_factor *= 2.0; lm.reuse_diagonal = 1;
-      continue;
-    }
-    lm.consecutive_invalid = 0;
-    lm.model_cost_change = model_cost_change;
-
-    double cand[6], delta_norm = 0;
+      double t = Lu[N][i];
 #pragma unroll
-    for (int a = 0; a < 6; ++a) cand[a] = lm.x[a];
+      for (int k = i + 1; k < N; ++k) t -= Lu[k][i] * y[k];
+      y[i] = t * rinv[i];
+    }
+#pragma unroll
+    for (int i = 0; i < N; ++i)
+      if (!isfinite(y[i])) ok = false;
+    stamp(2);
+    reuse_diagonal = 1;
+    // the model's cost change (meaningless, and not used, when the solve failed)
+    double step[N], t_row = 0, sg = 0, sHs = 0;
+#pragma unroll
+    for (int a = 0; a < N; ++a) step[a] = -y[a];
+#pragma unroll
+    for (int b = 0; b < N; ++b) t_row += Hrow[b] * step[b];
 #pragma unroll
     for (int a = 0; a < N; ++a)
     {
-      cand[lm_act<N>(a)] = lm.x[lm_act<N>(a)] + step[a] * lm.scale[a];
-      const double e = lm.x[lm_act<N>(a)] - cand[lm_act<N>(a)];
-      delta_norm += e * e;
+      sg += step[a] * gs[a];
+      sHs += step[a] * lane_bcast(t_row, a);
     }
-    lm.delta_norm = __builtin_sqrt(delta_norm);
-    set_point(sh, cand);
-    ++lm.evaluations;
-    if (sh.st0) { const unsigned long long n = wall_clock64(); sh.sub[3] += n - sh.st0; sh.st0 = n; }
-    return false;
+    const double change = -sg - 0.5 * sHs;
+    if (!ok || change < 0.0)
+    {
+      ++unsuccessful;
+      if (++consecutive_invalid >= max_consecutive_invalid) { code = kCodeInvalidSteps; break; }
+      radius /= decrease_factor; decrease_factor *= 2.0;
+      continue;
+    }
+    consecutive_invalid = 0;
+    model_cost_change = change;
+    double dn = 0;
+#pragma unroll
+    for (int a = 0; a < 6; ++a) cand[a] = x[a];
+#pragma unroll
+    for (int a = 0; a < N; ++a)
+    {
+      cand[lm_act<N>(a)] = x[lm_act<N>(a)] + step[a] * scale[a];
+      const double e = x[lm_act<N>(a)] - cand[lm_act<N>(a)];
+      dn += e * e;
+    }
+    delta_norm = __builtin_sqrt(dn);
+    ++evaluations;
+    break;
   }
-}
-// the three parts, by the first wavefront (all its lanes call); sh.stop = the solve is over
-template <int N>
-__device__ __forceinline__ void lm_step(const LmParams& p, Shared& sh, bool first)
-{
-  if (threadIdx.x == 0) sh.stop = lm_decide<N>(p, sh, first) ? 1 : 0;
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // one wavefront: its LDS operations are served in order
-  if (sh.stop) return;
-  lm_scale_system<N>(sh);
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  if (threadIdx.x == 0) sh.stop = lm_take_step<N>(p, sh) ? 1 : 0;
+
+  // ---- the state for the next evaluation, or for the result
+  if (lane < N) lm.diag[lane] = diag_row;
+  if (l0)
+  {
+    if (use_tot && !first)
+    {
+#pragma unroll
+      for (int a = 0; a < 6; ++a) lm.x[a] = x[a];
+    }
+    lm.cur_buf = cur_buf;
+    lm.x_norm = x_norm; lm.radius = radius; lm.decrease_factor = decrease_factor;
+    lm.model_cost_change = model_cost_change; lm.delta_norm = delta_norm;
+    lm.reuse_diagonal = reuse_diagonal; lm.consecutive_invalid = consecutive_invalid;
+    lm.iter = iter; lm.iterations = iter;
+    lm.successful = successful; lm.unsuccessful = unsuccessful; lm.evaluations = evaluations;
+    lm.code = code;
+    sh.stop = code != kCodeNone ? 1 : 0;
+  }
+  stamp(3);
+  return code != kCodeNone;
 }
 
 // What the host's loop does between two ICP iterations (host/lsa_slam_icp.cpp, Slam.cxx:940-950 / 1134-1151), for the
@@ -577,18 +688,9 @@ __global__ __launch_bounds__(kLmThreads) void k_lm_solve(LmParams p, u64* __rest
       return;
     }
   }
-  if (threadIdx.x == 0)
+  if (threadIdx.x < 64)
   {
-    for (int i = 0; i < 6; ++i) sh.lap[i] = 0;
-    for (int i = 0; i < 4; ++i) sh.sub[i] = 0;
-    sh.st0 = 0;
-    sh.tk = wall_clock64();
-    sh.lap[5] = sh.tk;
-    LmState& lm = sh.lm;
-#pragma unroll
-    for (int v = 0; v < kAccumVals; ++v) sh.sums[0][v] = 0.;
-    lm.cur_buf = 0;
-    // the start point: the launch's own argument, or what the link brought over (read into LDS, the arguments stay untouched)
+    // the start point: the launch's own argument, or what the link brought over (the arguments stay untouched)
     double x0[6];
 #pragma unroll
     for (int a = 0; a < 6; ++a) x0[a] = p.x0[a];
@@ -597,15 +699,26 @@ __global__ __launch_bounds__(kLmThreads) void k_lm_solve(LmParams p, u64* __rest
 #pragma unroll
       for (int a = 0; a < 6; ++a) x0[a] = p.link->in.x0[a];
     }
+    if (threadIdx.x == 0)
+    {
+      for (int i = 0; i < 6; ++i) sh.lap[i] = 0;
+      for (int i = 0; i < 4; ++i) sh.sub[i] = 0;
+      sh.st0 = 0;
+      sh.tk = wall_clock64();
+      sh.lap[5] = sh.tk;
+      LmState& lm = sh.lm;
 #pragma unroll
-    for (int a = 0; a < 6; ++a) { lm.x[a] = x0[a]; lm.scale[a] = 1.; lm.diag[a] = 0.; }
-    lm.radius = 1e4; lm.decrease_factor = 2.0; lm.x_norm = 0.; lm.model_cost_change = 0.; lm.delta_norm = 0.; lm.initial_cost = 0.;
-    lm.reuse_diagonal = 0; lm.consecutive_invalid = 0; lm.iter = 0;
-    lm.evaluations = 1; lm.successful = 0; lm.unsuccessful = 0; lm.iterations = 0; lm.code = kCodeNone; lm.skipped = 0; lm.matches = 0;
-    set_point(sh, x0);
-    sh.stop = 0;
+      for (int v = 0; v < kAccumVals; ++v) sh.sums[0][v] = 0.;
+      lm.cur_buf = 0;
+#pragma unroll
+      for (int a = 0; a < 6; ++a) { lm.x[a] = x0[a]; lm.scale[a] = 1.; lm.diag[a] = 0.; }
+      lm.radius = 1e4; lm.decrease_factor = 2.0; lm.x_norm = 0.; lm.model_cost_change = 0.; lm.delta_norm = 0.; lm.initial_cost = 0.;
+      lm.reuse_diagonal = 0; lm.consecutive_invalid = 0; lm.iter = 0;
+      lm.evaluations = 1; lm.successful = 0; lm.unsuccessful = 0; lm.iterations = 0; lm.code = kCodeNone; lm.skipped = 0; lm.matches = 0;
+      sh.stop = 0;
+    }
+    finish_point(sh, x0[0], x0[1], x0[2], x0[3], x0[4], x0[5]);
   }
-  if (threadIdx.x < 64) finish_point(sh);
   if (kRecordPrefetch && p.cslots > 0) record_stash(pre, lm_cache, p.cslots * kLmThreads, threadIdx.x);
   __syncthreads();
   bool failed = false;
@@ -616,12 +729,11 @@ __global__ __launch_bounds__(kLmThreads) void k_lm_solve(LmParams p, u64* __rest
     if (threadIdx.x < 64)
     {
       if (threadIdx.x == 0 && tr) sh.st0 = wall_clock64();
-      if (p.two_d) lm_step<3>(p, sh, epoch == 1);
-      else lm_step<6>(p, sh, epoch == 1);
+      double cand[6];
+      const bool stop = p.two_d ? lm_step<3>(p, sh, epoch == 1, cand) : lm_step<6>(p, sh, epoch == 1, cand);
       // the candidate's rotation and derivatives -- unless the solve is over: nobody evaluates at sh.w then, and neither
       // the result nor the link reads sh.w or sh.rot (they take the pose from LmState::x)
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // sh.stop was written by lane 0 of this wavefront
-      if (!sh.stop) finish_point(sh);
+      if (!stop) finish_point(sh, cand[0], cand[1], cand[2], cand[3], cand[4], cand[5]);
     }
     __syncthreads();
     if (tr) lm_lap(sh, 3);

@@ -5,6 +5,7 @@
 #pragma once
 #include <algorithm>
 #include <hip/hip_runtime.h>
+#include "lsa_wave.h"
 
 namespace lsa
 {
@@ -25,10 +26,8 @@ __global__ __launch_bounds__(256) void k_compact_count(Pred pred, const int* __r
     const int i = blockIdx.x * 1024 + q * 256 + threadIdx.x;
     if (i < n && pred(i)) ++mine;
   }
-  for (int o = 32; o > 0; o >>= 1) mine += __shfl_down(mine, o);
-  if ((threadIdx.x & 63) == 0) cnt[threadIdx.x >> 6] = mine;
-  __syncthreads();
-  if (threadIdx.x == 0) chunk_count[blockIdx.x] = cnt[0] + cnt[1] + cnt[2] + cnt[3];
+  mine = block_reduce<4>(mine, OpSum(), cnt);
+  if (threadIdx.x == 0) chunk_count[blockIdx.x] = mine;
 }
 // total_out: where the number kept goes (never the word n_ptr points at: the other blocks still read that one);
 // base_ptr: the output starts behind *base_ptr elements (appending), at 0 when null
@@ -44,10 +43,7 @@ __global__ __launch_bounds__(256) void k_compact_scatter(Pred pred, Emit emit, c
   if (blockIdx.x * 1024 >= n && !last) return;
   int mine = 0;
   for (int c = threadIdx.x; c < (int)blockIdx.x; c += 256) mine += chunk_count[c];
-  for (int o = 32; o > 0; o >>= 1) mine += __shfl_down(mine, o);
-  if ((threadIdx.x & 63) == 0) before[threadIdx.x >> 6] = mine;
-  __syncthreads();
-  int run = (base_ptr ? *base_ptr : 0) + before[0] + before[1] + before[2] + before[3];
+  int run = (base_ptr ? *base_ptr : 0) + block_reduce_all<4>(mine, OpSum(), before);
   for (int q = 0; q < 4; ++q)
   {
     const int i = blockIdx.x * 1024 + q * 256 + threadIdx.x;

@@ -60,7 +60,7 @@ __global__ void k_roll_decide(GridParams p, int* __restrict__ st, int use_box)
     int off = 0;
     if (use_box)
     {
-      const float mnv = o2f_i(st[kStTmp + d]), mxv = o2f_i(st[kStTmp + 3 + d]);
+      const float mnv = os2f(st[kStTmp + d]), mxv = os2f(st[kStTmp + 3 + d]);
       const float pos = __int_as_float(st[kStPosX + d]);
       const float down = mnv - (pos - h);
       const float up = mxv - (pos + h);
@@ -73,7 +73,7 @@ __global__ void k_roll_decide(GridParams p, int* __restrict__ st, int use_box)
     st[kStPosX + d] = __float_as_int(__int_as_float(st[kStPosX + d]) + (float)off * p.resolution);
   }
   // re-arm the box for the next batch
-  for (int d = 0; d < 3; ++d) { st[kStTmp + d] = 0x7fffffff; st[kStTmp + 3 + d] = (int)0x80000000; }
+  for (int d = 0; d < 3; ++d) { st[kStTmp + d] = kBoxLoArmedS; st[kStTmp + 3 + d] = kBoxHiArmedS; }
 }
 struct RollPred
 {
@@ -406,8 +406,8 @@ int lsa_device_grid_reset(lsa_device_grid* g, const float position[3])
   {
     const float v = std::floor((position ? position[d] : 0.f) / r) * r;
     std::memcpy(&h[kStPosX + d], &v, sizeof(float));
-    h[kStTmp + d] = 0x7fffffff;
-    h[kStTmp + 3 + d] = (int)0x80000000;
+    h[kStTmp + d] = kBoxLoArmedS;
+    h[kStTmp + 3 + d] = kBoxHiArmedS;
   }
   G_HIP(hipStreamSynchronize(g->stream));
   G_HIP(hipMemcpy(g->st, h, sizeof(h), hipMemcpyHostToDevice));
@@ -549,7 +549,7 @@ int lsa_device_grid_roll(lsa_device_grid* g, const float mn[3], const float mx[3
   int rc = begin_modification(g, std::max(g->n_upper, 1), 0);
   if (rc) return rc;
   int box[6];
-  for (int d = 0; d < 3; ++d) { box[d] = f2o_i(mn[d]); box[3 + d] = f2o_i(mx[d]); }
+  for (int d = 0; d < 3; ++d) { box[d] = f2os(mn[d]); box[3 + d] = f2os(mx[d]); }
   G_HIP(hipMemcpyAsync(g->st + kStTmp, box, sizeof(box), hipMemcpyHostToDevice, g->stream));
   G_HIP(hipStreamSynchronize(g->stream));
   rc = roll(g, true);

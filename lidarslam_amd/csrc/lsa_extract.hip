@@ -13,6 +13,7 @@
 #include <cmath>
 #include "lsa_ctx.h"
 #include "lsa_device_math.h"
+#include "lsa_wave.h"
 
 using namespace lsa;
 
@@ -52,12 +53,8 @@ __global__ void k_extract_init(int* __restrict__ out)
   if (i == 12 || i == 13) v = -1;          // time range lo = ~0ull
   out[i] = v;
 }
-// monotone encoding of doubles for 64-bit atomicMin/Max (as in lsa_transform.hip)
-__device__ __forceinline__ unsigned long long time_bits(const float4& b)
-{
-  const unsigned long long u = (unsigned long long)__double_as_longlong(__hiloint2double(__float_as_int(b.y), __float_as_int(b.x)));
-  return (u & 0x8000000000000000ull) ? ~u : (u | 0x8000000000000000ull);
-}
+// the point's time in the coding of the 64-bit atomicMin/Max
+__device__ __forceinline__ unsigned long long time_bits(const float4& b) { return d2ou(__hiloint2double(__float_as_int(b.y), __float_as_int(b.x))); }
 
 __global__ __launch_bounds__(256) void k_ring_hist(const float4* __restrict__ frame, int n, uint32_t* __restrict__ block_hist,
                                                    int* __restrict__ ring_meta)
@@ -82,7 +79,7 @@ __global__ __launch_bounds__(256) void k_ring_hist(const float4* __restrict__ fr
         atomicOr(&ring_meta[2], 1);
     }
   }
-  for (int o = 32; o > 0; o >>= 1) mx = max(mx, __shfl_down(mx, o));
+  mx = wave_max(mx);
   if ((threadIdx.x & 63) == 0 && mx >= 0) atomicMax(&ring_meta[1], mx);
   __syncthreads();
   for (int r = threadIdx.x; r < kMaxRings; r += blockDim.x) block_hist[(size_t)blockIdx.x * kMaxRings + r] = h[r];
@@ -97,13 +94,7 @@ __global__ __launch_bounds__(64) void k_ring_scan(uint32_t* __restrict__ block_h
   const int b0 = min(nblocks, lane * per), b1 = min(nblocks, b0 + per);
   uint32_t mine = 0;
   for (int b = b0; b < b1; ++b) mine += block_hist[(size_t)b * kMaxRings + r];
-  uint32_t inc = mine;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1)
-  {
-    const uint32_t t = __shfl_up(inc, o);
-    if (lane >= o) inc += t;
-  }
+  const uint32_t inc = wave_inclusive_scan(mine);
   uint32_t run = inc - mine;
   for (int b = b0; b < b1; ++b)
   {
@@ -154,17 +145,9 @@ __global__ __launch_bounds__(256) void k_ring_scatter(const float4* __restrict__
   {
     const int t = threadIdx.x;
     const int a0 = scan[2 * t], a1 = scan[2 * t + 1];
-    __shared__ int pair[256];
-    pair[t] = a0 + a1;
-    __syncthreads();
-    for (int o = 1; o < 256; o <<= 1)
-    {
-      const int v = (t >= o) ? pair[t - o] : 0;
-      __syncthreads();
-      pair[t] += v;
-      __syncthreads();
-    }
-    const int before = pair[t] - (a0 + a1);
+    __shared__ int wsum[4];
+    int all;
+    const int before = block_exclusive_scan<4>(a0 + a1, wsum, &all);
     const uint32_t s0 = (uint32_t)before, s1 = (uint32_t)(before + a0);
     slot[2 * t] = s0 + block_hist[(size_t)blockIdx.x * kMaxRings + 2 * t];
     slot[2 * t + 1] = s1 + block_hist[(size_t)blockIdx.x * kMaxRings + 2 * t + 1];
@@ -172,7 +155,7 @@ __global__ __launch_bounds__(256) void k_ring_scatter(const float4* __restrict__
     {
       ring_start[2 * t] = (int)s0;
       ring_start[2 * t + 1] = (int)s1;
-      if (t == 255) ring_start[kMaxRings] = pair[t];
+      if (t == 255) ring_start[kMaxRings] = all;
     }
   }
   __syncthreads();
@@ -476,8 +459,9 @@ __device__ __noinline__ void nms_fixed_point(volatile uint32_t* w, int np, int h
   while (true)
 #endif
   {
-    // a wavefront whose points are all decided has nothing to do but meet the others (decisions are final: it stays so);
-    // the chains of undecided candidates are local, after two or three rounds most of the block's wavefronts are done
+    // a wavefront whose points are all decided has nothing to do but meet the others at the round's one barrier (decisions
+    // are final: it stays so); the chains of undecided candidates are local, after two or three rounds most of the block's
+    // wavefronts are done
     bool mine = false;
 #pragma unroll
     for (int a = 0; a < PER; ++a)
@@ -486,45 +470,43 @@ __device__ __noinline__ void nms_fixed_point(volatile uint32_t* w, int np, int h
         const uint32_t v = w[j0 + a];
         mine = mine || (v != 0u && v != kSel);
       }
-    if (!__any(mine))
-    {
-      if (!__syncthreads_or(0)) break;
-      continue;
-    }
-    uint32_t x[WIN];
-#pragma unroll
-    for (int i = 0; i < WIN; ++i)
-    {
-      const int k = j0 - kNmsHalfMax + i;
-      x[i] = 0u;
-      if (i >= kNmsHalfMax - hw && i < kNmsHalfMax + PER + hw && k >= 0 && k < np) x[i] = w[k];
-    }
     int undecided = 0;
-    auto visit = [&](int a) -> int {
-      const int i = kNmsHalfMax + a;
-      const uint32_t wj = x[i];
-      if (wj == 0u || wj == kSel) return 0;
-      // the largest word on either side says it all: kSel (the largest there is) = a selected neighbour; otherwise a word
-      // above this one = an undecided neighbour of higher priority -- an equal score on the left (smaller index) wins among
-      // edges, on the right among planes
-      uint32_t ml = 0u, mr = 0u;
+    if (__any(mine))
+    {
+      uint32_t x[WIN];
 #pragma unroll
-      for (int d = 1; d <= kNmsHalfMax; ++d)
-        if (d <= hw)
-        {
-          ml = x[i - d] > ml ? x[i - d] : ml;
-          mr = x[i + d] > mr ? x[i + d] : mr;
-        }
-      const bool selNear = ml == kSel || mr == kSel;
-      const bool higher = PLANE ? (ml > wj || mr >= wj) : (ml >= wj || mr > wj);
-      if (selNear) { x[i] = 0u; w[j0 + a] = 0u; return 0; }
-      if (!higher) { x[i] = kSel; w[j0 + a] = kSel; return 0; }
-      return 1;
-    };
+      for (int i = 0; i < WIN; ++i)
+      {
+        const int k = j0 - kNmsHalfMax + i;
+        x[i] = 0u;
+        if (i >= kNmsHalfMax - hw && i < kNmsHalfMax + PER + hw && k >= 0 && k < np) x[i] = w[k];
+      }
+      auto visit = [&](int a) -> int {
+        const int i = kNmsHalfMax + a;
+        const uint32_t wj = x[i];
+        if (wj == 0u || wj == kSel) return 0;
+        // the largest word on either side says it all: kSel (the largest there is) = a selected neighbour; otherwise a word
+        // above this one = an undecided neighbour of higher priority -- an equal score on the left (smaller index) wins among
+        // edges, on the right among planes
+        uint32_t ml = 0u, mr = 0u;
 #pragma unroll
-    for (int a = 0; a < PER; ++a) visit(a);
+        for (int d = 1; d <= kNmsHalfMax; ++d)
+          if (d <= hw)
+          {
+            ml = x[i - d] > ml ? x[i - d] : ml;
+            mr = x[i + d] > mr ? x[i + d] : mr;
+          }
+        const bool selNear = ml == kSel || mr == kSel;
+        const bool higher = PLANE ? (ml > wj || mr >= wj) : (ml >= wj || mr > wj);
+        if (selNear) { x[i] = 0u; w[j0 + a] = 0u; return 0; }
+        if (!higher) { x[i] = kSel; w[j0 + a] = kSel; return 0; }
+        return 1;
+      };
 #pragma unroll
-    for (int a = PER - 1; a >= 0; --a) undecided |= visit(a);
+      for (int a = 0; a < PER; ++a) visit(a);
+#pragma unroll
+      for (int a = PER - 1; a >= 0; --a) undecided |= visit(a);
+    }
     if (!__syncthreads_or(undecided)) break;
   }
 }
@@ -626,10 +608,7 @@ __global__ __launch_bounds__(kLabelThreads) void k_label(const float* __restrict
     valid[s0 + j] = (f & 7) | lab;
     ce += lab & 1; cp += (lab >> 1) & 1; cb += (lab >> 2) & 1;
   }
-  for (int o = 32; o > 0; o >>= 1)
-  {
-    ce += __shfl_down(ce, o); cp += __shfl_down(cp, o); cb += __shfl_down(cb, o);
-  }
+  ce = wave_sum(ce); cp = wave_sum(cp); cb = wave_sum(cb);
   if ((threadIdx.x & 63) == 0)
   {
     atomicAdd(&cnt[0], ce); atomicAdd(&cnt[1], cp); atomicAdd(&cnt[2], cb);
@@ -663,7 +642,7 @@ __global__ __launch_bounds__(kCompactThreads) void k_compact(const float4* __res
     // keypoints of type `wave` in the rings in front of this one: the lanes share the rings, one reduction
     int s = 0;
     for (int q = lane; q < r; q += 64) s += ring_counts[q * 3 + wave];
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_down(s, o);
+    s = wave_sum(s);
     if (lane == 0)
     {
       base[wave] = s;
@@ -682,18 +661,7 @@ __global__ __launch_bounds__(kCompactThreads) void k_compact(const float4* __res
     mine += (unsigned long long)(l & 1) | ((unsigned long long)((l >> 1) & 1) << 21) | ((unsigned long long)((l >> 2) & 1) << 42);
   }
   // exclusive scan of the (packed) counts over the block: inside the wavefront by shuffles, across by the wavefronts' totals
-  unsigned long long inc = mine;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1)
-  {
-    const unsigned long long t = __shfl_up(inc, o);
-    if (lane >= o) inc += t;
-  }
-  if (lane == 63) wtot[wave] = inc;
-  __syncthreads();
-  unsigned long long before = 0;
-  for (int w = 0; w < wave; ++w) before += wtot[w];
-  unsigned long long excl = before + inc - mine;
+  const unsigned long long excl = block_exclusive_scan<kWaves>(mine, wtot);
   int pe = base[0] + (int)(excl & 0x1fffff);
   int pp = base[1] + (int)((excl >> 21) & 0x1fffff);
   int pb = base[2] + (int)((excl >> 42) & 0x1fffff);
@@ -712,19 +680,9 @@ __global__ __launch_bounds__(kCompactThreads) void k_compact(const float4* __res
     lo = tb < lo ? tb : lo;
     hi = tb > hi ? tb : hi;
   }
-  for (int s = 32; s > 0; s >>= 1)
-  {
-    const unsigned long long l2 = __shfl_down(lo, s), h2 = __shfl_down(hi, s);
-    lo = l2 < lo ? l2 : lo;
-    hi = h2 > hi ? h2 : hi;
-  }
-  if ((threadIdx.x & 63) == 0) { tlo[threadIdx.x >> 6] = lo; thi[threadIdx.x >> 6] = hi; }
-  __syncthreads();
-  if (threadIdx.x == 0)
-  {
-    for (int w = 1; w < kWaves; ++w) { lo = tlo[w] < lo ? tlo[w] : lo; hi = thi[w] > hi ? thi[w] : hi; }
-    if (hi >= lo) { atomicMin(&time_range[0], lo); atomicMax(&time_range[1], hi); }
-  }
+  lo = block_reduce<kWaves>(lo, OpMin(), tlo);
+  hi = block_reduce<kWaves>(hi, OpMax(), thi);
+  if (threadIdx.x == 0 && hi >= lo) { atomicMin(&time_range[0], lo); atomicMax(&time_range[1], hi); }
 }
 
 __global__ void k_debug_gather(const uint32_t* __restrict__ orig, int n, int id, const float* __restrict__ src,

@@ -6,6 +6,7 @@
 #include <string>
 #include "lsa_ctx.h"
 #include "lsa_compact.h"
+#include "lsa_wave.h"
 #include "host/lsa_map_order.h"
 
 namespace lsa
@@ -23,7 +24,6 @@ struct GridParams
 // state the kernels read and write (device memory, kStInts ints)
 enum { kStN = 0, kStNbPoints = 1, kStUpdated = 2, kStPosX = 3, kStGroups = 6, kStNew = 7, kStOff = 8, kStSub = 11, kStTmp = 12 /* 6 ints */, kStSubFirst = 18, kStCompact = 19, kStPred = 20 /* 6 ints: lo[3], hi[3]: outer voxels of the box a sub-map was extracted ahead for */,
        kStRec = 26 /* keys ClearOldPoints erased ("Ordered" = 0) */, kStInts = 32 };
-__device__ __forceinline__ float ordered_to_float(unsigned u) { return __uint_as_float((u & 0x80000000u) ? (u & 0x7fffffffu) : ~u); }
 __device__ __forceinline__ int round_to_int(float v)
 {
   // Eigen's .round().cast<int>(): round half away from zero, then a C cast (out of range: INT_MIN, as on x86-64)
@@ -38,9 +38,7 @@ struct MapView
   unsigned* count;
 };
 
-// floats as ordered ints: atomicMin / atomicMax on a box (st[kStTmp .. +5]), and lsa_device_grid_roll's box from the host
-__host__ __device__ __forceinline__ int f2o_i(float f) { const int i = __builtin_bit_cast(int, f); return i >= 0 ? i : i ^ 0x7fffffff; }
-__device__ __forceinline__ float o2f_i(int i) { return __int_as_float(i >= 0 ? i : i ^ 0x7fffffff); }
+// (the box in st[kStTmp .. +5] and lsa_device_grid_roll's box from the host: floats in the signed coding, f2os / os2f of lsa_wave.h)
 __device__ __forceinline__ int lower_bound_u64(const u64* __restrict__ a, int n, u64 key)
 {
   int lo = 0, hi = n;

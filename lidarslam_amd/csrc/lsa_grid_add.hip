@@ -16,30 +16,15 @@ constexpr u64 kNoKey = ~0ull;  // points outside the grid: sorted behind every v
 // bounding box of the batch: ordered-int atomics into st[kStTmp .. +5]
 __device__ __forceinline__ void d_batch_bbox(int bx, const float4* __restrict__ batch, int n, int* __restrict__ st)
 {
-  __shared__ float smn[4][3], smx[4][3];
+  __shared__ float s_box[4][6];
   const int i = bx * blockDim.x + threadIdx.x;
-  float mn[3] = {FLT_MAX, FLT_MAX, FLT_MAX}, mx[3] = {-FLT_MAX, -FLT_MAX, -FLT_MAX};
+  BoxF box;
   if (i < n)
   {
     const float4 a = batch[2 * (size_t)i];
-    mn[0] = mx[0] = a.x; mn[1] = mx[1] = a.y; mn[2] = mx[2] = a.z;
+    box = box_of_point(a.x, a.y, a.z);
   }
-  for (int d = 0; d < 3; ++d)
-    for (int o = 32; o > 0; o >>= 1)
-    {
-      mn[d] = fminf(mn[d], __shfl_down(mn[d], o));
-      mx[d] = fmaxf(mx[d], __shfl_down(mx[d], o));
-    }
-  if ((threadIdx.x & 63) == 0)
-    for (int d = 0; d < 3; ++d) { smn[threadIdx.x >> 6][d] = mn[d]; smx[threadIdx.x >> 6][d] = mx[d]; }
-  __syncthreads();
-  // six atomics per workgroup (every wavefront aiming at the same six words was 15 us for 27 k points)
-  if (threadIdx.x < 3)
-  {
-    const int d = threadIdx.x;
-    atomicMin(&st[kStTmp + d], f2o_i(fminf(fminf(smn[0][d], smn[1][d]), fminf(smn[2][d], smn[3][d]))));
-    atomicMax(&st[kStTmp + 3 + d], f2o_i(fmaxf(fmaxf(smx[0][d], smx[1][d]), fmaxf(smx[2][d], smx[3][d]))));
-  }
+  box_block_send<4>(box, st + kStTmp, s_box);
 }
 
 // ---- Add (RollingGrid.cxx:160-318) in seven launches --------------------------------------------------------------------
@@ -68,7 +53,7 @@ __device__ __forceinline__ Shift roll_shift(const GridParams& p, const int* __re
     int off = 0;
     if (use_box)
     {
-      const float mnv = o2f_i(st[kStTmp + d]), mxv = o2f_i(st[kStTmp + 3 + d]);
+      const float mnv = os2f(st[kStTmp + d]), mxv = os2f(st[kStTmp + 3 + d]);
       const float down = mnv - (pos - h);
       const float up = mxv - (pos + h);
       float o = (up + down) / 2.f;
@@ -590,20 +575,11 @@ __device__ __forceinline__ void d_add_merge(int bx, GridParams p, int* __restric
     {
       const int c = b0 + threadIdx.x;
       const int v = c < cnt ? src[c] : 0;
-      int inc = v;
-      for (int o = 1; o < 64; o <<= 1)
-      {
-        const int t = __shfl_up(inc, o);
-        if ((threadIdx.x & 63) >= o) inc += t;
-      }
       __shared__ int wsum[4];
-      if ((threadIdx.x & 63) == 63) wsum[threadIdx.x >> 6] = inc;
+      const int before = carry + block_exclusive_scan<4>(v, wsum);
+      if (c < cnt) out[c] = before;
       __syncthreads();
-      int add = carry;
-      for (int w = 0; w < (int)(threadIdx.x >> 6); ++w) add += wsum[w];
-      if (c < cnt) out[c] = add + inc - v;
-      __syncthreads();
-      if (threadIdx.x == 255) carry = add + inc;
+      if (threadIdx.x == 255) carry = before + v;
       __syncthreads();
     }
     if (threadIdx.x == 0) out[cnt] = carry;
@@ -659,8 +635,8 @@ __device__ __forceinline__ void d_add_commit(int bx, GridParams p, int* __restri
   {
     st[kStOff + d] = s.off[d];
     st[kStPosX + d] = __float_as_int(s.pos[d]);
-    st[kStTmp + d] = 0x7fffffff;            // the box is re-armed for the next batch
-    st[kStTmp + 3 + d] = (int)0x80000000;
+    st[kStTmp + d] = kBoxLoArmedS;            // the box is re-armed for the next batch
+    st[kStTmp + 3 + d] = kBoxHiArmedS;
   }
 }
 
@@ -763,21 +739,12 @@ __global__ __launch_bounds__(256) void k_scan_blocks(ScanLevel L)
   if ((int)blockIdx.x >= nb) return;  // (a launch shared with a longer array)
   const int c = blockIdx.x * per + threadIdx.x;
   const int v = c < cnt ? L.src[j][c] : 0;
-  int inc = v;
-  for (int o = 1; o < 64; o <<= 1)
-  {
-    const int t = __shfl_up(inc, o);
-    if ((threadIdx.x & 63) >= o) inc += t;
-  }
-  if ((threadIdx.x & 63) == 63) wsum[threadIdx.x >> 6] = inc;
-  __syncthreads();
-  int add = 0;
-  for (int w = 0; w < (int)(threadIdx.x >> 6); ++w) add += wsum[w];
-  if (c < cnt) L.out[j][c] = add + inc - v;
+  const int before = block_exclusive_scan<4>(v, wsum);  // (the block is `per` threads: one wavefront or four)
+  if (c < cnt) L.out[j][c] = before;
   if ((int)threadIdx.x == per - 1)
   {
-    L.sums[j][blockIdx.x] = add + inc;
-    if (nb == 1) L.out[j][cnt] = add + inc;
+    L.sums[j][blockIdx.x] = before + v;
+    if (nb == 1) L.out[j][cnt] = before + v;
   }
 }
 __global__ __launch_bounds__(256) void k_scan_addback(ScanLevel L)

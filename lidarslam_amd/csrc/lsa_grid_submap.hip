@@ -67,8 +67,8 @@ struct SubMapPred
 #pragma unroll
     for (int d = 0; d < 3; ++d)
     {
-      const float lo_f = ctx_box ? ordered_to_float(ctx_box[d]) : box.mn[d];
-      const float hi_f = ctx_box ? ordered_to_float(ctx_box[3 + d]) : box.mx[d];
+      const float lo_f = ctx_box ? ou2f(ctx_box[d]) : box.mn[d];
+      const float hi_f = ctx_box ? ou2f(ctx_box[3 + d]) : box.mx[d];
       const float origin = __int_as_float(st[kStPosX + d]) - (float)((double)(g / 2) * resolution_d);
       const int lo = round_to_int((lo_f - origin) / resolution), hi = round_to_int((hi_f - origin) / resolution);
       if (c[d] < (lo > 0 ? lo : 0) || c[d] > (hi < g - 1 ? hi : g - 1)) return false;
@@ -97,7 +97,7 @@ __device__ __forceinline__ void box_voxels(const unsigned* __restrict__ words, i
   for (int d = 0; d < 3; ++d)
   {
     const float origin = __int_as_float(st[kStPosX + d]) - (float)((double)(grid_size / 2) * resolution_d);
-    const int a = round_to_int((ordered_to_float(words[d]) - origin) / resolution), b = round_to_int((ordered_to_float(words[3 + d]) - origin) / resolution);
+    const int a = round_to_int((ou2f(words[d]) - origin) / resolution), b = round_to_int((ou2f(words[3 + d]) - origin) / resolution);
     lo[d] = a > 0 ? a : 0;
     hi[d] = b < grid_size - 1 ? b : grid_size - 1;
   }

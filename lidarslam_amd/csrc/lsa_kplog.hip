@@ -18,6 +18,7 @@
 #include "lsa_device_math.h"
 #include "lsa_device_grid_io.h"
 #include "lsa_kplog_io.h"
+#include "lsa_wave.h"
 
 using namespace lsa;
 
@@ -83,18 +84,6 @@ constexpr size_t kAlign = 256;
 inline size_t aligned(size_t b) { return (b + kAlign - 1) / kAlign * kAlign; }
 
 __device__ __forceinline__ double point_time(const float4& b) { return __hiloint2double(__float_as_int(b.y), __float_as_int(b.x)); }
-__device__ __forceinline__ unsigned f2ou(float f)
-{
-  unsigned u = __float_as_uint(f);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-inline float ou2f_host(unsigned u)
-{
-  u = (u & 0x80000000u) ? (u & 0x7fffffffu) : ~u;
-  float f;
-  std::memcpy(&f, &u, sizeof(f));
-  return f;
-}
 
 // the append: the three raw keypoint sets of a frame into their places in a chunk (blockIdx.y = type)
 struct AppendArgs
@@ -129,20 +118,11 @@ struct ReplayArgs
   long long total[3];
   int nframes;
 };
-__global__ void k_log_box_init(unsigned* __restrict__ b32)
+// The replayed point: which frame i lies in (one binary search in the offsets for the wavefront's first point, the lanes walk
+// on from there: a frame has hundreds of points, an empty one is stepped over), the point moved by that frame's motion --
+// k_undistort's / k_transform_stage's arithmetic: interp_eval + rigid_apply -- and stored.  first <= i < total.
+__device__ __forceinline__ int replay_point(const ReplayArgs& a, int t, long long first, long long i, float4& p)
 {
-  if (threadIdx.x < 18) b32[threadIdx.x] = (threadIdx.x % 6) < 3 ? ~0u : 0u;
-}
-// ONE launch for all frames and types (blockIdx.y = type), a thread per logged point.  A wavefront finds the frame of its
-// first point by one binary search in the offsets, its lanes walk on from there (a frame has hundreds of points; an empty
-// one is stepped over).  The point's arithmetic is k_undistort's / k_transform_stage's: interp_eval + rigid_apply.
-__global__ __launch_bounds__(256) void k_log_replay(ReplayArgs a, unsigned* __restrict__ bits)
-{
-  const int t = blockIdx.y;
-  const long long total = a.total[t];
-  const long long first = (long long)blockIdx.x * 256 + (threadIdx.x & ~63u);  // of this wavefront
-  if (first >= total) return;
-  const long long i = first + (threadIdx.x & 63u);
   const long long* __restrict__ off = a.off[t];
   int lo = 0, hi = a.nframes - 1;  // the largest f with off[f] <= first (off[0] = 0): its frame is not empty
   while (lo < hi)
@@ -152,54 +132,46 @@ __global__ __launch_bounds__(256) void k_log_replay(ReplayArgs a, unsigned* __re
     else hi = mid - 1;
   }
   int f = lo;
-  unsigned blo[3] = {~0u, ~0u, ~0u}, bhi[3] = {0u, 0u, 0u};
+  while (off[f + 1] <= i) ++f;  // off[nframes] = total > i
+  const float4* __restrict__ src = a.src[t][f];
+  const size_t j = (size_t)(i - off[f]);
+  p = src[2 * j];
+  const float4 q = src[2 * j + 1];
+  const FrameMotion& m = a.motion[f];
+  Rigid T;
+  if (m.interp) interp_eval(m.c, point_time(q), T);
+  else T = m.R;
+  double ox, oy, oz;
+  rigid_apply(T, (double)p.x, (double)p.y, (double)p.z, ox, oy, oz);
+  p.x = (float)ox; p.y = (float)oy; p.z = (float)oz;
+  a.out[t][2 * (size_t)i] = p;
+  a.out[t][2 * (size_t)i + 1] = q;
+  return f;
+}
+// ONE launch for all frames and types (blockIdx.y = type), a thread per logged point.
+__global__ __launch_bounds__(256) void k_log_replay(ReplayArgs a, unsigned* __restrict__ bits)
+{
+  const int t = blockIdx.y;
+  const long long total = a.total[t];
+  const long long first = (long long)blockIdx.x * 256 + (threadIdx.x & ~63u);  // of this wavefront
+  if (first >= total) return;
+  const long long i = first + (threadIdx.x & 63u);
+  BoxU box;
   bool in_last = false;
   if (i < total)
   {
-    while (off[f + 1] <= i) ++f;  // off[nframes] = total > i
-    const float4* __restrict__ src = a.src[t][f];
-    const size_t j = (size_t)(i - off[f]);
-    float4 p = src[2 * j];
-    const float4 q = src[2 * j + 1];
-    const FrameMotion& m = a.motion[f];
-    Rigid T;
-    if (m.interp) interp_eval(m.c, point_time(q), T);
-    else T = m.R;
-    double ox, oy, oz;
-    rigid_apply(T, (double)p.x, (double)p.y, (double)p.z, ox, oy, oz);
-    p.x = (float)ox; p.y = (float)oy; p.z = (float)oz;
-    a.out[t][2 * (size_t)i] = p;
-    a.out[t][2 * (size_t)i + 1] = q;
-    if (f == a.nframes - 1)
-    {
-      in_last = true;
-      const float v[3] = {p.x, p.y, p.z};
-      // a NaN coordinate takes no part, as in a min / max loop written with comparisons
-      for (int d = 0; d < 3; ++d)
-        if (v[d] == v[d]) blo[d] = bhi[d] = f2ou(v[d]);
-    }
+    float4 p;
+    in_last = replay_point(a, t, first, i, p) == a.nframes - 1;
+    if (in_last) box_take(box, p.x, p.y, p.z);
   }
   // the last frame's box (pcl::getMinMax3D of keypoints[k] after the loop, Slam.cxx:472-473): only its wavefronts reduce
   if (!__any(in_last)) return;
-  for (int d = 0; d < 3; ++d)
-    for (int s = 32; s > 0; s >>= 1)
-    {
-      const unsigned l2 = __shfl_down(blo[d], s), h2 = __shfl_down(bhi[d], s);
-      blo[d] = l2 < blo[d] ? l2 : blo[d];
-      bhi[d] = h2 > bhi[d] ? h2 : bhi[d];
-    }
-  if ((threadIdx.x & 63u) == 0)
-    for (int d = 0; d < 3; ++d)
-    {
-      atomicMin(&bits[6 * t + d], blo[d]);
-      atomicMax(&bits[6 * t + 3 + d], bhi[d]);
-    }
+  box_wave_send(box, bits + 6 * t);
 }
 
 // The replay of a RANGE of frames (lsa_kplog_replay_range): the tables hold the range's frames only, the point's arithmetic
 // is k_log_replay's, and the box is that of ALL the points of a type (what a sub-map made of the range is rolled onto), not
-// of the last frame's.  Every wavefront reduces its points by shuffles, the workgroup's four through LDS, and one thread
-// sends the workgroup's box: six atomics a workgroup.
+// of the last frame's: six atomics a workgroup.
 __global__ __launch_bounds__(256) void k_log_replay_range(ReplayArgs a, unsigned* __restrict__ bits)
 {
   __shared__ unsigned s_box[4][6];
@@ -208,60 +180,14 @@ __global__ __launch_bounds__(256) void k_log_replay_range(ReplayArgs a, unsigned
   if ((long long)blockIdx.x * 256 >= total) return;  // (the whole workgroup: nobody is left waiting at the barrier)
   const long long first = (long long)blockIdx.x * 256 + (threadIdx.x & ~63u);  // of this wavefront
   const long long i = first + (threadIdx.x & 63u);
-  unsigned blo[3] = {~0u, ~0u, ~0u}, bhi[3] = {0u, 0u, 0u};
+  BoxU box;
   if (i < total)
   {
-    const long long* __restrict__ off = a.off[t];
-    int lo = 0, hi = a.nframes - 1;  // the largest f with off[f] <= first (off[0] = 0): its frame is not empty
-    while (lo < hi)
-    {
-      const int mid = (lo + hi + 1) >> 1;
-      if (off[mid] <= first) lo = mid;
-      else hi = mid - 1;
-    }
-    int f = lo;
-    while (off[f + 1] <= i) ++f;  // off[nframes] = total > i
-    const float4* __restrict__ src = a.src[t][f];
-    const size_t j = (size_t)(i - off[f]);
-    float4 p = src[2 * j];
-    const float4 q = src[2 * j + 1];
-    const FrameMotion& m = a.motion[f];
-    Rigid T;
-    if (m.interp) interp_eval(m.c, point_time(q), T);
-    else T = m.R;
-    double ox, oy, oz;
-    rigid_apply(T, (double)p.x, (double)p.y, (double)p.z, ox, oy, oz);
-    p.x = (float)ox; p.y = (float)oy; p.z = (float)oz;
-    a.out[t][2 * (size_t)i] = p;
-    a.out[t][2 * (size_t)i + 1] = q;
-    const float v[3] = {p.x, p.y, p.z};
-    // a NaN coordinate takes no part, as in a min / max loop written with comparisons
-    for (int d = 0; d < 3; ++d)
-      if (v[d] == v[d]) blo[d] = bhi[d] = f2ou(v[d]);
+    float4 p;
+    replay_point(a, t, first, i, p);
+    box_take(box, p.x, p.y, p.z);
   }
-  for (int d = 0; d < 3; ++d)
-    for (int s = 32; s > 0; s >>= 1)
-    {
-      const unsigned l2 = __shfl_down(blo[d], s), h2 = __shfl_down(bhi[d], s);
-      blo[d] = l2 < blo[d] ? l2 : blo[d];
-      bhi[d] = h2 > bhi[d] ? h2 : bhi[d];
-    }
-  if ((threadIdx.x & 63u) == 0)
-    for (int d = 0; d < 3; ++d)
-    {
-      s_box[threadIdx.x >> 6][d] = blo[d];
-      s_box[threadIdx.x >> 6][3 + d] = bhi[d];
-    }
-  __syncthreads();
-  if (threadIdx.x < 6)
-  {
-    const int d = threadIdx.x;
-    unsigned v = s_box[0][d];
-    for (int w = 1; w < 4; ++w) v = d < 3 ? (s_box[w][d] < v ? s_box[w][d] : v) : (s_box[w][d] > v ? s_box[w][d] : v);
-    // (a word still as it was armed changes nothing: no atomic for it)
-    if (d < 3) { if (v != ~0u) atomicMin(&bits[6 * t + d], v); }
-    else if (v != 0u) atomicMax(&bits[6 * t + d], v);
-  }
+  box_block_send<4>(box, bits + 6 * t, s_box);
 }
 
 KpLog* log_of(lsa_ctx* ctx, bool create)
@@ -449,7 +375,7 @@ int run_replay(lsa_ctx* ctx, KpLog* log, Replay* r, float last_min[3][3], float 
   unsigned box[18];
   {
     ProfScope ps(ctx, "log_replay", (double)all * 64 + (double)r->args.nframes * (sizeof(FrameMotion) + 3 * 16));
-    hipLaunchKernelGGL(k_log_box_init, dim3(1), dim3(64), 0, ctx->stream, log->box_dev);
+    hipLaunchKernelGGL(k_box_arm, dim3(1), dim3(64), 0, ctx->stream, log->box_dev);
     hipLaunchKernelGGL(k_log_replay, dim3((unsigned)((nmax + 255) / 256), 3), dim3(256), 0, ctx->stream, r->args, log->box_dev);
   }
   LSA_HIP(ctx, hipMemcpyAsync(box, log->box_dev, sizeof(box), hipMemcpyDeviceToHost, ctx->stream));
@@ -459,8 +385,8 @@ int run_replay(lsa_ctx* ctx, KpLog* log, Replay* r, float last_min[3][3], float 
       for (int d = 0; d < 3; ++d)
       {
         // (every coordinate NaN: the words are as they were armed, and so are FLT_MAX / -FLT_MAX)
-        if (box[6 * k + d] != ~0u) last_min[k][d] = ou2f_host(box[6 * k + d]);
-        if (box[6 * k + 3 + d] != 0u) last_max[k][d] = ou2f_host(box[6 * k + 3 + d]);
+        if (box[6 * k + d] != kBoxLoArmed) last_min[k][d] = ou2f(box[6 * k + d]);
+        if (box[6 * k + 3 + d] != kBoxHiArmed) last_max[k][d] = ou2f(box[6 * k + 3 + d]);
       }
   return LSA_OK;
 }
@@ -552,7 +478,7 @@ int run_range(lsa_ctx* ctx, KpLog* log, Replay* r, float box_min[3][3], float bo
   unsigned box[18];
   {
     ProfScope ps(ctx, "log_replay_range", (double)all * 64 + (double)r->args.nframes * (sizeof(FrameMotion) + 3 * 16));
-    hipLaunchKernelGGL(k_log_box_init, dim3(1), dim3(64), 0, ctx->stream, log->box_dev);
+    hipLaunchKernelGGL(k_box_arm, dim3(1), dim3(64), 0, ctx->stream, log->box_dev);
     hipLaunchKernelGGL(k_log_replay_range, dim3((unsigned)((nmax + 255) / 256), 3), dim3(256), 0, ctx->stream, r->args, log->box_dev);
   }
   LSA_HIP(ctx, hipGetLastError());  // (a launch that failed: the outputs may feed another context, which would read them unwritten)
@@ -562,8 +488,8 @@ int run_range(lsa_ctx* ctx, KpLog* log, Replay* r, float box_min[3][3], float bo
     for (int d = 0; d < 3; ++d)
     {
       // (a word as it was armed: no point of the type, or that coordinate NaN in all of them)
-      if (box[6 * k + d] != ~0u) box_min[k][d] = ou2f_host(box[6 * k + d]);
-      if (box[6 * k + 3 + d] != 0u) box_max[k][d] = ou2f_host(box[6 * k + 3 + d]);
+      if (box[6 * k + d] != kBoxLoArmed) box_min[k][d] = ou2f(box[6 * k + d]);
+      if (box[6 * k + 3 + d] != kBoxHiArmed) box_max[k][d] = ou2f(box[6 * k + 3 + d]);
     }
   return LSA_OK;
 }

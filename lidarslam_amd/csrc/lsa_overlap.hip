@@ -5,6 +5,7 @@
 #include "lsa_ctx.h"
 #include "lsa_device_math.h"
 #include "lsa_match_internal.h"
+#include "lsa_wave.h"
 
 using namespace lsa;
 
@@ -51,10 +52,8 @@ __global__ __launch_bounds__(256) void k_overlap_score(OverlapConst c, int nb, f
       }
     acc += best;
   }
-  for (int o = 32; o > 0; o >>= 1) acc += __shfl_down(acc, o);
-  if ((threadIdx.x & 63) == 0) ws[threadIdx.x >> 6] = acc;
-  __syncthreads();
-  if (threadIdx.x == 0) partials[blockIdx.x] = ((ws[0] + ws[1]) + ws[2]) + ws[3];
+  acc = block_reduce<4>(acc, OpSum(), ws);  // (the fixed tree and ((a + b) + c) + d: the sum is compared bit for bit)
+  if (threadIdx.x == 0) partials[blockIdx.x] = acc;
 }
 
 }  // namespace

@@ -15,6 +15,7 @@
 #include "lsa_ctx.h"
 #include "lsa_kplog_io.h"
 #include "lsa_scan_descriptor.h"
+#include "lsa_wave.h"
 
 using namespace lsa;
 
@@ -80,13 +81,6 @@ constexpr int kMaxCells = place::kMaxRings * place::kMaxSectors;
 constexpr int kMaxLength = kMaxCells + place::kMaxSectors;
 // k_place_search's LDS at the largest shape: two descriptors and a tile of cosines with rows of an odd length
 static_assert((2 * kMaxLength + kShiftTile * (place::kMaxSectors | 1)) * sizeof(float) <= 64 * 1024, "k_place_search keeps to 64 KB of LDS");
-
-__device__ __forceinline__ unsigned f2ou(float f)
-{
-  unsigned u = __float_as_uint(f);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float ou2f(unsigned u) { return __uint_as_float((u & 0x80000000u) ? (u & 0x7fffffffu) : ~u); }
 
 struct DescribeFrame
 {

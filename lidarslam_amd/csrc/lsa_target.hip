@@ -7,18 +7,12 @@
 #include "lsa_ctx.h"
 #include "lsa_knn.h"
 #include "lsa_match_internal.h"
+#include "lsa_wave.h"
 
 using namespace lsa;
 
 namespace
 {
-
-__device__ __forceinline__ int f2o(float f)
-{
-  int i = __float_as_int(f);
-  return i >= 0 ? i : i ^ 0x7fffffff;
-}
-__device__ __forceinline__ float o2f(int i) { return __int_as_float(i >= 0 ? i : i ^ 0x7fffffff); }
 
 // ------------------------------------------------------------------------------------------
 // Search-grid construction.  Every target that changed since the last match (the two previous-scan targets
@@ -47,32 +41,16 @@ __global__ __launch_bounds__(256) void k_target_prep(GridBatch gb)
   const int m = gb.m[t];
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (blockIdx.x * blockDim.x >= m) return;
-  float mn[3] = {FLT_MAX, FLT_MAX, FLT_MAX}, mx[3] = {-FLT_MAX, -FLT_MAX, -FLT_MAX};
+  __shared__ float s_box[4][6];
+  BoxF box;
   if (i < m)
   {
     const float4 a = gb.pts[t][2 * (size_t)i];
     const float4 b = gb.pts[t][2 * (size_t)i + 1];
     gb.xyzl[t][i] = make_float4(a.x, a.y, a.z, __uint_as_float(__float_as_uint(b.w) & 0xffffu));
-    mn[0] = mx[0] = a.x; mn[1] = mx[1] = a.y; mn[2] = mx[2] = a.z;
+    box = box_of_point(a.x, a.y, a.z);
   }
-  for (int d = 0; d < 3; ++d)
-  {
-    for (int o = 32; o > 0; o >>= 1)
-    {
-      mn[d] = fminf(mn[d], __shfl_down(mn[d], o));
-      mx[d] = fmaxf(mx[d], __shfl_down(mx[d], o));
-    }
-  }
-  __shared__ float smn[4][3], smx[4][3];
-  if ((threadIdx.x & 63) == 0)
-    for (int d = 0; d < 3; ++d) { smn[threadIdx.x >> 6][d] = mn[d]; smx[threadIdx.x >> 6][d] = mx[d]; }
-  __syncthreads();
-  if (threadIdx.x < 3)
-  {
-    const int d = threadIdx.x;
-    atomicMin(&gb.bbox[t][d], f2o(fminf(fminf(smn[0][d], smn[1][d]), fminf(smn[2][d], smn[3][d]))));
-    atomicMax(&gb.bbox[t][3 + d], f2o(fmaxf(fmaxf(smx[0][d], smx[1][d]), fmaxf(smx[2][d], smx[3][d]))));
-  }
+  box_block_send<4>(box, gb.bbox[t], s_box);
 }
 
 // desc[0]: cell = hint (grown until the grid fits its cell budget); every further level has cells 4 x
@@ -85,7 +63,7 @@ __global__ void k_grid_setup(GridBatch gb)
   if (threadIdx.x != 0) return;
   const int* bbox = gb.bbox[t];
   float mn[3], mx[3];
-  for (int d = 0; d < 3; ++d) { mn[d] = o2f(bbox[d]); mx[d] = o2f(bbox[3 + d]); }
+  for (int d = 0; d < 3; ++d) { mn[d] = os2f(bbox[d]); mx[d] = os2f(bbox[3 + d]); }
   float cell = gb.cell_hint[t];
   for (int level = 0; level < kGridLevels; ++level)
   {
@@ -194,7 +172,7 @@ __global__ __launch_bounds__(256) void k_grid_count(GridBatch gb)
 // exclusive scan of cell_start[0 .. ncells] in three passes (1024 elements per block)
 __global__ __launch_bounds__(256) void k_scan_block(GridBatch gb)
 {
-  __shared__ uint32_t s[256];
+  __shared__ uint32_t wsum[4];
   const int t = blockIdx.y / kGridLevels, l = blockIdx.y % kGridLevels;
   const int total = gb.desc[t][l].ncells + 1;
   const int base = blockIdx.x * 1024;
@@ -207,23 +185,15 @@ __global__ __launch_bounds__(256) void k_scan_block(GridBatch gb)
     v[q] = (i < total) ? data[i] : 0;
     tsum += v[q];
   }
-  s[threadIdx.x] = tsum;
-  __syncthreads();
-  for (int o = 1; o < 256; o <<= 1)
-  {
-    uint32_t a = (threadIdx.x >= (unsigned)o) ? s[threadIdx.x - o] : 0;
-    __syncthreads();
-    s[threadIdx.x] += a;
-    __syncthreads();
-  }
-  uint32_t run = s[threadIdx.x] - tsum;
+  uint32_t block_sum;
+  uint32_t run = block_exclusive_scan<4>(tsum, wsum, &block_sum);
   for (int q = 0; q < 4; ++q)
   {
     const int i = base + threadIdx.x * 4 + q;
     if (i < total) data[i] = run;
     run += v[q];
   }
-  if (threadIdx.x == 255) gb.block_sums[t][l][blockIdx.x] = s[255];
+  if (threadIdx.x == 255) gb.block_sums[t][l][blockIdx.x] = block_sum;
 }
 // third pass fused into the second: every block sums the totals of the blocks in front of it itself (a grid of 4 M
 // cells is 4 096 blocks: sixteen loads per thread)
@@ -237,10 +207,7 @@ __global__ __launch_bounds__(256) void k_scan_add(GridBatch gb)
   const uint32_t* sums = gb.block_sums[t][l];
   uint32_t mine = 0;
   for (int j = threadIdx.x; j < (int)blockIdx.x; j += 256) mine += sums[j];
-  for (int o = 32; o > 0; o >>= 1) mine += __shfl_down(mine, o);
-  if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = mine;
-  __syncthreads();
-  const uint32_t add = part[0] + part[1] + part[2] + part[3];
+  const uint32_t add = block_reduce_all<4>(mine, OpSum(), part);
   uint32_t* data = gb.cell_start[t][l];
   for (int q = 0; q < 4; ++q)
   {
@@ -257,7 +224,7 @@ __global__ __launch_bounds__(256) void k_grid_scatter(GridBatch gb)
   {
     // the bounding box is re-armed for the next build (its last readers were k_grid_zero's workgroups)
     int* bbox = gb.bbox[t];
-    for (int d = 0; d < 3; ++d) { bbox[d] = 0x7fffffff; bbox[3 + d] = (int)0x80000000; }
+    for (int d = 0; d < 3; ++d) { bbox[d] = kBoxLoArmedS; bbox[3 + d] = kBoxHiArmedS; }
   }
   if (blockIdx.x * blockDim.x >= gb.m[t]) return;
   const bool active = i < gb.m[t];

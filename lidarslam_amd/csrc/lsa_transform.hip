@@ -1,15 +1,25 @@
 // lsa_transform.hip -- undistortion and rigid / interpolated transforms of device point sets.
 //   k_undistort          Slam::RefineUndistortion per-point loop (slam_lib/src/Slam.cxx:1342-1351)
 //   k_transform_out      Slam::TransformPointCloud (:1491-1509) / AggregateFrames(..., true) (:1512-1578)
-//   k_time_range, k_bbox Slam::InitUndistortion (:1291-1300), getMinMax3D of the world keypoints (:1026-1029)
+//   k_time_range3        Slam::InitUndistortion (:1291-1300): the time range of the three keypoint types
+//   k_bbox3, k_loc_start getMinMax3D of the world keypoints (:1026-1029), the three types in one launch
 // All arithmetic in double, stored as float (Utils::TransformPoint, Utilities.h:274-278).
 #include <cfloat>
 #include <cmath>
 #include <limits>
 #include "lsa_ctx.h"
 #include "lsa_device_math.h"
+#include "lsa_wave.h"
 
 using namespace lsa;
+
+namespace lsa
+{
+__global__ void k_box_arm(unsigned* __restrict__ words)
+{
+  if (threadIdx.x < 18) words[threadIdx.x] = (threadIdx.x % 6) < 3 ? kBoxLoArmed : kBoxHiArmed;
+}
+}  // namespace lsa
 
 namespace
 {
@@ -91,82 +101,6 @@ __global__ __launch_bounds__(256) void k_copy_sets(StageOut s)
   s.out[t][2 * (size_t)i + 1] = s.in[t][2 * (size_t)i + 1];
 }
 
-// monotone encoding of doubles for 64-bit atomicMin/Max
-__device__ __forceinline__ unsigned long long d2o(double d)
-{
-  unsigned long long u = (unsigned long long)__double_as_longlong(d);
-  return (u & 0x8000000000000000ull) ? ~u : (u | 0x8000000000000000ull);
-}
-__host__ inline double o2d_host(unsigned long long u)
-{
-  u = (u & 0x8000000000000000ull) ? (u & 0x7fffffffffffffffull) : ~u;
-  double d;
-  std::memcpy(&d, &u, sizeof(d));
-  return d;
-}
-
-__global__ __launch_bounds__(256) void k_time_range(const float4* __restrict__ pts, int n, unsigned long long* __restrict__ bits)
-{
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  unsigned long long lo = ~0ull, hi = 0ull;
-  if (i < n)
-  {
-    const unsigned long long o = d2o(point_time(pts[2 * (size_t)i + 1]));
-    lo = hi = o;
-  }
-  for (int s = 32; s > 0; s >>= 1)
-  {
-    const unsigned long long l2 = __shfl_down(lo, s), h2 = __shfl_down(hi, s);
-    lo = l2 < lo ? l2 : lo;
-    hi = h2 > hi ? h2 : hi;
-  }
-  if ((threadIdx.x & 63) == 0 && i < n + 64)
-  {
-    atomicMin(&bits[0], lo);
-    atomicMax(&bits[1], hi);
-  }
-}
-
-__device__ __forceinline__ unsigned f2ou(float f)
-{
-  unsigned u = __float_as_uint(f);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__host__ inline float ou2f_host(unsigned u)
-{
-  u = (u & 0x80000000u) ? (u & 0x7fffffffu) : ~u;
-  float f;
-  std::memcpy(&f, &u, sizeof(f));
-  return f;
-}
-
-__global__ __launch_bounds__(256) void k_bbox(const float4* __restrict__ pts, int n, Rigid T, unsigned* __restrict__ bits)
-{
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  unsigned lo[3] = {~0u, ~0u, ~0u}, hi[3] = {0u, 0u, 0u};
-  if (i < n)
-  {
-    const float4 a = pts[2 * (size_t)i];
-    double ox, oy, oz;
-    rigid_apply(T, (double)a.x, (double)a.y, (double)a.z, ox, oy, oz);
-    const float v[3] = {(float)ox, (float)oy, (float)oz};
-    for (int d = 0; d < 3; ++d) lo[d] = hi[d] = f2ou(v[d]);
-  }
-  for (int d = 0; d < 3; ++d)
-    for (int s = 32; s > 0; s >>= 1)
-    {
-      const unsigned l2 = __shfl_down(lo[d], s), h2 = __shfl_down(hi[d], s);
-      lo[d] = l2 < lo[d] ? l2 : lo[d];
-      hi[d] = h2 > hi[d] ? h2 : hi[d];
-    }
-  if ((threadIdx.x & 63) == 0)
-    for (int d = 0; d < 3; ++d)
-    {
-      atomicMin(&bits[d], lo[d]);
-      atomicMax(&bits[3 + d], hi[d]);
-    }
-}
-
 // the three keypoint sets at once: blockIdx.y = type, counts read from the device (they may not be on the
 // host yet), one set of atomics per block.  bits: [0..1] time range, [2 + 6 * type ..] bounding boxes.
 struct KpSets
@@ -178,10 +112,6 @@ __global__ void k_range_init(unsigned long long* __restrict__ bits)
 {
   if (threadIdx.x == 0) { bits[0] = ~0ull; bits[1] = 0ull; }
 }
-__global__ void k_bbox_init(unsigned* __restrict__ b32)
-{
-  if (threadIdx.x < 18) b32[threadIdx.x] = (threadIdx.x % 6) < 3 ? ~0u : 0u;
-}
 __global__ __launch_bounds__(256) void k_time_range3(KpSets sets, const int* __restrict__ counts, unsigned long long* __restrict__ bits)
 {
   __shared__ unsigned long long slo[4], shi[4];
@@ -190,30 +120,23 @@ __global__ __launch_bounds__(256) void k_time_range3(KpSets sets, const int* __r
   if ((int)(blockIdx.x * blockDim.x) >= n) return;
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   unsigned long long lo = ~0ull, hi = 0ull;
-  if (i < n) lo = hi = d2o(point_time(sets.pts[t][2 * (size_t)i + 1]));
-  for (int s = 32; s > 0; s >>= 1)
-  {
-    const unsigned long long l2 = __shfl_down(lo, s), h2 = __shfl_down(hi, s);
-    lo = l2 < lo ? l2 : lo;
-    hi = h2 > hi ? h2 : hi;
-  }
-  if ((threadIdx.x & 63) == 0) { slo[threadIdx.x >> 6] = lo; shi[threadIdx.x >> 6] = hi; }
-  __syncthreads();
+  if (i < n) lo = hi = d2ou(point_time(sets.pts[t][2 * (size_t)i + 1]));
+  lo = block_reduce<4>(lo, OpMin(), slo);
+  hi = block_reduce<4>(hi, OpMax(), shi);
   if (threadIdx.x == 0)
   {
-    for (int w = 1; w < 4; ++w) { lo = slo[w] < lo ? slo[w] : lo; hi = shi[w] > hi ? shi[w] : hi; }
     atomicMin(&bits[0], lo);
     atomicMax(&bits[1], hi);
   }
 }
 __global__ __launch_bounds__(256) void k_bbox3(KpSets sets, Rigid T0, int interpolate, InterpConst c, unsigned* __restrict__ bits)
 {
-  __shared__ unsigned slo[4][3], shi[4][3];
+  __shared__ unsigned s_box[4][6];
   const int t = blockIdx.y;
   const int n = sets.n[t];
   if ((int)(blockIdx.x * blockDim.x) >= n) return;
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  unsigned lo[3] = {~0u, ~0u, ~0u}, hi[3] = {0u, 0u, 0u};
+  BoxU box;
   if (i < n)
   {
     const float4 a = sets.pts[t][2 * (size_t)i];
@@ -221,43 +144,23 @@ __global__ __launch_bounds__(256) void k_bbox3(KpSets sets, Rigid T0, int interp
     if (interpolate) interp_eval(c, point_time(sets.pts[t][2 * (size_t)i + 1]), T);  // the pose at the point's own time
     double ox, oy, oz;
     rigid_apply(T, (double)a.x, (double)a.y, (double)a.z, ox, oy, oz);
-    const float v[3] = {(float)ox, (float)oy, (float)oz};
-    // a NaN coordinate takes no part, as in a min / max loop written with comparisons
-    for (int d = 0; d < 3; ++d)
-      if (v[d] == v[d]) lo[d] = hi[d] = f2ou(v[d]);
+    box_take(box, (float)ox, (float)oy, (float)oz);
   }
-  for (int d = 0; d < 3; ++d)
-    for (int s = 32; s > 0; s >>= 1)
-    {
-      const unsigned l2 = __shfl_down(lo[d], s), h2 = __shfl_down(hi[d], s);
-      lo[d] = l2 < lo[d] ? l2 : lo[d];
-      hi[d] = h2 > hi[d] ? h2 : hi[d];
-    }
-  if ((threadIdx.x & 63) == 0)
-    for (int d = 0; d < 3; ++d) { slo[threadIdx.x >> 6][d] = lo[d]; shi[threadIdx.x >> 6][d] = hi[d]; }
-  __syncthreads();
-  if (threadIdx.x < 3)
-  {
-    const int d = threadIdx.x;
-    unsigned l = slo[0][d], h = shi[0][d];
-    for (int w = 1; w < 4; ++w) { l = slo[w][d] < l ? slo[w][d] : l; h = shi[w][d] > h ? shi[w][d] : h; }
-    atomicMin(&bits[6 * t + d], l);
-    atomicMax(&bits[6 * t + 3 + d], h);
-  }
+  box_block_send<4>(box, bits + 6 * t, s_box);
 }
 
 // What the localization starts with, in ONE launch: working = the raw keypoints, undistorted (the reset and the first
 // RefineUndistortion of Slam::Localization, Slam.cxx:980-999), and the bounding boxes of the three types under the pose
-// guess (pcl::getMinMax3D of the transformed keypoints, Slam.cxx:1027-1029).  The boxes' words must be armed (k_bbox_init)
+// guess (pcl::getMinMax3D of the transformed keypoints, Slam.cxx:1027-1029).  The boxes' words must be armed (k_box_arm)
 // before the launch: the blocks reduce into them with atomics.
 __global__ __launch_bounds__(256) void k_loc_start(StageOut s, int undistort, InterpConst c, int boxes, Rigid T0, unsigned* __restrict__ bits)
 {
-  __shared__ unsigned slo[4][3], shi[4][3];
+  __shared__ unsigned s_box[4][6];
   const int t = blockIdx.y;
   const int n = s.n[t];
   if ((int)(blockIdx.x * blockDim.x) >= n) return;
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  unsigned lo[3] = {~0u, ~0u, ~0u}, hi[3] = {0u, 0u, 0u};
+  BoxU box;
   if (i < n)
   {
     float4 a = s.in[t][2 * (size_t)i];
@@ -276,30 +179,11 @@ __global__ __launch_bounds__(256) void k_loc_start(StageOut s, int undistort, In
     {
       double ox, oy, oz;
       rigid_apply(T0, (double)a.x, (double)a.y, (double)a.z, ox, oy, oz);
-      const float v[3] = {(float)ox, (float)oy, (float)oz};
-      for (int d = 0; d < 3; ++d)
-        if (v[d] == v[d]) lo[d] = hi[d] = f2ou(v[d]);
+      box_take(box, (float)ox, (float)oy, (float)oz);
     }
   }
   if (!boxes) return;
-  for (int d = 0; d < 3; ++d)
-    for (int sft = 32; sft > 0; sft >>= 1)
-    {
-      const unsigned l2 = __shfl_down(lo[d], sft), h2 = __shfl_down(hi[d], sft);
-      lo[d] = l2 < lo[d] ? l2 : lo[d];
-      hi[d] = h2 > hi[d] ? h2 : hi[d];
-    }
-  if ((threadIdx.x & 63) == 0)
-    for (int d = 0; d < 3; ++d) { slo[threadIdx.x >> 6][d] = lo[d]; shi[threadIdx.x >> 6][d] = hi[d]; }
-  __syncthreads();
-  if (threadIdx.x < 3)
-  {
-    const int d = threadIdx.x;
-    unsigned l = slo[0][d], h = shi[0][d];
-    for (int w = 1; w < 4; ++w) { l = slo[w][d] < l ? slo[w][d] : l; h = shi[w][d] > h ? shi[w][d] : h; }
-    atomicMin(&bits[6 * t + d], l);
-    atomicMax(&bits[6 * t + 3 + d], h);
-  }
+  box_block_send<4>(box, bits + 6 * t, s_box);
 }
 
 // Everything of LinearTransformInterpolator that is independent of the point (lsa_posemath.h: one source for the host
@@ -339,8 +223,8 @@ void finish_time_range(lsa_ctx* ctx, int set, const unsigned long long bits[2])
 {
   const int total = ctx->kp_n[set][0] + ctx->kp_n[set][1] + ctx->kp_n[set][2];
   // empty set: the reference's min/max loop leaves its initial values (Slam.cxx:1291-1300)
-  ctx->kp_time[set][0] = total == 0 ? std::numeric_limits<double>::max() : o2d_host(bits[0]);
-  ctx->kp_time[set][1] = total == 0 ? std::numeric_limits<double>::lowest() : o2d_host(bits[1]);
+  ctx->kp_time[set][0] = total == 0 ? std::numeric_limits<double>::max() : ou2d(bits[0]);
+  ctx->kp_time[set][1] = total == 0 ? std::numeric_limits<double>::lowest() : ou2d(bits[1]);
   ctx->kp_time_valid[set] = true;
 }
 }  // namespace lsa
@@ -395,7 +279,7 @@ int lsa_arm_localization_boxes(lsa_ctx* ctx)
   if (!ctx) return LSA_E_ARG;
   if (ctx->loc_armed) return LSA_OK;
   LSA_HIP(ctx, hipSetDevice(ctx->device));
-  hipLaunchKernelGGL(k_bbox_init, dim3(1), dim3(64), 0, ctx->stream, lsa::loc_box_words(ctx));
+  hipLaunchKernelGGL(k_box_arm, dim3(1), dim3(64), 0, ctx->stream, lsa::loc_box_words(ctx));
   ctx->loc_armed = true;
   return LSA_OK;
 }
@@ -479,7 +363,7 @@ static int bboxes_begin(lsa_ctx* ctx, int set, const double pose[16], const doub
   Rigid T;
   row_major_to_rt(pose, T.R, T.t);
   unsigned* bits = reinterpret_cast<unsigned*>(ctx->range_bits + 16);
-  hipLaunchKernelGGL(k_bbox_init, dim3(1), dim3(64), 0, ctx->stream, bits);
+  hipLaunchKernelGGL(k_box_arm, dim3(1), dim3(64), 0, ctx->stream, bits);
   InterpConst ic{};
   if (pose_end) ic = make_interp(pose, pose_end, t0, t1);
   hipLaunchKernelGGL(k_bbox3, dim3((nmax + 255) / 256, 3), dim3(256), 0, ctx->stream, sets, T, pose_end ? 1 : 0, ic, bits);
@@ -526,7 +410,7 @@ int lsa_keypoint_boxes_predicted(lsa_ctx* ctx, int set, const double H0[16], con
   hipStream_t st = ctx->prefetch_stream;
   LSA_HIP(ctx, hipStreamWaitEvent(st, ctx->ev_pred, 0));
   unsigned* bits = lsa::box_words(ctx);
-  hipLaunchKernelGGL(k_bbox_init, dim3(1), dim3(64), 0, st, bits);
+  hipLaunchKernelGGL(k_box_arm, dim3(1), dim3(64), 0, st, bits);
   hipLaunchKernelGGL(k_bbox3, dim3((nmax + 255) / 256, 3), dim3(256), 0, st, sets, T, H1 ? 1 : 0, ic, bits);
   ctx->pred_on_lookahead = true;
   return LSA_OK;
@@ -551,7 +435,7 @@ int lsa_keypoint_bboxes_end(lsa_ctx* ctx, float mn[9], float mx[9])
   const unsigned* hp = reinterpret_cast<const unsigned*>(ctx->host_pinned + 160);
   for (int k = 0; k < 3; ++k)
     if (ctx->bbox_n[k] > 0)
-      for (int d = 0; d < 3; ++d) { mn[3 * k + d] = ou2f_host(hp[6 * k + d]); mx[3 * k + d] = ou2f_host(hp[6 * k + 3 + d]); }
+      for (int d = 0; d < 3; ++d) { mn[3 * k + d] = ou2f(hp[6 * k + d]); mx[3 * k + d] = ou2f(hp[6 * k + 3 + d]); }
   return LSA_OK;
 }
 int lsa_working_bboxes(lsa_ctx* ctx, const double pose[16], float mn[9], float mx[9])

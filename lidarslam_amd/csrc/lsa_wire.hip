@@ -3,6 +3,7 @@
 #include <cmath>
 #include "lsa_ctx.h"
 #include "lsa_compact.h"
+#include "lsa_wave.h"
 #include "../../include/lsa_pmath.h"
 
 using namespace lsa;
@@ -224,18 +225,8 @@ __global__ __launch_bounds__(256) void k_soa_scan_chunks(SoaFrame f, long long* 
       m = t > m ? t : m;
     }
   }
-  for (int o = 32; o > 0; o >>= 1)
-  {
-    const long long t = __shfl_down(m, o);
-    m = t > m ? t : m;
-  }
-  if ((threadIdx.x & 63) == 0) mx[threadIdx.x >> 6] = m;
-  __syncthreads();
-  if (threadIdx.x == 0)
-  {
-    long long a = mx[0] > mx[1] ? mx[0] : mx[1], b = mx[2] > mx[3] ? mx[2] : mx[3];
-    atomicMax(tmax, a > b ? a : b);
-  }
+  m = block_reduce<4>(m, OpMax(), mx);
+  if (threadIdx.x == 0) atomicMax(tmax, m);
 }
 // points with all-zero coordinates are dropped
 struct SoaKeep

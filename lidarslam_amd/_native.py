@@ -115,14 +115,9 @@ def synth_lib():
             raise RuntimeError(
                 f"{SYNTH_LIB_PATH} is missing: run `python -c 'import __graft_entry__ as g; g.build()'` first"
             )
-        lib = C.CDLL(SYNTH_LIB_PATH)
-        lib.lsa_synth_frame.restype = C.c_int
-        lib.lsa_synth_frame.argtypes = [C.c_int, C.c_uint64, C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_uint64)]
-        lib.lsa_synth_sensor.restype = C.c_int
-        lib.lsa_synth_sensor.argtypes = [C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_double), C.POINTER(C.c_double)]
-        lib.lsa_synth_pose.restype = None
-        lib.lsa_synth_pose.argtypes = [C.c_int, C.c_void_p]
-        _synth = lib
+        from ._abi import declare  # _abi imports this module
+
+        _synth = declare(C.CDLL(SYNTH_LIB_PATH), ["lsa_synth_frame", "lsa_synth_sensor", "lsa_synth_pose"])
     return _synth
 
 

@@ -1,0 +1,152 @@
+"""Loop-closure candidates and place recognition: the parameter / result structs and the host statements."""
+import ctypes as C
+
+import numpy as np
+
+from ._abi import E_ARG, _error, lib
+from ._native import EDGE, PLANE, POINT_DTYPE, ptr
+
+
+class LoopClosureParams(C.Structure):
+    """lsa_loop_closure_params_t (include/lidarslam_amd.h): a value <= 0 of the last four means the Localization parameter
+    of the same meaning."""
+
+    _fields_ = [
+        ("revisited_half_window", C.c_int32), ("query_half_window", C.c_int32), ("icp_max_iter", C.c_int32), ("lm_max_iter", C.c_int32),
+        ("init_saturation", C.c_double), ("final_saturation", C.c_double),
+    ]
+
+    def __init__(self, revisited_half_window=5, query_half_window=0, icp_max_iter=0, lm_max_iter=0, init_saturation=0.0, final_saturation=0.0):
+        super().__init__(revisited_half_window, query_half_window, icp_max_iter, lm_max_iter, init_saturation, final_saturation)
+
+
+class LoopClosureResultStruct(C.Structure):
+    """lsa_loop_closure_result_t (include/lidarslam_amd.h)."""
+
+    _fields_ = [
+        ("world", C.c_double * 16), ("relative", C.c_double * 16), ("covariance", C.c_double * 36),
+        ("position_error", C.c_double), ("orientation_error", C.c_double), ("status", C.c_int32), ("iterations", C.c_int32),
+        ("first_histogram", C.c_int32 * 24), ("last_histogram", C.c_int32 * 24), ("target_points", C.c_int64 * 3), ("query_points", C.c_int64 * 3),
+    ]
+
+
+class LoopClosureResult:
+    """What Slam.register_logged_frames returns: world (4, 4), relative (4, 4) = inv(P[revisited]) @ world, covariance (6, 6),
+    position_error [m], orientation_error [deg], status (0 registered, 1 skipped), iterations, first_histogram /
+    last_histogram (3, 8) and target_points / query_points (3,)."""
+
+    def __init__(self, r):
+        self.world = np.array(r.world).reshape(4, 4)
+        self.relative = np.array(r.relative).reshape(4, 4)
+        self.covariance = np.array(r.covariance).reshape(6, 6)
+        self.position_error, self.orientation_error = r.position_error, r.orientation_error
+        self.status, self.iterations = r.status, r.iterations
+        self.first_histogram = np.array(r.first_histogram, np.int32).reshape(3, 8)
+        self.last_histogram = np.array(r.last_histogram, np.int32).reshape(3, 8)
+        self.target_points = np.array(r.target_points, np.int64)
+        self.query_points = np.array(r.query_points, np.int64)
+
+
+def loop_closure_candidate(poses, times, query, min_travelled, max_distance):
+    """lsa_loop_closure_candidate on a trajectory as Slam.trajectory() gives it (poses (n, 4, 4), times (n,)): among the
+    frames before `query` at least min_travelled metres back along the trajectory and within max_distance metres of
+    query's position, the nearest (the lower index on a tie); -1 when there is none.  Host only."""
+    P = np.asarray(poses, np.float64).reshape(-1, 16)
+    rows = np.ascontiguousarray(np.concatenate([P, np.asarray(times, np.float64).reshape(-1, 1)], axis=1))
+    rc = lib().lsa_loop_closure_candidate(ptr(rows), rows.shape[0], int(query), float(min_travelled), float(max_distance))
+    if rc < -1:
+        raise _error("lsa_loop_closure_candidate", rc, "bad argument")
+    return rc
+
+
+class PlaceParams(C.Structure):
+    """lsa_place_params_t (include/lidarslam_amd.h): the shape of a frame's descriptor.  min_common_sectors None: the default
+    of the shape, max(1, sectors // 4)."""
+
+    _fields_ = [
+        ("rings", C.c_int32), ("sectors", C.c_int32), ("type_mask", C.c_uint32), ("min_common_sectors", C.c_int32),
+        ("min_range", C.c_double), ("max_range", C.c_double), ("height_offset", C.c_double),
+    ]
+
+    def __init__(self, rings=20, sectors=60, type_mask=(1 << EDGE) | (1 << PLANE), min_range=0.0, max_range=80.0, height_offset=2.0, min_common_sectors=None):
+        if min_common_sectors is None:
+            min_common_sectors = max(1, int(sectors) // 4)
+        super().__init__(rings, sectors, type_mask, min_common_sectors, min_range, max_range, height_offset)
+
+    @property
+    def length(self):
+        """floats of a descriptor: rings * sectors cells, row-major [ring][sector], then the sectors column norms"""
+        return self.rings * self.sectors + self.sectors
+
+
+class PlaceSearch(C.Structure):
+    """lsa_place_search_t: the descriptor's parameters and the selection's."""
+
+    _fields_ = [
+        ("descriptor", PlaceParams), ("min_travelled", C.c_double), ("max_distance", C.c_double), ("max_descriptor_distance", C.c_double),
+        ("exclusion_half_window", C.c_int32), ("reserved", C.c_int32),
+    ]
+
+    def __init__(self, min_travelled=20.0, max_distance=0.0, max_descriptor_distance=0.0, exclusion_half_window=5, **descriptor):
+        super().__init__(PlaceParams(**descriptor), min_travelled, max_distance, max_descriptor_distance, exclusion_half_window, 0)
+
+
+class PlaceCandidateStruct(C.Structure):
+    """lsa_place_candidate_t."""
+
+    _fields_ = [("frame", C.c_int32), ("shift", C.c_int32), ("distance", C.c_float), ("reserved", C.c_float), ("yaw", C.c_double)]
+
+
+def _candidates(out, n):
+    """[(frame, distance, shift, yaw)]: distance a numpy float32, yaw a float [rad]"""
+    return [(int(c.frame), np.float32(c.distance), int(c.shift), float(c.yaw)) for c in out[:n]]
+
+
+def scan_descriptor(points, **params):
+    """The host statement of a frame's descriptor (lsa_scan_descriptor_host): points a POINT_DTYPE array, or (n, 3) xyz,
+    already filtered by type -> float32 (rings * sectors + sectors,).  params: PlaceParams' fields."""
+    p = PlaceParams(**params)
+    pts = np.asarray(points)
+    if pts.dtype != POINT_DTYPE:
+        xyz = np.asarray(points, np.float32).reshape(-1, 3)
+        pts = np.zeros(xyz.shape[0], POINT_DTYPE)
+        pts["x"], pts["y"], pts["z"] = xyz[:, 0], xyz[:, 1], xyz[:, 2]
+    pts = np.ascontiguousarray(pts)
+    out = np.zeros(max(p.rings, 0) * max(p.sectors, 0) + max(p.sectors, 0), np.float32)
+    rc = lib().lsa_scan_descriptor_host(C.byref(p), ptr(pts) if pts.size else None, pts.size, ptr(out))
+    if rc < 0:
+        raise _error("lsa_scan_descriptor_host", rc, "parameters out of limits")
+    return out
+
+
+def place_distance(a, b, **params):
+    """The host statement of the distance of query descriptor a to candidate descriptor b (lsa_place_distance_host) ->
+    (distance float32, shift): the smallest distance over the column shifts, the lowest shift on a tie."""
+    p = PlaceParams(**params)
+    a = np.ascontiguousarray(np.asarray(a, np.float32).reshape(-1))
+    b = np.ascontiguousarray(np.asarray(b, np.float32).reshape(-1))
+    if p.rings < 1 or p.sectors < 1 or a.size != p.length or b.size != p.length:
+        raise _error("lsa_place_distance_host", E_ARG, "descriptors of another shape than the parameters'")
+    d, s = C.c_float(), C.c_int()
+    rc = lib().lsa_place_distance_host(C.byref(p), ptr(a), ptr(b), C.byref(d), C.byref(s))
+    if rc < 0:
+        raise _error("lsa_place_distance_host", rc, "parameters out of limits")
+    return np.float32(d.value), int(s.value)
+
+
+def place_select(distance, shift, poses, times, query, sectors=60, min_travelled=20.0, max_distance=0.0, max_descriptor_distance=0.0,
+                 exclusion_half_window=5, capacity=5):
+    """The host statement of the selection (lsa_place_select_host): distance / shift the table of the frames 0..query-1,
+    poses (n, 4, 4) and times (n,) as Slam.trajectory() gives them -> [(frame, distance, shift, yaw)], best first."""
+    P = np.asarray(poses, np.float64).reshape(-1, 16)
+    rows = np.ascontiguousarray(np.concatenate([P, np.asarray(times, np.float64).reshape(-1, 1)], axis=1))
+    d = np.ascontiguousarray(np.asarray(distance, np.float32).reshape(-1))
+    s = np.ascontiguousarray(np.asarray(shift, np.int32).reshape(-1))
+    if d.size < max(int(query), 0) or s.size < max(int(query), 0):
+        raise _error("lsa_place_select_host", E_ARG, "a table shorter than the frames before query")
+    out = (PlaceCandidateStruct * max(int(capacity), 1))()
+    rc = lib().lsa_place_select_host(ptr(d) if d.size else None, ptr(s) if s.size else None, ptr(rows), rows.shape[0], int(query), int(sectors), float(min_travelled),
+                                     float(max_distance), float(max_descriptor_distance), int(exclusion_half_window), out, int(capacity))
+    if rc < 0:
+        raise _error("lsa_place_select_host", rc, "bad argument")
+    return _candidates(out, rc)

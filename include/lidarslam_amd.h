@@ -1128,7 +1128,8 @@ int lsa_kplog_replay_range(lsa_ctx* ctx, unsigned type_mask, const double* poses
  * lsa_slam_register_logged_frames produces.  The whole definition -- retraction t += R rho, R = R Exp(phi); the error
  * e = [Rz^T (Ri^T (tj - ti) - tz) ; Log(Rz^T Ri^T Rj)]; its exact Jacobians; the order of every sum; the rules for small angles
  * and angles near pi; the Levenberg-Marquardt loop with a preconditioned conjugate gradient inside -- is
- * lidarslam_amd/csrc/lsa_pose_graph.h, compiled for the host and the device alike.  No robust kernels.  Position
+ * lidarslam_amd/csrc/lsa_pose_graph.h, compiled for the host and the device alike.  Plain least squares in these calls; robust losses on chosen
+ * edges and on the priors, with a verdict per constraint: the lsa_pgo_*_robust calls further down.  Position
  * priors (GPS fixes) and the reference's RunPoseGraphOptimization on top of them: the next comment.
  * - lsa_pgo_edge_t: from -> to, `relative` the measured inv(P[from]) * P[to] (row-major 4x4), `information` its 6x6 weight
  *   over (translation, rotation) in the tangent of the retraction, row-major.  from != to.
@@ -1287,6 +1288,57 @@ int lsa_gps_match_trajectory(const double* slam_times, int n, const double* gps_
 int lsa_trajectory_alignment(const double* from_xyz, const double* to_xyz, int pairs, double* T16_out);
 int lsa_slam_run_pose_graph_optimization(lsa_slam* s, const double* gps_times, const double* gps_xyz, const double* gps_cov9, int G, double* gps_to_sensor16,
                                          double time_offset, const lsa_pgo_params_t* params, double* poses17_out, int capacity, lsa_pgo_result_t* result);
+
+/* Robust losses in the pose graph, and a verdict per constraint (the definition, with the order of every
+ * operation, is the section ROBUST LOSS of lidarslam_amd/csrc/lsa_pose_graph.h).
+ * - A loss acts on s = chi2 of one constraint with a scale c > 0 in sigmas: Huber, Geman-McClure or Tukey (LSA_PGO_LOSS_*),
+ *   first-order IRLS (the weight w = rho'(s) multiplies the constraint's block record, no second-derivative term: g2o's rule),
+ *   and the cost is F = 1/2 sum rho.  Geman-McClure and Tukey are not convex: the solve finds the minimum nearest its start.
+ * - lsa_pgo_robust_t: edge_loss / edge_scale act on the edges edge_mask selects (m bytes, non-zero = robustified; NULL = every
+ *   edge), prior_loss / prior_scale on every prior.  lsa_pgo_robust_init: both losses NONE, both scales 1.  A loss outside
+ *   0..3, or a scale that is not finite and positive while its loss is not NONE: LSA_E_ARG, nothing written.  robust NULL = init.
+ * - lsa_pgo_robust_rho_host(loss, scale, s, &rho, &w): the loss alone.
+ * - lsa_pgo_linearize_robust[_host] -> e[6 m], blocks[120 m] (each record times its w), chi2[m] (raw), rho[m], w[m];
+ *   lsa_pgo_linearize_robust_priors[_host] -> e[3 k], blocks[42 k], chi2[k], rho[k], w[k] (prior_loss on every prior).
+ * - lsa_pgo_solve_robust[_host]: lsa_pgo_solve_priors[_host] under the losses (which is now its case of both losses NONE, bit
+ *   for bit).  edge_verdict_out (2 m doubles) and prior_verdict_out (2 k doubles) may be NULL; else {chi2, weight} per
+ *   constraint at the returned poses, weight 1 for a constraint that is not robustified (on the device: one more launch of the
+ *   chi2 kernels after the loop, copied back with the poses).
+ * - lsa_slam_optimize_logged_trajectory_robust: lsa_slam_optimize_logged_trajectory with edge_loss on the caller's loop edges
+ *   alone (the odometry chain is never discounted: it keeps the graph connected); loop_verdict_out (2 m doubles or NULL).
+ *   lsa_slam_run_pose_graph_optimization_robust: lsa_slam_run_pose_graph_optimization with prior_loss on the GPS priors;
+ *   fix_verdict_out (2 G doubles or NULL): {chi2, weight} per fix, {0, -1} for a fix that matched no pose.  Refusals, `apply`,
+ *   "PoseGraphSeconds" and the scratch context as in those calls, which forward here with robust = init. */
+#define LSA_PGO_LOSS_NONE 0
+#define LSA_PGO_LOSS_HUBER 1
+#define LSA_PGO_LOSS_GEMAN_MCCLURE 2
+#define LSA_PGO_LOSS_TUKEY 3
+typedef struct lsa_pgo_robust_t
+{
+  int32_t edge_loss, prior_loss;
+  double edge_scale, prior_scale;
+} lsa_pgo_robust_t;
+void lsa_pgo_robust_init(lsa_pgo_robust_t* robust);
+int lsa_pgo_robust_rho_host(int loss, double scale, double s, double* rho_out, double* w_out);
+int lsa_pgo_linearize_robust_host(const double* poses16, int n, const lsa_pgo_edge_t* edges, int m, const uint8_t* edge_mask, const lsa_pgo_robust_t* robust, double* e_out,
+                                  double* blocks_out, double* chi2_out, double* rho_out, double* w_out);
+int lsa_pgo_linearize_robust(lsa_ctx* ctx, const double* poses16, int n, const lsa_pgo_edge_t* edges, int m, const uint8_t* edge_mask, const lsa_pgo_robust_t* robust,
+                             double* e_out, double* blocks_out, double* chi2_out, double* rho_out, double* w_out);
+int lsa_pgo_linearize_robust_priors_host(const double* poses16, int n, const lsa_pgo_prior_t* priors, int k, const double* offset16, const lsa_pgo_robust_t* robust,
+                                         double* e_out, double* blocks_out, double* chi2_out, double* rho_out, double* w_out);
+int lsa_pgo_linearize_robust_priors(lsa_ctx* ctx, const double* poses16, int n, const lsa_pgo_prior_t* priors, int k, const double* offset16, const lsa_pgo_robust_t* robust,
+                                    double* e_out, double* blocks_out, double* chi2_out, double* rho_out, double* w_out);
+int lsa_pgo_solve_robust_host(const double* poses16, int n, const uint8_t* fixed, const lsa_pgo_edge_t* edges, int m, const uint8_t* edge_mask, const lsa_pgo_prior_t* priors,
+                              int k, const double* offset16, const lsa_pgo_params_t* params, const lsa_pgo_robust_t* robust, double* poses_out, lsa_pgo_result_t* result,
+                              double* edge_verdict_out, double* prior_verdict_out);
+int lsa_pgo_solve_robust(lsa_ctx* ctx, const double* poses16, int n, const uint8_t* fixed, const lsa_pgo_edge_t* edges, int m, const uint8_t* edge_mask,
+                         const lsa_pgo_prior_t* priors, int k, const double* offset16, const lsa_pgo_params_t* params, const lsa_pgo_robust_t* robust, double* poses_out,
+                         lsa_pgo_result_t* result, double* edge_verdict_out, double* prior_verdict_out);
+int lsa_slam_optimize_logged_trajectory_robust(lsa_slam* s, const lsa_pgo_edge_t* loop_edges, int m, const lsa_pgo_params_t* params, const lsa_pgo_robust_t* robust,
+                                               double* poses17_out, int capacity, lsa_pgo_result_t* result, double* loop_verdict_out);
+int lsa_slam_run_pose_graph_optimization_robust(lsa_slam* s, const double* gps_times, const double* gps_xyz, const double* gps_cov9, int G, double* gps_to_sensor16,
+                                                double time_offset, const lsa_pgo_params_t* params, const lsa_pgo_robust_t* robust, double* poses17_out, int capacity,
+                                                lsa_pgo_result_t* result, double* fix_verdict_out);
 
 /* ---- the rolling voxel map (host) ---------------------------
  * LidarSlam::RollingGrid -- slam_lib/include/LidarSlam/RollingGrid.h:63-212,

@@ -317,6 +317,16 @@ SIGNATURES = {
     "lsa_gps_match_trajectory": (i32, [vp, i32, vp, i32, f64, f64, vp]),
     "lsa_trajectory_alignment": (i32, [vp, vp, i32, vp]),
     "lsa_slam_run_pose_graph_optimization": (i32, [vp, vp, vp, vp, i32, vp, f64, vp, vp, i32, vp]),
+    "lsa_pgo_robust_init": (None, [vp]),
+    "lsa_pgo_robust_rho_host": (i32, [i32, f64, f64, vp, vp]),
+    "lsa_pgo_linearize_robust_host": (i32, [vp, i32, vp, i32, vp, vp, vp, vp, vp, vp, vp]),
+    "lsa_pgo_linearize_robust": (i32, [vp, vp, i32, vp, i32, vp, vp, vp, vp, vp, vp, vp]),
+    "lsa_pgo_linearize_robust_priors_host": (i32, [vp, i32, vp, i32, vp, vp, vp, vp, vp, vp, vp]),
+    "lsa_pgo_linearize_robust_priors": (i32, [vp, vp, i32, vp, i32, vp, vp, vp, vp, vp, vp, vp]),
+    "lsa_pgo_solve_robust_host": (i32, [vp, i32, vp, vp, i32, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp]),
+    "lsa_pgo_solve_robust": (i32, [vp, vp, i32, vp, vp, i32, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp]),
+    "lsa_slam_optimize_logged_trajectory_robust": (i32, [vp, vp, i32, vp, vp, vp, i32, vp, vp]),
+    "lsa_slam_run_pose_graph_optimization_robust": (i32, [vp, vp, vp, vp, i32, vp, f64, vp, vp, vp, i32, vp, vp]),
     # ---- host maps
     "lsa_rolling_grid_create": (vp, []),
     "lsa_rolling_grid_destroy": (None, [vp]),

@@ -13,6 +13,8 @@ PGO_EDGE_BLOCK = 120  # doubles of an edge's block record: Haa[36] Hab[36] Hbb[3
 PGO_PRIOR_DTYPE = np.dtype([("pose", np.int32), ("reserved", np.int32), ("position", np.float64, (3,)), ("information", np.float64, (9,))])
 PGO_PRIOR_BLOCK = 42  # doubles of a prior's block record: Haa[36] ga[6]
 PGO_MAX_ITERATIONS, PGO_GRADIENT, PGO_STEP, PGO_COST, PGO_LAMBDA_CEILING, PGO_LINEAR_SOLVER_FAILED = range(6)
+# LSA_PGO_LOSS_*: the robust losses of lidarslam_amd/csrc/lsa_pose_graph.h (ROBUST LOSS)
+PGO_LOSS_NONE, PGO_LOSS_HUBER, PGO_LOSS_GEMAN_MCCLURE, PGO_LOSS_TUKEY = range(4)
 
 
 class PoseGraphParams(C.Structure):
@@ -33,6 +35,21 @@ class PoseGraphParams(C.Structure):
                 v = (C.c_double * 6)(*[float(a) for a in v])
             elif k not in dict(self._fields_):
                 raise TypeError(f"PoseGraphParams has no field {k!r}")
+            setattr(self, k, v)
+
+
+class PoseGraphRobust(C.Structure):
+    """lsa_pgo_robust_t: edge_loss / edge_scale act on the masked edges, prior_loss / prior_scale on every prior (PGO_LOSS_*,
+    scales in sigmas); the defaults are lsa_pgo_robust_init's: no loss, scale 1."""
+
+    _fields_ = [("edge_loss", C.c_int32), ("prior_loss", C.c_int32), ("edge_scale", C.c_double), ("prior_scale", C.c_double)]
+
+    def __init__(self, **kw):
+        super().__init__()
+        lib().lsa_pgo_robust_init(C.byref(self))
+        for k, v in kw.items():
+            if k not in dict(self._fields_):
+                raise TypeError(f"PoseGraphRobust has no field {k!r}")
             setattr(self, k, v)
 
 
@@ -143,6 +160,140 @@ def pose_graph_solve(poses, fixed, edges, ctx=None, params=None, priors=None, of
 def pose_graph_solve_host(poses, fixed, edges, params=None, priors=None, offset=None, **kw):
     """pose_graph_solve without a device."""
     return pose_graph_solve(poses, fixed, edges, None, params, priors, offset, **kw)
+
+
+def _pgo_mask(mask, m, what):
+    """the edge mask of a robust call: None (every edge), or m flags"""
+    if mask is None:
+        return None
+    f = np.ascontiguousarray(np.asarray(mask).astype(np.uint8).reshape(-1))
+    if f.size != m:
+        raise _error(what, E_ARG, "as many mask flags as edges")
+    return f
+
+
+def _pgo_robust(robust, what):
+    if not isinstance(robust, PoseGraphRobust):
+        raise _error(what, E_ARG, "robust must be a PoseGraphRobust")
+    return robust
+
+
+def pose_graph_robust_rho(loss, scale, s):
+    """(rho(s), w = rho'(s)) of one loss (PGO_LOSS_*) at `scale` sigmas: the function of lsa_pose_graph.h's ROBUST LOSS on its
+    own (lsa_pgo_robust_rho_host); s a number or an array."""
+    flat = np.ascontiguousarray(np.asarray(s, np.float64)).reshape(-1)
+    rho, w = np.zeros(flat.size), np.zeros(flat.size)
+    a, b = C.c_double(), C.c_double()
+    for i, v in enumerate(flat):
+        rc = lib().lsa_pgo_robust_rho_host(int(loss), float(scale), float(v), C.byref(a), C.byref(b))
+        if rc < 0:
+            raise _error("lsa_pgo_robust_rho_host", rc, "a loss outside 0..3, or a scale that is not finite and positive")
+        rho[i], w[i] = a.value, b.value
+    if np.ndim(s) == 0:
+        return float(rho[0]), float(w[0])
+    return rho.reshape(np.shape(s)), w.reshape(np.shape(s))
+
+
+def pose_graph_solve_robust(poses, fixed, edges, robust, mask=None, ctx=None, params=None, priors=None, offset=None, **kw):
+    """pose_graph_solve under robust losses (lsa_pgo_solve_robust[_host]): robust a PoseGraphRobust; mask (m,) flags selecting
+    the edges edge_loss acts on (None: every edge); prior_loss acts on every prior.
+    -> (poses (n, 4, 4), PoseGraphResult, edge_verdict (m, 2), prior_verdict (k, 2)): per constraint {chi2, weight} at the
+    returned poses, weight 1 for a constraint that is not robustified."""
+    name = "lsa_pgo_solve_robust" + ("_host" if ctx is None else "")
+    rb = _pgo_robust(robust, name)
+    p = params if params is not None else PoseGraphParams(**kw)
+    r = PoseGraphResultStruct()
+    P, f, E = _pgo_graph(poses, fixed, edges)
+    if f is None:
+        raise _error(name, E_ARG, "fixed flags are needed")
+    mk = _pgo_mask(mask, E.size, name)
+    pa, keep = _pgo_priors(priors, offset)
+    out = np.zeros((P.shape[0], 4, 4))
+    ev, pv = np.zeros((E.size, 2)), np.zeros((pa[1], 2))
+    L = lib()
+    args = ([] if ctx is None else [ctx.h]) + [ptr(P), P.shape[0], ptr(f), ptr(E) if E.size else None, E.size, None if mk is None else ptr(mk)] + pa + [
+        C.byref(p), C.byref(rb), ptr(out), C.byref(r), ptr(ev) if ev.size else None, ptr(pv) if pv.size else None]
+    rc = getattr(L, name)(*args)
+    if rc < 0:
+        raise _error(name, rc, "the graph, the parameters or the losses are outside the definition" if ctx is None else L.lsa_last_error(ctx.h).decode())
+    return out, PoseGraphResult(r), ev, pv
+
+
+def pose_graph_linearize_robust(poses, edges, robust, mask=None, ctx=None):
+    """-> e (m, 6), blocks (m, 120) (each record times its weight), chi2 (m,) (raw), rho (m,), w (m,): k_pgo_linearize_robust
+    with a Context, its host twin without."""
+    name = "lsa_pgo_linearize_robust" + ("_host" if ctx is None else "")
+    rb = _pgo_robust(robust, name)
+    P, _, E = _pgo_graph(poses, None, edges)
+    mk = _pgo_mask(mask, E.size, name)
+    m = E.size
+    outs = [np.zeros((m, 6)), np.zeros((m, PGO_EDGE_BLOCK)), np.zeros(m), np.zeros(m), np.zeros(m)]
+    L = lib()
+    args = ([] if ctx is None else [ctx.h]) + [ptr(P), P.shape[0], ptr(E) if m else None, m, None if mk is None else ptr(mk), C.byref(rb)] + [ptr(o) for o in outs]
+    rc = getattr(L, name)(*args)
+    if rc < 0:
+        raise _error(name, rc, L.lsa_last_error(ctx.h).decode() if ctx is not None else "the graph or the losses are outside the definition")
+    return tuple(outs)
+
+
+def pose_graph_linearize_priors_robust(poses, priors, robust, offset=None, ctx=None):
+    """-> e (k, 3), blocks (k, 42) (each record times its weight), chi2 (k,), rho (k,), w (k,) of the position priors under
+    robust.prior_loss: k_pgo_linearize_priors_robust with a Context, its host twin without."""
+    name = "lsa_pgo_linearize_robust_priors" + ("_host" if ctx is None else "")
+    rb = _pgo_robust(robust, name)
+    P = np.ascontiguousarray(np.asarray(poses, np.float64).reshape(-1, 16))
+    pa, keep = _pgo_priors(priors, offset)
+    k = pa[1]
+    outs = [np.zeros((k, 3)), np.zeros((k, PGO_PRIOR_BLOCK)), np.zeros(k), np.zeros(k), np.zeros(k)]
+    L = lib()
+    rc = getattr(L, name)(*([] if ctx is None else [ctx.h]), ptr(P), P.shape[0], *pa, C.byref(rb), *[ptr(o) for o in outs])
+    if rc < 0:
+        raise _error(name, rc, L.lsa_last_error(ctx.h).decode() if ctx is not None else "a prior or the losses are outside the definition")
+    return tuple(outs)
+
+
+def optimize_trajectory_robust(slam, loop_edges, robust, apply=False, params=None, **kw):
+    """Slam.optimize_trajectory under robust.edge_loss on the caller's loop edges (lsa_slam_optimize_logged_trajectory_robust);
+    the odometry chain is never discounted.  -> (poses (n, 4, 4), times (n,), PoseGraphResult, loop_verdict (m, 2) =
+    {chi2, weight} per loop edge at the returned poses)"""
+    name = "lsa_slam_optimize_logged_trajectory_robust"
+    rb = _pgo_robust(robust, name)
+    p = params if params is not None else PoseGraphParams(**kw)
+    p.apply = int(bool(apply))
+    E = pose_graph_edges(loop_edges)
+    n = slam._check(slam.L.lsa_slam_logged_frames(slam.h), "lsa_slam_logged_frames")
+    rows = np.zeros((max(n, 1), 17))
+    verdict = np.zeros((E.size, 2))
+    r = PoseGraphResultStruct()
+    got = slam._check(getattr(slam.L, name)(slam.h, ptr(E) if E.size else None, E.size, C.byref(p), C.byref(rb), ptr(rows), rows.shape[0], C.byref(r),
+                                            ptr(verdict) if E.size else None), name)
+    return rows[:got, :16].reshape(-1, 4, 4).copy(), rows[:got, 16].copy(), PoseGraphResult(r), verdict
+
+
+def run_pose_graph_optimization_robust(slam, gps_times, gps_xyz, gps_cov, robust, gps_to_sensor=None, apply=True, time_offset=0.0, params=None, **kw):
+    """Slam.run_pose_graph_optimization under robust.prior_loss on the GPS priors (lsa_slam_run_pose_graph_optimization_robust).
+    -> (poses (n, 4, 4), times (n,), gps_to_sensor (4, 4), PoseGraphResult, matches (G,), fix_verdict (G, 2) = {chi2, weight}
+    per fix at the returned poses, weight -1 for a fix that matched no pose)"""
+    name = "lsa_slam_run_pose_graph_optimization_robust"
+    rb = _pgo_robust(robust, name)
+    if params is None:
+        kw.setdefault("odometry_information", 1)
+    p = params if params is not None else PoseGraphParams(**kw)
+    p.apply = int(bool(apply))
+    t = np.ascontiguousarray(np.asarray(gps_times, np.float64).reshape(-1))
+    x = np.ascontiguousarray(np.asarray(gps_xyz, np.float64).reshape(-1, 3))
+    c = np.ascontiguousarray(np.asarray(gps_cov, np.float64).reshape(-1, 9))
+    if not (x.shape[0] == c.shape[0] == t.size):
+        raise _error(name, E_ARG, "as many positions and covariances as times")
+    cal = np.ascontiguousarray(np.asarray(np.eye(4) if gps_to_sensor is None else gps_to_sensor, np.float64).reshape(4, 4).copy())
+    n = slam._check(slam.L.lsa_slam_logged_frames(slam.h), "lsa_slam_logged_frames")
+    rows = np.zeros((max(n, 1), 17))
+    verdict = np.zeros((t.size, 2))
+    r = PoseGraphResultStruct()
+    got = slam._check(getattr(slam.L, name)(slam.h, ptr(t) if t.size else None, ptr(x) if t.size else None, ptr(c) if t.size else None, t.size, ptr(cal), float(time_offset),
+                                            C.byref(p), C.byref(rb), ptr(rows), rows.shape[0], C.byref(r), ptr(verdict) if t.size else None), name)
+    times = rows[:got, 16].copy()
+    return rows[:got, :16].reshape(-1, 4, 4).copy(), times, cal, PoseGraphResult(r), gps_match_trajectory(times, t, time_offset), verdict
 
 
 def pose_graph_linearize(poses, edges, ctx=None):

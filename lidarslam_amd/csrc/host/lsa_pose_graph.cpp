@@ -79,11 +79,21 @@ double Dot(const std::vector<double>& a, const std::vector<double>& b)
   return s;
 }
 
+// the losses of a solve and the edges they act on
+struct Robust
+{
+  lsa_pgo_robust_t r{LSA_PGO_LOSS_NONE, LSA_PGO_LOSS_NONE, 1., 1.};
+  const unsigned char* mask = nullptr;  // NULL: every edge
+  int EdgeLoss(int k) const { return (!mask || mask[k]) ? r.edge_loss : LSA_PGO_LOSS_NONE; }
+};
+
 struct System
 {
-  std::vector<double> e, blocks, chi2, pe, pblocks, D, dg, g, L, U;  // chi2: the m edge values, then the k prior values
+  std::vector<double> e, blocks, chi2, rho, w, pe, pblocks, D, dg, g, L, U;  // chi2, rho, w: the m edge values, then the k prior values
   void Size(int n, int m, int k = 0)
   {
+    rho.resize(static_cast<size_t>(m) + static_cast<size_t>(k));
+    w.resize(rho.size());
     e.resize(static_cast<size_t>(m) * 6);
     blocks.resize(static_cast<size_t>(m) * pg::kEdgeBlock);
     chi2.resize(static_cast<size_t>(m) + static_cast<size_t>(k));
@@ -95,19 +105,38 @@ struct System
     dg.resize(static_cast<size_t>(n) * 6);
     g.resize(dg.size());
   }
-  double Linearize(const double* poses, const lsa_pgo_edge_t* edges, int m, const lsa_pgo_prior_t* priors = nullptr, int np = 0, const pg::Pose* O = nullptr)
+  // F = 1/2 sum rho; a constraint that is not robustified goes through the plain functions (rho = chi2, w = 1)
+  double Linearize(const double* poses, const lsa_pgo_edge_t* edges, int m, const lsa_pgo_prior_t* priors = nullptr, int np = 0, const pg::Pose* O = nullptr,
+                   const Robust& rb = Robust())
   {
     double F = 0.;
     for (int k = 0; k < m; ++k)
     {
-      pg::linearize_edge(poses, edges[k], &e[6 * static_cast<size_t>(k)], &blocks[static_cast<size_t>(k) * pg::kEdgeBlock], &chi2[static_cast<size_t>(k)]);
-      F += chi2[static_cast<size_t>(k)];
+      const size_t at = static_cast<size_t>(k);
+      double* blk = &blocks[at * pg::kEdgeBlock];
+      if (rb.EdgeLoss(k) == LSA_PGO_LOSS_NONE)
+      {
+        pg::linearize_edge(poses, edges[k], &e[6 * at], blk, &chi2[at]);
+        rho[at] = chi2[at];
+        w[at] = 1.;
+      }
+      else
+        pg::linearize_edge_robust(poses, edges[k], rb.r.edge_loss, rb.r.edge_scale, &e[6 * at], blk, &chi2[at], &rho[at], &w[at]);
+      F += rho[at];
     }
     for (int k = 0; k < np; ++k)
     {
       const size_t at = static_cast<size_t>(m) + static_cast<size_t>(k);
-      pg::linearize_prior(poses, priors[k], *O, &pe[3 * static_cast<size_t>(k)], &pblocks[static_cast<size_t>(k) * pg::kPriorBlock], &chi2[at]);
-      F += chi2[at];
+      double* blk = &pblocks[static_cast<size_t>(k) * pg::kPriorBlock];
+      if (rb.r.prior_loss == LSA_PGO_LOSS_NONE)
+      {
+        pg::linearize_prior(poses, priors[k], *O, &pe[3 * static_cast<size_t>(k)], blk, &chi2[at]);
+        rho[at] = chi2[at];
+        w[at] = 1.;
+      }
+      else
+        pg::linearize_prior_robust(poses, priors[k], *O, rb.r.prior_loss, rb.r.prior_scale, &pe[3 * static_cast<size_t>(k)], blk, &chi2[at], &rho[at], &w[at]);
+      F += rho[at];
     }
     return 0.5 * F;
   }
@@ -248,12 +277,16 @@ bool PgoTridiagonalSolve(int n, const double* D, const double* L, const double* 
 }
 
 int PgoSolve(const double* poses16, int n, const unsigned char* fixed, const lsa_pgo_edge_t* edges, int m, const lsa_pgo_prior_t* priors, int np, const double* offset16,
-             const lsa_pgo_params_t* params, double* poses_out, lsa_pgo_result_t* result, std::string* why)
+             const lsa_pgo_params_t* params, double* poses_out, lsa_pgo_result_t* result, std::string* why, const unsigned char* edgeMask, const lsa_pgo_robust_t* robust,
+             double* edgeVerdict, double* priorVerdict)
 {
   lsa_pgo_params_t p;
   lsa_pgo_params_init(&p);
   if (params) p = *params;
-  if (!poses_out || !result || !pg::params_ok(p))
+  Robust rb;
+  rb.mask = edgeMask;
+  if (robust) rb.r = *robust;
+  if (!poses_out || !result || !pg::params_ok(p) || !pg::robust_ok(rb.r))
   {
     if (why) *why = "bad argument or parameters out of limits";
     return LSA_E_ARG;
@@ -270,7 +303,7 @@ int PgoSolve(const double* poses16, int n, const unsigned char* fixed, const lsa
   std::vector<double> delta(nv), r(nv), z(nv), pv(nv), q(nv), zeros;
   lsa_pgo_result_t R;
   std::memset(&R, 0, sizeof(R));
-  double F = S.Linearize(x.data(), edges, m, priors, np, &O);
+  double F = S.Linearize(x.data(), edges, m, priors, np, &O, rb);
   R.initial_cost = F;
   double lambda = p.initial_lambda;
   int term = LSA_PGO_MAX_ITERATIONS;
@@ -325,15 +358,16 @@ int PgoSolve(const double* poses16, int n, const unsigned char* fixed, const lsa
     model *= 0.5;
     for (int i = 0; i < n; ++i) pg::store(pg::retract(pg::load(&x[16 * static_cast<size_t>(i)]), &delta[6 * static_cast<size_t>(i)]), &cand[16 * static_cast<size_t>(i)]);
     double Fn = 0.;
-    for (int k = 0; k < m; ++k) Fn += pg::edge_chi2(cand.data(), edges[k]);
-    for (int k = 0; k < np; ++k) Fn += pg::prior_chi2(cand.data(), priors[k], O);
+    double raw, wt;
+    for (int k = 0; k < m; ++k) Fn += pg::edge_rho(cand.data(), edges[k], rb.EdgeLoss(k), rb.r.edge_scale, &raw, &wt);
+    for (int k = 0; k < np; ++k) Fn += pg::prior_rho(cand.data(), priors[k], O, rb.r.prior_loss, rb.r.prior_scale, &raw, &wt);
     Fn *= 0.5;
     if (model > 0. && pg::finite_d(Fn) && F - Fn > 0.)
     {
       const double dec = F - Fn;
       x = cand;
       const bool small = dec <= p.cost_tolerance * F;
-      F = S.Linearize(x.data(), edges, m, priors, np, &O);
+      F = S.Linearize(x.data(), edges, m, priors, np, &O, rb);
       ++R.accepted_steps;
       R.largest_step = step > R.largest_step ? step : R.largest_step;
       lambda = lambda * p.lambda_shrink > p.lambda_min ? lambda * p.lambda_shrink : p.lambda_min;
@@ -352,6 +386,10 @@ int PgoSolve(const double* poses16, int n, const unsigned char* fixed, const lsa
   R.final_lambda = lambda;
   R.termination = term;
   R.message = PgoMessage(term);
+  // the verdicts: one more evaluation at the returned poses
+  for (int k = 0; edgeVerdict && k < m; ++k) (void)pg::edge_rho(x.data(), edges[k], rb.EdgeLoss(k), rb.r.edge_scale, edgeVerdict + 2 * static_cast<size_t>(k), edgeVerdict + 2 * static_cast<size_t>(k) + 1);
+  for (int k = 0; priorVerdict && k < np; ++k)
+    (void)pg::prior_rho(x.data(), priors[k], O, rb.r.prior_loss, rb.r.prior_scale, priorVerdict + 2 * static_cast<size_t>(k), priorVerdict + 2 * static_cast<size_t>(k) + 1);
   std::memcpy(poses_out, x.data(), x.size() * sizeof(double));
   *result = R;
   return LSA_OK;
@@ -384,13 +422,70 @@ void lsa_pgo_params_init(lsa_pgo_params_t* p)
 int lsa_pgo_solve_host(const double* poses16, int n, const uint8_t* fixed, const lsa_pgo_edge_t* edges, int m, const lsa_pgo_params_t* params, double* poses_out,
                        lsa_pgo_result_t* result)
 {
-  return host::PgoSolve(poses16, n, fixed, edges, m, nullptr, 0, nullptr, params, poses_out, result, nullptr);
+  return lsa_pgo_solve_priors_host(poses16, n, fixed, edges, m, nullptr, 0, nullptr, params, poses_out, result);
 }
 
 int lsa_pgo_solve_priors_host(const double* poses16, int n, const uint8_t* fixed, const lsa_pgo_edge_t* edges, int m, const lsa_pgo_prior_t* priors, int k,
                               const double* offset16, const lsa_pgo_params_t* params, double* poses_out, lsa_pgo_result_t* result)
 {
-  return host::PgoSolve(poses16, n, fixed, edges, m, priors, k, offset16, params, poses_out, result, nullptr);
+  return lsa_pgo_solve_robust_host(poses16, n, fixed, edges, m, nullptr, priors, k, offset16, params, nullptr, poses_out, result, nullptr, nullptr);
+}
+
+void lsa_pgo_robust_init(lsa_pgo_robust_t* r)
+{
+  if (!r) return;
+  std::memset(r, 0, sizeof(*r));
+  r->edge_loss = LSA_PGO_LOSS_NONE;
+  r->prior_loss = LSA_PGO_LOSS_NONE;
+  r->edge_scale = 1.;
+  r->prior_scale = 1.;
+}
+
+int lsa_pgo_robust_rho_host(int loss, double scale, double s, double* rho_out, double* w_out)
+{
+  lsa_pgo_robust_t r;
+  lsa_pgo_robust_init(&r);
+  r.edge_loss = loss;
+  r.edge_scale = scale;
+  if (!rho_out || !w_out || !pg::robust_ok(r)) return LSA_E_ARG;
+  pg::robust_rho(loss, scale, s, rho_out, w_out);
+  return LSA_OK;
+}
+
+int lsa_pgo_solve_robust_host(const double* poses16, int n, const uint8_t* fixed, const lsa_pgo_edge_t* edges, int m, const uint8_t* edge_mask, const lsa_pgo_prior_t* priors,
+                              int k, const double* offset16, const lsa_pgo_params_t* params, const lsa_pgo_robust_t* robust, double* poses_out, lsa_pgo_result_t* result,
+                              double* edge_verdict_out, double* prior_verdict_out)
+{
+  return host::PgoSolve(poses16, n, fixed, edges, m, priors, k, offset16, params, poses_out, result, nullptr, edge_mask, robust, edge_verdict_out, prior_verdict_out);
+}
+
+int lsa_pgo_linearize_robust_host(const double* poses16, int n, const lsa_pgo_edge_t* edges, int m, const uint8_t* edge_mask, const lsa_pgo_robust_t* robust, double* e_out,
+                                  double* blocks_out, double* chi2_out, double* rho_out, double* w_out)
+{
+  host::Robust rb;
+  rb.mask = edge_mask;
+  if (robust) rb.r = *robust;
+  if (!e_out || !blocks_out || !chi2_out || !rho_out || !w_out || !pg::robust_ok(rb.r)) return LSA_E_ARG;
+  if (const int rc = host::PgoCheckEdges(poses16, n, edges, m, nullptr); rc != LSA_OK) return rc;
+  for (int a = 0; a < m; ++a)
+    pg::linearize_edge_robust(poses16, edges[a], rb.EdgeLoss(a), rb.r.edge_scale, e_out + 6 * static_cast<size_t>(a), blocks_out + static_cast<size_t>(a) * pg::kEdgeBlock,
+                              chi2_out + a, rho_out + a, w_out + a);
+  return LSA_OK;
+}
+
+int lsa_pgo_linearize_robust_priors_host(const double* poses16, int n, const lsa_pgo_prior_t* priors, int k, const double* offset16, const lsa_pgo_robust_t* robust,
+                                         double* e_out, double* blocks_out, double* chi2_out, double* rho_out, double* w_out)
+{
+  host::Robust rb;
+  if (robust) rb.r = *robust;
+  if (!e_out || !blocks_out || !chi2_out || !rho_out || !w_out || !pg::robust_ok(rb.r)) return LSA_E_ARG;
+  if (const int rc = host::PgoCheckPriors(poses16, n, priors, k, offset16, nullptr); rc != LSA_OK) return rc;
+  if (k == 0) return LSA_OK;
+  const pg::Pose O = pg::load(offset16);
+  for (int a = 0; a < k; ++a)
+    pg::linearize_prior_robust(poses16, priors[a], O, rb.r.prior_loss, rb.r.prior_scale, e_out + 3 * static_cast<size_t>(a),
+                               blocks_out + static_cast<size_t>(a) * pg::kPriorBlock, chi2_out + a, rho_out + a, w_out + a);
+  return LSA_OK;
 }
 
 int lsa_pgo_linearize_priors_host(const double* poses16, int n, const lsa_pgo_prior_t* priors, int k, const double* offset16, double* e_out, double* blocks_out,

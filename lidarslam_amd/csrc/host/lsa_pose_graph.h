@@ -31,6 +31,7 @@ int PgoBuild(const double* poses16, int n, const unsigned char* fixed, const lsa
 bool PgoTridiagonalSolve(int n, const double* D, const double* L, const double* U, const double* b, double* x);
 const char* PgoMessage(int termination);
 int PgoSolve(const double* poses16, int n, const unsigned char* fixed, const lsa_pgo_edge_t* edges, int m, const lsa_pgo_prior_t* priors, int k, const double* offset16,
-             const lsa_pgo_params_t* params, double* poses_out, lsa_pgo_result_t* result, std::string* why);
+             const lsa_pgo_params_t* params, double* poses_out, lsa_pgo_result_t* result, std::string* why, const unsigned char* edgeMask = nullptr,
+             const lsa_pgo_robust_t* robust = nullptr, double* edgeVerdict = nullptr, double* priorVerdict = nullptr);  // the losses: ../lsa_pose_graph.h ROBUST LOSS
 }  // namespace host
 }  // namespace lsa

@@ -347,14 +347,29 @@ int lsa_slam_optimize_logged_trajectory(lsa_slam* s, const lsa_pgo_edge_t* loop_
                                         lsa_pgo_result_t* result)
 {
   if (!s) return LSA_E_ARG;
-  return s->core.OptimizeLoggedTrajectory(loop_edges, m, params, poses17_out, capacity, result);
+  return lsa_slam_optimize_logged_trajectory_robust(s, loop_edges, m, params, nullptr, poses17_out, capacity, result, nullptr);
+}
+
+int lsa_slam_optimize_logged_trajectory_robust(lsa_slam* s, const lsa_pgo_edge_t* loop_edges, int m, const lsa_pgo_params_t* params, const lsa_pgo_robust_t* robust,
+                                               double* poses17_out, int capacity, lsa_pgo_result_t* result, double* loop_verdict_out)
+{
+  if (!s) return LSA_E_ARG;
+  return s->core.OptimizeLoggedTrajectory(loop_edges, m, params, poses17_out, capacity, result, robust, loop_verdict_out);
 }
 
 int lsa_slam_run_pose_graph_optimization(lsa_slam* s, const double* gps_times, const double* gps_xyz, const double* gps_cov9, int G, double* gps_to_sensor16,
                                          double time_offset, const lsa_pgo_params_t* params, double* poses17_out, int capacity, lsa_pgo_result_t* result)
 {
   if (!s) return LSA_E_ARG;
-  return s->core.RunPoseGraphOptimization(gps_times, gps_xyz, gps_cov9, G, gps_to_sensor16, time_offset, params, poses17_out, capacity, result);
+  return lsa_slam_run_pose_graph_optimization_robust(s, gps_times, gps_xyz, gps_cov9, G, gps_to_sensor16, time_offset, params, nullptr, poses17_out, capacity, result, nullptr);
+}
+
+int lsa_slam_run_pose_graph_optimization_robust(lsa_slam* s, const double* gps_times, const double* gps_xyz, const double* gps_cov9, int G, double* gps_to_sensor16,
+                                                double time_offset, const lsa_pgo_params_t* params, const lsa_pgo_robust_t* robust, double* poses17_out, int capacity,
+                                                lsa_pgo_result_t* result, double* fix_verdict_out)
+{
+  if (!s) return LSA_E_ARG;
+  return s->core.RunPoseGraphOptimization(gps_times, gps_xyz, gps_cov9, G, gps_to_sensor16, time_offset, params, poses17_out, capacity, result, robust, fix_verdict_out);
 }
 
 int lsa_loop_closure_candidate(const double* poses17, int n, int query, double min_travelled, double max_distance)

@@ -105,12 +105,15 @@ public:
   // Pose-graph optimization of the logged trajectory with the caller's loop edges (lsa_slam_optimize_logged_trajectory in
   // lidarslam_amd.h): the solve runs on the scratch context; with params->apply the result goes through
   // SetTrajectoryAndRebuildMaps, without it nothing of the frame path is touched.  Returns the number of poses.
-  int OptimizeLoggedTrajectory(const lsa_pgo_edge_t* loopEdges, int m, const lsa_pgo_params_t* params, double* poses17, int capacity, lsa_pgo_result_t* result);
+  // robust: the loss on the caller's loop edges (NULL: none; the odometry chain is never discounted); loopVerdict: 2 m doubles or NULL
+  int OptimizeLoggedTrajectory(const lsa_pgo_edge_t* loopEdges, int m, const lsa_pgo_params_t* params, double* poses17, int capacity, lsa_pgo_result_t* result,
+                               const lsa_pgo_robust_t* robust = nullptr, double* loopVerdict = nullptr);
   // Slam::RunPoseGraphOptimization (lsa_slam_run_pose_graph_optimization in lidarslam_amd.h): GPS fixes matched to the logged
   // poses by time become position priors on a graph of free poses; solved on the scratch context from the track laid onto
   // the fixes, brought back onto logged pose 0.  gpsToSensor16: in the calibration, out the optimized pose 0 in the GPS frame.
   int RunPoseGraphOptimization(const double* gpsTimes, const double* gpsXyz, const double* gpsCov9, int G, double* gpsToSensor16, double timeOffset,
-                               const lsa_pgo_params_t* params, double* poses17, int capacity, lsa_pgo_result_t* result);
+                               const lsa_pgo_params_t* params, double* poses17, int capacity, lsa_pgo_result_t* result, const lsa_pgo_robust_t* robust = nullptr,
+                               double* fixVerdict = nullptr);  // robust: the loss on the GPS priors; fixVerdict: 2 G doubles or NULL, weight -1 = unmatched
   int LoggedFrames() const;
   int GetLoggedKeypoints(int frame, int type, std::vector<lsa_point_t>& out);
   void HintNextStoredFrame(int slot) { NextStoredSlot = slot; }

@@ -279,7 +279,8 @@ int SlamCore::PoseGraphSolve(const std::string& who, const PoseGraphProblem& pb,
   return n;
 }
 
-int SlamCore::OptimizeLoggedTrajectory(const lsa_pgo_edge_t* loopEdges, int m,const lsa_pgo_params_t* params, double* poses17, int capacity, lsa_pgo_result_t* result)
+int SlamCore::OptimizeLoggedTrajectory(const lsa_pgo_edge_t* loopEdges, int m,const lsa_pgo_params_t* params, double* poses17, int capacity, lsa_pgo_result_t* result,
+                                       const lsa_pgo_robust_t* robust, double* loopVerdict)
 {
   if (!Ctx) return LSA_E_NO_DEVICE;
   const std::string who = "OptimizeLoggedTrajectory: ";
@@ -287,6 +288,7 @@ int SlamCore::OptimizeLoggedTrajectory(const lsa_pgo_edge_t* loopEdges, int m,co
   PoseGraphProblem pb;
   const int n = PoseGraphBegin(who, params, LogTrajectory.size() < 2 ? "at least two logged poses" : "", capacity, pb);
   if (n < 0) return n;
+  if (robust && !pg::robust_ok(*robust)) { LastError = who + "a loss outside 0..3, or a scale that is not finite and positive"; return LSA_E_ARG; }
   for (int k = 0; k < m; ++k)
     if (loopEdges[k].from < 0 || loopEdges[k].from >= n || loopEdges[k].to < 0 || loopEdges[k].to >= n || loopEdges[k].from == loopEdges[k].to)
     {
@@ -296,15 +298,23 @@ int SlamCore::OptimizeLoggedTrajectory(const lsa_pgo_edge_t* loopEdges, int m,co
   if (const int rc = PoseGraphEdges(who, loopEdges, m, pb); rc != LSA_OK) return rc;
   std::vector<unsigned char> fixed(static_cast<size_t>(n), 0);
   fixed[0] = 1;
+  // the losses act on the caller's loop edges alone: the odometry chain keeps the graph connected and is never discounted
+  std::vector<unsigned char> mask(pb.edges.size(), 0);
+  for (int k = 0; k < m; ++k) mask[static_cast<size_t>(n - 1 + k)] = 1;
+  std::vector<double> verdict(loopVerdict ? 2 * pb.edges.size() : 0);
   auto solve = [&](double* out, lsa_pgo_result_t* r) {
-    return lsa_pgo_solve(LoopCtx, pb.in.data(), n, fixed.data(), pb.edges.data(), static_cast<int>(pb.edges.size()), &pb.p, out, r);
+    return lsa_pgo_solve_robust(LoopCtx, pb.in.data(), n, fixed.data(), pb.edges.data(), static_cast<int>(pb.edges.size()), mask.data(), nullptr, 0, nullptr, &pb.p, robust, out, r,
+                                loopVerdict ? verdict.data() : nullptr, nullptr);
   };
-  return PoseGraphSolve(who, pb, solve, poses17, result);
+  const int rc = PoseGraphSolve(who, pb, solve, poses17, result);
+  if (rc >= 0 && loopVerdict && m > 0) std::memcpy(loopVerdict, verdict.data() + 2 * static_cast<size_t>(n - 1), 2 * static_cast<size_t>(m) * sizeof(double));
+  return rc;
 }
 
 // ---- Slam::RunPoseGraphOptimization (Slam.cxx:355-477, PoseGraphOptimization::Process): GPS positions as priors -------------
 int SlamCore::RunPoseGraphOptimization(const double* gpsTimes, const double* gpsXyz, const double* gpsCov9, int G, double* gpsToSensor16, double timeOffset,
-                                       const lsa_pgo_params_t* params, double* poses17, int capacity, lsa_pgo_result_t* result)
+                                       const lsa_pgo_params_t* params, double* poses17, int capacity, lsa_pgo_result_t* result, const lsa_pgo_robust_t* robust,
+                                       double* fixVerdict)
 {
   if (!Ctx) return LSA_E_NO_DEVICE;
   const std::string who = "RunPoseGraphOptimization: ";
@@ -315,6 +325,7 @@ int SlamCore::RunPoseGraphOptimization(const double* gpsTimes, const double* gps
   PoseGraphProblem pb;
   const int n = PoseGraphBegin(who, params, tooFew, capacity, pb);
   if (n < 0) return n;
+  if (robust && !pg::robust_ok(*robust)) { LastError = who + "a loss outside 0..3, or a scale that is not finite and positive"; return LSA_E_ARG; }
   const std::vector<double>& times = pb.times;
   for (int k = 0; k < 16; ++k)
     if (!pg::finite_d(gpsToSensor16[k])) { LastError = who + "the GPS to sensor calibration has a non-finite entry"; return LSA_E_ARG; }
@@ -364,15 +375,30 @@ int SlamCore::RunPoseGraphOptimization(const double* gpsTimes, const double* gps
   if (const int rc = PoseGraphEdges(who, nullptr, 0, pb); rc != LSA_OK) return rc;
   std::vector<double> start(pb.in.size()), opt(pb.in.size());
   std::vector<unsigned char> fixed(static_cast<size_t>(n), 0);  // every pose is free: the priors hold the graph
+  // prior_loss acts on the GPS priors; the odometry chain is never discounted
+  lsa_pgo_robust_t rb;
+  lsa_pgo_robust_init(&rb);
+  if (robust) { rb.prior_loss = robust->prior_loss; rb.prior_scale = robust->prior_scale; }
+  std::vector<double> verdict(fixVerdict ? 2 * priors.size() : 0);
   auto solve = [&](double* out, lsa_pgo_result_t* r) {
     int rc = lsa_pgo_premultiply(LoopCtx, pb.in.data(), n, W, start.data());
-    if (rc == LSA_OK) rc = lsa_pgo_solve_priors(LoopCtx, start.data(), n, fixed.data(), pb.edges.data(), n - 1, priors.data(), static_cast<int>(priors.size()), offset.m, &pb.p, opt.data(), r);
+    if (rc == LSA_OK)
+      rc = lsa_pgo_solve_robust(LoopCtx, start.data(), n, fixed.data(), pb.edges.data(), n - 1, nullptr, priors.data(), static_cast<int>(priors.size()), offset.m, &pb.p, &rb, opt.data(), r,
+                                nullptr, fixVerdict ? verdict.data() : nullptr);
     if (rc == LSA_OK) rc = lsa_pgo_reanchor(LoopCtx, opt.data(), n, out);
     return rc;
   };
   const int rc = PoseGraphSolve(who, pb, solve, poses17, result);
   if (rc < 0) return rc;
   std::memcpy(gpsToSensor16, opt.data(), 16 * sizeof(double));  // the optimized pose 0 in the GPS frame (Slam.cxx:404)
+  if (fixVerdict)
+    for (int f = 0, a = 0; f < G; ++f)
+    {
+      const bool matched = match[static_cast<size_t>(f)] >= 0;
+      fixVerdict[2 * static_cast<size_t>(f)] = matched ? verdict[2 * static_cast<size_t>(a)] : 0.;
+      fixVerdict[2 * static_cast<size_t>(f) + 1] = matched ? verdict[2 * static_cast<size_t>(a) + 1] : -1.;
+      a += matched ? 1 : 0;
+    }
   return rc;
 }
 

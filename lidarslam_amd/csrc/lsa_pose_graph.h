@@ -41,7 +41,8 @@
 // their diagonal blocks, the damping is positive); every other block is PCG's.
 //
 // THE LM LOOP (the host and the device follow this text; p = lsa_pgo_params_t)
-//   x = poses; linearize; F = 1/2 sum chi2 (the edges' values in edge order, then the priors' in prior order); F0 = F; lambda = p.initial_lambda
+//   x = poses; linearize; F = 1/2 sum rho_k (the edges' values in edge order, then the priors' in prior order; rho_k = chi2_k without a loss); F0 = F;
+//   lambda = p.initial_lambda
 //   for it = 0 .. p.max_iterations - 1:
 //     assemble at lambda;  if max |g| <= p.gradient_tolerance: GRADIENT
 //     factor T;  a block that is not SPD: LINEAR_SOLVER_FAILED (poses as they were before this iteration)
@@ -49,13 +50,35 @@
 //         q = H_lambda p; pq = p.q; not (pq > 0) or not finite: LINEAR_SOLVER_FAILED;  alpha = rz / pq;  delta += alpha p;
 //         r -= alpha q;  z = T^-1 r;  rz' = r.z;  rz' <= p.pcg_tolerance^2 rz0: done;  beta = rz' / rz;  p = z + beta p;  rz = rz'
 //       running out of iterations is no failure: LM takes the delta it has (counted in pcg_truncated)
-//     step = max |delta|;  model = 1/2 sum_k delta_k (lambda diag(H)_k delta_k - g_k);  candidate = retraction;  F' = its cost
+//     step = max |delta|;  model = 1/2 sum_k delta_k (lambda diag(H)_k delta_k - g_k);  candidate = retraction;  F' = its cost 1/2 sum rho_k
 //     accept when model > 0, F' finite and F - F' > 0 (the gain ratio (F - F') / model is positive):
 //         x = candidate; lambda = max(lambda * p.lambda_shrink, p.lambda_min); then step <= p.step_tolerance: STEP;
 //         (F - F') <= p.cost_tolerance * F: COST (both tested after the step was taken)
 //     else lambda *= p.lambda_grow;  step <= p.step_tolerance: STEP;  lambda > p.lambda_max: LAMBDA_CEILING
 //   MAX_ITERATIONS
 // Every loop is bounded by a parameter: LM by max_iterations, PCG by pcg_max_iter.
+//
+// ROBUST LOSS (lsa_pgo_robust_t).  A loss acts on s = chi2 of one constraint, the squared Mahalanobis norm above,
+// with a scale c > 0 in sigmas, c2 = c * c.  It yields the cost value rho(s) and the weight w = rho'(s).  First-order IRLS: the
+// weight alone, no second-derivative correction (g2o's rule).  No transcendental function: IEEE sqrt, *, /, + under
+// -ffp-contract=off pin the bits.  The order of operations below is part of the definition.
+//   NONE 0             rho = s                                                     w = 1; nothing is multiplied
+//   HUBER 1            s > c2:  r = sqrt(s);  rho = (2 * c) * r - c2               w = c / r
+//                      else     rho = s                                            w = 1
+//   GEMAN_MCCLURE 2    d = c2 + s;  rho = (c2 * s) / d                             q = c2 / d;  w = q * q
+//   TUKEY 3            s > c2:  rho = c2 / 3                                       w = 0
+//                      else     v = 1 - s / c2;  rho = (s / 3) * ((1 + v) + v * v) w = v * v
+// Tukey's inner form is c2/3 (1 - v^3) without the cancellation, so rho -> s for small s (Ceres' TukeyLoss, the loss the ICP
+// solve uses).  The outer branch is taken only when s > c2 is TRUE: a NaN chi2 stays a NaN cost and the LM loop rejects it as it
+// always did.  An indefinite information matrix that drives s <= -c2 under Geman-McClure is outside the definition.
+// Which constraints: edge_mask[m] (bytes; NULL = every edge) selects the edges edge_loss / edge_scale act on; prior_loss /
+// prior_scale act on every prior.  Linearization of a robustified constraint: e, the block record and chi2 exactly as above,
+// then blk[t] = w * blk[t] for t ascending (120 doubles of an edge, 42 of a prior); the value that enters F is rho; e and the raw
+// chi2 are kept.  A constraint that is not robustified -- an unmasked edge, or a loss NONE -- is left untouched.  Assembly,
+// H_lambda, the preconditioner, PCG, the model decrease and the accept rule read the weighted records and are as above.
+// Geman-McClure and Tukey are not convex: the loop finds the minimum nearest its start (the Slam calls start from the logged
+// odometry, the usual choice).  After the loop one more evaluation at the returned poses gives every constraint's VERDICT
+// {chi2, w}; w = 1 for a constraint that is not robustified.
 #pragma once
 #include "../../include/lidarslam_amd.h"
 #include "../../include/lsa_pmath.h"
@@ -368,6 +391,131 @@ LSA_HD double prior_chi2(const double* poses16, const lsa_pgo_prior_t& pr, const
   prior_eval(load(poses16 + 16 * (long long)pr.pose), O, pr.position, e, A);
   mulv3(pr.information, e, Oe);
   return (e[0] * Oe[0] + e[1] * Oe[1]) + e[2] * Oe[2];
+}
+
+// ROBUST LOSS: rho(s) and w = rho'(s) at scale c (the table in the opening comment, operation by operation)
+LSA_HD void robust_rho(int loss, double c, double s, double* rho, double* w)
+{
+  const double c2 = c * c;
+  if (loss == LSA_PGO_LOSS_HUBER)
+  {
+    if (s > c2)
+    {
+      const double r = __builtin_sqrt(s);
+      *rho = (2. * c) * r - c2;
+      *w = c / r;
+      return;
+    }
+  }
+  else if (loss == LSA_PGO_LOSS_GEMAN_MCCLURE)
+  {
+    const double d = c2 + s;
+    const double q = c2 / d;
+    *rho = (c2 * s) / d;
+    *w = q * q;
+    return;
+  }
+  else if (loss == LSA_PGO_LOSS_TUKEY)
+  {
+    if (s > c2)
+    {
+      *rho = c2 / 3.;
+      *w = 0.;
+      return;
+    }
+    const double v = 1. - s / c2;
+    *rho = (s / 3.) * ((1. + v) + v * v);
+    *w = v * v;
+    return;
+  }
+  *rho = s;
+  *w = 1.;
+}
+// A robustified constraint's record.  The definition is blk[t] = w * blk[t] for t ascending after the record is formed; each
+// element is one product of w and the finished sum, so it is formed here as the sum leaves the registers (the device writes
+// the 960 bytes once and never reads them back): the same bits.
+LSA_HD void tmul6_scaled(const double* A, const double* B, double w, double* C)
+{
+  for (int i = 0; i < 6; ++i)
+    for (int j = 0; j < 6; ++j)
+    {
+      double s = A[i] * B[j];
+      for (int k = 1; k < 6; ++k) s += A[k * 6 + i] * B[k * 6 + j];
+      C[i * 6 + j] = w * s;
+    }
+}
+LSA_HD void tmulv6_scaled(const double* A, const double* v, double w, double* y)
+{
+  for (int i = 0; i < 6; ++i)
+  {
+    double s = A[i] * v[0];
+    for (int k = 1; k < 6; ++k) s += A[k * 6 + i] * v[k];
+    y[i] = w * s;
+  }
+}
+// everything of one edge under a loss: e[6], blk[kEdgeBlock] (times w), the raw chi2, rho, w.  loss NONE (an unmasked edge
+// is handed NONE): rho = chi2 and w = 1, and a product with 1 is its other factor: linearize_edge's bits
+LSA_HD void linearize_edge_robust(const double* poses16, const lsa_pgo_edge_t& ed, int loss, double c, double* e, double* blk, double* chi2, double* rho, double* w)
+{
+  double A[36], B[36], OA[36], OB[36], Oe[6], ev[6], rv, wv;
+  edge_eval(load(poses16 + 16 * (long long)ed.from), load(poses16 + 16 * (long long)ed.to), load(ed.relative), ev, A, B);
+  mulv6(ed.information, ev, Oe);
+  const double s = dot6(ev, Oe);
+  robust_rho(loss, c, s, &rv, &wv);  // NONE: rho = s, w = 1
+  mul6(ed.information, A, OA);
+  mul6(ed.information, B, OB);
+  tmul6_scaled(A, OA, wv, blk);
+  tmul6_scaled(A, OB, wv, blk + 36);
+  tmul6_scaled(B, OB, wv, blk + 72);
+  tmulv6_scaled(A, Oe, wv, blk + 108);
+  tmulv6_scaled(B, Oe, wv, blk + 114);
+  for (int t = 0; t < 6; ++t) e[t] = ev[t];
+  *chi2 = s;
+  *rho = rv;
+  *w = wv;
+}
+// a candidate's cost value of one edge, and its weight (the verdict)
+LSA_HD double edge_rho(const double* poses16, const lsa_pgo_edge_t& ed, int loss, double c, double* chi2, double* w)
+{
+  double rho;
+  const double s = edge_chi2(poses16, ed);
+  *chi2 = s;
+  if (loss == LSA_PGO_LOSS_NONE) { *w = 1.; return s; }
+  robust_rho(loss, c, s, &rho, w);
+  return rho;
+}
+// the same of one prior
+LSA_HD void linearize_prior_robust(const double* poses16, const lsa_pgo_prior_t& pr, const Pose& O, int loss, double c, double* e, double* blk, double* chi2, double* rho,
+                                   double* w)
+{
+  double b[kPriorBlock], s, rv, wv = 1.;
+  linearize_prior(poses16, pr, O, e, b, &s);
+  rv = s;
+  if (loss != LSA_PGO_LOSS_NONE)
+  {
+    robust_rho(loss, c, s, &rv, &wv);
+    for (int t = 0; t < kPriorBlock; ++t) b[t] = wv * b[t];
+  }
+  for (int t = 0; t < kPriorBlock; ++t) blk[t] = b[t];
+  *chi2 = s;
+  *rho = rv;
+  *w = wv;
+}
+LSA_HD double prior_rho(const double* poses16, const lsa_pgo_prior_t& pr, const Pose& O, int loss, double c, double* chi2, double* w)
+{
+  double rho;
+  const double s = prior_chi2(poses16, pr, O);
+  *chi2 = s;
+  if (loss == LSA_PGO_LOSS_NONE) { *w = 1.; return s; }
+  robust_rho(loss, c, s, &rho, w);
+  return rho;
+}
+// lsa_pgo_robust_t within its limits
+LSA_HD bool robust_ok(const lsa_pgo_robust_t& r)
+{
+  return r.edge_loss >= 0 && r.edge_loss <= 3 && r.prior_loss >= 0 && r.prior_loss <= 3 &&
+         (r.edge_loss == LSA_PGO_LOSS_NONE || (r.edge_scale > 0. && r.edge_scale - r.edge_scale == 0.)) &&
+         (r.prior_loss == LSA_PGO_LOSS_NONE || (r.prior_scale > 0. && r.prior_scale - r.prior_scale == 0.));
 }
 
 // W P and inv(A) P of rigid poses: what brings a trajectory into the frame of the measured positions and back onto its pose 0

@@ -18,6 +18,9 @@
 //   one thread, which also forms alpha and beta -- they stay on the device; the host reads one status block per iteration
 //   to decide whether to enqueue the next.
 //   k_pgo_retract, k_pgo_chi2, k_pgo_chi2_priors and the sums for the candidate.
+//   k_pgo_linearize_robust, k_pgo_linearize_priors_robust, k_pgo_chi2_robust, k_pgo_chi2_priors_robust   the four kernels of the
+//                     constraints under robust losses, launched in place of them when a loss is set: no launch
+//                     is added to an LM iteration.  The verdicts are one more launch of the chi2 pair after the loop.
 //   k_pgo_premultiply, k_pgo_reanchor   a thread per pose: W P_i, and inv(P_0) P_i (a trajectory into the frame of the measured
 //                     positions and back onto its first pose).
 // Buffers belong to the context and grow through its graveyard; everything runs on the context's stream.
@@ -47,7 +50,7 @@ struct PgoBuf
 struct PgoBuffers
 {
   PgoBuf poses, cand, edges, fixed, row_start, inc, loop_start, loop_edge, loop_col, e, blocks, chi2, D, dg, g, L, U, work[2], alpha, gamma, Dinv, vec, partials, state, priors, prior_start, prior_of,
-      pe, pblocks;
+      pe, pblocks, mask, cost, weight, verdict;
   PgoState* host = nullptr;  // pinned
 };
 void pgo_destroy(lsa_ctx* ctx)
@@ -56,7 +59,7 @@ void pgo_destroy(lsa_ctx* ctx)
   if (!b) return;
   PgoBuf* all[] = {&b->poses, &b->cand, &b->edges, &b->fixed, &b->row_start, &b->inc, &b->loop_start, &b->loop_edge, &b->loop_col, &b->e, &b->blocks, &b->chi2, &b->D,
                    &b->dg, &b->g, &b->L, &b->U, &b->work[0], &b->work[1], &b->alpha, &b->gamma, &b->Dinv, &b->vec, &b->partials, &b->state, &b->priors, &b->prior_start,
-                   &b->prior_of, &b->pe, &b->pblocks};
+                   &b->prior_of, &b->pe, &b->pblocks, &b->mask, &b->cost, &b->weight, &b->verdict};
   for (PgoBuf* x : all)
     if (x->p) (void)hipFree(x->p);
   if (b->host) (void)hipHostFree(b->host);
@@ -101,6 +104,68 @@ __global__ __launch_bounds__(kThreads) void k_pgo_chi2_priors(const double* __re
   const int a = blockIdx.x * kThreads + threadIdx.x;
   if (a >= k) return;
   chi2[a] = pg::prior_chi2(poses, priors[a], O);
+}
+
+// The four kernels above under losses (lsa_pose_graph.h ROBUST LOSS): the variants a solve launches IN PLACE of them when a loss
+// is set, so a solve without one runs the kernels above untouched.  `cost` and `weight` hold the m edge values and then the k
+// prior values, as chi2 does; the cost is summed from `cost`.
+struct PgoLoss
+{
+  int edge_loss, prior_loss;
+  double edge_scale, prior_scale;
+  const unsigned char* mask;  // NULL: every edge
+};
+__device__ inline int edge_loss_of(const PgoLoss& loss, int k) { return (!loss.mask || loss.mask[k]) ? loss.edge_loss : LSA_PGO_LOSS_NONE; }
+
+// the weight scales each element of the record as its sum leaves the registers: the record is written once, never read back
+__global__ __launch_bounds__(kThreads) void k_pgo_linearize_robust(const double* __restrict__ poses, const lsa_pgo_edge_t* __restrict__ edges, int m, PgoLoss loss,
+                                                                   double* __restrict__ e, double* __restrict__ blocks, double* __restrict__ chi2,
+                                                                   double* __restrict__ cost, double* __restrict__ weight)
+{
+  const int k = blockIdx.x * kThreads + threadIdx.x;
+  if (k >= m) return;
+  pg::linearize_edge_robust(poses, edges[k], edge_loss_of(loss, k), loss.edge_scale, e + 6LL * k, blocks + (long long)k * pg::kEdgeBlock, chi2 + k, cost + k, weight + k);
+}
+__global__ __launch_bounds__(kThreads) void k_pgo_linearize_priors_robust(const double* __restrict__ poses, const lsa_pgo_prior_t* __restrict__ priors, int k, pg::Pose O,
+                                                                          PgoLoss loss, double* __restrict__ e, double* __restrict__ blocks, double* __restrict__ chi2,
+                                                                          double* __restrict__ cost, double* __restrict__ weight)
+{
+  const int a = blockIdx.x * kThreads + threadIdx.x;
+  if (a >= k) return;
+  pg::linearize_prior_robust(poses, priors[a], O, loss.prior_loss, loss.prior_scale, e + 3LL * a, blocks + (long long)a * pg::kPriorBlock, chi2 + a, cost + a, weight + a);
+}
+// VERDICT false: out[k] = rho (a candidate's cost values); true: out[2 k] = chi2, out[2 k + 1] = w (the verdicts after the loop)
+template <bool VERDICT>
+__global__ __launch_bounds__(kThreads) void k_pgo_chi2_robust(const double* __restrict__ poses, const lsa_pgo_edge_t* __restrict__ edges, int m, PgoLoss loss,
+                                                              double* __restrict__ out)
+{
+  const int k = blockIdx.x * kThreads + threadIdx.x;
+  if (k >= m) return;
+  double s, w;
+  const double rho = pg::edge_rho(poses, edges[k], edge_loss_of(loss, k), loss.edge_scale, &s, &w);
+  if constexpr (VERDICT)
+  {
+    out[2LL * k] = s;
+    out[2LL * k + 1] = w;
+  }
+  else
+    out[k] = rho;
+}
+template <bool VERDICT>
+__global__ __launch_bounds__(kThreads) void k_pgo_chi2_priors_robust(const double* __restrict__ poses, const lsa_pgo_prior_t* __restrict__ priors, int k, pg::Pose O,
+                                                                     PgoLoss loss, double* __restrict__ out)
+{
+  const int a = blockIdx.x * kThreads + threadIdx.x;
+  if (a >= k) return;
+  double s, w;
+  const double rho = pg::prior_rho(poses, priors[a], O, loss.prior_loss, loss.prior_scale, &s, &w);
+  if constexpr (VERDICT)
+  {
+    out[2LL * a] = s;
+    out[2LL * a + 1] = w;
+  }
+  else
+    out[a] = rho;
 }
 
 __global__ __launch_bounds__(kThreads) void k_pgo_assemble(int n, const unsigned char* __restrict__ fixed, pg::Graph G, const lsa_pgo_edge_t* __restrict__ edges,
@@ -412,6 +477,8 @@ struct Problem
   bool haveGraph = false;
   pg::Graph G{};
   pg::Pose O{};  // the priors' offset
+  bool robust = false;  // a loss is set: the _robust kernels, the cost summed from B->cost
+  PgoLoss loss{LSA_PGO_LOSS_NONE, LSA_PGO_LOSS_NONE, 1., 1., nullptr};
   double* vec(int k) const { return ptr_of<double>(B->vec) + 6LL * n * k; }
   PgoState* state() const { return ptr_of<PgoState>(B->state); }
 };
@@ -425,7 +492,7 @@ struct Problem
 
 // buffers for n poses, m edges and k priors; poses, edges, priors (and the graph, when given) uploaded
 int setup(Problem& P, lsa_ctx* ctx, const double* poses16, int n, const unsigned char* fixed, const lsa_pgo_edge_t* edges, int m, const host::PoseGraph* G,
-          const lsa_pgo_prior_t* priors = nullptr, int k = 0, const double* offset16 = nullptr)
+          const lsa_pgo_prior_t* priors = nullptr, int k = 0, const double* offset16 = nullptr, const unsigned char* mask = nullptr, const lsa_pgo_robust_t* rb = nullptr)
 {
   LSA_HIP(ctx, hipSetDevice(ctx->device));
   if (!ctx->pgo) ctx->pgo = new PgoBuffers;
@@ -476,6 +543,20 @@ int setup(Problem& P, lsa_ctx* ctx, const double* poses16, int n, const unsigned
   if (m > 0 && edges) LSA_HIP(ctx, hipMemcpyAsync(B->edges.p, edges, (size_t)m * sizeof(lsa_pgo_edge_t), hipMemcpyHostToDevice, st));
   if (fixed) LSA_HIP(ctx, hipMemcpyAsync(B->fixed.p, fixed, (size_t)n, hipMemcpyHostToDevice, st));
   if (k > 0 && priors) LSA_HIP(ctx, hipMemcpyAsync(B->priors.p, priors, (size_t)k * sizeof(lsa_pgo_prior_t), hipMemcpyHostToDevice, st));
+  if (rb && (rb->edge_loss != LSA_PGO_LOSS_NONE || rb->prior_loss != LSA_PGO_LOSS_NONE))
+  {
+    // the losses' own buffers; the mask travels once, with the edges
+    P.robust = true;
+    P.loss = PgoLoss{rb->edge_loss, rb->prior_loss, rb->edge_scale, rb->prior_scale, nullptr};
+    PGO_TRY(ensure(ctx, B->cost, std::max<size_t>(1, (size_t)m + (size_t)k) * sizeof(double)));
+    PGO_TRY(ensure(ctx, B->weight, std::max<size_t>(1, (size_t)m + (size_t)k) * sizeof(double)));
+    if (mask && m > 0)
+    {
+      PGO_TRY(ensure(ctx, B->mask, (size_t)m));
+      LSA_HIP(ctx, hipMemcpyAsync(B->mask.p, mask, (size_t)m, hipMemcpyHostToDevice, st));
+      P.loss.mask = ptr_of<unsigned char>(B->mask);
+    }
+  }
   P.haveGraph = G != nullptr;
   if (G)
   {
@@ -499,8 +580,13 @@ int launch_linearize_priors(const Problem& P, const double* poses)
 {
   if (P.k == 0) return LSA_OK;
   ProfScope ps(P.ctx, "pgo_linearize_priors", (double)P.k * (sizeof(lsa_pgo_prior_t) + (pg::kPriorBlock + 4) * 8.));
-  hipLaunchKernelGGL(k_pgo_linearize_priors, dim3(blocks_for(P.k)), dim3(kThreads), 0, P.ctx->stream, poses, ptr_of<lsa_pgo_prior_t>(P.B->priors), P.k, P.O,
-                     ptr_of<double>(P.B->pe), ptr_of<double>(P.B->pblocks), ptr_of<double>(P.B->chi2) + P.m);
+  if (P.robust)
+    hipLaunchKernelGGL(k_pgo_linearize_priors_robust, dim3(blocks_for(P.k)), dim3(kThreads), 0, P.ctx->stream, poses, ptr_of<lsa_pgo_prior_t>(P.B->priors), P.k, P.O, P.loss,
+                       ptr_of<double>(P.B->pe), ptr_of<double>(P.B->pblocks), ptr_of<double>(P.B->chi2) + P.m, ptr_of<double>(P.B->cost) + P.m,
+                       ptr_of<double>(P.B->weight) + P.m);
+  else
+    hipLaunchKernelGGL(k_pgo_linearize_priors, dim3(blocks_for(P.k)), dim3(kThreads), 0, P.ctx->stream, poses, ptr_of<lsa_pgo_prior_t>(P.B->priors), P.k, P.O,
+                       ptr_of<double>(P.B->pe), ptr_of<double>(P.B->pblocks), ptr_of<double>(P.B->chi2) + P.m);
   LSA_HIP(P.ctx, hipGetLastError());
   return LSA_OK;
 }
@@ -510,17 +596,53 @@ int launch_linearize(const Problem& P, const double* poses)
   if (P.m > 0)
   {
     ProfScope ps(P.ctx, "pgo_linearize", (double)P.m * (sizeof(lsa_pgo_edge_t) + (pg::kEdgeBlock + 7) * 8.));
-    hipLaunchKernelGGL(k_pgo_linearize, dim3(blocks_for(P.m)), dim3(kThreads), 0, P.ctx->stream, poses, ptr_of<lsa_pgo_edge_t>(P.B->edges), P.m, ptr_of<double>(P.B->e),
-                       ptr_of<double>(P.B->blocks), ptr_of<double>(P.B->chi2));
+    if (P.robust)
+      hipLaunchKernelGGL(k_pgo_linearize_robust, dim3(blocks_for(P.m)), dim3(kThreads), 0, P.ctx->stream, poses, ptr_of<lsa_pgo_edge_t>(P.B->edges), P.m, P.loss,
+                         ptr_of<double>(P.B->e), ptr_of<double>(P.B->blocks), ptr_of<double>(P.B->chi2), ptr_of<double>(P.B->cost), ptr_of<double>(P.B->weight));
+    else
+      hipLaunchKernelGGL(k_pgo_linearize, dim3(blocks_for(P.m)), dim3(kThreads), 0, P.ctx->stream, poses, ptr_of<lsa_pgo_edge_t>(P.B->edges), P.m, ptr_of<double>(P.B->e),
+                         ptr_of<double>(P.B->blocks), ptr_of<double>(P.B->chi2));
     LSA_HIP(P.ctx, hipGetLastError());
   }
   return launch_linearize_priors(P, poses);
 }
-// sum of chi2 (the m edge values, then the k prior values) into stat[3]
+// the cost values of a candidate: chi2, or rho under a loss
+int launch_candidate(const Problem& P, const double* cand)
+{
+  hipStream_t st = P.ctx->stream;
+  if (P.robust)
+  {
+    if (P.m > 0) hipLaunchKernelGGL(k_pgo_chi2_robust<false>, dim3(blocks_for(P.m)), dim3(kThreads), 0, st, cand, ptr_of<lsa_pgo_edge_t>(P.B->edges), P.m, P.loss, ptr_of<double>(P.B->cost));
+    if (P.k > 0)
+      hipLaunchKernelGGL(k_pgo_chi2_priors_robust<false>, dim3(blocks_for(P.k)), dim3(kThreads), 0, st, cand, ptr_of<lsa_pgo_prior_t>(P.B->priors), P.k, P.O, P.loss,
+                         ptr_of<double>(P.B->cost) + P.m);
+  }
+  else
+  {
+    if (P.m > 0) hipLaunchKernelGGL(k_pgo_chi2, dim3(blocks_for(P.m)), dim3(kThreads), 0, st, cand, ptr_of<lsa_pgo_edge_t>(P.B->edges), P.m, ptr_of<double>(P.B->chi2));
+    if (P.k > 0)
+      hipLaunchKernelGGL(k_pgo_chi2_priors, dim3(blocks_for(P.k)), dim3(kThreads), 0, st, cand, ptr_of<lsa_pgo_prior_t>(P.B->priors), P.k, P.O, ptr_of<double>(P.B->chi2) + P.m);
+  }
+  LSA_HIP(P.ctx, hipGetLastError());
+  return LSA_OK;
+}
+// the verdicts {chi2, w} of the m edges and then the k priors at `poses`: the chi2 kernels once more, into B->verdict
+int launch_verdicts(const Problem& P, const double* poses)
+{
+  hipStream_t st = P.ctx->stream;
+  PGO_TRY(ensure(P.ctx, P.B->verdict, std::max<size_t>(1, (size_t)P.m + (size_t)P.k) * 2 * sizeof(double)));
+  double* out = ptr_of<double>(P.B->verdict);
+  if (P.m > 0) hipLaunchKernelGGL(k_pgo_chi2_robust<true>, dim3(blocks_for(P.m)), dim3(kThreads), 0, st, poses, ptr_of<lsa_pgo_edge_t>(P.B->edges), P.m, P.loss, out);
+  if (P.k > 0)
+    hipLaunchKernelGGL(k_pgo_chi2_priors_robust<true>, dim3(blocks_for(P.k)), dim3(kThreads), 0, st, poses, ptr_of<lsa_pgo_prior_t>(P.B->priors), P.k, P.O, P.loss, out + 2LL * P.m);
+  LSA_HIP(P.ctx, hipGetLastError());
+  return LSA_OK;
+}
+// sum of the cost values (the m edge values, then the k prior values: chi2, or rho under a loss) into stat[3]
 int launch_cost(const Problem& P)
 {
   const int nb = (int)blocks_for((long long)P.m + P.k);
-  hipLaunchKernelGGL(k_pgo_sum, dim3(nb), dim3(kThreads), 0, P.ctx->stream, P.m + P.k, ptr_of<double>(P.B->chi2), ptr_of<double>(P.B->partials));
+  hipLaunchKernelGGL(k_pgo_sum, dim3(nb), dim3(kThreads), 0, P.ctx->stream, P.m + P.k, ptr_of<double>(P.robust ? P.B->cost : P.B->chi2), ptr_of<double>(P.B->partials));
   hipLaunchKernelGGL(k_pgo_finish, dim3(1), dim3(64), 0, P.ctx->stream, (int)FIN_CHI2, nb, ptr_of<double>(P.B->partials), 0., P.state());
   LSA_HIP(P.ctx, hipGetLastError());
   return LSA_OK;
@@ -775,17 +897,28 @@ int lsa_pgo_reanchor(lsa_ctx* ctx, const double* poses16, int n, double* poses_o
 int lsa_pgo_solve_priors(lsa_ctx* ctx, const double* poses16, int n, const uint8_t* fixed, const lsa_pgo_edge_t* edges, int m, const lsa_pgo_prior_t* priors, int k,
                          const double* offset16, const lsa_pgo_params_t* params, double* poses_out, lsa_pgo_result_t* result)
 {
+  return lsa_pgo_solve_robust(ctx, poses16, n, fixed, edges, m, nullptr, priors, k, offset16, params, nullptr, poses_out, result, nullptr, nullptr);
+}
+
+int lsa_pgo_solve_robust(lsa_ctx* ctx, const double* poses16, int n, const uint8_t* fixed, const lsa_pgo_edge_t* edges, int m, const uint8_t* edge_mask,
+                         const lsa_pgo_prior_t* priors, int k, const double* offset16, const lsa_pgo_params_t* params, const lsa_pgo_robust_t* robust, double* poses_out,
+                         lsa_pgo_result_t* result, double* edge_verdict_out, double* prior_verdict_out)
+{
   if (!ctx) return LSA_E_ARG;
   lsa_pgo_params_t p;
   lsa_pgo_params_init(&p);
   if (params) p = *params;
+  lsa_pgo_robust_t rb;
+  lsa_pgo_robust_init(&rb);
+  if (robust) rb = *robust;
   if (!poses_out || !result || !pg::params_ok(p)) return ctx->fail(LSA_E_ARG, "lsa_pgo_solve: bad argument or parameters out of limits");
+  if (!pg::robust_ok(rb)) return ctx->fail(LSA_E_ARG, "lsa_pgo_solve: a loss outside 0..3, or a scale that is not finite and positive");
   std::string why;
   host::PoseGraph G;
   if (const int rc = host::PgoBuild(poses16, n, fixed, edges, m, &G, &why, priors, k, offset16); rc != LSA_OK) return ctx->fail(rc, "lsa_pgo_solve: " + why);
   if (n > kMaxPoses) return ctx->fail(LSA_E_CAPACITY, "lsa_pgo_solve: more than 262144 poses (the cyclic reduction keeps every level)");
   Problem P;
-  PGO_TRY(setup(P, ctx, poses16, n, fixed, edges, m, &G, priors, k, offset16));
+  PGO_TRY(setup(P, ctx, poses16, n, fixed, edges, m, &G, priors, k, offset16, edge_mask, &rb));
   hipStream_t st = ctx->stream;
   const long long nv = 6LL * n;
   const bool diag = p.preconditioner == 1;
@@ -840,9 +973,7 @@ int lsa_pgo_solve_priors(lsa_ctx* ctx, const double* poses16, int n, const uint8
     hipLaunchKernelGGL(k_pgo_row_stats, dim3(nbn), dim3(kThreads), 0, st, n, lambda, P.vec(V_DELTA), ptr_of<double>(P.B->dg), ptr_of<double>(P.B->g), partials);
     PGO_TRY(finish(P, FIN_STATS, nbn, 0.));
     hipLaunchKernelGGL(k_pgo_retract, dim3(nbn), dim3(kThreads), 0, st, n, x, P.vec(V_DELTA), cand);
-    if (m > 0) hipLaunchKernelGGL(k_pgo_chi2, dim3(blocks_for(m)), dim3(kThreads), 0, st, cand, ptr_of<lsa_pgo_edge_t>(P.B->edges), m, ptr_of<double>(P.B->chi2));
-    if (k > 0)
-      hipLaunchKernelGGL(k_pgo_chi2_priors, dim3(blocks_for(k)), dim3(kThreads), 0, st, cand, ptr_of<lsa_pgo_prior_t>(P.B->priors), k, P.O, ptr_of<double>(P.B->chi2) + m);
+    PGO_TRY(launch_candidate(P, cand));
     PGO_TRY(launch_cost(P));
     PGO_TRY(read_state(P, &s));
     const double model = s.stat[0], step = s.stat[1], Fn = 0.5 * s.stat[3];
@@ -873,11 +1004,77 @@ int lsa_pgo_solve_priors(lsa_ctx* ctx, const double* poses16, int n, const uint8
   R.final_lambda = lambda;
   R.termination = term;
   R.message = host::PgoMessage(term);
-  std::vector<double> out((size_t)n * 16);
+  std::vector<double> out((size_t)n * 16), verdict;
+  if (edge_verdict_out || prior_verdict_out)
+  {
+    verdict.resize(((size_t)m + (size_t)k) * 2);
+    PGO_TRY(launch_verdicts(P, x));
+    PGO_TRY(download(ctx, verdict.data(), P.B->verdict.p, verdict.size() * sizeof(double)));
+  }
   PGO_TRY(download(ctx, out.data(), x, out.size() * sizeof(double)));
   LSA_HIP(ctx, hipStreamSynchronize(st));
   std::memcpy(poses_out, out.data(), out.size() * sizeof(double));
+  if (edge_verdict_out && m > 0) std::memcpy(edge_verdict_out, verdict.data(), (size_t)m * 2 * sizeof(double));
+  if (prior_verdict_out && k > 0) std::memcpy(prior_verdict_out, verdict.data() + (size_t)m * 2, (size_t)k * 2 * sizeof(double));
   *result = R;
+  return LSA_OK;
+}
+
+int lsa_pgo_linearize_robust(lsa_ctx* ctx, const double* poses16, int n, const lsa_pgo_edge_t* edges, int m, const uint8_t* edge_mask, const lsa_pgo_robust_t* robust,
+                             double* e_out, double* blocks_out, double* chi2_out, double* rho_out, double* w_out)
+{
+  if (!ctx) return LSA_E_ARG;
+  std::string why = "bad argument";
+  lsa_pgo_robust_t rb;
+  lsa_pgo_robust_init(&rb);
+  if (robust) rb = *robust;
+  if (!e_out || !blocks_out || !chi2_out || !rho_out || !w_out || !pg::robust_ok(rb) || host::PgoCheckEdges(poses16, n, edges, m, &why) != LSA_OK)
+    return ctx->fail(LSA_E_ARG, "lsa_pgo_linearize_robust: " + why);
+  if (n > kMaxPoses) return ctx->fail(LSA_E_CAPACITY, "lsa_pgo_linearize_robust: more than 262144 poses");
+  if (m == 0) return LSA_OK;
+  Problem P;
+  PGO_TRY(setup(P, ctx, poses16, n, nullptr, edges, m, nullptr, nullptr, 0, nullptr, edge_mask, &rb));
+  PGO_TRY(launch_linearize(P, ptr_of<double>(P.B->poses)));
+  PGO_TRY(download(ctx, e_out, P.B->e.p, (size_t)m * 6 * sizeof(double)));
+  PGO_TRY(download(ctx, blocks_out, P.B->blocks.p, (size_t)m * pg::kEdgeBlock * sizeof(double)));
+  PGO_TRY(download(ctx, chi2_out, P.B->chi2.p, (size_t)m * sizeof(double)));
+  if (P.robust)
+  {
+    PGO_TRY(download(ctx, rho_out, P.B->cost.p, (size_t)m * sizeof(double)));
+    PGO_TRY(download(ctx, w_out, P.B->weight.p, (size_t)m * sizeof(double)));
+  }
+  LSA_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  if (!P.robust)  // no loss: the plain kernel ran; rho = chi2, w = 1
+    for (int a = 0; a < m; ++a) { rho_out[a] = chi2_out[a]; w_out[a] = 1.; }
+  return LSA_OK;
+}
+
+int lsa_pgo_linearize_robust_priors(lsa_ctx* ctx, const double* poses16, int n, const lsa_pgo_prior_t* priors, int k, const double* offset16, const lsa_pgo_robust_t* robust,
+                                    double* e_out, double* blocks_out, double* chi2_out, double* rho_out, double* w_out)
+{
+  if (!ctx) return LSA_E_ARG;
+  std::string why = "bad argument";
+  lsa_pgo_robust_t rb;
+  lsa_pgo_robust_init(&rb);
+  if (robust) rb = *robust;
+  if (!e_out || !blocks_out || !chi2_out || !rho_out || !w_out || !pg::robust_ok(rb) || host::PgoCheckPriors(poses16, n, priors, k, offset16, &why) != LSA_OK)
+    return ctx->fail(LSA_E_ARG, "lsa_pgo_linearize_robust_priors: " + why);
+  if (n > kMaxPoses) return ctx->fail(LSA_E_CAPACITY, "lsa_pgo_linearize_robust_priors: more than 262144 poses");
+  if (k == 0) return LSA_OK;
+  Problem P;
+  PGO_TRY(setup(P, ctx, poses16, n, nullptr, nullptr, 0, nullptr, priors, k, offset16, nullptr, &rb));
+  PGO_TRY(launch_linearize_priors(P, ptr_of<double>(P.B->poses)));
+  PGO_TRY(download(ctx, e_out, P.B->pe.p, (size_t)k * 3 * sizeof(double)));
+  PGO_TRY(download(ctx, blocks_out, P.B->pblocks.p, (size_t)k * pg::kPriorBlock * sizeof(double)));
+  PGO_TRY(download(ctx, chi2_out, P.B->chi2.p, (size_t)k * sizeof(double)));
+  if (P.robust)
+  {
+    PGO_TRY(download(ctx, rho_out, P.B->cost.p, (size_t)k * sizeof(double)));
+    PGO_TRY(download(ctx, w_out, P.B->weight.p, (size_t)k * sizeof(double)));
+  }
+  LSA_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  if (!P.robust)
+    for (int a = 0; a < k; ++a) { rho_out[a] = chi2_out[a]; w_out[a] = 1.; }
   return LSA_OK;
 }
 

@@ -17,7 +17,8 @@
 // trajectory back, and the loop-closure constraint an optimizer needs as input: FindLoopClosureCandidate and
 // RegisterLoggedFrames.  OptimizeLoggedTrajectory optimizes the logged trajectory with such edges on the device, and
 // RunPoseGraphOptimization, the reference's entry point with GPS positions, runs on the same device solver with the positions
-// as priors (no g2o).
+// as priors (no g2o).  Both have an overload that takes RobustParameters -- a robust loss on the loop edges or on the GPS priors --
+// and gives a ConstraintVerdict {chi2, weight} per constraint, so that a false loop edge or an outlying fix is discounted and seen.
 #pragma once
 #include <algorithm>
 #include <array>
@@ -312,6 +313,26 @@ public:
                                                   std::array<double, 16>& gpsToSensorOffset, const lsa_pgo_params_t& params, double timeOffset = 0.,
                                                   lsa_pgo_result_t* summary = nullptr)
   {
+    return this->RunPoseGraphOptimization(gpsPositions, gpsCovariances, gpsToSensorOffset, params, DefaultRobustParameters(), timeOffset, summary, nullptr);
+  }
+  // ... under a robust loss on the GPS priors (robust.prior_loss / prior_scale; lsa_slam_run_pose_graph_optimization_robust): a fix
+  // tens of metres off is discounted instead of bending the track.  fixVerdicts: per fix {chi2, weight} at the optimized poses,
+  // weight -1 for a fix that matched no pose.  Geman-McClure and Tukey find the minimum nearest the logged odometry.
+  using RobustParameters = lsa_pgo_robust_t;
+  struct ConstraintVerdict
+  {
+    double chi2, weight;
+  };
+  static RobustParameters DefaultRobustParameters()
+  {
+    RobustParameters r;
+    lsa_pgo_robust_init(&r);
+    return r;
+  }
+  std::vector<Transform> RunPoseGraphOptimization(const std::vector<Transform>& gpsPositions, const std::vector<std::array<double, 9>>& gpsCovariances,
+                                                  std::array<double, 16>& gpsToSensorOffset, const lsa_pgo_params_t& params, const RobustParameters& robust,
+                                                  double timeOffset = 0., lsa_pgo_result_t* summary = nullptr, std::vector<ConstraintVerdict>* fixVerdicts = nullptr)
+  {
     std::vector<Transform> poses = this->GetTrajectory();
     std::vector<double> rows((poses.size() + 1) * 17), times(gpsPositions.size()), xyz(gpsPositions.size() * 3), cov(gpsPositions.size() * 9);
     lsa_pgo_result_t result;
@@ -327,8 +348,14 @@ public:
         std::memcpy(cov.data() + 9 * f, gpsCovariances[f].data(), 9 * sizeof(double));
       }
       std::array<double, 16> offset = gpsToSensorOffset;
-      rc = lsa_slam_run_pose_graph_optimization(this->Handle, times.data(), xyz.data(), cov.data(), static_cast<int>(gpsPositions.size()), offset.data(), timeOffset, &params,
-                                                rows.data(), static_cast<int>(poses.size()), &result);
+      std::vector<double> verdict(2 * gpsPositions.size());
+      rc = lsa_slam_run_pose_graph_optimization_robust(this->Handle, times.data(), xyz.data(), cov.data(), static_cast<int>(gpsPositions.size()), offset.data(), timeOffset,
+                                                       &params, &robust, rows.data(), static_cast<int>(poses.size()), &result, verdict.data());
+      if (fixVerdicts)
+      {
+        fixVerdicts->clear();
+        for (std::size_t f = 0; rc >= 0 && f < gpsPositions.size(); ++f) fixVerdicts->push_back(ConstraintVerdict{verdict[2 * f], verdict[2 * f + 1]});
+      }
       this->LastError = rc < 0 ? std::string("RunPoseGraphOptimization: ") + lsa_slam_last_error(this->Handle) : std::string();
       if (rc >= 0) gpsToSensorOffset = offset;
     }
@@ -434,12 +461,25 @@ public:
   std::vector<Transform> OptimizeLoggedTrajectory(const std::vector<PoseGraphEdge>& loopEdges, const PoseGraphParameters& params = DefaultPoseGraphParameters(),
                                                   PoseGraphSummary* summary = nullptr)
   {
+    return this->OptimizeLoggedTrajectory(loopEdges, params, DefaultRobustParameters(), summary, nullptr);
+  }
+  // ... under a robust loss on the loop edges (robust.edge_loss / edge_scale; lsa_slam_optimize_logged_trajectory_robust): a false
+  // loop edge is discounted instead of bending the trajectory; the odometry chain is never discounted.  loopVerdicts: per loop
+  // edge {chi2, weight} at the optimized poses -- under Tukey a weight of 0 says the edge was disregarded.
+  std::vector<Transform> OptimizeLoggedTrajectory(const std::vector<PoseGraphEdge>& loopEdges, const PoseGraphParameters& params, const RobustParameters& robust,
+                                                  PoseGraphSummary* summary = nullptr, std::vector<ConstraintVerdict>* loopVerdicts = nullptr)
+  {
     std::vector<Transform> poses = this->GetTrajectory();
-    std::vector<double> rows((poses.size() + 1) * 17);
+    std::vector<double> rows((poses.size() + 1) * 17), verdict(2 * loopEdges.size() + 2);
     PoseGraphSummary result;
     std::memset(&result, 0, sizeof(result));
-    const int rc = lsa_slam_optimize_logged_trajectory(this->Handle, loopEdges.empty() ? nullptr : loopEdges.data(), static_cast<int>(loopEdges.size()), &params, rows.data(),
-                                                       static_cast<int>(poses.size()), &result);
+    const int rc = lsa_slam_optimize_logged_trajectory_robust(this->Handle, loopEdges.empty() ? nullptr : loopEdges.data(), static_cast<int>(loopEdges.size()), &params, &robust,
+                                                              rows.data(), static_cast<int>(poses.size()), &result, verdict.data());
+    if (loopVerdicts)
+    {
+      loopVerdicts->clear();
+      for (std::size_t k = 0; rc >= 0 && k < loopEdges.size(); ++k) loopVerdicts->push_back(ConstraintVerdict{verdict[2 * k], verdict[2 * k + 1]});
+    }
     this->LastError = rc < 0 ? std::string("OptimizeLoggedTrajectory: ") + lsa_slam_last_error(this->Handle) : std::string();
     if (rc < 0) result.termination = rc;
     if (summary) *summary = result;

@@ -407,7 +407,7 @@ int lsa_download_knn(lsa_ctx* ctx, int type, int* idx, float* d2, int* cnt, int 
  *   cost = 1/2 sum rho,  g = sum rho' J^T r,  H = sum rho' J^T J (upper part
  *   mirrored, row-major 6x6), w = (x, y, z, rx, ry, rz).
  * The 6-dof trust-region control flow itself stays on the host (it is a
- * 6x6 solve); see lidarslam_amd/csrc/host/lsa_lm.cpp. */
+ * 6x6 solve); see lidarslam_amd/csrc/host/lsa_lm_loop.cpp. */
 int lsa_accumulate(lsa_ctx* ctx, unsigned type_mask, const double w[6], int want_jacobian, double* cost, double g[6],
                    double H[36], int* n_valid);
 /* 1 when the partial sums of lsa_accumulate arrive through coherent host memory the kernel writes directly (the
@@ -668,13 +668,39 @@ int lsa_selftest_math(lsa_ctx* ctx, int fn, const double* x, const double* y, in
  *    7  42  39  POSE    in: M0[12] M1[12] w[6] qa[4] qb[4] s t t0 t1.  out: FromXYZRPY(w)[12], ToXYZRPY(M0)[6],
  *                       ToQuaternion(M0)[4], Slerp(qa, qb, s)[4], RotationAngle(M0), interp_eval of
  *                       MakeInterpConst(M0, M1, t0, t1) at t [12]
- *    8  12   4  SPD3_HOST   SolveSPD of the host LM loop (host/lsa_lm.cpp), layout of fn 4
+ *    8  12   4  SPD3_HOST   SolveSPD of the host LM loop (host/lsa_lm_loop.cpp), layout of fn 4
  *    9  42   7  SPD6_HOST   layout of fn 5
  *   10   9  12  JACOBI3_HOST  the host's cyclic Jacobi eigen-solver. in: A[9]. out: evals[3] ascending, V[9] row-major
  *                            (columns = eigenvectors)
  *   11  36  42  JACOBI6_HOST  in: A[36]. out: evals[6], V[36]
  * fn 8-11 run on the CPU and accept ctx == NULL. */
 int lsa_selftest_numerics(lsa_ctx* ctx, int fn, const double* in, int n, double* out);
+/* Self-test of the trust-region step of the LM solve on scripted sums: what the solve does between two evaluations --
+ * step acceptance, radius update, damped Cholesky solve, the invalid-step retry, the ways of ending -- reads 29 sums per
+ * evaluation, its own state, max_iter and min_matches, and nothing of the residual blocks.  lsa_selftest_lm_step runs the
+ * device's step (lm_step of lsa_lm.hip, the code lsa_solve_device inlines) with one workgroup per script, all scripts in
+ * one launch; lsa_selftest_lm_host runs the host loop (host/lsa_lm_loop.cpp, the code behind lsa_solve) and needs neither
+ * a context nor a device.  Same arguments, same outputs, bit for bit.
+ *   header[4 * s ..]  two_d, max_iter (>= 0), min_matches, K (1..4096) of script s
+ *   x0[6 * s ..]      its start point x y z rx ry rz
+ *   sums              the scripts' evaluations one after the other, script s's K first; an evaluation is 29 doubles:
+ *                     cost, g[6], the upper triangle of H row by row [21], the number of residual blocks.  Evaluation 0
+ *                     is the one at x0; evaluation k + 1 is taken for the candidate record k holds, wherever that is.
+ *                     In 2D mode the rows and columns z rx ry of g and H are never read.
+ *   records           one record of 42 doubles per evaluation, in the order of `sums` (all 0 behind the stop):
+ *                       [0..5] the next candidate (0 when the solve is over)  [6] termination code  [7] 1: the solve is over
+ *                       [8] radius  [9] decrease_factor  [10] |x| over the active parameters  [11] model_cost_change
+ *                       [12] |step|  [13] initial_cost  [14] reuse_diagonal  [15] consecutive invalid steps  [16] iteration
+ *                       [17] evaluations, the candidate's included  [18] successful  [19] unsuccessful steps  [20] iterations
+ *                       [21] skipped  [22] matches  [23..28] the current point  [29..34] Jacobi scales and [35..40] LM
+ *                       diagonal of the active parameters, in their order (1 and 0 behind them)
+ *                       [41] parity of the evaluations whose sums became the current ones (the device's buffer index)
+ *   results[45 * s ..] as lsa_solve_device_end receives it: pose[6], initial cost, final cost, the 29 sums at the final
+ *                     point, successful, unsuccessful, iterations, evaluations, skipped, termination, matches, 0
+ *   status[2 * s ..]  0: the solve ended / 1: the script ran out first (records up to there, result all 0); evaluations used
+ * The number of residual blocks of an evaluation must be finite.  Returns LSA_E_ARG for a bad header. */
+int lsa_selftest_lm_step(lsa_ctx* ctx, int n_scripts, const int* header, const double* x0, const double* sums, double* records, double* results, int* status);
+int lsa_selftest_lm_host(int n_scripts, const int* header, const double* x0, const double* sums, double* records, double* results, int* status);
 /* Device self-test of the keypoint labelling (SetKeyPointsLabels, SSKE.cxx:474-590) on its own: the labelling kernel of
  * the extraction, launched as the extraction launches it, on scores and validity the caller provides instead of those
  * the curvature kernels computed.  nrings (1..512) rings of ring_lengths[r] >= 0 points; the four score arrays and

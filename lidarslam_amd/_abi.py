@@ -173,6 +173,8 @@ SIGNATURES = {
     # ---- self tests and profiling
     "lsa_selftest_math": (i32, [vp, i32, vp, vp, i32, vp]),
     "lsa_selftest_numerics": (i32, [vp, i32, vp, i32, vp]),
+    "lsa_selftest_lm_step": (i32, [vp, i32, vp, vp, vp, vp, vp, vp]),
+    "lsa_selftest_lm_host": (i32, [i32, vp, vp, vp, vp, vp, vp]),
     "lsa_selftest_labels": (i32, [vp, P(ExtractParams), vp, i32, vp, vp, vp, vp, vp, vp, vp, vp]),
     "lsa_selftest_keep_busy": (i32, [vp, i32, i32]),
     "lsa_profile_enable": (i32, [vp, i32]),

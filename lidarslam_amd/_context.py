@@ -53,6 +53,28 @@ def selftest_numerics(fn, records, ctx=None):
     return out
 
 
+LM_STEP_RECORD, LM_STEP_RESULT = 42, 45  # doubles of lsa_selftest_lm_step's record and result (include/lidarslam_amd.h)
+
+
+def selftest_lm_step(scripts, ctx=None):
+    """lsa_selftest_lm_step (ctx: the device's step) or lsa_selftest_lm_host (ctx None: the host loop, no device) on
+    scripts [(two_d, max_iter, min_matches, x0[6], sums (K, 29))] -> ([records (K, 42)], results (n, 45), status (n, 2))"""
+    header = np.ascontiguousarray([(int(t), int(mi), int(mm), len(s)) for t, mi, mm, _x, s in scripts], np.int32).reshape(-1, 4)
+    x0 = np.ascontiguousarray([x for _t, _mi, _mm, x, _s in scripts], np.float64).reshape(-1, 6)
+    sums = np.ascontiguousarray(np.concatenate([np.asarray(s, np.float64).reshape(-1, 29) for *_h, s in scripts]))
+    n, total = header.shape[0], sums.shape[0]
+    records, results, status = np.zeros((total, LM_STEP_RECORD)), np.zeros((n, LM_STEP_RESULT)), np.zeros((n, 2), np.int32)
+    L = lib()
+    if ctx is None:
+        rc = L.lsa_selftest_lm_host(n, ptr(header), ptr(x0), ptr(sums), ptr(records), ptr(results), ptr(status))
+    else:
+        rc = L.lsa_selftest_lm_step(ctx.h, n, ptr(header), ptr(x0), ptr(sums), ptr(records), ptr(results), ptr(status))
+    if rc < 0:
+        raise LsaError(f"lsa_selftest_lm_{'host' if ctx is None else 'step'} failed ({rc})" + (f": {L.lsa_last_error(ctx.h).decode()}" if ctx is not None else ""))
+    ends = np.cumsum(header[:, 3])
+    return [records[e - k:e] for e, k in zip(ends, header[:, 3])], results, status
+
+
 def _profile(L, h):
     buf = (KernelStat * 64)()
     n = L.lsa_profile_get(h, buf, 64)

@@ -11,57 +11,7 @@ namespace lsa
 {
 namespace host
 {
-namespace
-{
-
-struct Eval
-{
-  double cost = 0.;
-  double g[6] = {0};
-  double H[36] = {0};
-  int nValid = 0;
-};
-
-// small dense symmetric positive definite solve (normal equations of the augmented LM system)
-bool SolveSPD(int n, const double* A, const double* b, double* x)
-{
-  // (divisions by a diagonal element are multiplications by its reciprocal, taken once: as solve_spd of lsa_lm.hip)
-  double L[36], rinv[6];
-  for (int i = 0; i < n; ++i)
-    for (int j = 0; j <= i; ++j)
-    {
-      double s = A[i * n + j];
-      for (int k = 0; k < j; ++k) s -= L[i * n + k] * L[j * n + k];
-      if (i == j)
-      {
-        if (!(s > 0.0) || !std::isfinite(s)) return false;
-        L[i * n + i] = std::sqrt(s);
-        rinv[i] = 1.0 / L[i * n + i];
-      }
-      else
-        L[i * n + j] = s * rinv[j];
-    }
-  double y[6];
-  for (int i = 0; i < n; ++i)
-  {
-    double s = b[i];
-    for (int k = 0; k < i; ++k) s -= L[i * n + k] * y[k];
-    y[i] = s * rinv[i];
-  }
-  for (int i = n - 1; i >= 0; --i)
-  {
-    double s = y[i];
-    for (int k = i + 1; k < n; ++k) s -= L[k * n + i] * x[k];
-    x[i] = s * rinv[i];
-  }
-  for (int i = 0; i < n; ++i)
-    if (!std::isfinite(x[i])) return false;
-  return true;
-}
-
-}  // namespace
-
-// lsa_selftest_numerics, fn 8-11: the two file-local solvers above on one record (layouts: include/lidarslam_amd.h)
+// lsa_selftest_numerics, fn 8-11: the loop's solver (lsa_lm_loop.cpp) and the eigen-solver on one record (layouts: include/lidarslam_amd.h)
 bool ProbeSolveSPD(int n, const double* A, const double* b, double* x) { return SolveSPD(n, A, b, x); }
 void ProbeSymEigen(int n, const double* A, double* evals, double* evecs) { SymEigen(n, A, evals, evecs); }
 
@@ -122,137 +72,12 @@ int LocalOptimizer::End(SolveSummary& sum)
 
 int LocalOptimizer::SolveOnHost(SolveSummary& sum)
 {
-  sum = SolveSummary();
   int act[6], n = 0;
   for (int i = 0; i < 6; ++i)
     if (!(TwoDMode && (i == 2 || i == 3 || i == 4))) act[n++] = i;  // SubsetParameterization(6, {2,3,4}), LocalOptimizer.cxx:89-90
-
-  // ceres::Solver::Options defaults
-  const double function_tolerance = 1e-6, gradient_tolerance = 1e-10, parameter_tolerance = 1e-8;
-  const double min_relative_decrease = 1e-3, min_trust_region_radius = 1e-32, max_radius = 1e16;
-  const double min_diagonal = 1e-6, max_diagonal = 1e32;
-  const int max_consecutive_invalid = 5;
-  double radius = 1e4, decrease_factor = 2.0;
-  bool reuse_diagonal = false;
-
-  auto evaluate = [&](const double* w, bool jac, Eval& e) -> int {
-    sum.num_evaluations++;
-    return lsa_accumulate(Ctx, TypeMask, w, jac ? 1 : 0, &e.cost, e.g, e.H, &e.nValid);
-  };
-
-  double x[6];
-  std::memcpy(x, PoseArray, sizeof(x));
-  Eval cur;
-  int rc = evaluate(x, true, cur);
-  if (rc) return rc;
-  sum.num_matches = cur.nValid;
-  if (static_cast<unsigned>(cur.nValid) < MinMatches)
-  {
-    sum.skipped = true;
-    sum.message = "not enough matches";
-    return LSA_OK;
-  }
-  sum.initial_cost = sum.final_cost = cur.cost;
-  sum.num_successful_steps = 1;  // iteration 0 is reported as a successful step by Ceres
-
-  double scale[6];
-  for (int a = 0; a < n; ++a) scale[a] = 1.0 / (1.0 + std::sqrt(cur.H[act[a] * 6 + act[a]]));  // Jacobi scaling, once
-  auto gradMax = [&](const Eval& e) { double m = 0; for (int a = 0; a < n; ++a) m = std::max(m, std::abs(e.g[act[a]])); return m; };
-  auto xnorm = [&](const double* v) { double s = 0; for (int a = 0; a < n; ++a) s += v[act[a]] * v[act[a]]; return std::sqrt(s); };
-
-  if (gradMax(cur) <= gradient_tolerance) { sum.message = "gradient tolerance (iteration 0)"; return LSA_OK; }
-  double x_norm = xnorm(x);
-  double diag[6] = {0};
-  int consecutive_invalid = 0, iter = 0;
-
-  while (true)
-  {
-    if (iter >= (int)LMMaxIter) { sum.message = "max iterations"; break; }
-    if (gradMax(cur) <= gradient_tolerance) { sum.message = "gradient tolerance"; break; }
-    if (radius < min_trust_region_radius) { sum.message = "min trust region radius"; break; }
-    ++iter;
-    sum.num_iterations = iter;
-
-    double Hs[36], gs[6];
-    for (int a = 0; a < n; ++a)
-    {
-      gs[a] = cur.g[act[a]] * scale[a];
-      for (int b = 0; b < n; ++b) Hs[a * n + b] = cur.H[act[a] * 6 + act[b]] * scale[a] * scale[b];
-    }
-    if (!reuse_diagonal)
-      for (int a = 0; a < n; ++a) diag[a] = std::min(std::max(Hs[a * n + a], min_diagonal), max_diagonal);
-    double M[36], y[6], step[6];
-    for (int i = 0; i < n * n; ++i) M[i] = Hs[i];
-    for (int a = 0; a < n; ++a) M[a * n + a] += diag[a] / radius;
-    bool ok = SolveSPD(n, M, gs, y);
-    reuse_diagonal = true;
-    double model_cost_change = 0;
-    if (ok)
-    {
-      for (int a = 0; a < n; ++a) step[a] = -y[a];
-      double sg = 0, sHs = 0;
-      for (int a = 0; a < n; ++a)
-      {
-        sg += step[a] * gs[a];
-        double t = 0;
-        for (int b = 0; b < n; ++b) t += Hs[a * n + b] * step[b];
-        sHs += step[a] * t;
-      }
-      model_cost_change = -sg - 0.5 * sHs;
-      if (model_cost_change < 0.0) ok = false;
-    }
-    if (!ok)
-    {
-      ++sum.num_unsuccessful_steps;
-      if (++consecutive_invalid >= max_consecutive_invalid) { sum.message = "too many invalid steps"; break; }
-      radius /= decrease_factor; decrease_factor *= 2.0; reuse_diagonal = true;
-      continue;
-    }
-    consecutive_invalid = 0;
-
-    double cand[6], delta_norm = 0;
-    std::memcpy(cand, x, sizeof(cand));
-    for (int a = 0; a < n; ++a)
-    {
-      cand[act[a]] = x[act[a]] + step[a] * scale[a];
-      const double e = x[act[a]] - cand[act[a]];
-      delta_norm += e * e;
-    }
-    delta_norm = std::sqrt(delta_norm);
-    // Ceres evaluates the cost only here and, if the step is accepted, residuals + Jacobian again at
-    // the same point.  On the device the Jacobian costs nothing extra (the kernel is bound by the
-    // record reads), so it is evaluated speculatively and reused on acceptance: one launch + one
-    // read-back per LM iteration instead of two, same arithmetic.
-    Eval cc;
-    rc = evaluate(cand, true, cc);
-    if (rc) return rc;
-
-    // parameter / function tolerance terminate WITHOUT taking the candidate step
-    if (delta_norm <= parameter_tolerance * (x_norm + parameter_tolerance)) { sum.message = "parameter tolerance"; break; }
-    const double cost_change = cur.cost - cc.cost;
-    if (std::abs(cost_change) <= function_tolerance * cur.cost) { sum.message = "function tolerance"; break; }
-
-    const double relative_decrease = cost_change / model_cost_change;
-    if (relative_decrease > min_relative_decrease)
-    {
-      std::memcpy(x, cand, sizeof(x));
-      x_norm = xnorm(x);
-      cur = cc;  // gradient and J^T J at the accepted point were evaluated speculatively above
-      ++sum.num_successful_steps;
-      const double t = 2.0 * relative_decrease - 1.0;
-      radius = std::min(max_radius, radius / std::max(1.0 / 3.0, 1.0 - t * t * t));
-      decrease_factor = 2.0;
-      reuse_diagonal = false;
-    }
-    else
-    {
-      ++sum.num_unsuccessful_steps;
-      radius /= decrease_factor; decrease_factor *= 2.0; reuse_diagonal = true;
-    }
-  }
-  std::memcpy(PoseArray, x, sizeof(x));
-  sum.final_cost = cur.cost;
-  return LSA_OK;
+  // the loop is lsa_lm_loop.cpp's; every evaluation it asks for is one lsa_accumulate call
+  const LmEvaluate evaluate = [&](const double* w, LmEval& e) -> int { return lsa_accumulate(Ctx, TypeMask, w, 1, &e.cost, e.g, e.H, &e.nValid); };
+  return RunLmLoop(act, n, PoseArray, static_cast<int>(LMMaxIter), MinMatches, evaluate, sum, nullptr, nullptr, nullptr);
 }
 
 // LocalOptimizer.cxx:112-140: covariance = pseudo-inverse of the loss-corrected J^T J
@@ -263,7 +88,7 @@ int LocalOptimizer::EstimateRegistrationError(RegistrationError& err)
   int act[6], n = 0;
   for (int i = 0; i < 6; ++i)
     if (!(TwoDMode && (i == 2 || i == 3 || i == 4))) act[n++] = i;
-  Eval cur;
+  LmEval cur;
   if (HaveFinal) std::memcpy(cur.H, FinalH, sizeof(FinalH));
   else
   {

@@ -10,24 +10,12 @@
 #include <array>
 #include "../lsa_ctx.h"
 #include "lsa_hostmath.h"
+#include "lsa_lm_loop.h"  // SolveSummary, the loop itself
 
 namespace lsa
 {
 namespace host
 {
-
-// counterpart of ceres::Solver::Summary fields the reference reads (Slam.cxx:950, 1151)
-struct SolveSummary
-{
-  int num_successful_steps = 0;
-  int num_unsuccessful_steps = 0;
-  int num_iterations = 0;
-  int num_evaluations = 0;
-  double initial_cost = 0., final_cost = 0.;
-  int num_matches = 0;      // residual blocks (successful matches) the problem was built from
-  bool skipped = false;     // fewer than SetMinMatches(): nothing was optimised, the prior is returned
-  const char* message = "";
-};
 
 // LocalOptimizer::RegistrationError (LocalOptimizer.h:36-52)
 struct RegistrationError
@@ -77,7 +65,7 @@ private:
   void TakeResult(const lsa_solve_result_t& r, SolveSummary& summary);
 };
 
-// SolveSPD / SymEigen of lsa_lm.cpp for the self-test (lsa_selftest_numerics)
+// SolveSPD (lsa_lm_loop.cpp) / SymEigen for the self-test (lsa_selftest_numerics)
 bool ProbeSolveSPD(int n, const double* A, const double* b, double* x);
 void ProbeSymEigen(int n, const double* A, double* evals, double* evecs);
 

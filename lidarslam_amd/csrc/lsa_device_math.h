@@ -267,12 +267,12 @@ LSA_DEV void interp_eval(const InterpConst& c, double t, Rigid& out)
   out.t[2] = c.trans0[2] + time * (c.trans1[2] - c.trans0[2]);
 }
 
-// dense symmetric positive definite solve, as SolveSPD of host/lsa_lm.cpp: Cholesky, forward, backward
+// dense symmetric positive definite solve, as SolveSPD of host/lsa_lm_loop.cpp: Cholesky, forward, backward
 template <int N>
 __device__ __forceinline__ bool solve_spd(const double A[N * N], const double b[N], double x[N])
 {
   // (every division by a diagonal element is a multiplication by its reciprocal, taken once: 6 divisions instead of 27
-  // on the one thread that runs the step; host/lsa_lm.cpp and the oracle do the same, operation for operation)
+  // on the one thread that runs the step; host/lsa_lm_loop.cpp and the oracle do the same, operation for operation)
   double L[N * N], rinv[N];
 #pragma unroll
   for (int i = 0; i < N * N; ++i) L[i] = 0.;

@@ -1,6 +1,6 @@
 // lsa_lm.hip -- LocalOptimizer::Solve (slam_lib/src/LocalOptimizer.cxx:74-102) as ONE launch.
 //
-// The host-driven loop (host/lsa_lm.cpp) pays a kernel launch and a PCIe round trip per trust-region
+// The host-driven loop (host/lsa_lm_loop.cpp) pays a kernel launch and a PCIe round trip per trust-region
 // evaluation, ~4 per solve, ~25 per frame.  Here the whole Levenberg-Marquardt loop of Ceres (unpinned
 // master >= 2.0 in the reference CI: TukeyLoss a^2/3, ScaledLoss(weight), DENSE_QR on a 6-column
 // Jacobian = the 6x6 normal equations, Solver::Options defaults) runs inside one kernel:
@@ -296,7 +296,7 @@ __device__ __forceinline__ void finish_point(Shared& sh, double x, double y, dou
   }
 }
 
-// What the trust-region loop of host/lsa_lm.cpp (LocalOptimizer::Solve) does between two evaluations, N active
+// What the trust-region loop of host/lsa_lm_loop.cpp (LocalOptimizer::Solve) does between two evaluations, N active
 // parameters: all 6, or (x, y, rz) in 2D mode (SubsetParameterization(6, {2, 3, 4}), LocalOptimizer.cxx:89-90).
 // In: sh.sums[1 - cur_buf] = the sums at sh.w (the start point when first, a candidate afterwards).  Out: cand = the next
 // candidate, or true = the solve is over (sh.stop says so to the other wavefronts behind the barrier).
@@ -316,14 +316,22 @@ __device__ __forceinline__ void finish_point(Shared& sh, double x, double y, dou
 // candidate is accepted -- its loads and products are independent of the decision's divisions and run in their shadow --
 // and stored only if it is.  Everything the step reads from LDS is loaded at its head, one latency for all of it.
 // The arithmetic of every value is the host loop's, operation for operation, every sum in the host's order.
+// The orders are a contract (tests/lm_step_cases.py states the loop independently and compares bit patterns; device: this
+// step through lsa_selftest_lm_step, host: host/lsa_lm_loop.cpp through lsa_selftest_lm_host): Hs_ab = (H_ab s_a) s_b and
+// gs_a = g_a s_a; M_aa = Hs_aa + D_a / radius; every entry of the factor subtracts its products with k ascending and is
+// multiplied by the reciprocal of the pivot, 1 / sqrt(d); both substitutions subtract with k ascending; t_a = sum_b Hs_ab
+// step_b, s.g = sum_a step_a gs_a and s.Hs = sum_a step_a t_a from 0 in index order; the change is -s.g - 0.5 s.Hs;
+// cand_a = x_a + step_a s_a, |step|^2 = sum (x_a - cand_a)^2 in index order.
 template <int N> __device__ __forceinline__ constexpr int lm_act(int a) { return N == 6 ? a : (a == 2 ? 5 : a); }
+// the gradient tolerance: max |g_a| <= tolerance, said entry by entry -- a gradient with a NaN in it has not converged,
+// wherever the NaN stands (a maximum by comparisons loses it again at the next entry)
 template <int N>
-__device__ __forceinline__ double lm_grad_max(const double g[N])
+__device__ __forceinline__ bool lm_grad_below(const double g[N], double tolerance)
 {
-  double m = 0;
+  bool below = true;
 #pragma unroll
-  for (int a = 0; a < N; ++a) { const double v = __builtin_fabs(g[a]); m = m > v ? m : v; }  // std::max(m, v)
-  return m;
+  for (int a = 0; a < N; ++a) below = below && __builtin_fabs(g[a]) <= tolerance;
+  return below;
 }
 template <int N>
 __device__ __forceinline__ double lm_x_norm(const double x[6])
@@ -401,7 +409,7 @@ __device__ __forceinline__ bool lm_step(const LmParams& p, Shared& sh, bool firs
     for (int a = 0; a < N; ++a) scale[a] = lane_bcast(scale_row, a);
     if (lane < N) lm.scale[lane] = scale_row;
     if (l0) { lm.initial_cost = tot_cost; lm.cur_buf = cur_buf ^ 1; lm.successful = 1; }
-    if (lm_grad_max<N>(tot_g) <= gradient_tolerance)
+    if (lm_grad_below<N>(tot_g, gradient_tolerance))
     {
       if (l0) { lm.code = kCodeGradient0; sh.stop = 1; }
       return true;
@@ -474,7 +482,7 @@ __device__ __forceinline__ bool lm_step(const LmParams& p, Shared& sh, bool firs
       for (int a = 0; a < N; ++a) sh.gs[a] = gs[a];
     }
   }
-  const double grad_max = lm_grad_max<N>(g);
+  const bool grad_below = lm_grad_below<N>(g, gradient_tolerance);
   double Hdiag = Hrow[0];  // Hs(row, row)
 #pragma unroll
   for (int b = 1; b < N; ++b)
@@ -485,7 +493,7 @@ __device__ __forceinline__ bool lm_step(const LmParams& p, Shared& sh, bool firs
   while (true)
   {
     if (iter >= p.max_iter) { code = kCodeMaxIterations; break; }
-    if (grad_max <= gradient_tolerance) { code = kCodeGradient; break; }
+    if (grad_below) { code = kCodeGradient; break; }
     if (radius < min_trust_region_radius) { code = kCodeMinRadius; break; }
     ++iter;
     if (!reuse_diagonal)
@@ -706,6 +714,7 @@ __global__ __launch_bounds__(kLmThreads) void k_lm_solve(LmParams p, u64* __rest
       sh.st0 = 0;
       sh.tk = wall_clock64();
       sh.lap[5] = sh.tk;
+      // (k_selftest_lm_step starts the step from THE SAME VALUES: the two must stay equal)
       LmState& lm = sh.lm;
 #pragma unroll
       for (int v = 0; v < kAccumVals; ++v) sh.sums[0][v] = 0.;
@@ -772,6 +781,97 @@ __global__ __launch_bounds__(kLmThreads) void k_lm_solve(LmParams p, u64* __rest
     const u64 bits = (u64)__double_as_longlong(r);
     const unsigned word = half ? (unsigned)(bits >> 32) : (unsigned)(bits & 0xffffffffull);
     __hip_atomic_store(mailbox + threadIdx.x, ((u64)out_tag << 32) | word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+  }
+}
+
+// lsa_selftest_lm_step: lm_step on scripted sums, a workgroup of one wavefront per script.  What k_lm_solve's first
+// wavefront does between two evaluations, with the evaluation replaced by 29 values read from the script: the fold's last
+// store into sh.sums[1 - cur_buf], the step, the candidate's rotation, and one record of the state the step left.
+constexpr int kStepRecord = 42;  // include/lidarslam_amd.h: the record of lsa_selftest_lm_step
+__global__ __launch_bounds__(64) void k_selftest_lm_step(const int* __restrict__ header, const int* __restrict__ first_eval, const double* __restrict__ x0s,
+                                                         const double* __restrict__ sums, double* __restrict__ records, double* __restrict__ results,
+                                                         int* __restrict__ status)
+{
+  __shared__ Shared sh;
+  const int s = blockIdx.x;
+  const int two_d = header[4 * s], evals = header[4 * s + 3];
+  const size_t first = (size_t)first_eval[s];
+  LmParams p;  // (lm_step reads max_iter and min_matches, nothing else)
+  p.max_iter = header[4 * s + 1];
+  p.min_matches = header[4 * s + 2];
+  {
+    double x0[6];
+#pragma unroll
+    for (int a = 0; a < 6; ++a) x0[a] = x0s[(size_t)s * 6 + a];
+    if (threadIdx.x == 0)
+    {
+      // THE SAME VALUES as the head of k_lm_solve: the two must stay equal (st0 = 0: the step traces nothing)
+      for (int i = 0; i < 6; ++i) sh.lap[i] = 0;
+      for (int i = 0; i < 4; ++i) sh.sub[i] = 0;
+      sh.st0 = 0;
+      sh.tk = 0;
+      LmState& lm = sh.lm;
+#pragma unroll
+      for (int v = 0; v < kAccumVals; ++v) sh.sums[0][v] = 0.;
+      lm.cur_buf = 0;
+#pragma unroll
+      for (int a = 0; a < 6; ++a) { lm.x[a] = x0[a]; lm.scale[a] = 1.; lm.diag[a] = 0.; }
+      lm.radius = 1e4; lm.decrease_factor = 2.0; lm.x_norm = 0.; lm.model_cost_change = 0.; lm.delta_norm = 0.; lm.initial_cost = 0.;
+      lm.reuse_diagonal = 0; lm.consecutive_invalid = 0; lm.iter = 0;
+      lm.evaluations = 1; lm.successful = 0; lm.unsuccessful = 0; lm.iterations = 0; lm.code = kCodeNone; lm.skipped = 0; lm.matches = 0;
+      sh.stop = 0;
+      sh.failed = 0;
+    }
+    finish_point(sh, x0[0], x0[1], x0[2], x0[3], x0[4], x0[5]);
+  }
+  __syncthreads();
+  int used = 0;
+  bool stopped = false;
+  while (used < evals && !stopped)
+  {
+    // as the last lines of lm_evaluate's fold: lane v stores value v of the evaluation, the step's loads follow in order
+    if (threadIdx.x < kAccumVals) sh.sums[1 - sh.lm.cur_buf][threadIdx.x] = sums[(first + used) * kAccumVals + threadIdx.x];
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    double cand[6];
+    const bool stop = two_d ? lm_step<3>(p, sh, used == 0, cand) : lm_step<6>(p, sh, used == 0, cand);
+    if (!stop) finish_point(sh, cand[0], cand[1], cand[2], cand[3], cand[4], cand[5]);
+    __syncthreads();
+    if (threadIdx.x == 0)
+    {
+      const LmState& lm = sh.lm;
+      double* o = records + (first + used) * kStepRecord;
+#pragma unroll
+      for (int a = 0; a < 6; ++a) o[a] = stop ? 0. : cand[a];
+      o[6] = lm.code; o[7] = sh.stop;
+      o[8] = lm.radius; o[9] = lm.decrease_factor; o[10] = lm.x_norm; o[11] = lm.model_cost_change; o[12] = lm.delta_norm; o[13] = lm.initial_cost;
+      o[14] = lm.reuse_diagonal; o[15] = lm.consecutive_invalid; o[16] = lm.iter; o[17] = lm.evaluations; o[18] = lm.successful;
+      o[19] = lm.unsuccessful; o[20] = lm.iterations; o[21] = lm.skipped; o[22] = lm.matches;
+      for (int a = 0; a < 6; ++a) { o[23 + a] = lm.x[a]; o[29 + a] = lm.scale[a]; o[35 + a] = lm.diag[a]; }
+      o[41] = lm.cur_buf;
+    }
+    ++used;
+    stopped = sh.stop != 0;
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) { status[2 * s] = stopped ? 0 : 1; status[2 * s + 1] = used; }
+  // the result as k_lm_solve composes it: the pose and the counts from LmState, the sums from the buffer cur_buf names
+  if (threadIdx.x < kResCount)
+  {
+    const LmState& lm = sh.lm;
+    const int v = threadIdx.x;
+    double r = 0.;
+    if (v < kResInitial) r = lm.x[v - kResPose];
+    else if (v == kResInitial) r = lm.initial_cost;
+    else if (v == kResFinal) r = sh.sums[lm.cur_buf][0];
+    else if (v < kResSums + kAccumVals) r = sh.sums[lm.cur_buf][v - kResSums];
+    else if (v == kResSuccessful) r = lm.successful;
+    else if (v == kResUnsuccessful) r = lm.unsuccessful;
+    else if (v == kResIterations) r = lm.iterations;
+    else if (v == kResEvaluations) r = lm.evaluations;
+    else if (v == kResSkipped) r = lm.skipped;
+    else if (v == kResCode) r = lm.code;
+    else if (v == kResMatches) r = lm.matches;
+    results[(size_t)s * kResCount + v] = stopped ? r : 0.;  // (a script that ran out has no result)
   }
 }
 
@@ -1178,6 +1278,45 @@ int lsa_solve_device_interlude(lsa_ctx* ctx, void (*fn)(void*), void* arg)
   if (!ctx) return LSA_E_ARG;
   ctx->solve_hook = fn;
   ctx->solve_hook_arg = arg;
+  return LSA_OK;
+}
+
+int lsa_selftest_lm_step(lsa_ctx* ctx, int n_scripts, const int* header, const double* x0, const double* sums, double* records, double* results, int* status)
+{
+  if (!ctx) return LSA_E_ARG;
+  if (n_scripts <= 0 || n_scripts > 65536 || !header || !x0 || !sums || !records || !results || !status) return ctx->fail(LSA_E_ARG, "lsa_selftest_lm_step: bad argument");
+  std::vector<int> first(n_scripts);
+  size_t total = 0;
+  for (int s = 0; s < n_scripts; ++s)
+  {
+    if (header[4 * s + 1] < 0 || header[4 * s + 3] < 1 || header[4 * s + 3] > 4096) return ctx->fail(LSA_E_ARG, "lsa_selftest_lm_step: a script needs max_iter >= 0 and 1 to 4096 evaluations");
+    first[s] = (int)total;
+    total += (size_t)header[4 * s + 3];
+  }
+  LSA_HIP(ctx, hipSetDevice(ctx->device));
+  // doubles first (x0, sums, records, results), then the ints (header, first evaluation, status)
+  const size_t n = (size_t)n_scripts;
+  const size_t doubles = n * 6 + total * kAccumVals + total * kStepRecord + n * kResCount, ints = n * 4 + n + n * 2;
+  const int rc = ensure_scratch(ctx, doubles * sizeof(double) + ints * sizeof(int));
+  if (rc) return rc;
+  double* d_x0 = (double*)ctx->scratch_out;
+  double* d_sums = d_x0 + n * 6;
+  double* d_records = d_sums + total * kAccumVals;
+  double* d_results = d_records + total * kStepRecord;
+  int* d_header = (int*)(d_results + n * kResCount);
+  int* d_first = d_header + n * 4;
+  int* d_status = d_first + n;
+  LSA_HIP(ctx, hipMemcpyAsync(d_x0, x0, n * 6 * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+  LSA_HIP(ctx, hipMemcpyAsync(d_sums, sums, total * kAccumVals * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+  LSA_HIP(ctx, hipMemcpyAsync(d_header, header, n * 4 * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
+  LSA_HIP(ctx, hipMemcpyAsync(d_first, first.data(), n * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
+  LSA_HIP(ctx, hipMemsetAsync(d_records, 0, total * kStepRecord * sizeof(double), ctx->stream));  // evaluations behind the stop: zeros
+  hipLaunchKernelGGL(k_selftest_lm_step, dim3(n_scripts), dim3(64), 0, ctx->stream, d_header, d_first, d_x0, d_sums, d_records, d_results, d_status);
+  LSA_HIP(ctx, hipGetLastError());
+  LSA_HIP(ctx, hipMemcpyAsync(records, d_records, total * kStepRecord * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  LSA_HIP(ctx, hipMemcpyAsync(results, d_results, n * kResCount * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  LSA_HIP(ctx, hipMemcpyAsync(status, d_status, n * 2 * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+  LSA_HIP(ctx, hipStreamSynchronize(ctx->stream));
   return LSA_OK;
 }
 

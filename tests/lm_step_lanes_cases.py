@@ -16,7 +16,8 @@ rejections fall:
   wild_d   iterations 5 to 8 are rejected;
   wild_64  HDL-64: iterations 1 and 2 are rejected.
 In 2D mode z, rx and ry of a start are not parameters but stay part of the point, so a wild start is a tilted 2D problem.
-No start was found that makes the parent's damped Cholesky fail or the model's cost change negative (the invalid step).
+No start was found that makes the parent's damped Cholesky fail or the model's cost change negative (the invalid step):
+these records do not walk it.  tests/lm_step_cases.py does, with scripted sums instead of residual blocks.
 
 A case is (name, rings, two_d, w0 | None, max_iter, min_matches, give_up_block, restart_of, yaw_turns): with `restart_of`
 the start point is the pose the named case (run before it) returned, plus `yaw_turns` full turns on the yaw -- whole

@@ -8,8 +8,12 @@ of commit 3f43cd1 ("Split the SLAM host pipeline by job; one refusal path for th
 never from the code under test.  The comparison is `==` on the bit patterns of all 45 doubles of every case
 (tests/lm_step_lanes_cases.py).
 
-Not reached by any input found (a random search with the parent's library over some thousand starts): the invalid step --
-a failed Cholesky factorization or a negative model cost change; the damping makes it nearly unreachable.
+Not walked by these records: the invalid step -- a failed Cholesky factorization or a negative model cost change -- with its
+retry, the reset of the count and kCodeInvalidSteps; kCodeMinRadius; the clamps at max_radius and min_diagonal; kCodeGradient
+after iteration 0; non-finite sums.  No start on residual blocks was found that reaches them (a random search with the
+parent's library over some thousand starts): the residual blocks decide what the step sees.  tests/test_gpu_lm_step.py and
+tests/test_lm_step_reference.py walk them by feeding the step its 29 sums directly, against an independent statement of
+the loop (tests/lm_step_cases.py) instead of a parent's bits.
 """
 import os
 

@@ -518,7 +518,9 @@ int lsa_solve_device_trace(lsa_ctx* ctx, unsigned long long out[12]);
  *   "lm_blocks" (LSA_LM_BLOCKS 1..128), "lm_records" (LSA_LM_RECORDS 256..4096), "lm_cache" (LSA_LM_CACHE, at most the
  *   LDS layers the solve kernel has room for), "accum_blocks" (LSA_ACCUM_BLOCKS 1..256), "mailbox_check" (LSA_MAILBOX_CHECK)
  * and of the keypoint log: "kplog_chunk_kib" n (chunks made from now on hold n KiB; negative: 32 MiB again), "kplog_fail_alloc"
- * 1 / 0 (while 1, a chunk allocation fails as if the device were out of memory) */
+ * 1 / 0 (while 1, a chunk allocation fails as if the device were out of memory);
+ * and of the map descriptors: "map_describe_slice" n (points a slice of the next description; <= 0: 4096), "map_describe_cull"
+ * 1 / 0 (slices out of a viewpoint's reach are passed over, or read like the others: the same bytes either way) */
 int lsa_debug_set(lsa_ctx* ctx, const char* name, int value);
 /* The shape of the last one-launch solve (lsa_solve_device_begin): {workgroups, residual blocks per thread, of those kept
  * in LDS, residual blocks in all}. */
@@ -971,6 +973,61 @@ int lsa_place_select_host(const float* distance, const int32_t* shift, const dou
                           double max_distance, double max_descriptor_distance, int exclusion_half_window, lsa_place_candidate_t* out, int capacity);
 int lsa_slam_recognize_place(lsa_slam* s, int query, const lsa_place_search_t* search, lsa_place_candidate_t* out, int capacity);
 
+/* Place recognition against the MAPS: where in a loaded map is the vehicle, when nobody can say.  A saved
+ * map has no logged frames to compare with, only points; what is compared with the last frame's descriptor is the descriptor
+ * of the map AS SEEN FROM A VIEWPOINT, made for many viewpoints at once.
+ * - A viewpoint is a position v (three doubles) in the maps' frame; its axes are the maps' axes.  LIMIT: the BASE is assumed
+ *   level there -- roll and pitch are ignored.  A map point p takes part as the frame point x = (float)((double)p.x - v.x),
+ *   likewise y and z (lsa_scan_descriptor.h: map_coord); from there on the descriptor is the frame descriptor's, verbatim:
+ *   the descriptor of the map at v is lsa_scan_descriptor_host of the translated points of every map in type_mask --
+ *   unfiltered Get content, any order (a cell holds a maximum), a NaN takes no part.
+ * - The query is the last frame's raw keypoints in BASE (LSA_SET_RAW_CURRENT), the types of type_mask, described as a logged
+ *   frame is; distance, shift and yaw are those of "Place recognition" above.  A candidate's start guess for the localization
+ *   is Translation(v) * Rz(yaw): lsa_slam_set_world_transform_from_guess(candidate.guess).
+ * - host statement, no device: lsa_map_descriptor_host, and lsa_map_place_select_host: from a table of (distance, shift) for
+ *   V viewpoints (rows of three doubles) the admissible ones -- distance <= max_descriptor_distance if that is > 0, within
+ *   max_distance of near_xyz (a GPS fix, the last good pose) if max_distance > 0, a NaN distance never -- ranked by
+ *   (distance, index); a viewpoint within exclusion_radius metres (<=; only if exclusion_radius > 0) of one already picked is
+ *   passed over.  Returns how many of at most `capacity` were written.  search NULL = defaults.  LSA_E_ARG: V < 1, a
+ *   viewpoint or a search field that is not finite, sectors outside 1..120, no room.
+ * - lsa_slam_recognize_place_in_maps(viewpoints, V, search, out, capacity, summary): waits for the map workers, describes
+ *   the maps at the viewpoints on the device (k_map_describe; only when the descriptor's parameters, the viewpoints -- compared
+ *   by content -- or a used map changed since the last call: summary->described says how many viewpoints this call
+ *   described), describes the query, searches (k_place_search, exhaustive and exact) and selects on the host.  Returns the
+ *   number of candidates.  Changes nothing the next frame relies on, and does not move the pose.  LSA_E_STATE, with the
+ *   reason in lsa_slam_last_error, when no frame has been added since construction, Reset or SetWorldTransformFromGuess (the
+ *   raw keypoints are empty), or when every map in the mask is empty; LSA_E_ARG as the host statement. */
+typedef struct lsa_map_place_search_t
+{
+  lsa_place_params_t descriptor;
+  double max_descriptor_distance; /* <= 0: no descriptor gate (default 0) */
+  double exclusion_radius;        /* [m] <= 0: none (default 5) */
+  double near_xyz[3];             /* [m] in the maps' frame; read only when max_distance > 0 */
+  double max_distance;            /* [m] <= 0: no position gate (default 0) */
+} lsa_map_place_search_t;
+typedef struct lsa_map_place_candidate_t
+{
+  int32_t viewpoint;
+  int32_t shift;
+  float distance;
+  float reserved;
+  double yaw;                     /* [rad] */
+  double guess[16];               /* row-major Translation(viewpoint) * Rz(yaw) */
+} lsa_map_place_candidate_t;
+typedef struct lsa_map_place_summary_t
+{
+  int32_t viewpoints;
+  int32_t described;              /* viewpoints this call described (0: the table was kept) */
+  int64_t map_points[3];          /* points of each map that were described (0 for a type outside the mask) */
+  int64_t query_points[3];        /* keypoints of the query per type (0 for a type outside the mask) */
+} lsa_map_place_summary_t;
+void lsa_map_place_search_init(lsa_map_place_search_t* search);
+int lsa_map_descriptor_host(const lsa_place_params_t* params, const lsa_point_t* pts, int n, const double viewpoint[3], float* out);
+int lsa_map_place_select_host(const float* distance, const int32_t* shift, const double* viewpoints, int V, int sectors, const lsa_map_place_search_t* search,
+                              lsa_map_place_candidate_t* out, int capacity);
+int lsa_slam_recognize_place_in_maps(lsa_slam* s, const double* viewpoints, int V, const lsa_map_place_search_t* search, lsa_map_place_candidate_t* out, int capacity,
+                                     lsa_map_place_summary_t* summary);
+
 
 /* ------------------------------------------------------------------------- */
 /* LidarSlam::RollingGrid ON THE DEVICE (slam_lib/include/LidarSlam/RollingGrid.h:63-212, slam_lib/src/RollingGrid.cxx): the
@@ -1148,6 +1205,40 @@ int lsa_kplog_replay_to_grids(lsa_ctx* ctx, unsigned type_mask, const double* po
                               float last_min[3][3], float last_max[3][3]);
 int lsa_kplog_replay_range(lsa_ctx* ctx, unsigned type_mask, const double* poses, const double* times, int n, int first, int last, int rule,
                            lsa_point_t* const out[3], float box_min[3][3], float box_max[3][3]);
+
+/* ------------------------------------------------------------------------- */
+/* The table of map descriptors (lsa_map_place.hip; the definition: "Place recognition against the MAPS" above).  The context
+ * owns ONE table of V + 1 slots of rings * sectors + sectors floats: slot i < V is the descriptor of the maps at viewpoint i,
+ * slot V the query.  The source of the map points is "two float4 per point, n points" -- a device grid's own array of voxel
+ * points, or an uploaded lsa_point_t array --, cut into contiguous slices ("map_describe_slice" points each, default 4096):
+ *   k_map_slice_boxes  a workgroup per slice: its xy box (a NaN takes no part); once per map version
+ *   k_map_describe     a workgroup of 256 per viewpoint and row of slices (blockIdx.y strides the slices): an LDS image of the
+ *                      cells in the order-preserving coding of floats, LDS atomic max per point, then its non-empty words
+ *                      merged into the viewpoint's zeroed image in global memory by 32-bit integer atomic max.  A slice whose
+ *                      box lies farther from v than max_range * (1 + 2^-20) is passed over ("map_describe_cull" 0 switches
+ *                      that off); a point whose squared planar distance exceeds that reach squared is dropped before the
+ *                      square root and the angle.  Maxima commute: the bytes do not depend on the slicing or the cull.
+ *   k_map_finish       a workgroup per viewpoint: decodes, writes the cells and the column norms, rings ascending
+ * No float atomics; no workgroup waits for another.  The grids are read on their own stream behind their last modification,
+ * as lsa_device_grid_get reads them; the call returns when the table is written.
+ * - lsa_map_place_describe_points(params, pts, n, viewpoints, V): uploads the points and describes them; returns V.
+ * - lsa_map_place_describe_grids(grids, params, viewpoints, V): grids[k] (NULL allowed) of the types in type_mask, all of
+ *   this context.  The table is kept: when the parameters, the viewpoints (by content) and every used grid's modification
+ *   count are those of the table, nothing is launched and 0 is returned; otherwise V.
+ * - lsa_map_place_descriptors(first, last, out): copies slots first..last out (slot V only after a search described it).
+ * - lsa_map_place_search(params, set, distance_out, shift_out): describes the keypoint set `set` (types of type_mask) into
+ *   slot V with k_log_describe's code, ONE launch of k_place_search over the V viewpoints, ONE copy of the V (distance,
+ *   shift) pairs to pinned memory, one wait.
+ * - lsa_map_place_slices(boxes, capacity): the slices of the last description and (where boxes != NULL) their boxes, four
+ *   floats each (min x, min y, max x, max y); returns the number of slices.  lsa_map_place_viewpoints: V of the table (0: none).
+ * Refusals write nothing: LSA_E_ARG for parameters out of limits, V < 1, a viewpoint that is not finite, grids of another
+ * context, a bad range; LSA_E_STATE for no table, a table made under other parameters, or an empty query set. */
+int lsa_map_place_describe_points(lsa_ctx* ctx, const lsa_place_params_t* params, const lsa_point_t* pts, int n, const double* viewpoints, int V);
+int lsa_map_place_describe_grids(lsa_ctx* ctx, lsa_device_grid* const grids[3], const lsa_place_params_t* params, const double* viewpoints, int V);
+int lsa_map_place_descriptors(lsa_ctx* ctx, int first, int last, float* out);
+int lsa_map_place_search(lsa_ctx* ctx, const lsa_place_params_t* params, int set, float* distance_out, int32_t* shift_out);
+int lsa_map_place_slices(lsa_ctx* ctx, float* boxes, int capacity);
+int lsa_map_place_viewpoints(const lsa_ctx* ctx);
 
 /* ------------------------------------------------------------------------- */
 /* Pose-graph optimization of relative-pose edges: the odometry chain of a logged trajectory plus the loop-closure edges

@@ -234,6 +234,10 @@ SIGNATURES = {
     "lsa_place_distance_host": (i32, [vp, vp, vp, vp, vp]),
     "lsa_place_select_host": (i32, [vp, vp, vp, i32, i32, i32, f64, f64, f64, i32, vp, i32]),
     "lsa_slam_recognize_place": (i32, [vp, i32, vp, vp, i32]),
+    "lsa_map_place_search_init": (None, [vp]),
+    "lsa_map_descriptor_host": (i32, [vp, vp, i32, vp, vp]),
+    "lsa_map_place_select_host": (i32, [vp, vp, vp, i32, i32, vp, vp, i32]),
+    "lsa_slam_recognize_place_in_maps": (i32, [vp, vp, i32, vp, vp, i32, vp]),
     # ---- device maps
     "lsa_device_grid_create": (i32, [vp, P(vp)]),
     "lsa_device_grid_destroy": (None, [vp]),
@@ -285,6 +289,13 @@ SIGNATURES = {
     "lsa_kplog_replayed": (i64, [vp, i32, vp]),
     "lsa_kplog_replay_to_grids": (i32, [vp, u32, vp, vp, i32, i32, vp, vp, vp]),
     "lsa_kplog_replay_range": (i32, [vp, u32, vp, vp, i32, i32, i32, i32, vp, vp, vp]),
+    # ---- the table of map descriptors
+    "lsa_map_place_describe_points": (i32, [vp, vp, vp, i32, vp, i32]),
+    "lsa_map_place_describe_grids": (i32, [vp, vp, vp, vp, i32]),
+    "lsa_map_place_descriptors": (i32, [vp, i32, i32, vp]),
+    "lsa_map_place_search": (i32, [vp, vp, i32, vp, vp]),
+    "lsa_map_place_slices": (i32, [vp, vp, i32]),
+    "lsa_map_place_viewpoints": (i32, [vp]),
     # ---- pose graph
     "lsa_pgo_params_init": (None, [vp]),
     "lsa_pgo_solve_host": (i32, [vp, i32, vp, vp, i32, vp, vp, vp]),

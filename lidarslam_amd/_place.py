@@ -150,3 +150,152 @@ def place_select(distance, shift, poses, times, query, sectors=60, min_travelled
     if rc < 0:
         raise _error("lsa_place_select_host", rc, "bad argument")
     return _candidates(out, rc)
+
+
+# ---- place recognition against the maps: the map as seen from a viewpoint (include/lidarslam_amd.h) ----------
+class MapPlaceSearch(C.Structure):
+    """lsa_map_place_search_t: the descriptor's parameters and the selection's.  near_xyz is read only when max_distance > 0."""
+
+    _fields_ = [
+        ("descriptor", PlaceParams), ("max_descriptor_distance", C.c_double), ("exclusion_radius", C.c_double), ("near_xyz", C.c_double * 3),
+        ("max_distance", C.c_double),
+    ]
+
+    def __init__(self, max_descriptor_distance=0.0, exclusion_radius=5.0, near_xyz=(0.0, 0.0, 0.0), max_distance=0.0, **descriptor):
+        super().__init__(PlaceParams(**descriptor), max_descriptor_distance, exclusion_radius, (C.c_double * 3)(*[float(v) for v in near_xyz]), max_distance)
+
+
+class MapPlaceCandidateStruct(C.Structure):
+    """lsa_map_place_candidate_t."""
+
+    _fields_ = [("viewpoint", C.c_int32), ("shift", C.c_int32), ("distance", C.c_float), ("reserved", C.c_float), ("yaw", C.c_double), ("guess", C.c_double * 16)]
+
+
+class MapPlaceSummaryStruct(C.Structure):
+    """lsa_map_place_summary_t."""
+
+    _fields_ = [("viewpoints", C.c_int32), ("described", C.c_int32), ("map_points", C.c_int64 * 3), ("query_points", C.c_int64 * 3)]
+
+
+def _map_candidates(out, n):
+    """[(viewpoint, distance, shift, yaw, guess)]: distance a numpy float32, yaw a float [rad], guess (4, 4) float64"""
+    return [(int(c.viewpoint), np.float32(c.distance), int(c.shift), float(c.yaw), np.array(c.guess, np.float64).reshape(4, 4)) for c in out[:n]]
+
+
+def _as_points(points):
+    pts = np.asarray(points)
+    if pts.dtype != POINT_DTYPE:
+        xyz = np.asarray(points, np.float32).reshape(-1, 3)
+        pts = np.zeros(xyz.shape[0], POINT_DTYPE)
+        pts["x"], pts["y"], pts["z"] = xyz[:, 0], xyz[:, 1], xyz[:, 2]
+    return np.ascontiguousarray(pts.reshape(-1))
+
+
+def _as_viewpoints(viewpoints):
+    return np.ascontiguousarray(np.asarray(viewpoints, np.float64).reshape(-1, 3))
+
+
+def map_descriptor(points, viewpoint, **params):
+    """The host statement of the descriptor of a map as seen from `viewpoint` (lsa_map_descriptor_host): points a POINT_DTYPE
+    array, or (n, 3) xyz, of every map that takes part; viewpoint (3,) in the maps' frame -> float32 (rings * sectors +
+    sectors,).  By definition scan_descriptor of the points translated as x = float32(float64(p.x) - v.x).  params:
+    PlaceParams' fields."""
+    p = PlaceParams(**params)
+    pts = _as_points(points)
+    v = np.ascontiguousarray(np.asarray(viewpoint, np.float64).reshape(-1))
+    if v.size != 3:
+        raise _error("lsa_map_descriptor_host", E_ARG, "a viewpoint is three coordinates")
+    out = np.zeros(max(p.rings, 0) * max(p.sectors, 0) + max(p.sectors, 0), np.float32)
+    rc = lib().lsa_map_descriptor_host(C.byref(p), ptr(pts) if pts.size else None, pts.size, ptr(v), ptr(out))
+    if rc < 0:
+        raise _error("lsa_map_descriptor_host", rc, "parameters out of limits or a viewpoint that is not finite")
+    return out
+
+
+def map_place_select(distance, shift, viewpoints, capacity=5, **search):
+    """The host statement of the selection among viewpoints (lsa_map_place_select_host): distance / shift the table of the V
+    viewpoints (V, 3) -> [(viewpoint, distance, shift, yaw, guess)], best first; guess = Translation(viewpoint) @ Rz(yaw).
+    search: MapPlaceSearch's fields and PlaceParams' (of which the selection reads sectors)."""
+    p = MapPlaceSearch(**search)
+    vp = _as_viewpoints(viewpoints)
+    d = np.ascontiguousarray(np.asarray(distance, np.float32).reshape(-1))
+    s = np.ascontiguousarray(np.asarray(shift, np.int32).reshape(-1))
+    if d.size != vp.shape[0] or s.size != vp.shape[0]:
+        raise _error("lsa_map_place_select_host", E_ARG, "a table of another length than the viewpoints")
+    out = (MapPlaceCandidateStruct * max(int(capacity), 1))()
+    rc = lib().lsa_map_place_select_host(ptr(d) if d.size else None, ptr(s) if s.size else None, ptr(vp) if vp.size else None, vp.shape[0], p.descriptor.sectors,
+                                         C.byref(p), out, int(capacity))
+    if rc < 0:
+        raise _error("lsa_map_place_select_host", rc, "bad argument")
+    return _map_candidates(out, rc)
+
+
+def map_place_describe(ctx, points_or_grids, viewpoints, **params):
+    """Fills the context's table of map descriptors (k_map_describe): points_or_grids a POINT_DTYPE array (uploaded), or a
+    sequence of three DeviceGrid / None, the maps by type, read where they live.  Returns how many viewpoints were described:
+    all, or 0 when the grids, the viewpoints and the parameters are those of the table (it is kept)."""
+    p = PlaceParams(**params)
+    vp = _as_viewpoints(viewpoints)
+    if isinstance(points_or_grids, (list, tuple)) and len(points_or_grids) == 3 and all(g is None or hasattr(g, "h") for g in points_or_grids):
+        grids = (C.c_void_p * 3)(*[None if g is None else g.h for g in points_or_grids])
+        return ctx._check(ctx.L.lsa_map_place_describe_grids(ctx.h, grids, C.byref(p), ptr(vp) if vp.size else None, vp.shape[0]), "lsa_map_place_describe_grids")
+    pts = _as_points(points_or_grids)
+    return ctx._check(ctx.L.lsa_map_place_describe_points(ctx.h, C.byref(p), ptr(pts) if pts.size else None, pts.size, ptr(vp) if vp.size else None, vp.shape[0]),
+                      "lsa_map_place_describe_points")
+
+
+def map_place_descriptors(ctx, first, last, out=None, **params):
+    """slots first..last of the context's table -> float32 (last - first + 1, length); slot V, the query's, once a search
+    has described it.  params: PlaceParams' fields as the table was made under (they give the length of a slot)."""
+    count = max(int(last) - int(first) + 1, 1)
+    if out is None:
+        out = np.zeros((count, max(PlaceParams(**params).length, 1)), np.float32)
+    ctx._check(ctx.L.lsa_map_place_descriptors(ctx.h, int(first), int(last), ptr(out)), "lsa_map_place_descriptors")
+    return out
+
+
+def map_place_search(ctx, kset, out=None, **params):
+    """The keypoint set `kset` of the context against the table's V viewpoints (k_log_describe into the query's slot, then
+    k_place_search) -> (distance float32 (V,), shift int32 (V,)), written into out = (distance, shift) where given."""
+    p = PlaceParams(**params)
+    v = ctx.L.lsa_map_place_viewpoints(ctx.h)
+    d, s = out if out is not None else (np.zeros(max(v, 1), np.float32), np.zeros(max(v, 1), np.int32))
+    ctx._check(ctx.L.lsa_map_place_search(ctx.h, C.byref(p), int(kset), ptr(d), ptr(s)), "lsa_map_place_search")
+    return d[:v], s[:v]
+
+
+def map_place_slices(ctx):
+    """the slices of the table's last description -> float32 (slices, 4): min x, min y, max x, max y of each"""
+    n = ctx._check(ctx.L.lsa_map_place_slices(ctx.h, None, 0), "lsa_map_place_slices")
+    out = np.zeros((max(n, 1), 4), np.float32)
+    ctx._check(ctx.L.lsa_map_place_slices(ctx.h, ptr(out), out.shape[0]), "lsa_map_place_slices")
+    return out[:n]
+
+
+class MapPlaceSummary:
+    """What recognize_place_in_maps says beside the candidates: viewpoints, described (viewpoints this call described; 0: the
+    table was kept), map_points / query_points (3,) per keypoint type."""
+
+    def __init__(self, r):
+        self.viewpoints, self.described = int(r.viewpoints), int(r.described)
+        self.map_points = np.array(r.map_points, np.int64)
+        self.query_points = np.array(r.query_points, np.int64)
+
+
+def recognize_place_in_maps(slam, viewpoints=None, capacity=5, **search):
+    """Place recognition against the maps (lsa_slam_recognize_place_in_maps): the viewpoints (V, 3), positions in the maps'
+    frame, from which the maps look like the last frame -> ([(viewpoint, distance, shift, yaw, guess)], MapPlaceSummary), best
+    first.  slam.set_world_transform_from_guess(guess) starts the localization there; the call itself moves nothing.
+    viewpoints None: the positions of slam.trajectory().  search: MapPlaceSearch's fields and PlaceParams'.  Raises LsaError
+    (.code E_STATE or E_ARG) when it cannot."""
+    p = MapPlaceSearch(**search)
+    if viewpoints is None:
+        viewpoints = np.asarray(slam.trajectory()[0], np.float64).reshape(-1, 4, 4)[:, :3, 3]
+        if viewpoints.shape[0] == 0:
+            raise _error("lsa_slam_recognize_place_in_maps", E_ARG, "the trajectory is empty and no viewpoints were given")
+    vp = _as_viewpoints(viewpoints)
+    out = (MapPlaceCandidateStruct * max(int(capacity), 1))()
+    summary = MapPlaceSummaryStruct()
+    n = slam._check(slam.L.lsa_slam_recognize_place_in_maps(slam.h, ptr(vp) if vp.size else None, vp.shape[0], C.byref(p), out, int(capacity), C.byref(summary)),
+                    "lsa_slam_recognize_place_in_maps")
+    return _map_candidates(out, n), MapPlaceSummary(summary)

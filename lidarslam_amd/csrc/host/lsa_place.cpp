@@ -101,6 +101,75 @@ int PlaceSelect(const float* distance, const int32_t* shift, const double* poses
   return found;
 }
 
+int MapDescriptor(const lsa_place_params_t& p, const lsa_point_t* pts, int n, const double viewpoint[3], float* out)
+{
+  if (!place::params_ok(p) || !out || n < 0 || (n > 0 && !pts) || !viewpoint) return LSA_E_ARG;
+  for (int d = 0; d < 3; ++d)
+    if (!(viewpoint[d] - viewpoint[d] == 0.)) return LSA_E_ARG;
+  // the definition, literally: the frame descriptor of the translated points
+  std::vector<lsa_point_t> moved(pts, pts + n);
+  for (lsa_point_t& q : moved)
+  {
+    q.x = place::map_coord(q.x, viewpoint[0]);
+    q.y = place::map_coord(q.y, viewpoint[1]);
+    q.z = place::map_coord(q.z, viewpoint[2]);
+  }
+  return ScanDescriptor(p, moved.data(), n, out);
+}
+
+bool MapSearchOk(const lsa_map_place_search_t& s)
+{
+  auto finite = [](double v) { return v - v == 0.; };
+  if (!place::params_ok(s.descriptor) || !finite(s.max_descriptor_distance) || !finite(s.exclusion_radius) || !finite(s.max_distance)) return false;
+  if (s.max_distance > 0. && !(finite(s.near_xyz[0]) && finite(s.near_xyz[1]) && finite(s.near_xyz[2]))) return false;
+  return true;
+}
+
+int MapPlaceSelect(const float* distance, const int32_t* shift, const double* viewpoints, int V, int sectors, const lsa_map_place_search_t& s,
+                   lsa_map_place_candidate_t* out, int capacity)
+{
+  if (!distance || !shift || !viewpoints || V < 1 || sectors < 1 || sectors > place::kMaxSectors || capacity < 0 || (capacity > 0 && !out) || !MapSearchOk(s))
+    return LSA_E_ARG;
+  for (size_t i = 0; i < 3 * static_cast<size_t>(V); ++i)
+    if (!(viewpoints[i] - viewpoints[i] == 0.)) return LSA_E_ARG;
+  auto metres = [&](const double* a, const double* b) {
+    const double dx = a[0] - b[0], dy = a[1] - b[1], dz = a[2] - b[2];
+    return std::sqrt(dx * dx + dy * dy + dz * dz);
+  };
+  std::vector<char> eligible(static_cast<size_t>(V), 0);
+  for (int i = 0; i < V; ++i)
+  {
+    if (distance[i] != distance[i]) continue;  // (a NaN has no rank)
+    if (s.max_descriptor_distance > 0. && !(static_cast<double>(distance[i]) <= s.max_descriptor_distance)) continue;
+    if (s.max_distance > 0. && !(metres(viewpoints + 3 * static_cast<size_t>(i), s.near_xyz) <= s.max_distance)) continue;
+    eligible[i] = 1;
+  }
+  int found = 0;
+  while (found < capacity)
+  {
+    int best = -1;
+    for (int i = 0; i < V; ++i)
+      if (eligible[i] && (best < 0 || distance[i] < distance[best])) best = i;  // ascending: the lower index on a tie
+    if (best < 0) break;
+    const double* v = viewpoints + 3 * static_cast<size_t>(best);
+    lsa_map_place_candidate_t c;
+    std::memset(&c, 0, sizeof(c));
+    c.viewpoint = best;
+    c.shift = shift[best];
+    c.distance = distance[best];
+    c.yaw = place::yaw_of(shift[best], sectors);
+    const double cy = std::cos(c.yaw), sy = std::sin(c.yaw);
+    const double guess[16] = {cy, -sy, 0., v[0], sy, cy, 0., v[1], 0., 0., 1., v[2], 0., 0., 0., 1.};  // Translation(v) * Rz(yaw)
+    std::memcpy(c.guess, guess, sizeof(guess));
+    out[found++] = c;
+    eligible[best] = 0;
+    if (s.exclusion_radius > 0.)
+      for (int i = 0; i < V; ++i)
+        if (eligible[i] && metres(viewpoints + 3 * static_cast<size_t>(i), v) <= s.exclusion_radius) eligible[i] = 0;
+  }
+  return found;
+}
+
 }  // namespace host
 }  // namespace lsa
 
@@ -145,6 +214,29 @@ int lsa_place_select_host(const float* distance, const int32_t* shift, const dou
 {
   return lsa::host::PlaceSelect(distance, shift, poses17, n, query, sectors, min_travelled, max_distance, max_descriptor_distance, exclusion_half_window, out,
                                 capacity);
+}
+
+void lsa_map_place_search_init(lsa_map_place_search_t* search)
+{
+  if (!search) return;
+  std::memset(search, 0, sizeof(*search));
+  lsa_place_params_init(&search->descriptor);
+  search->exclusion_radius = 5.;
+}
+
+int lsa_map_descriptor_host(const lsa_place_params_t* params, const lsa_point_t* pts, int n, const double viewpoint[3], float* out)
+{
+  if (!params) return LSA_E_ARG;
+  return lsa::host::MapDescriptor(*params, pts, n, viewpoint, out);
+}
+
+int lsa_map_place_select_host(const float* distance, const int32_t* shift, const double* viewpoints, int V, int sectors, const lsa_map_place_search_t* search,
+                              lsa_map_place_candidate_t* out, int capacity)
+{
+  lsa_map_place_search_t s;
+  lsa_map_place_search_init(&s);
+  if (search) s = *search;
+  return lsa::host::MapPlaceSelect(distance, shift, viewpoints, V, sectors, s, out, capacity);
 }
 
 }  // extern "C"

@@ -17,5 +17,11 @@ int PlaceDistance(const lsa_place_params_t& p, const float* a, const float* b, f
 // lsa_place_select_host (include/lidarslam_amd.h)
 int PlaceSelect(const float* distance, const int32_t* shift, const double* poses17, int n, int query, int sectors, double minTravelled, double maxDistance,
                 double maxDescriptorDistance, int exclusionHalfWindow, lsa_place_candidate_t* out, int capacity);
+// the descriptor of a map as seen from a viewpoint (lsa_scan_descriptor.h: map_coord): ScanDescriptor of the translated points
+int MapDescriptor(const lsa_place_params_t& p, const lsa_point_t* pts, int n, const double viewpoint[3], float* out);
+// lsa_map_place_select_host (include/lidarslam_amd.h)
+bool MapSearchOk(const lsa_map_place_search_t& s);
+int MapPlaceSelect(const float* distance, const int32_t* shift, const double* viewpoints, int V, int sectors, const lsa_map_place_search_t& s,
+                   lsa_map_place_candidate_t* out, int capacity);
 }  // namespace host
 }  // namespace lsa

@@ -79,6 +79,7 @@ void RollingGrid::Reset(const float position[3])
 // RollingGrid.cxx:51-56
 void RollingGrid::Clear()
 {
+  ++Modifications;
   NbPoints = 0;
   Voxels.clear();
   SubMapValid = false;
@@ -139,6 +140,7 @@ RollingGrid::PointCloud RollingGrid::Get(bool clean) const
 // RollingGrid.cxx:117-157
 void RollingGrid::Roll(const float minPoint[3], const float maxPoint[3])
 {
+  ++Modifications;
   const float half = static_cast<float>(static_cast<double>(GridSize) / 2 * VoxelResolution);
   const float res = static_cast<float>(VoxelResolution);
   int shift[3];
@@ -180,6 +182,7 @@ void RollingGrid::Roll(const float minPoint[3], const float maxPoint[3])
 void RollingGrid::Add(const lsa_point_t* points, size_t count, bool fixed, double currentTime, bool roll)
 {
   if (count == 0) return;
+  ++Modifications;
   if (roll)
   {
     float mn[3], mx[3];
@@ -531,6 +534,7 @@ void RollingGrid::SetAddThreads(int n)
 // RollingGrid.cxx:325-351
 void RollingGrid::ClearOldPoints(double currentTime)
 {
+  ++Modifications;
   for (auto out = Voxels.begin(); out != Voxels.end();)
   {
     for (auto in = out->second.begin(); in != out->second.end();)

@@ -93,6 +93,8 @@ public:
 
   PointCloud Get(bool clean = false) const;
   unsigned int Size() const { return this->NbPoints; }
+  // Add, Roll, Clear and ClearOldPoints so far: what a reader of the map keeps its results by (the device grids count alike)
+  unsigned long long GetModifications() const { return this->Modifications; }
   void Roll(const float minPoint[3], const float maxPoint[3]);
   void Add(const PointCloud& pointcloud, bool fixed = false, double currentTime = -1., bool roll = true)
   {
@@ -126,6 +128,7 @@ private:
   float VoxelGridPosition[3] = {0.f, 0.f, 0.f};
   unsigned int NbPoints = 0;
   unsigned int AddSerial = 0;
+  unsigned long long Modifications = 0;
   PointCloud SubMapOwn;
   std::function<lsa_point_t*(std::size_t)> SubMapStorage;
   lsa_point_t* SubMapPtr = nullptr;

@@ -343,6 +343,13 @@ int lsa_slam_recognize_place(lsa_slam* s, int query, const lsa_place_search_t* s
   return s->core.RecognizePlace(query, search, out, capacity);
 }
 
+int lsa_slam_recognize_place_in_maps(lsa_slam* s, const double* viewpoints, int V, const lsa_map_place_search_t* search, lsa_map_place_candidate_t* out, int capacity,
+                                     lsa_map_place_summary_t* summary)
+{
+  if (!s) return LSA_E_ARG;
+  return s->core.RecognizePlaceInMaps(viewpoints, V, search, out, capacity, summary);
+}
+
 int lsa_slam_optimize_logged_trajectory(lsa_slam* s, const lsa_pgo_edge_t* loop_edges, int m, const lsa_pgo_params_t* params, double* poses17_out, int capacity,
                                         lsa_pgo_result_t* result)
 {

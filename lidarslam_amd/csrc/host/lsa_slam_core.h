@@ -102,6 +102,12 @@ public:
   // (lsa_slam_recognize_place in lidarslam_amd.h).  Runs on the log's context after the map workers; reads the log, writes
   // the log's descriptor store and nothing else.  Returns the number of candidates written.
   int RecognizePlace(int query, const lsa_place_search_t* search, lsa_place_candidate_t* out, int capacity);
+  // Place recognition against the maps: the viewpoints from which the maps look like the last frame (lsa_slam_recognize_place_in_maps
+  // in lidarslam_amd.h).  Runs after the map workers; reads the maps and the raw keypoints, writes the context's table of map
+  // descriptors and nothing else; the pose is the caller's to set (SetWorldTransformFromGuess(candidate.guess)).  A refusal
+  // changes nothing and leaves its reason in Error().
+  int RecognizePlaceInMaps(const double* viewpoints, int V, const lsa_map_place_search_t* search, lsa_map_place_candidate_t* out, int capacity,
+                           lsa_map_place_summary_t* summary);
   // Pose-graph optimization of the logged trajectory with the caller's loop edges (lsa_slam_optimize_logged_trajectory in
   // lidarslam_amd.h): the solve runs on the scratch context; with params->apply the result goes through
   // SetTrajectoryAndRebuildMaps, without it nothing of the frame path is touched.  Returns the number of poses.
@@ -265,6 +271,14 @@ public:
 
 private:
   int Fail(int rc, const char* where);
+  // what the context's table of map descriptors was made of when the maps live on the host: the device grids keep count themselves
+  struct HostMapTable
+  {
+    bool valid = false;
+    lsa_place_params_t params;
+    std::vector<double> viewpoints;
+    unsigned long long modifications[3] = {0, 0, 0};
+  } MapPlaceHostTable;
   lsa_ctx* Ctx = nullptr;
   std::string LastError;
 

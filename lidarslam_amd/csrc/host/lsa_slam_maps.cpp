@@ -4,8 +4,10 @@
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
+#include <cstring>
 #include <ctime>
 #include "lsa_pcd.h"
+#include "lsa_place.h"
 
 namespace lsa
 {
@@ -506,6 +508,91 @@ int SlamCore::GetTargetSubMap(int k, std::vector<lsa_point_t>& out)
   const RollingGrid& map = Map(k);
   out.assign(map.SubMapData(), map.SubMapData() + map.SubMapSize());
   return static_cast<int>(out.size());
+}
+
+// ---- place recognition against the maps: where in a loaded map is the vehicle (lsa_map_place.hip) -----------
+int SlamCore::RecognizePlaceInMaps(const double* viewpoints, int V, const lsa_map_place_search_t* search, lsa_map_place_candidate_t* out, int capacity,
+                                   lsa_map_place_summary_t* summary)
+{
+  if (!Ctx) return LSA_E_NO_DEVICE;
+  const std::string who = "RecognizePlaceInMaps: ";
+  if (capacity < 0 || (capacity > 0 && !out)) { LastError = who + "no place for the candidates"; return LSA_E_ARG; }
+  lsa_map_place_search_t p;
+  lsa_map_place_search_init(&p);
+  if (search) p = *search;
+  if (!MapSearchOk(p)) { LastError = who + "parameters out of limits"; return LSA_E_ARG; }
+  if (!viewpoints || V < 1) { LastError = who + "at least one viewpoint"; return LSA_E_ARG; }
+  for (size_t i = 0; i < 3 * static_cast<size_t>(V); ++i)
+    if (!(viewpoints[i] - viewpoints[i] == 0.)) { LastError = who + "viewpoint " + std::to_string(i / 3) + " is not finite"; return LSA_E_ARG; }
+  const lsa_place_params_t& d = p.descriptor;
+  lsa_map_place_summary_t sum;
+  std::memset(&sum, 0, sizeof(sum));
+  sum.viewpoints = V;
+  long long queryPoints = 0;
+  for (int k = 0; k < 3; ++k)
+    if ((d.type_mask >> k) & 1u) queryPoints += sum.query_points[k] = std::max(lsa_keypoint_count(Ctx, LSA_SET_RAW_CURRENT, k), 0);
+  if (queryPoints == 0)
+  {
+    LastError = who + "there are no keypoints to describe: no frame has been added since construction, Reset or SetWorldTransformFromGuess";
+    return LSA_E_STATE;
+  }
+  // the device works from here on: the map workers and the look-ahead have enqueued what they had (nothing of theirs is changed)
+  WaitMaps();
+  const bool onDevice = DeviceMapsInUse();
+  long long mapPoints = 0;
+  for (int k = 0; k < 3; ++k)
+    if ((d.type_mask >> k) & 1u)
+      mapPoints += sum.map_points[k] = onDevice ? static_cast<long long>(lsa_device_grid_get_param(DevMaps[k], "Voxels")) : static_cast<long long>(LocalMaps[k]->Size());
+  if (mapPoints == 0) { LastError = who + "every map of the type mask is empty"; return LSA_E_STATE; }
+  int described = 0;
+  if (onDevice)
+  {
+    MapPlaceHostTable.valid = false;
+    lsa_device_grid* grids[3] = {DevMaps[0], DevMaps[1], DevMaps[2]};
+    described = lsa_map_place_describe_grids(Ctx, grids, &d, viewpoints, V);
+  }
+  else
+  {
+    HostMapTable& t = MapPlaceHostTable;
+    bool same = t.valid && std::memcmp(&t.params, &d, sizeof(d)) == 0 && t.viewpoints.size() == 3 * static_cast<size_t>(V) &&
+                std::memcmp(t.viewpoints.data(), viewpoints, t.viewpoints.size() * sizeof(double)) == 0;
+    for (int k = 0; k < 3 && same; ++k)
+      if ((d.type_mask >> k) & 1u) same = t.modifications[k] == LocalMaps[k]->GetModifications();
+    if (!same)
+    {
+      // Get into one array, which the context uploads and describes
+      t.valid = false;
+      std::vector<lsa_point_t> all;
+      all.reserve(static_cast<size_t>(mapPoints));
+      for (int k = 0; k < 3; ++k)
+        if ((d.type_mask >> k) & 1u)
+        {
+          const RollingGrid::PointCloud pts = LocalMaps[k]->Get();
+          all.insert(all.end(), pts.begin(), pts.end());
+          t.modifications[k] = LocalMaps[k]->GetModifications();
+        }
+      described = lsa_map_place_describe_points(Ctx, &d, all.data(), static_cast<int>(all.size()), viewpoints, V);
+      if (described >= 0)
+      {
+        t.params = d;
+        t.viewpoints.assign(viewpoints, viewpoints + 3 * static_cast<size_t>(V));
+        t.valid = true;
+      }
+    }
+  }
+  if (described < 0) { LastError = who + lsa_last_error(Ctx); return described; }
+  sum.described = described;
+  std::vector<float> distance(static_cast<size_t>(V));
+  std::vector<int32_t> shift(static_cast<size_t>(V));
+  if (const int rc = lsa_map_place_search(Ctx, &d, LSA_SET_RAW_CURRENT, distance.data(), shift.data()); rc < 0)
+  {
+    LastError = who + lsa_last_error(Ctx);
+    return rc;
+  }
+  const int found = MapPlaceSelect(distance.data(), shift.data(), viewpoints, V, d.sectors, p, out, capacity);
+  if (found < 0) { LastError = who + "bad argument"; return found; }
+  if (summary) *summary = sum;
+  return found;
 }
 
 // The maps live either in the device grids or in the host grids ("MapsOnDevice" = 0): a setter that

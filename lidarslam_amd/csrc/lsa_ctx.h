@@ -138,6 +138,7 @@ struct PendingEvent
 struct KpLog;  // lsa_kplog.hip
 struct PlaceStore;  // lsa_place.hip
 struct PgoBuffers;  // lsa_pose_graph.hip
+struct MapPlaceStore;  // lsa_map_place.hip
 
 }  // namespace lsa
 
@@ -330,6 +331,10 @@ struct lsa_ctx
   // the log's descriptor store (lsa_place.hip): made by the first describe, follows the log's appends, pops and clears
   lsa::PlaceStore* place = nullptr;
   int place_max_blocks = 0;                     // lsa_debug_set "place_max_blocks": 0 = the default
+  // the table of map descriptors (lsa_map_place.hip): made by the first description, kept until the context goes
+  lsa::MapPlaceStore* map_place = nullptr;
+  int map_describe_slice = 0;                   // lsa_debug_set "map_describe_slice": points a slice, 0 = the default
+  bool map_describe_cull = true;                // lsa_debug_set "map_describe_cull": slices out of a viewpoint's reach are passed over
   // the pose-graph solver's buffers (lsa_pose_graph.hip): made by the first call, grown through the graveyard
   lsa::PgoBuffers* pgo = nullptr;
 
@@ -373,6 +378,7 @@ extern std::atomic<int> g_live_contexts;  // contexts of this process (lsa_lm.hi
 int lm_blocks_share();
 void kplog_destroy(lsa_ctx* ctx);  // lsa_kplog.hip
 void pgo_destroy(lsa_ctx* ctx);    // lsa_pose_graph.hip
+void map_place_destroy(lsa_ctx* ctx);  // lsa_map_place.hip
 inline void retire_dev(lsa_ctx* ctx, void* p)
 {
   if (!p) return;

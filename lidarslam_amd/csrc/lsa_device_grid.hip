@@ -273,6 +273,7 @@ int refresh_state(lsa_device_grid* g)
 // voxels, and ("Ordered" = 0) the last record replayed and room for the next one's `record_entries` keys ...
 int begin_modification(lsa_device_grid* g, int voxels_wanted, size_t record_entries)
 {
+  ++g->version;
   int rc = after_submap(g);
   if (!rc) rc = ensure_map(g, voxels_wanted);
   if (!rc && !g->Ordered) rc = apply_record(g);
@@ -412,6 +413,7 @@ int lsa_device_grid_reset(lsa_device_grid* g, const float position[3])
   G_HIP(hipStreamSynchronize(g->stream));
   G_HIP(hipMemcpy(g->st, h, sizeof(h), hipMemcpyHostToDevice));
   std::memcpy(g->host_st, h, sizeof(h));
+  ++g->version;
   g->n_upper = 0;
   g->submap_valid = false;
   return g->Ordered ? LSA_OK : forget_records(g);  // Reset goes through Clear (RollingGrid.cxx:40-48)
@@ -425,6 +427,7 @@ int lsa_device_grid_clear(lsa_device_grid* g)
   if (rc) return rc;
   hipLaunchKernelGGL(k_set_int, dim3(1), dim3(64), 0, g->stream, g->st + kStN, 0);
   hipLaunchKernelGGL(k_set_int, dim3(1), dim3(64), 0, g->stream, g->st + kStNbPoints, 0);
+  ++g->version;
   g->n_upper = 0;
   g->submap_valid = false;
   if (!g->Ordered) rc = forget_records(g);

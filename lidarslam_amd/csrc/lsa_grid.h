@@ -66,6 +66,7 @@ struct lsa_device_grid
   int cur = 0;
   int cap = 0;
   int n_upper = 0;  // upper bound of the number of voxels (what has been added so far)
+  unsigned long long version = 0;  // modifications enqueued so far (Add, Roll, decay, Clear, Reset): what a reader of the map keeps its results by
   int* st = nullptr;           // device state (16 ints)
   int* host_st = nullptr;      // pinned copy of it, refreshed behind every modification
   hipEvent_t ev_state = nullptr;

@@ -14,6 +14,7 @@
 #include <vector>
 #include "lsa_ctx.h"
 #include "lsa_kplog_io.h"
+#include "lsa_place_io.h"
 #include "lsa_scan_descriptor.h"
 #include "lsa_wave.h"
 
@@ -21,11 +22,6 @@ using namespace lsa;
 
 namespace lsa
 {
-struct PlaceResult
-{
-  float distance;
-  int shift;
-};
 struct PlaceStore
 {
   lsa_place_params_t params;
@@ -81,13 +77,6 @@ constexpr int kMaxCells = place::kMaxRings * place::kMaxSectors;
 constexpr int kMaxLength = kMaxCells + place::kMaxSectors;
 // k_place_search's LDS at the largest shape: two descriptors and a tile of cosines with rows of an odd length
 static_assert((2 * kMaxLength + kShiftTile * (place::kMaxSectors | 1)) * sizeof(float) <= 64 * 1024, "k_place_search keeps to 64 KB of LDS");
-
-struct DescribeFrame
-{
-  const float4* pts[3];  // the frame's keypoints in the log (a LidarPoint is two float4: x y z w, then the rest)
-  int n[3];              // 0 for a type outside the mask
-  int slot;
-};
 
 // A workgroup per frame.  The image of the cells is LDS words in the order-preserving coding of floats (f2ou), 0 = no
 // point yet (no float codes to 0 but a NaN, and a NaN takes no part), so the largest offer of a cell is one LDS atomic max
@@ -206,6 +195,34 @@ __global__ __launch_bounds__(kSearchThreads) void k_place_search(SearchArgs a, l
   }
 }
 
+}  // namespace
+
+namespace lsa
+{
+void place_describe_launch(const DescribeFrame* frames_dev, int count, float* slots, int stride, const lsa_place_params_t& p, hipStream_t stream)
+{
+  hipLaunchKernelGGL(k_log_describe, dim3((unsigned)count), dim3(kDescribeThreads), 0, stream, frames_dev, slots, stride, p);
+}
+void place_search_launch(lsa_ctx* ctx, const float* slots, long long cap, long long head, int stride, int query, int first, int count, PlaceResult* out_dev,
+                         const lsa_place_params_t& p, hipStream_t stream)
+{
+  const size_t lds = (size_t)(2 * place::length(p) + kShiftTile * (p.sectors | 1)) * sizeof(float);  // <= 64 KB (the static_assert above)
+  const int blocks = std::min(count, ctx->place_max_blocks > 0 ? ctx->place_max_blocks : kSearchBlocks);
+  SearchArgs a;
+  a.slots = slots;
+  a.out = out_dev;
+  a.cap = cap;
+  a.head = head;
+  a.stride = stride;
+  a.query = query;
+  a.first = first;
+  a.count = count;
+  hipLaunchKernelGGL(k_place_search, dim3((unsigned)blocks), dim3(kSearchThreads), lds, stream, a, p);
+}
+}  // namespace lsa
+
+namespace
+{
 int check(lsa_ctx* ctx, const char* who, const lsa_place_params_t* params, int first, int last)
 {
   if (!ctx) return LSA_E_ARG;
@@ -307,8 +324,7 @@ int describe_missing(lsa_ctx* ctx, PlaceStore* st, int first, int last, int also
   LSA_HIP(ctx, hipMemcpyAsync(st->table, frames.data(), bytes, hipMemcpyHostToDevice, ctx->stream));
   {
     ProfScope ps(ctx, "log_describe", (double)points * 32 + (double)frames.size() * ((double)st->stride * 4 + sizeof(DescribeFrame)));
-    hipLaunchKernelGGL(k_log_describe, dim3((unsigned)frames.size()), dim3(kDescribeThreads), 0, ctx->stream, reinterpret_cast<const DescribeFrame*>(st->table), st->slots,
-                       st->stride, p);
+    place_describe_launch(reinterpret_cast<const DescribeFrame*>(st->table), (int)frames.size(), st->slots, st->stride, p, ctx->stream);
   }
   LSA_HIP(ctx, hipGetLastError());
   LSA_HIP(ctx, hipStreamSynchronize(ctx->stream));  // `frames` goes away
@@ -383,20 +399,9 @@ int lsa_kplog_place_search(lsa_ctx* ctx, const lsa_place_params_t* params, int q
   }
   const lsa_place_params_t& p = st->params;
   const int length = place::length(p);
-  const size_t lds = (size_t)(2 * length + kShiftTile * (p.sectors | 1)) * sizeof(float);  // <= 64 KB (the static_assert above)
-  const int blocks = (int)std::min<long long>(count, ctx->place_max_blocks > 0 ? ctx->place_max_blocks : kSearchBlocks);
-  SearchArgs a;
-  a.slots = st->slots;
-  a.out = st->result_dev;
-  a.cap = st->cap;
-  a.head = st->head;
-  a.stride = st->stride;
-  a.query = query;
-  a.first = first;
-  a.count = (int)count;
   {
     ProfScope ps(ctx, "place_search", (double)(count + 1) * length * 4 + (double)count * sizeof(PlaceResult));
-    hipLaunchKernelGGL(k_place_search, dim3((unsigned)blocks), dim3(kSearchThreads), lds, ctx->stream, a, p);
+    place_search_launch(ctx, st->slots, st->cap, st->head, st->stride, query, first, (int)count, st->result_dev, p, ctx->stream);
   }
   LSA_HIP(ctx, hipGetLastError());
   LSA_HIP(ctx, hipMemcpyAsync(st->result_host, st->result_dev, (size_t)count * sizeof(PlaceResult), hipMemcpyDeviceToHost, ctx->stream));

@@ -87,5 +87,27 @@ LSA_HDP double yaw_of(int shift, int sectors)
   const double yaw = shift * TWO_PI / sectors;
   return yaw > PI ? yaw - TWO_PI : yaw;
 }
+
+// ---- the map as seen from a viewpoint -------------------------------------------------------------------------
+// A viewpoint is a position v in the maps' frame, its axes the maps' axes: the base is assumed LEVEL there (roll and pitch
+// are ignored -- a limit of the definition).  A map point p takes part as the frame point (map_coord(p.x, v.x), map_coord(p.y,
+// v.y), map_coord(p.z, v.z)); cell_of, offer, cell_value and column_norm then apply verbatim, so the descriptor of the map at
+// v is the frame descriptor of the translated points.
+LSA_HDP float map_coord(float p, double v) { return (float)((double)p - v); }
+// What a slice of map points whose xy box is [lo, hi] can be passed over by, and a point be dropped by before the square
+// root: the planar distance the text above can still accept, with a margin.  The translation rounds to float, |x - x_true|
+// <= 2^-24 |x_true|, so cell_of's r is at least d_true (1 - 2^-23) for a point at the true planar distance d_true; a point
+// (or a box) farther than max_range (1 + 2^-20) therefore has r > max_range and takes no part -- sixteen times the rounding,
+// which also covers the double arithmetic of the comparison itself.  max_range <= 0 accepts nothing: reach 0.
+LSA_HDP double map_reach(const lsa_place_params_t& p) { return p.max_range > 0. ? p.max_range * (1. + 9.5367431640625e-07) : 0.; }
+// the squared planar distance from v to the box (0 inside); an empty box (lo > hi) is infinitely far
+LSA_HDP double map_box_distance2(float lox, float loy, float hix, float hiy, double vx, double vy)
+{
+  double dx = (double)lox - vx > vx - (double)hix ? (double)lox - vx : vx - (double)hix;
+  double dy = (double)loy - vy > vy - (double)hiy ? (double)loy - vy : vy - (double)hiy;
+  if (!(dx > 0.)) dx = 0.;
+  if (!(dy > 0.)) dy = 0.;
+  return dx * dx + dy * dy;
+}
 }  // namespace place
 }  // namespace lsa

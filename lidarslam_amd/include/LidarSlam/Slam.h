@@ -434,6 +434,45 @@ public:
     found.resize(static_cast<std::size_t>(rc > 0 ? rc : 0));
     return found;
   }
+  // ---- place recognition against the MAPS: where in the maps (LoadMapsFromPCD, or the maps this object built) does the
+  // last frame belong, when nobody can say -- a robot switched on somewhere inside its map, a localization that lost its
+  // matches.  The maps are described as seen from each of `viewpoints` (positions in the maps' frame; the BASE is assumed
+  // level there) and the last frame's descriptor is searched among them, on the device (lsa_slam_recognize_place_in_maps).
+  // Best first; candidate.guess = Translation(viewpoint) * Rz(yaw) is what SetWorldTransformFromGuess takes -- the call
+  // itself does not move the pose.  Needs one AddFrame since construction, Reset or SetWorldTransformFromGuess.  Empty when
+  // there is none or when it cannot (GetLastError() says why).  Without viewpoints: the positions of GetTrajectory().
+  using MapPlaceSearchParameters = lsa_map_place_search_t;
+  using MapPlaceCandidate = lsa_map_place_candidate_t;
+  using MapPlaceSummary = lsa_map_place_summary_t;
+  static MapPlaceSearchParameters DefaultMapPlaceSearchParameters()
+  {
+    MapPlaceSearchParameters p;
+    lsa_map_place_search_init(&p);
+    return p;
+  }
+  std::vector<MapPlaceCandidate> RecognizePlaceInMaps(const std::vector<std::array<double, 3>>& viewpoints,
+                                                      const MapPlaceSearchParameters& params = DefaultMapPlaceSearchParameters(), std::size_t maxCandidates = 5,
+                                                      MapPlaceSummary* summary = nullptr)
+  {
+    std::vector<MapPlaceCandidate> found(maxCandidates);
+    const int rc = lsa_slam_recognize_place_in_maps(this->Handle, viewpoints.empty() ? nullptr : viewpoints.front().data(), static_cast<int>(viewpoints.size()), &params,
+                                                    found.data(), static_cast<int>(maxCandidates), summary);
+    this->LastError = rc < 0 ? std::string("RecognizePlaceInMaps: ") + lsa_slam_last_error(this->Handle) : std::string();
+    found.resize(static_cast<std::size_t>(rc > 0 ? rc : 0));
+    return found;
+  }
+  std::vector<MapPlaceCandidate> RecognizePlaceInMaps(const MapPlaceSearchParameters& params = DefaultMapPlaceSearchParameters(), std::size_t maxCandidates = 5,
+                                                      MapPlaceSummary* summary = nullptr)
+  {
+    std::vector<std::array<double, 3>> viewpoints;
+    for (const Transform& t : this->GetTrajectory()) viewpoints.push_back({t.matrix[3], t.matrix[7], t.matrix[11]});
+    if (viewpoints.empty())
+    {
+      this->LastError = "RecognizePlaceInMaps: the trajectory is empty and no viewpoints were given";
+      return {};
+    }
+    return this->RecognizePlaceInMaps(viewpoints, params, maxCandidates, summary);
+  }
   // ---- pose-graph optimization of the logged trajectory on the device (lsa_slam_optimize_logged_trajectory): the odometry
   // chain of the log, pose 0 fixed, plus the loop edges given -- LoopClosureEdge(revisited, query, registration) makes one from
   // what RegisterLoggedFrames returned.  Returns the optimized poses with their logged times (empty when it cannot:

@@ -973,6 +973,44 @@ int lsa_place_select_host(const float* distance, const int32_t* shift, const dou
                           double max_distance, double max_descriptor_distance, int exclusion_half_window, lsa_place_candidate_t* out, int capacity);
 int lsa_slam_recognize_place(lsa_slam* s, int query, const lsa_place_search_t* search, lsa_place_candidate_t* out, int capacity);
 
+/* Loop detection over the whole log: every place this drive revisited, in one call.
+ * - A query set is first_query, first_query + query_stride, ... <= last_query (last_query < 0: the last logged frame;
+ *   query_stride >= 1).  The result for query q is BY DEFINITION what lsa_place_select_host returns for q, with capacity
+ *   per_query (1..16), from the table lsa_place_distance_host(D[q], D[i]), i = 0..q-1, under the same lsa_place_search_t.  The
+ *   result of the call is the concatenation over the queries, ascending: records {query, frame, shift, distance, yaw}.  A
+ *   query without an admissible frame contributes nothing; no candidate at all is an answer (0), not an error.
+ * - lsa_loop_detect_init: lsa_place_search_init, first_query 0, last_query -1, query_stride 1, per_query 1.
+ * - lsa_place_detect_host(detect, descriptors, poses17, n, out, capacity): the host statement, no device -- n descriptors of
+ *   rings * sectors + sectors floats and n rows of 17 doubles; literally the loop over lsa_place_distance_host and
+ *   lsa_place_select_host.  The gates and the ranking are lidarslam_amd/csrc/lsa_place_select.h, compiled for the device too.
+ * - lsa_slam_detect_loop_closures(detect, out, capacity): the same for the keypoint log, on the device: the frames without a
+ *   descriptor are described, many queries are compared in one pass over the descriptor store (k_place_search_rows), the
+ *   selection runs on the device too (k_place_select_rows), and only the candidates come back -- one copy, one wait.  Equal
+ *   to lsa_slam_recognize_place called for every query of the set, byte for byte.  Runs on the log's context after the map
+ *   workers; changes nothing the frame path reads.  detect NULL = defaults.
+ * All three return the number of candidates written.  LSA_E_ARG, with nothing written: a query set that is not one of this
+ * log, per_query outside 1..16, capacity below queries * per_query, parameters out of limits.  LSA_E_STATE as
+ * lsa_slam_recognize_place. */
+typedef struct lsa_loop_detect_t
+{
+  lsa_place_search_t search;
+  int32_t first_query;            /* (default 0) */
+  int32_t last_query;             /* < 0: the last logged frame (default -1) */
+  int32_t query_stride;           /* >= 1 (default 1) */
+  int32_t per_query;              /* candidates a query, 1..16 (default 1) */
+} lsa_loop_detect_t;
+typedef struct lsa_loop_candidate_t
+{
+  int32_t query;
+  int32_t frame;
+  int32_t shift;
+  float distance;
+  double yaw;                     /* [rad] */
+} lsa_loop_candidate_t;
+void lsa_loop_detect_init(lsa_loop_detect_t* detect);
+int lsa_place_detect_host(const lsa_loop_detect_t* detect, const float* descriptors, const double* poses17, int n, lsa_loop_candidate_t* out, int capacity);
+int lsa_slam_detect_loop_closures(lsa_slam* s, const lsa_loop_detect_t* detect, lsa_loop_candidate_t* out, int capacity);
+
 /* Place recognition against the MAPS: where in a loaded map is the vehicle, when nobody can say.  A saved
  * map has no logged frames to compare with, only points; what is compared with the last frame's descriptor is the descriptor
  * of the map AS SEEN FROM A VIEWPOINT, made for many viewpoints at once.
@@ -1189,6 +1227,21 @@ int lsa_kplog_descriptors(lsa_ctx* ctx, int first, int last, float* out);
 int lsa_kplog_place_search(lsa_ctx* ctx, const lsa_place_params_t* params, int query, int first, int last, float* distance_out, int32_t* shift_out);
 int lsa_kplog_described(const lsa_ctx* ctx);
 int lsa_kplog_descriptor_length(const lsa_ctx* ctx);
+/* Loop detection over the log (lsa_place_detect.hip; the definition: "Loop detection over the whole log" above).
+ * - lsa_kplog_place_search_rows(params, first_query, last_query, query_stride, distance_out, shift_out): k_place_search_rows
+ *   alone, no gates: the ragged table of the query set, row of query q = (distance, shift) of q against the frames 0..q-1,
+ *   rows concatenated in the queries' order (a query 0 has an empty row).  Each entry equals lsa_place_distance_host.
+ * - lsa_kplog_detect_loops(detect, poses17, n, out, capacity): n = lsa_kplog_size rows of 17 doubles; describes what is
+ *   missing, then per run of consecutive queries whose tables fit the table's byte budget ONE launch of k_place_search_rows
+ *   (the pairs behind the min_travelled and max_distance gates are not computed) and ONE of k_place_select_rows; the
+ *   candidates accumulate on the device; ONE copy to pinned memory and ONE wait for the call.  Returns their number.
+ * The table is scratch space of the context, 8 bytes a pair, at most 256 MiB (or one row, if that is larger); lsa_debug_set
+ * "place_table_bytes" n lowers the budget to n bytes (<= 0: the default); "place_max_blocks" holds for both launches;
+ * "place_untiled" 1 makes the search walk its columns one at a time instead of four (the same table; kept to measure against).
+ * Refusals as above, with nothing written. */
+int lsa_kplog_place_search_rows(lsa_ctx* ctx, const lsa_place_params_t* params, int first_query, int last_query, int query_stride, float* distance_out,
+                                int32_t* shift_out);
+int lsa_kplog_detect_loops(lsa_ctx* ctx, const lsa_loop_detect_t* detect, const double* poses17, int n, lsa_loop_candidate_t* out, int capacity);
 int lsa_kplog_append(lsa_ctx* ctx);
 int lsa_kplog_append_points(lsa_ctx* ctx, const lsa_point_t* const pts[3], const int n[3]);
 int lsa_kplog_pop_front(lsa_ctx* ctx);
@@ -1456,6 +1509,38 @@ int lsa_slam_optimize_logged_trajectory_robust(lsa_slam* s, const lsa_pgo_edge_t
 int lsa_slam_run_pose_graph_optimization_robust(lsa_slam* s, const double* gps_times, const double* gps_xyz, const double* gps_cov9, int G, double* gps_to_sensor16,
                                                 double time_offset, const lsa_pgo_params_t* params, const lsa_pgo_robust_t* robust, double* poses17_out, int capacity,
                                                 lsa_pgo_result_t* result, double* fix_verdict_out);
+
+/* Close every loop of the log: detect, register, solve, apply -- exactly the composition of the calls above.
+ *  1. lsa_slam_detect_loop_closures(detect).
+ *  2. Every candidate in order: lsa_slam_register_logged_frames(query, frame, loop_params, P[frame] * Rz(yaw)), all under the
+ *     logged poses as they stand.
+ *  3. An edge {from = frame, to = query, relative = the registration's} with lsa_pgo_information_from_covariance where the
+ *     registration's status is 0 and its covariance is positive definite.
+ *  4. One lsa_slam_optimize_logged_trajectory_robust over these edges; pgo_params->apply decides whether its poses go through
+ *     lsa_slam_set_trajectory_and_rebuild_maps.
+ * Returns the number of reports (= candidates) written; poses17_out gets the n = lsa_slam_logged_frames optimized poses
+ * (capacity >= n rows), *result the solver's summary, reports_out one lsa_loop_report_t per candidate: status = the
+ * registration's (0 registered, 1 too few matches, < 0 the LSA_E_* code of a refused registration), edge = its index among
+ * the loop edges or -1, {chi2, weight} its verdict at the returned poses ({0, -1} without an edge).  Without a candidate, or
+ * without an edge, nothing is solved and nothing changes: the poses are the logged ones, result->iterations is 0 and
+ * result->message says so.  NULL detect / loop_params / pgo_params / robust = their defaults.  Refusals as the calls it is
+ * made of; report_capacity below queries * per_query is LSA_E_ARG. */
+typedef struct lsa_loop_report_t
+{
+  int32_t query;
+  int32_t frame;
+  float distance;                 /* of the descriptors */
+  int32_t status;
+  double yaw;                     /* [rad] the start guess's turn */
+  int32_t iterations;             /* of the registration's ICP loop */
+  int32_t edge;
+  double position_error;          /* [m] of the registration */
+  double chi2;
+  double weight;
+} lsa_loop_report_t;
+int lsa_slam_close_loops(lsa_slam* s, const lsa_loop_detect_t* detect, const lsa_loop_closure_params_t* loop_params, const lsa_pgo_params_t* pgo_params,
+                         const lsa_pgo_robust_t* robust, double* poses17_out, int capacity, lsa_pgo_result_t* result, lsa_loop_report_t* reports_out,
+                         int report_capacity);
 
 /* ---- the rolling voxel map (host) ---------------------------
  * LidarSlam::RollingGrid -- slam_lib/include/LidarSlam/RollingGrid.h:63-212,

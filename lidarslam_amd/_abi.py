@@ -234,6 +234,9 @@ SIGNATURES = {
     "lsa_place_distance_host": (i32, [vp, vp, vp, vp, vp]),
     "lsa_place_select_host": (i32, [vp, vp, vp, i32, i32, i32, f64, f64, f64, i32, vp, i32]),
     "lsa_slam_recognize_place": (i32, [vp, i32, vp, vp, i32]),
+    "lsa_loop_detect_init": (None, [vp]),
+    "lsa_place_detect_host": (i32, [vp, vp, vp, i32, vp, i32]),
+    "lsa_slam_detect_loop_closures": (i32, [vp, vp, vp, i32]),
     "lsa_map_place_search_init": (None, [vp]),
     "lsa_map_descriptor_host": (i32, [vp, vp, i32, vp, vp]),
     "lsa_map_place_select_host": (i32, [vp, vp, vp, i32, i32, vp, vp, i32]),
@@ -276,6 +279,8 @@ SIGNATURES = {
     "lsa_kplog_place_search": (i32, [vp, vp, i32, i32, i32, vp, vp]),
     "lsa_kplog_described": (i32, [vp]),
     "lsa_kplog_descriptor_length": (i32, [vp]),
+    "lsa_kplog_place_search_rows": (i32, [vp, vp, i32, i32, i32, vp, vp]),
+    "lsa_kplog_detect_loops": (i32, [vp, vp, vp, i32, vp, i32]),
     "lsa_kplog_append": (i32, [vp]),
     "lsa_kplog_append_points": (i32, [vp, vp, vp]),
     "lsa_kplog_pop_front": (i32, [vp]),
@@ -340,6 +345,7 @@ SIGNATURES = {
     "lsa_pgo_solve_robust": (i32, [vp, vp, i32, vp, vp, i32, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp]),
     "lsa_slam_optimize_logged_trajectory_robust": (i32, [vp, vp, i32, vp, vp, vp, i32, vp, vp]),
     "lsa_slam_run_pose_graph_optimization_robust": (i32, [vp, vp, vp, vp, i32, vp, f64, vp, vp, vp, i32, vp, vp]),
+    "lsa_slam_close_loops": (i32, [vp, vp, vp, vp, vp, vp, i32, vp, vp, i32]),
     # ---- host maps
     "lsa_rolling_grid_create": (vp, []),
     "lsa_rolling_grid_destroy": (None, [vp]),

@@ -152,6 +152,111 @@ def place_select(distance, shift, poses, times, query, sectors=60, min_travelled
     return _candidates(out, rc)
 
 
+# ---- loop detection over the whole log (include/lidarslam_amd.h) ------------------------------------------------
+MAX_PER_QUERY = 16  # candidates a query
+
+
+class LoopDetect(C.Structure):
+    """lsa_loop_detect_t: a PlaceSearch, the query set first_query, first_query + query_stride, ... <= last_query
+    (last_query < 0: the last logged frame) and per_query (1..16) candidates a query."""
+
+    _fields_ = [("search", PlaceSearch), ("first_query", C.c_int32), ("last_query", C.c_int32), ("query_stride", C.c_int32), ("per_query", C.c_int32)]
+
+    def __init__(self, first_query=0, last_query=-1, query_stride=1, per_query=1, **search):
+        super().__init__(PlaceSearch(**search), first_query, last_query, query_stride, per_query)
+
+    @property
+    def queries(self):
+        return range(self.first_query, self.last_query + 1, self.query_stride)
+
+
+class LoopCandidateStruct(C.Structure):
+    """lsa_loop_candidate_t."""
+
+    _fields_ = [("query", C.c_int32), ("frame", C.c_int32), ("shift", C.c_int32), ("distance", C.c_float), ("yaw", C.c_double)]
+
+
+def _loop_candidates(out, n):
+    """[(query, frame, distance, shift, yaw)]: distance a numpy float32, yaw a float [rad]"""
+    return [(int(c.query), int(c.frame), np.float32(c.distance), int(c.shift), float(c.yaw)) for c in out[:n]]
+
+
+def _loop_detect(what, n, first_query, last_query, query_stride, per_query, search):
+    """-> (LoopDetect with last_query resolved on a log of n frames, room for its candidates); refuses what has no size"""
+    d = LoopDetect(int(first_query), int(last_query), int(query_stride), int(per_query), **search)
+    if d.last_query < 0:
+        d.last_query = n - 1
+    if not (n >= 1 and d.query_stride >= 1 and 0 <= d.first_query <= d.last_query < n and 1 <= d.per_query <= MAX_PER_QUERY):
+        raise _error(what, E_ARG, "a query set outside the log, or per_query outside 1..16")
+    return d, (LoopCandidateStruct * (len(d.queries) * d.per_query))()
+
+
+def _rows17(poses, times):
+    P = np.asarray(poses, np.float64).reshape(-1, 16)
+    return np.ascontiguousarray(np.concatenate([P, np.asarray(times, np.float64).reshape(-1, 1)], axis=1))
+
+
+def place_detect_host(descriptors, poses, times, first_query=0, last_query=-1, query_stride=1, per_query=1, **search):
+    """The host statement of loop detection over a log (lsa_place_detect_host): descriptors (n, length) float32, poses
+    (n, 4, 4) and times (n,) -> [(query, frame, distance, shift, yaw)], the queries ascending, each query's candidates best
+    first: by definition place_select on the table of place_distance for every query of the set.  search: PlaceSearch's
+    fields and PlaceParams'."""
+    what = "lsa_place_detect_host"
+    rows = _rows17(poses, times)
+    n = rows.shape[0]
+    d, out = _loop_detect(what, n, first_query, last_query, query_stride, per_query, search)
+    D = np.ascontiguousarray(np.asarray(descriptors, np.float32).reshape(n, -1))
+    if D.shape[1] != d.search.descriptor.length:
+        raise _error(what, E_ARG, "descriptors of another shape than the parameters'")
+    rc = lib().lsa_place_detect_host(C.byref(d), ptr(D), ptr(rows), n, out, len(out))
+    if rc < 0:
+        raise _error(what, rc, "parameters out of limits")
+    return _loop_candidates(out, rc)
+
+
+def place_search_rows(ctx, first_query=0, last_query=-1, query_stride=1, **params):
+    """k_place_search_rows alone on the context's keypoint log (lsa_kplog_place_search_rows), no gates: per query of the set
+    the (distance float32 (q,), shift int32 (q,)) of query q against the frames 0..q-1 -> [(query, distance, shift)]."""
+    what = "lsa_kplog_place_search_rows"
+    p = PlaceParams(**params)
+    n = ctx.L.lsa_kplog_size(ctx.h)
+    last = n - 1 if int(last_query) < 0 else int(last_query)
+    if not (int(query_stride) >= 1 and 0 <= int(first_query) <= last < n):
+        raise _error(what, E_ARG, "a query set outside the log")
+    queries = list(range(int(first_query), last + 1, int(query_stride)))
+    total = sum(queries)
+    d, s = np.zeros(max(total, 1), np.float32), np.zeros(max(total, 1), np.int32)
+    ctx._check(ctx.L.lsa_kplog_place_search_rows(ctx.h, C.byref(p), int(first_query), last, int(query_stride), ptr(d), ptr(s)), what)
+    out, at = [], 0
+    for q in queries:
+        out.append((q, d[at:at + q], s[at:at + q]))
+        at += q
+    return out
+
+
+def kplog_detect_loops(ctx, poses, times, first_query=0, last_query=-1, query_stride=1, per_query=1, **search):
+    """Loop detection over the context's keypoint log (lsa_kplog_detect_loops: k_place_search_rows and k_place_select_rows per
+    run of queries) under poses (n, 4, 4) dated times (n,) -> [(query, frame, distance, shift, yaw)] as place_detect_host."""
+    what = "lsa_kplog_detect_loops"
+    rows = _rows17(poses, times)
+    d, out = _loop_detect(what, rows.shape[0], first_query, last_query, query_stride, per_query, search)
+    return _loop_candidates(out, ctx._check(ctx.L.lsa_kplog_detect_loops(ctx.h, C.byref(d), ptr(rows), rows.shape[0], out, len(out)), what))
+
+
+def detect_loop_closures(slam, first_query=0, last_query=-1, query_stride=1, per_query=1, **search):
+    """Every place the logged drive revisited (lsa_slam_detect_loop_closures): slam.recognize_place(q, capacity=per_query)
+    for every query of the set in one pass on the device -> [(query, frame, distance, shift, yaw)], the queries ascending,
+    each query's candidates best first.  search: PlaceSearch's fields and PlaceParams'.  Raises LsaError (.code E_STATE or
+    E_ARG) when it cannot."""
+    what = "lsa_slam_detect_loop_closures"
+    n = slam._check(slam.L.lsa_slam_logged_frames(slam.h), "lsa_slam_logged_frames")
+    if n < 1:
+        d, out = LoopDetect(int(first_query), int(last_query), int(query_stride), int(per_query), **search), (LoopCandidateStruct * 1)()
+        return _loop_candidates(out, slam._check(slam.L.lsa_slam_detect_loop_closures(slam.h, C.byref(d), out, 0), what))  # (the library says why not)
+    d, out = _loop_detect(what, n, first_query, last_query, query_stride, per_query, search)
+    return _loop_candidates(out, slam._check(slam.L.lsa_slam_detect_loop_closures(slam.h, C.byref(d), out, len(out)), what))
+
+
 # ---- place recognition against the maps: the map as seen from a viewpoint (include/lidarslam_amd.h, DESIGN.md 3.12) ----------
 class MapPlaceSearch(C.Structure):
     """lsa_map_place_search_t: the descriptor's parameters and the selection's.  near_xyz is read only when max_distance > 0."""

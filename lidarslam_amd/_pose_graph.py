@@ -270,6 +270,53 @@ def optimize_trajectory_robust(slam, loop_edges, robust, apply=False, params=Non
     return rows[:got, :16].reshape(-1, 4, 4).copy(), rows[:got, 16].copy(), PoseGraphResult(r), verdict
 
 
+class LoopReportStruct(C.Structure):
+    """lsa_loop_report_t."""
+
+    _fields_ = [
+        ("query", C.c_int32), ("frame", C.c_int32), ("distance", C.c_float), ("status", C.c_int32), ("yaw", C.c_double), ("iterations", C.c_int32),
+        ("edge", C.c_int32), ("position_error", C.c_double), ("chi2", C.c_double), ("weight", C.c_double),
+    ]
+
+
+class LoopReport:
+    """What close_loops says of one candidate: query, frame, distance (float32, of the descriptors), yaw [rad], status (the
+    registration's: 0 registered, 1 too few matches, < 0 an E_* code), iterations, position_error [m], edge (its index among
+    the loop edges, -1: none came of it), chi2 and weight (its verdict at the returned poses; 0 and -1 without an edge)."""
+
+    def __init__(self, r):
+        for name, _ in LoopReportStruct._fields_:
+            setattr(self, name, getattr(r, name))
+        self.distance = np.float32(r.distance)
+
+    def __repr__(self):
+        return f"LoopReport({self.__dict__})"
+
+
+def close_loops(slam, robust=None, loop_params=None, apply=False, params=None, first_query=0, last_query=-1, query_stride=1, per_query=1, **search):
+    """Finds every loop closure of the logged drive and closes them (lsa_slam_close_loops): detect_loop_closures, then
+    register_logged_frames(query, frame, loop_params, P[frame] @ Rz(yaw)) for every candidate under the logged poses, an edge
+    (frame, query, relative, information_from_covariance(covariance)) for every registration with status 0 and a positive
+    definite covariance, and one optimize_trajectory_robust over them; apply=True puts the result back and rebuilds the maps.
+    robust: a PoseGraphRobust (None: no loss); loop_params: a LoopClosureParams; params: a PoseGraphParams; search:
+    PlaceSearch's fields and PlaceParams'.  -> (poses (n, 4, 4), times (n,), PoseGraphResult, [LoopReport]).  Without a
+    candidate or an edge nothing is solved or changed, and the result's message says so."""
+    from ._place import LoopClosureParams, _loop_detect
+
+    name = "lsa_slam_close_loops"
+    rb = PoseGraphRobust() if robust is None else _pgo_robust(robust, name)
+    p = params if params is not None else PoseGraphParams()
+    p.apply = int(bool(apply))
+    lp = loop_params if loop_params is not None else LoopClosureParams()
+    n = slam._check(slam.L.lsa_slam_logged_frames(slam.h), "lsa_slam_logged_frames")
+    d, _ = _loop_detect(name, max(n, 1), first_query, last_query, query_stride, per_query, search)
+    reports = (LoopReportStruct * (len(d.queries) * d.per_query))()
+    rows = np.zeros((max(n, 1), 17))
+    r = PoseGraphResultStruct()
+    got = slam._check(slam.L.lsa_slam_close_loops(slam.h, C.byref(d), C.byref(lp), C.byref(p), C.byref(rb), ptr(rows), rows.shape[0], C.byref(r), reports, len(reports)), name)
+    return rows[:n, :16].reshape(-1, 4, 4).copy(), rows[:n, 16].copy(), PoseGraphResult(r), [LoopReport(x) for x in reports[:got]]
+
+
 def run_pose_graph_optimization_robust(slam, gps_times, gps_xyz, gps_cov, robust, gps_to_sensor=None, apply=True, time_offset=0.0, params=None, **kw):
     """Slam.run_pose_graph_optimization under robust.prior_loss on the GPS priors (lsa_slam_run_pose_graph_optimization_robust).
     -> (poses (n, 4, 4), times (n,), gps_to_sensor (4, 4), PoseGraphResult, matches (G,), fix_verdict (G, 2) = {chi2, weight}

@@ -101,6 +101,65 @@ int PlaceSelect(const float* distance, const int32_t* shift, const double* poses
   return found;
 }
 
+int DetectQueries(const lsa_loop_detect_t& detect, int n, int capacity, int* last)
+{
+  if (!place::search_ok(detect.search) || detect.per_query < 1 || detect.per_query > place::kMaxPerQuery || capacity < 0) return LSA_E_ARG;
+  if (!place::query_set_ok(n, detect.first_query, detect.last_query, detect.query_stride, last)) return LSA_E_ARG;
+  const int queries = place::query_count(detect.first_query, *last, detect.query_stride);
+  if (static_cast<long long>(capacity) < static_cast<long long>(queries) * detect.per_query) return LSA_E_ARG;
+  return queries;
+}
+
+void FramePositions(const double* poses17, int n, place::FramePosition* out)
+{
+  for (int i = 0; i < n; ++i)
+  {
+    const double* m = poses17 + 17 * static_cast<size_t>(i);
+    out[i] = place::FramePosition{m[3], m[7], m[11], 0.};
+    if (i > 0) out[i].travelled = out[i - 1].travelled + place::metres(out[i], out[i - 1]);
+  }
+}
+
+int PlaceDetect(const lsa_loop_detect_t& detect, const float* descriptors, const double* poses17, int n, lsa_loop_candidate_t* out, int capacity)
+{
+  int last = 0;
+  const int queries = DetectQueries(detect, n, capacity, &last);
+  if (queries < 0 || !descriptors || !poses17 || !out) return LSA_E_ARG;
+  const lsa_place_search_t& s = detect.search;
+  const size_t length = static_cast<size_t>(place::length(s.descriptor));
+  std::vector<float> distance;
+  std::vector<int32_t> shift;
+  lsa_place_candidate_t picked[place::kMaxPerQuery];
+  int found = 0;
+  for (int q = detect.first_query; q <= last; q += detect.query_stride)
+  {
+    distance.resize(static_cast<size_t>(q));
+    shift.resize(static_cast<size_t>(q));
+    for (int i = 0; i < q; ++i)
+    {
+      int sh = 0;
+      if (PlaceDistance(s.descriptor, descriptors + length * q, descriptors + length * i, &distance[i], &sh) != LSA_OK) return LSA_E_ARG;
+      shift[i] = sh;
+    }
+    const int got = PlaceSelect(distance.data(), shift.data(), poses17, n, q, s.descriptor.sectors, s.min_travelled, s.max_distance, s.max_descriptor_distance,
+                                s.exclusion_half_window, picked, detect.per_query);
+    if (got < 0) return got;
+    for (int k = 0; k < got; ++k)
+    {
+      lsa_loop_candidate_t c;
+      std::memset(&c, 0, sizeof(c));
+      c.query = q;
+      c.frame = picked[k].frame;
+      c.shift = picked[k].shift;
+      c.distance = picked[k].distance;
+      c.yaw = picked[k].yaw;
+      out[found++] = c;
+    }
+    if (q > last - detect.query_stride) break;  // (q + stride may not be an int)
+  }
+  return found;
+}
+
 int MapDescriptor(const lsa_place_params_t& p, const lsa_point_t* pts, int n, const double viewpoint[3], float* out)
 {
   if (!place::params_ok(p) || !out || n < 0 || (n > 0 && !pts) || !viewpoint) return LSA_E_ARG;
@@ -214,6 +273,24 @@ int lsa_place_select_host(const float* distance, const int32_t* shift, const dou
 {
   return lsa::host::PlaceSelect(distance, shift, poses17, n, query, sectors, min_travelled, max_distance, max_descriptor_distance, exclusion_half_window, out,
                                 capacity);
+}
+
+void lsa_loop_detect_init(lsa_loop_detect_t* detect)
+{
+  if (!detect) return;
+  std::memset(detect, 0, sizeof(*detect));
+  lsa_place_search_init(&detect->search);
+  detect->last_query = -1;
+  detect->query_stride = 1;
+  detect->per_query = 1;
+}
+
+int lsa_place_detect_host(const lsa_loop_detect_t* detect, const float* descriptors, const double* poses17, int n, lsa_loop_candidate_t* out, int capacity)
+{
+  lsa_loop_detect_t d;
+  lsa_loop_detect_init(&d);
+  if (detect) d = *detect;
+  return lsa::host::PlaceDetect(d, descriptors, poses17, n, out, capacity);
 }
 
 void lsa_map_place_search_init(lsa_map_place_search_t* search)

@@ -343,6 +343,20 @@ int lsa_slam_recognize_place(lsa_slam* s, int query, const lsa_place_search_t* s
   return s->core.RecognizePlace(query, search, out, capacity);
 }
 
+int lsa_slam_detect_loop_closures(lsa_slam* s, const lsa_loop_detect_t* detect, lsa_loop_candidate_t* out, int capacity)
+{
+  if (!s) return LSA_E_ARG;
+  return s->core.DetectLoopClosures(detect, out, capacity);
+}
+
+int lsa_slam_close_loops(lsa_slam* s, const lsa_loop_detect_t* detect, const lsa_loop_closure_params_t* loop_params, const lsa_pgo_params_t* pgo_params,
+                         const lsa_pgo_robust_t* robust, double* poses17_out, int capacity, lsa_pgo_result_t* result, lsa_loop_report_t* reports_out,
+                         int report_capacity)
+{
+  if (!s) return LSA_E_ARG;
+  return s->core.CloseLoops(detect, loop_params, pgo_params, robust, poses17_out, capacity, result, reports_out, report_capacity);
+}
+
 int lsa_slam_recognize_place_in_maps(lsa_slam* s, const double* viewpoints, int V, const lsa_map_place_search_t* search, lsa_map_place_candidate_t* out, int capacity,
                                      lsa_map_place_summary_t* summary)
 {

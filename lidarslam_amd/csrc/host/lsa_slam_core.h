@@ -102,6 +102,13 @@ public:
   // (lsa_slam_recognize_place in lidarslam_amd.h).  Runs on the log's context after the map workers; reads the log, writes
   // the log's descriptor store and nothing else.  Returns the number of candidates written.
   int RecognizePlace(int query, const lsa_place_search_t* search, lsa_place_candidate_t* out, int capacity);
+  // Loop detection over the whole log: RecognizePlace for every query of a set in one pass on the device
+  // (lsa_slam_detect_loop_closures in lidarslam_amd.h).  Refuses, waits and runs as RecognizePlace does.
+  int DetectLoopClosures(const lsa_loop_detect_t* detect, lsa_loop_candidate_t* out, int capacity);
+  // Detect, register every candidate, solve under the robust loss, apply where asked: the composition of DetectLoopClosures,
+  // RegisterLoggedFrames and OptimizeLoggedTrajectory (lsa_slam_close_loops in lidarslam_amd.h).  Returns the number of reports.
+  int CloseLoops(const lsa_loop_detect_t* detect, const lsa_loop_closure_params_t* loopParams, const lsa_pgo_params_t* pgoParams, const lsa_pgo_robust_t* robust,
+                 double* poses17, int capacity, lsa_pgo_result_t* result, lsa_loop_report_t* reports, int reportCapacity);
   // Place recognition against the maps: the viewpoints from which the maps look like the last frame (lsa_slam_recognize_place_in_maps
   // in lidarslam_amd.h).  Runs after the map workers; reads the maps and the raw keypoints, writes the context's table of map
   // descriptors and nothing else; the pose is the caller's to set (SetWorldTransformFromGuess(candidate.guess)).  A refusal

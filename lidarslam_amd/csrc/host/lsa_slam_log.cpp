@@ -2,6 +2,7 @@
 // rebuilt, place recognition, the two pose-graph optimizations, the registration of two logged frames.
 #include "lsa_slam_icp_loop.h"
 #include <algorithm>
+#include <cmath>
 #include <cstring>
 #include "../lsa_device_grid_io.h"
 #include "../lsa_kplog_io.h"
@@ -181,6 +182,114 @@ int SlamCore::RecognizePlace(int query, const lsa_place_search_t* search, lsa_pl
                                 p.exclusion_half_window, out, capacity);
   if (found < 0) LastError = who + "bad argument";
   return found;
+}
+
+// ---- loop detection over the whole log: RecognizePlace for a set of queries in one pass (lsa_place_detect.hip) --------------
+int SlamCore::DetectLoopClosures(const lsa_loop_detect_t* detect, lsa_loop_candidate_t* out, int capacity)
+{
+  if (!Ctx) return LSA_E_NO_DEVICE;
+  const std::string who = "DetectLoopClosures: ";
+  if (capacity < 0 || (capacity > 0 && !out)) { LastError = who + "no place for the candidates"; return LSA_E_ARG; }
+  const int n = LogReady(who, "there are no logged keypoints to describe");
+  if (n < 0) return n;
+  lsa_loop_detect_t d;
+  lsa_loop_detect_init(&d);
+  if (detect) d = *detect;
+  int last = 0;
+  if (DetectQueries(d, n, capacity, &last) < 0)
+  {
+    LastError = who + "a query set outside the " + std::to_string(n) + " logged frames, per_query outside 1..16, room for fewer than queries * per_query candidates, or parameters out of limits";
+    return LSA_E_ARG;
+  }
+  // the device works from here on: the map workers and the look-ahead have enqueued what they had (nothing of theirs is changed)
+  WaitMaps();
+  std::vector<double> poses;
+  LoggedPoses16(poses, nullptr);
+  const std::vector<double> rows = RowsOf(poses.data(), n);
+  const int found = lsa_kplog_detect_loops(Ctx, &d, rows.data(), n, out, capacity);
+  if (found < 0) LastError = who + lsa_last_error(Ctx);
+  return found;
+}
+
+// ---- detect, register, solve, apply: the calls above and below, composed (lsa_slam_close_loops) ------------------------------
+int SlamCore::CloseLoops(const lsa_loop_detect_t* detect, const lsa_loop_closure_params_t* loopParams, const lsa_pgo_params_t* pgoParams, const lsa_pgo_robust_t* robust,
+                         double* poses17, int capacity, lsa_pgo_result_t* result, lsa_loop_report_t* reports, int reportCapacity)
+{
+  if (!Ctx) return LSA_E_NO_DEVICE;
+  const std::string who = "CloseLoops: ";
+  if (!poses17 || !result || reportCapacity < 0 || (reportCapacity > 0 && !reports)) { LastError = who + "bad argument"; return LSA_E_ARG; }
+  // what the solve would refuse is refused before anything runs: a refusal changes nothing
+  const int n = LogReady(who, "there is no logged trajectory to optimize");
+  if (n < 0) return n;
+  lsa_pgo_params_t pp;
+  lsa_pgo_params_init(&pp);
+  if (pgoParams) pp = *pgoParams;
+  if (!pg::params_ok(pp) || (robust && !pg::robust_ok(*robust))) { LastError = who + "pose-graph parameters out of limits, a loss outside 0..3, or a scale that is not finite and positive"; return LSA_E_ARG; }
+  if (n < 2) { LastError = who + "at least two logged poses"; return LSA_E_ARG; }
+  if (capacity < n) { LastError = who + "room for " + std::to_string(capacity) + " of " + std::to_string(n) + " poses"; return LSA_E_ARG; }
+  std::vector<lsa_loop_candidate_t> found(static_cast<size_t>(reportCapacity));
+  const int m = DetectLoopClosures(detect, found.data(), reportCapacity);
+  if (m < 0) return m;
+  std::vector<lsa_loop_report_t> rep(static_cast<size_t>(m));
+  std::vector<lsa_pgo_edge_t> edges;
+  for (int k = 0; k < m; ++k)
+  {
+    const lsa_loop_candidate_t& c = found[static_cast<size_t>(k)];
+    lsa_loop_report_t& r = rep[static_cast<size_t>(k)];
+    std::memset(&r, 0, sizeof(r));
+    r.query = c.query;
+    r.frame = c.frame;
+    r.distance = c.distance;
+    r.yaw = c.yaw;
+    r.edge = -1;
+    r.weight = -1.;
+    // the start: the revisited frame's pose with the base turned by the descriptors' yaw, P[frame] * Rz(yaw)
+    Pose rz = Pose::Identity();
+    rz(0, 0) = std::cos(c.yaw);
+    rz(0, 1) = -std::sin(c.yaw);
+    rz(1, 0) = std::sin(c.yaw);
+    rz(1, 1) = std::cos(c.yaw);
+    const Pose guess = LogTrajectory[c.frame].pose * rz;
+    lsa_loop_closure_result_t reg;
+    const int rc = RegisterLoggedFrames(c.query, c.frame, loopParams, guess.m, &reg);
+    r.status = rc < 0 ? rc : reg.status;
+    if (rc < 0) continue;  // (windows that overlap, say: the candidate is reported, no edge comes of it)
+    r.iterations = reg.iterations;
+    r.position_error = reg.position_error;
+    lsa_pgo_edge_t ed;
+    std::memset(&ed, 0, sizeof(ed));
+    ed.from = c.frame;
+    ed.to = c.query;
+    std::memcpy(ed.relative, reg.relative, sizeof(ed.relative));
+    if (reg.status != 0 || lsa_pgo_information_from_covariance(reg.covariance, ed.information) != LSA_OK) continue;
+    r.edge = static_cast<int>(edges.size());
+    edges.push_back(ed);
+  }
+  if (edges.empty())
+  {
+    // nothing to solve: the poses as they are logged, a summary that says so
+    std::vector<double> poses;
+    LoggedPoses16(poses, nullptr);
+    const std::vector<double> rows = RowsOf(poses.data(), n);
+    std::memcpy(poses17, rows.data(), rows.size() * sizeof(double));
+    std::memset(result, 0, sizeof(*result));
+    result->message = m == 0 ? "no loop candidate: nothing to solve" : "no loop edge: nothing to solve";
+  }
+  else
+  {
+    std::vector<double> verdict(2 * edges.size());
+    const int rc = OptimizeLoggedTrajectory(edges.data(), static_cast<int>(edges.size()), &pp, poses17, capacity, result, robust, verdict.data());
+    if (rc < 0) return rc;
+    for (lsa_loop_report_t& r : rep)
+      if (r.edge >= 0)
+      {
+        r.chi2 = verdict[2 * static_cast<size_t>(r.edge)];
+        r.weight = verdict[2 * static_cast<size_t>(r.edge) + 1];
+      }
+  }
+  LastError.clear();  // (a refused registration left its reason; the call as a whole went through, and its reports say the rest)
+  if (m > 0) std::memcpy(reports, rep.data(), static_cast<size_t>(m) * sizeof(lsa_loop_report_t));
+  return m;
 }
 
 // ---- pose-graph optimization of the logged trajectory (lsa_pose_graph.hip) ---------------------------------------------------

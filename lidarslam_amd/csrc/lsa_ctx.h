@@ -331,6 +331,8 @@ struct lsa_ctx
   // the log's descriptor store (lsa_place.hip): made by the first describe, follows the log's appends, pops and clears
   lsa::PlaceStore* place = nullptr;
   int place_max_blocks = 0;                     // lsa_debug_set "place_max_blocks": 0 = the default
+  int place_untiled = 0;                        // lsa_debug_set "place_untiled": k_place_search_rows a column at a time (to measure against)
+  int place_table_bytes = 0;                    // lsa_debug_set "place_table_bytes": the budget of loop detection's table, 0 = the default
   // the table of map descriptors (lsa_map_place.hip): made by the first description, kept until the context goes
   lsa::MapPlaceStore* map_place = nullptr;
   int map_describe_slice = 0;                   // lsa_debug_set "map_describe_slice": points a slice, 0 = the default

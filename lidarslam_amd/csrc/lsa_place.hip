@@ -22,23 +22,6 @@ using namespace lsa;
 
 namespace lsa
 {
-struct PlaceStore
-{
-  lsa_place_params_t params;
-  bool have_params = false;
-  float* slots = nullptr;
-  long long cap = 0;        // slots
-  int stride = 0;           // floats a slot
-  long long head = 0;       // the slot of frame 0
-  std::deque<char> valid;   // of the log's first valid.size() frames; the frames behind them have no descriptor
-  void* table = nullptr;    // k_log_describe's frames
-  size_t table_cap = 0;
-  PlaceResult* result_dev = nullptr;
-  PlaceResult* result_host = nullptr;  // pinned
-  long long result_cap = 0;
-  int described = 0;        // by the last call
-};
-
 void place_pop_front(lsa_ctx* ctx)
 {
   PlaceStore* st = ctx->place;
@@ -62,6 +45,11 @@ void place_destroy(lsa_ctx* ctx)
   if (st->table) (void)hipFree(st->table);
   if (st->result_dev) (void)hipFree(st->result_dev);
   if (st->result_host) (void)hipHostFree(st->result_host);
+  if (st->rows_table) (void)hipFree(st->rows_table);
+  if (st->detect_up_dev) (void)hipFree(st->detect_up_dev);
+  if (st->detect_up_host) (void)hipHostFree(st->detect_up_host);
+  if (st->detect_res_dev) (void)hipFree(st->detect_res_dev);
+  if (st->detect_res_host) (void)hipHostFree(st->detect_res_host);
   delete st;
   ctx->place = nullptr;
 }
@@ -333,6 +321,19 @@ int describe_missing(lsa_ctx* ctx, PlaceStore* st, int first, int last, int also
   return LSA_OK;
 }
 }  // namespace
+
+namespace lsa
+{
+int place_prepare(lsa_ctx* ctx, const char* who, const lsa_place_params_t* params, int first, int last)
+{
+  int rc = check(ctx, who, params, first, last);
+  if (rc) return rc;
+  LSA_HIP(ctx, hipSetDevice(ctx->device));
+  rc = ensure_store(ctx, *params);
+  if (rc) return rc;
+  return describe_missing(ctx, ctx->place, first, last, -1);
+}
+}  // namespace lsa
 
 extern "C" {
 

@@ -526,6 +526,60 @@ public:
     for (std::size_t i = 0; i < poses.size(); ++i) std::memcpy(poses[i].matrix.data(), rows.data() + 17 * i, 16 * sizeof(double));
     return poses;
   }
+  // ---- every loop closure of the log.  DetectLoopClosures: where did this drive revisit itself -- RecognizePlace for every
+  // query of a set (first_query, first_query + query_stride, ... <= last_query; < 0: the last logged frame) with per_query
+  // (1..16) candidates each, in one pass on the device (lsa_slam_detect_loop_closures).  The queries ascending, each query's
+  // candidates best first; empty when there is none or when it cannot (GetLastError() says why).
+  using LoopDetectionParameters = lsa_loop_detect_t;
+  using LoopCandidate = lsa_loop_candidate_t;
+  using LoopReport = lsa_loop_report_t;
+  static LoopDetectionParameters DefaultLoopDetectionParameters()
+  {
+    LoopDetectionParameters p;
+    lsa_loop_detect_init(&p);
+    return p;
+  }
+  std::vector<LoopCandidate> DetectLoopClosures(const LoopDetectionParameters& detect = DefaultLoopDetectionParameters())
+  {
+    const int n = lsa_slam_logged_frames(this->Handle);
+    const int last = detect.last_query < 0 ? n - 1 : detect.last_query;
+    const long long room = detect.query_stride >= 1 && detect.per_query >= 1 && last >= detect.first_query
+                             ? ((static_cast<long long>(last) - detect.first_query) / detect.query_stride + 1) * detect.per_query : 0;
+    std::vector<LoopCandidate> found(static_cast<std::size_t>(room > 0 ? room : 1));
+    const int rc = lsa_slam_detect_loop_closures(this->Handle, &detect, found.data(), static_cast<int>(room));
+    this->LastError = rc < 0 ? std::string("DetectLoopClosures: ") + lsa_slam_last_error(this->Handle) : std::string();
+    found.resize(static_cast<std::size_t>(rc > 0 ? rc : 0));
+    return found;
+  }
+  // CloseLoops: fix it -- DetectLoopClosures, RegisterLoggedFrames(query, frame, loopParams, pose[frame] * Rz(yaw)) for every
+  // candidate under the logged poses, a LoopClosureEdge for every registration with status 0 and a positive definite
+  // covariance, one OptimizeLoggedTrajectory over them under `robust` (a false place match is discounted, not obeyed), applied
+  // where pgoParams.apply != 0 (lsa_slam_close_loops).  Returns the optimized poses; `reports` gets one entry per candidate:
+  // its registration, its edge's index (-1: none came of it) and its verdict {chi2, weight}.  Without a candidate or an edge
+  // nothing is solved or changed: the logged poses come back, summary->message says so, GetLastError() is empty.  Empty when it
+  // cannot (GetLastError() says why and summary->termination is the negative LSA_E_* code).
+  std::vector<Transform> CloseLoops(const LoopDetectionParameters& detect, const LoopClosureParameters& loopParams, const PoseGraphParameters& pgoParams,
+                                    const RobustParameters& robust, PoseGraphSummary* summary = nullptr, std::vector<LoopReport>* reports = nullptr)
+  {
+    std::vector<Transform> poses = this->GetTrajectory();
+    const int last = detect.last_query < 0 ? static_cast<int>(poses.size()) - 1 : detect.last_query;
+    const long long room = detect.query_stride >= 1 && detect.per_query >= 1 && last >= detect.first_query
+                             ? ((static_cast<long long>(last) - detect.first_query) / detect.query_stride + 1) * detect.per_query : 0;
+    std::vector<LoopReport> rep(static_cast<std::size_t>(room > 0 ? room : 1));
+    std::vector<double> rows((poses.size() + 1) * 17);
+    PoseGraphSummary result;
+    std::memset(&result, 0, sizeof(result));
+    const int rc = lsa_slam_close_loops(this->Handle, &detect, &loopParams, &pgoParams, &robust, rows.data(), static_cast<int>(poses.size()), &result, rep.data(),
+                                        static_cast<int>(room));
+    this->LastError = rc < 0 ? std::string("CloseLoops: ") + lsa_slam_last_error(this->Handle) : std::string();
+    if (rc < 0) result.termination = rc;
+    if (summary) *summary = result;
+    rep.resize(static_cast<std::size_t>(rc > 0 ? rc : 0));
+    if (reports) *reports = rep;
+    if (rc < 0) return {};
+    for (std::size_t i = 0; i < poses.size(); ++i) std::memcpy(poses[i].matrix.data(), rows.data() + 17 * i, 16 * sizeof(double));
+    return poses;
+  }
   // The logged frame to try a loop closure of `query` against BY POSITION: among the frames at least minTravelled metres
   // back along GetTrajectory() and within maxDistance metres of query's position, the nearest; -1 when there is none.  Host
   // only.  By appearance: RecognizePlace above.

@@ -15,6 +15,7 @@
 //   pose graph   poses, edges, per-edge block records, block rows D / L / U, the cyclic reduction's levels, PCG vectors (lsa_pose_graph.hip; only once asked for)
 #pragma once
 #include <hip/hip_runtime.h>
+#include <algorithm>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -137,6 +138,14 @@ struct PendingEvent
 
 struct KpLog;  // lsa_kplog.hip
 struct PlaceStore;  // lsa_place.hip
+struct PlaceResult;  // lsa_place_io.h
+// where a search's (distance, shift) table lands and is copied back to: one for the log's store and the maps' table alike
+struct PlaceResults
+{
+  PlaceResult* dev = nullptr;
+  PlaceResult* pinned = nullptr;
+  long long cap = 0;  // entries
+};
 struct PgoBuffers;  // lsa_pose_graph.hip
 struct MapPlaceStore;  // lsa_map_place.hip
 
@@ -332,6 +341,7 @@ struct lsa_ctx
   lsa::PlaceStore* place = nullptr;
   int place_max_blocks = 0;                     // lsa_debug_set "place_max_blocks": 0 = the default
   int place_untiled = 0;                        // lsa_debug_set "place_untiled": k_place_search_rows a column at a time (to measure against)
+  lsa::PlaceResults place_results;              // lsa_place_search.hip: of the single-query searches
   int place_table_bytes = 0;                    // lsa_debug_set "place_table_bytes": the budget of loop detection's table, 0 = the default
   // the table of map descriptors (lsa_map_place.hip): made by the first description, kept until the context goes
   lsa::MapPlaceStore* map_place = nullptr;
@@ -392,6 +402,27 @@ inline void retire_host(lsa_ctx* ctx, void* p)
   if (!p) return;
   std::lock_guard<std::mutex> l(ctx->grave_mutex);
   ctx->grave_host.push_back(p);
+}
+// Room for `count` elements in a device buffer whose contents need not survive, and in its pinned twin where there is one
+// (pinned != nullptr); what is outgrown goes to the graveyard.  The new capacity is count and half as much again but at
+// least `floor`, or, with exact, count.
+template <typename T, typename N>
+int scratch_room(lsa_ctx* ctx, T** dev, T** pinned, N* cap, size_t count, size_t floor = 0, bool exact = false)
+{
+  if (count <= (size_t)*cap) return LSA_OK;
+  retire_dev(ctx, *dev);
+  *dev = nullptr;
+  if (pinned)
+  {
+    retire_host(ctx, *pinned);
+    *pinned = nullptr;
+  }
+  *cap = 0;
+  const size_t want = exact ? count : std::max(count + count / 2, floor);
+  LSA_HIP(ctx, hipMalloc((void**)dev, want * sizeof(T)));
+  if (pinned) LSA_HIP(ctx, hipHostMalloc((void**)pinned, want * sizeof(T), hipHostMallocDefault));
+  *cap = (N)want;
+  return LSA_OK;
 }
 // the 18 words of the keypoints' bounding boxes: [16..24] of range_bits for lsa_keypoint_bboxes_begin, [32..40] for lsa_localization_begin
 inline unsigned* box_words(lsa_ctx* ctx) { return reinterpret_cast<unsigned*>(ctx->range_bits + 16); }

@@ -291,6 +291,8 @@ void lsa_ctx_destroy(lsa_ctx* ctx)
   kplog_destroy(ctx);
   pgo_destroy(ctx);
   map_place_destroy(ctx);
+  fr(ctx->place_results.dev);
+  if (ctx->place_results.pinned) (void)hipHostFree(ctx->place_results.pinned);
   fr(ctx->partials); fr(ctx->reduce_out); fr(ctx->hist_dev); fr(ctx->scratch_out); fr(ctx->range_bits);
   for (auto& s : ctx->store) fr(s.first);
   if (ctx->host_pinned) (void)hipHostFree(ctx->host_pinned);

@@ -1244,8 +1244,8 @@ int lsa_debug_set(lsa_ctx* ctx, const char* name, int value)
   else if (n == "pcd_lds") ctx->pcd_lds = value < 0 ? -1 : (value != 0);  // lsa_pcd.hip: the form of the two conversion kernels
   else if (n == "kplog_chunk_kib") ctx->kplog_chunk_bytes = value < 0 ? ((size_t)32 << 20) : (size_t)std::max(value, 1) << 10;  // lsa_kplog.hip: chunks made from now on
   else if (n == "kplog_fail_alloc") ctx->debug_kplog_fail_alloc = value > 0 ? 1 : 0;
-  else if (n == "place_max_blocks") ctx->place_max_blocks = value > 0 ? value : 0;  // lsa_place.hip: workgroups of a search launch
-  else if (n == "place_untiled") ctx->place_untiled = value != 0;  // lsa_place_detect.hip: the search's columns one at a time
+  else if (n == "place_max_blocks") ctx->place_max_blocks = value > 0 ? value : 0;  // lsa_place_search.hip: workgroups (k_place_search) or pieces (k_place_search_rows) of a search launch
+  else if (n == "place_untiled") ctx->place_untiled = value != 0;  // lsa_place_search.hip: the search's columns one at a time
   else if (n == "place_table_bytes") ctx->place_table_bytes = value > 0 ? value : 0;  // lsa_place_detect.hip: the table's byte budget
   else if (n == "map_describe_slice") ctx->map_describe_slice = value > 0 ? value : 0;  // lsa_map_place.hip: points a slice (the next description's)
   else if (n == "map_describe_cull") ctx->map_describe_cull = value != 0;

@@ -8,16 +8,16 @@
 //                      the viewpoint's zeroed image in global memory by integer atomic max.  Maxima commute: the image does
 //                      not depend on the slicing, on the order or on which slices were passed over as out of reach
 //   k_map_finish       a workgroup per viewpoint: words -> cell values, then a lane per sector for the column norms
-// The query's slot is written by k_log_describe and the table searched by k_place_search (lsa_place_io.h).
+// Offer and finish are lsa_place_image.h's, k_log_describe's own.  The query's slot is written by k_log_describe and the
+// table searched by k_place_search (lsa_place_io.h).
 // The source is "two float4 per point, n points": a device grid's own array (MapView::pts) or an uploaded lsa_point_t array.
 // The table belongs to the context and is kept between calls; nothing is freed while work may be in flight (the graveyard).
 #include <algorithm>
 #include <cstring>
 #include <vector>
 #include "lsa_grid.h"
+#include "lsa_place_image.h"
 #include "lsa_place_io.h"
-#include "lsa_scan_descriptor.h"
-#include "lsa_wave.h"
 
 using namespace lsa;
 
@@ -26,7 +26,6 @@ namespace
 constexpr int kThreads = 256;
 constexpr int kDefaultSlice = 4096;   // points a slice, unless lsa_debug_set "map_describe_slice" says otherwise
 constexpr int kTargetBlocks = 2048;   // workgroups a description aims at: rows of slices per viewpoint = kTargetBlocks / V
-constexpr int kMaxCells = place::kMaxRings * place::kMaxSectors;
 
 // up to three point arrays, cut into slices that are numbered through: source k has the slices first[k] .. first[k + 1] - 1
 struct MapSources
@@ -72,8 +71,8 @@ __global__ __launch_bounds__(kThreads) void k_map_slice_boxes(MapSources m, int 
 __global__ __launch_bounds__(kThreads) void k_map_describe(MapSources m, int slice_size, int slices, const float4* __restrict__ boxes /* nullptr: no slice is passed over */,
                                                            const double* __restrict__ viewpoints, unsigned* __restrict__ images, lsa_place_params_t p, double reach2)
 {
-  __shared__ unsigned s_img[kMaxCells];
-  const int cells = p.rings * p.sectors;  // <= kMaxCells: the parameters were checked
+  __shared__ unsigned s_img[kImageCells];
+  const int cells = p.rings * p.sectors;  // <= kImageCells: the parameters were checked
   const double vx = viewpoints[3 * (size_t)blockIdx.x], vy = viewpoints[3 * (size_t)blockIdx.x + 1], vz = viewpoints[3 * (size_t)blockIdx.x + 2];
   for (int c = threadIdx.x; c < cells; c += kThreads) s_img[c] = 0u;
   __syncthreads();
@@ -95,8 +94,7 @@ __global__ __launch_bounds__(kThreads) void k_map_describe(MapSources m, int sli
       const float x = place::map_coord(a.x, vx), y = place::map_coord(a.y, vy), z = place::map_coord(a.z, vz);
       // out of reach (lsa_scan_descriptor.h: map_reach) before the square root and the angle; a NaN compares false and is cell_of's
       if ((double)x * (double)x + (double)y * (double)y > reach2) continue;
-      int cell;
-      if (place::cell_of(p, x, y, z, &cell)) atomicMax(&s_img[cell], f2ou(place::offer(p, z)));
+      image_offer(s_img, p, x, y, z);
     }
   }
   if (!touched) return;
@@ -109,22 +107,11 @@ __global__ __launch_bounds__(kThreads) void k_map_describe(MapSources m, int sli
   }
 }
 
-// A workgroup per viewpoint: k_log_describe's second half on the merged image.
+// A workgroup per viewpoint: the merged image finished from global words into LDS floats.
 __global__ __launch_bounds__(kThreads) void k_map_finish(const unsigned* __restrict__ images, float* __restrict__ table, int stride, lsa_place_params_t p)
 {
-  __shared__ float s_val[kMaxCells];
-  const int cells = p.rings * p.sectors;
-  const unsigned* __restrict__ img = images + (size_t)blockIdx.x * (size_t)cells;
-  float* __restrict__ out = table + (size_t)blockIdx.x * (size_t)stride;
-  for (int c = threadIdx.x; c < cells; c += kThreads)
-  {
-    const unsigned u = img[c];
-    const float v = u ? place::cell_value(ou2f(u)) : 0.f;
-    out[c] = v;
-    s_val[c] = v;
-  }
-  __syncthreads();
-  for (int j = threadIdx.x; j < p.sectors; j += kThreads) out[cells + j] = place::column_norm(s_val, p.rings, p.sectors, j);
+  __shared__ float s_val[kImageCells];
+  image_finish<kThreads>(images + (size_t)blockIdx.x * (size_t)(p.rings * p.sectors), s_val, table + (size_t)blockIdx.x * (size_t)stride, p);
 }
 
 struct SourceKey
@@ -163,18 +150,14 @@ struct MapPlaceStore
   size_t upload_cap = 0;          // points
   DescribeFrame* frame_dev = nullptr;
   DescribeFrame frame_host;
-  PlaceResult* result_dev = nullptr;
-  PlaceResult* result_host = nullptr;  // pinned
-  int result_cap = 0;
 };
 
 void map_place_destroy(lsa_ctx* ctx)
 {
   MapPlaceStore* st = ctx->map_place;
   if (!st) return;
-  for (void* p : {(void*)st->boxes, (void*)st->table, (void*)st->images, (void*)st->vp_dev, (void*)st->upload, (void*)st->frame_dev, (void*)st->result_dev})
+  for (void* p : {(void*)st->boxes, (void*)st->table, (void*)st->images, (void*)st->vp_dev, (void*)st->upload, (void*)st->frame_dev})
     if (p) (void)hipFree(p);
-  if (st->result_host) (void)hipHostFree(st->result_host);
   delete st;
   ctx->map_place = nullptr;
 }
@@ -182,24 +165,14 @@ void map_place_destroy(lsa_ctx* ctx)
 
 namespace
 {
-// room for `count` elements in a device buffer whose contents need not survive
+// room for `count` elements in a device buffer of the store: half as much again, 64 at the least
 template <typename T, typename N>
-int ensure_dev(lsa_ctx* ctx, T** buf, N* cap, size_t count)
-{
-  if (count <= (size_t)*cap && *buf) return LSA_OK;
-  retire_dev(ctx, *buf);
-  *buf = nullptr;
-  *cap = 0;
-  const size_t want = std::max<size_t>(count + count / 2, 64);
-  LSA_HIP(ctx, hipMalloc((void**)buf, want * sizeof(T)));
-  *cap = (N)want;
-  return LSA_OK;
-}
+int room(lsa_ctx* ctx, T** buf, N* cap, size_t count) { return scratch_room<T>(ctx, buf, nullptr, cap, count, 64); }
 
 int check_call(lsa_ctx* ctx, const char* who, const lsa_place_params_t* params, const double* viewpoints, int V)
 {
   if (!ctx) return LSA_E_ARG;
-  if (!params || !place::params_ok(*params)) return ctx->fail(LSA_E_ARG, std::string(who) + ": descriptor parameters out of limits");
+  if (int rc = check_params(ctx, who, params)) return rc;
   if (!viewpoints || V < 1) return ctx->fail(LSA_E_ARG, std::string(who) + ": at least one viewpoint");
   for (size_t i = 0; i < 3 * (size_t)V; ++i)
     if (!(viewpoints[i] - viewpoints[i] == 0.)) return ctx->fail(LSA_E_ARG, std::string(who) + ": viewpoint " + std::to_string(i / 3) + " is not finite");
@@ -209,7 +182,6 @@ int check_call(lsa_ctx* ctx, const char* who, const lsa_place_params_t* params, 
 // The descriptors of `m` at the viewpoints into slots 0..V-1 of the table, enqueued on `stream`; the caller waits.
 int describe(lsa_ctx* ctx, MapPlaceStore* st, const MapSources& src, const SourceKey key[3], const lsa_place_params_t& p, const double* viewpoints, int V, hipStream_t stream)
 {
-  static_assert(sizeof(lsa_place_params_t) == 4 * sizeof(int32_t) + 3 * sizeof(double), "no padding: compared by bytes");
   st->valid = false;
   st->query_valid = false;
   const int cells = place::cells(p), stride = place::length(p);
@@ -223,10 +195,10 @@ int describe(lsa_ctx* ctx, MapPlaceStore* st, const MapSources& src, const Sourc
     m.first[k + 1] = (int)first;
   }
   const int slices = m.first[3];
-  int rc = ensure_dev(ctx, &st->table, &st->table_cap, ((size_t)V + 1) * (size_t)stride);
-  if (!rc) rc = ensure_dev(ctx, &st->images, &st->images_cap, (size_t)V * (size_t)cells);
-  if (!rc) rc = ensure_dev(ctx, &st->vp_dev, &st->vp_cap, 3 * (size_t)V);
-  if (!rc) rc = ensure_dev(ctx, &st->boxes, &st->boxes_cap, (size_t)std::max(slices, 1));
+  int rc = room(ctx, &st->table, &st->table_cap, ((size_t)V + 1) * (size_t)stride);
+  if (!rc) rc = room(ctx, &st->images, &st->images_cap, (size_t)V * (size_t)cells);
+  if (!rc) rc = room(ctx, &st->vp_dev, &st->vp_cap, 3 * (size_t)V);
+  if (!rc) rc = room(ctx, &st->boxes, &st->boxes_cap, (size_t)std::max(slices, 1));
   if (rc) return rc;
   st->viewpoints.assign(viewpoints, viewpoints + 3 * (size_t)V);
   LSA_HIP(ctx, hipMemcpyAsync(st->vp_dev, st->viewpoints.data(), 3 * (size_t)V * sizeof(double), hipMemcpyHostToDevice, stream));
@@ -285,7 +257,7 @@ int lsa_map_place_describe_points(lsa_ctx* ctx, const lsa_place_params_t* params
   if (n < 0 || (n > 0 && !pts)) return ctx->fail(LSA_E_ARG, std::string(who) + ": bad argument");
   LSA_HIP(ctx, hipSetDevice(ctx->device));
   MapPlaceStore* st = store_of(ctx);
-  rc = ensure_dev(ctx, &st->upload, &st->upload_cap, (size_t)std::max(n, 1));
+  rc = room(ctx, &st->upload, &st->upload_cap, (size_t)std::max(n, 1));
   if (rc) return rc;
   if (n > 0) LSA_HIP(ctx, hipMemcpyAsync(st->upload, pts, (size_t)n * sizeof(lsa_point_t), hipMemcpyHostToDevice, ctx->stream));
   MapSources m = {};
@@ -330,7 +302,7 @@ int lsa_map_place_describe_grids(lsa_ctx* ctx, lsa_device_grid* const grids[3], 
     key[k].n = m.n[k];
     if (!stream) stream = g->stream;
   }
-  if (st->valid && st->from_grids && st->V == V && std::memcmp(&st->params, params, sizeof(*params)) == 0 && st->key[0] == key[0] && st->key[1] == key[1] &&
+  if (st->valid && st->from_grids && st->V == V && same_params(st->params, *params) && st->key[0] == key[0] && st->key[1] == key[1] &&
       st->key[2] == key[2] && std::memcmp(st->viewpoints.data(), viewpoints, 3 * (size_t)V * sizeof(double)) == 0)
     return 0;
   if (!stream) stream = ctx->stream;
@@ -359,11 +331,11 @@ int lsa_map_place_search(lsa_ctx* ctx, const lsa_place_params_t* params, int set
 {
   const char* who = "lsa_map_place_search";
   if (!ctx) return LSA_E_ARG;
-  if (!params || !place::params_ok(*params)) return ctx->fail(LSA_E_ARG, std::string(who) + ": descriptor parameters out of limits");
+  if (int rc = check_params(ctx, who, params)) return rc;
   if (set < 0 || set > 2 || !distance_out || !shift_out) return ctx->fail(LSA_E_ARG, std::string(who) + ": bad argument");
   MapPlaceStore* st = ctx->map_place;
   if (!st || !st->valid) return ctx->fail(LSA_E_STATE, std::string(who) + ": no table (lsa_map_place_describe_points / _grids)");
-  if (std::memcmp(&st->params, params, sizeof(*params)) != 0) return ctx->fail(LSA_E_STATE, std::string(who) + ": the table was described under other parameters");
+  if (!same_params(st->params, *params)) return ctx->fail(LSA_E_STATE, std::string(who) + ": the table was described under other parameters");
   DescribeFrame f;
   long long points = 0;
   for (int k = 0; k < 3; ++k)
@@ -378,18 +350,6 @@ int lsa_map_place_search(lsa_ctx* ctx, const lsa_place_params_t* params, int set
   LSA_HIP(ctx, hipSetDevice(ctx->device));
   const int V = st->V;
   if (!st->frame_dev) LSA_HIP(ctx, hipMalloc((void**)&st->frame_dev, sizeof(DescribeFrame)));
-  if (V > st->result_cap)
-  {
-    retire_dev(ctx, st->result_dev);
-    retire_host(ctx, st->result_host);
-    st->result_dev = nullptr;
-    st->result_host = nullptr;
-    st->result_cap = 0;
-    const int cap = V + V / 2;
-    LSA_HIP(ctx, hipMalloc((void**)&st->result_dev, (size_t)cap * sizeof(PlaceResult)));
-    LSA_HIP(ctx, hipHostMalloc((void**)&st->result_host, (size_t)cap * sizeof(PlaceResult), hipHostMallocDefault));
-    st->result_cap = cap;
-  }
   st->query_valid = false;
   st->frame_host = f;
   LSA_HIP(ctx, hipMemcpyAsync(st->frame_dev, &st->frame_host, sizeof(DescribeFrame), hipMemcpyHostToDevice, ctx->stream));
@@ -398,19 +358,9 @@ int lsa_map_place_search(lsa_ctx* ctx, const lsa_place_params_t* params, int set
     place_describe_launch(st->frame_dev, 1, st->table, st->stride, st->params, ctx->stream);
   }
   LSA_HIP(ctx, hipGetLastError());
-  {
-    ProfScope ps(ctx, "place_search", (double)(V + 1) * st->stride * 4 + (double)V * sizeof(PlaceResult));
-    place_search_launch(ctx, st->table, (long long)V + 1, 0, st->stride, V, 0, V, st->result_dev, st->params, ctx->stream);
-  }
-  LSA_HIP(ctx, hipGetLastError());
-  LSA_HIP(ctx, hipMemcpyAsync(st->result_host, st->result_dev, (size_t)V * sizeof(PlaceResult), hipMemcpyDeviceToHost, ctx->stream));
-  LSA_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  const int rc = place_search_one(ctx, st->table, (long long)V + 1, 0, st->stride, st->params, V, 0, V, distance_out, shift_out);
+  if (rc) return rc;
   st->query_valid = true;
-  for (int i = 0; i < V; ++i)
-  {
-    distance_out[i] = st->result_host[i].distance;
-    shift_out[i] = st->result_host[i].shift;
-  }
   return LSA_OK;
 }
 

@@ -4,8 +4,7 @@
 // v = op(v, shuffled), a workgroup's combine runs over the wavefronts left to right, ((s0 op s1) op s2) op s3 -- integer
 // results do not depend on either, k_overlap_score's float sum does and is compared bit for bit.
 // Outside on purpose (hot path or another shape, each with tests of its own): the DPP group scans of lsa_match_fused.hip /
-// lsa_knn.h, the sub-wavefront group scan of lsa_match_staged.hip, lsa_accum.h, lsa_lm.hip, the (distance, shift) arg-min
-// of lsa_place.hip.
+// lsa_knn.h, the sub-wavefront group scan of lsa_match_staged.hip, lsa_accum.h, lsa_lm.hip.
 #pragma once
 #include <cfloat>
 #include <hip/hip_runtime.h>
@@ -42,6 +41,25 @@ __device__ __forceinline__ T wave_reduce(T v, Op op)
 template <typename T> __device__ __forceinline__ T wave_sum(T v) { return wave_reduce(v, OpSum()); }
 template <typename T> __device__ __forceinline__ T wave_min(T v) { return wave_reduce(v, OpMin()); }
 template <typename T> __device__ __forceinline__ T wave_max(T v) { return wave_reduce(v, OpMax()); }
+
+// The arg-min of (value, index) pairs, index -1: none.  before(v2, i2, v, i) says that (v2, i2) ranks before (v, i) and
+// must be a total order: then any tree gives the sequential loop's answer.  argmin_take is one step of that loop.
+template <typename Before>
+__device__ __forceinline__ void argmin_take(float& v, int& i, float v2, int i2, Before before)
+{
+  if (i2 >= 0 && (i < 0 || before(v2, i2, v, i))) { v = v2; i = i2; }
+}
+// lane 0 holds the result
+template <typename Before>
+__device__ __forceinline__ void wave_argmin(float& v, int& i, Before before)
+{
+  for (int o = 32; o > 0; o >>= 1)
+  {
+    const float v2 = __shfl_down(v, o);
+    const int i2 = __shfl_down(i, o);
+    argmin_take(v, i, v2, i2, before);
+  }
+}
 
 // EVERY thread of the workgroup (WAVES wavefronts) must call it; scratch: the caller's __shared__ array of WAVES elements,
 // not to be used again before the workgroup's next barrier.  One barrier; thread 0 holds the result.

@@ -4,10 +4,10 @@ frame a query, the descriptors present.
                 only way to ask before; its code is untouched, so the loop run here is the parent commit's), alternated,
                 --runs each; the two must give the same candidates
   kernel        event time (ProfScope) of k_place_search_rows per computed pair -- four columns at a time, and one at a time
-                (lsa_debug_set "place_untiled") -- against k_place_search's, at 20 x 60 and 32 x 120, in a run of its own with
-                profiling on
+                (lsa_debug_set "place_untiled"), the scope "place_search_rows" -- against k_place_search's over the loop of
+                recognitions (the scope "place_search"), at 20 x 60 and 32 x 120, in a run of its own with profiling on
   gates         pairs computed / pairs total with max_distance = 30 m
-Appends to profiles/loop_detection.jsonl."""
+--tag goes into every line (which build was measured).  Appends to profiles/loop_detection.jsonl."""
 import argparse, json, os, sys, time
 import numpy as np
 sys.path.insert(0, os.getcwd())
@@ -17,12 +17,15 @@ ap = argparse.ArgumentParser()
 ap.add_argument("--frames", type=int, default=200)
 ap.add_argument("--model", type=int, default=128)
 ap.add_argument("--runs", type=int, default=3)
+ap.add_argument("--tag", default="")
 ap.add_argument("--out", default="profiles/loop_detection.jsonl")
 a = ap.parse_args()
 out = open(a.out, "a")
 
 
 def emit(**kw):
+    if a.tag:
+        kw["tag"] = a.tag
     out.write(json.dumps(kw) + "\n"); out.flush(); print(kw, flush=True)
 
 

@@ -4,6 +4,9 @@ maps at every viewpoint, then searches), of --runs further calls (search only: t
 copy, one wait), of a description with the slices out of reach passed over and with all of them read ("map_describe_cull"),
 and of the same answer from the host statement on the downloaded maps (L.map_descriptor, L.place_distance,
 L.map_place_select) -- the only reference there is for a time, the library having had no such call before.  One run each.
+--viewpoints N ...: instead of a viewpoint at every logged position, the last N of them (a search among one or four
+candidates), first call and search-only calls for each N; --profile 1: then --runs more search-only calls with profiling on,
+for the event time of the "place_search" scope.  --tag goes into every line (which build was measured).
 --strip N: instead, a made-up map much longer than the descriptor's reach -- N points on a strip of --strip-km sorted along it,
 a viewpoint every 2 m -- described from an uploaded array (map_place_describe) with the cull on and off: what passing slices
 over is worth where most of them are out of reach.  Appends to profiles/map_place.jsonl."""
@@ -19,12 +22,17 @@ ap.add_argument("--runs", type=int, default=5)
 ap.add_argument("--host", type=int, default=1)
 ap.add_argument("--strip", type=int, default=0)
 ap.add_argument("--strip-km", type=float, default=4.0)
+ap.add_argument("--viewpoints", type=int, nargs="*", default=[0])
+ap.add_argument("--profile", type=int, default=0)
+ap.add_argument("--tag", default="")
 ap.add_argument("--out", default="profiles/map_place.jsonl")
 a = ap.parse_args()
 out = open(a.out, "a")
 
 
 def emit(**kw):
+    if a.tag:
+        kw["tag"] = a.tag
     out.write(json.dumps(kw) + "\n"); out.flush(); print(kw, flush=True)
 
 
@@ -59,18 +67,31 @@ for f in range(a.frames):
     pts, stamp = L.synth_frame(a.model, 1000, f)
     s.add_frame(pts, stamp, f)
 P, _, _ = s.trajectory()
-vp = P[:, :3, 3].copy()
 ctx = s.context()
-t0 = time.perf_counter()
-first, summary = L.recognize_place_in_maps(s, vp, capacity=5)
-wall = time.perf_counter() - t0
-case = dict(model=a.model, frames=a.frames, viewpoints=int(vp.shape[0]), rings=20, sectors=60, map_points=[int(v) for v in summary.map_points],
-            query_points=[int(v) for v in summary.query_points], way_m=float(np.linalg.norm(np.diff(vp, axis=0), axis=1).sum()))
-emit(what="first_call_describe_and_search", **case, wall_s=wall, described=summary.described, candidates=brief(first))
-for run in range(a.runs):
+for nv in a.viewpoints:
+    vp = P[-nv:, :3, 3].copy()  # (nv = 0: all of them)
     t0 = time.perf_counter()
-    again, summary = L.recognize_place_in_maps(s, vp, capacity=5)
-    emit(what="search_only", run=run, **case, wall_s=time.perf_counter() - t0, described=summary.described, same=brief(again) == brief(first))
+    first, summary = L.recognize_place_in_maps(s, vp, capacity=5)
+    wall = time.perf_counter() - t0
+    case = dict(model=a.model, frames=a.frames, viewpoints=int(vp.shape[0]), rings=20, sectors=60, map_points=[int(v) for v in summary.map_points],
+                query_points=[int(v) for v in summary.query_points], way_m=float(np.linalg.norm(np.diff(P[:, :3, 3], axis=0), axis=1).sum()))
+    emit(what="first_call_describe_and_search", **case, wall_s=wall, described=summary.described, candidates=brief(first))
+    for run in range(a.runs):
+        t0 = time.perf_counter()
+        again, summary = L.recognize_place_in_maps(s, vp, capacity=5)
+        emit(what="search_only", run=run, **case, wall_s=time.perf_counter() - t0, described=summary.described, same=brief(again) == brief(first))
+    if a.profile:
+        ctx.profile(True)
+        ctx.profile_reset()
+        for run in range(a.runs):
+            L.recognize_place_in_maps(s, vp, capacity=5)
+        ctx.sync()
+        stat = {k["name"]: k for k in ctx.profile_stats()}["place_search"]
+        ctx.profile(False)
+        emit(what="place_search_scope", **case, total_ms=stat["total_ms"], launches=stat["launches"], event_overhead_us=ctx.profile_event_overhead_us())
+if a.viewpoints != [0]:
+    s.close()
+    sys.exit(0)
 # a description again (viewpoint 0 moved by a nanometre, so that the table is not kept), slices out of reach passed over or not
 boxes = L.map_place_slices(ctx)
 reach = 80.0 * (1.0 + 2.0 ** -20)

@@ -2,6 +2,8 @@
 the last frame (describes every logged frame, then searches), of --runs further calls (search only: one launch, one copy,
 one wait), and of the same query answered by the host statement on downloaded keypoints (L.scan_descriptor,
 L.place_distance, L.place_select) -- the only reference there is for a time, the library having had no such call before.
+--profile 1: then --runs more search-only calls with profiling on, for the event time of the "place_search" scope (the
+search kernel's launch).  --tag goes into every line (which build was measured).
 Appends to profiles/place_recognition.jsonl."""
 import argparse, json, os, sys, time
 import numpy as np
@@ -13,12 +15,16 @@ ap.add_argument("--frames", type=int, default=200)
 ap.add_argument("--model", type=int, default=128)
 ap.add_argument("--runs", type=int, default=5)
 ap.add_argument("--host", type=int, default=1)
+ap.add_argument("--profile", type=int, default=0)
+ap.add_argument("--tag", default="")
 ap.add_argument("--out", default="profiles/place_recognition.jsonl")
 a = ap.parse_args()
 out = open(a.out, "a")
 
 
 def emit(**kw):
+    if a.tag:
+        kw["tag"] = a.tag
     out.write(json.dumps(kw) + "\n"); out.flush(); print(kw, flush=True)
 
 
@@ -38,6 +44,16 @@ for run in range(a.runs):
     t0 = time.perf_counter()
     again = s.recognize_place(query, capacity=5, **search)
     emit(what="recognize_place_search_only", run=run, **case, wall_s=time.perf_counter() - t0, described=s.context().kplog_described(), same=again == first)
+if a.profile:
+    ctx = s.context()
+    ctx.profile(True)
+    ctx.profile_reset()
+    for run in range(a.runs):
+        s.recognize_place(query, capacity=5, **search)
+    ctx.sync()
+    stat = {k["name"]: k for k in ctx.profile_stats()}["place_search"]
+    ctx.profile(False)
+    emit(what="place_search_scope", **case, total_ms=stat["total_ms"], launches=stat["launches"], event_overhead_us=ctx.profile_event_overhead_us())
 if a.host:
     t0 = time.perf_counter()
     raw = [np.concatenate([s.logged_keypoints(i, k) for k in (L.EDGE, L.PLANE)]) for i in range(a.frames)]

@@ -1,5 +1,5 @@
 """Loop detection over the whole keypoint log on the device (lidarslam_amd/csrc/lsa_place_detect.hip): k_place_search_rows
-through L.place_search_rows, k_place_select_rows through L.kplog_detect_loops, and L.detect_loop_closures / L.close_loops on
+(lsa_place_search.hip) through L.place_search_rows, k_place_select_rows through L.kplog_detect_loops, and L.detect_loop_closures / L.close_loops on
 top of them.
 
 The reference is always the host statement -- L.place_distance for the table, L.place_detect_host for the candidates, the calls

@@ -255,6 +255,7 @@ def search_ctx(L, gpu_ctx, search_log):
         ctx.kplog_append_points(fr)
     yield ctx
     ctx.debug_set("place_max_blocks", 0)
+    ctx.debug_set("place_untiled", 0)
     ctx.kplog_clear()
 
 
@@ -264,14 +265,52 @@ def test_search_table_equals_the_host_statement(L, search_ctx, search_expected, 
     p = dict(rings=rings, sectors=sectors, type_mask=7, **extra)
     for query in QUERIES:
         want_d, want_s = search_expected(rings, sectors, extra, query)
-        # 300 candidates: more workgroups than the chip has CUs; 7 workgroups: every one strides over 42 or 43 candidates
-        for first, last, blocks in [(0, NCAND - 1, 0), (0, NCAND - 1, 7), (17, 17, 0), (29, 30, 0), (101, 165, 0), (101, 165, 64)]:
-            ctx.debug_set("place_max_blocks", blocks)
-            d, s = ctx.kplog_place_search(QUERIES[query], first, last, **p)
-            assert d.size == last - first + 1
-            assert d.tobytes() == want_d[first:last + 1].tobytes(), (query, first, last, blocks, np.flatnonzero(d != want_d[first:last + 1])[:8])
-            assert np.array_equal(s, want_s[first:last + 1]), (query, first, last, blocks, np.flatnonzero(s != want_s[first:last + 1])[:8])
+        # 300 candidates: more workgroups than the chip has CUs; 7 workgroups: every one strides over 42 or 43 candidates;
+        # short ranges from a first > 0 (lengths 3 and 5: no multiple of four or of two pairs, should the search ever run as a row
+        # of k_place_search_rows), the first and the last frame alone; all of it under both settings of "place_untiled", which
+        # k_place_search does not read
+        for first, last, blocks in [(0, NCAND - 1, 0), (0, NCAND - 1, 7), (17, 17, 0), (29, 30, 0), (101, 165, 0), (101, 165, 64), (7, 9, 0), (40, 44, 0), (0, 0, 0),
+                                    (NCAND - 1, NCAND - 1, 0)]:
+            for untiled in (0, 1):
+                ctx.debug_set("place_max_blocks", blocks)
+                ctx.debug_set("place_untiled", untiled)
+                d, s = ctx.kplog_place_search(QUERIES[query], first, last, **p)
+                assert d.size == last - first + 1
+                assert d.tobytes() == want_d[first:last + 1].tobytes(), (query, first, last, blocks, untiled, np.flatnonzero(d != want_d[first:last + 1])[:8])
+                assert np.array_equal(s, want_s[first:last + 1]), (query, first, last, blocks, untiled, np.flatnonzero(s != want_s[first:last + 1])[:8])
     ctx.debug_set("place_max_blocks", 0)
+    ctx.debug_set("place_untiled", 0)
+
+
+@pytest.mark.parametrize("rings,sectors,extra", SHAPES[1:3])
+def test_search_across_the_wrap_of_the_store(L, search_log, rings, sectors, extra):
+    """70 frames described: a store of 105 slots (half as much again as the log, lsa_place.hip: ensure_store), frame i in slot
+    i.  40 popped from the front, 40 appended: 70 <= 105, so the store stays and its head is slot 40 -- frame i in slot
+    (40 + i) % 105, the frames 65..69 in slots 0..4, past the wrap, the query (69) among them.  A context of its own: the
+    store of another test would be larger and not wrap."""
+    p = dict(rings=rings, sectors=sectors, type_mask=7, **extra)
+    ctx = L.Context(0)
+    try:
+        for fr in search_log[:70]:
+            ctx.kplog_append_points(fr)
+        assert ctx.kplog_describe(0, 69, **p) == 70
+        for _ in range(40):
+            ctx.kplog_pop_front()
+        for fr in search_log[100:140]:
+            ctx.kplog_append_points(fr)
+        log = search_log[40:70] + search_log[100:140]
+        assert ctx.kplog_size() == len(log) == 70
+        d, s = ctx.kplog_place_search(69, 0, 68, **p)
+        assert ctx.kplog_described() == 40  # the survivors kept their descriptors, the store was not made anew
+        desc = [host_descriptor(L, fr, **p) for fr in log]
+        assert ctx.kplog_descriptors(0, 69, **p).tobytes() == np.stack(desc).tobytes()
+        table = [L.place_distance(desc[69], desc[c], **p) for c in range(69)]
+        want_d, want_s = np.array([t[0] for t in table], np.float32), np.array([t[1] for t in table], np.int32)
+        assert d.tobytes() == want_d.tobytes(), np.flatnonzero(d != want_d)[:8]
+        assert np.array_equal(s, want_s), np.flatnonzero(s != want_s)[:8]
+        assert len(set(want_d.tolist())) > 10  # (the table is no constant)
+    finally:
+        ctx.close()
 
 
 def test_search_cases_are_what_they_are_meant_to_be(L, search_ctx, search_expected):

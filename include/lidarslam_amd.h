@@ -1170,6 +1170,74 @@ int lsa_device_grid_save_pcd(lsa_device_grid* g, const char* path, int format, i
 int lsa_pcd_io_times(const lsa_ctx* ctx, double out[8]);
 
 /* ------------------------------------------------------------------------- */
+/* The dense point-cloud map: registered frames voxel-hashed on the device (lsa_dense_map.hip).  The keypoint
+ * maps above are the ICP's target; this is the point cloud of the place, one LidarPoint per voxel of `leaf` metres, built
+ * from whole registered frames without any of them leaving the device.  The host statement it is held to byte for byte is
+ * DenseMapHost (lidarslam_amd/_dense_map.py):
+ * - a point takes no part, and is counted in `skipped`, when a coordinate is not finite or an index i_a = floor((double)p_a /
+ *   (double)leaf) lies outside [-2^20, 2^20); key = ((iz + 2^20) << 42) | ((iy + 2^20) << 21) | (ix + 2^20), ascending key is
+ *   z-major order; -0.0 falls into voxel 0, -0.125 into voxel -1;
+ * - within one call a voxel's winner is its point of largest intensity (compared by lsa_wave.h's ordered code: a NaN loses to
+ *   every number, -0.0 to +0.0), ties to the smallest index of the call; n_f = the call's points in the voxel;
+ * - a new voxel: point = the winner's 32 bytes, count = n_f, frames = 1, first_frame = last_frame = frame; an existing one:
+ *   count += n_f, frames += 1 unless last_frame == frame, last_frame = frame, and the point is replaced only when the winner's
+ *   intensity is strictly greater (the earlier frame keeps ties).
+ * `frame` is an ordinal that must not decrease from one call to the next (LSA_E_ARG).  Nothing depends on the order in which
+ * the points of one call arrive.
+ * - lsa_dense_map_set: "MaxBytes" (of the table; default 16 GiB, 0 = no limit), "InitialCapacity" (slots of the table the
+ *   next insertion into a map without one makes; rounded up to a power of two), "ProbeStress" (a TEST KNOB: every key's home
+ *   slot is 0; only on an empty map).  lsa_dense_map_get_param also answers "LeafSize", "Capacity", "Rehashes", "ExportSeconds".
+ * - _insert_points: world points of the caller's (the table alone).  _insert_frame: the context's current frame moved as
+ *   lsa_transform_frame_at moves it, fused with the insertion: equal, byte for byte, to _insert_points of that call's
+ *   download; nothing is waited for, and the frame's device buffer is held by an event until the insertion has read it.
+ * - Growth: before an insertion the table is made large enough for (upper bound of occupied slots) + n <= capacity / 2, by a
+ *   rehash into a table of twice the size on the same stream; the old one is freed by lsa_collect_garbage.  When that table
+ *   would exceed "MaxBytes" (or cannot be allocated) the WHOLE insertion is refused with LSA_E_CAPACITY, lsa_last_error says
+ *   why and the map is untouched: never a partial frame, never a silently dropped point.
+ * - _size (voxels), _skipped, _get and _save_pcd wait for the insertions in flight.  _get returns the number of voxels with
+ *   frames >= min_frames and writes at most `capacity` of them in ascending key order (pts or voxels may be NULL); _save_pcd
+ *   writes the same points, returns their number, 0 and no file for none.  LSA_E_STATE when a probe sequence ran through
+ *   the whole table (it is bounded by the capacity; cannot happen at load <= 1/2). */
+typedef struct lsa_dense_voxel_t
+{
+  uint64_t key;
+  uint32_t count;       /* points that fell into the voxel */
+  uint32_t frames;      /* frame ordinals that touched it */
+  int32_t first_frame;
+  int32_t last_frame;
+} lsa_dense_voxel_t;
+typedef struct lsa_dense_map lsa_dense_map;
+int lsa_dense_map_create(lsa_ctx* ctx, double leaf, lsa_dense_map** out);
+void lsa_dense_map_destroy(lsa_dense_map* dm); /* before lsa_ctx_destroy of its context */
+int lsa_dense_map_set(lsa_dense_map* dm, const char* name, double value);
+double lsa_dense_map_get_param(lsa_dense_map* dm, const char* name);
+int lsa_dense_map_insert_points(lsa_dense_map* dm, const lsa_point_t* pts, int n, int frame);
+int lsa_dense_map_insert_frame(lsa_dense_map* dm, int interpolate, const double H0[16], const double H1[16], double t0, double t1, double time_offset, int frame);
+int lsa_dense_map_reserve(lsa_dense_map* dm, long long n); /* room for n more points now, as an insertion of n would make it: LSA_E_CAPACITY as there */
+int lsa_dense_map_size(lsa_dense_map* dm);
+long long lsa_dense_map_skipped(lsa_dense_map* dm);
+long long lsa_dense_map_bytes(const lsa_dense_map* dm);
+int lsa_dense_map_get(lsa_dense_map* dm, int min_frames, lsa_point_t* pts, lsa_dense_voxel_t* voxels, int capacity);
+int lsa_dense_map_clear(lsa_dense_map* dm);
+int lsa_dense_map_save_pcd(lsa_dense_map* dm, const char* path, int format, int min_frames);
+/* The pipeline's dense map (lsa_slam_set_param "DenseMap": 0 off, the default, under which nothing whatever changes; 1 every
+ * registered frame; 2 keyframes only; "DenseMapLeafSize", default 0.1; "DenseMapMaxBytes"; read-only "DenseMapVoxels",
+ * "DenseMapBytes", "DenseMapSkipped", "DenseMapRefusedFrames", "DenseMapClears").  At the end of AddFrame(s) the frame or frames of the
+ * call are inserted under the poses lsa_slam_get_registered_frame would use, every device frame of one call with the same
+ * ordinal, the count of inserted calls; room for all the device frames of a call is made before the first goes in, so a call
+ * is inserted whole or refused whole (LSA_E_CAPACITY): a refused one counts in "DenseMapRefusedFrames", leaves its reason in
+ * lsa_slam_last_error and does not fail the frame.  Also read-only: "DenseMapCapacity" (slots), "DenseMapFrames", "DenseMapRehashes",
+ * "DenseMapExportSeconds".  The map is cleared by Reset, ClearMaps and everything that applies a corrected
+ * trajectory (lsa_slam_set_trajectory_and_rebuild_maps; the pose-graph calls and lsa_slam_close_loops with `apply`): its
+ * points were placed under the old poses and raw frames are not logged, so a stale map must not pass for a corrected one
+ * ("DenseMapClears" counts, the first one warns on stderr), also while "DenseMap" is 0 for the moment.  The four calls wait for the insertions in flight and refuse
+ * with LSA_E_STATE while "DenseMap" is 0. */
+int lsa_slam_dense_map_size(lsa_slam* s);
+int lsa_slam_get_dense_map(lsa_slam* s, int min_frames, lsa_point_t* pts, lsa_dense_voxel_t* voxels, int capacity);
+int lsa_slam_save_dense_map_pcd(lsa_slam* s, const char* path, int format, int min_frames);
+int lsa_slam_clear_dense_map(lsa_slam* s);
+
+/* ------------------------------------------------------------------------- */
 /* The keypoint log (Slam::LogKeypoints, slam_lib/src/Slam.cxx:1225-1255) in the memory of the device, and its replay under
  * a corrected trajectory (the part of Slam::RunPoseGraphOptimization that comes after the optimizer, Slam.cxx:416-475).
  * A frame of the log is the three RAW keypoint sets (BASE coordinates, not undistorted) of one logged pose.  Storage:

@@ -45,6 +45,7 @@ from ._native import (  # noqa: F401
     synth_pose,
 )
 from ._context import *  # noqa: F401,F403
+from ._dense_map import *  # noqa: F401,F403
 from ._grids import *  # noqa: F401,F403
 from ._pcd import *  # noqa: F401,F403
 from ._place import *  # noqa: F401,F403

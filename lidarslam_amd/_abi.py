@@ -273,6 +273,24 @@ SIGNATURES = {
     "lsa_device_grid_add_pcd": (i32, [vp, s, i32, f64, i32]),
     "lsa_device_grid_save_pcd": (i32, [vp, s, i32, i32]),
     "lsa_pcd_io_times": (i32, [vp, vp]),
+    # ---- the dense point-cloud map
+    "lsa_dense_map_create": (i32, [vp, f64, P(vp)]),
+    "lsa_dense_map_destroy": (None, [vp]),
+    "lsa_dense_map_set": (i32, [vp, s, f64]),
+    "lsa_dense_map_get_param": (f64, [vp, s]),
+    "lsa_dense_map_insert_points": (i32, [vp, vp, i32, i32]),
+    "lsa_dense_map_insert_frame": (i32, [vp, i32, vp, vp, f64, f64, f64, i32]),
+    "lsa_dense_map_reserve": (i32, [vp, i64]),
+    "lsa_dense_map_size": (i32, [vp]),
+    "lsa_dense_map_skipped": (i64, [vp]),
+    "lsa_dense_map_bytes": (i64, [vp]),
+    "lsa_dense_map_get": (i32, [vp, i32, vp, vp, i32]),
+    "lsa_dense_map_clear": (i32, [vp]),
+    "lsa_dense_map_save_pcd": (i32, [vp, s, i32, i32]),
+    "lsa_slam_dense_map_size": (i32, [vp]),
+    "lsa_slam_get_dense_map": (i32, [vp, i32, vp, vp, i32]),
+    "lsa_slam_save_dense_map_pcd": (i32, [vp, s, i32, i32]),
+    "lsa_slam_clear_dense_map": (i32, [vp]),
     # ---- the keypoint log and its descriptor store
     "lsa_kplog_describe": (i32, [vp, vp, i32, i32]),
     "lsa_kplog_descriptors": (i32, [vp, i32, i32, vp]),

@@ -305,6 +305,23 @@ int lsa_slam_map_io_counts(const lsa_slam* s, int counts[3])
   return LSA_OK;
 }
 
+// ---- the dense point-cloud map (lsa_slam_dense.cpp) ----
+int lsa_slam_dense_map_size(lsa_slam* s) { return s ? s->core.DenseMapSize() : LSA_E_ARG; }
+
+int lsa_slam_get_dense_map(lsa_slam* s, int min_frames, lsa_point_t* pts, lsa_dense_voxel_t* voxels, int capacity)
+{
+  if (!s) return LSA_E_ARG;
+  return s->core.GetDenseMap(min_frames, pts, voxels, capacity);
+}
+
+int lsa_slam_save_dense_map_pcd(lsa_slam* s, const char* path, int format, int min_frames)
+{
+  if (!s || !path) return LSA_E_ARG;
+  return s->core.SaveDenseMapToPCD(path, format, min_frames);
+}
+
+int lsa_slam_clear_dense_map(lsa_slam* s) { return s ? s->core.ClearDenseMap() : LSA_E_ARG; }
+
 // ---- a corrected trajectory brought back: what Slam::RunPoseGraphOptimization does after its optimizer (Slam.cxx:404-477) ----
 int lsa_slam_set_trajectory_and_rebuild_maps(lsa_slam* s, const double* poses17, int n)
 {

@@ -59,6 +59,7 @@ SlamCore::~SlamCore()
   if (LoopCtx) lsa_ctx_destroy(LoopCtx);
   for (auto* g : DevMaps)
     if (g) lsa_device_grid_destroy(g);
+  if (Dense) lsa_dense_map_destroy(Dense);
   if (Ctx) lsa_ctx_destroy(Ctx);
 }
 
@@ -82,6 +83,7 @@ void SlamCore::Reset(bool resetLog)
   for (int k = 0; k < 3; ++k) LocalMaps[k]->Reset();
   for (auto* g : DevMaps)
     if (g) lsa_device_grid_reset(g, nullptr);
+  DropDenseMap("Reset or an applied trajectory");
   KfLastPose = Pose::Identity();
   KfCounter = 0;
   Tworld = PreviousTworld = Trelative = Pose::Identity();
@@ -368,6 +370,7 @@ int SlamCore::ProcessCurrentFrame(uint64_t stampUs)
     if (rc < 0) return rc;
   }
   if (TimeWindowDuration > 0) CheckMotionLimits();
+  const int keyframesBefore = KfCounter;
   if (MapUpdate == MappingMode::ADD_KPTS_TO_FIXED_MAP || MapUpdate == MappingMode::UPDATE)
   {
     Tick t;
@@ -378,6 +381,12 @@ int SlamCore::ProcessCurrentFrame(uint64_t stampUs)
   // the words the next frame's localization reduces its keypoints' boxes into, armed while the device has nothing to do
   if (LocalizationStartFused && DeviceMapsInUse() && MapUpdate != MappingMode::NONE) LSA_TRY(lsa_arm_localization_boxes(Ctx));
   LogCurrentFrameState(CurrentTime);
+  // Tworld and the motion within the frame are final: the registered frame goes into the dense map (off: nothing)
+  if (DenseMapMode != 0)
+  {
+    rc = InsertDenseFrame(KfCounter != keyframesBefore);
+    if (rc < 0) return rc;
+  }
   // the next frame's first jobs for the look-ahead thread (the sub-maps under the predicted pose, the ego-motion targets) come
   // within a fraction of a millisecond when the caller replays: the thread is awake for them
   if (WorkerPrewake && DeviceMapsInUse()) AheadWorker.Expect(300e-6);

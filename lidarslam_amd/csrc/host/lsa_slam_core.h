@@ -9,7 +9,8 @@
 //
 // One class, one unit per job: lsa_slam_core.cpp (construction, the frame path, the look-ahead, the getters),
 // lsa_slam_icp.cpp (the two registrations; their loop is lsa_slam_icp_loop.h), lsa_slam_maps.cpp (sub-maps, speculation,
-// insertion, load / save), lsa_slam_log.cpp (the keypoint log and the calls on it), lsa_slam_params.cpp (parameters by name).
+// insertion, load / save), lsa_slam_log.cpp (the keypoint log and the calls on it), lsa_slam_dense.cpp (the dense point-cloud
+// map), lsa_slam_params.cpp (parameters by name).
 #pragma once
 #include <array>
 #include <atomic>
@@ -83,6 +84,7 @@ public:
     for (auto& m : LocalMaps) m->Reset();
     for (auto* g : DevMaps)
       if (g) lsa_device_grid_reset(g, nullptr);
+    DropDenseMap("ClearMaps");
   }
   // Points put into the map of one keypoint type: RollingGrid::Add(pts, fixed, time) with its default roll = true.  What
   // the map loader sits on; waits for the map workers and drops what the look-ahead had prepared from the maps as they were.
@@ -264,6 +266,20 @@ public:
   int GetMap(int k, bool clean, std::vector<lsa_point_t>& out);
   int GetTargetSubMap(int k, std::vector<lsa_point_t>& out);
 
+  // ---- the dense point-cloud map (lsa_slam_dense.cpp; lsa_dense_map.hip) ----
+  // "DenseMap": 0 off (nothing whatever changes), 1 every registered frame, 2 keyframes only.  The frame or frames of an
+  // AddFrame(s) call go into a voxel hash table on the device at its end, under the poses GetRegisteredFrame would use, all
+  // with one ordinal: the count of inserted calls.  Cleared by Reset, ClearMaps and every applied trajectory (the points
+  // were placed under the old poses).  The four calls wait for the insertions in flight and refuse while the map is off.
+  int DenseMapMode = 0;
+  double DenseMapLeafSize = 0.1;
+  double DenseMapMaxBytes = 16. * 1024. * 1024. * 1024.;  // of the table; 0: no limit
+  unsigned DenseFrames = 0, DenseRefused = 0, DenseClears = 0;
+  int DenseMapSize();
+  int GetDenseMap(int minFrames, lsa_point_t* pts, lsa_dense_voxel_t* voxels, int capacity);
+  int SaveDenseMapToPCD(const std::string& path, int format, int minFrames);
+  int ClearDenseMap();
+
   // ---- state ----
   Pose Tworld, PreviousTworld, Trelative;
   RegistrationError LocalizationUncertainty;
@@ -402,6 +418,13 @@ private:
   lsa_ctx* LoopCtx = nullptr;
   lsa_device_grid* LoopMaps[3] = {nullptr, nullptr, nullptr};
   int EnsureLoopClosureScratch();
+
+  // ---- the dense map (lsa_slam_dense.cpp) ----
+  lsa_dense_map* Dense = nullptr;  // made by the first insertion
+  bool DenseWarned = false;
+  int InsertDenseFrame(bool keyframe);
+  void DropDenseMap(const char* why);  // why == nullptr: the caller asked for it, nothing to warn about
+  int DenseReady(const char* who);
 
   // ---- diagnostics ----
   double DbgAcc[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // (LSA_STAGE_DEBUG=1: seconds outside the stage timers, printed when the object goes)

@@ -1,0 +1,135 @@
+// lsa_slam_dense.cpp -- see lsa_slam_core.h: the pipeline's dense point-cloud map (lsa_dense_map.hip).  The
+// registered frame goes into the table at the end of AddFrame without leaving the device; what moves the poses under the
+// points that are already in it clears it.
+#include "lsa_slam_internal.h"
+#include <cstdio>
+
+namespace lsa
+{
+namespace host
+{
+// The frame or frames of the call under exactly the poses GetRegisteredFrame uses, fused with the insertion, on the
+// look-ahead stream; nothing is waited for.  A refused insertion (the table would outgrow "DenseMapMaxBytes") is counted
+// and reported, and does not fail the frame.
+int SlamCore::InsertDenseFrame(bool keyframe)
+{
+  if (DenseMapMode == 2 && !keyframe) return LSA_OK;
+  if (!Dense)
+  {
+    LSA_TRY(lsa_dense_map_create(Ctx, DenseMapLeafSize, &Dense));
+    LSA_TRY(lsa_dense_map_set(Dense, "MaxBytes", DenseMapMaxBytes));
+  }
+  const int ordinal = static_cast<int>(DenseFrames);
+  bool inserted = false, refused = false;
+  auto insert = [&](const Pose& offset, double timeOffset) -> int {
+    int rc;
+    if (Undistortion)
+    {
+      const Pose H0 = (Tworld * Motion.GetH0()) * offset;
+      const Pose H1 = (Tworld * Motion.GetH1()) * offset;
+      rc = lsa_dense_map_insert_frame(Dense, 1, H0.m, H1.m, Motion.Time0, Motion.Time1, timeOffset, ordinal);
+    }
+    else
+    {
+      const Pose tf = Tworld * offset;
+      rc = lsa_dense_map_insert_frame(Dense, 0, tf.m, nullptr, 0., 0., timeOffset, ordinal);
+    }
+    if (rc == LSA_E_CAPACITY)
+    {
+      refused = true;
+      LastError = std::string("dense map: frame not inserted: ") + lsa_last_error(Ctx);
+      return LSA_OK;
+    }
+    if (rc < 0) return Fail(rc, "lsa_dense_map_insert_frame");
+    inserted = true;
+    return LSA_OK;
+  };
+  if (!CurrentFrames.empty())
+  {
+    // the call is inserted whole or not at all: room for all its device frames is made before the first of them goes in
+    long long total = 0;
+    for (const HeldFrame& f : CurrentFrames) total += f.n;
+    if (const int rc = lsa_dense_map_reserve(Dense, total); rc == LSA_E_CAPACITY)
+    {
+      DenseRefused++;
+      LastError = std::string("dense map: frames not inserted: ") + lsa_last_error(Ctx);
+      return LSA_OK;
+    }
+    else if (rc < 0) return Fail(rc, "lsa_dense_map_reserve");
+    // AggregateFrames(CurrentFrames, true): every device frame with its own offset and time shift, one ordinal for the call
+    for (const HeldFrame& f : CurrentFrames)
+    {
+      LSA_TRY(lsa_frame_store_use(Ctx, f.slot));
+      if (const int rc = insert(GetBaseToLidarOffset(f.device), f.timeOffset); rc < 0) return rc;
+    }
+  }
+  else if (lsa_frame_size(Ctx) > 0)
+  {
+    if (const int rc = insert(BaseToLidarOffset, 0.); rc < 0) return rc;
+  }
+  if (refused) DenseRefused++;
+  if (inserted) DenseFrames++;
+  return LSA_OK;
+}
+
+// Reset, ClearMaps, a corrected trajectory: the points in the map were placed under poses that no longer hold -- also while
+// "DenseMap" is 0 for the moment: a map made before must not come back stale when it is switched on again
+void SlamCore::DropDenseMap(const char* why)
+{
+  if (!Dense) return;
+  (void)lsa_dense_map_clear(Dense);
+  DenseFrames = 0;
+  DenseClears++;
+  if (why && !DenseWarned)
+  {
+    DenseWarned = true;
+    std::fprintf(stderr, "lidarslam_amd: the dense map was cleared by %s: its points were placed under the poses of before, and raw frames are not logged to place them again (said once)\n", why);
+  }
+}
+
+int SlamCore::DenseReady(const char* who)
+{
+  if (!Ctx) return LSA_E_NO_DEVICE;
+  if (DenseMapMode == 0)
+  {
+    LastError = std::string(who) + ": the dense map is off (set \"DenseMap\" to 1 or 2 before the frames)";
+    return LSA_E_STATE;
+  }
+  WaitMaps();
+  return LSA_OK;
+}
+
+int SlamCore::DenseMapSize()
+{
+  if (const int rc = DenseReady("DenseMapSize"); rc < 0) return rc;
+  if (!Dense) return 0;
+  const int n = lsa_dense_map_size(Dense);
+  return n < 0 ? Fail(n, "lsa_dense_map_size") : n;
+}
+
+int SlamCore::GetDenseMap(int minFrames, lsa_point_t* pts, lsa_dense_voxel_t* voxels, int capacity)
+{
+  if (const int rc = DenseReady("GetDenseMap"); rc < 0) return rc;
+  if (capacity < 0) { LastError = "GetDenseMap: bad argument"; return LSA_E_ARG; }
+  if (!Dense) return 0;
+  const int n = lsa_dense_map_get(Dense, minFrames, pts, voxels, capacity);
+  return n < 0 ? Fail(n, "lsa_dense_map_get") : n;
+}
+
+int SlamCore::SaveDenseMapToPCD(const std::string& path, int format, int minFrames)
+{
+  if (const int rc = DenseReady("SaveDenseMapToPCD"); rc < 0) return rc;
+  if (!Dense) return 0;  // an empty cloud is not saved
+  const int n = lsa_dense_map_save_pcd(Dense, path.c_str(), format, minFrames);
+  return n < 0 ? Fail(n, "lsa_dense_map_save_pcd") : n;
+}
+
+int SlamCore::ClearDenseMap()
+{
+  if (const int rc = DenseReady("ClearDenseMap"); rc < 0) return rc;
+  DropDenseMap(nullptr);
+  return LSA_OK;
+}
+
+}  // namespace host
+}  // namespace lsa

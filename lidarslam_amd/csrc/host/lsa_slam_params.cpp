@@ -133,6 +133,27 @@ int SlamCore::SetParamValue(const std::string& name, double v)
   if (name == "VoxelGridMinFramesPerVoxel") { for (int k = 0; k < 3; ++k) { LocalMaps[k]->SetMinFramesPerVoxel(static_cast<unsigned>(v)); dev(k, "MinFramesPerVoxel", v); } return LSA_OK; }
   if (name == "VoxelGridDecayingThreshold") { for (int k = 0; k < 3; ++k) { LocalMaps[k]->SetDecayingThreshold(v); dev(k, "DecayingThreshold", v); } return LSA_OK; }
   if (name == "VoxelGridSamplingMode") { for (int k = 0; k < 3; ++k) { LocalMaps[k]->SetSampling(static_cast<SamplingMode>(static_cast<int>(v))); dev(k, "Sampling", v); } return LSA_OK; }
+  if (name == "DenseMap")
+  {
+    if (!(v == 0. || v == 1. || v == 2.)) { LastError = "DenseMap: 0 off, 1 every registered frame, 2 keyframes only"; return LSA_E_ARG; }
+    DenseMapMode = static_cast<int>(v);
+    return LSA_OK;
+  }
+  if (name == "DenseMapLeafSize")
+  {
+    if (!(v > 0.) || !(v < 1e9)) { LastError = "DenseMapLeafSize: a positive length"; return LSA_E_ARG; }
+    // the voxels of a map made under another leaf size mean nothing under this one: the next insertion makes a new map
+    if (Dense && v != DenseMapLeafSize) { lsa_dense_map_destroy(Dense); Dense = nullptr; DenseFrames = 0; }
+    DenseMapLeafSize = v;
+    return LSA_OK;
+  }
+  if (name == "DenseMapMaxBytes")
+  {
+    if (!(v >= 0.)) { LastError = "DenseMapMaxBytes: >= 0 (0: no limit)"; return LSA_E_ARG; }
+    DenseMapMaxBytes = v;
+    if (Dense) lsa_dense_map_set(Dense, "MaxBytes", v);
+    return LSA_OK;
+  }
   if (name == "OrderedMaps")
   {
     // both homes of the maps: the host grids, and the device grids (which put the points they hold back in, in the order
@@ -202,6 +223,19 @@ int SlamCore::GetParam(const std::string& name, double* v) const
   if (name == "AccelerationLimitAngular") { *v = AccelerationLimits[1]; return LSA_OK; }
   if (name == "ComplyMotionLimits") { *v = ComplyMotionLimits ? 1. : 0.; return LSA_OK; }
   if (name == "Latency") { *v = Latency; return LSA_OK; }
+  if (name == "DenseMap") { *v = DenseMapMode; return LSA_OK; }
+  if (name == "DenseMapLeafSize") { *v = DenseMapLeafSize; return LSA_OK; }
+  if (name == "DenseMapMaxBytes") { *v = DenseMapMaxBytes; return LSA_OK; }
+  if (name == "DenseMapCapacity") { *v = Dense ? lsa_dense_map_get_param(Dense, "Capacity") : 0.; return LSA_OK; }
+  // (the two that count on the device wait for the insertions in flight)
+  if (name == "DenseMapVoxels") { *v = Dense ? std::max(lsa_dense_map_size(Dense), 0) : 0; return LSA_OK; }
+  if (name == "DenseMapSkipped") { *v = Dense ? static_cast<double>(std::max(lsa_dense_map_skipped(Dense), 0ll)) : 0.; return LSA_OK; }
+  if (name == "DenseMapBytes") { *v = Dense ? static_cast<double>(lsa_dense_map_bytes(Dense)) : 0.; return LSA_OK; }
+  if (name == "DenseMapRefusedFrames") { *v = DenseRefused; return LSA_OK; }
+  if (name == "DenseMapClears") { *v = DenseClears; return LSA_OK; }
+  if (name == "DenseMapFrames") { *v = DenseFrames; return LSA_OK; }
+  if (name == "DenseMapRehashes") { *v = Dense ? lsa_dense_map_get_param(Dense, "Rehashes") : 0.; return LSA_OK; }
+  if (name == "DenseMapExportSeconds") { *v = Dense ? lsa_dense_map_get_param(Dense, "ExportSeconds") : 0.; return LSA_OK; }
   return LSA_E_ARG;
 }
 

@@ -13,6 +13,7 @@
 //   keypoint log AoS lsa_point_t in chunks of 32 MiB, a frame's three types one after the other (lsa_kplog.hip; only with logging on)
 //   descriptors  a ring of slots of rings * sectors + sectors floats, one per logged frame (lsa_place.hip; only once asked for)
 //   pose graph   poses, edges, per-edge block records, block rows D / L / U, the cyclic reduction's levels, PCG vectors (lsa_pose_graph.hip; only once asked for)
+//   dense map    a voxel hash table of 64-byte slots, owned by an lsa_dense_map of the context (lsa_dense_map.hip; only with "DenseMap" on)
 #pragma once
 #include <hip/hip_runtime.h>
 #include <algorithm>
@@ -349,6 +350,10 @@ struct lsa_ctx
   bool map_describe_cull = true;                // lsa_debug_set "map_describe_cull": slices out of a viewpoint's reach are passed over
   // the pose-graph solver's buffers (lsa_pose_graph.hip): made by the first call, grown through the graveyard
   lsa::PgoBuffers* pgo = nullptr;
+  // the dense map's fused insertion (lsa_dense_map.hip) reads a frame's device buffer on the look-ahead stream: ev_dense is
+  // recorded behind the last of them, and whoever writes a frame buffer next waits for it on its stream (frame_writer_guard)
+  hipEvent_t ev_dense = nullptr;     // made with the context's first dense map
+  bool dense_frame_pending = false;  // a fused insertion has been enqueued (never: nothing is waited for)
 
   // profiling
   bool profiling = false;
@@ -403,6 +408,8 @@ inline void retire_host(lsa_ctx* ctx, void* p)
   std::lock_guard<std::mutex> l(ctx->grave_mutex);
   ctx->grave_host.push_back(p);
 }
+// before a frame buffer (the context's own, an inbox slot, a frame-store slot) is written on `st`
+inline hipError_t frame_writer_guard(lsa_ctx* ctx, hipStream_t st) { return ctx->dense_frame_pending ? hipStreamWaitEvent(st, ctx->ev_dense, 0) : hipSuccess; }
 // Room for `count` elements in a device buffer whose contents need not survive, and in its pinned twin where there is one
 // (pinned != nullptr); what is outgrown goes to the graveyard.  The new capacity is count and half as much again but at
 // least `floor`, or, with exact, count.

@@ -274,6 +274,7 @@ void lsa_ctx_destroy(lsa_ctx* ctx)
   for (int k = 0; k < 3; ++k)
     if (ctx->ev_map_ahead[k]) (void)hipEventDestroy(ctx->ev_map_ahead[k]);
   if (ctx->ev_kp_ready) (void)hipEventDestroy(ctx->ev_kp_ready);
+  if (ctx->ev_dense) (void)hipEventDestroy(ctx->ev_dense);
   if (ctx->prefetch_stream) (void)hipStreamDestroy(ctx->prefetch_stream);
   for (int i = 0; i < 4; ++i) fr(ctx->score[i]);
   fr(ctx->valid); fr(ctx->label); fr(ctx->ring_counts);

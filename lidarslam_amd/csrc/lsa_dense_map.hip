@@ -1,0 +1,651 @@
+// lsa_dense_map.hip -- the dense point-cloud map: registered frames voxel-hashed on the device (the host
+// statement the table is held to, byte for byte, is DenseMapHost in lidarslam_amd/_dense_map.py).
+//
+// An open-addressing hash table in HBM, capacity a power of two, one 64-byte slot per voxel:
+//   key   u64   0 = empty, otherwise bit 63 | ((iz + 2^20) << 42) | ((iy + 2^20) << 21) | (ix + 2^20); claimed with a 64-bit CAS
+//   cand  u64   the call's candidate word (ordered intensity << 32) | ~index, 0 between two calls
+//   point 32 B  the voxel's LidarPoint
+//   count, frames, first_frame, last_frame
+// An insertion's cost is the frame's size, not the map's.  Two launches, one thread per point:
+//   k_dense_claim  finds or claims the point's slot, adds 1 to its count, atomicMax'es the candidate word, notes the slot
+//   k_dense_apply  the thread whose index the candidate word names applies the new / existing voxel rule and disarms the word
+// The kernel boundary is the only synchronisation: no workgroup waits for another, no flag is spun on, and a probe sequence
+// is bounded by the capacity (a thread that exhausts it raises the map's error word and returns).  Every rule is
+// independent of the order in which the points of a call arrive, which is what lets atomics give the host's bytes.
+// The fused form (lsa_dense_map_insert_frame) moves the context's frame to the world inside both kernels with
+// frame_point_to_world, k_transform_out's own arithmetic: a world point only reaches memory when it wins its voxel.
+// Growth: the host keeps (upper bound of occupied slots) + n <= capacity / 2 from the last count the device left in
+// coherent host memory plus the points inserted since -- never waited for --, and k_dense_rehash moves the slots into a
+// table of twice the size on the same stream; the old table goes to the context's graveyard.
+// Export (not on the frame path): lsa_compact.h's stable compaction of the slots that pass min_frames, rocprim's radix sort
+// by key, a gather.
+#include <cstring>
+#include <rocprim/device/device_radix_sort.hpp>
+#include <chrono>
+#include <cmath>
+#include <cstdint>
+#include <deque>
+#include <new>
+#include "lsa_compact.h"
+#include "lsa_ctx.h"
+#include "lsa_device_grid_io.h"
+#include "lsa_device_math.h"
+#include "lsa_wave.h"
+#include "host/lsa_pcd.h"
+
+namespace lsa
+{
+InterpConst make_interp_const(const double H0[16], const double H1[16], double t0, double t1);  // lsa_transform.hip
+}
+using namespace lsa;
+
+namespace
+{
+constexpr u64 kOccupied = 1ull << 63;
+constexpr double kIndexRange = 1048576.;  // 2^20: indices in [-2^20, 2^20)
+constexpr unsigned kMinCapacity = 64, kMaxCapacity = 1u << 30;
+constexpr size_t kDefaultMaxBytes = (size_t)16 << 30;
+
+struct alignas(64) Slot
+{
+  u64 key;
+  u64 cand;
+  float4 a, b;  // the LidarPoint: x y z w | time, intensity, laser / device / label
+  unsigned count, frames;
+  int first, last;
+};
+static_assert(sizeof(Slot) == 64, "a slot is one 64-byte record");
+
+struct Table
+{
+  Slot* slots;
+  unsigned mask;  // capacity - 1
+  int stress;     // "ProbeStress": every key's home slot is 0
+};
+// device words of a map: [0] occupied slots, [1] error (a probe sequence ran out), [2] points skipped
+enum { kStatOccupied = 0, kStatError = 1, kStatSkipped = 2, kStatWords = 4 };
+
+// the order-preserving code of an intensity: f2ou, and 0 -- below -inf -- for a NaN
+__device__ __forceinline__ unsigned intensity_code(float v) { return v == v ? f2ou(v) : 0u; }
+
+__device__ __forceinline__ bool voxel_key(const float4& a, double leaf, u64& key)
+{
+  if (!(__builtin_isfinite(a.x) && __builtin_isfinite(a.y) && __builtin_isfinite(a.z))) return false;
+  const double ix = __builtin_floor((double)a.x / leaf), iy = __builtin_floor((double)a.y / leaf), iz = __builtin_floor((double)a.z / leaf);
+  if (!(ix >= -kIndexRange && ix < kIndexRange && iy >= -kIndexRange && iy < kIndexRange && iz >= -kIndexRange && iz < kIndexRange)) return false;
+  key = ((u64)((long long)iz + 1048576ll) << 42) | ((u64)((long long)iy + 1048576ll) << 21) | (u64)((long long)ix + 1048576ll);
+  return true;
+}
+
+__device__ __forceinline__ unsigned home_slot(const Table& t, u64 key)
+{
+  if (t.stress) return 0u;
+  key ^= key >> 33; key *= 0xff51afd7ed558ccdull;
+  key ^= key >> 33; key *= 0xc4ceb9fe1a85ec53ull;
+  key ^= key >> 33;
+  return (unsigned)key & t.mask;
+}
+
+// the slot of `key`, claimed when the table does not hold it; -1 after capacity probes (the caller raises the error word)
+__device__ __forceinline__ int find_or_claim(const Table& t, u64 key, u64* __restrict__ stat)
+{
+  const u64 want = key | kOccupied;
+  unsigned s = home_slot(t, key);
+  for (unsigned probe = 0; probe <= t.mask; ++probe, s = (s + 1u) & t.mask)
+  {
+    u64* kp = &t.slots[s].key;
+    u64 cur = __hip_atomic_load(kp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (cur == 0ull)
+    {
+      cur = atomicCAS(kp, 0ull, want);
+      if (cur == 0ull)
+      {
+        atomicAdd(&stat[kStatOccupied], 1ull);
+        return (int)s;
+      }
+    }
+    if (cur == want) return (int)s;
+  }
+  return -1;
+}
+
+struct FrameMove
+{
+  int fused;        // 0: the points are world points already
+  int interpolate;
+  InterpConst c;
+  Rigid R;
+  double time_offset;
+};
+
+// launch 1: slot, count, candidate
+__global__ __launch_bounds__(256) void k_dense_claim(const float4* __restrict__ in, int n, const FrameMove m, double leaf, Table t, u64* __restrict__ stat,
+                                                     int* __restrict__ slot_of)
+{
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  float4 a = in[2 * (size_t)i];
+  float4 b = in[2 * (size_t)i + 1];
+  if (m.fused) frame_point_to_world(a, b, m.interpolate, m.c, m.R, m.time_offset);
+  u64 key = 0;
+  const bool ok = voxel_key(a, leaf, key);
+  const u64 skipping = __ballot(!ok);
+  if (!ok)
+  {
+    // one add a wavefront
+    if ((int)(threadIdx.x & 63) == __ffsll((long long)skipping) - 1) atomicAdd(&stat[kStatSkipped], (u64)__popcll(skipping));
+    slot_of[i] = -1;
+    return;
+  }
+  const int s = find_or_claim(t, key, stat);
+  slot_of[i] = s;
+  if (s < 0)
+  {
+    atomicOr(&stat[kStatError], 1ull);
+    return;
+  }
+  atomicAdd(&t.slots[s].count, 1u);
+  atomicMax(&t.slots[s].cand, ((u64)intensity_code(b.z) << 32) | (u64)(~(unsigned)i));
+}
+
+// launch 2: the winner of every voxel of the call applies the rule.  host_words: coherent host memory, [0] = serial << 32 |
+// occupied slots, written last, [1] error, [2] skipped -- by one thread, after launch 1 has left them final.
+__global__ __launch_bounds__(256) void k_dense_apply(const float4* __restrict__ in, int n, const FrameMove m, Table t, const int* __restrict__ slot_of, int frame,
+                                                     const u64* __restrict__ stat, u64* __restrict__ host_words, unsigned serial)
+{
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i == 0)
+  {
+    __hip_atomic_store(&host_words[1], stat[kStatError], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    __hip_atomic_store(&host_words[2], stat[kStatSkipped], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    __hip_atomic_store(&host_words[0], ((u64)serial << 32) | (stat[kStatOccupied] & 0xffffffffull), __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+  }
+  if (i >= n) return;
+  const int s = slot_of[i];
+  if (s < 0) return;
+  Slot& S = t.slots[s];
+  // (only this voxel's winner writes the word during this launch, and the 0 it writes names nobody: an index is never 2^32 - 1)
+  const u64 w = __hip_atomic_load(&S.cand, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  if ((unsigned)w != ~(unsigned)i) return;
+  float4 a = in[2 * (size_t)i];
+  float4 b = in[2 * (size_t)i + 1];
+  if (m.fused) frame_point_to_world(a, b, m.interpolate, m.c, m.R, m.time_offset);
+  if (S.frames == 0u)
+  {
+    S.a = a; S.b = b;
+    S.frames = 1u;
+    S.first = S.last = frame;
+  }
+  else
+  {
+    if (S.last != frame) { S.frames += 1u; S.last = frame; }
+    if ((unsigned)(w >> 32) > intensity_code(S.b.z)) { S.a = a; S.b = b; }  // strictly greater: the earlier frame keeps a tie
+  }
+  S.cand = 0ull;
+}
+
+// every occupied slot of the old table into the new one (zeroed); keys are unique, so a slot is only ever claimed from empty
+__global__ __launch_bounds__(256) void k_dense_rehash(const Slot* __restrict__ old, unsigned old_capacity, Table t, u64* __restrict__ stat)
+{
+  const unsigned i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= old_capacity) return;
+  const Slot o = old[i];
+  if (o.key == 0ull) return;
+  unsigned s = home_slot(t, o.key & ~kOccupied);
+  for (unsigned probe = 0; probe <= t.mask; ++probe, s = (s + 1u) & t.mask)
+  {
+    if (atomicCAS(&t.slots[s].key, 0ull, o.key) != 0ull) continue;
+    Slot& S = t.slots[s];
+    S.a = o.a; S.b = o.b;
+    S.count = o.count; S.frames = o.frames; S.first = o.first; S.last = o.last;
+    return;
+  }
+  atomicOr(&stat[kStatError], 1ull);
+}
+
+// ---- export -------------------------------------------------------------------------------------------------------------
+struct ExportPred
+{
+  const Slot* slots;
+  unsigned min_frames;
+  __device__ bool operator()(int i) const { return slots[i].key != 0ull && slots[i].frames >= min_frames; }
+};
+struct ExportEmit
+{
+  const Slot* slots;
+  u64* keys;
+  unsigned* index;
+  __device__ void operator()(int i, int pos) const
+  {
+    keys[pos] = slots[i].key & ~kOccupied;
+    index[pos] = (unsigned)i;
+  }
+};
+__global__ __launch_bounds__(256) void k_dense_gather(const Slot* __restrict__ slots, const u64* __restrict__ keys, const unsigned* __restrict__ index, int n,
+                                                      float4* __restrict__ pts, lsa_dense_voxel_t* __restrict__ voxels)
+{
+  const int j = blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= n) return;
+  const Slot& S = slots[index[j]];
+  pts[2 * (size_t)j] = S.a;
+  pts[2 * (size_t)j + 1] = S.b;
+  lsa_dense_voxel_t v;
+  v.key = keys[j];
+  v.count = S.count; v.frames = S.frames; v.first_frame = S.first; v.last_frame = S.last;
+  voxels[j] = v;
+}
+}  // namespace
+
+struct lsa_dense_map
+{
+  lsa_ctx* ctx = nullptr;
+  hipStream_t stream = nullptr;  // the context's look-ahead stream
+  double leaf = 0.1;
+  Slot* slots = nullptr;
+  unsigned capacity = 0;
+  unsigned initial_capacity = 1u << 16;
+  size_t max_bytes = kDefaultMaxBytes;
+  int stress = 0;
+  u64* stat = nullptr;        // device, kStatWords
+  u64* host_words = nullptr;  // coherent host memory, 4 words
+  int* slot_of = nullptr;     // [slot_cap] the slot of every point of the call in flight
+  int slot_cap = 0;
+  lsa_point_t* staged = nullptr;  // lsa_dense_map_insert_points: the caller's points on the device
+  int staged_cap = 0;
+  hipEvent_t ev_frame = nullptr;  // the context's stream up to the frame the fused insertion reads
+  // the host's bound of the occupied slots: the last count the device published plus the points inserted since
+  unsigned next_serial = 1, epoch = 1, seen_serial = 0;
+  unsigned known = 0;
+  std::deque<std::pair<unsigned, int>> pending;
+  long long pending_sum = 0;
+  int last_frame = INT32_MIN;
+  int rehashes = 0;
+  // export scratch, kept between exports
+  int* chunks = nullptr; int chunks_cap = 0;
+  int* totals = nullptr;  // device, 2 ints: the total and the compaction's aside slot
+  u64* keys[2] = {nullptr, nullptr}; unsigned* index[2] = {nullptr, nullptr}; int keys_cap = 0;
+  void* sort_tmp = nullptr; size_t sort_tmp_cap = 0;
+  lsa_point_t* out_pts = nullptr; lsa_dense_voxel_t* out_vox = nullptr; int out_cap = 0;
+  double export_seconds = 0.;
+};
+
+namespace
+{
+Table table_of(const lsa_dense_map* dm) { return Table{dm->slots, dm->capacity - 1u, dm->stress}; }
+
+long long occupied_bound(lsa_dense_map* dm)
+{
+  const u64 w = __atomic_load_n(&dm->host_words[0], __ATOMIC_ACQUIRE);
+  const unsigned ws = (unsigned)(w >> 32);
+  if (ws >= dm->epoch && ws > dm->seen_serial && ws < dm->next_serial)
+  {
+    dm->seen_serial = ws;
+    dm->known = (unsigned)w;
+    while (!dm->pending.empty() && dm->pending.front().first <= ws)
+    {
+      dm->pending_sum -= dm->pending.front().second;
+      dm->pending.pop_front();
+    }
+  }
+  return (long long)dm->known + dm->pending_sum;
+}
+
+// the table with room for n more points: (bound of occupied slots) + n <= capacity / 2, by rehashing into a larger one
+int make_room(lsa_dense_map* dm, long long n, const char* who)
+{
+  lsa_ctx* ctx = dm->ctx;
+  const long long need = occupied_bound(dm) + n;
+  unsigned cap = dm->capacity ? dm->capacity : dm->initial_capacity;
+  // (a first table of "InitialCapacity" slots is a wish, not a demand: under a "MaxBytes" below it the table starts smaller)
+  if (!dm->capacity && dm->max_bytes)
+    while (cap > kMinCapacity && (size_t)cap * sizeof(Slot) > dm->max_bytes) cap /= 2;
+  while ((long long)(cap / 2) < need)
+  {
+    if (cap >= kMaxCapacity) return ctx->fail(LSA_E_CAPACITY, std::string(who) + ": the table would need more than 2^30 slots");
+    cap *= 2;
+  }
+  if (cap == dm->capacity) return LSA_OK;
+  const size_t bytes = (size_t)cap * sizeof(Slot);
+  if (dm->max_bytes && bytes > dm->max_bytes)
+    return ctx->fail(LSA_E_CAPACITY, std::string(who) + ": a table of " + std::to_string(bytes) + " bytes for " + std::to_string(need) +
+                                         " voxels at most is over MaxBytes = " + std::to_string(dm->max_bytes) + "; nothing was inserted");
+  Slot* fresh = nullptr;
+  if (hipMalloc((void**)&fresh, bytes) != hipSuccess)
+  {
+    (void)hipGetLastError();
+    return ctx->fail(LSA_E_CAPACITY, std::string(who) + ": no device memory for a table of " + std::to_string(bytes) + " bytes; nothing was inserted");
+  }
+  if (const hipError_t e = hipMemsetAsync(fresh, 0, bytes, dm->stream); e != hipSuccess)
+  {
+    (void)hipFree(fresh);
+    return ctx->fail(LSA_E_HIP, std::string(who) + ": hipMemsetAsync: " + hipGetErrorString(e));
+  }
+  Slot* old = dm->slots;
+  const unsigned old_capacity = dm->capacity;
+  dm->slots = fresh;
+  dm->capacity = cap;
+  if (old)
+  {
+    ProfScope ps(ctx, "dense_rehash", (double)old_capacity * sizeof(Slot) * 2, dm->stream);
+    hipLaunchKernelGGL(k_dense_rehash, dim3((old_capacity + 255) / 256), dim3(256), 0, dm->stream, old, old_capacity, table_of(dm), dm->stat);
+    dm->rehashes++;
+    retire_dev(ctx, old);  // launches in flight keep it; freed by lsa_collect_garbage
+  }
+  return LSA_OK;
+}
+
+// the two launches over n points at `src` (device), in the world already or moved there by m
+int insert_device_points(lsa_dense_map* dm, const lsa_point_t* src, int n, const FrameMove& m, int frame, const char* who)
+{
+  lsa_ctx* ctx = dm->ctx;
+  int rc = make_room(dm, n, who);
+  if (rc) return rc;
+  rc = scratch_room(ctx, &dm->slot_of, (int**)nullptr, &dm->slot_cap, (size_t)n, 4096);
+  if (rc) return rc;
+  const unsigned serial = dm->next_serial++;
+  const float4* in = reinterpret_cast<const float4*>(src);
+  const dim3 grid((n + 255) / 256);
+  {
+    ProfScope ps(ctx, "dense_claim", (double)n * 56, dm->stream);  // 32 B read, 4 B slot index, 20 B of atomic words
+    hipLaunchKernelGGL(k_dense_claim, grid, dim3(256), 0, dm->stream, in, n, m, dm->leaf, table_of(dm), dm->stat, dm->slot_of);
+  }
+  {
+    ProfScope ps(ctx, "dense_apply", (double)n * 12, dm->stream);
+    hipLaunchKernelGGL(k_dense_apply, grid, dim3(256), 0, dm->stream, in, n, m, table_of(dm), dm->slot_of, frame, dm->stat, dm->host_words, serial);
+  }
+  dm->pending.emplace_back(serial, n);
+  dm->pending_sum += n;
+  dm->last_frame = frame;
+  return LSA_OK;
+}
+
+// waits for the insertions in flight; a probe sequence that ran out is reported here
+int settle(lsa_dense_map* dm, const char* who)
+{
+  lsa_ctx* ctx = dm->ctx;
+  LSA_HIP(ctx, hipSetDevice(ctx->device));
+  LSA_HIP(ctx, hipStreamSynchronize(dm->stream));
+  if (__atomic_load_n(&dm->host_words[1], __ATOMIC_ACQUIRE) != 0ull)
+    return ctx->fail(LSA_E_STATE, std::string(who) + ": a probe sequence ran through the whole table (the map is incomplete; lsa_dense_map_clear starts again)");
+  return LSA_OK;
+}
+
+// the voxels with frames >= min_frames in ascending key order, left in dm->out_pts / out_vox; returns their number
+int export_sorted(lsa_dense_map* dm, int min_frames, const char* who)
+{
+  lsa_ctx* ctx = dm->ctx;
+  int rc = settle(dm, who);
+  if (rc) return rc;
+  const int occupied = (int)occupied_bound(dm);  // exact: everything enqueued has been published
+  if (occupied <= 0 || !dm->slots) return 0;
+  const int nchunks = (int)((dm->capacity + 1023u) / 1024u);
+  rc = scratch_room(ctx, &dm->chunks, (int**)nullptr, &dm->chunks_cap, (size_t)nchunks, 64);
+  if (rc) return rc;
+  if (occupied > dm->keys_cap)
+  {
+    for (int b = 0; b < 2; ++b) { retire_dev(ctx, dm->keys[b]); retire_dev(ctx, dm->index[b]); dm->keys[b] = nullptr; dm->index[b] = nullptr; }
+    dm->keys_cap = 0;
+    const size_t want = (size_t)occupied + (size_t)occupied / 2;
+    for (int b = 0; b < 2; ++b)
+    {
+      LSA_HIP(ctx, hipMalloc((void**)&dm->keys[b], want * sizeof(u64)));
+      LSA_HIP(ctx, hipMalloc((void**)&dm->index[b], want * sizeof(unsigned)));
+    }
+    dm->keys_cap = (int)want;
+  }
+  const Slot* slots = dm->slots;
+  stable_compact(dm->stream, dm->chunks, dm->totals + 1, ExportPred{slots, (unsigned)std::max(min_frames, 0)}, ExportEmit{slots, dm->keys[0], dm->index[0]},
+                 (const int*)nullptr, (int)dm->capacity, dm->totals);
+  int kept = 0;
+  LSA_HIP(ctx, hipMemcpyAsync(&kept, dm->totals, sizeof(int), hipMemcpyDeviceToHost, dm->stream));
+  LSA_HIP(ctx, hipStreamSynchronize(dm->stream));
+  if (kept <= 0) return 0;
+  size_t tmp_bytes = 0;
+  LSA_HIP(ctx, rocprim::radix_sort_pairs(nullptr, tmp_bytes, dm->keys[0], dm->keys[1], dm->index[0], dm->index[1], (size_t)kept, 0u, 63u, dm->stream));
+  if (tmp_bytes > dm->sort_tmp_cap)
+  {
+    retire_dev(ctx, dm->sort_tmp);
+    dm->sort_tmp = nullptr;
+    dm->sort_tmp_cap = 0;
+    LSA_HIP(ctx, hipMalloc(&dm->sort_tmp, tmp_bytes));
+    dm->sort_tmp_cap = tmp_bytes;
+  }
+  LSA_HIP(ctx, rocprim::radix_sort_pairs(dm->sort_tmp, tmp_bytes, dm->keys[0], dm->keys[1], dm->index[0], dm->index[1], (size_t)kept, 0u, 63u, dm->stream));
+  if (kept > dm->out_cap)
+  {
+    retire_dev(ctx, dm->out_pts);
+    retire_dev(ctx, dm->out_vox);
+    dm->out_pts = nullptr; dm->out_vox = nullptr; dm->out_cap = 0;
+    const size_t want = (size_t)kept + (size_t)kept / 2;
+    LSA_HIP(ctx, hipMalloc((void**)&dm->out_pts, want * sizeof(lsa_point_t)));
+    LSA_HIP(ctx, hipMalloc((void**)&dm->out_vox, want * sizeof(lsa_dense_voxel_t)));
+    dm->out_cap = (int)want;
+  }
+  hipLaunchKernelGGL(k_dense_gather, dim3((kept + 255) / 256), dim3(256), 0, dm->stream, slots, dm->keys[1], dm->index[1], kept, reinterpret_cast<float4*>(dm->out_pts),
+                     dm->out_vox);
+  return kept;
+}
+
+double now_seconds() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+}  // namespace
+
+extern "C" {
+
+int lsa_dense_map_create(lsa_ctx* ctx, double leaf, lsa_dense_map** out)
+{
+  if (!ctx || !out) return ctx ? ctx->fail(LSA_E_ARG, "lsa_dense_map_create: bad argument") : LSA_E_ARG;
+  *out = nullptr;
+  if (!(leaf > 0.) || !std::isfinite(leaf)) return ctx->fail(LSA_E_ARG, "lsa_dense_map_create: the leaf size must be positive and finite");
+  LSA_HIP(ctx, hipSetDevice(ctx->device));
+  lsa_dense_map* dm = new lsa_dense_map;
+  dm->ctx = ctx;
+  dm->stream = ctx->prefetch_stream;  // beside the next frame's registration, with the rolling maps' kernels: no fourth stream
+  dm->leaf = leaf;
+  bool ok = hipMalloc((void**)&dm->stat, kStatWords * sizeof(u64)) == hipSuccess;
+  ok = ok && hipMemset(dm->stat, 0, kStatWords * sizeof(u64)) == hipSuccess;
+  ok = ok && hipMalloc((void**)&dm->totals, 2 * sizeof(int)) == hipSuccess;
+  ok = ok && hipHostMalloc((void**)&dm->host_words, 4 * sizeof(u64), hipHostMallocCoherent | hipHostMallocMapped) == hipSuccess;
+  ok = ok && hipEventCreateWithFlags(&dm->ev_frame, hipEventDisableTiming) == hipSuccess;
+  if (ok && !ctx->ev_dense) ok = hipEventCreateWithFlags(&ctx->ev_dense, hipEventDisableTiming) == hipSuccess;
+  if (!ok)
+  {
+    (void)hipGetLastError();
+    lsa_dense_map_destroy(dm);
+    return ctx->fail(LSA_E_HIP, "lsa_dense_map_create: allocation failed");
+  }
+  std::memset(dm->host_words, 0, 4 * sizeof(u64));
+  *out = dm;
+  return LSA_OK;
+}
+
+void lsa_dense_map_destroy(lsa_dense_map* dm)
+{
+  if (!dm) return;
+  (void)hipSetDevice(dm->ctx->device);
+  if (dm->stream) (void)hipStreamSynchronize(dm->stream);
+  auto fr = [](void* p) { if (p) (void)hipFree(p); };
+  fr(dm->slots); fr(dm->stat); fr(dm->slot_of); fr(dm->staged); fr(dm->chunks); fr(dm->totals);
+  for (int b = 0; b < 2; ++b) { fr(dm->keys[b]); fr(dm->index[b]); }
+  fr(dm->sort_tmp); fr(dm->out_pts); fr(dm->out_vox);
+  if (dm->host_words) (void)hipHostFree(dm->host_words);
+  if (dm->ev_frame) (void)hipEventDestroy(dm->ev_frame);
+  delete dm;
+}
+
+int lsa_dense_map_set(lsa_dense_map* dm, const char* name, double value)
+{
+  if (!dm || !name) return LSA_E_ARG;
+  lsa_ctx* ctx = dm->ctx;
+  const std::string n(name);
+  if (n == "MaxBytes")
+  {
+    if (!(value >= 0.)) return ctx->fail(LSA_E_ARG, "lsa_dense_map_set: MaxBytes >= 0 (0: no limit)");
+    dm->max_bytes = (size_t)value;
+    return LSA_OK;
+  }
+  if (n == "InitialCapacity")
+  {
+    if (!(value >= 1.) || value > (double)kMaxCapacity) return ctx->fail(LSA_E_ARG, "lsa_dense_map_set: InitialCapacity between 1 and 2^30 slots");
+    unsigned cap = kMinCapacity;
+    while ((double)cap < value) cap *= 2;
+    dm->initial_capacity = cap;  // of the table the next insertion into a map without one makes
+    return LSA_OK;
+  }
+  if (n == "ProbeStress")
+  {
+    // a TEST KNOB: every key's home slot is 0, so that probe sequences are as long as the table is full
+    if (dm->slots && ((value != 0.) != (dm->stress != 0)))
+    {
+      const int rc = settle(dm, "lsa_dense_map_set");
+      if (rc) return rc;
+      if (occupied_bound(dm) > 0) return ctx->fail(LSA_E_STATE, "lsa_dense_map_set: ProbeStress only on an empty map");
+    }
+    dm->stress = value != 0. ? 1 : 0;
+    return LSA_OK;
+  }
+  return ctx->fail(LSA_E_ARG, "lsa_dense_map_set: unknown parameter " + n);
+}
+
+double lsa_dense_map_get_param(lsa_dense_map* dm, const char* name)
+{
+  if (!dm || !name) return -1.;
+  const std::string n(name);
+  if (n == "LeafSize") return dm->leaf;
+  if (n == "MaxBytes") return (double)dm->max_bytes;
+  if (n == "InitialCapacity") return dm->initial_capacity;
+  if (n == "ProbeStress") return dm->stress;
+  if (n == "Capacity") return dm->capacity;
+  if (n == "Rehashes") return dm->rehashes;
+  if (n == "ExportSeconds") return dm->export_seconds;
+  return -1.;
+}
+
+int lsa_dense_map_insert_points(lsa_dense_map* dm, const lsa_point_t* pts, int n, int frame)
+{
+  if (!dm) return LSA_E_ARG;
+  lsa_ctx* ctx = dm->ctx;
+  if (n < 0 || (n > 0 && !pts)) return ctx->fail(LSA_E_ARG, "lsa_dense_map_insert_points: bad argument");
+  if (frame < dm->last_frame) return ctx->fail(LSA_E_ARG, "lsa_dense_map_insert_points: frame ordinals must not decrease");
+  if (n == 0) { dm->last_frame = frame; return LSA_OK; }
+  LSA_HIP(ctx, hipSetDevice(ctx->device));
+  int rc = make_room(dm, n, "lsa_dense_map_insert_points");  // a refusal comes before anything is touched
+  if (rc) return rc;
+  rc = scratch_room(ctx, &dm->staged, (lsa_point_t**)nullptr, &dm->staged_cap, (size_t)n, 4096);
+  if (rc) return rc;
+  LSA_HIP(ctx, hipMemcpyAsync(dm->staged, pts, (size_t)n * sizeof(lsa_point_t), hipMemcpyHostToDevice, dm->stream));
+  LSA_HIP(ctx, hipStreamSynchronize(dm->stream));  // pts may be pageable and reused by the caller
+  FrameMove m{};
+  return insert_device_points(dm, dm->staged, n, m, frame, "lsa_dense_map_insert_points");
+}
+
+int lsa_dense_map_insert_frame(lsa_dense_map* dm, int interpolate, const double H0[16], const double H1[16], double t0, double t1, double time_offset, int frame)
+{
+  if (!dm) return LSA_E_ARG;
+  lsa_ctx* ctx = dm->ctx;
+  if (!H0 || (interpolate && !H1)) return ctx->fail(LSA_E_ARG, "lsa_dense_map_insert_frame: bad argument");
+  if (!ctx->frame || ctx->frame_n <= 0) return ctx->fail(LSA_E_STATE, "lsa_dense_map_insert_frame: no frame");
+  if (frame < dm->last_frame) return ctx->fail(LSA_E_ARG, "lsa_dense_map_insert_frame: frame ordinals must not decrease");
+  LSA_HIP(ctx, hipSetDevice(ctx->device));
+  const int n = ctx->frame_n;
+  FrameMove m{};
+  m.fused = 1;
+  m.interpolate = interpolate ? 1 : 0;
+  row_major_to_rt(H0, m.R.R, m.R.t);
+  if (interpolate) m.c = make_interp_const(H0, H1, t0, t1);
+  m.time_offset = time_offset;
+  // the frame is whatever the context's stream has made of it so far (upload, times from the advancement); the buffer is
+  // then held until the insertion is over by an event its next writer waits for (frame_writer_guard), never by the host
+  LSA_HIP(ctx, hipEventRecord(dm->ev_frame, ctx->stream));
+  LSA_HIP(ctx, hipStreamWaitEvent(dm->stream, dm->ev_frame, 0));
+  // (a refusal comes from make_room, before anything is touched)
+  const int rc = insert_device_points(dm, ctx->frame, n, m, frame, "lsa_dense_map_insert_frame");
+  if (rc) return rc;
+  LSA_HIP(ctx, hipEventRecord(ctx->ev_dense, dm->stream));
+  ctx->dense_frame_pending = true;
+  return LSA_OK;
+}
+
+int lsa_dense_map_reserve(lsa_dense_map* dm, long long n)
+{
+  if (!dm) return LSA_E_ARG;
+  if (n < 0) return dm->ctx->fail(LSA_E_ARG, "lsa_dense_map_reserve: bad argument");
+  if (hipSetDevice(dm->ctx->device) != hipSuccess) return dm->ctx->fail(LSA_E_HIP, "lsa_dense_map_reserve: hipSetDevice");
+  return make_room(dm, n, "lsa_dense_map_reserve");
+}
+
+int lsa_dense_map_size(lsa_dense_map* dm)
+{
+  if (!dm) return LSA_E_ARG;
+  const int rc = settle(dm, "lsa_dense_map_size");
+  return rc ? rc : (int)occupied_bound(dm);
+}
+
+long long lsa_dense_map_skipped(lsa_dense_map* dm)
+{
+  if (!dm) return LSA_E_ARG;
+  const int rc = settle(dm, "lsa_dense_map_skipped");
+  if (rc) return rc;
+  return dm->seen_serial >= dm->epoch ? (long long)__atomic_load_n(&dm->host_words[2], __ATOMIC_ACQUIRE) : 0ll;
+}
+
+long long lsa_dense_map_bytes(const lsa_dense_map* dm)
+{
+  if (!dm) return LSA_E_ARG;
+  return (long long)dm->capacity * (long long)sizeof(Slot) + (long long)dm->slot_cap * (long long)sizeof(int);
+}
+
+int lsa_dense_map_get(lsa_dense_map* dm, int min_frames, lsa_point_t* pts, lsa_dense_voxel_t* voxels, int capacity)
+{
+  if (!dm) return LSA_E_ARG;
+  lsa_ctx* ctx = dm->ctx;
+  if (capacity < 0) return ctx->fail(LSA_E_ARG, "lsa_dense_map_get: bad argument");
+  const double t0 = now_seconds();
+  const int kept = export_sorted(dm, min_frames, "lsa_dense_map_get");
+  if (kept <= 0) return kept;
+  const int n = std::min(kept, capacity);
+  if (n > 0 && pts) LSA_HIP(ctx, hipMemcpyAsync(pts, dm->out_pts, (size_t)n * sizeof(lsa_point_t), hipMemcpyDeviceToHost, dm->stream));
+  if (n > 0 && voxels) LSA_HIP(ctx, hipMemcpyAsync(voxels, dm->out_vox, (size_t)n * sizeof(lsa_dense_voxel_t), hipMemcpyDeviceToHost, dm->stream));
+  LSA_HIP(ctx, hipStreamSynchronize(dm->stream));
+  dm->export_seconds = now_seconds() - t0;
+  return kept;
+}
+
+int lsa_dense_map_clear(lsa_dense_map* dm)
+{
+  if (!dm) return LSA_E_ARG;
+  lsa_ctx* ctx = dm->ctx;
+  LSA_HIP(ctx, hipSetDevice(ctx->device));
+  if (dm->slots) LSA_HIP(ctx, hipMemsetAsync(dm->slots, 0, (size_t)dm->capacity * sizeof(Slot), dm->stream));
+  LSA_HIP(ctx, hipMemsetAsync(dm->stat, 0, kStatWords * sizeof(u64), dm->stream));
+  // what insertions before the clear still publish is older than the epoch and ignored; the error word goes with them
+  LSA_HIP(ctx, hipStreamSynchronize(dm->stream));
+  dm->host_words[1] = 0ull;
+  dm->epoch = dm->next_serial;
+  dm->seen_serial = dm->epoch - 1u;
+  dm->known = 0;
+  dm->pending.clear();
+  dm->pending_sum = 0;
+  dm->last_frame = INT32_MIN;
+  return LSA_OK;
+}
+
+int lsa_dense_map_save_pcd(lsa_dense_map* dm, const char* path, int format, int min_frames)
+{
+  if (!dm) return LSA_E_ARG;
+  lsa_ctx* ctx = dm->ctx;
+  if (!path) return ctx->fail(LSA_E_ARG, "lsa_dense_map_save_pcd: no path");
+  if (format < pcd::kAscii || format > pcd::kBinaryCompressed) return ctx->fail(-4, std::string(path) + ": unknown PCD format " + std::to_string(format));
+  try
+  {
+    double* T = ctx->pcd_times;
+    std::fill(T, T + 8, 0.);
+    const double t0 = now_seconds();
+    const int kept = export_sorted(dm, min_frames, "lsa_dense_map_save_pcd");
+    if (kept < 0) return kept;
+    T[4] = now_seconds() - t0;
+    return pcd_save_device_points(ctx, dm->stream, dm->out_pts, kept, path, format);
+  }
+  catch (const std::bad_alloc&) { return ctx->fail(LSA_E_CAPACITY, std::string(path) + ": not enough host memory"); }
+}
+
+}  // extern "C"

@@ -267,6 +267,26 @@ LSA_DEV void interp_eval(const InterpConst& c, double t, Rigid& out)
   out.t[2] = c.trans0[2] + time * (c.trans1[2] - c.trans0[2]);
 }
 
+// A frame's point (a = x y z w, b = time | intensity, laser, device, label) moved to the world the way
+// Slam::AggregateFrames(..., true) does (Slam.cxx:1512-1578): point.time += time_offset before the pose is evaluated at it,
+// double arithmetic stored as float.  ONE statement for k_transform_out (lsa_transform.hip) and for the dense map's fused
+// insertion (lsa_dense_map.hip), which must give the same bytes.
+LSA_DEV void frame_point_to_world(float4& a, float4& b, int interpolate, const InterpConst& c, const Rigid& R, double time_offset)
+{
+  double t = __hiloint2double(__float_as_int(b.y), __float_as_int(b.x));
+  if (time_offset != 0.)
+  {
+    t = t + time_offset;
+    b.x = __int_as_float(__double2loint(t));
+    b.y = __int_as_float(__double2hiint(t));
+  }
+  Rigid T = R;
+  if (interpolate) interp_eval(c, t, T);
+  double ox, oy, oz;
+  rigid_apply(T, (double)a.x, (double)a.y, (double)a.z, ox, oy, oz);
+  a.x = (float)ox; a.y = (float)oy; a.z = (float)oz;
+}
+
 // dense symmetric positive definite solve, as SolveSPD of host/lsa_lm_loop.cpp: Cholesky, forward, backward
 template <int N>
 __device__ __forceinline__ bool solve_spd(const double A[N * N], const double b[N], double x[N])

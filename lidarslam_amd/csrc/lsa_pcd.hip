@@ -285,11 +285,19 @@ static int save_pcd(lsa_device_grid* g, const char* path, int format, int clean)
   int rc = grid_collect(g, clean, &pts, &n);
   if (rc) return rc;
   T[4] = now_s() - t_get;
+  return lsa::pcd_save_device_points(ctx, grid_stream(g), pts, n, path, format);
+}
+}  // extern "C"
+
+// n LidarPoints on the device (what kernels on `gs` left) into a PCD file: the part of a save that comes behind the collection,
+// for the keypoint maps above and the dense map (lsa_dense_map.hip).  The caller has checked path and format and set T[4].
+int lsa::pcd_save_device_points(lsa_ctx* ctx, hipStream_t gs, const lsa_point_t* pts, int n, const char* path, int format)
+{
+  double* T = ctx->pcd_times;
   T[6] = n;
   if (n == 0) return 0;
-  rc = ensure_pieces(ctx);
+  int rc = ensure_pieces(ctx);
   if (rc) return rc;
-  hipStream_t gs = grid_stream(g);
   const bool columns = format == pcd::kBinaryCompressed;
   const bool lds = !columns && (ctx->pcd_lds < 0 ? kLdsDefault : ctx->pcd_lds) != 0;
   int per_piece = (int)(kPieceBytes / pcd::kRecordBytes);
@@ -339,6 +347,7 @@ static int save_pcd(lsa_device_grid* g, const char* path, int format, int clean)
   return n;
 }
 
+extern "C" {
 // Seconds of the last lsa_device_grid_add_pcd / _save_pcd of the context (diagnostics): [0] file, [1] LZF, [2] text,
 // [3] pieces on their way (upload + conversion, overlapped), [4] the grid's Add / Get, [5] bytes moved, [6] points.
 // [3] and [4] wait for the device only while profiling is on; otherwise they are the time to enqueue.

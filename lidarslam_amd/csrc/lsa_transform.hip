@@ -55,18 +55,7 @@ __global__ __launch_bounds__(256) void k_transform_out(const float4* __restrict_
   if (i >= n) return;
   float4 a = in[2 * (size_t)i];
   float4 b = in[2 * (size_t)i + 1];
-  if (time_offset != 0.)
-  {
-    // point.time += timeOffset, before the pose is evaluated at it (Slam.cxx:1547-1549)
-    const double t = point_time(b) + time_offset;
-    b.x = __int_as_float(__double2loint(t));
-    b.y = __int_as_float(__double2hiint(t));
-  }
-  Rigid T = R;
-  if (interpolate) interp_eval(c, point_time(b), T);
-  double ox, oy, oz;
-  rigid_apply(T, (double)a.x, (double)a.y, (double)a.z, ox, oy, oz);
-  a.x = (float)ox; a.y = (float)oy; a.z = (float)oz;
+  frame_point_to_world(a, b, interpolate, c, R, time_offset);  // lsa_device_math.h: shared with the dense map's insertion
   out[2 * (size_t)i] = a;
   out[2 * (size_t)i + 1] = b;
 }

@@ -204,6 +204,7 @@ int lsa_upload_frame_begin(lsa_ctx* ctx, const lsa_point_t* pts, int n)
   }
   in.n = n;
   in.src = pts;
+  LSA_HIP(ctx, frame_writer_guard(ctx, ctx->copy_stream));  // this slot's last frame may still be read by the dense map's insertion
   in.state.store(1, std::memory_order_release);
   ctx->inbox_queue.push_back(slot);
   {
@@ -302,6 +303,7 @@ int lsa_upload_frame(lsa_ctx* ctx, const lsa_point_t* pts, int n)
   int rc = ensure_capacity(ctx, n);
   if (rc) return rc;
   maybe_estimate_resolution(ctx, pts, n);
+  LSA_HIP(ctx, frame_writer_guard(ctx, ctx->stream));
   LSA_HIP(ctx, hipMemcpyAsync(ctx->frame_own, pts, (size_t)n * sizeof(lsa_point_t), hipMemcpyHostToDevice, ctx->stream));
   ctx->frame = ctx->frame_own;
   ctx->frame_n = n;
@@ -332,6 +334,7 @@ int lsa_frame_store_put(lsa_ctx* ctx, int slot, const lsa_point_t* pts, int n)
     LSA_HIP(ctx, hipMalloc((void**)&d, (size_t)n * sizeof(lsa_point_t)));
     ctx->store_cap[slot] = n;
   }
+  LSA_HIP(ctx, frame_writer_guard(ctx, ctx->stream));
   LSA_HIP(ctx, hipMemcpyAsync(d, pts, (size_t)n * sizeof(lsa_point_t), hipMemcpyHostToDevice, ctx->stream));
   LSA_HIP(ctx, hipStreamSynchronize(ctx->stream));  // pts may be pageable and reused by the caller
   ctx->store[slot] = {d, n};
@@ -344,6 +347,7 @@ int lsa_frame_store_use(lsa_ctx* ctx, int slot)
 {
   if (!ctx || slot < 0 || slot >= (int)ctx->store.size() || !ctx->store[slot].first)
     return ctx ? ctx->fail(LSA_E_ARG, "lsa_frame_store_use: empty slot") : LSA_E_ARG;
+  LSA_HIP(ctx, frame_writer_guard(ctx, ctx->stream));  // what works on the slot in place next (times from the advancement) comes behind a dense-map insertion that reads it
   ctx->frame = ctx->store[slot].first;
   ctx->frame_n = ctx->store[slot].second;
   ctx->inbox_current = -1;

@@ -152,6 +152,7 @@ int lsa_upload_wire_frame(lsa_ctx* ctx, const void* data, int n, const lsa_wire_
   if (ctx->az_res <= 0.f) return on_host();
   int rc = ensure_capacity(ctx, n);
   if (rc) return rc;
+  LSA_HIP(ctx, frame_writer_guard(ctx, ctx->stream));  // frame_own is about to be rewritten: behind a dense-map insertion that reads it
   const size_t bytes = (size_t)n * lay->point_step;
   rc = ensure_scratch(ctx, bytes);
   if (rc) return rc;
@@ -272,6 +273,7 @@ int lsa_upload_polydata_frame(lsa_ctx* ctx, int n, const void* xyz, int xyz_type
   LSA_HIP(ctx, hipSetDevice(ctx->device));
   int rc = ensure_capacity(ctx, n);
   if (rc) return rc;
+  LSA_HIP(ctx, frame_writer_guard(ctx, ctx->stream));  // frame_own is about to be rewritten: behind a dense-map insertion that reads it
   // the four arrays go to the device as they are (structure of arrays, no LidarPoint cloud is built on the host)
   const size_t sz[4] = {(size_t)3 * n * scalar_size(xyz_type), (size_t)n * scalar_size(time_type), (size_t)n * scalar_size(laser_type),
                         (size_t)n * scalar_size(intensity_type)};
@@ -431,6 +433,7 @@ int lsa_upload_robosense_frame(lsa_ctx* ctx, const void* records, int width, int
   const int n = width * height;
   int rc = ensure_capacity(ctx, n);
   if (rc) return rc;
+  LSA_HIP(ctx, frame_writer_guard(ctx, ctx->stream));  // frame_own is about to be rewritten: behind a dense-map insertion that reads it
   const size_t bytes = (size_t)n * lay->point_step;
   const int nchunks = (n + 1023) / 1024;
   const size_t off_keep = (bytes + 255) / 256 * 256, off_last = off_keep + ((size_t)n + 255) / 256 * 256,

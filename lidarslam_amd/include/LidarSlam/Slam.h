@@ -749,6 +749,44 @@ public:
   // Slam::ClearMaps (Slam.cxx): empties the three keypoint maps, poses and parameters stay
   void ClearMaps() { lsa_slam_clear_maps(this->Handle); }
 
+  // ---- the dense point-cloud map (not in the reference, whose wrappers voxelize GetRegisteredFrame themselves): the
+  // registered frame of every AddFrame (mode 1) or of every keyframe (mode 2) goes into a voxel hash table on the device,
+  // one point per voxel of SetDenseMapLeafSize metres (default 0.1).  minFrames: only voxels seen in that many frames, the
+  // MinFramesPerVoxel idea (a passing car touches a voxel in a frame or two, a wall in many).  Cleared by Reset, ClearMaps
+  // and every applied trajectory.  A failure is reported through GetLastError().
+  void SetDenseMap(int mode) { this->SetParam("DenseMap", mode); }
+  int GetDenseMapMode() const { return static_cast<int>(this->GetParam("DenseMap")); }
+  void SetDenseMapLeafSize(double size) { this->SetParam("DenseMapLeafSize", size); }
+  double GetDenseMapLeafSize() const { return this->GetParam("DenseMapLeafSize"); }
+  // the size is asked for first, so the map is exported once and whole whatever its size; on a failure the cloud is empty
+  PointCloud::Ptr GetDenseMap(int minFrames = 1)
+  {
+    PointCloud::Ptr pc(new PointCloud);
+    pc->header.stamp = this->CurrentStamp;
+    pc->header.frame_id = this->WorldFrameId;
+    int n = lsa_slam_dense_map_size(this->Handle);
+    if (n > 0)
+    {
+      pc->points.resize(static_cast<std::size_t>(n));
+      n = lsa_slam_get_dense_map(this->Handle, minFrames, reinterpret_cast<lsa_point_t*>(pc->points.data()), nullptr, n);
+      pc->points.resize(static_cast<std::size_t>(std::max(n, 0)));
+    }
+    this->LastError = n < 0 ? std::string("GetDenseMap: ") + lsa_slam_last_error(this->Handle) : std::string();
+    return pc;
+  }
+  // returns the points written (0 and no file for an empty map), negative on failure
+  int SaveDenseMapToPCD(const std::string& path, PCDFormat pcdFormat = PCDFormat::BINARY_COMPRESSED, int minFrames = 1) const
+  {
+    const int rc = lsa_slam_save_dense_map_pcd(this->Handle, path.c_str(), static_cast<int>(pcdFormat), minFrames);
+    this->LastError = rc < 0 ? std::string("SaveDenseMapToPCD: ") + lsa_slam_last_error(this->Handle) : std::string();
+    return rc;
+  }
+  void ClearDenseMap()
+  {
+    const int rc = lsa_slam_clear_dense_map(this->Handle);
+    this->LastError = rc < 0 ? std::string("ClearDenseMap: ") + lsa_slam_last_error(this->Handle) : std::string();
+  }
+
   // ---- keypoint extractor parameters (SpinningSensorKeypointExtractor.h:44-70); one extractor (device 0)
   LSA_SLAM_PARAM(NeighborWidth, int)
   LSA_SLAM_PARAM(MinDistanceToSensor, float)

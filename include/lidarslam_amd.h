@@ -1197,7 +1197,26 @@ int lsa_pcd_io_times(const lsa_ctx* ctx, double out[8]);
  * - _size (voxels), _skipped, _get and _save_pcd wait for the insertions in flight.  _get returns the number of voxels with
  *   frames >= min_frames and writes at most `capacity` of them in ascending key order (pts or voxels may be NULL); _save_pcd
  *   writes the same points, returns their number, 0 and no file for none.  LSA_E_STATE when a probe sequence ran through
- *   the whole table (it is bounded by the capacity; cannot happen at load <= 1/2). */
+ *   the whole table (it is bounded by the capacity; cannot happen at load <= 1/2).
+ * - Source: beside its record a voxel keeps `source`, the ordinal of the call whose point it holds (set when the voxel is made
+ *   or its point replaced).  _get_sources returns them aligned with _get(min_frames), same order, same return convention.
+ * - _reproject moves what the map kept under a corrected trajectory -- one point per voxel, moved by the correction of the
+ *   frame that measured it; not a rebuild from raw frames, which are not logged: two neighbouring surface voxels may merge
+ *   and the voxel between them may stay empty until it is seen again.  corrections16: n row-major 4x4 rigid transforms,
+ *   entry j for ordinal first_frame + j; a voxel takes entry c = clamp(source - first_frame, 0, n - 1).  Its point moves as
+ *   lsa_device_math.h's rigid_apply moves it, in double, without contraction, narrowed to float: x' = (float)(((R0 x + R1 y)
+ *   + R2 z) + t0) and likewise y', z' (a -0.0 comes out +0.0 under the identity); the other 20 bytes are kept.  The new key
+ *   is the moved point's; a moved point that is not finite or outside the index range drops its voxel (counted in *dropped
+ *   and in "Dropped", not in `skipped`).  Voxels that arrive at one key merge: count the sum modulo 2^32, first_frame the
+ *   min, last_frame the max, frames = min(sum of frames, last_frame - first_frame + 1), point and source from the voxel of
+ *   largest intensity code, ties to the smaller source, then to the smaller old key.  Nothing depends on the order in which
+ *   the voxels are visited; the guard on non-decreasing ordinals is unchanged and insertion goes on afterwards.  The call
+ *   waits for the insertions in flight, builds a second table of the same capacity (the voxel count cannot grow) with three
+ *   launches over the old slots and retires the old one; its cost is the map's size, not the drive's.  LSA_E_ARG for n < 1
+ *   or a NULL pointer, LSA_E_CAPACITY when the second table cannot be allocated: the map is untouched by either.
+ *   lsa_dense_map_get_param answers "Reprojections", "Dropped" (voxels, since the last clear), "ReprojectSeconds" (the last).
+ * - lsa_pose_corrections: out_i = new_i * inverse(old_i) for n poses (row-major 4x4, rigid inverse R^T, -R^T t, in double):
+ *   the corrections the pipeline hands _reproject. */
 typedef struct lsa_dense_voxel_t
 {
   uint64_t key;
@@ -1218,6 +1237,9 @@ int lsa_dense_map_size(lsa_dense_map* dm);
 long long lsa_dense_map_skipped(lsa_dense_map* dm);
 long long lsa_dense_map_bytes(const lsa_dense_map* dm);
 int lsa_dense_map_get(lsa_dense_map* dm, int min_frames, lsa_point_t* pts, lsa_dense_voxel_t* voxels, int capacity);
+int lsa_dense_map_get_sources(lsa_dense_map* dm, int min_frames, int32_t* out, int capacity);
+int lsa_dense_map_reproject(lsa_dense_map* dm, const double* corrections16, int first_frame, int n, long long* dropped);
+int lsa_pose_corrections(const double* old16, const double* new16, int n, double* out16);
 int lsa_dense_map_clear(lsa_dense_map* dm);
 int lsa_dense_map_save_pcd(lsa_dense_map* dm, const char* path, int format, int min_frames);
 /* The pipeline's dense map (lsa_slam_set_param "DenseMap": 0 off, the default, under which nothing whatever changes; 1 every
@@ -1230,10 +1252,20 @@ int lsa_dense_map_save_pcd(lsa_dense_map* dm, const char* path, int format, int 
  * "DenseMapExportSeconds".  The map is cleared by Reset, ClearMaps and everything that applies a corrected
  * trajectory (lsa_slam_set_trajectory_and_rebuild_maps; the pose-graph calls and lsa_slam_close_loops with `apply`): its
  * points were placed under the old poses and raw frames are not logged, so a stale map must not pass for a corrected one
- * ("DenseMapClears" counts, the first one warns on stderr), also while "DenseMap" is 0 for the moment.  The four calls wait for the insertions in flight and refuse
- * with LSA_E_STATE while "DenseMap" is 0. */
+ * ("DenseMapClears" counts, the first one warns on stderr), also while "DenseMap" is 0 for the moment.  The calls below wait for the insertions in flight and refuse
+ * with LSA_E_STATE while "DenseMap" is 0.
+ * "DenseMapOnTrajectory" (default 0: an applied trajectory clears, as said; 1: it re-projects): with 1 and a map that is not
+ * empty, lsa_slam_set_trajectory_and_rebuild_maps -- and so every call that applies through it -- takes D_i = new_i *
+ * inverse(old_i) per logged pose (lsa_pose_corrections, against the poses it actually applies), gives every dense ordinal
+ * the correction of the logged pose dated like its frame (8 B a frame are kept for that; ordinals that have left the log under
+ * a positive LoggingTimeout take the oldest logged pose's), and calls lsa_dense_map_reproject; "DenseMapFrames" is not reset
+ * and mapping goes on with the next ordinal.  If the second table cannot be allocated the trajectory is applied all the same
+ * and the map is cleared as under 0 ("DenseMapClears", the reason in lsa_slam_last_error).  Reset, ClearMaps,
+ * lsa_slam_clear_dense_map and a changed leaf size clear under either value.  Read-only: "DenseMapReprojections",
+ * "DenseMapDropped", "DenseMapReprojectSeconds".  _get_dense_map_sources: lsa_dense_map_get_sources of the pipeline's map. */
 int lsa_slam_dense_map_size(lsa_slam* s);
 int lsa_slam_get_dense_map(lsa_slam* s, int min_frames, lsa_point_t* pts, lsa_dense_voxel_t* voxels, int capacity);
+int lsa_slam_get_dense_map_sources(lsa_slam* s, int min_frames, int32_t* out, int capacity);
 int lsa_slam_save_dense_map_pcd(lsa_slam* s, const char* path, int format, int min_frames);
 int lsa_slam_clear_dense_map(lsa_slam* s);
 

@@ -285,6 +285,10 @@ SIGNATURES = {
     "lsa_dense_map_skipped": (i64, [vp]),
     "lsa_dense_map_bytes": (i64, [vp]),
     "lsa_dense_map_get": (i32, [vp, i32, vp, vp, i32]),
+    "lsa_dense_map_get_sources": (i32, [vp, i32, vp, i32]),
+    "lsa_dense_map_reproject": (i32, [vp, vp, i32, i32, P(i64)]),
+    "lsa_pose_corrections": (i32, [vp, vp, i32, vp]),
+    "lsa_slam_get_dense_map_sources": (i32, [vp, i32, vp, i32]),
     "lsa_dense_map_clear": (i32, [vp]),
     "lsa_dense_map_save_pcd": (i32, [vp, s, i32, i32]),
     "lsa_slam_dense_map_size": (i32, [vp]),

@@ -43,14 +43,19 @@ def dense_voxel_keys(points, leaf):
 
 
 class DenseMapHost:
-    """The definition.  State: key -> (point, count, frames, first_frame, last_frame).
+    """The definition.  State: key -> (point, count, frames, first_frame, last_frame, intensity code, source).
 
     insert(points, frame): world points as lsa_transform_frame writes them and an ordinal that must not decrease.  Within one
     call a voxel's winner is the point of largest intensity (dense_intensity_code: a NaN loses to every number), ties to
     the smallest index of the call; n_f is the number of the call's points in the voxel.  A new voxel takes the winner's 32
     bytes as they are, count = n_f, frames = 1, first_frame = last_frame = frame.  An existing one: count += n_f, frames += 1
     unless last_frame == frame, last_frame = frame, and the point is replaced only when the winner's intensity is strictly
-    greater -- the earlier frame keeps ties.  Nothing depends on the order in which the points of one call arrive."""
+    greater -- the earlier frame keeps ties.  Nothing depends on the order in which the points of one call arrive.
+    source is the ordinal of the call whose point the voxel holds: set when the voxel is made or its point replaced.
+
+    reproject(corrections, first_frame): the map under a corrected trajectory.  This moves what the map kept -- one point per
+    voxel, moved by the correction of the frame that measured it; it is not a rebuild from raw frames: two neighbouring
+    surface voxels may merge, and the voxel between them may stay empty until it is seen again."""
 
     def __init__(self, leaf):
         if not (leaf > 0 and np.isfinite(leaf)):
@@ -61,6 +66,7 @@ class DenseMapHost:
     def clear(self):
         self.voxels = {}
         self.skipped = 0
+        self.dropped = 0
         self.last_frame = None
 
     def size(self):
@@ -89,7 +95,7 @@ class DenseMapHost:
             c = int(code[order[at]])
             v = self.voxels.get(key)
             if v is None:
-                self.voxels[key] = [pts[w].copy(), n, 1, frame, frame, c]
+                self.voxels[key] = [pts[w].copy(), n, 1, frame, frame, c, frame]
                 continue
             v[1] += n
             if v[4] != frame:
@@ -98,6 +104,7 @@ class DenseMapHost:
             if c > v[5]:
                 v[0] = pts[w].copy()
                 v[5] = c
+                v[6] = frame
 
     def get(self, min_frames=1):
         """(points, voxels) of the voxels with frames >= min_frames, in ascending key order"""
@@ -105,10 +112,61 @@ class DenseMapHost:
         pts = np.zeros(len(keys), POINT_DTYPE)
         vox = np.zeros(len(keys), dense_voxel_dtype)
         for j, k in enumerate(keys):
-            p, count, frames, first, last, _ = self.voxels[k]
+            p, count, frames, first, last = self.voxels[k][:5]
             pts[j] = p
             vox[j] = (k, count, frames, first, last)
         return pts, vox
+
+    def sources(self, min_frames=1):
+        """the source of every voxel of get(min_frames), in its order"""
+        keys = sorted(k for k, v in self.voxels.items() if v[2] >= min_frames)
+        return np.array([self.voxels[k][6] for k in keys], np.int32)
+
+    def reproject(self, corrections, first_frame=0):
+        """corrections: (n, 16) float64, row-major 4x4 rigid transforms, entry j for ordinal first_frame + j.  Returns the
+        number of voxels dropped (also added to self.dropped; skipped is not touched).
+
+        Every voxel takes entry c = clamp(source - first_frame, 0, n - 1) and its point moves as rigid_apply of
+        lsa_device_math.h moves it, in double, without contraction, narrowed to float: x' = (float)(((R0*x + R1*y) + R2*z)
+        + t0), likewise y' and z' (so a -0.0 comes out +0.0 under the identity); the other 20 bytes are kept.  The new key
+        is dense_voxel_keys of the moved point; a moved point that is not finite or lies outside the index range drops its
+        voxel.  Voxels that arrive at one key merge: count is the sum modulo 2^32, first_frame the min, last_frame the
+        max, frames = min(sum of frames, last_frame - first_frame + 1), point and source from the voxel of largest
+        intensity code, ties to the smaller source, then to the smaller old key.  Nothing depends on the order in which
+        the voxels are visited; last_frame of the map, the guard on the ordinals, is unchanged."""
+        D = np.ascontiguousarray(corrections, np.float64).reshape(-1, 16)
+        n = D.shape[0]
+        if n < 1:
+            raise ValueError("at least one correction")
+        old = sorted(self.voxels)
+        if not old:
+            return 0
+        recs = [self.voxels[k] for k in old]
+        pts = np.array([v[0] for v in recs], POINT_DTYPE)
+        source = np.array([v[6] for v in recs], np.int64)
+        T = D[np.clip(source - int(first_frame), 0, n - 1)]
+        x, y, z = (pts[a].astype(np.float64) for a in ("x", "y", "z"))
+        with np.errstate(over="ignore", invalid="ignore"):
+            for row, a in enumerate(("x", "y", "z")):
+                pts[a] = (((T[:, 4 * row] * x + T[:, 4 * row + 1] * y) + T[:, 4 * row + 2] * z) + T[:, 4 * row + 3]).astype(np.float32)
+        keys, ok = dense_voxel_keys(pts, self.leaf)
+        merged = {}
+        for j in np.flatnonzero(ok).tolist():
+            p, count, frames, first, last, code, src = recs[j]
+            rank = (-code, src, old[j])  # the smallest wins: largest code, then smaller source, then smaller old key
+            m = merged.get(int(keys[j]))
+            if m is None:
+                merged[int(keys[j])] = [pts[j].copy(), count, frames, first, last, code, src, rank]
+                continue
+            m[1] = (m[1] + count) & 0xFFFFFFFF
+            m[2] += frames
+            m[3], m[4] = min(m[3], first), max(m[4], last)
+            if rank < m[7]:
+                m[0], m[5], m[6], m[7] = pts[j].copy(), code, src, rank
+        self.voxels = {k: [m[0], m[1], min(m[2], m[4] - m[3] + 1), m[3], m[4], m[5], m[6]] for k, m in merged.items()}
+        dropped = int((~ok).sum())
+        self.dropped += dropped
+        return dropped
 
 
 class DenseMap:
@@ -174,6 +232,22 @@ class DenseMap:
         n = self._check(self.L.lsa_dense_map_get(self.h, int(min_frames), ptr(pts), ptr(vox), cap), "lsa_dense_map_get")
         return pts[:n].copy(), vox[:n].copy()
 
+    def sources(self, min_frames=1):
+        """int32 ordinals of the calls whose points the voxels of get(min_frames) hold, in its order"""
+        cap = max(self.size(), 1)
+        out = np.zeros(cap, np.int32)
+        n = self._check(self.L.lsa_dense_map_get_sources(self.h, int(min_frames), ptr(out), cap), "lsa_dense_map_get_sources")
+        return out[:n].copy()
+
+    def reproject(self, corrections, first_frame=0):
+        """the map under per-frame rigid corrections ((n, 16) or (n, 4, 4); entry j for ordinal first_frame + j), as
+        DenseMapHost.reproject states it; returns the number of voxels dropped.  LsaError with .code E_CAPACITY, the map
+        untouched, when the second table cannot be allocated; E_ARG for no corrections"""
+        D = np.ascontiguousarray(corrections, np.float64).reshape(-1, 16)
+        dropped = C.c_longlong(0)
+        self._check(self.L.lsa_dense_map_reproject(self.h, ptr(D) if D.size else None, int(first_frame), D.shape[0], C.byref(dropped)), "lsa_dense_map_reproject")
+        return int(dropped.value)
+
     def clear(self):
         self._check(self.L.lsa_dense_map_clear(self.h), "lsa_dense_map_clear")
 
@@ -196,6 +270,28 @@ def dense_map(slam, min_frames=1):
     pts, vox = np.zeros(cap, POINT_DTYPE), np.zeros(cap, dense_voxel_dtype)
     n = slam._check(slam.L.lsa_slam_get_dense_map(slam.h, int(min_frames), ptr(pts), ptr(vox), cap), "lsa_slam_get_dense_map")
     return pts[:n].copy(), vox[:n].copy()
+
+
+def dense_map_sources(slam, min_frames=1):
+    """int32 ordinals of the frames whose points the voxels of dense_map(slam, min_frames) hold, in its order"""
+    cap = max(dense_map_size(slam), 1)
+    out = np.zeros(cap, np.int32)
+    n = slam._check(slam.L.lsa_slam_get_dense_map_sources(slam.h, int(min_frames), ptr(out), cap), "lsa_slam_get_dense_map_sources")
+    return out[:n].copy()
+
+
+def pose_corrections(old, new):
+    """(n, 16) float64: new_i @ inverse(old_i) per pose, by the library's own arithmetic (lsa_pose_corrections) -- what
+    Slam.set_trajectory hands the dense map's re-projection under "DenseMapOnTrajectory" 1"""
+    a = np.ascontiguousarray(old, np.float64).reshape(-1, 16)
+    b = np.ascontiguousarray(new, np.float64).reshape(-1, 16)
+    if a.shape != b.shape:
+        raise ValueError("as many new poses as old ones")
+    out = np.zeros_like(a)
+    rc = lib().lsa_pose_corrections(ptr(a), ptr(b), a.shape[0], ptr(out))
+    if rc != 0:
+        raise _error("lsa_pose_corrections", rc, "bad argument")
+    return out
 
 
 def save_dense_map_pcd(slam, path, format=PCD_BINARY, min_frames=1):  # noqa: A002 (the C ABI's name of the parameter)

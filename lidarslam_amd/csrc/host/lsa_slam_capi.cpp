@@ -314,6 +314,12 @@ int lsa_slam_get_dense_map(lsa_slam* s, int min_frames, lsa_point_t* pts, lsa_de
   return s->core.GetDenseMap(min_frames, pts, voxels, capacity);
 }
 
+int lsa_slam_get_dense_map_sources(lsa_slam* s, int min_frames, int* out, int capacity)
+{
+  if (!s) return LSA_E_ARG;
+  return s->core.GetDenseMapSources(min_frames, out, capacity);
+}
+
 int lsa_slam_save_dense_map_pcd(lsa_slam* s, const char* path, int format, int min_frames)
 {
   if (!s || !path) return LSA_E_ARG;

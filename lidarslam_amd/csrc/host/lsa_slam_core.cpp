@@ -77,13 +77,13 @@ int SlamCore::Fail(int rc, const char* where)
 }
 
 // Slam::Reset (Slam.cxx:164-210)
-void SlamCore::Reset(bool resetLog)
+void SlamCore::Reset(bool resetLog, bool keepDenseMap)
 {
   WaitMaps();
   for (int k = 0; k < 3; ++k) LocalMaps[k]->Reset();
   for (auto* g : DevMaps)
     if (g) lsa_device_grid_reset(g, nullptr);
-  DropDenseMap("Reset or an applied trajectory");
+  if (!keepDenseMap) DropDenseMap("Reset or an applied trajectory");
   KfLastPose = Pose::Identity();
   KfCounter = 0;
   Tworld = PreviousTworld = Trelative = Pose::Identity();
@@ -384,7 +384,7 @@ int SlamCore::ProcessCurrentFrame(uint64_t stampUs)
   // Tworld and the motion within the frame are final: the registered frame goes into the dense map (off: nothing)
   if (DenseMapMode != 0)
   {
-    rc = InsertDenseFrame(KfCounter != keyframesBefore);
+    rc = InsertDenseFrame(KfCounter != keyframesBefore, CurrentTime);
     if (rc < 0) return rc;
   }
   // the next frame's first jobs for the look-ahead thread (the sub-maps under the predicted pose, the ego-motion targets) come

@@ -71,7 +71,8 @@ public:
   const std::string& Error() const { return LastError; }
   lsa_ctx* Context() { return Ctx; }
 
-  void Reset(bool resetLog = true);
+  // keepDenseMap: SetTrajectoryAndRebuildMaps' alone, when the dense map is re-projected instead of cleared
+  void Reset(bool resetLog = true, bool keepDenseMap = false);
   // Slam::AddFrame on a host scan / on a scan resident in the frame store
   int AddFrame(const lsa_point_t* pts, int n, uint64_t stampUs, uint32_t seq);
   int AddStoredFrame(int slot, uint64_t stampUs, uint32_t seq);
@@ -275,8 +276,14 @@ public:
   double DenseMapLeafSize = 0.1;
   double DenseMapMaxBytes = 16. * 1024. * 1024. * 1024.;  // of the table; 0: no limit
   unsigned DenseFrames = 0, DenseRefused = 0, DenseClears = 0;
+  // "DenseMapOnTrajectory": what an applied trajectory does to the map.  0 clears it (the default); 1 re-projects it on the
+  // device, every voxel's point under new * inverse(old) of the logged pose of the frame that measured it
+  // (ReprojectDenseMap), and the ordinals go on.  Reset, ClearMaps and ClearDenseMap clear under either value.
+  int DenseMapOnTrajectory = 0;
+  unsigned DenseReprojections = 0;
   int DenseMapSize();
   int GetDenseMap(int minFrames, lsa_point_t* pts, lsa_dense_voxel_t* voxels, int capacity);
+  int GetDenseMapSources(int minFrames, int* out, int capacity);
   int SaveDenseMapToPCD(const std::string& path, int format, int minFrames);
   int ClearDenseMap();
 
@@ -422,7 +429,12 @@ private:
   // ---- the dense map (lsa_slam_dense.cpp) ----
   lsa_dense_map* Dense = nullptr;  // made by the first insertion
   bool DenseWarned = false;
-  int InsertDenseFrame(bool keyframe);
+  std::vector<double> DenseTimes;  // per ordinal, the time under which LogCurrentFrameState logged the frame
+  int InsertDenseFrame(bool keyframe, double time);
+  // the corrections of the dense ordinals still logged (from *firstOrdinal on) for the trajectory poses16 about to replace
+  // the logged one; false when the map is to be cleared instead
+  bool DenseCorrections(const double* poses16, int n, std::vector<double>& corrections, int* firstOrdinal) const;
+  int ReprojectDenseMap(const std::vector<double>& corrections, int firstOrdinal);
   void DropDenseMap(const char* why);  // why == nullptr: the caller asked for it, nothing to warn about
   int DenseReady(const char* who);
 

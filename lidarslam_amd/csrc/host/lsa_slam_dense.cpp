@@ -1,8 +1,11 @@
 // lsa_slam_dense.cpp -- see lsa_slam_core.h: the pipeline's dense point-cloud map (lsa_dense_map.hip).  The
 // registered frame goes into the table at the end of AddFrame without leaving the device; what moves the poses under the
-// points that are already in it clears it.
+// points that are already in it clears it -- or, under "DenseMapOnTrajectory" 1 and for an applied trajectory alone,
+// re-projects it: every voxel's point moved by the correction of the frame that measured it.
 #include "lsa_slam_internal.h"
+#include <algorithm>
 #include <cstdio>
+#include <cstring>
 
 namespace lsa
 {
@@ -11,7 +14,7 @@ namespace host
 // The frame or frames of the call under exactly the poses GetRegisteredFrame uses, fused with the insertion, on the
 // look-ahead stream; nothing is waited for.  A refused insertion (the table would outgrow "DenseMapMaxBytes") is counted
 // and reported, and does not fail the frame.
-int SlamCore::InsertDenseFrame(bool keyframe)
+int SlamCore::InsertDenseFrame(bool keyframe, double time)
 {
   if (DenseMapMode == 2 && !keyframe) return LSA_OK;
   if (!Dense)
@@ -68,7 +71,11 @@ int SlamCore::InsertDenseFrame(bool keyframe)
     if (const int rc = insert(BaseToLidarOffset, 0.); rc < 0) return rc;
   }
   if (refused) DenseRefused++;
-  if (inserted) DenseFrames++;
+  if (inserted)
+  {
+    DenseFrames++;
+    DenseTimes.push_back(time);  // 8 B a frame: which logged pose an applied trajectory corrects this ordinal by
+  }
   return LSA_OK;
 }
 
@@ -79,12 +86,53 @@ void SlamCore::DropDenseMap(const char* why)
   if (!Dense) return;
   (void)lsa_dense_map_clear(Dense);
   DenseFrames = 0;
+  DenseTimes.clear();
   DenseClears++;
   if (why && !DenseWarned)
   {
     DenseWarned = true;
     std::fprintf(stderr, "lidarslam_amd: the dense map was cleared by %s: its points were placed under the poses of before, and raw frames are not logged to place them again (said once)\n", why);
   }
+}
+
+// SetTrajectoryAndRebuildMaps, before the logged poses are overwritten: D_i = new_i * inverse(old_i) per logged pose, then per
+// dense ordinal the correction of the logged pose with its time.  Ordinals older than the log (a positive LoggingTimeout)
+// precede *firstOrdinal and take the oldest logged pose's correction: the clamp of lsa_dense_map_reproject.
+bool SlamCore::DenseCorrections(const double* poses16, int n, std::vector<double>& corrections, int* firstOrdinal) const
+{
+  if (DenseMapOnTrajectory != 1 || !Dense || DenseFrames == 0 || DenseTimes.size() != DenseFrames || n < 1) return false;
+  std::vector<double> old, times, D(static_cast<size_t>(n) * 16);
+  LoggedPoses16(old, &times);
+  if (lsa_pose_corrections(old.data(), poses16, n, D.data()) != LSA_OK) return false;
+  const size_t first = static_cast<size_t>(std::lower_bound(DenseTimes.begin(), DenseTimes.end(), times[0]) - DenseTimes.begin());
+  corrections.clear();
+  size_t i = 0;
+  for (size_t j = first; j < DenseTimes.size(); ++j)
+  {
+    // the logged pose dated like the ordinal (the last one not after it, should a time ever be missing from the log)
+    while (i + 1 < static_cast<size_t>(n) && times[i + 1] <= DenseTimes[j]) ++i;
+    corrections.insert(corrections.end(), D.begin() + 16 * i, D.begin() + 16 * (i + 1));
+  }
+  if (corrections.empty()) corrections.assign(D.begin(), D.begin() + 16);  // every ordinal is older than the log
+  *firstOrdinal = static_cast<int>(first);
+  return true;
+}
+
+// The map under the corrections; the ordinals go on.  Without memory for the second table the map is cleared as under
+// "DenseMapOnTrajectory" 0, counted in "DenseMapClears", the reason in LastError: the trajectory is applied all the same.
+int SlamCore::ReprojectDenseMap(const std::vector<double>& corrections, int firstOrdinal)
+{
+  long long dropped = 0;
+  const int rc = lsa_dense_map_reproject(Dense, corrections.data(), firstOrdinal, static_cast<int>(corrections.size() / 16), &dropped);
+  if (rc == LSA_OK)
+  {
+    DenseReprojections++;
+    return LSA_OK;
+  }
+  const std::string why = std::string("dense map: not re-projected, cleared: ") + lsa_last_error(Ctx);
+  DropDenseMap("an applied trajectory whose re-projection failed");
+  LastError = why;
+  return rc == LSA_E_CAPACITY ? LSA_OK : rc;
 }
 
 int SlamCore::DenseReady(const char* who)
@@ -116,6 +164,15 @@ int SlamCore::GetDenseMap(int minFrames, lsa_point_t* pts, lsa_dense_voxel_t* vo
   return n < 0 ? Fail(n, "lsa_dense_map_get") : n;
 }
 
+int SlamCore::GetDenseMapSources(int minFrames, int* out, int capacity)
+{
+  if (const int rc = DenseReady("GetDenseMapSources"); rc < 0) return rc;
+  if (capacity < 0) { LastError = "GetDenseMapSources: bad argument"; return LSA_E_ARG; }
+  if (!Dense) return 0;
+  const int n = lsa_dense_map_get_sources(Dense, minFrames, out, capacity);
+  return n < 0 ? Fail(n, "lsa_dense_map_get_sources") : n;
+}
+
 int SlamCore::SaveDenseMapToPCD(const std::string& path, int format, int minFrames)
 {
   if (const int rc = DenseReady("SaveDenseMapToPCD"); rc < 0) return rc;
@@ -133,3 +190,19 @@ int SlamCore::ClearDenseMap()
 
 }  // namespace host
 }  // namespace lsa
+
+// D_i = new_i * inverse(old_i) with the rigid inverse (R^T, -R^T t), in double: what moves a point placed under old_i to
+// where new_i places it.  The pipeline's own numbers, for the callers and tests that hold lsa_dense_map_reproject to them.
+extern "C" int lsa_pose_corrections(const double* old16, const double* new16, int n, double* out16)
+{
+  if (!old16 || !new16 || !out16 || n < 0) return LSA_E_ARG;
+  for (int i = 0; i < n; ++i)
+  {
+    lsa::host::Pose a, b;
+    std::memcpy(a.m, old16 + 16 * static_cast<size_t>(i), sizeof(a.m));
+    std::memcpy(b.m, new16 + 16 * static_cast<size_t>(i), sizeof(b.m));
+    const lsa::host::Pose d = b * lsa::host::Inverse(a);
+    std::memcpy(out16 + 16 * static_cast<size_t>(i), d.m, sizeof(d.m));
+  }
+  return LSA_OK;
+}

@@ -116,9 +116,16 @@ int SlamCore::SetTrajectoryAndRebuildMaps(const double* poses17, int n)
     std::memcpy(&poses[16 * static_cast<size_t>(i)], poses17 + 17 * static_cast<size_t>(i), 16 * sizeof(double));
     times[i] = poses17[17 * static_cast<size_t>(i) + 16];
   }
+  // "DenseMapOnTrajectory" 1: the dense map's corrections, against the logged poses while they still stand
+  std::vector<double> denseCorrections;
+  int denseFirstOrdinal = 0;
+  const bool reproject = DenseCorrections(poses.data(), n, denseCorrections, &denseFirstOrdinal);
   // the map workers and the look-ahead are waited for, then what Reset(false) does (Slam.cxx:408)
-  Reset(false);
+  Reset(false, reproject);
   for (int i = 0; i < n; ++i) std::memcpy(LogTrajectory[i].pose.m, &poses[16 * static_cast<size_t>(i)], 16 * sizeof(double));
+  // (before the replay: whatever fails behind it, the dense map stands under the poses the log now holds, or is empty)
+  const int denseRc = reproject ? ReprojectDenseMap(denseCorrections, denseFirstOrdinal) : LSA_OK;
+  const std::string denseError = LastError;
   const unsigned mask = UsedTypesMask();
   float mn[3][3], mx[3][3];
   const int undistort = Undistortion != UNDISTORTION_NONE ? 1 : 0;
@@ -144,7 +151,9 @@ int SlamCore::SetTrajectoryAndRebuildMaps(const double* poses17, int n)
   }
   std::memcpy(Tworld.m, &poses[16 * static_cast<size_t>(n - 1)], 16 * sizeof(double));
   std::memcpy(PreviousTworld.m, &poses[16 * static_cast<size_t>(n - 2)], 16 * sizeof(double));
-  return LSA_OK;
+  // the trajectory is applied; a re-projection that failed for another reason than memory is the call's answer (map cleared)
+  if (denseRc < 0) LastError = denseError;
+  return denseRc;
 }
 
 // ---- place recognition: which logged frame looks like this one (descriptors of the keypoint log, lsa_place.hip) -------------

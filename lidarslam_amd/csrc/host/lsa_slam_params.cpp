@@ -143,7 +143,7 @@ int SlamCore::SetParamValue(const std::string& name, double v)
   {
     if (!(v > 0.) || !(v < 1e9)) { LastError = "DenseMapLeafSize: a positive length"; return LSA_E_ARG; }
     // the voxels of a map made under another leaf size mean nothing under this one: the next insertion makes a new map
-    if (Dense && v != DenseMapLeafSize) { lsa_dense_map_destroy(Dense); Dense = nullptr; DenseFrames = 0; }
+    if (Dense && v != DenseMapLeafSize) { lsa_dense_map_destroy(Dense); Dense = nullptr; DenseFrames = 0; DenseTimes.clear(); }
     DenseMapLeafSize = v;
     return LSA_OK;
   }
@@ -152,6 +152,12 @@ int SlamCore::SetParamValue(const std::string& name, double v)
     if (!(v >= 0.)) { LastError = "DenseMapMaxBytes: >= 0 (0: no limit)"; return LSA_E_ARG; }
     DenseMapMaxBytes = v;
     if (Dense) lsa_dense_map_set(Dense, "MaxBytes", v);
+    return LSA_OK;
+  }
+  if (name == "DenseMapOnTrajectory")
+  {
+    if (!(v == 0. || v == 1.)) { LastError = "DenseMapOnTrajectory: 0 an applied trajectory clears the dense map, 1 it re-projects it"; return LSA_E_ARG; }
+    DenseMapOnTrajectory = static_cast<int>(v);
     return LSA_OK;
   }
   if (name == "OrderedMaps")
@@ -234,6 +240,10 @@ int SlamCore::GetParam(const std::string& name, double* v) const
   if (name == "DenseMapRefusedFrames") { *v = DenseRefused; return LSA_OK; }
   if (name == "DenseMapClears") { *v = DenseClears; return LSA_OK; }
   if (name == "DenseMapFrames") { *v = DenseFrames; return LSA_OK; }
+  if (name == "DenseMapOnTrajectory") { *v = DenseMapOnTrajectory; return LSA_OK; }
+  if (name == "DenseMapReprojections") { *v = DenseReprojections; return LSA_OK; }
+  if (name == "DenseMapDropped") { *v = Dense ? lsa_dense_map_get_param(Dense, "Dropped") : 0.; return LSA_OK; }
+  if (name == "DenseMapReprojectSeconds") { *v = Dense ? lsa_dense_map_get_param(Dense, "ReprojectSeconds") : 0.; return LSA_OK; }
   if (name == "DenseMapRehashes") { *v = Dense ? lsa_dense_map_get_param(Dense, "Rehashes") : 0.; return LSA_OK; }
   if (name == "DenseMapExportSeconds") { *v = Dense ? lsa_dense_map_get_param(Dense, "ExportSeconds") : 0.; return LSA_OK; }
   return LSA_E_ARG;

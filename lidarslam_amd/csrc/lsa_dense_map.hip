@@ -19,6 +19,14 @@
 // table of twice the size on the same stream; the old table goes to the context's graveyard.
 // Export (not on the frame path): lsa_compact.h's stable compaction of the slots that pass min_frames, rocprim's radix sort
 // by key, a gather.
+// Beside the slots, source[capacity]: the ordinal of the call whose point the voxel holds (the 64-byte slot is full).  It is
+// what lets a corrected trajectory move the map (lsa_dense_map_reproject, not on the frame path either): every voxel's point
+// under the correction of the frame that measured it, re-keyed into a fresh table of the same capacity, voxels that meet
+// merged -- three launches, one thread per old slot, under the same rules as the insertion:
+//   k_dense_move    moves the point, finds or claims its slot in the new table, adds count and frames, folds first / last
+//                   and the candidate word (intensity code << 32) | ~ordered(source) in with atomics, notes the new slot
+//   k_dense_elect   the old slots whose word the candidate names atomicMin their old key: ties on intensity and source
+//   k_dense_settle  the old slot named by both writes the moved point and its source, caps frames, disarms the word
 #include <cstring>
 #include <rocprim/device/device_radix_sort.hpp>
 #include <chrono>
@@ -59,11 +67,13 @@ static_assert(sizeof(Slot) == 64, "a slot is one 64-byte record");
 struct Table
 {
   Slot* slots;
+  int* source;    // [capacity] the ordinal of the call whose point the slot holds
   unsigned mask;  // capacity - 1
   int stress;     // "ProbeStress": every key's home slot is 0
 };
-// device words of a map: [0] occupied slots, [1] error (a probe sequence ran out), [2] points skipped
-enum { kStatOccupied = 0, kStatError = 1, kStatSkipped = 2, kStatWords = 4 };
+// device words of a map: [0] occupied slots, [1] error (a probe sequence ran out), [2] points skipped, [3] voxels the
+// re-projection in flight dropped
+enum { kStatOccupied = 0, kStatError = 1, kStatSkipped = 2, kStatDropped = 3, kStatWords = 4 };
 
 // the order-preserving code of an intensity: f2ou, and 0 -- below -inf -- for a NaN
 __device__ __forceinline__ unsigned intensity_code(float v) { return v == v ? f2ou(v) : 0u; }
@@ -173,19 +183,21 @@ __global__ __launch_bounds__(256) void k_dense_apply(const float4* __restrict__ 
   if (S.frames == 0u)
   {
     S.a = a; S.b = b;
+    t.source[s] = frame;
     S.frames = 1u;
     S.first = S.last = frame;
   }
   else
   {
     if (S.last != frame) { S.frames += 1u; S.last = frame; }
-    if ((unsigned)(w >> 32) > intensity_code(S.b.z)) { S.a = a; S.b = b; }  // strictly greater: the earlier frame keeps a tie
+    if ((unsigned)(w >> 32) > intensity_code(S.b.z)) { S.a = a; S.b = b; t.source[s] = frame; }  // strictly greater: the earlier frame keeps a tie
   }
   S.cand = 0ull;
 }
 
 // every occupied slot of the old table into the new one (zeroed); keys are unique, so a slot is only ever claimed from empty
-__global__ __launch_bounds__(256) void k_dense_rehash(const Slot* __restrict__ old, unsigned old_capacity, Table t, u64* __restrict__ stat)
+__global__ __launch_bounds__(256) void k_dense_rehash(const Slot* __restrict__ old, const int* __restrict__ old_source, unsigned old_capacity, Table t,
+                                                      u64* __restrict__ stat)
 {
   const unsigned i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= old_capacity) return;
@@ -198,9 +210,127 @@ __global__ __launch_bounds__(256) void k_dense_rehash(const Slot* __restrict__ o
     Slot& S = t.slots[s];
     S.a = o.a; S.b = o.b;
     S.count = o.count; S.frames = o.frames; S.first = o.first; S.last = o.last;
+    t.source[s] = old_source[i];
     return;
   }
   atomicOr(&stat[kStatError], 1ull);
+}
+
+// ---- re-projection under a corrected trajectory --------------------------------------------------------------------------
+// The scratch of one re-projection, [capacity] each: pick (armed ~0: the smallest old key among the winners of a new voxel),
+// frames (the sum of the merged voxels' frames, in 64 bits), to (the new slot of every old one; -1: empty, dropped, no slot).
+struct Reproject
+{
+  const Slot* old;
+  const int* old_source;
+  unsigned old_capacity;
+  const double* corrections;  // [n][16] row-major; entry j belongs to ordinal first_frame + j
+  int first_frame, n;
+  double leaf;
+  u64* pick;
+  u64* frames;
+  int* to;
+};
+
+// first_frame / last_frame of a slot of the new table are folded with atomicMax on words under which the zeroed slot is the
+// identity: a larger last_frame has a larger word, a smaller first_frame has a larger word.  k_dense_settle decodes them.
+__device__ __forceinline__ unsigned last_word(int v) { return (unsigned)v ^ 0x80000000u; }
+__device__ __forceinline__ unsigned first_word(int v) { return ~((unsigned)v ^ 0x80000000u); }
+// largest intensity code, then the smaller source (signed)
+__device__ __forceinline__ u64 merge_word(const float4& b, int source) { return ((u64)intensity_code(b.z) << 32) | (u64)first_word(source); }
+
+// rigid_apply under the correction of the frame that measured the point, narrowed to float; w is kept
+__device__ __forceinline__ float4 reprojected(const Reproject& r, const float4& a, int source)
+{
+  long long c = (long long)source - (long long)r.first_frame;
+  c = c < 0 ? 0 : (c > (long long)r.n - 1 ? (long long)r.n - 1 : c);
+  const double* T = r.corrections + 16 * c;
+  Rigid g;
+  for (int row = 0; row < 3; ++row)
+  {
+    for (int col = 0; col < 3; ++col) g.R[3 * row + col] = T[4 * row + col];
+    g.t[row] = T[4 * row + 3];
+  }
+  double ox, oy, oz;
+  rigid_apply(g, (double)a.x, (double)a.y, (double)a.z, ox, oy, oz);
+  return make_float4((float)ox, (float)oy, (float)oz, a.w);
+}
+
+// launch 1: every occupied old slot moves its point, finds or claims the voxel it falls into, and folds its record in
+__global__ __launch_bounds__(256) void k_dense_move(const Reproject r, Table t, u64* __restrict__ stat)
+{
+  const unsigned i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= r.old_capacity) return;
+  const Slot& o = r.old[i];
+  if (o.key == 0ull) { r.to[i] = -1; return; }
+  const int source = r.old_source[i];
+  const float4 a = reprojected(r, o.a, source);
+  u64 key = 0;
+  if (!voxel_key(a, r.leaf, key))
+  {
+    atomicAdd(&stat[kStatDropped], 1ull);
+    r.to[i] = -1;
+    return;
+  }
+  const int s = find_or_claim(t, key, stat);
+  r.to[i] = s;
+  if (s < 0)
+  {
+    atomicOr(&stat[kStatError], 1ull);
+    return;
+  }
+  Slot& S = t.slots[s];
+  atomicAdd(&S.count, o.count);
+  atomicAdd(&r.frames[s], (u64)o.frames);
+  atomicMax(reinterpret_cast<unsigned*>(&S.first), first_word(o.first));
+  atomicMax(reinterpret_cast<unsigned*>(&S.last), last_word(o.last));
+  atomicMax(&S.cand, merge_word(o.b, source));
+}
+
+// launch 2: among the old voxels the candidate word names -- equal intensity code and source -- the smallest old key
+__global__ __launch_bounds__(256) void k_dense_elect(const Reproject r, Table t)
+{
+  const unsigned i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= r.old_capacity) return;
+  const int s = r.to[i];
+  if (s < 0) return;
+  const Slot& o = r.old[i];
+  const u64 w = __hip_atomic_load(&t.slots[s].cand, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  if (w == merge_word(o.b, r.old_source[i])) atomicMin(&r.pick[s], o.key);
+}
+
+// launch 3: the old voxel named by both gives the new one its point and source and finishes its record; one thread
+// publishes the counts as k_dense_apply does ([3]: the voxels dropped)
+__global__ __launch_bounds__(256) void k_dense_settle(const Reproject r, Table t, const u64* __restrict__ stat, u64* __restrict__ host_words, unsigned serial)
+{
+  const unsigned i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i == 0)
+  {
+    __hip_atomic_store(&host_words[1], stat[kStatError], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    __hip_atomic_store(&host_words[2], stat[kStatSkipped], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    __hip_atomic_store(&host_words[3], stat[kStatDropped], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    __hip_atomic_store(&host_words[0], ((u64)serial << 32) | (stat[kStatOccupied] & 0xffffffffull), __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+  }
+  if (i >= r.old_capacity) return;
+  const int s = r.to[i];
+  if (s < 0) return;
+  const Slot& o = r.old[i];
+  const int source = r.old_source[i];
+  Slot& S = t.slots[s];
+  // (only this voxel's winner writes its slot during this launch.  A loser may read the 0 the winner leaves in the word and
+  //  find it equal to its own; the pick, which nobody writes here, holds a key that is not the loser's: old keys are unique)
+  const u64 w = __hip_atomic_load(&S.cand, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  if (w != merge_word(o.b, source) || r.pick[s] != o.key) return;
+  S.a = reprojected(r, o.a, source);
+  S.b = o.b;
+  t.source[s] = source;
+  const unsigned fw = __builtin_bit_cast(unsigned, S.first), lw = __builtin_bit_cast(unsigned, S.last);
+  const int first = (int)(~fw ^ 0x80000000u), last = (int)(lw ^ 0x80000000u);
+  S.first = first;
+  S.last = last;
+  const u64 span = (u64)((long long)last - (long long)first + 1ll), sum = r.frames[s];
+  S.frames = (unsigned)(sum < span ? sum : span);
+  S.cand = 0ull;
 }
 
 // ---- export -------------------------------------------------------------------------------------------------------------
@@ -221,12 +351,14 @@ struct ExportEmit
     index[pos] = (unsigned)i;
   }
 };
-__global__ __launch_bounds__(256) void k_dense_gather(const Slot* __restrict__ slots, const u64* __restrict__ keys, const unsigned* __restrict__ index, int n,
-                                                      float4* __restrict__ pts, lsa_dense_voxel_t* __restrict__ voxels)
+__global__ __launch_bounds__(256) void k_dense_gather(const Slot* __restrict__ slots, const int* __restrict__ source, const u64* __restrict__ keys,
+                                                      const unsigned* __restrict__ index, int n, float4* __restrict__ pts, lsa_dense_voxel_t* __restrict__ voxels,
+                                                      int* __restrict__ sources)
 {
   const int j = blockIdx.x * blockDim.x + threadIdx.x;
   if (j >= n) return;
   const Slot& S = slots[index[j]];
+  sources[j] = source[index[j]];
   pts[2 * (size_t)j] = S.a;
   pts[2 * (size_t)j + 1] = S.b;
   lsa_dense_voxel_t v;
@@ -242,6 +374,7 @@ struct lsa_dense_map
   hipStream_t stream = nullptr;  // the context's look-ahead stream
   double leaf = 0.1;
   Slot* slots = nullptr;
+  int* source = nullptr;  // [capacity], beside the slots
   unsigned capacity = 0;
   unsigned initial_capacity = 1u << 16;
   size_t max_bytes = kDefaultMaxBytes;
@@ -265,13 +398,17 @@ struct lsa_dense_map
   int* totals = nullptr;  // device, 2 ints: the total and the compaction's aside slot
   u64* keys[2] = {nullptr, nullptr}; unsigned* index[2] = {nullptr, nullptr}; int keys_cap = 0;
   void* sort_tmp = nullptr; size_t sort_tmp_cap = 0;
-  lsa_point_t* out_pts = nullptr; lsa_dense_voxel_t* out_vox = nullptr; int out_cap = 0;
+  lsa_point_t* out_pts = nullptr; lsa_dense_voxel_t* out_vox = nullptr; int* out_src = nullptr; int out_cap = 0;
   double export_seconds = 0.;
+  // re-projections (lsa_dense_map_reproject)
+  int reprojections = 0;
+  long long dropped = 0;  // voxels, since the last clear
+  double reproject_seconds = 0.;
 };
 
 namespace
 {
-Table table_of(const lsa_dense_map* dm) { return Table{dm->slots, dm->capacity - 1u, dm->stress}; }
+Table table_of(const lsa_dense_map* dm) { return Table{dm->slots, dm->source, dm->capacity - 1u, dm->stress}; }
 
 long long occupied_bound(lsa_dense_map* dm)
 {
@@ -288,6 +425,34 @@ long long occupied_bound(lsa_dense_map* dm)
     }
   }
   return (long long)dm->known + dm->pending_sum;
+}
+
+// a zeroed table of cap slots with its source array, zeroed behind what the stream holds; LSA_E_CAPACITY without memory
+int fresh_table(lsa_dense_map* dm, unsigned cap, Slot** slots, int** source, const char* who, const char* consequence)
+{
+  lsa_ctx* ctx = dm->ctx;
+  const size_t bytes = (size_t)cap * sizeof(Slot), source_bytes = (size_t)cap * sizeof(int);
+  *slots = nullptr;
+  *source = nullptr;
+  if (hipMalloc((void**)slots, bytes) != hipSuccess || hipMalloc((void**)source, source_bytes) != hipSuccess)
+  {
+    (void)hipGetLastError();
+    if (*slots) (void)hipFree(*slots);
+    *slots = nullptr;
+    return ctx->fail(LSA_E_CAPACITY, std::string(who) + ": no device memory for a table of " + std::to_string(bytes + source_bytes) + " bytes; " + consequence);
+  }
+  hipError_t e = hipMemsetAsync(*slots, 0, bytes, dm->stream);
+  if (e == hipSuccess) e = hipMemsetAsync(*source, 0, source_bytes, dm->stream);
+  if (e != hipSuccess)
+  {
+    (void)hipStreamSynchronize(dm->stream);
+    (void)hipFree(*slots);
+    (void)hipFree(*source);
+    *slots = nullptr;
+    *source = nullptr;
+    return ctx->fail(LSA_E_HIP, std::string(who) + ": hipMemsetAsync: " + hipGetErrorString(e));
+  }
+  return LSA_OK;
 }
 
 // the table with room for n more points: (bound of occupied slots) + n <= capacity / 2, by rehashing into a larger one
@@ -310,26 +475,21 @@ int make_room(lsa_dense_map* dm, long long n, const char* who)
     return ctx->fail(LSA_E_CAPACITY, std::string(who) + ": a table of " + std::to_string(bytes) + " bytes for " + std::to_string(need) +
                                          " voxels at most is over MaxBytes = " + std::to_string(dm->max_bytes) + "; nothing was inserted");
   Slot* fresh = nullptr;
-  if (hipMalloc((void**)&fresh, bytes) != hipSuccess)
-  {
-    (void)hipGetLastError();
-    return ctx->fail(LSA_E_CAPACITY, std::string(who) + ": no device memory for a table of " + std::to_string(bytes) + " bytes; nothing was inserted");
-  }
-  if (const hipError_t e = hipMemsetAsync(fresh, 0, bytes, dm->stream); e != hipSuccess)
-  {
-    (void)hipFree(fresh);
-    return ctx->fail(LSA_E_HIP, std::string(who) + ": hipMemsetAsync: " + hipGetErrorString(e));
-  }
+  int* fresh_source = nullptr;
+  if (const int rc = fresh_table(dm, cap, &fresh, &fresh_source, who, "nothing was inserted")) return rc;
   Slot* old = dm->slots;
+  int* old_source = dm->source;
   const unsigned old_capacity = dm->capacity;
   dm->slots = fresh;
+  dm->source = fresh_source;
   dm->capacity = cap;
   if (old)
   {
-    ProfScope ps(ctx, "dense_rehash", (double)old_capacity * sizeof(Slot) * 2, dm->stream);
-    hipLaunchKernelGGL(k_dense_rehash, dim3((old_capacity + 255) / 256), dim3(256), 0, dm->stream, old, old_capacity, table_of(dm), dm->stat);
+    ProfScope ps(ctx, "dense_rehash", (double)old_capacity * (sizeof(Slot) + sizeof(int)) * 2, dm->stream);
+    hipLaunchKernelGGL(k_dense_rehash, dim3((old_capacity + 255) / 256), dim3(256), 0, dm->stream, old, old_source, old_capacity, table_of(dm), dm->stat);
     dm->rehashes++;
     retire_dev(ctx, old);  // launches in flight keep it; freed by lsa_collect_garbage
+    retire_dev(ctx, old_source);
   }
   return LSA_OK;
 }
@@ -370,7 +530,7 @@ int settle(lsa_dense_map* dm, const char* who)
   return LSA_OK;
 }
 
-// the voxels with frames >= min_frames in ascending key order, left in dm->out_pts / out_vox; returns their number
+// the voxels with frames >= min_frames in ascending key order, left in dm->out_pts / out_vox / out_src; returns their number
 int export_sorted(lsa_dense_map* dm, int min_frames, const char* who)
 {
   lsa_ctx* ctx = dm->ctx;
@@ -415,14 +575,16 @@ int export_sorted(lsa_dense_map* dm, int min_frames, const char* who)
   {
     retire_dev(ctx, dm->out_pts);
     retire_dev(ctx, dm->out_vox);
-    dm->out_pts = nullptr; dm->out_vox = nullptr; dm->out_cap = 0;
+    retire_dev(ctx, dm->out_src);
+    dm->out_pts = nullptr; dm->out_vox = nullptr; dm->out_src = nullptr; dm->out_cap = 0;
     const size_t want = (size_t)kept + (size_t)kept / 2;
     LSA_HIP(ctx, hipMalloc((void**)&dm->out_pts, want * sizeof(lsa_point_t)));
     LSA_HIP(ctx, hipMalloc((void**)&dm->out_vox, want * sizeof(lsa_dense_voxel_t)));
+    LSA_HIP(ctx, hipMalloc((void**)&dm->out_src, want * sizeof(int)));
     dm->out_cap = (int)want;
   }
-  hipLaunchKernelGGL(k_dense_gather, dim3((kept + 255) / 256), dim3(256), 0, dm->stream, slots, dm->keys[1], dm->index[1], kept, reinterpret_cast<float4*>(dm->out_pts),
-                     dm->out_vox);
+  hipLaunchKernelGGL(k_dense_gather, dim3((kept + 255) / 256), dim3(256), 0, dm->stream, slots, dm->source, dm->keys[1], dm->index[1], kept,
+                     reinterpret_cast<float4*>(dm->out_pts), dm->out_vox, dm->out_src);
   return kept;
 }
 
@@ -464,9 +626,9 @@ void lsa_dense_map_destroy(lsa_dense_map* dm)
   (void)hipSetDevice(dm->ctx->device);
   if (dm->stream) (void)hipStreamSynchronize(dm->stream);
   auto fr = [](void* p) { if (p) (void)hipFree(p); };
-  fr(dm->slots); fr(dm->stat); fr(dm->slot_of); fr(dm->staged); fr(dm->chunks); fr(dm->totals);
+  fr(dm->slots); fr(dm->source); fr(dm->stat); fr(dm->slot_of); fr(dm->staged); fr(dm->chunks); fr(dm->totals);
   for (int b = 0; b < 2; ++b) { fr(dm->keys[b]); fr(dm->index[b]); }
-  fr(dm->sort_tmp); fr(dm->out_pts); fr(dm->out_vox);
+  fr(dm->sort_tmp); fr(dm->out_pts); fr(dm->out_vox); fr(dm->out_src);
   if (dm->host_words) (void)hipHostFree(dm->host_words);
   if (dm->ev_frame) (void)hipEventDestroy(dm->ev_frame);
   delete dm;
@@ -517,6 +679,9 @@ double lsa_dense_map_get_param(lsa_dense_map* dm, const char* name)
   if (n == "Capacity") return dm->capacity;
   if (n == "Rehashes") return dm->rehashes;
   if (n == "ExportSeconds") return dm->export_seconds;
+  if (n == "Reprojections") return dm->reprojections;
+  if (n == "Dropped") return (double)dm->dropped;
+  if (n == "ReprojectSeconds") return dm->reproject_seconds;
   return -1.;
 }
 
@@ -591,7 +756,7 @@ long long lsa_dense_map_skipped(lsa_dense_map* dm)
 long long lsa_dense_map_bytes(const lsa_dense_map* dm)
 {
   if (!dm) return LSA_E_ARG;
-  return (long long)dm->capacity * (long long)sizeof(Slot) + (long long)dm->slot_cap * (long long)sizeof(int);
+  return (long long)dm->capacity * (long long)(sizeof(Slot) + sizeof(int)) + (long long)dm->slot_cap * (long long)sizeof(int);
 }
 
 int lsa_dense_map_get(lsa_dense_map* dm, int min_frames, lsa_point_t* pts, lsa_dense_voxel_t* voxels, int capacity)
@@ -610,12 +775,126 @@ int lsa_dense_map_get(lsa_dense_map* dm, int min_frames, lsa_point_t* pts, lsa_d
   return kept;
 }
 
+int lsa_dense_map_get_sources(lsa_dense_map* dm, int min_frames, int* out, int capacity)
+{
+  if (!dm) return LSA_E_ARG;
+  lsa_ctx* ctx = dm->ctx;
+  if (capacity < 0) return ctx->fail(LSA_E_ARG, "lsa_dense_map_get_sources: bad argument");
+  const int kept = export_sorted(dm, min_frames, "lsa_dense_map_get_sources");
+  if (kept <= 0) return kept;
+  const int n = std::min(kept, capacity);
+  if (n > 0 && out) LSA_HIP(ctx, hipMemcpyAsync(out, dm->out_src, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, dm->stream));
+  LSA_HIP(ctx, hipStreamSynchronize(dm->stream));
+  return kept;
+}
+
+int lsa_dense_map_reproject(lsa_dense_map* dm, const double* corrections16, int first_frame, int n, long long* dropped)
+{
+  if (!dm) return LSA_E_ARG;
+  lsa_ctx* ctx = dm->ctx;
+  const char* who = "lsa_dense_map_reproject";
+  if (!corrections16 || !dropped || n < 1) return ctx->fail(LSA_E_ARG, std::string(who) + ": bad argument");
+  int rc = settle(dm, who);
+  if (rc) return rc;
+  const double t0 = now_seconds();
+  *dropped = 0;
+  if (!dm->slots || occupied_bound(dm) <= 0)  // exact after settle: an empty map has nothing to move
+  {
+    dm->reprojections++;
+    dm->reproject_seconds = now_seconds() - t0;
+    return LSA_OK;
+  }
+  const unsigned cap = dm->capacity;
+  // everything that needs memory comes first: a refusal leaves the map as it was
+  const size_t corrections_bytes = (size_t)n * 16 * sizeof(double);
+  const size_t scratch_bytes = (size_t)cap * (2 * sizeof(u64) + sizeof(int));  // pick, frames, to
+  double* corrections = nullptr;
+  unsigned char* scratch = nullptr;
+  if (hipMalloc((void**)&corrections, corrections_bytes) != hipSuccess || hipMalloc((void**)&scratch, scratch_bytes) != hipSuccess)
+  {
+    (void)hipGetLastError();
+    if (corrections) (void)hipFree(corrections);
+    return ctx->fail(LSA_E_CAPACITY, std::string(who) + ": no device memory for " + std::to_string(corrections_bytes + scratch_bytes) + " bytes of corrections and scratch; the map is as it was");
+  }
+  Slot* fresh = nullptr;
+  int* fresh_source = nullptr;
+  rc = fresh_table(dm, cap, &fresh, &fresh_source, who, "the map is as it was");
+  if (rc)
+  {
+    (void)hipFree(corrections);
+    (void)hipFree(scratch);
+    return rc;
+  }
+  Reproject r;
+  r.old = dm->slots;
+  r.old_source = dm->source;
+  r.old_capacity = cap;
+  r.corrections = corrections;
+  r.first_frame = first_frame;
+  r.n = n;
+  r.leaf = dm->leaf;
+  r.pick = reinterpret_cast<u64*>(scratch);
+  r.frames = r.pick + cap;
+  r.to = reinterpret_cast<int*>(r.frames + cap);
+  // from here on the old table belongs to the graveyard and the new one is the map's, whatever a launch answers
+  Slot* old = dm->slots;
+  int* old_source = dm->source;
+  dm->slots = fresh;
+  dm->source = fresh_source;
+  const Table t = table_of(dm);
+  const unsigned serial = dm->next_serial++;
+  const dim3 grid((cap + 255) / 256);
+  hipError_t e = hipMemcpyAsync(corrections, corrections16, corrections_bytes, hipMemcpyHostToDevice, dm->stream);
+  if (e == hipSuccess) e = hipMemsetAsync(r.pick, 0xff, (size_t)cap * sizeof(u64), dm->stream);
+  if (e == hipSuccess) e = hipMemsetAsync(r.frames, 0, (size_t)cap * sizeof(u64), dm->stream);
+  // the new table counts its own slots; error and skipped go on
+  if (e == hipSuccess) e = hipMemsetAsync(&dm->stat[kStatOccupied], 0, sizeof(u64), dm->stream);
+  if (e == hipSuccess) e = hipMemsetAsync(&dm->stat[kStatDropped], 0, sizeof(u64), dm->stream);
+  if (e == hipSuccess)
+  {
+    {
+      // per old slot 4 B of `to`; per voxel 68 B read, the correction, 8 B of key CAS and 28 B of atomic words
+      ProfScope ps(ctx, "dense_move", (double)cap * 4 + (double)dm->known * 104, dm->stream);
+      hipLaunchKernelGGL(k_dense_move, grid, dim3(256), 0, dm->stream, r, t, dm->stat);
+    }
+    {
+      ProfScope ps(ctx, "dense_elect", (double)cap * 4 + (double)dm->known * 84, dm->stream);
+      hipLaunchKernelGGL(k_dense_elect, grid, dim3(256), 0, dm->stream, r, t);
+    }
+    {
+      ProfScope ps(ctx, "dense_settle", (double)cap * 4 + (double)dm->known * 160, dm->stream);
+      hipLaunchKernelGGL(k_dense_settle, grid, dim3(256), 0, dm->stream, r, t, dm->stat, dm->host_words, serial);
+    }
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipStreamSynchronize(dm->stream);  // the count of the dropped is the call's answer
+  retire_dev(ctx, old);
+  retire_dev(ctx, old_source);
+  retire_dev(ctx, corrections);
+  retire_dev(ctx, scratch);
+  if (e != hipSuccess) return ctx->fail(LSA_E_HIP, std::string(who) + ": " + hipGetErrorString(e));
+  // everything enqueued has been published: the bound of the occupied slots is the new table's count
+  const u64 w = __atomic_load_n(&dm->host_words[0], __ATOMIC_ACQUIRE);
+  dm->seen_serial = serial;
+  dm->known = (unsigned)w;
+  dm->pending.clear();
+  dm->pending_sum = 0;
+  *dropped = (long long)__atomic_load_n(&dm->host_words[3], __ATOMIC_ACQUIRE);
+  dm->dropped += *dropped;
+  dm->reprojections++;
+  dm->reproject_seconds = now_seconds() - t0;
+  if (__atomic_load_n(&dm->host_words[1], __ATOMIC_ACQUIRE) != 0ull)
+    return ctx->fail(LSA_E_STATE, std::string(who) + ": a probe sequence ran through the whole table (the map is incomplete; lsa_dense_map_clear starts again)");
+  return LSA_OK;
+}
+
 int lsa_dense_map_clear(lsa_dense_map* dm)
 {
   if (!dm) return LSA_E_ARG;
   lsa_ctx* ctx = dm->ctx;
   LSA_HIP(ctx, hipSetDevice(ctx->device));
   if (dm->slots) LSA_HIP(ctx, hipMemsetAsync(dm->slots, 0, (size_t)dm->capacity * sizeof(Slot), dm->stream));
+  if (dm->source) LSA_HIP(ctx, hipMemsetAsync(dm->source, 0, (size_t)dm->capacity * sizeof(int), dm->stream));
   LSA_HIP(ctx, hipMemsetAsync(dm->stat, 0, kStatWords * sizeof(u64), dm->stream));
   // what insertions before the clear still publish is older than the epoch and ignored; the error word goes with them
   LSA_HIP(ctx, hipStreamSynchronize(dm->stream));
@@ -626,6 +905,7 @@ int lsa_dense_map_clear(lsa_dense_map* dm)
   dm->pending.clear();
   dm->pending_sum = 0;
   dm->last_frame = INT32_MIN;
+  dm->dropped = 0;
   return LSA_OK;
 }
 

@@ -774,6 +774,26 @@ public:
     this->LastError = n < 0 ? std::string("GetDenseMap: ") + lsa_slam_last_error(this->Handle) : std::string();
     return pc;
   }
+  // What an applied trajectory (SetTrajectoryAndRebuildMaps, the pose-graph calls and CloseLoops with apply) does to the dense
+  // map.  0, the default: it is cleared.  1: it is re-projected on the device -- one point per voxel, moved by new * inverse(old)
+  // of the logged pose of the frame that measured it; not a rebuild from raw frames, so two neighbouring surface voxels may
+  // merge and the voxel between them stay empty until it is seen again.  Reset, ClearMaps and ClearDenseMap clear either way.
+  void SetDenseMapOnTrajectory(int mode) { this->SetParam("DenseMapOnTrajectory", mode); }
+  int GetDenseMapOnTrajectory() const { return static_cast<int>(this->GetParam("DenseMapOnTrajectory")); }
+  // per point of GetDenseMap(minFrames), in its order: the ordinal (count of inserted calls) of the frame that measured it
+  std::vector<int> GetDenseMapSources(int minFrames = 1)
+  {
+    std::vector<int> out;
+    int n = lsa_slam_dense_map_size(this->Handle);
+    if (n > 0)
+    {
+      out.resize(static_cast<std::size_t>(n));
+      n = lsa_slam_get_dense_map_sources(this->Handle, minFrames, out.data(), n);
+      out.resize(static_cast<std::size_t>(std::max(n, 0)));
+    }
+    this->LastError = n < 0 ? std::string("GetDenseMapSources: ") + lsa_slam_last_error(this->Handle) : std::string();
+    return out;
+  }
   // returns the points written (0 and no file for an empty map), negative on failure
   int SaveDenseMapToPCD(const std::string& path, PCDFormat pcdFormat = PCDFormat::BINARY_COMPRESSED, int minFrames = 1) const
   {

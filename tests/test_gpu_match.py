@@ -125,7 +125,7 @@ def test_matching_edge_cases(gpu_ctx, O, L, kps):
     # duplicated target points: exact distance ties are ordered by index
     dup = np.concatenate([prev[1], prev[1]])
     assert_match_equal(gpu_ctx, O, L, 1, cur[1], dup, ego, perturbed())
-    # collinear / coincident neighbourhoods (degenerate covariance)
+    # collinear / coincident neighbourhoods (degenerate covariance); by design, per branch and form: tests/test_gpu_model_branches.py
     line = prev[1][:200].copy()
     line["y"], line["z"] = 0, 0
     line["x"] = np.linspace(-5, 5, 200, dtype=np.float32)

@@ -1216,7 +1216,34 @@ int lsa_pcd_io_times(const lsa_ctx* ctx, double out[8]);
  *   or a NULL pointer, LSA_E_CAPACITY when the second table cannot be allocated: the map is untouched by either.
  *   lsa_dense_map_get_param answers "Reprojections", "Dropped" (voxels, since the last clear), "ReprojectSeconds" (the last).
  * - lsa_pose_corrections: out_i = new_i * inverse(old_i) for n poses (row-major 4x4, rigid inverse R^T, -R^T t, in double):
- *   the corrections the pipeline hands _reproject. */
+ *   the corrections the pipeline hands _reproject.
+ * - Free space (DenseMapHost.carve is the statement, and exact).  Beside `source` a voxel keeps `misses` (u32) and the last
+ *   ordinal that counted one.  _carve_points: every point with index % "CarveStride" == 0 casts a ray from its origin
+ *   (origins_xyz: n_origins = 1 or n float triples, world positions of the sensor) to the point, in double, without
+ *   contraction: d = p - o, len = sqrt((dx*dx + dy*dy) + dz*dz), t = min(len - "CarveMarginLeaves" * leaf, "CarveRange");
+ *   no ray when a coordinate is not finite, t is not > 0 or a start or end index is outside [-2^20, 2^20); e = o + d * (t /
+ *   len), i0 = floor(o / leaf), i1 = floor(e / leaf); per axis left = |i1 - i0|, step = sign(i1 - i0), tmax = ((i0 + (step >
+ *   0)) * leaf - o) / (e - o), tdelta = leaf / |e - o|; the ray visits i0 and then, left_x + left_y + left_z times, steps
+ *   along the axis of smallest tmax among those with steps left (ties x, y, z) and visits: a 6-connected path that ends in
+ *   i1.  A visited voxel that exists and whose last_frame and last counted ordinal both differ from `frame` takes one miss:
+ *   once an ordinal, whatever the rays and calls, none in an ordinal that hit it -- so insert every frame of an ordinal before
+ *   carving any.  Nothing depends on the order of the rays.  A carve makes, moves and removes no voxel and touches no point
+ *   or record.  `frame` must not be below the map's last ordinal, nor -2^31 (LSA_E_ARG), and becomes the last.  One launch,
+ *   one thread a ray, behind the insertions on the same stream; nothing is waited for.  _carve_frame: the context's current
+ *   frame, fused as _insert_frame: the point is lsa_transform_frame_at's, the origin what that call makes of the frame's own
+ *   (0, 0, 0) at the point's time (lsa_transform_frame_origins_at hands those out, float xyz per frame point): under
+ *   undistortion every ray starts where the sensor was when it fired.  The frame's buffer is held until the carve has read it.
+ *   lsa_dense_map_set: "CarveMarginLeaves" (default 2), "CarveRange" (metres, default 30; LSA_E_ARG above 4096 leaves: the
+ *   bound of a ray's walk), "CarveStride" (default 1).  get_param: those, "Rays" (cast since the last clear), "Pruned"
+ *   (voxels, since the last clear), "Prunes", "CarveSeconds" (the host's, of the last call).  The misses live in an array of
+ *   8 B a slot made by the first carve (counted by _bytes, not by "MaxBytes"): a map never carved pays nothing.
+ * - _get_filtered, _get_sources_filtered, _get_misses, _save_pcd_filtered: as _get and its neighbours, of the voxels with
+ *   frames >= min_frames and, for max_miss_ratio >= 0, (double)misses <= max_miss_ratio * (double)frames; the calls without
+ *   a ratio are these with -1.  _prune removes the other voxels for good: a rehash of what passes into a zeroed table of the
+ *   smallest power-of-two capacity >= 64 with capacity / 2 >= the kept (the old one is freed by lsa_collect_garbage);
+ *   *removed and "Pruned" count them, `skipped` and "Dropped" do not.  LSA_E_CAPACITY, the map untouched, without memory for
+ *   the second table.  _reproject carries the state: merged voxels take the sum of the misses modulo 2^32 and the later
+ *   ordinal. */
 typedef struct lsa_dense_voxel_t
 {
   uint64_t key;
@@ -1242,6 +1269,14 @@ int lsa_dense_map_reproject(lsa_dense_map* dm, const double* corrections16, int 
 int lsa_pose_corrections(const double* old16, const double* new16, int n, double* out16);
 int lsa_dense_map_clear(lsa_dense_map* dm);
 int lsa_dense_map_save_pcd(lsa_dense_map* dm, const char* path, int format, int min_frames);
+int lsa_dense_map_carve_points(lsa_dense_map* dm, const lsa_point_t* pts, int n, const float* origins_xyz, int n_origins, int frame);
+int lsa_dense_map_carve_frame(lsa_dense_map* dm, int interpolate, const double H0[16], const double H1[16], double t0, double t1, double time_offset, int frame);
+int lsa_transform_frame_origins_at(lsa_ctx* ctx, int interpolate, const double H0[16], const double H1[16], double t0, double t1, double time_offset, float* xyz, int capacity);
+int lsa_dense_map_get_filtered(lsa_dense_map* dm, int min_frames, double max_miss_ratio, lsa_point_t* pts, lsa_dense_voxel_t* voxels, int capacity);
+int lsa_dense_map_get_sources_filtered(lsa_dense_map* dm, int min_frames, double max_miss_ratio, int32_t* out, int capacity);
+int lsa_dense_map_get_misses(lsa_dense_map* dm, int min_frames, double max_miss_ratio, uint32_t* out, int capacity);
+int lsa_dense_map_prune(lsa_dense_map* dm, int min_frames, double max_miss_ratio, long long* removed);
+int lsa_dense_map_save_pcd_filtered(lsa_dense_map* dm, const char* path, int format, int min_frames, double max_miss_ratio);
 /* The pipeline's dense map (lsa_slam_set_param "DenseMap": 0 off, the default, under which nothing whatever changes; 1 every
  * registered frame; 2 keyframes only; "DenseMapLeafSize", default 0.1; "DenseMapMaxBytes"; read-only "DenseMapVoxels",
  * "DenseMapBytes", "DenseMapSkipped", "DenseMapRefusedFrames", "DenseMapClears").  At the end of AddFrame(s) the frame or frames of the
@@ -1262,12 +1297,24 @@ int lsa_dense_map_save_pcd(lsa_dense_map* dm, const char* path, int format, int 
  * and mapping goes on with the next ordinal.  If the second table cannot be allocated the trajectory is applied all the same
  * and the map is cleared as under 0 ("DenseMapClears", the reason in lsa_slam_last_error).  Reset, ClearMaps,
  * lsa_slam_clear_dense_map and a changed leaf size clear under either value.  Read-only: "DenseMapReprojections",
- * "DenseMapDropped", "DenseMapReprojectSeconds".  _get_dense_map_sources: lsa_dense_map_get_sources of the pipeline's map. */
+ * "DenseMapDropped", "DenseMapReprojectSeconds".  _get_dense_map_sources: lsa_dense_map_get_sources of the pipeline's map.
+ * Free space: "DenseMapCarve" (default 0: nothing changes, not a launch; 1: on), "DenseMapCarveRange", "DenseMapCarveMarginLeaves",
+ * "DenseMapCarveStride" (lsa_dense_map_set's, same defaults); read-only "DenseMapRays", "DenseMapPruned".  With 1, once ALL device
+ * frames of the call are inserted, all of them are carved (lsa_dense_map_carve_frame) under the same poses and the same ordinal,
+ * so that a voxel the second LiDAR hit is not seen through by the first; a refused insertion carves nothing.  _filtered,
+ * _misses, _save_..._filtered and _prune_dense_map are the map's calls of those names; the state survives "DenseMapOnTrajectory"
+ * 1 and goes with everything that clears the map.  _get_registered_frame_origins: float xyz per point of
+ * lsa_slam_get_registered_frame, in its order: where the sensor stood when it measured the point -- the origins of the carve. */
 int lsa_slam_dense_map_size(lsa_slam* s);
 int lsa_slam_get_dense_map(lsa_slam* s, int min_frames, lsa_point_t* pts, lsa_dense_voxel_t* voxels, int capacity);
 int lsa_slam_get_dense_map_sources(lsa_slam* s, int min_frames, int32_t* out, int capacity);
 int lsa_slam_save_dense_map_pcd(lsa_slam* s, const char* path, int format, int min_frames);
 int lsa_slam_clear_dense_map(lsa_slam* s);
+int lsa_slam_get_dense_map_filtered(lsa_slam* s, int min_frames, double max_miss_ratio, lsa_point_t* pts, lsa_dense_voxel_t* voxels, int capacity);
+int lsa_slam_get_dense_map_misses(lsa_slam* s, int min_frames, double max_miss_ratio, uint32_t* out, int capacity);
+int lsa_slam_save_dense_map_pcd_filtered(lsa_slam* s, const char* path, int format, int min_frames, double max_miss_ratio);
+int lsa_slam_prune_dense_map(lsa_slam* s, int min_frames, double max_miss_ratio, long long* removed);
+int lsa_slam_get_registered_frame_origins(lsa_slam* s, float* xyz, int capacity);
 
 /* ------------------------------------------------------------------------- */
 /* The keypoint log (Slam::LogKeypoints, slam_lib/src/Slam.cxx:1225-1255) in the memory of the device, and its replay under

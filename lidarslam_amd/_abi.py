@@ -295,6 +295,19 @@ SIGNATURES = {
     "lsa_slam_get_dense_map": (i32, [vp, i32, vp, vp, i32]),
     "lsa_slam_save_dense_map_pcd": (i32, [vp, s, i32, i32]),
     "lsa_slam_clear_dense_map": (i32, [vp]),
+    "lsa_dense_map_carve_points": (i32, [vp, vp, i32, vp, i32, i32]),
+    "lsa_dense_map_carve_frame": (i32, [vp, i32, vp, vp, f64, f64, f64, i32]),
+    "lsa_transform_frame_origins_at": (i32, [vp, i32, vp, vp, f64, f64, f64, vp, i32]),
+    "lsa_dense_map_get_filtered": (i32, [vp, i32, f64, vp, vp, i32]),
+    "lsa_dense_map_get_sources_filtered": (i32, [vp, i32, f64, vp, i32]),
+    "lsa_dense_map_get_misses": (i32, [vp, i32, f64, vp, i32]),
+    "lsa_dense_map_prune": (i32, [vp, i32, f64, P(i64)]),
+    "lsa_dense_map_save_pcd_filtered": (i32, [vp, s, i32, i32, f64]),
+    "lsa_slam_get_dense_map_filtered": (i32, [vp, i32, f64, vp, vp, i32]),
+    "lsa_slam_get_dense_map_misses": (i32, [vp, i32, f64, vp, i32]),
+    "lsa_slam_save_dense_map_pcd_filtered": (i32, [vp, s, i32, i32, f64]),
+    "lsa_slam_prune_dense_map": (i32, [vp, i32, f64, P(i64)]),
+    "lsa_slam_get_registered_frame_origins": (i32, [vp, vp, i32]),
     # ---- the keypoint log and its descriptor store
     "lsa_kplog_describe": (i32, [vp, vp, i32, i32]),
     "lsa_kplog_descriptors": (i32, [vp, i32, i32, vp]),

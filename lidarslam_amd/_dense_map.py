@@ -1,8 +1,9 @@
 """The dense point-cloud map: registered frames voxel-hashed on the device (lsa_dense_map_*, lsa_slam_*dense_map*).
 
 DenseMapHost is the numpy statement of what the map computes; the device table (lidarslam_amd/csrc/lsa_dense_map.hip) is
-held to it byte for byte, on points and voxel records.  DenseMap is the table alone on a Context; dense_map(slam, ...) and
-its neighbours reach the pipeline's map (Slam.set_param("DenseMap", 1 or 2)).
+held to it byte for byte, on points, voxel records, sources and misses (free-space carving: DenseMapHost.carve).  DenseMap is
+the table alone on a Context; dense_map(slam, ...) and its neighbours reach the pipeline's map (Slam.set_param("DenseMap", 1
+or 2)).
 """
 import ctypes as C
 import os
@@ -42,6 +43,70 @@ def dense_voxel_keys(points, leaf):
     return keys, ok
 
 
+def dense_ray_steps(points, origins, leaf, margin_leaves=2.0, max_range=30.0, stride=1):
+    """The walk of DenseMapHost.carve, for all rays at once.  Yields (ray, index): `ray` the indices into `points` of the rays
+    that visit a voxel in this round, `index` (len(ray), 3) int64 the voxel each visits.  The first round is every ray's
+    start voxel; a ray of k steps appears in the first k + 1 rounds.  A point that casts no ray never appears."""
+    pts = np.ascontiguousarray(points, POINT_DTYPE)
+    n = pts.size
+    org = np.ascontiguousarray(origins, np.float32).reshape(-1, 3)
+    if org.shape[0] != n and org.shape[0] != 1:
+        raise ValueError("one origin, or one per point")
+    stride = int(stride)
+    if stride < 1:
+        raise ValueError("stride >= 1")
+    sel = np.arange(0, n, stride)
+    if sel.size == 0:
+        return
+    leaf = np.float64(leaf)
+    p = np.stack([pts["x"], pts["y"], pts["z"]], axis=1)[sel].astype(np.float64)
+    o = (org[sel] if org.shape[0] == n else np.repeat(org, sel.size, axis=0)).astype(np.float64)
+    with np.errstate(all="ignore"):
+        d = p - o
+        length = np.sqrt((d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]) + d[:, 2] * d[:, 2])
+        reach = length - np.float64(margin_leaves) * leaf
+        t = np.where(reach < np.float64(max_range), reach, np.float64(max_range))
+        ok = np.isfinite(o).all(axis=1) & np.isfinite(p).all(axis=1) & (t > 0)
+        e = o + d * (t / length)[:, None]
+        f0, f1 = np.floor(o / leaf), np.floor(e / leaf)
+        ok &= ((f0 >= -DENSE_INDEX_RANGE) & (f0 < DENSE_INDEX_RANGE) & (f1 >= -DENSE_INDEX_RANGE) & (f1 < DENSE_INDEX_RANGE)).all(axis=1)
+        at = np.flatnonzero(ok)
+        if at.size == 0:
+            return
+        ray, o, e = sel[at], o[at], e[at]
+        i, i1 = f0[at].astype(np.int64), f1[at].astype(np.int64)
+        left = np.abs(i1 - i)
+        step = np.sign(i1 - i)
+        tmax = ((i + (step > 0)).astype(np.float64) * leaf - o) / (e - o)
+        tdelta = leaf / np.abs(e - o)
+    yield ray, i.copy()
+    while True:
+        go = left.sum(axis=1) > 0
+        if not go.any():
+            return
+        if not go.all():
+            ray, i, left, step, tmax, tdelta = ray[go], i[go], left[go], step[go], tmax[go], tdelta[go]
+        # among the axes with steps left the smallest tmax, the earlier axis on a tie
+        a = np.full(ray.size, -1)
+        best = np.zeros(ray.size)
+        for ax in range(3):
+            take = (left[:, ax] > 0) & ((a < 0) | (tmax[:, ax] < best))
+            a = np.where(take, ax, a)
+            best = np.where(take, tmax[:, ax], best)
+        rows = np.arange(ray.size)
+        i[rows, a] += step[rows, a]
+        with np.errstate(all="ignore"):
+            tmax[rows, a] += tdelta[rows, a]
+        left[rows, a] -= 1
+        yield ray, i.copy()
+
+
+def dense_index_keys(index):
+    """the keys of voxel indices (n, 3) int64 in [-2^20, 2^20)"""
+    i = np.asarray(index, np.int64) + DENSE_INDEX_RANGE
+    return (i[:, 2].astype(np.uint64) << np.uint64(42)) | (i[:, 1].astype(np.uint64) << np.uint64(21)) | i[:, 0].astype(np.uint64)
+
+
 class DenseMapHost:
     """The definition.  State: key -> (point, count, frames, first_frame, last_frame, intensity code, source).
 
@@ -55,7 +120,23 @@ class DenseMapHost:
 
     reproject(corrections, first_frame): the map under a corrected trajectory.  This moves what the map kept -- one point per
     voxel, moved by the correction of the frame that measured it; it is not a rebuild from raw frames: two neighbouring
-    surface voxels may merge, and the voxel between them may stay empty until it is seen again."""
+    surface voxels may merge, and the voxel between them may stay empty until it is seen again.
+
+    carve(points, origins, frame, ...): free space.  Beside the above a voxel has misses (u32, 0 when made) and miss_frame
+    (none when made).  Every point with index % stride == 0 casts a ray from its origin o to the point p, both float widened
+    to double, everything in double and without contraction: d = p - o, len = sqrt((dx*dx + dy*dy) + dz*dz), t = min(len -
+    margin_leaves * leaf, max_range).  No ray when a coordinate is not finite, t is not > 0, or a start or end index lies
+    outside [-2^20, 2^20).  e = o + d * (t / len); i0 = floor(o / leaf), i1 = floor(e / leaf); per axis left = |i1 - i0|,
+    step = sign(i1 - i0) and, where left > 0, tmax = ((i0 + (step > 0)) * leaf - o) / (e - o), tdelta = leaf / |e - o|.
+    The ray visits i0 and then, exactly left_x + left_y + left_z times, steps along the axis of smallest tmax among those
+    with left > 0 (ties to x, then y): i[a] += step[a], tmax[a] += tdelta[a], left[a] -= 1, and visits i.  It ends in i1.
+    A visited voxel that exists, with last_frame != frame and miss_frame != frame, takes misses += 1 (modulo 2^32) and
+    miss_frame = frame: one count an ordinal, whatever the number of rays and calls, and none in an ordinal that hit it.
+    Nothing depends on the order of the rays.  carve makes, moves and removes no voxel and touches no point and no record.
+    The ordinal must not be below the map's last one (nor be -2^31, which the device keeps for "none") and becomes the last.
+
+    get / sources / misses (min_frames, max_miss_ratio): the voxels with frames >= min_frames and, for a ratio >= 0,
+    (double)misses <= max_miss_ratio * (double)frames.  prune removes the others for good."""
 
     def __init__(self, leaf):
         if not (leaf > 0 and np.isfinite(leaf)):
@@ -67,6 +148,8 @@ class DenseMapHost:
         self.voxels = {}
         self.skipped = 0
         self.dropped = 0
+        self.rays = 0
+        self.pruned = 0
         self.last_frame = None
 
     def size(self):
@@ -95,7 +178,7 @@ class DenseMapHost:
             c = int(code[order[at]])
             v = self.voxels.get(key)
             if v is None:
-                self.voxels[key] = [pts[w].copy(), n, 1, frame, frame, c, frame]
+                self.voxels[key] = [pts[w].copy(), n, 1, frame, frame, c, frame, 0, None]
                 continue
             v[1] += n
             if v[4] != frame:
@@ -106,9 +189,39 @@ class DenseMapHost:
                 v[5] = c
                 v[6] = frame
 
-    def get(self, min_frames=1):
-        """(points, voxels) of the voxels with frames >= min_frames, in ascending key order"""
-        keys = sorted(k for k, v in self.voxels.items() if v[2] >= min_frames)
+    def carve(self, points, origins, frame, margin_leaves=2.0, max_range=30.0, stride=1):
+        """origins: (n, 3) or (1, 3) float32 world positions of the sensor per point; see the class"""
+        frame = int(frame)
+        if frame == -(1 << 31):
+            raise ValueError("the ordinal -2^31 is not carved")
+        if self.last_frame is not None and frame < self.last_frame:
+            raise ValueError("frame ordinals must not decrease")
+        rounds = list(dense_ray_steps(points, origins, self.leaf, margin_leaves, max_range, stride))
+        self.last_frame = frame
+        if not rounds:
+            return
+        self.rays += int(rounds[0][0].size)
+        if not self.voxels:
+            return
+        have = np.fromiter(self.voxels.keys(), np.uint64, len(self.voxels))
+        seen = np.unique(np.concatenate([np.unique(dense_index_keys(index)) for _, index in rounds]))
+        for key in seen[np.isin(seen, have)].tolist():
+            v = self.voxels[key]
+            if v[4] != frame and v[8] != frame:
+                v[7] = (v[7] + 1) & 0xFFFFFFFF
+                v[8] = frame
+
+    @staticmethod
+    def _passes(v, min_frames, max_miss_ratio):
+        return v[2] >= min_frames and (not max_miss_ratio >= 0 or float(v[7]) <= float(max_miss_ratio) * float(v[2]))
+
+    def _kept(self, min_frames, max_miss_ratio):
+        return sorted(k for k, v in self.voxels.items() if self._passes(v, min_frames, max_miss_ratio))
+
+    def get(self, min_frames=1, max_miss_ratio=-1.0):
+        """(points, voxels) of the voxels with frames >= min_frames and, for a ratio >= 0, misses <= ratio * frames, in
+        ascending key order"""
+        keys = self._kept(min_frames, max_miss_ratio)
         pts = np.zeros(len(keys), POINT_DTYPE)
         vox = np.zeros(len(keys), dense_voxel_dtype)
         for j, k in enumerate(keys):
@@ -117,10 +230,21 @@ class DenseMapHost:
             vox[j] = (k, count, frames, first, last)
         return pts, vox
 
-    def sources(self, min_frames=1):
-        """the source of every voxel of get(min_frames), in its order"""
-        keys = sorted(k for k, v in self.voxels.items() if v[2] >= min_frames)
-        return np.array([self.voxels[k][6] for k in keys], np.int32)
+    def sources(self, min_frames=1, max_miss_ratio=-1.0):
+        """the source of every voxel of get(min_frames, max_miss_ratio), in its order"""
+        return np.array([self.voxels[k][6] for k in self._kept(min_frames, max_miss_ratio)], np.int32)
+
+    def misses(self, min_frames=1, max_miss_ratio=-1.0):
+        """the misses of every voxel of get(min_frames, max_miss_ratio), in its order"""
+        return np.array([self.voxels[k][7] for k in self._kept(min_frames, max_miss_ratio)], np.uint32)
+
+    def prune(self, min_frames=1, max_miss_ratio=-1.0):
+        """removes every voxel get(min_frames, max_miss_ratio) leaves out; returns their number (also added to self.pruned)"""
+        gone = [k for k, v in self.voxels.items() if not self._passes(v, min_frames, max_miss_ratio)]
+        for k in gone:
+            del self.voxels[k]
+        self.pruned += len(gone)
+        return len(gone)
 
     def reproject(self, corrections, first_frame=0):
         """corrections: (n, 16) float64, row-major 4x4 rigid transforms, entry j for ordinal first_frame + j.  Returns the
@@ -132,8 +256,8 @@ class DenseMapHost:
         is dense_voxel_keys of the moved point; a moved point that is not finite or lies outside the index range drops its
         voxel.  Voxels that arrive at one key merge: count is the sum modulo 2^32, first_frame the min, last_frame the
         max, frames = min(sum of frames, last_frame - first_frame + 1), point and source from the voxel of largest
-        intensity code, ties to the smaller source, then to the smaller old key.  Nothing depends on the order in which
-        the voxels are visited; last_frame of the map, the guard on the ordinals, is unchanged."""
+        intensity code, ties to the smaller source, then to the smaller old key; misses is the sum modulo 2^32 and
+        miss_frame the max.  Nothing depends on the order in which the voxels are visited; last_frame of the map, the guard on the ordinals, is unchanged."""
         D = np.ascontiguousarray(corrections, np.float64).reshape(-1, 16)
         n = D.shape[0]
         if n < 1:
@@ -152,18 +276,21 @@ class DenseMapHost:
         keys, ok = dense_voxel_keys(pts, self.leaf)
         merged = {}
         for j in np.flatnonzero(ok).tolist():
-            p, count, frames, first, last, code, src = recs[j]
+            p, count, frames, first, last, code, src, misses, miss_frame = recs[j]
             rank = (-code, src, old[j])  # the smallest wins: largest code, then smaller source, then smaller old key
             m = merged.get(int(keys[j]))
             if m is None:
-                merged[int(keys[j])] = [pts[j].copy(), count, frames, first, last, code, src, rank]
+                merged[int(keys[j])] = [pts[j].copy(), count, frames, first, last, code, src, rank, misses, miss_frame]
                 continue
             m[1] = (m[1] + count) & 0xFFFFFFFF
             m[2] += frames
             m[3], m[4] = min(m[3], first), max(m[4], last)
+            m[8] = (m[8] + misses) & 0xFFFFFFFF
+            if miss_frame is not None and (m[9] is None or miss_frame > m[9]):
+                m[9] = miss_frame
             if rank < m[7]:
                 m[0], m[5], m[6], m[7] = pts[j].copy(), code, src, rank
-        self.voxels = {k: [m[0], m[1], min(m[2], m[4] - m[3] + 1), m[3], m[4], m[5], m[6]] for k, m in merged.items()}
+        self.voxels = {k: [m[0], m[1], min(m[2], m[4] - m[3] + 1), m[3], m[4], m[5], m[6], m[8], m[9]] for k, m in merged.items()}
         dropped = int((~ok).sum())
         self.dropped += dropped
         return dropped
@@ -225,19 +352,52 @@ class DenseMap:
     def bytes(self):
         return int(self.L.lsa_dense_map_bytes(self.h))
 
-    def get(self, min_frames=1):
-        """(points, voxels) with frames >= min_frames in ascending key order"""
+    def get(self, min_frames=1, max_miss_ratio=-1.0):
+        """(points, voxels) with frames >= min_frames and, for a ratio >= 0, misses <= ratio * frames, in ascending key order"""
         cap = max(self.size(), 1)
         pts, vox = np.zeros(cap, POINT_DTYPE), np.zeros(cap, dense_voxel_dtype)
-        n = self._check(self.L.lsa_dense_map_get(self.h, int(min_frames), ptr(pts), ptr(vox), cap), "lsa_dense_map_get")
+        n = self._check(self.L.lsa_dense_map_get_filtered(self.h, int(min_frames), float(max_miss_ratio), ptr(pts), ptr(vox), cap), "lsa_dense_map_get_filtered")
         return pts[:n].copy(), vox[:n].copy()
 
-    def sources(self, min_frames=1):
-        """int32 ordinals of the calls whose points the voxels of get(min_frames) hold, in its order"""
+    def sources(self, min_frames=1, max_miss_ratio=-1.0):
+        """int32 ordinals of the calls whose points the voxels of get(min_frames, max_miss_ratio) hold, in its order"""
         cap = max(self.size(), 1)
         out = np.zeros(cap, np.int32)
-        n = self._check(self.L.lsa_dense_map_get_sources(self.h, int(min_frames), ptr(out), cap), "lsa_dense_map_get_sources")
+        n = self._check(self.L.lsa_dense_map_get_sources_filtered(self.h, int(min_frames), float(max_miss_ratio), ptr(out), cap), "lsa_dense_map_get_sources_filtered")
         return out[:n].copy()
+
+    def misses(self, min_frames=1, max_miss_ratio=-1.0):
+        """uint32 per voxel of get(min_frames, max_miss_ratio), in its order: the ordinals whose rays passed through it"""
+        cap = max(self.size(), 1)
+        out = np.zeros(cap, np.uint32)
+        n = self._check(self.L.lsa_dense_map_get_misses(self.h, int(min_frames), float(max_miss_ratio), ptr(out), cap), "lsa_dense_map_get_misses")
+        return out[:n].copy()
+
+    def carve_points(self, points, origins, frame):
+        """DenseMapHost.carve under the map's "CarveMarginLeaves", "CarveRange" and "CarveStride": world points of the caller's and
+        the sensor's world position per point ((n, 3) float32) or for all of them ((1, 3))"""
+        pts = np.ascontiguousarray(points, POINT_DTYPE)
+        org = np.ascontiguousarray(origins, np.float32).reshape(-1, 3)
+        self._check(
+            self.L.lsa_dense_map_carve_points(self.h, ptr(pts) if pts.size else None, pts.size, ptr(org) if org.size else None, org.shape[0], int(frame)),
+            "lsa_dense_map_carve_points",
+        )
+
+    def carve_frame(self, frame, H0, H1=None, t0=0.0, t1=0.0, time_offset=0.0):
+        """the rays of the context's current frame moved as insert_frame moves it, every one from where the sensor stood at the
+        point's time (frame_origins_at), fused with the walk"""
+        interp = H1 is not None
+        self._check(
+            self.L.lsa_dense_map_carve_frame(self.h, int(interp), ptr(pose16(H0)), ptr(pose16(H1)) if interp else None, float(t0), float(t1), float(time_offset), int(frame)),
+            "lsa_dense_map_carve_frame",
+        )
+
+    def prune(self, min_frames=1, max_miss_ratio=-1.0):
+        """removes the voxels get(min_frames, max_miss_ratio) leaves out and shrinks the table to what is left; returns their
+        number.  LsaError with .code E_CAPACITY, the map untouched, when the second table cannot be allocated"""
+        removed = C.c_longlong(0)
+        self._check(self.L.lsa_dense_map_prune(self.h, int(min_frames), float(max_miss_ratio), C.byref(removed)), "lsa_dense_map_prune")
+        return int(removed.value)
 
     def reproject(self, corrections, first_frame=0):
         """the map under per-frame rigid corrections ((n, 16) or (n, 4, 4); entry j for ordinal first_frame + j), as
@@ -251,9 +411,23 @@ class DenseMap:
     def clear(self):
         self._check(self.L.lsa_dense_map_clear(self.h), "lsa_dense_map_clear")
 
-    def save_pcd(self, path, fmt=PCD_BINARY, min_frames=1):
-        """the points of get(min_frames) into a PCD file; returns their number (0 and no file for none)"""
-        return self._check(self.L.lsa_dense_map_save_pcd(self.h, os.fsencode(path), int(fmt), int(min_frames)), "lsa_dense_map_save_pcd")
+    def save_pcd(self, path, fmt=PCD_BINARY, min_frames=1, max_miss_ratio=-1.0):
+        """the points of get(min_frames, max_miss_ratio) into a PCD file; returns their number (0 and no file for none)"""
+        return self._check(
+            self.L.lsa_dense_map_save_pcd_filtered(self.h, os.fsencode(path), int(fmt), int(min_frames), float(max_miss_ratio)), "lsa_dense_map_save_pcd_filtered"
+        )
+
+
+def frame_origins_at(ctx, H0, H1=None, t0=0.0, t1=0.0, time_offset=0.0):
+    """(n, 3) float32: where the sensor stood when it measured each point of the context's current frame -- the frame's own
+    origin under the pose lsa_transform_frame_at gives the point: the origins of DenseMap.carve_frame"""
+    n = ctx.L.lsa_frame_size(ctx.h)
+    out = np.zeros((max(n, 1), 3), np.float32)
+    interp = H1 is not None
+    rc = ctx.L.lsa_transform_frame_origins_at(ctx.h, int(interp), ptr(pose16(H0)), ptr(pose16(H1)) if interp else None, float(t0), float(t1), float(time_offset), ptr(out), n)
+    if rc < 0:
+        raise _error("lsa_transform_frame_origins_at", rc, ctx.L.lsa_last_error(ctx.h).decode())
+    return out[:rc].copy()
 
 
 # ---- the pipeline's dense map (Slam.set_param("DenseMap", 1): every registered frame; 2: keyframes only)
@@ -297,6 +471,44 @@ def pose_corrections(old, new):
 def save_dense_map_pcd(slam, path, format=PCD_BINARY, min_frames=1):  # noqa: A002 (the C ABI's name of the parameter)
     """the points of dense_map(slam, min_frames) into a PCD file; returns their number (0 and no file for none)"""
     return slam._check(slam.L.lsa_slam_save_dense_map_pcd(slam.h, os.fsencode(path), int(format), int(min_frames)), "lsa_slam_save_dense_map_pcd")
+
+
+def dense_map_filtered(slam, min_frames=1, max_miss_ratio=-1.0):
+    """dense_map of the voxels that also have misses <= max_miss_ratio * frames (a ratio below 0: all)"""
+    cap = max(dense_map_size(slam), 1)
+    pts, vox = np.zeros(cap, POINT_DTYPE), np.zeros(cap, dense_voxel_dtype)
+    n = slam._check(slam.L.lsa_slam_get_dense_map_filtered(slam.h, int(min_frames), float(max_miss_ratio), ptr(pts), ptr(vox), cap), "lsa_slam_get_dense_map_filtered")
+    return pts[:n].copy(), vox[:n].copy()
+
+
+def dense_map_misses(slam, min_frames=1, max_miss_ratio=-1.0):
+    """uint32 per voxel of dense_map_filtered(slam, min_frames, max_miss_ratio), in its order"""
+    cap = max(dense_map_size(slam), 1)
+    out = np.zeros(cap, np.uint32)
+    n = slam._check(slam.L.lsa_slam_get_dense_map_misses(slam.h, int(min_frames), float(max_miss_ratio), ptr(out), cap), "lsa_slam_get_dense_map_misses")
+    return out[:n].copy()
+
+
+def prune_dense_map(slam, min_frames=1, max_miss_ratio=-1.0):
+    """removes what dense_map_filtered leaves out from the pipeline's map; returns the number of voxels removed"""
+    removed = C.c_longlong(0)
+    slam._check(slam.L.lsa_slam_prune_dense_map(slam.h, int(min_frames), float(max_miss_ratio), C.byref(removed)), "lsa_slam_prune_dense_map")
+    return int(removed.value)
+
+
+def save_dense_map_pcd_filtered(slam, path, format=PCD_BINARY, min_frames=1, max_miss_ratio=-1.0):  # noqa: A002
+    """the points of dense_map_filtered into a PCD file; returns their number (0 and no file for none)"""
+    return slam._check(
+        slam.L.lsa_slam_save_dense_map_pcd_filtered(slam.h, os.fsencode(path), int(format), int(min_frames), float(max_miss_ratio)), "lsa_slam_save_dense_map_pcd_filtered"
+    )
+
+
+def registered_frame_origins(slam):
+    """(n, 3) float32 per point of slam.registered_frame(), in its order: where the sensor stood when it measured the point"""
+    cap = max(slam._n, 1 << 19)  # as Slam.registered_frame
+    out = np.zeros((cap, 3), np.float32)
+    rc = slam._check(slam.L.lsa_slam_get_registered_frame_origins(slam.h, ptr(out), cap), "lsa_slam_get_registered_frame_origins")
+    return out[:rc].copy()
 
 
 def clear_dense_map(slam):

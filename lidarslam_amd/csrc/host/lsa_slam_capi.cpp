@@ -328,6 +328,41 @@ int lsa_slam_save_dense_map_pcd(lsa_slam* s, const char* path, int format, int m
 
 int lsa_slam_clear_dense_map(lsa_slam* s) { return s ? s->core.ClearDenseMap() : LSA_E_ARG; }
 
+int lsa_slam_get_dense_map_filtered(lsa_slam* s, int min_frames, double max_miss_ratio, lsa_point_t* pts, lsa_dense_voxel_t* voxels, int capacity)
+{
+  if (!s) return LSA_E_ARG;
+  return s->core.GetDenseMapFiltered(min_frames, max_miss_ratio, pts, voxels, capacity);
+}
+
+int lsa_slam_get_dense_map_misses(lsa_slam* s, int min_frames, double max_miss_ratio, uint32_t* out, int capacity)
+{
+  if (!s) return LSA_E_ARG;
+  return s->core.GetDenseMapMisses(min_frames, max_miss_ratio, out, capacity);
+}
+
+int lsa_slam_save_dense_map_pcd_filtered(lsa_slam* s, const char* path, int format, int min_frames, double max_miss_ratio)
+{
+  if (!s || !path) return LSA_E_ARG;
+  return s->core.SaveDenseMapToPCDFiltered(path, format, min_frames, max_miss_ratio);
+}
+
+int lsa_slam_prune_dense_map(lsa_slam* s, int min_frames, double max_miss_ratio, long long* removed)
+{
+  if (!s) return LSA_E_ARG;
+  return s->core.PruneDenseMap(min_frames, max_miss_ratio, removed);
+}
+
+int lsa_slam_get_registered_frame_origins(lsa_slam* s, float* xyz, int capacity)
+{
+  if (!s || (!xyz && capacity > 0)) return LSA_E_ARG;
+  std::vector<float> origins;
+  int n = s->core.GetRegisteredFrameOrigins(origins);
+  if (n < 0) return n;
+  n = std::min(n, capacity);
+  if (n > 0) std::memcpy(xyz, origins.data(), (size_t)n * 3 * sizeof(float));
+  return n;
+}
+
 // ---- a corrected trajectory brought back: what Slam::RunPoseGraphOptimization does after its optimizer (Slam.cxx:404-477) ----
 int lsa_slam_set_trajectory_and_rebuild_maps(lsa_slam* s, const double* poses17, int n)
 {

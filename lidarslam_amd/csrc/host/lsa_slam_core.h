@@ -286,6 +286,15 @@ public:
   int GetDenseMapSources(int minFrames, int* out, int capacity);
   int SaveDenseMapToPCD(const std::string& path, int format, int minFrames);
   int ClearDenseMap();
+  // free space: "DenseMapCarve" 0 off (the default: one more untaken branch), 1 the rays of every inserted
+  // frame are walked once all device frames of the call are in the map; the three knobs are lsa_dense_map_set's
+  int DenseMapCarve = 0;
+  double DenseMapCarveRange = 30., DenseMapCarveMarginLeaves = 2., DenseMapCarveStride = 1.;
+  int GetDenseMapFiltered(int minFrames, double maxMissRatio, lsa_point_t* pts, lsa_dense_voxel_t* voxels, int capacity);
+  int GetDenseMapMisses(int minFrames, double maxMissRatio, uint32_t* out, int capacity);
+  int SaveDenseMapToPCDFiltered(const std::string& path, int format, int minFrames, double maxMissRatio);
+  int PruneDenseMap(int minFrames, double maxMissRatio, long long* removed);
+  int GetRegisteredFrameOrigins(std::vector<float>& out);
 
   // ---- state ----
   Pose Tworld, PreviousTworld, Trelative;
@@ -437,6 +446,7 @@ private:
   int ReprojectDenseMap(const std::vector<double>& corrections, int firstOrdinal);
   void DropDenseMap(const char* why);  // why == nullptr: the caller asked for it, nothing to warn about
   int DenseReady(const char* who);
+  int SetDenseCarveParams();  // the knobs into the map, when there is one
 
   // ---- diagnostics ----
   double DbgAcc[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // (LSA_STAGE_DEBUG=1: seconds outside the stage timers, printed when the object goes)

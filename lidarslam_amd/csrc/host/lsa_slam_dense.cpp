@@ -1,7 +1,8 @@
 // lsa_slam_dense.cpp -- see lsa_slam_core.h: the pipeline's dense point-cloud map (lsa_dense_map.hip).  The
 // registered frame goes into the table at the end of AddFrame without leaving the device; what moves the poses under the
 // points that are already in it clears it -- or, under "DenseMapOnTrajectory" 1 and for an applied trajectory alone,
-// re-projects it: every voxel's point moved by the correction of the frame that measured it.
+// re-projects it: every voxel's point moved by the correction of the frame that measured it.  Under "DenseMapCarve" 1 the rays
+// of the inserted frames are walked through the table behind the insertions (free space: misses per voxel, filter, prune).
 #include "lsa_slam_internal.h"
 #include <algorithm>
 #include <cstdio>
@@ -21,22 +22,25 @@ int SlamCore::InsertDenseFrame(bool keyframe, double time)
   {
     LSA_TRY(lsa_dense_map_create(Ctx, DenseMapLeafSize, &Dense));
     LSA_TRY(lsa_dense_map_set(Dense, "MaxBytes", DenseMapMaxBytes));
+    if (DenseMapCarve) LSA_TRY(SetDenseCarveParams());
   }
   const int ordinal = static_cast<int>(DenseFrames);
   bool inserted = false, refused = false;
-  auto insert = [&](const Pose& offset, double timeOffset) -> int {
+  // the frame in use under the poses GetRegisteredFrame uses: inserted, or (carve) its rays walked
+  auto insert = [&](const Pose& offset, double timeOffset, bool carve = false) -> int {
     int rc;
     if (Undistortion)
     {
       const Pose H0 = (Tworld * Motion.GetH0()) * offset;
       const Pose H1 = (Tworld * Motion.GetH1()) * offset;
-      rc = lsa_dense_map_insert_frame(Dense, 1, H0.m, H1.m, Motion.Time0, Motion.Time1, timeOffset, ordinal);
+      rc = (carve ? lsa_dense_map_carve_frame : lsa_dense_map_insert_frame)(Dense, 1, H0.m, H1.m, Motion.Time0, Motion.Time1, timeOffset, ordinal);
     }
     else
     {
       const Pose tf = Tworld * offset;
-      rc = lsa_dense_map_insert_frame(Dense, 0, tf.m, nullptr, 0., 0., timeOffset, ordinal);
+      rc = (carve ? lsa_dense_map_carve_frame : lsa_dense_map_insert_frame)(Dense, 0, tf.m, nullptr, 0., 0., timeOffset, ordinal);
     }
+    if (carve) return rc < 0 ? Fail(rc, "lsa_dense_map_carve_frame") : LSA_OK;
     if (rc == LSA_E_CAPACITY)
     {
       refused = true;
@@ -71,6 +75,20 @@ int SlamCore::InsertDenseFrame(bool keyframe, double time)
     if (const int rc = insert(BaseToLidarOffset, 0.); rc < 0) return rc;
   }
   if (refused) DenseRefused++;
+  if (DenseMapCarve && inserted && !refused)
+  {
+    // free space: only now that every device frame of the call is in the map -- a voxel the second LiDAR hit carries this
+    // ordinal and is not seen through by the first
+    if (!CurrentFrames.empty())
+    {
+      for (const HeldFrame& f : CurrentFrames)
+      {
+        LSA_TRY(lsa_frame_store_use(Ctx, f.slot));
+        if (const int rc = insert(GetBaseToLidarOffset(f.device), f.timeOffset, true); rc < 0) return rc;
+      }
+    }
+    else if (const int rc = insert(BaseToLidarOffset, 0., true); rc < 0) return rc;
+  }
   if (inserted)
   {
     DenseFrames++;
@@ -179,6 +197,88 @@ int SlamCore::SaveDenseMapToPCD(const std::string& path, int format, int minFram
   if (!Dense) return 0;  // an empty cloud is not saved
   const int n = lsa_dense_map_save_pcd(Dense, path.c_str(), format, minFrames);
   return n < 0 ? Fail(n, "lsa_dense_map_save_pcd") : n;
+}
+
+int SlamCore::SetDenseCarveParams()
+{
+  if (!Dense) return LSA_OK;
+  if (const int rc = lsa_dense_map_set(Dense, "CarveRange", DenseMapCarveRange); rc < 0) return Fail(rc, "lsa_dense_map_set");
+  if (const int rc = lsa_dense_map_set(Dense, "CarveMarginLeaves", DenseMapCarveMarginLeaves); rc < 0) return Fail(rc, "lsa_dense_map_set");
+  if (const int rc = lsa_dense_map_set(Dense, "CarveStride", DenseMapCarveStride); rc < 0) return Fail(rc, "lsa_dense_map_set");
+  return LSA_OK;
+}
+
+int SlamCore::GetDenseMapFiltered(int minFrames, double maxMissRatio, lsa_point_t* pts, lsa_dense_voxel_t* voxels, int capacity)
+{
+  if (const int rc = DenseReady("GetDenseMap"); rc < 0) return rc;
+  if (capacity < 0) { LastError = "GetDenseMap: bad argument"; return LSA_E_ARG; }
+  if (!Dense) return 0;
+  const int n = lsa_dense_map_get_filtered(Dense, minFrames, maxMissRatio, pts, voxels, capacity);
+  return n < 0 ? Fail(n, "lsa_dense_map_get_filtered") : n;
+}
+
+int SlamCore::GetDenseMapMisses(int minFrames, double maxMissRatio, uint32_t* out, int capacity)
+{
+  if (const int rc = DenseReady("GetDenseMapMisses"); rc < 0) return rc;
+  if (capacity < 0) { LastError = "GetDenseMapMisses: bad argument"; return LSA_E_ARG; }
+  if (!Dense) return 0;
+  const int n = lsa_dense_map_get_misses(Dense, minFrames, maxMissRatio, out, capacity);
+  return n < 0 ? Fail(n, "lsa_dense_map_get_misses") : n;
+}
+
+int SlamCore::SaveDenseMapToPCDFiltered(const std::string& path, int format, int minFrames, double maxMissRatio)
+{
+  if (const int rc = DenseReady("SaveDenseMapToPCD"); rc < 0) return rc;
+  if (!Dense) return 0;  // an empty cloud is not saved
+  const int n = lsa_dense_map_save_pcd_filtered(Dense, path.c_str(), format, minFrames, maxMissRatio);
+  return n < 0 ? Fail(n, "lsa_dense_map_save_pcd_filtered") : n;
+}
+
+int SlamCore::PruneDenseMap(int minFrames, double maxMissRatio, long long* removed)
+{
+  if (const int rc = DenseReady("PruneDenseMap"); rc < 0) return rc;
+  if (!removed) { LastError = "PruneDenseMap: bad argument"; return LSA_E_ARG; }
+  *removed = 0;
+  if (!Dense) return LSA_OK;
+  const int rc = lsa_dense_map_prune(Dense, minFrames, maxMissRatio, removed);
+  return rc < 0 ? Fail(rc, "lsa_dense_map_prune") : LSA_OK;
+}
+
+// per point of GetRegisteredFrame, in its order: where the sensor stood when it measured the point (float xyz)
+int SlamCore::GetRegisteredFrameOrigins(std::vector<float>& out)
+{
+  if (!Ctx) return LSA_E_NO_DEVICE;
+  out.clear();
+  if (!HaveFrame) return 0;
+  auto origins = [&](const Pose& offset, double timeOffset, float* xyz, int n) -> int {
+    if (Undistortion)
+    {
+      const Pose H0 = (Tworld * Motion.GetH0()) * offset;
+      const Pose H1 = (Tworld * Motion.GetH1()) * offset;
+      return lsa_transform_frame_origins_at(Ctx, 1, H0.m, H1.m, Motion.Time0, Motion.Time1, timeOffset, xyz, n);
+    }
+    const Pose tf = Tworld * offset;
+    return lsa_transform_frame_origins_at(Ctx, 0, tf.m, nullptr, 0., 0., timeOffset, xyz, n);
+  };
+  if (!CurrentFrames.empty())
+  {
+    size_t total = 0;
+    for (const HeldFrame& f : CurrentFrames) total += static_cast<size_t>(f.n);
+    out.resize(3 * total);
+    size_t at = 0;
+    for (const HeldFrame& f : CurrentFrames)
+    {
+      LSA_TRY(lsa_frame_store_use(Ctx, f.slot));
+      LSA_TRY(origins(GetBaseToLidarOffset(f.device), f.timeOffset, out.data() + 3 * at, f.n));
+      at += static_cast<size_t>(f.n);
+    }
+    return static_cast<int>(total);
+  }
+  const int n = lsa_frame_size(Ctx);
+  if (n <= 0) return 0;
+  out.resize(3 * static_cast<size_t>(n));
+  LSA_TRY(origins(BaseToLidarOffset, 0., out.data(), n));
+  return n;
 }
 
 int SlamCore::ClearDenseMap()

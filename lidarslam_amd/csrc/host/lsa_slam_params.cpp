@@ -154,6 +154,21 @@ int SlamCore::SetParamValue(const std::string& name, double v)
     if (Dense) lsa_dense_map_set(Dense, "MaxBytes", v);
     return LSA_OK;
   }
+  if (name == "DenseMapCarve")
+  {
+    if (!(v == 0. || v == 1.)) { LastError = "DenseMapCarve: 0 off, 1 the rays of every inserted frame carve free space"; return LSA_E_ARG; }
+    DenseMapCarve = static_cast<int>(v);
+    return DenseMapCarve ? SetDenseCarveParams() : LSA_OK;
+  }
+  if (name == "DenseMapCarveRange" || name == "DenseMapCarveMarginLeaves" || name == "DenseMapCarveStride")
+  {
+    double& knob = name == "DenseMapCarveRange" ? DenseMapCarveRange : (name == "DenseMapCarveMarginLeaves" ? DenseMapCarveMarginLeaves : DenseMapCarveStride);
+    const bool ok = name == "DenseMapCarveRange" ? (v > 0. && v / DenseMapLeafSize <= 4096.)
+                    : name == "DenseMapCarveMarginLeaves" ? (v >= 0. && v < 1e9) : (v >= 1. && v <= 1e9 && v == static_cast<double>(static_cast<long long>(v)));
+    if (!ok) { LastError = name + ": out of range (a range of at most 4096 leaves, a margin >= 0, a whole stride >= 1)"; return LSA_E_ARG; }
+    knob = v;
+    return SetDenseCarveParams();
+  }
   if (name == "DenseMapOnTrajectory")
   {
     if (!(v == 0. || v == 1.)) { LastError = "DenseMapOnTrajectory: 0 an applied trajectory clears the dense map, 1 it re-projects it"; return LSA_E_ARG; }
@@ -241,6 +256,12 @@ int SlamCore::GetParam(const std::string& name, double* v) const
   if (name == "DenseMapClears") { *v = DenseClears; return LSA_OK; }
   if (name == "DenseMapFrames") { *v = DenseFrames; return LSA_OK; }
   if (name == "DenseMapOnTrajectory") { *v = DenseMapOnTrajectory; return LSA_OK; }
+  if (name == "DenseMapCarve") { *v = DenseMapCarve; return LSA_OK; }
+  if (name == "DenseMapCarveRange") { *v = DenseMapCarveRange; return LSA_OK; }
+  if (name == "DenseMapCarveMarginLeaves") { *v = DenseMapCarveMarginLeaves; return LSA_OK; }
+  if (name == "DenseMapCarveStride") { *v = DenseMapCarveStride; return LSA_OK; }
+  if (name == "DenseMapRays") { *v = Dense ? std::max(lsa_dense_map_get_param(Dense, "Rays"), 0.) : 0.; return LSA_OK; }
+  if (name == "DenseMapPruned") { *v = Dense ? lsa_dense_map_get_param(Dense, "Pruned") : 0.; return LSA_OK; }
   if (name == "DenseMapReprojections") { *v = DenseReprojections; return LSA_OK; }
   if (name == "DenseMapDropped") { *v = Dense ? lsa_dense_map_get_param(Dense, "Dropped") : 0.; return LSA_OK; }
   if (name == "DenseMapReprojectSeconds") { *v = Dense ? lsa_dense_map_get_param(Dense, "ReprojectSeconds") : 0.; return LSA_OK; }

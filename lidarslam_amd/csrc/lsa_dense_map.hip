@@ -27,6 +27,14 @@
 //                   and the candidate word (intensity code << 32) | ~ordered(source) in with atomics, notes the new slot
 //   k_dense_elect   the old slots whose word the candidate names atomicMin their old key: ties on intensity and source
 //   k_dense_settle  the old slot named by both writes the moved point and its source, caps frames, disarms the word
+// Free space (DenseMapHost.carve): miss[2 * capacity], made by the first carve -- a map never carved has none and pays for
+// none --: the voxel's misses, then the word of the last ordinal that counted one (ordinal ^ 2^31: the zeroed word is "none").
+//   k_dense_carve   one thread per ray walks the voxels from the sensor to shortly before the point -- a number of steps
+//                   known before the first -- and looks each up without ever claiming; a voxel found whose last_frame is
+//                   not the ordinal takes atomicMax on its word, and the one thread that raised it adds the miss
+// It runs behind k_dense_apply of its ordinal on the same stream, so last_frame is final.  The array is carried by the rehash,
+// merged by the re-projection (atomicAdd, atomicMax), read by the export's predicate; lsa_dense_map_prune is the rehash under
+// that predicate into the smallest table that holds what passes.
 #include <cstring>
 #include <rocprim/device/device_radix_sort.hpp>
 #include <chrono>
@@ -53,6 +61,7 @@ constexpr u64 kOccupied = 1ull << 63;
 constexpr double kIndexRange = 1048576.;  // 2^20: indices in [-2^20, 2^20)
 constexpr unsigned kMinCapacity = 64, kMaxCapacity = 1u << 30;
 constexpr size_t kDefaultMaxBytes = (size_t)16 << 30;
+constexpr double kMaxRangeLeaves = 4096.;  // "CarveRange" / leaf at most
 
 struct alignas(64) Slot
 {
@@ -68,12 +77,13 @@ struct Table
 {
   Slot* slots;
   int* source;    // [capacity] the ordinal of the call whose point the slot holds
+  unsigned* miss; // [2 * capacity] misses, then miss-frame words; null in a map never carved
   unsigned mask;  // capacity - 1
   int stress;     // "ProbeStress": every key's home slot is 0
 };
 // device words of a map: [0] occupied slots, [1] error (a probe sequence ran out), [2] points skipped, [3] voxels the
-// re-projection in flight dropped
-enum { kStatOccupied = 0, kStatError = 1, kStatSkipped = 2, kStatDropped = 3, kStatWords = 4 };
+// re-projection in flight dropped, [4] rays cast
+enum { kStatOccupied = 0, kStatError = 1, kStatSkipped = 2, kStatDropped = 3, kStatRays = 4, kStatWords = 5 };
 
 // the order-preserving code of an intensity: f2ou, and 0 -- below -inf -- for a NaN
 __device__ __forceinline__ unsigned intensity_code(float v) { return v == v ? f2ou(v) : 0u; }
@@ -118,6 +128,34 @@ __device__ __forceinline__ int find_or_claim(const Table& t, u64 key, u64* __res
   }
   return -1;
 }
+
+// the slot of `key`, -1 when the table does not hold it: read-only, until the key or an empty slot, capacity probes at most
+__device__ __forceinline__ int find(const Table& t, u64 key)
+{
+  const u64 want = key | kOccupied;
+  unsigned s = home_slot(t, key);
+  for (unsigned probe = 0; probe <= t.mask; ++probe, s = (s + 1u) & t.mask)
+  {
+    const u64 cur = __hip_atomic_load(&t.slots[s].key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (cur == want) return (int)s;
+    if (cur == 0ull) return -1;
+  }
+  return -1;
+}
+
+// what the exports hand out and a prune keeps: frames >= min_frames and, for a ratio >= 0, misses <= ratio * frames
+struct Keep
+{
+  const unsigned* miss;  // null: no voxel has a miss
+  unsigned min_frames;
+  double ratio;
+  __device__ bool operator()(const Slot& S, unsigned i) const
+  {
+    if (S.key == 0ull || S.frames < min_frames) return false;
+    if (!(ratio >= 0.)) return true;
+    return (double)(miss ? miss[i] : 0u) <= ratio * (double)S.frames;
+  }
+};
 
 struct FrameMove
 {
@@ -196,13 +234,15 @@ __global__ __launch_bounds__(256) void k_dense_apply(const float4* __restrict__ 
 }
 
 // every occupied slot of the old table into the new one (zeroed); keys are unique, so a slot is only ever claimed from empty
-__global__ __launch_bounds__(256) void k_dense_rehash(const Slot* __restrict__ old, const int* __restrict__ old_source, unsigned old_capacity, Table t,
-                                                      u64* __restrict__ stat)
+// (a prune is this launch under its `keep`; growth's keeps every voxel.  old_miss: null in a map never carved)
+__global__ __launch_bounds__(256) void k_dense_rehash(const Slot* __restrict__ old, const int* __restrict__ old_source, const unsigned* __restrict__ old_miss,
+                                                      unsigned old_capacity, Keep keep, Table t, u64* __restrict__ stat)
 {
   const unsigned i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= old_capacity) return;
   const Slot o = old[i];
   if (o.key == 0ull) return;
+  if (!keep(o, i)) return;
   unsigned s = home_slot(t, o.key & ~kOccupied);
   for (unsigned probe = 0; probe <= t.mask; ++probe, s = (s + 1u) & t.mask)
   {
@@ -211,9 +251,123 @@ __global__ __launch_bounds__(256) void k_dense_rehash(const Slot* __restrict__ o
     S.a = o.a; S.b = o.b;
     S.count = o.count; S.frames = o.frames; S.first = o.first; S.last = o.last;
     t.source[s] = old_source[i];
+    if (old_miss)
+    {
+      t.miss[s] = old_miss[i];
+      t.miss[(size_t)t.mask + 1u + s] = old_miss[(size_t)old_capacity + i];
+    }
     return;
   }
   atomicOr(&stat[kStatError], 1ull);
+}
+
+// the occupied count of a table whose slots the host counted (a prune), published as k_dense_apply publishes
+__global__ void k_dense_publish(u64* __restrict__ stat, u64* __restrict__ host_words, unsigned serial, unsigned occupied)
+{
+  if (blockIdx.x != 0 || threadIdx.x != 0) return;
+  stat[kStatOccupied] = occupied;
+  __hip_atomic_store(&host_words[1], stat[kStatError], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+  __hip_atomic_store(&host_words[2], stat[kStatSkipped], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+  __hip_atomic_store(&host_words[0], ((u64)serial << 32) | (u64)occupied, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+
+// ---- free space ------------------------------------------------------------------------------------------------------------
+struct Carve
+{
+  const float* origins;  // unfused: [n_origins][3] world positions of the sensor
+  int n_origins;         // 1 or the number of points
+  int stride;            // ray r belongs to point r * stride
+  int rays;
+  int frame;
+  double leaf, margin, range;  // margin = margin_leaves * leaf
+  long long max_steps;         // 3 * (ceil(range / leaf) + 2): no ray has more, whatever it is given
+};
+
+// DenseMapHost.carve, statement for statement: double, no contraction (the unit is built with -ffp-contract=off)
+__global__ __launch_bounds__(256) void k_dense_carve(const float4* __restrict__ in, const FrameMove m, const Carve c, Table t, u64* __restrict__ stat)
+{
+  const int r = blockIdx.x * blockDim.x + threadIdx.x;
+  if (r >= c.rays) return;
+  const size_t at = (size_t)r * (size_t)c.stride;
+  float4 a = in[2 * at];
+  float4 b = in[2 * at + 1];
+  float ofx, ofy, ofz;
+  if (m.fused)
+  {
+    // the sensor at the time the point was measured: what the frame's own origin becomes under the point's pose
+    float4 oa = make_float4(0.f, 0.f, 0.f, a.w), ob = b;
+    frame_point_to_world(oa, ob, m.interpolate, m.c, m.R, m.time_offset);
+    frame_point_to_world(a, b, m.interpolate, m.c, m.R, m.time_offset);
+    ofx = oa.x; ofy = oa.y; ofz = oa.z;
+  }
+  else
+  {
+    const float* o = c.origins + (c.n_origins == 1 ? (size_t)0 : 3 * at);
+    ofx = o[0]; ofy = o[1]; ofz = o[2];
+  }
+  const double o[3] = {(double)ofx, (double)ofy, (double)ofz};
+  const double p[3] = {(double)a.x, (double)a.y, (double)a.z};
+  const double d[3] = {p[0] - o[0], p[1] - o[1], p[2] - o[2]};
+  const double len = __builtin_sqrt((d[0] * d[0] + d[1] * d[1]) + d[2] * d[2]);
+  const double reach = len - c.margin;
+  const double tt = reach < c.range ? reach : c.range;
+  bool ok = __builtin_isfinite(o[0]) && __builtin_isfinite(o[1]) && __builtin_isfinite(o[2]) && __builtin_isfinite(p[0]) && __builtin_isfinite(p[1]) &&
+            __builtin_isfinite(p[2]) && tt > 0.;
+  const double scale = tt / len;
+  double e[3], f0[3], f1[3];
+#pragma unroll
+  for (int k = 0; k < 3; ++k)
+  {
+    e[k] = o[k] + d[k] * scale;
+    f0[k] = __builtin_floor(o[k] / c.leaf);
+    f1[k] = __builtin_floor(e[k] / c.leaf);
+    ok = ok && f0[k] >= -kIndexRange && f0[k] < kIndexRange && f1[k] >= -kIndexRange && f1[k] < kIndexRange;
+  }
+  const u64 casting = __ballot(ok);
+  if (!ok) return;
+  // one add a wavefront
+  if ((int)(threadIdx.x & 63) == __ffsll((long long)casting) - 1) atomicAdd(&stat[kStatRays], (u64)__popcll(casting));
+  long long i[3], left[3], step[3];
+  double tmax[3], tdelta[3];
+  long long total = 0;
+#pragma unroll
+  for (int k = 0; k < 3; ++k)
+  {
+    i[k] = (long long)f0[k];
+    const long long i1 = (long long)f1[k];
+    left[k] = i1 > i[k] ? i1 - i[k] : i[k] - i1;
+    step[k] = i1 > i[k] ? 1 : (i1 < i[k] ? -1 : 0);
+    tmax[k] = 0.;
+    tdelta[k] = 0.;
+    if (left[k] > 0)
+    {
+      const double span = e[k] - o[k];
+      tmax[k] = ((double)(i[k] + (step[k] > 0 ? 1 : 0)) * c.leaf - o[k]) / span;
+      tdelta[k] = c.leaf / __builtin_fabs(span);
+    }
+    total += left[k];
+  }
+  if (total > c.max_steps) total = c.max_steps;  // (never: the ray is no longer than the range)
+  const unsigned word = (unsigned)c.frame ^ 0x80000000u;
+  unsigned* __restrict__ words = t.miss + (size_t)t.mask + 1u;
+  for (long long k = 0;; ++k)
+  {
+    const u64 key = ((u64)(i[2] + 1048576ll) << 42) | ((u64)(i[1] + 1048576ll) << 21) | (u64)(i[0] + 1048576ll);
+    const int s = find(t, key);
+    // (last_frame is final: k_dense_apply of this ordinal ran before this launch)
+    if (s >= 0 && t.slots[s].last != c.frame && atomicMax(&words[s], word) < word) atomicAdd(&t.miss[s], 1u);
+    if (k >= total) break;
+    int ax = -1;
+    double best = 0.;
+#pragma unroll
+    for (int q = 0; q < 3; ++q)
+      if (left[q] > 0 && (ax < 0 || tmax[q] < best)) { ax = q; best = tmax[q]; }
+    if (ax < 0) break;  // (never: total is the sum of what is left)
+    // (indexed by a run-time axis, written out: no private array leaves the registers)
+    if (ax == 0) { i[0] += step[0]; tmax[0] += tdelta[0]; left[0] -= 1; }
+    else if (ax == 1) { i[1] += step[1]; tmax[1] += tdelta[1]; left[1] -= 1; }
+    else { i[2] += step[2]; tmax[2] += tdelta[2]; left[2] -= 1; }
+  }
 }
 
 // ---- re-projection under a corrected trajectory --------------------------------------------------------------------------
@@ -223,6 +377,7 @@ struct Reproject
 {
   const Slot* old;
   const int* old_source;
+  const unsigned* old_miss;  // null in a map never carved
   unsigned old_capacity;
   const double* corrections;  // [n][16] row-major; entry j belongs to ordinal first_frame + j
   int first_frame, n;
@@ -285,6 +440,13 @@ __global__ __launch_bounds__(256) void k_dense_move(const Reproject r, Table t, 
   atomicMax(reinterpret_cast<unsigned*>(&S.first), first_word(o.first));
   atomicMax(reinterpret_cast<unsigned*>(&S.last), last_word(o.last));
   atomicMax(&S.cand, merge_word(o.b, source));
+  if (r.old_miss)
+  {
+    // misses add up modulo 2^32; the larger ordinal has the larger word and the zeroed word, "none", is the identity
+    const unsigned misses = r.old_miss[i], word = r.old_miss[(size_t)r.old_capacity + i];
+    if (misses) atomicAdd(&t.miss[s], misses);
+    if (word) atomicMax(&t.miss[(size_t)t.mask + 1u + s], word);
+  }
 }
 
 // launch 2: among the old voxels the candidate word names -- equal intensity code and source -- the smallest old key
@@ -337,8 +499,8 @@ __global__ __launch_bounds__(256) void k_dense_settle(const Reproject r, Table t
 struct ExportPred
 {
   const Slot* slots;
-  unsigned min_frames;
-  __device__ bool operator()(int i) const { return slots[i].key != 0ull && slots[i].frames >= min_frames; }
+  Keep keep;
+  __device__ bool operator()(int i) const { return keep(slots[i], (unsigned)i); }
 };
 struct ExportEmit
 {
@@ -351,14 +513,15 @@ struct ExportEmit
     index[pos] = (unsigned)i;
   }
 };
-__global__ __launch_bounds__(256) void k_dense_gather(const Slot* __restrict__ slots, const int* __restrict__ source, const u64* __restrict__ keys,
-                                                      const unsigned* __restrict__ index, int n, float4* __restrict__ pts, lsa_dense_voxel_t* __restrict__ voxels,
-                                                      int* __restrict__ sources)
+__global__ __launch_bounds__(256) void k_dense_gather(const Slot* __restrict__ slots, const int* __restrict__ source, const unsigned* __restrict__ miss,
+                                                      const u64* __restrict__ keys, const unsigned* __restrict__ index, int n, float4* __restrict__ pts,
+                                                      lsa_dense_voxel_t* __restrict__ voxels, int* __restrict__ sources, unsigned* __restrict__ misses)
 {
   const int j = blockIdx.x * blockDim.x + threadIdx.x;
   if (j >= n) return;
   const Slot& S = slots[index[j]];
   sources[j] = source[index[j]];
+  misses[j] = miss ? miss[index[j]] : 0u;
   pts[2 * (size_t)j] = S.a;
   pts[2 * (size_t)j + 1] = S.b;
   lsa_dense_voxel_t v;
@@ -375,6 +538,7 @@ struct lsa_dense_map
   double leaf = 0.1;
   Slot* slots = nullptr;
   int* source = nullptr;  // [capacity], beside the slots
+  unsigned* miss = nullptr;  // [2 * capacity] misses and miss-frame words, from the first carve on
   unsigned capacity = 0;
   unsigned initial_capacity = 1u << 16;
   size_t max_bytes = kDefaultMaxBytes;
@@ -398,17 +562,25 @@ struct lsa_dense_map
   int* totals = nullptr;  // device, 2 ints: the total and the compaction's aside slot
   u64* keys[2] = {nullptr, nullptr}; unsigned* index[2] = {nullptr, nullptr}; int keys_cap = 0;
   void* sort_tmp = nullptr; size_t sort_tmp_cap = 0;
-  lsa_point_t* out_pts = nullptr; lsa_dense_voxel_t* out_vox = nullptr; int* out_src = nullptr; int out_cap = 0;
+  lsa_point_t* out_pts = nullptr; lsa_dense_voxel_t* out_vox = nullptr; int* out_src = nullptr; unsigned* out_miss = nullptr; int out_cap = 0;
   double export_seconds = 0.;
   // re-projections (lsa_dense_map_reproject)
   int reprojections = 0;
   long long dropped = 0;  // voxels, since the last clear
   double reproject_seconds = 0.;
+  // free space (lsa_dense_map_carve_*, lsa_dense_map_prune)
+  double carve_margin_leaves = 2., carve_range = 30.;
+  int carve_stride = 1;
+  float* staged_origins = nullptr;  // lsa_dense_map_carve_points: the caller's origins on the device
+  int staged_origins_cap = 0;
+  double carve_seconds = 0.;  // the host's, of the last carve call: what enqueueing it cost
+  long long pruned = 0;       // voxels, since the last clear
+  int prunes = 0;
 };
 
 namespace
 {
-Table table_of(const lsa_dense_map* dm) { return Table{dm->slots, dm->source, dm->capacity - 1u, dm->stress}; }
+Table table_of(const lsa_dense_map* dm) { return Table{dm->slots, dm->source, dm->miss, dm->capacity - 1u, dm->stress}; }
 
 long long occupied_bound(lsa_dense_map* dm)
 {
@@ -427,32 +599,63 @@ long long occupied_bound(lsa_dense_map* dm)
   return (long long)dm->known + dm->pending_sum;
 }
 
-// a zeroed table of cap slots with its source array, zeroed behind what the stream holds; LSA_E_CAPACITY without memory
-int fresh_table(lsa_dense_map* dm, unsigned cap, Slot** slots, int** source, const char* who, const char* consequence)
+// a zeroed table of cap slots with its source array -- and, in a map that has been carved, its miss array --, zeroed behind
+// what the stream holds; LSA_E_CAPACITY without memory
+int fresh_table(lsa_dense_map* dm, unsigned cap, Slot** slots, int** source, unsigned** miss, const char* who, const char* consequence)
 {
   lsa_ctx* ctx = dm->ctx;
-  const size_t bytes = (size_t)cap * sizeof(Slot), source_bytes = (size_t)cap * sizeof(int);
+  const size_t bytes = (size_t)cap * sizeof(Slot), source_bytes = (size_t)cap * sizeof(int), miss_bytes = dm->miss ? (size_t)cap * 2 * sizeof(unsigned) : 0;
   *slots = nullptr;
   *source = nullptr;
-  if (hipMalloc((void**)slots, bytes) != hipSuccess || hipMalloc((void**)source, source_bytes) != hipSuccess)
+  *miss = nullptr;
+  if (hipMalloc((void**)slots, bytes) != hipSuccess || hipMalloc((void**)source, source_bytes) != hipSuccess ||
+      (miss_bytes && hipMalloc((void**)miss, miss_bytes) != hipSuccess))
   {
     (void)hipGetLastError();
     if (*slots) (void)hipFree(*slots);
+    if (*source) (void)hipFree(*source);
     *slots = nullptr;
-    return ctx->fail(LSA_E_CAPACITY, std::string(who) + ": no device memory for a table of " + std::to_string(bytes + source_bytes) + " bytes; " + consequence);
+    *source = nullptr;
+    *miss = nullptr;
+    return ctx->fail(LSA_E_CAPACITY, std::string(who) + ": no device memory for a table of " + std::to_string(bytes + source_bytes + miss_bytes) + " bytes; " + consequence);
   }
   hipError_t e = hipMemsetAsync(*slots, 0, bytes, dm->stream);
   if (e == hipSuccess) e = hipMemsetAsync(*source, 0, source_bytes, dm->stream);
+  if (e == hipSuccess && miss_bytes) e = hipMemsetAsync(*miss, 0, miss_bytes, dm->stream);
   if (e != hipSuccess)
   {
     (void)hipStreamSynchronize(dm->stream);
     (void)hipFree(*slots);
     (void)hipFree(*source);
+    if (*miss) (void)hipFree(*miss);
     *slots = nullptr;
     *source = nullptr;
+    *miss = nullptr;
     return ctx->fail(LSA_E_HIP, std::string(who) + ": hipMemsetAsync: " + hipGetErrorString(e));
   }
   return LSA_OK;
+}
+
+// the table `fresh` of `cap` slots takes what `keep` lets through of the map's and becomes the map's;
+// the old one goes to the graveyard, which launches in flight keep alive (freed by lsa_collect_garbage)
+void rehash_into(lsa_dense_map* dm, Slot* fresh, int* fresh_source, unsigned* fresh_miss, unsigned cap, const Keep& keep)
+{
+  lsa_ctx* ctx = dm->ctx;
+  Slot* old = dm->slots;
+  int* old_source = dm->source;
+  unsigned* old_miss = dm->miss;
+  const unsigned old_capacity = dm->capacity;
+  dm->slots = fresh;
+  dm->source = fresh_source;
+  if (fresh_miss) dm->miss = fresh_miss;
+  dm->capacity = cap;
+  if (!old) return;
+  ProfScope ps(ctx, "dense_rehash", (double)old_capacity * (sizeof(Slot) + sizeof(int)) * 2, dm->stream);
+  hipLaunchKernelGGL(k_dense_rehash, dim3((old_capacity + 255) / 256), dim3(256), 0, dm->stream, old, old_source, fresh_miss ? old_miss : nullptr, old_capacity, keep,
+                     table_of(dm), dm->stat);
+  retire_dev(ctx, old);
+  retire_dev(ctx, old_source);
+  if (fresh_miss) retire_dev(ctx, old_miss);
 }
 
 // the table with room for n more points: (bound of occupied slots) + n <= capacity / 2, by rehashing into a larger one
@@ -476,21 +679,10 @@ int make_room(lsa_dense_map* dm, long long n, const char* who)
                                          " voxels at most is over MaxBytes = " + std::to_string(dm->max_bytes) + "; nothing was inserted");
   Slot* fresh = nullptr;
   int* fresh_source = nullptr;
-  if (const int rc = fresh_table(dm, cap, &fresh, &fresh_source, who, "nothing was inserted")) return rc;
-  Slot* old = dm->slots;
-  int* old_source = dm->source;
-  const unsigned old_capacity = dm->capacity;
-  dm->slots = fresh;
-  dm->source = fresh_source;
-  dm->capacity = cap;
-  if (old)
-  {
-    ProfScope ps(ctx, "dense_rehash", (double)old_capacity * (sizeof(Slot) + sizeof(int)) * 2, dm->stream);
-    hipLaunchKernelGGL(k_dense_rehash, dim3((old_capacity + 255) / 256), dim3(256), 0, dm->stream, old, old_source, old_capacity, table_of(dm), dm->stat);
-    dm->rehashes++;
-    retire_dev(ctx, old);  // launches in flight keep it; freed by lsa_collect_garbage
-    retire_dev(ctx, old_source);
-  }
+  unsigned* fresh_miss = nullptr;
+  if (const int rc = fresh_table(dm, cap, &fresh, &fresh_source, &fresh_miss, who, "nothing was inserted")) return rc;
+  if (dm->slots) dm->rehashes++;
+  rehash_into(dm, fresh, fresh_source, fresh_miss, cap, Keep{nullptr, 0u, -1.});  // every voxel
   return LSA_OK;
 }
 
@@ -519,6 +711,54 @@ int insert_device_points(lsa_dense_map* dm, const lsa_point_t* src, int n, const
   return LSA_OK;
 }
 
+int carve_ordinal(lsa_dense_map* dm, int frame, const char* who)
+{
+  if (frame < dm->last_frame) return dm->ctx->fail(LSA_E_ARG, std::string(who) + ": frame ordinals must not decrease");
+  if (frame == INT32_MIN) return dm->ctx->fail(LSA_E_ARG, std::string(who) + ": the ordinal -2^31 is not carved (its word is the one for \"none\")");
+  // (the default range under a leaf so small that lsa_dense_map_set would have refused it)
+  if (!(dm->carve_range / dm->leaf <= kMaxRangeLeaves)) return dm->ctx->fail(LSA_E_ARG, std::string(who) + ": CarveRange is more than 4096 leaves");
+  return LSA_OK;
+}
+
+// one launch over the rays of n points at `src` (device): every "CarveStride"-th point's, from origins (device, unfused) or
+// from the frame's own origin under the point's pose (fused).  The first carve of a map makes its miss array.
+int carve_device_points(lsa_dense_map* dm, const lsa_point_t* src, int n, const FrameMove& m, const float* origins, int n_origins, int frame, const char* who)
+{
+  lsa_ctx* ctx = dm->ctx;
+  if (!dm->slots)
+  {
+    if (const int rc = make_room(dm, 0, who)) return rc;  // an empty table: the rays are counted all the same
+  }
+  if (!dm->miss)
+  {
+    const size_t bytes = (size_t)dm->capacity * 2 * sizeof(unsigned);
+    if (hipMalloc((void**)&dm->miss, bytes) != hipSuccess)
+    {
+      (void)hipGetLastError();
+      dm->miss = nullptr;
+      return ctx->fail(LSA_E_CAPACITY, std::string(who) + ": no device memory for " + std::to_string(bytes) + " bytes of misses; nothing was carved");
+    }
+    LSA_HIP(ctx, hipMemsetAsync(dm->miss, 0, bytes, dm->stream));
+  }
+  Carve c{};
+  c.origins = origins;
+  c.n_origins = n_origins;
+  c.stride = dm->carve_stride;
+  c.rays = (int)(((long long)n + c.stride - 1) / c.stride);
+  c.frame = frame;
+  c.leaf = dm->leaf;
+  c.margin = dm->carve_margin_leaves * dm->leaf;
+  c.range = dm->carve_range;
+  c.max_steps = 3ll * ((long long)std::ceil(dm->carve_range / dm->leaf) + 2ll);
+  {
+    // per ray 32 B (and 12 B of origin) read; per visited voxel an 8-byte key at least -- not known here
+    ProfScope ps(ctx, "dense_carve", (double)c.rays * 44, dm->stream);
+    hipLaunchKernelGGL(k_dense_carve, dim3((c.rays + 255) / 256), dim3(256), 0, dm->stream, reinterpret_cast<const float4*>(src), m, c, table_of(dm), dm->stat);
+  }
+  dm->last_frame = frame;
+  return LSA_OK;
+}
+
 // waits for the insertions in flight; a probe sequence that ran out is reported here
 int settle(lsa_dense_map* dm, const char* who)
 {
@@ -530,17 +770,17 @@ int settle(lsa_dense_map* dm, const char* who)
   return LSA_OK;
 }
 
-// the voxels with frames >= min_frames in ascending key order, left in dm->out_pts / out_vox / out_src; returns their number
-int export_sorted(lsa_dense_map* dm, int min_frames, const char* who)
+Keep keep_of(const lsa_dense_map* dm, int min_frames, double max_miss_ratio) { return Keep{dm->miss, (unsigned)std::max(min_frames, 0), max_miss_ratio}; }
+
+// keys and slot indices of the voxels that pass, in slot order, left in dm->keys[0] / index[0]; returns their number.  The
+// map must be settled.
+int compact_kept(lsa_dense_map* dm, int min_frames, double max_miss_ratio)
 {
   lsa_ctx* ctx = dm->ctx;
-  int rc = settle(dm, who);
-  if (rc) return rc;
   const int occupied = (int)occupied_bound(dm);  // exact: everything enqueued has been published
   if (occupied <= 0 || !dm->slots) return 0;
   const int nchunks = (int)((dm->capacity + 1023u) / 1024u);
-  rc = scratch_room(ctx, &dm->chunks, (int**)nullptr, &dm->chunks_cap, (size_t)nchunks, 64);
-  if (rc) return rc;
+  if (const int rc = scratch_room(ctx, &dm->chunks, (int**)nullptr, &dm->chunks_cap, (size_t)nchunks, 64)) return rc;
   if (occupied > dm->keys_cap)
   {
     for (int b = 0; b < 2; ++b) { retire_dev(ctx, dm->keys[b]); retire_dev(ctx, dm->index[b]); dm->keys[b] = nullptr; dm->index[b] = nullptr; }
@@ -554,12 +794,23 @@ int export_sorted(lsa_dense_map* dm, int min_frames, const char* who)
     dm->keys_cap = (int)want;
   }
   const Slot* slots = dm->slots;
-  stable_compact(dm->stream, dm->chunks, dm->totals + 1, ExportPred{slots, (unsigned)std::max(min_frames, 0)}, ExportEmit{slots, dm->keys[0], dm->index[0]},
+  stable_compact(dm->stream, dm->chunks, dm->totals + 1, ExportPred{slots, keep_of(dm, min_frames, max_miss_ratio)}, ExportEmit{slots, dm->keys[0], dm->index[0]},
                  (const int*)nullptr, (int)dm->capacity, dm->totals);
   int kept = 0;
   LSA_HIP(ctx, hipMemcpyAsync(&kept, dm->totals, sizeof(int), hipMemcpyDeviceToHost, dm->stream));
   LSA_HIP(ctx, hipStreamSynchronize(dm->stream));
-  if (kept <= 0) return 0;
+  return std::max(kept, 0);
+}
+
+// the voxels that pass (Keep) in ascending key order, left in dm->out_pts / out_vox / out_src / out_miss; returns their number
+int export_sorted(lsa_dense_map* dm, int min_frames, double max_miss_ratio, const char* who)
+{
+  lsa_ctx* ctx = dm->ctx;
+  const int rc = settle(dm, who);
+  if (rc) return rc;
+  const int kept = compact_kept(dm, min_frames, max_miss_ratio);
+  if (kept <= 0) return kept;
+  const Slot* slots = dm->slots;
   size_t tmp_bytes = 0;
   LSA_HIP(ctx, rocprim::radix_sort_pairs(nullptr, tmp_bytes, dm->keys[0], dm->keys[1], dm->index[0], dm->index[1], (size_t)kept, 0u, 63u, dm->stream));
   if (tmp_bytes > dm->sort_tmp_cap)
@@ -576,15 +827,17 @@ int export_sorted(lsa_dense_map* dm, int min_frames, const char* who)
     retire_dev(ctx, dm->out_pts);
     retire_dev(ctx, dm->out_vox);
     retire_dev(ctx, dm->out_src);
-    dm->out_pts = nullptr; dm->out_vox = nullptr; dm->out_src = nullptr; dm->out_cap = 0;
+    retire_dev(ctx, dm->out_miss);
+    dm->out_pts = nullptr; dm->out_vox = nullptr; dm->out_src = nullptr; dm->out_miss = nullptr; dm->out_cap = 0;
     const size_t want = (size_t)kept + (size_t)kept / 2;
     LSA_HIP(ctx, hipMalloc((void**)&dm->out_pts, want * sizeof(lsa_point_t)));
     LSA_HIP(ctx, hipMalloc((void**)&dm->out_vox, want * sizeof(lsa_dense_voxel_t)));
     LSA_HIP(ctx, hipMalloc((void**)&dm->out_src, want * sizeof(int)));
+    LSA_HIP(ctx, hipMalloc((void**)&dm->out_miss, want * sizeof(unsigned)));
     dm->out_cap = (int)want;
   }
-  hipLaunchKernelGGL(k_dense_gather, dim3((kept + 255) / 256), dim3(256), 0, dm->stream, slots, dm->source, dm->keys[1], dm->index[1], kept,
-                     reinterpret_cast<float4*>(dm->out_pts), dm->out_vox, dm->out_src);
+  hipLaunchKernelGGL(k_dense_gather, dim3((kept + 255) / 256), dim3(256), 0, dm->stream, slots, dm->source, dm->miss, dm->keys[1], dm->index[1], kept,
+                     reinterpret_cast<float4*>(dm->out_pts), dm->out_vox, dm->out_src, dm->out_miss);
   return kept;
 }
 
@@ -626,7 +879,7 @@ void lsa_dense_map_destroy(lsa_dense_map* dm)
   (void)hipSetDevice(dm->ctx->device);
   if (dm->stream) (void)hipStreamSynchronize(dm->stream);
   auto fr = [](void* p) { if (p) (void)hipFree(p); };
-  fr(dm->slots); fr(dm->source); fr(dm->stat); fr(dm->slot_of); fr(dm->staged); fr(dm->chunks); fr(dm->totals);
+  fr(dm->slots); fr(dm->source); fr(dm->miss); fr(dm->staged_origins); fr(dm->out_miss); fr(dm->stat); fr(dm->slot_of); fr(dm->staged); fr(dm->chunks); fr(dm->totals);
   for (int b = 0; b < 2; ++b) { fr(dm->keys[b]); fr(dm->index[b]); }
   fr(dm->sort_tmp); fr(dm->out_pts); fr(dm->out_vox); fr(dm->out_src);
   if (dm->host_words) (void)hipHostFree(dm->host_words);
@@ -665,6 +918,25 @@ int lsa_dense_map_set(lsa_dense_map* dm, const char* name, double value)
     dm->stress = value != 0. ? 1 : 0;
     return LSA_OK;
   }
+  if (n == "CarveMarginLeaves")
+  {
+    if (!(value >= 0.) || !std::isfinite(value)) return ctx->fail(LSA_E_ARG, "lsa_dense_map_set: CarveMarginLeaves >= 0");
+    dm->carve_margin_leaves = value;
+    return LSA_OK;
+  }
+  if (n == "CarveRange")
+  {
+    // the bound of every ray's walk: 3 * (CarveRange / leaf + 2) steps
+    if (!(value > 0.) || !(value / dm->leaf <= kMaxRangeLeaves)) return ctx->fail(LSA_E_ARG, "lsa_dense_map_set: CarveRange positive and at most 4096 leaves");
+    dm->carve_range = value;
+    return LSA_OK;
+  }
+  if (n == "CarveStride")
+  {
+    if (!(value >= 1.) || value > 1e9 || value != std::floor(value)) return ctx->fail(LSA_E_ARG, "lsa_dense_map_set: CarveStride a whole number >= 1");
+    dm->carve_stride = (int)value;
+    return LSA_OK;
+  }
   return ctx->fail(LSA_E_ARG, "lsa_dense_map_set: unknown parameter " + n);
 }
 
@@ -682,6 +954,20 @@ double lsa_dense_map_get_param(lsa_dense_map* dm, const char* name)
   if (n == "Reprojections") return dm->reprojections;
   if (n == "Dropped") return (double)dm->dropped;
   if (n == "ReprojectSeconds") return dm->reproject_seconds;
+  if (n == "CarveMarginLeaves") return dm->carve_margin_leaves;
+  if (n == "CarveRange") return dm->carve_range;
+  if (n == "CarveStride") return dm->carve_stride;
+  if (n == "CarveSeconds") return dm->carve_seconds;
+  if (n == "Pruned") return (double)dm->pruned;
+  if (n == "Prunes") return dm->prunes;
+  if (n == "Rays")
+  {
+    // the device's word, behind the carves in flight
+    u64 rays = 0;
+    if (settle(dm, "lsa_dense_map_get_param") != LSA_OK) return -1.;
+    if (hipMemcpy(&rays, dm->stat + kStatRays, sizeof(u64), hipMemcpyDeviceToHost) != hipSuccess) return -1.;
+    return (double)rays;
+  }
   return -1.;
 }
 
@@ -730,6 +1016,96 @@ int lsa_dense_map_insert_frame(lsa_dense_map* dm, int interpolate, const double 
   return LSA_OK;
 }
 
+int lsa_dense_map_carve_points(lsa_dense_map* dm, const lsa_point_t* pts, int n, const float* origins_xyz, int n_origins, int frame)
+{
+  if (!dm) return LSA_E_ARG;
+  lsa_ctx* ctx = dm->ctx;
+  const char* who = "lsa_dense_map_carve_points";
+  if (n < 0 || (n > 0 && (!pts || !origins_xyz)) || (n > 0 && n_origins != 1 && n_origins != n)) return ctx->fail(LSA_E_ARG, std::string(who) + ": bad argument (one origin, or one per point)");
+  if (const int rc = carve_ordinal(dm, frame, who)) return rc;
+  if (n == 0) { dm->last_frame = frame; return LSA_OK; }
+  const double t0 = now_seconds();
+  LSA_HIP(ctx, hipSetDevice(ctx->device));
+  int rc = scratch_room(ctx, &dm->staged, (lsa_point_t**)nullptr, &dm->staged_cap, (size_t)n, 4096);
+  if (rc) return rc;
+  rc = scratch_room(ctx, &dm->staged_origins, (float**)nullptr, &dm->staged_origins_cap, (size_t)n_origins * 3, 3 * 4096);
+  if (rc) return rc;
+  LSA_HIP(ctx, hipMemcpyAsync(dm->staged, pts, (size_t)n * sizeof(lsa_point_t), hipMemcpyHostToDevice, dm->stream));
+  LSA_HIP(ctx, hipMemcpyAsync(dm->staged_origins, origins_xyz, (size_t)n_origins * 3 * sizeof(float), hipMemcpyHostToDevice, dm->stream));
+  LSA_HIP(ctx, hipStreamSynchronize(dm->stream));  // both may be pageable and reused by the caller
+  FrameMove m{};
+  rc = carve_device_points(dm, dm->staged, n, m, dm->staged_origins, n_origins, frame, who);
+  dm->carve_seconds = now_seconds() - t0;
+  return rc;
+}
+
+int lsa_dense_map_carve_frame(lsa_dense_map* dm, int interpolate, const double H0[16], const double H1[16], double t0, double t1, double time_offset, int frame)
+{
+  if (!dm) return LSA_E_ARG;
+  lsa_ctx* ctx = dm->ctx;
+  const char* who = "lsa_dense_map_carve_frame";
+  if (!H0 || (interpolate && !H1)) return ctx->fail(LSA_E_ARG, std::string(who) + ": bad argument");
+  if (!ctx->frame || ctx->frame_n <= 0) return ctx->fail(LSA_E_STATE, std::string(who) + ": no frame");
+  if (const int rc = carve_ordinal(dm, frame, who)) return rc;
+  const double started = now_seconds();
+  LSA_HIP(ctx, hipSetDevice(ctx->device));
+  FrameMove m{};
+  m.fused = 1;
+  m.interpolate = interpolate ? 1 : 0;
+  row_major_to_rt(H0, m.R.R, m.R.t);
+  if (interpolate) m.c = make_interp_const(H0, H1, t0, t1);
+  m.time_offset = time_offset;
+  // as the fused insertion: the frame as the context's stream has left it, held by an event its next writer waits for --
+  // recorded behind the carve, which reads the buffer last
+  LSA_HIP(ctx, hipEventRecord(dm->ev_frame, ctx->stream));
+  LSA_HIP(ctx, hipStreamWaitEvent(dm->stream, dm->ev_frame, 0));
+  const int rc = carve_device_points(dm, ctx->frame, ctx->frame_n, m, nullptr, 0, frame, who);
+  if (rc) return rc;
+  LSA_HIP(ctx, hipEventRecord(ctx->ev_dense, dm->stream));
+  ctx->dense_frame_pending = true;
+  dm->carve_seconds = now_seconds() - started;
+  return LSA_OK;
+}
+
+int lsa_dense_map_prune(lsa_dense_map* dm, int min_frames, double max_miss_ratio, long long* removed)
+{
+  if (!dm) return LSA_E_ARG;
+  lsa_ctx* ctx = dm->ctx;
+  const char* who = "lsa_dense_map_prune";
+  if (!removed) return ctx->fail(LSA_E_ARG, std::string(who) + ": bad argument");
+  *removed = 0;
+  int rc = settle(dm, who);
+  if (rc) return rc;
+  const long long occupied = occupied_bound(dm);  // exact after settle
+  dm->prunes++;
+  if (!dm->slots || occupied <= 0) return LSA_OK;
+  const int kept = compact_kept(dm, min_frames, max_miss_ratio);
+  if (kept < 0) return kept;
+  if (kept == occupied) return LSA_OK;  // nothing to remove: the table stays
+  unsigned cap = kMinCapacity;
+  while ((long long)(cap / 2) < (long long)kept) cap *= 2;  // kept <= occupied <= capacity / 2: never above the table's own
+  Slot* fresh = nullptr;
+  int* fresh_source = nullptr;
+  unsigned* fresh_miss = nullptr;
+  rc = fresh_table(dm, cap, &fresh, &fresh_source, &fresh_miss, who, "the map is as it was");
+  if (rc) return rc;
+  const Keep keep = keep_of(dm, min_frames, max_miss_ratio);  // reads the old miss array
+  rehash_into(dm, fresh, fresh_source, fresh_miss, cap, keep);
+  const unsigned serial = dm->next_serial++;
+  hipLaunchKernelGGL(k_dense_publish, dim3(1), dim3(64), 0, dm->stream, dm->stat, dm->host_words, serial, (unsigned)kept);
+  LSA_HIP(ctx, hipGetLastError());
+  LSA_HIP(ctx, hipStreamSynchronize(dm->stream));
+  dm->seen_serial = serial;
+  dm->known = (unsigned)kept;
+  dm->pending.clear();
+  dm->pending_sum = 0;
+  *removed = occupied - kept;
+  dm->pruned += *removed;
+  if (__atomic_load_n(&dm->host_words[1], __ATOMIC_ACQUIRE) != 0ull)
+    return ctx->fail(LSA_E_STATE, std::string(who) + ": a probe sequence ran through the whole table (the map is incomplete; lsa_dense_map_clear starts again)");
+  return LSA_OK;
+}
+
 int lsa_dense_map_reserve(lsa_dense_map* dm, long long n)
 {
   if (!dm) return LSA_E_ARG;
@@ -756,16 +1132,21 @@ long long lsa_dense_map_skipped(lsa_dense_map* dm)
 long long lsa_dense_map_bytes(const lsa_dense_map* dm)
 {
   if (!dm) return LSA_E_ARG;
-  return (long long)dm->capacity * (long long)(sizeof(Slot) + sizeof(int)) + (long long)dm->slot_cap * (long long)sizeof(int);
+  return (long long)dm->capacity * (long long)(sizeof(Slot) + sizeof(int) + (dm->miss ? 2 * sizeof(unsigned) : 0)) + (long long)dm->slot_cap * (long long)sizeof(int);
 }
 
 int lsa_dense_map_get(lsa_dense_map* dm, int min_frames, lsa_point_t* pts, lsa_dense_voxel_t* voxels, int capacity)
+{
+  return lsa_dense_map_get_filtered(dm, min_frames, -1., pts, voxels, capacity);
+}
+
+int lsa_dense_map_get_filtered(lsa_dense_map* dm, int min_frames, double max_miss_ratio, lsa_point_t* pts, lsa_dense_voxel_t* voxels, int capacity)
 {
   if (!dm) return LSA_E_ARG;
   lsa_ctx* ctx = dm->ctx;
   if (capacity < 0) return ctx->fail(LSA_E_ARG, "lsa_dense_map_get: bad argument");
   const double t0 = now_seconds();
-  const int kept = export_sorted(dm, min_frames, "lsa_dense_map_get");
+  const int kept = export_sorted(dm, min_frames, max_miss_ratio, "lsa_dense_map_get");
   if (kept <= 0) return kept;
   const int n = std::min(kept, capacity);
   if (n > 0 && pts) LSA_HIP(ctx, hipMemcpyAsync(pts, dm->out_pts, (size_t)n * sizeof(lsa_point_t), hipMemcpyDeviceToHost, dm->stream));
@@ -777,10 +1158,28 @@ int lsa_dense_map_get(lsa_dense_map* dm, int min_frames, lsa_point_t* pts, lsa_d
 
 int lsa_dense_map_get_sources(lsa_dense_map* dm, int min_frames, int* out, int capacity)
 {
+  return lsa_dense_map_get_sources_filtered(dm, min_frames, -1., out, capacity);
+}
+
+int lsa_dense_map_get_misses(lsa_dense_map* dm, int min_frames, double max_miss_ratio, uint32_t* out, int capacity)
+{
+  if (!dm) return LSA_E_ARG;
+  lsa_ctx* ctx = dm->ctx;
+  if (capacity < 0) return ctx->fail(LSA_E_ARG, "lsa_dense_map_get_misses: bad argument");
+  const int kept = export_sorted(dm, min_frames, max_miss_ratio, "lsa_dense_map_get_misses");
+  if (kept <= 0) return kept;
+  const int n = std::min(kept, capacity);
+  if (n > 0 && out) LSA_HIP(ctx, hipMemcpyAsync(out, dm->out_miss, (size_t)n * sizeof(unsigned), hipMemcpyDeviceToHost, dm->stream));
+  LSA_HIP(ctx, hipStreamSynchronize(dm->stream));
+  return kept;
+}
+
+int lsa_dense_map_get_sources_filtered(lsa_dense_map* dm, int min_frames, double max_miss_ratio, int* out, int capacity)
+{
   if (!dm) return LSA_E_ARG;
   lsa_ctx* ctx = dm->ctx;
   if (capacity < 0) return ctx->fail(LSA_E_ARG, "lsa_dense_map_get_sources: bad argument");
-  const int kept = export_sorted(dm, min_frames, "lsa_dense_map_get_sources");
+  const int kept = export_sorted(dm, min_frames, max_miss_ratio, "lsa_dense_map_get_sources");
   if (kept <= 0) return kept;
   const int n = std::min(kept, capacity);
   if (n > 0 && out) LSA_HIP(ctx, hipMemcpyAsync(out, dm->out_src, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, dm->stream));
@@ -818,7 +1217,8 @@ int lsa_dense_map_reproject(lsa_dense_map* dm, const double* corrections16, int 
   }
   Slot* fresh = nullptr;
   int* fresh_source = nullptr;
-  rc = fresh_table(dm, cap, &fresh, &fresh_source, who, "the map is as it was");
+  unsigned* fresh_miss = nullptr;
+  rc = fresh_table(dm, cap, &fresh, &fresh_source, &fresh_miss, who, "the map is as it was");
   if (rc)
   {
     (void)hipFree(corrections);
@@ -828,6 +1228,7 @@ int lsa_dense_map_reproject(lsa_dense_map* dm, const double* corrections16, int 
   Reproject r;
   r.old = dm->slots;
   r.old_source = dm->source;
+  r.old_miss = fresh_miss ? dm->miss : nullptr;
   r.old_capacity = cap;
   r.corrections = corrections;
   r.first_frame = first_frame;
@@ -839,8 +1240,10 @@ int lsa_dense_map_reproject(lsa_dense_map* dm, const double* corrections16, int 
   // from here on the old table belongs to the graveyard and the new one is the map's, whatever a launch answers
   Slot* old = dm->slots;
   int* old_source = dm->source;
+  unsigned* old_miss = fresh_miss ? dm->miss : nullptr;
   dm->slots = fresh;
   dm->source = fresh_source;
+  if (fresh_miss) dm->miss = fresh_miss;
   const Table t = table_of(dm);
   const unsigned serial = dm->next_serial++;
   const dim3 grid((cap + 255) / 256);
@@ -870,6 +1273,7 @@ int lsa_dense_map_reproject(lsa_dense_map* dm, const double* corrections16, int 
   if (e == hipSuccess) e = hipStreamSynchronize(dm->stream);  // the count of the dropped is the call's answer
   retire_dev(ctx, old);
   retire_dev(ctx, old_source);
+  retire_dev(ctx, old_miss);
   retire_dev(ctx, corrections);
   retire_dev(ctx, scratch);
   if (e != hipSuccess) return ctx->fail(LSA_E_HIP, std::string(who) + ": " + hipGetErrorString(e));
@@ -895,6 +1299,7 @@ int lsa_dense_map_clear(lsa_dense_map* dm)
   LSA_HIP(ctx, hipSetDevice(ctx->device));
   if (dm->slots) LSA_HIP(ctx, hipMemsetAsync(dm->slots, 0, (size_t)dm->capacity * sizeof(Slot), dm->stream));
   if (dm->source) LSA_HIP(ctx, hipMemsetAsync(dm->source, 0, (size_t)dm->capacity * sizeof(int), dm->stream));
+  if (dm->miss) LSA_HIP(ctx, hipMemsetAsync(dm->miss, 0, (size_t)dm->capacity * 2 * sizeof(unsigned), dm->stream));
   LSA_HIP(ctx, hipMemsetAsync(dm->stat, 0, kStatWords * sizeof(u64), dm->stream));
   // what insertions before the clear still publish is older than the epoch and ignored; the error word goes with them
   LSA_HIP(ctx, hipStreamSynchronize(dm->stream));
@@ -906,10 +1311,16 @@ int lsa_dense_map_clear(lsa_dense_map* dm)
   dm->pending_sum = 0;
   dm->last_frame = INT32_MIN;
   dm->dropped = 0;
+  dm->pruned = 0;
   return LSA_OK;
 }
 
 int lsa_dense_map_save_pcd(lsa_dense_map* dm, const char* path, int format, int min_frames)
+{
+  return lsa_dense_map_save_pcd_filtered(dm, path, format, min_frames, -1.);
+}
+
+int lsa_dense_map_save_pcd_filtered(lsa_dense_map* dm, const char* path, int format, int min_frames, double max_miss_ratio)
 {
   if (!dm) return LSA_E_ARG;
   lsa_ctx* ctx = dm->ctx;
@@ -920,7 +1331,7 @@ int lsa_dense_map_save_pcd(lsa_dense_map* dm, const char* path, int format, int 
     double* T = ctx->pcd_times;
     std::fill(T, T + 8, 0.);
     const double t0 = now_seconds();
-    const int kept = export_sorted(dm, min_frames, "lsa_dense_map_save_pcd");
+    const int kept = export_sorted(dm, min_frames, max_miss_ratio, "lsa_dense_map_save_pcd");
     if (kept < 0) return kept;
     T[4] = now_seconds() - t0;
     return pcd_save_device_points(ctx, dm->stream, dm->out_pts, kept, path, format);

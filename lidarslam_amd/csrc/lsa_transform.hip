@@ -60,6 +60,21 @@ __global__ __launch_bounds__(256) void k_transform_out(const float4* __restrict_
   out[2 * (size_t)i + 1] = b;
 }
 
+// where the sensor stood when it measured each point: the frame's own origin under the point's pose, float xyz -- the
+// origins of the dense map's fused carve (lsa_dense_map.hip), by the same statement
+__global__ __launch_bounds__(256) void k_frame_origins(const float4* __restrict__ in, int n, int interpolate, InterpConst c, Rigid R, double time_offset,
+                                                       float* __restrict__ out)
+{
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  float4 a = make_float4(0.f, 0.f, 0.f, in[2 * (size_t)i].w);
+  float4 b = in[2 * (size_t)i + 1];
+  frame_point_to_world(a, b, interpolate, c, R, time_offset);
+  out[3 * (size_t)i] = a.x;
+  out[3 * (size_t)i + 1] = a.y;
+  out[3 * (size_t)i + 2] = a.z;
+}
+
 // the three keypoint types of a set in one launch, written straight into pinned host memory (blockIdx.y = type)
 struct StageOut
 {
@@ -573,6 +588,27 @@ int lsa_transform_frame_at(lsa_ctx* ctx, int interpolate, const double H0[16], c
                        time_offset, reinterpret_cast<float4*>(ctx->scratch_out));
   }
   LSA_HIP(ctx, hipMemcpyAsync(out, ctx->scratch_out, (size_t)n * sizeof(lsa_point_t), hipMemcpyDeviceToHost, ctx->stream));
+  LSA_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return n;
+}
+
+int lsa_transform_frame_origins_at(lsa_ctx* ctx, int interpolate, const double H0[16], const double H1[16], double t0, double t1, double time_offset,
+                                   float* xyz, int capacity)
+{
+  if (!ctx || !H0 || (interpolate && !H1) || !xyz) return ctx ? ctx->fail(LSA_E_ARG, "lsa_transform_frame_origins_at: bad argument") : LSA_E_ARG;
+  if (!ctx->frame || ctx->frame_n <= 0) return ctx->fail(LSA_E_STATE, "lsa_transform_frame_origins_at: no frame");
+  LSA_HIP(ctx, hipSetDevice(ctx->device));
+  const int n = ctx->frame_n;
+  if (capacity < n) return ctx->fail(LSA_E_CAPACITY, "lsa_transform_frame_origins_at: capacity < frame size");
+  int rc = ensure_scratch(ctx, (size_t)n * 3 * sizeof(float));
+  if (rc) return rc;
+  Rigid T;
+  row_major_to_rt(H0, T.R, T.t);
+  InterpConst c{};
+  if (interpolate) c = make_interp(H0, H1, t0, t1);
+  hipLaunchKernelGGL(k_frame_origins, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, reinterpret_cast<const float4*>(ctx->frame), n, interpolate, c, T,
+                     time_offset, reinterpret_cast<float*>(ctx->scratch_out));
+  LSA_HIP(ctx, hipMemcpyAsync(xyz, ctx->scratch_out, (size_t)n * 3 * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
   LSA_HIP(ctx, hipStreamSynchronize(ctx->stream));
   return n;
 }

@@ -806,6 +806,67 @@ public:
     const int rc = lsa_slam_clear_dense_map(this->Handle);
     this->LastError = rc < 0 ? std::string("ClearDenseMap: ") + lsa_slam_last_error(this->Handle) : std::string();
   }
+  // Free space: with SetDenseMapCarve(1) the ray of every inserted point, from where the sensor stood when it measured the
+  // point to CarveMarginLeaves voxels before it (CarveRange metres at most, every CarveStride-th point), is walked through the
+  // voxel grid on the device, and a voxel it passes through that the same frame did not hit counts one miss for the frame.
+  // maxMissRatio: only voxels with misses <= maxMissRatio * frames (below 0: all) -- what moved away is seen through more often
+  // than it was seen.  PruneDenseMap removes the others from the table for good and returns their number (negative on failure).
+  void SetDenseMapCarve(int on) { this->SetParam("DenseMapCarve", on); }
+  int GetDenseMapCarve() const { return static_cast<int>(this->GetParam("DenseMapCarve")); }
+  void SetDenseMapCarveRange(double metres) { this->SetParam("DenseMapCarveRange", metres); }
+  void SetDenseMapCarveMarginLeaves(double leaves) { this->SetParam("DenseMapCarveMarginLeaves", leaves); }
+  void SetDenseMapCarveStride(int stride) { this->SetParam("DenseMapCarveStride", stride); }
+  PointCloud::Ptr GetDenseMap(int minFrames, double maxMissRatio)
+  {
+    PointCloud::Ptr pc(new PointCloud);
+    pc->header.stamp = this->CurrentStamp;
+    pc->header.frame_id = this->WorldFrameId;
+    int n = lsa_slam_dense_map_size(this->Handle);
+    if (n > 0)
+    {
+      pc->points.resize(static_cast<std::size_t>(n));
+      n = lsa_slam_get_dense_map_filtered(this->Handle, minFrames, maxMissRatio, reinterpret_cast<lsa_point_t*>(pc->points.data()), nullptr, n);
+      pc->points.resize(static_cast<std::size_t>(std::max(n, 0)));
+    }
+    this->LastError = n < 0 ? std::string("GetDenseMap: ") + lsa_slam_last_error(this->Handle) : std::string();
+    return pc;
+  }
+  // per point of GetDenseMap(minFrames, maxMissRatio), in its order: the frames whose rays passed through its voxel
+  std::vector<std::uint32_t> GetDenseMapMisses(int minFrames = 1, double maxMissRatio = -1.)
+  {
+    std::vector<std::uint32_t> out;
+    int n = lsa_slam_dense_map_size(this->Handle);
+    if (n > 0)
+    {
+      out.resize(static_cast<std::size_t>(n));
+      n = lsa_slam_get_dense_map_misses(this->Handle, minFrames, maxMissRatio, out.data(), n);
+      out.resize(static_cast<std::size_t>(std::max(n, 0)));
+    }
+    this->LastError = n < 0 ? std::string("GetDenseMapMisses: ") + lsa_slam_last_error(this->Handle) : std::string();
+    return out;
+  }
+  int SaveDenseMapToPCD(const std::string& path, PCDFormat pcdFormat, int minFrames, double maxMissRatio) const
+  {
+    const int rc = lsa_slam_save_dense_map_pcd_filtered(this->Handle, path.c_str(), static_cast<int>(pcdFormat), minFrames, maxMissRatio);
+    this->LastError = rc < 0 ? std::string("SaveDenseMapToPCD: ") + lsa_slam_last_error(this->Handle) : std::string();
+    return rc;
+  }
+  long long PruneDenseMap(int minFrames = 1, double maxMissRatio = 1.)
+  {
+    long long removed = 0;
+    const int rc = lsa_slam_prune_dense_map(this->Handle, minFrames, maxMissRatio, &removed);
+    this->LastError = rc < 0 ? std::string("PruneDenseMap: ") + lsa_slam_last_error(this->Handle) : std::string();
+    return rc < 0 ? rc : removed;
+  }
+  // float xyz per point of GetRegisteredFrame(), in its order: where the sensor stood when it measured the point
+  std::vector<float> GetRegisteredFrameOrigins()
+  {
+    std::vector<float> out(3 * (static_cast<std::size_t>(1) << 19));
+    int n = lsa_slam_get_registered_frame_origins(this->Handle, out.data(), static_cast<int>(out.size() / 3));
+    out.resize(3 * static_cast<std::size_t>(std::max(n, 0)));
+    this->LastError = n < 0 ? std::string("GetRegisteredFrameOrigins: ") + lsa_slam_last_error(this->Handle) : std::string();
+    return out;
+  }
 
   // ---- keypoint extractor parameters (SpinningSensorKeypointExtractor.h:44-70); one extractor (device 0)
   LSA_SLAM_PARAM(NeighborWidth, int)

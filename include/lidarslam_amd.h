@@ -1277,6 +1277,33 @@ int lsa_dense_map_get_sources_filtered(lsa_dense_map* dm, int min_frames, double
 int lsa_dense_map_get_misses(lsa_dense_map* dm, int min_frames, double max_miss_ratio, uint32_t* out, int capacity);
 int lsa_dense_map_prune(lsa_dense_map* dm, int min_frames, double max_miss_ratio, long long* removed);
 int lsa_dense_map_save_pcd_filtered(lsa_dense_map* dm, const char* path, int format, int min_frames, double max_miss_ratio);
+/* Normals (DenseMapHost.normals is the statement, held byte for byte): one record per voxel of _get_filtered(min_frames,
+ * max_miss_ratio), in its order, computed from the table as it stands -- nothing is stored, no state changes.  For a voxel of
+ * index (ix, iy, iz) and point p the cells (ix+dx, iy+dy, iz+dz), dz, dy, dx in -radius_leaves .. radius_leaves with dx fastest,
+ * are visited (none with an index outside [-2^20, 2^20)); a cell is a neighbour when its voxel exists and passes the same
+ * predicate, the voxel itself among them.  In double, from +0.0, without contraction, in that order: d = q - p, s += d, S_ab
+ * += d_a * d_b, k = neighbors.  k < min_neighbors: the four floats are the quiet NaN 0x7fc00000 (PCL's "no normal").  Else
+ * C_ab = S_ab / k - (s_a / k) * (s_b / k), pcl::eigen33 in double gives l0 <= l1 <= l2 and e0 (not finite: that NaN); with
+ * n_viewpoints > 0 the voxel takes viewpoint clamp(source - first_frame, 0, n_viewpoints - 1) and e0 is negated when (e0 .
+ * (viewpoint - p)) < 0; normal = (float)e0, curvature = (float)|l0 / (l0 + l1 + l2)| (0 when the sum is not positive).
+ * LSA_E_ARG, the map untouched: radius_leaves not 1 or 2, min_neighbors < 3 or > (2 radius_leaves + 1)^3, min_frames < 1,
+ * n_viewpoints < 0 or viewpoints missing.  Two launches behind the export's compaction and sort (k_dense_normals: a group of 32
+ * lanes a voxel for the sums; k_dense_normal_records: one thread a voxel for the rest), one upload of the viewpoints; the call
+ * waits and returns the count under _get_filtered's capacity rules.
+ * get_param: "NormalsSeconds" (the last call).  _save_pcd_normals: the points of _save_pcd_filtered with the fields normal_x
+ * normal_y normal_z curvature behind the LidarPoint's eight (44-byte records; "nan" in ascii); lsa_pcd_read gives the points of
+ * such a file as of any other, lsa_pcd_read_normals the four floats per point (LSA_E_ARG, the reason in lsa_pcd_last_error,
+ * when one of the four fields is missing or is not a 4-byte F). */
+typedef struct lsa_dense_normal_t
+{
+  float nx, ny, nz, curvature;
+  uint32_t neighbors;
+} lsa_dense_normal_t;
+int lsa_dense_map_get_normals(lsa_dense_map* dm, int min_frames, double max_miss_ratio, int radius_leaves, int min_neighbors, const float* viewpoints_xyz,
+                              int n_viewpoints, int first_frame, lsa_dense_normal_t* out, int capacity);
+int lsa_dense_map_save_pcd_normals(lsa_dense_map* dm, const char* path, int format, int min_frames, double max_miss_ratio, int radius_leaves, int min_neighbors,
+                                   const float* viewpoints_xyz, int n_viewpoints, int first_frame);
+int lsa_pcd_read_normals(const char* path, float* out4, int capacity);
 /* The pipeline's dense map (lsa_slam_set_param "DenseMap": 0 off, the default, under which nothing whatever changes; 1 every
  * registered frame; 2 keyframes only; "DenseMapLeafSize", default 0.1; "DenseMapMaxBytes"; read-only "DenseMapVoxels",
  * "DenseMapBytes", "DenseMapSkipped", "DenseMapRefusedFrames", "DenseMapClears").  At the end of AddFrame(s) the frame or frames of the
@@ -1315,6 +1342,15 @@ int lsa_slam_get_dense_map_misses(lsa_slam* s, int min_frames, double max_miss_r
 int lsa_slam_save_dense_map_pcd_filtered(lsa_slam* s, const char* path, int format, int min_frames, double max_miss_ratio);
 int lsa_slam_prune_dense_map(lsa_slam* s, int min_frames, double max_miss_ratio, long long* removed);
 int lsa_slam_get_registered_frame_origins(lsa_slam* s, float* xyz, int capacity);
+/* Normals of the pipeline's map: with "DenseMap" on, every inserted ordinal keeps its viewpoint (12 B a frame on the host): the
+ * translation of Tworld * BaseToLidarOffset(device of the call's first frame), narrowed to float; what clears the map clears
+ * the list, and under "DenseMapOnTrajectory" 1 an applied trajectory moves each viewpoint by the correction its ordinal's
+ * voxels take, in the arithmetic of the re-projection.  _get_dense_map_viewpoints hands the list out (the count; *first_frame:
+ * the ordinal of entry 0).  _get_dense_map_normals / _save_dense_map_pcd_normals: the map's calls, with these viewpoints
+ * when `orient` is not 0 and none otherwise. */
+int lsa_slam_get_dense_map_normals(lsa_slam* s, int min_frames, double max_miss_ratio, int radius_leaves, int min_neighbors, int orient, lsa_dense_normal_t* out, int capacity);
+int lsa_slam_save_dense_map_pcd_normals(lsa_slam* s, const char* path, int format, int min_frames, double max_miss_ratio, int radius_leaves, int min_neighbors, int orient);
+int lsa_slam_get_dense_map_viewpoints(lsa_slam* s, float* xyz, int capacity, int* first_frame);
 
 /* ------------------------------------------------------------------------- */
 /* The keypoint log (Slam::LogKeypoints, slam_lib/src/Slam.cxx:1225-1255) in the memory of the device, and its replay under

@@ -307,6 +307,12 @@ SIGNATURES = {
     "lsa_slam_get_dense_map_misses": (i32, [vp, i32, f64, vp, i32]),
     "lsa_slam_save_dense_map_pcd_filtered": (i32, [vp, s, i32, i32, f64]),
     "lsa_slam_prune_dense_map": (i32, [vp, i32, f64, P(i64)]),
+    "lsa_dense_map_get_normals": (i32, [vp, i32, f64, i32, i32, vp, i32, i32, vp, i32]),
+    "lsa_dense_map_save_pcd_normals": (i32, [vp, s, i32, i32, f64, i32, i32, vp, i32, i32]),
+    "lsa_pcd_read_normals": (i32, [s, vp, i32]),
+    "lsa_slam_get_dense_map_normals": (i32, [vp, i32, f64, i32, i32, i32, vp, i32]),
+    "lsa_slam_save_dense_map_pcd_normals": (i32, [vp, s, i32, i32, f64, i32, i32, i32]),
+    "lsa_slam_get_dense_map_viewpoints": (i32, [vp, vp, i32, P(i32)]),
     "lsa_slam_get_registered_frame_origins": (i32, [vp, vp, i32]),
     # ---- the keypoint log and its descriptor store
     "lsa_kplog_describe": (i32, [vp, vp, i32, i32]),

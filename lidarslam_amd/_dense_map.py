@@ -1,7 +1,8 @@
 """The dense point-cloud map: registered frames voxel-hashed on the device (lsa_dense_map_*, lsa_slam_*dense_map*).
 
 DenseMapHost is the numpy statement of what the map computes; the device table (lidarslam_amd/csrc/lsa_dense_map.hip) is
-held to it byte for byte, on points, voxel records, sources and misses (free-space carving: DenseMapHost.carve).  DenseMap is
+held to it byte for byte, on points, voxel records, sources and misses (free-space carving: DenseMapHost.carve) and on the
+normals computed from the table (DenseMapHost.normals, dense_normals).  DenseMap is
 the table alone on a Context; dense_map(slam, ...) and its neighbours reach the pipeline's map (Slam.set_param("DenseMap", 1
 or 2)).
 """
@@ -10,14 +11,18 @@ import os
 
 import numpy as np
 
-from ._abi import _error, lib
+from ._abi import LsaError, _error, lib
 from ._native import POINT_DTYPE, pose16, ptr
 from ._pcd import PCD_BINARY
 
 # lsa_dense_voxel_t (include/lidarslam_amd.h)
 dense_voxel_dtype = np.dtype([("key", "<u8"), ("count", "<u4"), ("frames", "<u4"), ("first_frame", "<i4"), ("last_frame", "<i4")])
 
+# lsa_dense_normal_t (include/lidarslam_amd.h)
+dense_normal_dtype = np.dtype([("normal_x", "<f4"), ("normal_y", "<f4"), ("normal_z", "<f4"), ("curvature", "<f4"), ("neighbors", "<u4")])
+
 DENSE_INDEX_RANGE = 1 << 20  # voxel indices lie in [-2^20, 2^20)
+DENSE_NO_NORMAL = 0x7FC00000  # the four floats of a voxel without a normal: this quiet NaN
 
 
 def dense_intensity_code(intensity):
@@ -107,6 +112,108 @@ def dense_index_keys(index):
     return (i[:, 2].astype(np.uint64) << np.uint64(42)) | (i[:, 1].astype(np.uint64) << np.uint64(21)) | i[:, 0].astype(np.uint64)
 
 
+def eigh_eig(cov):
+    """The eigen step by numpy.linalg.eigh, in the layout of lsa_selftest_numerics fn 3: (m, 6) Sym3 doubles xx xy xz yy yz zz
+    -> (m, 12) l0 l1 l2 e0 e1 e2.  NOT the byte definition of dense_normals (that is eigen33<double> of lsa_device_math.h):
+    normals agree with it up to sign and the bound of tests/test_dense_normals_host.py."""
+    c = np.ascontiguousarray(cov, np.float64).reshape(-1, 6)
+    A = c[:, [0, 1, 2, 1, 3, 4, 2, 4, 5]].reshape(-1, 3, 3)
+    out = np.zeros((c.shape[0], 12))
+    if c.shape[0]:
+        w, v = np.linalg.eigh(A)
+        out[:, :3] = w
+        out[:, 3:] = np.transpose(v, (0, 2, 1)).reshape(-1, 9)
+    return out
+
+
+def dense_normal_sums(points, keys, radius_leaves=2):
+    """(k (n,) int64, s (n, 3), S (n, 6)) of dense_normals: per voxel the neighbour count and the sums of d and of its
+    products xx xy xz yy yz zz over the neighbours, in cell order"""
+    pts = np.ascontiguousarray(points, POINT_DTYPE)
+    K = np.ascontiguousarray(keys, np.uint64)
+    n = K.size
+    r = int(radius_leaves)
+    p = np.stack([pts["x"], pts["y"], pts["z"]], axis=1).astype(np.float64)
+    mask = np.uint64((1 << 21) - 1)
+    idx = np.stack([(K & mask), ((K >> np.uint64(21)) & mask), (K >> np.uint64(42)) & mask], axis=1).astype(np.int64) - DENSE_INDEX_RANGE
+    k = np.zeros(n, np.int64)
+    s, S = np.zeros((n, 3)), np.zeros((n, 6))
+    if n == 0:
+        return k, s, S
+    for dz in range(-r, r + 1):
+        for dy in range(-r, r + 1):
+            for dx in range(-r, r + 1):
+                cell = idx + np.array([dx, dy, dz], np.int64)
+                inside = ((cell >= -DENSE_INDEX_RANGE) & (cell < DENSE_INDEX_RANGE)).all(axis=1)
+                want = dense_index_keys(np.where(inside[:, None], cell, 0))
+                at = np.minimum(np.searchsorted(K, want), n - 1)
+                found = inside & (K[at] == want)
+                # (a sum that began at +0.0 is never -0.0, so the +0.0 a cell without a neighbour adds changes no bit)
+                d = np.where(found[:, None], p[at] - p, 0.0)
+                k += found
+                s += d
+                for c, (a, b) in enumerate(((0, 0), (0, 1), (0, 2), (1, 1), (1, 2), (2, 2))):
+                    S[:, c] += d[:, a] * d[:, b]
+    return k, s, S
+
+
+def dense_normal_covariances(k, s, S):
+    """(m, 6) Sym3 xx xy xz yy yz zz of dense_normals from the sums of dense_normal_sums (k > 0): C_ab = S_ab / k - (s_a / k) * (s_b / k)"""
+    kk = np.asarray(k).astype(np.float64)
+    m = np.asarray(s, np.float64) / kk[:, None]
+    cov = np.empty((kk.size, 6))
+    for c, (a, b) in enumerate(((0, 0), (0, 1), (0, 2), (1, 1), (1, 2), (2, 2))):
+        cov[:, c] = np.asarray(S, np.float64)[:, c] / kk - m[:, a] * m[:, b]
+    return cov
+
+
+def dense_normals(points, keys, sources, radius_leaves=2, min_neighbors=5, viewpoints=None, first_frame=0, eig=None):
+    """The definition of the dense map's normals over an export: points, keys (ascending) and sources of the voxels that count.
+    One dense_normal_dtype record per voxel, in their order; see DenseMapHost.normals."""
+    r = int(radius_leaves)
+    if r not in (1, 2):
+        raise ValueError("radius_leaves is 1 or 2")
+    min_neighbors = int(min_neighbors)
+    if min_neighbors < 3 or min_neighbors > (2 * r + 1) ** 3:
+        raise ValueError("min_neighbors between 3 and (2 * radius_leaves + 1)^3")
+    vp = None
+    if viewpoints is not None:
+        vp = np.asarray(viewpoints)
+        if vp.ndim != 2 or vp.shape[1] != 3:
+            raise ValueError("viewpoints of shape (n, 3)")
+        vp = np.ascontiguousarray(vp, np.float32)
+    pts = np.ascontiguousarray(points, POINT_DTYPE)
+    n = pts.size
+    out = np.zeros(n, dense_normal_dtype)
+    if n == 0:
+        return out
+    k, s, S = dense_normal_sums(pts, keys, r)
+    floats = np.full((n, 4), DENSE_NO_NORMAL, np.uint32)
+    out["neighbors"] = k
+    fit = np.flatnonzero(k >= min_neighbors)
+    if fit.size:
+        cov = dense_normal_covariances(k[fit], s[fit], S[fit])
+        E = np.asarray((eigh_eig if eig is None else eig)(cov), np.float64).reshape(-1, 12)
+        lam, e0 = E[:, :3], E[:, 3:6].copy()
+        ok = np.isfinite(E[:, :6]).all(axis=1)
+        if vp is not None and vp.shape[0] > 0:
+            c = np.clip(np.asarray(sources, np.int64)[fit] - int(first_frame), 0, vp.shape[0] - 1)
+            p = np.stack([pts["x"], pts["y"], pts["z"]], axis=1).astype(np.float64)[fit]
+            w = vp[c].astype(np.float64) - p
+            with np.errstate(invalid="ignore", over="ignore"):
+                dot = (e0[:, 0] * w[:, 0] + e0[:, 1] * w[:, 1]) + e0[:, 2] * w[:, 2]
+                e0 = np.where((dot < 0)[:, None], -e0, e0)
+        with np.errstate(invalid="ignore", over="ignore", divide="ignore"):
+            t = (lam[:, 0] + lam[:, 1]) + lam[:, 2]
+            curv = np.where(t > 0, np.abs(lam[:, 0] / np.where(t > 0, t, 1.0)).astype(np.float32), np.float32(0))
+            res = np.concatenate([e0.astype(np.float32), curv.astype(np.float32)[:, None]], axis=1)
+        good = fit[ok]
+        floats[good] = np.ascontiguousarray(res[ok]).view(np.uint32)
+    for c, name in enumerate(("normal_x", "normal_y", "normal_z", "curvature")):
+        out[name] = floats[:, c].view(np.float32)
+    return out
+
+
 class DenseMapHost:
     """The definition.  State: key -> (point, count, frames, first_frame, last_frame, intensity code, source).
 
@@ -136,7 +243,22 @@ class DenseMapHost:
     The ordinal must not be below the map's last one (nor be -2^31, which the device keeps for "none") and becomes the last.
 
     get / sources / misses (min_frames, max_miss_ratio): the voxels with frames >= min_frames and, for a ratio >= 0,
-    (double)misses <= max_miss_ratio * (double)frames.  prune removes the others for good."""
+    (double)misses <= max_miss_ratio * (double)frames.  prune removes the others for good.
+
+    normals(radius_leaves, min_neighbors, min_frames, max_miss_ratio, viewpoints, first_frame, eig): one record (normal,
+    curvature, neighbors) per voxel of get(min_frames, max_miss_ratio), in its order, from the voxels' kept points.  For a
+    voxel of index (ix, iy, iz) and point p the cells (ix+dx, iy+dy, iz+dz), dz, dy, dx in -r .. r with dx fastest (ascending
+    key order), are visited; a cell with an index outside [-2^20, 2^20) is skipped, and a cell is a neighbour when its voxel
+    exists and passes the same predicate -- the voxel itself is one.  With q the neighbour's point, all in double, from
+    +0.0, without contraction and in that order: d = (double)q - (double)p, s_a += d_a, S_ab += d_a * d_b (ab = xx xy xz yy
+    yz zz, the product rounded, then added), k the count = neighbors.  k < min_neighbors: the four floats are the quiet NaN
+    0x7fc00000.  Otherwise m = s / k, C_ab = S_ab / k - m_a * m_b, eigen33<double>(C) of lsa_device_math.h gives l0 <= l1 <=
+    l2 and e0; a non-finite eigenvalue or e0 gives that NaN too.  With viewpoints (n > 0, float32 (n, 3)): c = clamp(source
+    - first_frame, 0, n - 1), w = (double)viewpoints[c] - p, dot = (e0x*wx + e0y*wy) + e0z*wz, and dot < 0 negates every
+    component of e0 (anything else keeps eigen33's sign).  normal = (float)e0, t = (l0 + l1) + l2, curvature = t > 0 ?
+    (float)|l0 / t| : 0 (PCL's surface variation).  Nothing depends on the order of the voxels; no state changes.
+    `eig` is the eigen step, (m, 6) -> (m, 12) in the layout of lsa_selftest_numerics fn 3; None is numpy.linalg.eigh
+    (eigh_eig), which is NOT the byte definition."""
 
     def __init__(self, leaf):
         if not (leaf > 0 and np.isfinite(leaf)):
@@ -237,6 +359,13 @@ class DenseMapHost:
     def misses(self, min_frames=1, max_miss_ratio=-1.0):
         """the misses of every voxel of get(min_frames, max_miss_ratio), in its order"""
         return np.array([self.voxels[k][7] for k in self._kept(min_frames, max_miss_ratio)], np.uint32)
+
+    def normals(self, radius_leaves=2, min_neighbors=5, min_frames=1, max_miss_ratio=-1.0, viewpoints=None, first_frame=0, eig=None):
+        """dense_normal_dtype records of the voxels of get(min_frames, max_miss_ratio), in its order; see the class"""
+        if int(min_frames) < 1:
+            raise ValueError("min_frames >= 1")
+        pts, vox = self.get(min_frames, max_miss_ratio)
+        return dense_normals(pts, vox["key"], self.sources(min_frames, max_miss_ratio), radius_leaves, min_neighbors, viewpoints, first_frame, eig)
 
     def prune(self, min_frames=1, max_miss_ratio=-1.0):
         """removes every voxel get(min_frames, max_miss_ratio) leaves out; returns their number (also added to self.pruned)"""
@@ -411,11 +540,60 @@ class DenseMap:
     def clear(self):
         self._check(self.L.lsa_dense_map_clear(self.h), "lsa_dense_map_clear")
 
+    def normals(self, radius_leaves=2, min_neighbors=5, min_frames=1, max_miss_ratio=-1.0, viewpoints=None, first_frame=0):
+        """dense_normal_dtype records of the voxels of get(min_frames, max_miss_ratio), in its order, as DenseMapHost.normals states
+        them (with eigen33<double> as the eigen step); viewpoints: (n, 3) float32, entry j for ordinal first_frame + j.  LsaError
+        with .code E_ARG, the map untouched, for what the statement refuses"""
+        vp, n = _viewpoints(viewpoints)
+        cap = max(self.size(), 1)
+        out = np.zeros(cap, dense_normal_dtype)
+        got = self._check(
+            self.L.lsa_dense_map_get_normals(self.h, int(min_frames), float(max_miss_ratio), int(radius_leaves), int(min_neighbors), ptr(vp) if n else None, n, int(first_frame), ptr(out), cap),
+            "lsa_dense_map_get_normals",
+        )
+        return out[:got].copy()
+
+    def save_pcd_normals(self, path, fmt=PCD_BINARY, radius_leaves=2, min_neighbors=5, min_frames=1, max_miss_ratio=-1.0, viewpoints=None, first_frame=0):
+        """the points of get(min_frames, max_miss_ratio) with the fields normal_x normal_y normal_z curvature of normals(...) behind
+        them into a PCD file; returns their number (0 and no file for none)"""
+        vp, n = _viewpoints(viewpoints)
+        return self._check(
+            self.L.lsa_dense_map_save_pcd_normals(
+                self.h, os.fsencode(path), int(fmt), int(min_frames), float(max_miss_ratio), int(radius_leaves), int(min_neighbors), ptr(vp) if n else None, n, int(first_frame)
+            ),
+            "lsa_dense_map_save_pcd_normals",
+        )
+
     def save_pcd(self, path, fmt=PCD_BINARY, min_frames=1, max_miss_ratio=-1.0):
         """the points of get(min_frames, max_miss_ratio) into a PCD file; returns their number (0 and no file for none)"""
         return self._check(
             self.L.lsa_dense_map_save_pcd_filtered(self.h, os.fsencode(path), int(fmt), int(min_frames), float(max_miss_ratio)), "lsa_dense_map_save_pcd_filtered"
         )
+
+
+def _viewpoints(viewpoints):
+    """(float32 (n, 3) array or None, n); ValueError for another shape"""
+    if viewpoints is None:
+        return None, 0
+    vp = np.asarray(viewpoints)
+    if vp.ndim != 2 or vp.shape[1] != 3:
+        raise ValueError("viewpoints of shape (n, 3)")
+    vp = np.ascontiguousarray(vp, np.float32)
+    return vp, vp.shape[0]
+
+
+def read_pcd_normals(path):
+    """(n, 4) float32 normal_x normal_y normal_z curvature of a PCD file that has those fields, the bytes as the file holds them;
+    LsaError naming the file when one is missing or is not a 4-byte F; host only"""
+    L = lib()
+    out = np.zeros((1, 4), np.float32)
+    got = L.lsa_pcd_read_normals(os.fsencode(path), ptr(out), 0)
+    if got > 0:
+        out = np.zeros((got, 4), np.float32)
+        got = L.lsa_pcd_read_normals(os.fsencode(path), ptr(out), got)
+    if got < 0:
+        raise LsaError(L.lsa_pcd_last_error().decode())
+    return out[:got].copy()
 
 
 def frame_origins_at(ctx, H0, H1=None, t0=0.0, t1=0.0, time_offset=0.0):
@@ -513,3 +691,36 @@ def registered_frame_origins(slam):
 
 def clear_dense_map(slam):
     slam._check(slam.L.lsa_slam_clear_dense_map(slam.h), "lsa_slam_clear_dense_map")
+
+
+def dense_map_viewpoints(slam):
+    """(viewpoints (n, 3) float32, first_frame): per inserted ordinal since the last clear where the sensor of the call's first
+    frame stood -- the translation of its pose, narrowed to float, moved with the map by an applied trajectory under
+    "DenseMapOnTrajectory" 1; first_frame is the ordinal of entry 0"""
+    first = C.c_int(0)
+    n = slam._check(slam.L.lsa_slam_get_dense_map_viewpoints(slam.h, None, 0, C.byref(first)), "lsa_slam_get_dense_map_viewpoints")
+    out = np.zeros((max(n, 1), 3), np.float32)
+    n = slam._check(slam.L.lsa_slam_get_dense_map_viewpoints(slam.h, ptr(out), out.shape[0], C.byref(first)), "lsa_slam_get_dense_map_viewpoints")
+    return out[:n].copy(), int(first.value)
+
+
+def dense_map_normals(slam, min_frames=1, max_miss_ratio=-1.0, radius_leaves=2, min_neighbors=5, orient=True):
+    """dense_normal_dtype records of the voxels of dense_map_filtered(slam, min_frames, max_miss_ratio), in its order: DenseMap.normals
+    of the pipeline's map, turned towards dense_map_viewpoints(slam) when `orient`"""
+    cap = max(dense_map_size(slam), 1)
+    out = np.zeros(cap, dense_normal_dtype)
+    n = slam._check(
+        slam.L.lsa_slam_get_dense_map_normals(slam.h, int(min_frames), float(max_miss_ratio), int(radius_leaves), int(min_neighbors), int(bool(orient)), ptr(out), cap),
+        "lsa_slam_get_dense_map_normals",
+    )
+    return out[:n].copy()
+
+
+def save_dense_map_pcd_normals(slam, path, format=PCD_BINARY, min_frames=1, max_miss_ratio=-1.0, radius_leaves=2, min_neighbors=5, orient=True):  # noqa: A002
+    """dense_map_filtered with the normals of dense_map_normals behind every point into a PCD file; returns the number of points"""
+    return slam._check(
+        slam.L.lsa_slam_save_dense_map_pcd_normals(
+            slam.h, os.fsencode(path), int(format), int(min_frames), float(max_miss_ratio), int(radius_leaves), int(min_neighbors), int(bool(orient))
+        ),
+        "lsa_slam_save_dense_map_pcd_normals",
+    )

@@ -15,9 +15,9 @@ namespace
 {
 double now_s() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
-const char* const kFieldNames[kNbFields] = {"x", "y", "z", "time", "intensity", "laser_id", "device_id", "label"};
-const int kFieldSizes[kNbFields] = {4, 4, 4, 8, 4, 2, 1, 1};
-const char kFieldTypes[kNbFields] = {'F', 'F', 'F', 'F', 'F', 'U', 'U', 'U'};
+const char* const kFieldNames[kNbColumns] = {"x", "y", "z", "time", "intensity", "laser_id", "device_id", "label", "normal_x", "normal_y", "normal_z", "curvature"};
+const int kFieldSizes[kNbColumns] = {4, 4, 4, 8, 4, 2, 1, 1, 4, 4, 4, 4};
+const char kFieldTypes[kNbColumns] = {'F', 'F', 'F', 'F', 'F', 'U', 'U', 'U', 'F', 'F', 'F', 'F'};
 
 struct File
 {
@@ -149,7 +149,7 @@ ColumnTable table_of(const Header& h, bool columns, long long n)
   for (const Field& f : h.fields)
   {
     // the first field of a name counts, with COUNT 1 only: every other one is skipped by its width
-    for (int k = 0; k < kNbFields && f.count == 1; ++k)
+    for (int k = 0; k < kNbColumns && f.count == 1; ++k)
       if (f.name == kFieldNames[k] && t.c[k].type == kAbsent)
       {
         Column& c = t.c[k];
@@ -280,6 +280,29 @@ int read_points(const std::string& path, std::vector<lsa_point_t>& out, std::str
   return LSA_OK;
 }
 
+int read_normals(const std::string& path, std::vector<float>& out4, std::string& err)
+{
+  Cloud c;
+  const int rc = read_cloud(path, c, err);
+  if (rc) return rc;
+  for (int k = kNormalX; k < kNbColumns; ++k)
+  {
+    const Column& col = c.table.c[k];
+    if (col.type == kAbsent) return bad(err, path, 0, std::string("no field ") + kFieldNames[k] + " (of COUNT 1)");
+    if (col.type != kFloat || col.size != 4) return bad(err, path, 0, std::string("the field ") + kFieldNames[k] + " is not a 4-byte F");
+  }
+  try { out4.resize((size_t)c.header.points * 4); }
+  catch (const std::bad_alloc&) { return bad(err, path, 0, "not enough memory for the normals"); }
+  for (long long i = 0; i < c.header.points; ++i)
+    for (int k = 0; k < 4; ++k)
+    {
+      // (the bytes as they are: a NaN keeps its bits)
+      const Column& col = c.table.c[kNormalX + k];
+      std::memcpy(&out4[(size_t)i * 4 + k], c.data.data() + col.base + i * col.step, 4);
+    }
+  return LSA_OK;
+}
+
 namespace
 {
 void records_to_columns(const unsigned char* rec, long long n, unsigned char* col)
@@ -295,7 +318,8 @@ void records_to_columns(const unsigned char* rec, long long n, unsigned char* co
 }
 }  // namespace
 
-int write_records(const std::string& path, const unsigned char* records, const unsigned char* columns, long long n, int format, std::string& err)
+int write_records(const std::string& path, const unsigned char* records, const unsigned char* columns, long long n, int format, std::string& err,
+                  const float* normals4)
 {
   timing() = Timing{};
   if (n <= 0) return -3;
@@ -305,18 +329,33 @@ int write_records(const std::string& path, const unsigned char* records, const u
     return -4;
   }
   if (!records && !(columns && format == kBinaryCompressed)) return bad(err, path, 0, "no points given");
+  const int nfields = normals4 ? (int)kNbColumns : (int)kNbFields;
+  const int record_bytes = normals4 ? kRecordBytes + kNormalBytes : kRecordBytes;
   std::string head = "# .PCD v0.7 - Point Cloud Data file format\nVERSION 0.7\nFIELDS";
-  for (int k = 0; k < kNbFields; ++k) head += std::string(" ") + kFieldNames[k];
+  for (int k = 0; k < nfields; ++k) head += std::string(" ") + kFieldNames[k];
   head += "\nSIZE";
-  for (int k = 0; k < kNbFields; ++k) head += " " + std::to_string(kFieldSizes[k]);
+  for (int k = 0; k < nfields; ++k) head += " " + std::to_string(kFieldSizes[k]);
   head += "\nTYPE";
-  for (int k = 0; k < kNbFields; ++k) head += std::string(" ") + kFieldTypes[k];
-  head += "\nCOUNT 1 1 1 1 1 1 1 1\nWIDTH " + std::to_string(n) + "\nHEIGHT 1\nVIEWPOINT 0 0 0 1 0 0 0\nPOINTS " + std::to_string(n) + "\nDATA ";
+  for (int k = 0; k < nfields; ++k) head += std::string(" ") + kFieldTypes[k];
+  head += "\nCOUNT";
+  for (int k = 0; k < nfields; ++k) head += " 1";
+  head += "\nWIDTH " + std::to_string(n) + "\nHEIGHT 1\nVIEWPOINT 0 0 0 1 0 0 0\nPOINTS " + std::to_string(n) + "\nDATA ";
   head += format == kAscii ? "ascii\n" : format == kBinary ? "binary\n" : "binary_compressed\n";
   std::vector<unsigned char> body;
   const unsigned char* out = records;
-  size_t out_bytes = (size_t)n * kRecordBytes;
+  size_t out_bytes = (size_t)n * record_bytes;
   double t0 = now_s();
+  if (format == kBinary && normals4)
+  {
+    // the 16 bytes of every normal behind the 28 of its point
+    body.resize(out_bytes);
+    for (long long i = 0; i < n; ++i)
+    {
+      std::memcpy(body.data() + (size_t)i * record_bytes, records + (size_t)i * kRecordBytes, kRecordBytes);
+      std::memcpy(body.data() + (size_t)i * record_bytes + kRecordBytes, normals4 + (size_t)i * 4, kNormalBytes);
+    }
+    out = body.data();
+  }
   if (format == kAscii)
   {
     // nine and seventeen significant digits: a float and a double read back to the same bits
@@ -330,7 +369,14 @@ int write_records(const std::string& path, const unsigned char* records, const u
       double t;
       uint16_t laser;
       std::memcpy(&x, r, 4); std::memcpy(&y, r + 4, 4); std::memcpy(&z, r + 8, 4); std::memcpy(&t, r + 12, 8); std::memcpy(&in, r + 20, 4); std::memcpy(&laser, r + 24, 2);
-      const int len = std::snprintf(row, sizeof(row), "%.9g %.9g %.9g %.17g %.9g %u %u %u\n", x, y, z, t, in, (unsigned)laser, (unsigned)r[26], (unsigned)r[27]);
+      int len = std::snprintf(row, sizeof(row), "%.9g %.9g %.9g %.17g %.9g %u %u %u", x, y, z, t, in, (unsigned)laser, (unsigned)r[26], (unsigned)r[27]);
+      for (int k = 0; normals4 && k < 4; ++k)
+      {
+        // a voxel without a normal is spelled nan, whatever the C library makes of the sign
+        const float v = normals4[(size_t)i * 4 + k];
+        len += v != v ? std::snprintf(row + len, sizeof(row) - (size_t)len, " nan") : std::snprintf(row + len, sizeof(row) - (size_t)len, " %.9g", v);
+      }
+      row[len++] = '\n';
       text.append(row, (size_t)len);
     }
     body.assign(text.begin(), text.end());
@@ -342,10 +388,14 @@ int write_records(const std::string& path, const unsigned char* records, const u
   {
     if ((unsigned long long)out_bytes > 0xffffffffull) return bad(err, path, 0, "more than 4 GiB do not fit the compressed format's sizes");
     std::vector<unsigned char> made;
-    if (!columns)
+    if (!columns || normals4)
     {
       made.resize(out_bytes);
-      records_to_columns(records, n, made.data());
+      if (columns) std::memcpy(made.data(), columns, (size_t)n * kRecordBytes);
+      else records_to_columns(records, n, made.data());
+      // the four columns of the normals behind the eight
+      for (int k = 0; normals4 && k < 4; ++k)
+        for (long long i = 0; i < n; ++i) std::memcpy(made.data() + (size_t)n * kRecordBytes + ((size_t)k * n + (size_t)i) * 4, normals4 + (size_t)i * 4 + k, 4);
       columns = made.data();
     }
     const std::vector<unsigned char> z = lzf_compress(columns, out_bytes);
@@ -501,6 +551,17 @@ int lsa_pcd_read(const char* path, lsa_point_t* out, int capacity)
   const size_t n = std::min(pts.size(), (size_t)capacity);
   if (n > 0) std::memcpy(out, pts.data(), n * sizeof(lsa_point_t));
   return (int)pts.size();
+}
+
+int lsa_pcd_read_normals(const char* path, float* out4, int capacity)
+{
+  if (!path || capacity < 0 || (capacity > 0 && !out4)) return LSA_E_ARG;
+  std::vector<float> normals;
+  const int rc = lsa::pcd::read_normals(path, normals, pcd_error());
+  if (rc) return rc;
+  const size_t n = std::min(normals.size() / 4, (size_t)capacity);
+  if (n > 0) std::memcpy(out4, normals.data(), n * 4 * sizeof(float));
+  return (int)(normals.size() / 4);
 }
 
 int lsa_pcd_write(const char* path, const lsa_point_t* pts, int n, int format)

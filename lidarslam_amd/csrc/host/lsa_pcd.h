@@ -27,7 +27,10 @@ namespace pcd
 // the registered fields of LidarPoint in order (slam_lib/include/LidarSlam/LidarPoint.h:68-77): what a written file holds
 enum { kX = 0, kY, kZ, kTime, kIntensity, kLaserId, kDeviceId, kLabel, kNbFields };
 constexpr int kRecordBytes = 28;  // 4 4 4 8 4 2 1 1, packed
-constexpr int kMaxFields = 16;    // columns a table can name (the eight of a LidarPoint are used)
+constexpr int kMaxFields = 16;    // columns a table can name (the eight of a LidarPoint, the four of a normal)
+// the fields a dense map's normals add behind a LidarPoint's (pcl::Normal's names): four floats, 16 bytes
+enum { kNormalX = kNbFields, kNormalY, kNormalZ, kCurvature, kNbColumns };
+constexpr int kNormalBytes = 16;
 enum { kAbsent = 0, kFloat = 1, kSigned = 2, kUnsigned = 3 };
 
 struct Column
@@ -163,7 +166,12 @@ int read_points(const std::string& path, std::vector<lsa_point_t>& out, std::str
 // Writes the LidarPoint field list.  `records`: n packed 28-byte records; `columns` (binary_compressed only, may be
 // null: made from the records): the eight columns of n points, field after field.  n == 0 writes nothing and returns -3,
 // savePointCloudToPCD's result for an empty cloud (PointCloudStorage.h:91-92); an unknown format returns -4 (:111-113).
-int write_records(const std::string& path, const unsigned char* records, const unsigned char* columns, long long n, int format, std::string& err);
+// `normals4` (may be null: the file is the LidarPoint's alone, as ever): n x 4 floats normal_x normal_y normal_z curvature,
+// written as four more fields behind the eight, 44 bytes a record.
+int write_records(const std::string& path, const unsigned char* records, const unsigned char* columns, long long n, int format, std::string& err,
+                  const float* normals4 = nullptr);
+// the four floats per point of a file that has the fields normal_x normal_y normal_z curvature, each a 4-byte F of COUNT 1
+int read_normals(const std::string& path, std::vector<float>& out4, std::string& err);
 int write_points(const std::string& path, const lsa_point_t* pts, long long n, int format, std::string& err);
 
 // LZF: a stream of literal runs (control byte c < 32: c + 1 bytes follow) and back references (c >> 5 = length - 2, 7

@@ -352,6 +352,24 @@ int lsa_slam_prune_dense_map(lsa_slam* s, int min_frames, double max_miss_ratio,
   return s->core.PruneDenseMap(min_frames, max_miss_ratio, removed);
 }
 
+int lsa_slam_get_dense_map_normals(lsa_slam* s, int min_frames, double max_miss_ratio, int radius_leaves, int min_neighbors, int orient, lsa_dense_normal_t* out, int capacity)
+{
+  if (!s) return LSA_E_ARG;
+  return s->core.GetDenseMapNormals(min_frames, max_miss_ratio, radius_leaves, min_neighbors, orient, out, capacity);
+}
+
+int lsa_slam_save_dense_map_pcd_normals(lsa_slam* s, const char* path, int format, int min_frames, double max_miss_ratio, int radius_leaves, int min_neighbors, int orient)
+{
+  if (!s || !path) return LSA_E_ARG;
+  return s->core.SaveDenseMapToPCDNormals(path, format, min_frames, max_miss_ratio, radius_leaves, min_neighbors, orient);
+}
+
+int lsa_slam_get_dense_map_viewpoints(lsa_slam* s, float* xyz, int capacity, int* first_frame)
+{
+  if (!s) return LSA_E_ARG;
+  return s->core.GetDenseMapViewpoints(xyz, capacity, first_frame);
+}
+
 int lsa_slam_get_registered_frame_origins(lsa_slam* s, float* xyz, int capacity)
 {
   if (!s || (!xyz && capacity > 0)) return LSA_E_ARG;

@@ -295,6 +295,10 @@ public:
   int SaveDenseMapToPCDFiltered(const std::string& path, int format, int minFrames, double maxMissRatio);
   int PruneDenseMap(int minFrames, double maxMissRatio, long long* removed);
   int GetRegisteredFrameOrigins(std::vector<float>& out);
+  // normals: computed from the table as it stands, towards the viewpoints below when `orient`
+  int GetDenseMapNormals(int minFrames, double maxMissRatio, int radiusLeaves, int minNeighbors, int orient, lsa_dense_normal_t* out, int capacity);
+  int SaveDenseMapToPCDNormals(const std::string& path, int format, int minFrames, double maxMissRatio, int radiusLeaves, int minNeighbors, int orient);
+  int GetDenseMapViewpoints(float* xyz, int capacity, int* firstFrame);
 
   // ---- state ----
   Pose Tworld, PreviousTworld, Trelative;
@@ -439,6 +443,7 @@ private:
   lsa_dense_map* Dense = nullptr;  // made by the first insertion
   bool DenseWarned = false;
   std::vector<double> DenseTimes;  // per ordinal, the time under which LogCurrentFrameState logged the frame
+  std::vector<float> DenseViewpoints;  // per ordinal, xyz: where the call's first sensor stood (12 B a frame); entry 0 is ordinal 0
   int InsertDenseFrame(bool keyframe, double time);
   // the corrections of the dense ordinals still logged (from *firstOrdinal on) for the trajectory poses16 about to replace
   // the logged one; false when the map is to be cleared instead

@@ -26,6 +26,8 @@ int SlamCore::InsertDenseFrame(bool keyframe, double time)
   }
   const int ordinal = static_cast<int>(DenseFrames);
   bool inserted = false, refused = false;
+  // the ordinal's viewpoint: where the sensor of the call's first frame stands under the pose of the insertion
+  const Pose view = Tworld * (CurrentFrames.empty() ? BaseToLidarOffset : GetBaseToLidarOffset(CurrentFrames.front().device));
   // the frame in use under the poses GetRegisteredFrame uses: inserted, or (carve) its rays walked
   auto insert = [&](const Pose& offset, double timeOffset, bool carve = false) -> int {
     int rc;
@@ -93,6 +95,7 @@ int SlamCore::InsertDenseFrame(bool keyframe, double time)
   {
     DenseFrames++;
     DenseTimes.push_back(time);  // 8 B a frame: which logged pose an applied trajectory corrects this ordinal by
+    for (int a = 0; a < 3; ++a) DenseViewpoints.push_back(static_cast<float>(view.m[4 * a + 3]));  // 12 B a frame: what the normals are turned towards
   }
   return LSA_OK;
 }
@@ -105,6 +108,7 @@ void SlamCore::DropDenseMap(const char* why)
   (void)lsa_dense_map_clear(Dense);
   DenseFrames = 0;
   DenseTimes.clear();
+  DenseViewpoints.clear();
   DenseClears++;
   if (why && !DenseWarned)
   {
@@ -145,6 +149,17 @@ int SlamCore::ReprojectDenseMap(const std::vector<double>& corrections, int firs
   if (rc == LSA_OK)
   {
     DenseReprojections++;
+    // every viewpoint moves as the voxels of its ordinal moved: the clamp and the arithmetic of the re-projection (rigid_apply
+    // in double, without contraction, narrowed to float)
+    const long long n = static_cast<long long>(corrections.size() / 16);
+    for (size_t j = 0; 3 * j + 2 < DenseViewpoints.size(); ++j)
+    {
+      const long long c = std::min(std::max(static_cast<long long>(j) - firstOrdinal, 0ll), n - 1);
+      const double* T = corrections.data() + 16 * c;
+      float* v = DenseViewpoints.data() + 3 * j;
+      const double x = v[0], y = v[1], z = v[2];
+      for (int a = 0; a < 3; ++a) v[a] = static_cast<float>(((T[4 * a] * x + T[4 * a + 1] * y) + T[4 * a + 2] * z) + T[4 * a + 3]);
+    }
     return LSA_OK;
   }
   const std::string why = std::string("dense map: not re-projected, cleared: ") + lsa_last_error(Ctx);
@@ -278,6 +293,37 @@ int SlamCore::GetRegisteredFrameOrigins(std::vector<float>& out)
   if (n <= 0) return 0;
   out.resize(3 * static_cast<size_t>(n));
   LSA_TRY(origins(BaseToLidarOffset, 0., out.data(), n));
+  return n;
+}
+
+int SlamCore::GetDenseMapNormals(int minFrames, double maxMissRatio, int radiusLeaves, int minNeighbors, int orient, lsa_dense_normal_t* out, int capacity)
+{
+  if (const int rc = DenseReady("GetDenseMapNormals"); rc < 0) return rc;
+  if (capacity < 0) { LastError = "GetDenseMapNormals: bad argument"; return LSA_E_ARG; }
+  if (!Dense) return 0;
+  const int nv = orient ? static_cast<int>(DenseViewpoints.size() / 3) : 0;
+  const int n = lsa_dense_map_get_normals(Dense, minFrames, maxMissRatio, radiusLeaves, minNeighbors, nv ? DenseViewpoints.data() : nullptr, nv, 0, out, capacity);
+  return n < 0 ? Fail(n, "lsa_dense_map_get_normals") : n;
+}
+
+int SlamCore::SaveDenseMapToPCDNormals(const std::string& path, int format, int minFrames, double maxMissRatio, int radiusLeaves, int minNeighbors, int orient)
+{
+  if (const int rc = DenseReady("SaveDenseMapWithNormalsToPCD"); rc < 0) return rc;
+  if (!Dense) return 0;  // an empty cloud is not saved
+  const int nv = orient ? static_cast<int>(DenseViewpoints.size() / 3) : 0;
+  const int n = lsa_dense_map_save_pcd_normals(Dense, path.c_str(), format, minFrames, maxMissRatio, radiusLeaves, minNeighbors, nv ? DenseViewpoints.data() : nullptr, nv, 0);
+  return n < 0 ? Fail(n, "lsa_dense_map_save_pcd_normals") : n;
+}
+
+// per inserted ordinal since the last clear, float xyz; *firstFrame: the ordinal of entry 0
+int SlamCore::GetDenseMapViewpoints(float* xyz, int capacity, int* firstFrame)
+{
+  if (const int rc = DenseReady("GetDenseMapViewpoints"); rc < 0) return rc;
+  if (capacity < 0 || (capacity > 0 && !xyz)) { LastError = "GetDenseMapViewpoints: bad argument"; return LSA_E_ARG; }
+  const int n = static_cast<int>(DenseViewpoints.size() / 3);
+  if (firstFrame) *firstFrame = static_cast<int>(DenseFrames) - n;  // (0: what clears the map starts the ordinals again)
+  const int take = std::min(n, capacity);
+  if (take > 0) std::memcpy(xyz, DenseViewpoints.data(), static_cast<size_t>(take) * 3 * sizeof(float));
   return n;
 }
 

@@ -143,7 +143,7 @@ int SlamCore::SetParamValue(const std::string& name, double v)
   {
     if (!(v > 0.) || !(v < 1e9)) { LastError = "DenseMapLeafSize: a positive length"; return LSA_E_ARG; }
     // the voxels of a map made under another leaf size mean nothing under this one: the next insertion makes a new map
-    if (Dense && v != DenseMapLeafSize) { lsa_dense_map_destroy(Dense); Dense = nullptr; DenseFrames = 0; DenseTimes.clear(); }
+    if (Dense && v != DenseMapLeafSize) { lsa_dense_map_destroy(Dense); Dense = nullptr; DenseFrames = 0; DenseTimes.clear(); DenseViewpoints.clear(); }
     DenseMapLeafSize = v;
     return LSA_OK;
   }

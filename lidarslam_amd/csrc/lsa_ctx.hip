@@ -26,7 +26,11 @@ int ensure_capacity(lsa_ctx* ctx, int n)
   if (ctx->prefetch_stream) LSA_HIP(ctx, hipStreamSynchronize(ctx->prefetch_stream));
   ctx->prefetch_pending = false;
   for (int k = 0; k < 3; ++k) LSA_HIP(ctx, dev_alloc(ctx, &ctx->kp_next[k], (size_t)cap));
-  // keypoint sets must survive a growth (raw previous is still needed): copy them over
+  // keypoint sets must survive a growth (raw previous is still needed): copy them over -- on the context's stream and waited
+  // for below.  (A device-to-device hipMemcpy goes to the null stream, which the context's non-blocking streams are not ordered
+  // with, and need not block the host: the old frame could land in the new buffer AFTER the upload that follows the growth
+  // and overwrite its head -- the first frame of a larger scan then came out with the points of the frame before in front.)
+  bool carried = false;
   lsa_point_t* old_kp[3][3];
   for (int s = 0; s < 3; ++s)
     for (int k = 0; k < 3; ++k) { old_kp[s][k] = ctx->kp[s][k]; ctx->kp[s][k] = nullptr; }
@@ -35,7 +39,10 @@ int ensure_capacity(lsa_ctx* ctx, int n)
     {
       LSA_HIP(ctx, dev_alloc(ctx, &ctx->kp[s][k], (size_t)cap));
       if (old_kp[s][k] && ctx->kp_n[s][k] > 0)
-        LSA_HIP(ctx, hipMemcpy(ctx->kp[s][k], old_kp[s][k], (size_t)ctx->kp_n[s][k] * sizeof(lsa_point_t), hipMemcpyDeviceToDevice));
+      {
+        LSA_HIP(ctx, hipMemcpyAsync(ctx->kp[s][k], old_kp[s][k], (size_t)ctx->kp_n[s][k] * sizeof(lsa_point_t), hipMemcpyDeviceToDevice, ctx->stream));
+        carried = true;
+      }
       retire_dev(ctx, old_kp[s][k]);
     }
   {
@@ -46,7 +53,8 @@ int ensure_capacity(lsa_ctx* ctx, int n)
     LSA_HIP(ctx, dev_alloc(ctx, &ctx->frame_own, (size_t)cap));
     if (current)
     {
-      LSA_HIP(ctx, hipMemcpy(ctx->frame_own, old_frame, (size_t)ctx->frame_n * sizeof(lsa_point_t), hipMemcpyDeviceToDevice));
+      LSA_HIP(ctx, hipMemcpyAsync(ctx->frame_own, old_frame, (size_t)ctx->frame_n * sizeof(lsa_point_t), hipMemcpyDeviceToDevice, ctx->stream));
+      carried = true;
       ctx->frame = ctx->frame_own;
     }
     retire_dev(ctx, old_frame);
@@ -60,6 +68,7 @@ int ensure_capacity(lsa_ctx* ctx, int n)
   LSA_HIP(ctx, dev_alloc(ctx, &ctx->valid, (size_t)cap));
   LSA_HIP(ctx, dev_alloc(ctx, &ctx->label, (size_t)cap));
   ctx->cap_n = cap;
+  if (carried) LSA_HIP(ctx, hipStreamSynchronize(ctx->stream));  // every stream of the context may use the new buffers from here on
   return LSA_OK;
 }
 

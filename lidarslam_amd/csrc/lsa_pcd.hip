@@ -291,7 +291,8 @@ static int save_pcd(lsa_device_grid* g, const char* path, int format, int clean)
 
 // n LidarPoints on the device (what kernels on `gs` left) into a PCD file: the part of a save that comes behind the collection,
 // for the keypoint maps above and the dense map (lsa_dense_map.hip).  The caller has checked path and format and set T[4].
-int lsa::pcd_save_device_points(lsa_ctx* ctx, hipStream_t gs, const lsa_point_t* pts, int n, const char* path, int format)
+// normals4 (host, may be null): n x 4 floats the writer puts behind every point -- interleaved on the host, the path is not hot.
+int lsa::pcd_save_device_points(lsa_ctx* ctx, hipStream_t gs, const lsa_point_t* pts, int n, const char* path, int format, const float* normals4)
 {
   double* T = ctx->pcd_times;
   T[6] = n;
@@ -339,9 +340,9 @@ int lsa::pcd_save_device_points(lsa_ctx* ctx, hipStream_t gs, const lsa_point_t*
   }
   if ((rc = take(pieces - 1)) != LSA_OK) return rc;
   T[3] = now_s() - t_begin;
-  T[5] = (double)n * pcd::kRecordBytes;
+  T[5] = (double)n * (pcd::kRecordBytes + (normals4 ? pcd::kNormalBytes : 0));
   std::string err;
-  rc = pcd::write_records(path, columns ? nullptr : raw.data(), columns ? raw.data() : nullptr, n, format, err);
+  rc = pcd::write_records(path, columns ? nullptr : raw.data(), columns ? raw.data() : nullptr, n, format, err, normals4);
   T[0] = pcd::timing().file; T[1] = pcd::timing().lzf; T[2] = pcd::timing().text;
   if (rc) return ctx->fail(rc, err);
   return n;

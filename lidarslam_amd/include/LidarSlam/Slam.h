@@ -858,6 +858,49 @@ public:
     this->LastError = rc < 0 ? std::string("PruneDenseMap: ") + lsa_slam_last_error(this->Handle) : std::string();
     return rc < 0 ? rc : removed;
   }
+  // Normals: per point of GetDenseMap(minFrames, maxMissRatio), in its order, the eigenvector of the smallest eigenvalue of the
+  // covariance of the kept points of the voxels within radiusLeaves (1 or 2) that pass the same filter, PCL's surface variation
+  // as curvature and the number of those voxels; NaN (PCL's "no normal") below minNeighbors.  With orient the normal is turned
+  // towards where the sensor stood when it measured the point (GetDenseMapViewpoints).  Computed on the device from the table
+  // as it stands; nothing is stored.
+  struct DenseNormal
+  {
+    float normal_x, normal_y, normal_z, curvature;
+    std::uint32_t neighbors;
+  };
+  std::vector<DenseNormal> GetDenseMapNormals(int minFrames = 1, double maxMissRatio = -1., int radiusLeaves = 2, int minNeighbors = 5, bool orient = true)
+  {
+    static_assert(sizeof(DenseNormal) == sizeof(lsa_dense_normal_t), "DenseNormal is lsa_dense_normal_t");
+    std::vector<DenseNormal> out;
+    int n = lsa_slam_dense_map_size(this->Handle);
+    if (n > 0)
+    {
+      out.resize(static_cast<std::size_t>(n));
+      n = lsa_slam_get_dense_map_normals(this->Handle, minFrames, maxMissRatio, radiusLeaves, minNeighbors, orient ? 1 : 0, reinterpret_cast<lsa_dense_normal_t*>(out.data()), n);
+      out.resize(static_cast<std::size_t>(std::max(n, 0)));
+    }
+    this->LastError = n < 0 ? std::string("GetDenseMapNormals: ") + lsa_slam_last_error(this->Handle) : std::string();
+    return out;
+  }
+  // GetDenseMap(minFrames, maxMissRatio) with the fields normal_x normal_y normal_z curvature behind every point
+  int SaveDenseMapWithNormalsToPCD(const std::string& path, PCDFormat pcdFormat = PCDFormat::BINARY, int minFrames = 1, double maxMissRatio = -1., int radiusLeaves = 2,
+                                   int minNeighbors = 5, bool orient = true) const
+  {
+    const int rc = lsa_slam_save_dense_map_pcd_normals(this->Handle, path.c_str(), static_cast<int>(pcdFormat), minFrames, maxMissRatio, radiusLeaves, minNeighbors, orient ? 1 : 0);
+    this->LastError = rc < 0 ? std::string("SaveDenseMapWithNormalsToPCD: ") + lsa_slam_last_error(this->Handle) : std::string();
+    return rc;
+  }
+  // float xyz per inserted frame since the map was last cleared: where the (first) sensor stood
+  std::vector<float> GetDenseMapViewpoints()
+  {
+    int first = 0;
+    int n = lsa_slam_get_dense_map_viewpoints(this->Handle, nullptr, 0, &first);
+    std::vector<float> out(3 * static_cast<std::size_t>(std::max(n, 0)));
+    if (n > 0) n = lsa_slam_get_dense_map_viewpoints(this->Handle, out.data(), n, &first);
+    out.resize(3 * static_cast<std::size_t>(std::max(n, 0)));
+    this->LastError = n < 0 ? std::string("GetDenseMapViewpoints: ") + lsa_slam_last_error(this->Handle) : std::string();
+    return out;
+  }
   // float xyz per point of GetRegisteredFrame(), in its order: where the sensor stood when it measured the point
   std::vector<float> GetRegisteredFrameOrigins()
   {

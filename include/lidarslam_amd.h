@@ -1304,6 +1304,58 @@ int lsa_dense_map_get_normals(lsa_dense_map* dm, int min_frames, double max_miss
 int lsa_dense_map_save_pcd_normals(lsa_dense_map* dm, const char* path, int format, int min_frames, double max_miss_ratio, int radius_leaves, int min_neighbors,
                                    const float* viewpoints_xyz, int n_viewpoints, int first_frame);
 int lsa_pcd_read_normals(const char* path, float* out4, int capacity);
+/* The floor plan (DenseMapHost.grid is the statement, held byte for byte): elevation, ground and a 2-D occupancy grid in the
+ * convention of nav_msgs/OccupancyGrid, rasterised on the device from the table as it stands -- nothing is stored, no state
+ * changes, nothing is launched on the frame path.  Only the voxels of _get_filtered(min_frames, max_miss_ratio) take part.  A
+ * voxel of index (ix, iy, iz) belongs to cell (ix // cell_leaves, iy // cell_leaves), floor division.  Floats are compared by
+ * their ordered codes (-0.0 below +0.0).  elevation: the kept point z of smallest code among the cell's voxels.  ground: the
+ * smallest-code elevation over the (2 ground_radius + 1)^2 cells around that have a voxel, the cell among them, inside the
+ * extent or not.  Per voxel h = (double)z - (double)ground(cell): h <= min_height counts in floor_voxels, min_height < h <=
+ * max_height in obstacle_voxels (top: the obstacle z of largest code), anything higher is ignored.  state: 100 when
+ * obstacle_voxels >= min_obstacle_voxels, else 0 when floor_voxels >= 1, else -1: free means the floor was seen.  A float that
+ * is not there is the quiet NaN 0x7fc00000.
+ * Extent: without a window the bounding box of the kept voxels' cells (none: width = height = 0, no error).  With use_window
+ * the cells cx0 = floor(x_min / leaf) // cell_leaves .. floor(x_max / leaf) // cell_leaves, likewise in y, whatever the map
+ * holds (a window wholly outside the index range [-2^20, 2^20) has no cell, any other is clamped to it): a window's answer
+ * is the crop of the whole grid's.  resolution = cell_leaves * leaf, origin_x = (double)(cx0 * cell_leaves) * leaf; cells are
+ * row-major, row 0 is cy0, x fastest.
+ * _get_grid fills *info, writes min(cells, capacity) records and states (either output may be null; with both null only the
+ * extent is computed) and returns width * height.  LSA_E_ARG, the map untouched: cell_leaves outside 1..64, ground_radius
+ * outside 0..16, not (0 <= min_height < max_height, both finite), min_obstacle_voxels < 1, a window that is not finite or has
+ * min > max, capacity < 0.  LSA_E_CAPACITY, before anything is allocated: width * height, formed in 64 bits, above
+ * "GridMaxCells" (lsa_dense_map_set, 1 .. 2^28, default 2^24); also when the rasters cannot be allocated.
+ * get_param: "GridMaxCells", "GridSeconds" (the last call).  _save_grid writes the states as <prefix>.pgm and <prefix>.yaml
+ * for map_server (lsa_occupancy_write) and returns the number of cells; 0 and no files for none.
+ * lsa_occupancy_write (host only): binary P5 of maxval 255 -- occupied 0, free 254, anything else 205 --, image row 0 the
+ * grid's last row; the yaml holds image (the file's name), resolution, origin: [origin_x, origin_y, 0], negate: 0,
+ * occupied_thresh: 0.65, free_thresh: 0.196.  LSA_E_ARG with the reason in lsa_occupancy_last_error (of the calling thread) when a
+ * file cannot be written; nothing is written for a grid without cells. */
+typedef struct lsa_dense_grid_params_t
+{
+  double min_height, max_height; /* metres above the ground: 0.2, 2.0 */
+  double max_miss_ratio;         /* the export's filter; below 0: none */
+  double window[4];              /* x_min, y_min, x_max, y_max in metres; read under use_window */
+  int32_t cell_leaves;           /* 1..64: 2 */
+  int32_t ground_radius;         /* cells, 0..16: 2 */
+  int32_t min_obstacle_voxels;   /* >= 1: 1 */
+  int32_t min_frames;            /* the export's filter: 1 */
+  int32_t use_window;
+} lsa_dense_grid_params_t;
+typedef struct lsa_dense_grid_info_t
+{
+  int32_t cx0, cy0, width, height;
+  double resolution, origin_x, origin_y;
+} lsa_dense_grid_info_t;
+typedef struct lsa_dense_cell_t
+{
+  float elevation, ground, top;
+  uint32_t floor_voxels, obstacle_voxels;
+} lsa_dense_cell_t;
+long long lsa_dense_map_get_grid(lsa_dense_map* dm, const lsa_dense_grid_params_t* params, lsa_dense_grid_info_t* info, lsa_dense_cell_t* cells, int8_t* state,
+                                 long long capacity);
+long long lsa_dense_map_save_grid(lsa_dense_map* dm, const lsa_dense_grid_params_t* params, const char* prefix);
+int lsa_occupancy_write(const char* prefix, const lsa_dense_grid_info_t* info, const int8_t* state);
+const char* lsa_occupancy_last_error(void);
 /* The pipeline's dense map (lsa_slam_set_param "DenseMap": 0 off, the default, under which nothing whatever changes; 1 every
  * registered frame; 2 keyframes only; "DenseMapLeafSize", default 0.1; "DenseMapMaxBytes"; read-only "DenseMapVoxels",
  * "DenseMapBytes", "DenseMapSkipped", "DenseMapRefusedFrames", "DenseMapClears").  At the end of AddFrame(s) the frame or frames of the
@@ -1351,6 +1403,12 @@ int lsa_slam_get_registered_frame_origins(lsa_slam* s, float* xyz, int capacity)
 int lsa_slam_get_dense_map_normals(lsa_slam* s, int min_frames, double max_miss_ratio, int radius_leaves, int min_neighbors, int orient, lsa_dense_normal_t* out, int capacity);
 int lsa_slam_save_dense_map_pcd_normals(lsa_slam* s, const char* path, int format, int min_frames, double max_miss_ratio, int radius_leaves, int min_neighbors, int orient);
 int lsa_slam_get_dense_map_viewpoints(lsa_slam* s, float* xyz, int capacity, int* first_frame);
+/* The floor plan of the pipeline's map: lsa_dense_map_get_grid / _save_grid behind the insertions in flight; "DenseMapGridMaxCells"
+ * (lsa_slam_set_param) is the map's "GridMaxCells".  LSA_E_STATE while "DenseMap" is 0.  A map that no frame has reached yet
+ * is an empty one. */
+long long lsa_slam_get_dense_map_grid(lsa_slam* s, const lsa_dense_grid_params_t* params, lsa_dense_grid_info_t* info, lsa_dense_cell_t* cells, int8_t* state,
+                                      long long capacity);
+long long lsa_slam_save_dense_map_grid(lsa_slam* s, const lsa_dense_grid_params_t* params, const char* prefix);
 
 /* ------------------------------------------------------------------------- */
 /* The keypoint log (Slam::LogKeypoints, slam_lib/src/Slam.cxx:1225-1255) in the memory of the device, and its replay under

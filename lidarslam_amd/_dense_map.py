@@ -2,7 +2,8 @@
 
 DenseMapHost is the numpy statement of what the map computes; the device table (lidarslam_amd/csrc/lsa_dense_map.hip) is
 held to it byte for byte, on points, voxel records, sources and misses (free-space carving: DenseMapHost.carve) and on the
-normals computed from the table (DenseMapHost.normals, dense_normals).  DenseMap is
+normals computed from the table (DenseMapHost.normals, dense_normals) and on the floor plan rasterised from it
+(DenseMapHost.grid, dense_grid: elevation, ground, and a 2-D occupancy grid of occupied / free / unknown cells).  DenseMap is
 the table alone on a Context; dense_map(slam, ...) and its neighbours reach the pipeline's map (Slam.set_param("DenseMap", 1
 or 2)).
 """
@@ -21,8 +22,31 @@ dense_voxel_dtype = np.dtype([("key", "<u8"), ("count", "<u4"), ("frames", "<u4"
 # lsa_dense_normal_t (include/lidarslam_amd.h)
 dense_normal_dtype = np.dtype([("normal_x", "<f4"), ("normal_y", "<f4"), ("normal_z", "<f4"), ("curvature", "<f4"), ("neighbors", "<u4")])
 
+# lsa_dense_cell_t and lsa_dense_grid_info_t (include/lidarslam_amd.h)
+dense_cell_dtype = np.dtype([("elevation", "<f4"), ("ground", "<f4"), ("top", "<f4"), ("floor_voxels", "<u4"), ("obstacle_voxels", "<u4")])
+dense_grid_info_dtype = np.dtype([("cx0", "<i4"), ("cy0", "<i4"), ("width", "<i4"), ("height", "<i4"), ("resolution", "<f8"), ("origin_x", "<f8"), ("origin_y", "<f8")])
+
 DENSE_INDEX_RANGE = 1 << 20  # voxel indices lie in [-2^20, 2^20)
 DENSE_NO_NORMAL = 0x7FC00000  # the four floats of a voxel without a normal: this quiet NaN
+DENSE_GRID_ABSENT = 0x7FC00000  # a cell's elevation, ground or top that is not there: the same quiet NaN
+DENSE_GRID_MAX_CELLS = 1 << 24  # "GridMaxCells" of a map that was not told otherwise
+GRID_OCCUPIED, GRID_FREE, GRID_UNKNOWN = 100, 0, -1  # nav_msgs/OccupancyGrid
+PGM_OCCUPIED, PGM_FREE, PGM_UNKNOWN = 0, 254, 205  # map_server's grey levels
+
+
+class DenseGridParams(C.Structure):
+    """lsa_dense_grid_params_t"""
+
+    _fields_ = [
+        ("min_height", C.c_double), ("max_height", C.c_double), ("max_miss_ratio", C.c_double), ("window", C.c_double * 4),
+        ("cell_leaves", C.c_int32), ("ground_radius", C.c_int32), ("min_obstacle_voxels", C.c_int32), ("min_frames", C.c_int32), ("use_window", C.c_int32),
+    ]
+
+
+class DenseGridInfo(C.Structure):
+    """lsa_dense_grid_info_t"""
+
+    _fields_ = [("cx0", C.c_int32), ("cy0", C.c_int32), ("width", C.c_int32), ("height", C.c_int32), ("resolution", C.c_double), ("origin_x", C.c_double), ("origin_y", C.c_double)]
 
 
 def dense_intensity_code(intensity):
@@ -214,6 +238,157 @@ def dense_normals(points, keys, sources, radius_leaves=2, min_neighbors=5, viewp
     return out
 
 
+def dense_order_decode(code):
+    """the floats of ordered codes (ou2f of lsa_wave.h), the inverse of dense_intensity_code on numbers"""
+    u = np.ascontiguousarray(code, np.uint32)
+    return np.where(u & np.uint32(0x80000000), u & np.uint32(0x7FFFFFFF), ~u).astype(np.uint32).view(np.float32)
+
+
+def dense_grid_check(cell_leaves=2, ground_radius=2, min_height=0.2, max_height=2.0, min_obstacle_voxels=1, window=None):
+    """ValueError for what DenseMapHost.grid refuses (the device: LSA_E_ARG)"""
+    if not 1 <= int(cell_leaves) <= 64:
+        raise ValueError("cell_leaves between 1 and 64")
+    if not 0 <= int(ground_radius) <= 16:
+        raise ValueError("ground_radius between 0 and 16 cells")
+    if not (np.isfinite(min_height) and np.isfinite(max_height) and 0 <= min_height < max_height):
+        raise ValueError("0 <= min_height < max_height, both finite")
+    if int(min_obstacle_voxels) < 1:
+        raise ValueError("min_obstacle_voxels >= 1")
+    if window is not None:
+        w = np.asarray(window, np.float64).reshape(-1)
+        if w.size != 4 or not np.isfinite(w).all() or w[0] > w[2] or w[1] > w[3]:
+            raise ValueError("window = (x_min, y_min, x_max, y_max), finite, x_min <= x_max, y_min <= y_max")
+
+
+def dense_grid_window_cells(leaf, cell_leaves, window):
+    """(cx0, cy0, cx1, cy1) of a window in metres, None for one without a cell: per end i = floor((double)v / (double)leaf),
+    the two IEEE operations of the keys; a window wholly below or above the index range has no cell, any other is clamped
+    to it; c = i // cell_leaves"""
+    w = np.asarray(window, np.float64).reshape(4)
+    cl = int(cell_leaves)
+    ends = []
+    for lo, hi in ((w[0], w[2]), (w[1], w[3])):
+        with np.errstate(over="ignore"):
+            i0, i1 = np.floor(lo / np.float64(leaf)), np.floor(hi / np.float64(leaf))
+        if i1 < -DENSE_INDEX_RANGE or i0 >= DENSE_INDEX_RANGE:
+            return None
+        i0, i1 = (int(min(max(i, -DENSE_INDEX_RANGE), DENSE_INDEX_RANGE - 1)) for i in (i0, i1))
+        ends.append((i0 // cl, i1 // cl))
+    return ends[0][0], ends[1][0], ends[0][1], ends[1][1]
+
+
+def dense_grid(points, keys, leaf, cell_leaves=2, ground_radius=2, min_height=0.2, max_height=2.0, min_obstacle_voxels=1, window=None, max_cells=DENSE_GRID_MAX_CELLS):
+    """The definition of the dense map's floor plan over an export: points and keys of the voxels that count, in any order.
+    -> (info: a dense_grid_info_dtype scalar, cells: (height, width) dense_cell_dtype, state: (height, width) int8); see
+    DenseMapHost.grid.  OverflowError when width * height > max_cells."""
+    dense_grid_check(cell_leaves, ground_radius, min_height, max_height, min_obstacle_voxels, window)
+    cl, r = int(cell_leaves), int(ground_radius)
+    pts = np.ascontiguousarray(points, POINT_DTYPE)
+    K = np.ascontiguousarray(keys, np.uint64)
+    mask = np.uint64((1 << 21) - 1)
+    cx = ((K & mask).astype(np.int64) - DENSE_INDEX_RANGE) // cl  # floor division: voxel -1 is in cell -1
+    cy = (((K >> np.uint64(21)) & mask).astype(np.int64) - DENSE_INDEX_RANGE) // cl
+    z = pts["z"].astype(np.float32)
+    code = dense_intensity_code(z)
+    info = np.zeros((), dense_grid_info_dtype)
+    info["resolution"] = np.float64(cl) * np.float64(leaf)
+    if window is not None:
+        extent = dense_grid_window_cells(leaf, cl, window)
+    else:
+        extent = (int(cx.min()), int(cy.min()), int(cx.max()), int(cy.max())) if K.size else None
+    if extent is None:
+        return info, np.zeros((0, 0), dense_cell_dtype), np.zeros((0, 0), np.int8)
+    cx0, cy0, cx1, cy1 = extent
+    W, H = cx1 - cx0 + 1, cy1 - cy0 + 1
+    if W * H > int(max_cells):
+        raise OverflowError(f"a grid of {W} x {H} cells is over max_cells = {int(max_cells)}")
+    info["cx0"], info["cy0"], info["width"], info["height"] = cx0, cy0, W, H
+    info["origin_x"] = np.float64(cx0 * cl) * np.float64(leaf)
+    info["origin_y"] = np.float64(cy0 * cl) * np.float64(leaf)
+    none = np.uint32(0xFFFFFFFF)
+    # column pass, over the window expanded by the radius: the smallest code of a column
+    col = np.full((H + 2 * r, W + 2 * r), none, np.uint32)
+    ex, ey = cx - (cx0 - r), cy - (cy0 - r)
+    near = (ex >= 0) & (ex < W + 2 * r) & (ey >= 0) & (ey < H + 2 * r)
+    np.minimum.at(col, (ey[near], ex[near]), code[near])
+    # ground pass: the smallest code of the (2r + 1)^2 columns around; min is exact and associative, so rows first
+    rows = col[:, 0:W].copy()
+    for d in range(1, 2 * r + 1):
+        np.minimum(rows, col[:, d:d + W], out=rows)
+    ground = rows[0:H].copy()
+    for d in range(1, 2 * r + 1):
+        np.minimum(ground, rows[d:d + H], out=ground)
+    # band pass: every voxel of the window against the ground of its cell (which has one: its own column at least)
+    inside = np.flatnonzero((cx >= cx0) & (cx <= cx1) & (cy >= cy0) & (cy <= cy1))
+    at = (cy[inside] - cy0, cx[inside] - cx0)
+    h = z[inside].astype(np.float64) - dense_order_decode(ground[at]).astype(np.float64)
+    low = h <= np.float64(min_height)
+    mid = ~low & (h <= np.float64(max_height))
+    floor_voxels, obstacle_voxels, top = np.zeros((H, W), np.uint32), np.zeros((H, W), np.uint32), np.zeros((H, W), np.uint32)
+    np.add.at(floor_voxels, (at[0][low], at[1][low]), np.uint32(1))
+    np.add.at(obstacle_voxels, (at[0][mid], at[1][mid]), np.uint32(1))
+    np.maximum.at(top, (at[0][mid], at[1][mid]), code[inside][mid])
+    cells = np.zeros((H, W), dense_cell_dtype)
+    elevation = col[r:r + H, r:r + W]
+    absent = np.uint32(DENSE_GRID_ABSENT)
+    cells["elevation"] = np.where(elevation != none, dense_order_decode(elevation).view(np.uint32), absent).view(np.float32)
+    cells["ground"] = np.where(ground != none, dense_order_decode(ground).view(np.uint32), absent).view(np.float32)
+    cells["top"] = np.where(top != 0, dense_order_decode(top).view(np.uint32), absent).view(np.float32)
+    cells["floor_voxels"], cells["obstacle_voxels"] = floor_voxels, obstacle_voxels
+    state = np.where(obstacle_voxels >= np.uint32(int(min_obstacle_voxels)), GRID_OCCUPIED, np.where(floor_voxels >= 1, GRID_FREE, GRID_UNKNOWN)).astype(np.int8)
+    return info, cells, state
+
+
+def occupancy_pgm(state):
+    """(height, width) uint8 as <prefix>.pgm holds it: occupied 0, free 254, unknown 205, image row 0 the grid's last row"""
+    s = np.asarray(state, np.int8)
+    return np.where(s == GRID_OCCUPIED, PGM_OCCUPIED, np.where(s == GRID_FREE, PGM_FREE, PGM_UNKNOWN)).astype(np.uint8)[::-1]
+
+
+def write_occupancy_pgm(prefix, info, state):
+    """<prefix>.pgm and <prefix>.yaml of a grid, written from Python: the statement of what lsa_occupancy_write writes, byte
+    for byte.  Nothing is written for a grid without cells; returns the number of cells"""
+    s = np.asarray(state, np.int8)
+    h, w = (int(info["height"]), int(info["width"]))
+    if h * w == 0:
+        return 0
+    prefix = os.fspath(prefix)
+    with open(prefix + ".pgm", "wb") as f:
+        f.write(b"P5\n%d %d\n255\n" % (w, h))
+        f.write(occupancy_pgm(s.reshape(h, w)).tobytes())
+    with open(prefix + ".yaml", "w") as f:
+        f.write("image: %s.pgm\nresolution: %s\norigin: [%s, %s, 0]\nnegate: 0\noccupied_thresh: 0.65\nfree_thresh: 0.196\n" % (
+            os.path.basename(prefix), "%.17g" % float(info["resolution"]), "%.17g" % float(info["origin_x"]), "%.17g" % float(info["origin_y"])))
+    return h * w
+
+
+def read_occupancy_pgm(prefix):
+    """(state (height, width) int8 with row 0 the grid's first row again, resolution, (origin_x, origin_y)) of <prefix>.pgm and
+    <prefix>.yaml; ValueError for a file that is not a map of save_grid's"""
+    prefix = os.fspath(prefix)
+    data = open(prefix + ".pgm", "rb").read()
+    head = data.split(b"\n", 3)
+    if len(head) < 4 or head[0] != b"P5" or head[2] != b"255":
+        raise ValueError(prefix + ".pgm: not a binary PGM of maxval 255")
+    w, h = (int(v) for v in head[1].split())
+    grey = np.frombuffer(head[3], np.uint8)
+    if grey.size != w * h:
+        raise ValueError(prefix + ".pgm: %d bytes of pixels for %d x %d" % (grey.size, w, h))
+    grey = grey.reshape(h, w)[::-1]
+    known = (grey == PGM_OCCUPIED) | (grey == PGM_FREE) | (grey == PGM_UNKNOWN)
+    if not known.all():
+        raise ValueError(prefix + ".pgm: a grey level that is none of 0, 254, 205")
+    state = np.where(grey == PGM_OCCUPIED, GRID_OCCUPIED, np.where(grey == PGM_FREE, GRID_FREE, GRID_UNKNOWN)).astype(np.int8)
+    fields = {}
+    for line in open(prefix + ".yaml"):
+        name, _, value = line.partition(":")
+        fields[name.strip()] = value.strip()
+    if fields.get("image") != os.path.basename(prefix) + ".pgm" or fields.get("negate") != "0":
+        raise ValueError(prefix + ".yaml: not the description of " + prefix + ".pgm")
+    origin = [float(v) for v in fields["origin"].strip("[]").split(",")]
+    return state, float(fields["resolution"]), (origin[0], origin[1])
+
+
 class DenseMapHost:
     """The definition.  State: key -> (point, count, frames, first_frame, last_frame, intensity code, source).
 
@@ -258,7 +433,22 @@ class DenseMapHost:
     component of e0 (anything else keeps eigen33's sign).  normal = (float)e0, t = (l0 + l1) + l2, curvature = t > 0 ?
     (float)|l0 / t| : 0 (PCL's surface variation).  Nothing depends on the order of the voxels; no state changes.
     `eig` is the eigen step, (m, 6) -> (m, 12) in the layout of lsa_selftest_numerics fn 3; None is numpy.linalg.eigh
-    (eigh_eig), which is NOT the byte definition."""
+    (eigh_eig), which is NOT the byte definition.
+
+    grid(cell_leaves, ground_radius, min_height, max_height, min_obstacle_voxels, min_frames, max_miss_ratio, window): the floor
+    plan, from the voxels of get(min_frames, max_miss_ratio) alone.  A voxel (ix, iy, iz) -- the indices of its key -- belongs
+    to cell (ix // cell_leaves, iy // cell_leaves), floor division.  Codes are dense_intensity_code's (f2ou: -0.0 below +0.0).
+    Column: a cell's elevation is the kept point z (the float of the slot) of smallest code among its voxels.  Ground:
+    ground(c) is the smallest-code elevation over the (2 * ground_radius + 1)^2 cells around c that have a column, c among
+    them, whether or not they lie inside the extent; none when none has one.  Band: per voxel h = (double)z -
+    (double)ground(cell); h <= min_height is a floor voxel, min_height < h <= max_height an obstacle voxel, above that it is
+    ignored; top is the obstacle z of largest code; the counts are uint32.  State (int8): 100 when obstacle_voxels >=
+    min_obstacle_voxels, else 0 when floor_voxels >= 1, else -1 -- free means the floor was seen.  An absent float is the NaN
+    0x7fc00000.  Extent: without a window the bounding box of the kept voxels' cells (no kept voxel: width = height = 0); with
+    window = (x_min, y_min, x_max, y_max) the cells of dense_grid_window_cells, whatever the map holds, so that a window's
+    answer is the crop of the whole grid's, to the byte.  resolution = cell_leaves * leaf, origin_x = (double)(cx0 *
+    cell_leaves) * leaf; cells are row-major, row 0 is cy0, x fastest.  Nothing depends on the order of the voxels; no state
+    changes.  ValueError for what dense_grid_check refuses, OverflowError above max_cells."""
 
     def __init__(self, leaf):
         if not (leaf > 0 and np.isfinite(leaf)):
@@ -366,6 +556,14 @@ class DenseMapHost:
             raise ValueError("min_frames >= 1")
         pts, vox = self.get(min_frames, max_miss_ratio)
         return dense_normals(pts, vox["key"], self.sources(min_frames, max_miss_ratio), radius_leaves, min_neighbors, viewpoints, first_frame, eig)
+
+    def grid(self, cell_leaves=2, ground_radius=2, min_height=0.2, max_height=2.0, min_obstacle_voxels=1, min_frames=1, max_miss_ratio=-1.0, window=None,
+             max_cells=DENSE_GRID_MAX_CELLS):
+        """(info, cells (height, width) dense_cell_dtype, state (height, width) int8) of the voxels of get(min_frames,
+        max_miss_ratio); see the class"""
+        dense_grid_check(cell_leaves, ground_radius, min_height, max_height, min_obstacle_voxels, window)
+        pts, vox = self.get(min_frames, max_miss_ratio)
+        return dense_grid(pts, vox["key"], self.leaf, cell_leaves, ground_radius, min_height, max_height, min_obstacle_voxels, window, max_cells)
 
     def prune(self, min_frames=1, max_miss_ratio=-1.0):
         """removes every voxel get(min_frames, max_miss_ratio) leaves out; returns their number (also added to self.pruned)"""
@@ -564,6 +762,19 @@ class DenseMap:
             "lsa_dense_map_save_pcd_normals",
         )
 
+    def grid(self, cell_leaves=2, ground_radius=2, min_height=0.2, max_height=2.0, min_obstacle_voxels=1, min_frames=1, max_miss_ratio=-1.0, window=None):
+        """(info, cells (height, width) dense_cell_dtype, state (height, width) int8) as DenseMapHost.grid states them, computed on
+        the device from the table as it stands.  LsaError with .code E_ARG for what the statement refuses, E_CAPACITY for a
+        grid of more than "GridMaxCells" cells; the map is untouched either way"""
+        return _grid_call(lambda *a: self.L.lsa_dense_map_get_grid(self.h, *a), self._check, "lsa_dense_map_get_grid",
+                          _grid_params(cell_leaves, ground_radius, min_height, max_height, min_obstacle_voxels, min_frames, max_miss_ratio, window))
+
+    def save_grid(self, prefix, cell_leaves=2, ground_radius=2, min_height=0.2, max_height=2.0, min_obstacle_voxels=1, min_frames=1, max_miss_ratio=-1.0, window=None):
+        """the states of grid(...) into <prefix>.pgm and <prefix>.yaml for map_server; returns the number of cells (0 and no
+        files for none)"""
+        p = _grid_params(cell_leaves, ground_radius, min_height, max_height, min_obstacle_voxels, min_frames, max_miss_ratio, window)
+        return self._check(self.L.lsa_dense_map_save_grid(self.h, C.byref(p), os.fsencode(prefix)), "lsa_dense_map_save_grid")
+
     def save_pcd(self, path, fmt=PCD_BINARY, min_frames=1, max_miss_ratio=-1.0):
         """the points of get(min_frames, max_miss_ratio) into a PCD file; returns their number (0 and no file for none)"""
         return self._check(
@@ -580,6 +791,34 @@ def _viewpoints(viewpoints):
         raise ValueError("viewpoints of shape (n, 3)")
     vp = np.ascontiguousarray(vp, np.float32)
     return vp, vp.shape[0]
+
+
+def _grid_params(cell_leaves, ground_radius, min_height, max_height, min_obstacle_voxels, min_frames, max_miss_ratio, window):
+    """the lsa_dense_grid_params_t of a call; ValueError only for a window that is not four numbers (the library refuses the rest)"""
+    p = DenseGridParams()
+    p.cell_leaves, p.ground_radius, p.min_obstacle_voxels, p.min_frames = int(cell_leaves), int(ground_radius), int(min_obstacle_voxels), int(min_frames)
+    p.min_height, p.max_height, p.max_miss_ratio = float(min_height), float(max_height), float(max_miss_ratio)
+    if window is not None:
+        w = np.asarray(window, np.float64).reshape(-1)
+        if w.size != 4:
+            raise ValueError("window = (x_min, y_min, x_max, y_max)")
+        p.use_window = 1
+        p.window[:] = w.tolist()
+    return p
+
+
+def _grid_call(call, check, what, p):
+    """the two calls of a grid export: the extent alone (no output asked for: no cell is computed), then the cells"""
+    info = DenseGridInfo()
+    n = check(call(C.byref(p), C.byref(info), None, None, 0), what)
+    cells, state = np.zeros(max(n, 1), dense_cell_dtype), np.zeros(max(n, 1), np.int8)
+    if n > 0:
+        n = check(call(C.byref(p), C.byref(info), ptr(cells), ptr(state), n), what)
+    out = np.zeros((), dense_grid_info_dtype)
+    for name in dense_grid_info_dtype.names:
+        out[name] = getattr(info, name)
+    h, w = int(info.height), int(info.width)
+    return out, cells[:n].reshape(h, w).copy(), state[:n].reshape(h, w).copy()
 
 
 def read_pcd_normals(path):
@@ -724,3 +963,19 @@ def save_dense_map_pcd_normals(slam, path, format=PCD_BINARY, min_frames=1, max_
         ),
         "lsa_slam_save_dense_map_pcd_normals",
     )
+
+
+def dense_map_grid(slam, cell_leaves=2, ground_radius=2, min_height=0.2, max_height=2.0, min_obstacle_voxels=1, min_frames=1, max_miss_ratio=-1.0, window=None, half_extent=None):
+    """DenseMap.grid of the pipeline's map: (info, cells, state).  half_extent (metres): the window of that half side around
+    the translation of slam.world_transform() -- the local costmap -- when no window is given"""
+    if window is None and half_extent is not None:
+        T = np.asarray(slam.world_transform(), np.float64).reshape(4, 4)
+        window = (T[0, 3] - float(half_extent), T[1, 3] - float(half_extent), T[0, 3] + float(half_extent), T[1, 3] + float(half_extent))
+    return _grid_call(lambda *a: slam.L.lsa_slam_get_dense_map_grid(slam.h, *a), slam._check, "lsa_slam_get_dense_map_grid",
+                      _grid_params(cell_leaves, ground_radius, min_height, max_height, min_obstacle_voxels, min_frames, max_miss_ratio, window))
+
+
+def save_dense_map_grid(slam, prefix, cell_leaves=2, ground_radius=2, min_height=0.2, max_height=2.0, min_obstacle_voxels=1, min_frames=1, max_miss_ratio=-1.0, window=None):
+    """the states of dense_map_grid into <prefix>.pgm and <prefix>.yaml; returns the number of cells (0 and no files for none)"""
+    p = _grid_params(cell_leaves, ground_radius, min_height, max_height, min_obstacle_voxels, min_frames, max_miss_ratio, window)
+    return slam._check(slam.L.lsa_slam_save_dense_map_grid(slam.h, C.byref(p), os.fsencode(prefix)), "lsa_slam_save_dense_map_grid")

@@ -370,6 +370,19 @@ int lsa_slam_get_dense_map_viewpoints(lsa_slam* s, float* xyz, int capacity, int
   return s->core.GetDenseMapViewpoints(xyz, capacity, first_frame);
 }
 
+long long lsa_slam_get_dense_map_grid(lsa_slam* s, const lsa_dense_grid_params_t* params, lsa_dense_grid_info_t* info, lsa_dense_cell_t* cells, int8_t* state,
+                                      long long capacity)
+{
+  if (!s) return LSA_E_ARG;
+  return s->core.GetDenseMapGrid(params, info, cells, state, capacity);
+}
+
+long long lsa_slam_save_dense_map_grid(lsa_slam* s, const lsa_dense_grid_params_t* params, const char* prefix)
+{
+  if (!s || !prefix) return LSA_E_ARG;
+  return s->core.SaveDenseMapGrid(params, prefix);
+}
+
 int lsa_slam_get_registered_frame_origins(lsa_slam* s, float* xyz, int capacity)
 {
   if (!s || (!xyz && capacity > 0)) return LSA_E_ARG;

@@ -275,6 +275,7 @@ public:
   int DenseMapMode = 0;
   double DenseMapLeafSize = 0.1;
   double DenseMapMaxBytes = 16. * 1024. * 1024. * 1024.;  // of the table; 0: no limit
+  double DenseMapGridMaxCells = 16777216.;  // the map's "GridMaxCells": the most cells GetDenseMapGrid hands out
   unsigned DenseFrames = 0, DenseRefused = 0, DenseClears = 0;
   // "DenseMapOnTrajectory": what an applied trajectory does to the map.  0 clears it (the default); 1 re-projects it on the
   // device, every voxel's point under new * inverse(old) of the logged pose of the frame that measured it
@@ -299,6 +300,9 @@ public:
   int GetDenseMapNormals(int minFrames, double maxMissRatio, int radiusLeaves, int minNeighbors, int orient, lsa_dense_normal_t* out, int capacity);
   int SaveDenseMapToPCDNormals(const std::string& path, int format, int minFrames, double maxMissRatio, int radiusLeaves, int minNeighbors, int orient);
   int GetDenseMapViewpoints(float* xyz, int capacity, int* firstFrame);
+  // the floor plan: elevation, ground and the occupancy grid, rasterised from the table as it stands
+  long long GetDenseMapGrid(const lsa_dense_grid_params_t* params, lsa_dense_grid_info_t* info, lsa_dense_cell_t* cells, int8_t* state, long long capacity);
+  long long SaveDenseMapGrid(const lsa_dense_grid_params_t* params, const std::string& prefix);
 
   // ---- state ----
   Pose Tworld, PreviousTworld, Trelative;
@@ -451,6 +455,7 @@ private:
   int ReprojectDenseMap(const std::vector<double>& corrections, int firstOrdinal);
   void DropDenseMap(const char* why);  // why == nullptr: the caller asked for it, nothing to warn about
   int DenseReady(const char* who);
+  int MakeDenseMap();  // the map with the pipeline's knobs, when there is none yet
   int SetDenseCarveParams();  // the knobs into the map, when there is one
 
   // ---- diagnostics ----

@@ -15,15 +15,20 @@ namespace host
 // The frame or frames of the call under exactly the poses GetRegisteredFrame uses, fused with the insertion, on the
 // look-ahead stream; nothing is waited for.  A refused insertion (the table would outgrow "DenseMapMaxBytes") is counted
 // and reported, and does not fail the frame.
+int SlamCore::MakeDenseMap()
+{
+  if (Dense) return LSA_OK;
+  LSA_TRY(lsa_dense_map_create(Ctx, DenseMapLeafSize, &Dense));
+  LSA_TRY(lsa_dense_map_set(Dense, "MaxBytes", DenseMapMaxBytes));
+  LSA_TRY(lsa_dense_map_set(Dense, "GridMaxCells", DenseMapGridMaxCells));
+  if (DenseMapCarve) LSA_TRY(SetDenseCarveParams());
+  return LSA_OK;
+}
+
 int SlamCore::InsertDenseFrame(bool keyframe, double time)
 {
   if (DenseMapMode == 2 && !keyframe) return LSA_OK;
-  if (!Dense)
-  {
-    LSA_TRY(lsa_dense_map_create(Ctx, DenseMapLeafSize, &Dense));
-    LSA_TRY(lsa_dense_map_set(Dense, "MaxBytes", DenseMapMaxBytes));
-    if (DenseMapCarve) LSA_TRY(SetDenseCarveParams());
-  }
+  LSA_TRY(MakeDenseMap());
   const int ordinal = static_cast<int>(DenseFrames);
   bool inserted = false, refused = false;
   // the ordinal's viewpoint: where the sensor of the call's first frame stands under the pose of the insertion
@@ -325,6 +330,25 @@ int SlamCore::GetDenseMapViewpoints(float* xyz, int capacity, int* firstFrame)
   const int take = std::min(n, capacity);
   if (take > 0) std::memcpy(xyz, DenseViewpoints.data(), static_cast<size_t>(take) * 3 * sizeof(float));
   return n;
+}
+
+// (a map no frame has reached yet is made here, empty: a window is answered whatever the map holds)
+long long SlamCore::GetDenseMapGrid(const lsa_dense_grid_params_t* params, lsa_dense_grid_info_t* info, lsa_dense_cell_t* cells, int8_t* state, long long capacity)
+{
+  if (const int rc = DenseReady("GetDenseMapGrid"); rc < 0) return rc;
+  if (!params || !info || capacity < 0) { LastError = "GetDenseMapGrid: bad argument"; return LSA_E_ARG; }
+  if (const int rc = MakeDenseMap(); rc < 0) return rc;
+  const long long n = lsa_dense_map_get_grid(Dense, params, info, cells, state, capacity);
+  return n < 0 ? Fail(static_cast<int>(n), "lsa_dense_map_get_grid") : n;
+}
+
+long long SlamCore::SaveDenseMapGrid(const lsa_dense_grid_params_t* params, const std::string& prefix)
+{
+  if (const int rc = DenseReady("SaveDenseMapGrid"); rc < 0) return rc;
+  if (!params) { LastError = "SaveDenseMapGrid: bad argument"; return LSA_E_ARG; }
+  if (const int rc = MakeDenseMap(); rc < 0) return rc;
+  const long long n = lsa_dense_map_save_grid(Dense, params, prefix.c_str());
+  return n < 0 ? Fail(static_cast<int>(n), "lsa_dense_map_save_grid") : n;
 }
 
 int SlamCore::ClearDenseMap()

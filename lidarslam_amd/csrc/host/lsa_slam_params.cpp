@@ -154,6 +154,13 @@ int SlamCore::SetParamValue(const std::string& name, double v)
     if (Dense) lsa_dense_map_set(Dense, "MaxBytes", v);
     return LSA_OK;
   }
+  if (name == "DenseMapGridMaxCells")
+  {
+    if (!(v >= 1.) || v > 268435456. || v != static_cast<double>(static_cast<long long>(v))) { LastError = "DenseMapGridMaxCells: a whole number between 1 and 2^28"; return LSA_E_ARG; }
+    DenseMapGridMaxCells = v;
+    if (Dense) lsa_dense_map_set(Dense, "GridMaxCells", v);
+    return LSA_OK;
+  }
   if (name == "DenseMapCarve")
   {
     if (!(v == 0. || v == 1.)) { LastError = "DenseMapCarve: 0 off, 1 the rays of every inserted frame carve free space"; return LSA_E_ARG; }
@@ -247,6 +254,7 @@ int SlamCore::GetParam(const std::string& name, double* v) const
   if (name == "DenseMap") { *v = DenseMapMode; return LSA_OK; }
   if (name == "DenseMapLeafSize") { *v = DenseMapLeafSize; return LSA_OK; }
   if (name == "DenseMapMaxBytes") { *v = DenseMapMaxBytes; return LSA_OK; }
+  if (name == "DenseMapGridMaxCells") { *v = DenseMapGridMaxCells; return LSA_OK; }
   if (name == "DenseMapCapacity") { *v = Dense ? lsa_dense_map_get_param(Dense, "Capacity") : 0.; return LSA_OK; }
   // (the two that count on the device wait for the insertions in flight)
   if (name == "DenseMapVoxels") { *v = Dense ? std::max(lsa_dense_map_size(Dense), 0) : 0; return LSA_OK; }

@@ -901,6 +901,85 @@ public:
     this->LastError = n < 0 ? std::string("GetDenseMapViewpoints: ") + lsa_slam_last_error(this->Handle) : std::string();
     return out;
   }
+  // The floor plan: the dense map rasterised on the device into cells of cellLeaves voxels -- elevation (the lowest kept point
+  // of the cell), ground (the lowest elevation within groundRadius cells), and the state of nav_msgs/OccupancyGrid: 100
+  // occupied (minObstacleVoxels voxels at least between minHeight and maxHeight above the ground), 0 free (the floor was seen
+  // and nothing stands on it; what is higher than maxHeight is driven under), -1 unknown.  Only the voxels of
+  // GetDenseMap(minFrames, maxMissRatio) count.  With useWindow the grid is exactly the window (metres, world frame), and is the
+  // crop of the whole grid; without, the bounding box of the map.  Cells are row-major, row 0 is the lowest y, x fastest.
+  struct DenseGridParams
+  {
+    int cellLeaves = 2, groundRadius = 2, minObstacleVoxels = 1, minFrames = 1;
+    double minHeight = 0.2, maxHeight = 2.0, maxMissRatio = -1.;
+    bool useWindow = false;
+    double xMin = 0., yMin = 0., xMax = 0., yMax = 0.;
+    DenseGridParams() {}  // (user-provided: the defaults above are used as default arguments inside the enclosing class)
+  };
+  struct DenseCell
+  {
+    float elevation, ground, top;  // NaN: not there
+    std::uint32_t floor_voxels, obstacle_voxels;
+  };
+  struct DenseGrid
+  {
+    int cx0 = 0, cy0 = 0, width = 0, height = 0;         // in cells
+    double resolution = 0., origin_x = 0., origin_y = 0.;  // metres: the cell's side, the world position of the corner of cell (0, 0)
+    std::vector<DenseCell> cells;
+    std::vector<std::int8_t> states;
+  };
+  void SetDenseMapGridMaxCells(double cells) { this->SetParam("DenseMapGridMaxCells", cells); }
+  double GetDenseMapGridMaxCells() const { return this->GetParam("DenseMapGridMaxCells"); }
+  DenseGrid GetDenseMapGrid(const DenseGridParams& params = DenseGridParams())
+  {
+    static_assert(sizeof(DenseCell) == sizeof(lsa_dense_cell_t), "DenseCell is lsa_dense_cell_t");
+    const lsa_dense_grid_params_t p = GridParams(params);
+    lsa_dense_grid_info_t info;
+    DenseGrid out;
+    // the extent is asked for first (no cell is computed for it), so the grid is handed out once and whole
+    long long n = lsa_slam_get_dense_map_grid(this->Handle, &p, &info, nullptr, nullptr, 0);
+    if (n > 0)
+    {
+      out.cells.resize(static_cast<std::size_t>(n));
+      out.states.resize(static_cast<std::size_t>(n));
+      n = lsa_slam_get_dense_map_grid(this->Handle, &p, &info, reinterpret_cast<lsa_dense_cell_t*>(out.cells.data()), out.states.data(), n);
+    }
+    if (n >= 0)
+    {
+      out.cx0 = info.cx0; out.cy0 = info.cy0; out.width = info.width; out.height = info.height;
+      out.resolution = info.resolution; out.origin_x = info.origin_x; out.origin_y = info.origin_y;
+    }
+    out.cells.resize(static_cast<std::size_t>(std::max(n, 0ll)));
+    out.states.resize(static_cast<std::size_t>(std::max(n, 0ll)));
+    this->LastError = n < 0 ? std::string("GetDenseMapGrid: ") + lsa_slam_last_error(this->Handle) : std::string();
+    return out;
+  }
+  // the local costmap: the window of 2 * halfExtent metres a side around the current GetWorldTransform translation
+  DenseGrid GetDenseMapGridAround(double halfExtent, DenseGridParams params = DenseGridParams())
+  {
+    const Transform t = this->GetWorldTransform();
+    params.useWindow = true;
+    params.xMin = t.matrix[3] - halfExtent; params.xMax = t.matrix[3] + halfExtent;
+    params.yMin = t.matrix[7] - halfExtent; params.yMax = t.matrix[7] + halfExtent;
+    return this->GetDenseMapGrid(params);
+  }
+  // <prefix>.pgm and <prefix>.yaml for map_server: occupied 0, free 254, unknown 205; the number of cells, 0 and no files for none
+  long long SaveDenseMapGrid(const std::string& prefix, const DenseGridParams& params = DenseGridParams()) const
+  {
+    const lsa_dense_grid_params_t p = GridParams(params);
+    const long long rc = lsa_slam_save_dense_map_grid(this->Handle, &p, prefix.c_str());
+    this->LastError = rc < 0 ? std::string("SaveDenseMapGrid: ") + lsa_slam_last_error(this->Handle) : std::string();
+    return rc;
+  }
+  static lsa_dense_grid_params_t GridParams(const DenseGridParams& params)
+  {
+    lsa_dense_grid_params_t p;
+    std::memset(&p, 0, sizeof(p));
+    p.cell_leaves = params.cellLeaves; p.ground_radius = params.groundRadius; p.min_obstacle_voxels = params.minObstacleVoxels; p.min_frames = params.minFrames;
+    p.min_height = params.minHeight; p.max_height = params.maxHeight; p.max_miss_ratio = params.maxMissRatio;
+    p.use_window = params.useWindow ? 1 : 0;
+    p.window[0] = params.xMin; p.window[1] = params.yMin; p.window[2] = params.xMax; p.window[3] = params.yMax;
+    return p;
+  }
   // float xyz per point of GetRegisteredFrame(), in its order: where the sensor stood when it measured the point
   std::vector<float> GetRegisteredFrameOrigins()
   {

@@ -1410,6 +1410,69 @@ long long lsa_slam_get_dense_map_grid(lsa_slam* s, const lsa_dense_grid_params_t
                                       long long capacity);
 long long lsa_slam_save_dense_map_grid(lsa_slam* s, const lsa_dense_grid_params_t* params, const char* prefix);
 
+/* Rays through the dense map (lsa_dense_cast.hip, DESIGN.md 3.14 "Rays"; the statement is DenseMapHost.cast / .compare, and the
+ * device is held to its bytes).  A ray runs from an origin o towards a target t, both float widened to double, with the
+ * geometry of the carve and len + extend in place of len - margin: tt = min(len + extend, max_range), e = o + (t - o) * (tt /
+ * len); no ray when a coordinate is not finite, tt is not > 0, len is 0 or an end index lies outside [-2^20, 2^20).  The walk
+ * is the carve's (one device function, dense_ray_begin / dense_ray_step).  A visited voxel counts when it exists, frames >=
+ * min_frames, for max_miss_ratio >= 0 misses <= max_miss_ratio * frames (the export's predicate) and, under use_before,
+ * first_frame < before.  The first that counts is the hit and ends the walk.  lsa_dense_hit_t: key (as lsa_dense_voxel_t's; 0
+ * unless status 1), entry / exit = (float)(t_in * tt) / (float)(t_out * tt) -- metres along the ray at which it enters and
+ * leaves the voxel --, depth = the kept point projected on the ray, steps = voxels visited (up to the hit; all for a miss; 0
+ * for no ray), source = the hit voxel's source ordinal, status -1 no ray, 0 miss, 1 hit.  points (may be NULL): the hit
+ * voxel's LidarPoint, 32 zero bytes otherwise.
+ * lsa_dense_map_compare_*: one label per point, the ray from its origin to the point with extend = the tolerance (finite, >=
+ * 0): 0 NOT_JUDGED (no ray, or len > max_range), 2 UNMAPPED (no hit), 3 THROUGH_MAP (hit whose t_out * tt < len - tolerance),
+ * 1 CONSISTENT (any other hit); counts[4] the number of each.  _compare_frame: the context's current frame under the poses of
+ * lsa_dense_map_carve_frame -- the labels of _compare_points of lsa_transform_frame_at's points and
+ * lsa_transform_frame_origins_at's origins; returns the number of points (LSA_E_CAPACITY, nothing written, above capacity).
+ * Two limits of a test by voxels: at tolerance 0 a point exactly on a voxel face may end its walk one voxel short (o + (t - o)
+ * need not be t), and at grazing incidence the ray meets occupied voxels of the same surface well before the point, so far
+ * ground reads THROUGH_MAP at a small tolerance; UNMAPPED is the robust label.
+ * The calls wait for the insertions and carves in flight, change nothing in the map (no voxel, record, miss, "Rays", last
+ * ordinal) and claim nothing in the table; a thread makes at most 3 * (4096 + 2) steps.  LSA_E_ARG, outputs and map untouched:
+ * a NULL pointer, n < 0, n_origins neither 1 nor n, max_range not finite, not > 0 or above 4096 leaves, extend NaN (compare:
+ * not finite or < 0), min_frames < 1, use_before neither 0 nor 1, reserved not 0.  n == 0 is LSA_OK.
+ * lsa_dense_map_get_param: "CastRays" (rays cast by these calls since the last clear), "CastSeconds" (the host's, of the last).
+ * lsa_scan_targets (host only): the rays of a spinning sensor at a pose: origin = the translation narrowed to float, target
+ * (r, c) = the pose applied to (cos el_r cos az_c, cos el_r sin az_c, sin el_r), az_c = 2 pi c / n_azimuth, in double, narrowed
+ * to float, ring-major.  A render is lsa_dense_map_cast of these with extend = +inf. */
+typedef struct lsa_dense_cast_params_t
+{
+  double max_range;      /* metres, finite, > 0, at most 4096 leaves */
+  double extend;         /* metres past the target; +inf: to max_range; NaN refused; compare: the tolerance, finite, >= 0 */
+  double max_miss_ratio; /* the export's filter; below 0: none */
+  int32_t min_frames;    /* >= 1 */
+  int32_t use_before;    /* 0: every voxel; 1: only first_frame < before */
+  int32_t before;
+  int32_t reserved;      /* 0 */
+} lsa_dense_cast_params_t;
+typedef struct lsa_dense_hit_t
+{
+  uint64_t key;
+  float entry, exit, depth;
+  int32_t steps, source, status;
+} lsa_dense_hit_t;
+int lsa_dense_map_cast(lsa_dense_map* dm, const float* origins_xyz, int n_origins, const float* targets_xyz, int n, const lsa_dense_cast_params_t* params,
+                       lsa_dense_hit_t* hits, lsa_point_t* points);
+int lsa_dense_map_compare_points(lsa_dense_map* dm, const lsa_point_t* pts, int n, const float* origins_xyz, int n_origins, const lsa_dense_cast_params_t* params,
+                                 uint8_t* labels, long long counts[4]);
+int lsa_dense_map_compare_frame(lsa_dense_map* dm, int interpolate, const double H0[16], const double H1[16], double t0, double t1, double time_offset,
+                                const lsa_dense_cast_params_t* params, uint8_t* labels, int capacity, long long counts[4]);
+int lsa_scan_targets(const double pose16[16], const double* elevations_rad, int n_rings, int n_azimuth, float* origin_xyz, float* targets_xyz);
+/* The pipeline's map under these calls; LSA_E_STATE while "DenseMap" is 0; each waits for the maps' work in flight and adds
+ * nothing to a frame.  _render_dense_map_scan: lsa_dense_map_cast of lsa_scan_targets at pose16 (NULL: Tworld *
+ * BaseToLidarOffset) with the params as given (extend = +inf for a scan); hits: n_rings * n_azimuth.
+ * _compare_frame_to_dense_map: one label per point of lsa_slam_get_registered_frame, in its order, every device frame of the
+ * last call under the poses the insertion used; returns their number.  params NULL: max_range 30, tolerance one leaf,
+ * min_frames 1, ratio -1, use_before 2.  use_before == 2 (this call only): when the call that brought the current frame was
+ * inserted into the map, before = that call's ordinal -- the map as it stood before this frame --, otherwise every voxel. */
+int lsa_slam_cast_dense_map_rays(lsa_slam* s, const float* origins_xyz, int n_origins, const float* targets_xyz, int n, const lsa_dense_cast_params_t* params,
+                                 lsa_dense_hit_t* hits, lsa_point_t* points);
+int lsa_slam_render_dense_map_scan(lsa_slam* s, const double* pose16, const double* elevations_rad, int n_rings, int n_azimuth, const lsa_dense_cast_params_t* params,
+                                   lsa_dense_hit_t* hits);
+int lsa_slam_compare_frame_to_dense_map(lsa_slam* s, const lsa_dense_cast_params_t* params, uint8_t* labels, int capacity, long long counts[4]);
+
 /* ------------------------------------------------------------------------- */
 /* The keypoint log (Slam::LogKeypoints, slam_lib/src/Slam.cxx:1225-1255) in the memory of the device, and its replay under
  * a corrected trajectory (the part of Slam::RunPoseGraphOptimization that comes after the optimizer, Slam.cxx:416-475).

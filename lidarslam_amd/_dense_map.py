@@ -13,7 +13,7 @@ import os
 import numpy as np
 
 from ._abi import LsaError, _error, lib
-from ._native import POINT_DTYPE, pose16, ptr
+from ._native import LIB_PATH, POINT_DTYPE, pose16, ptr
 from ._pcd import PCD_BINARY
 
 # lsa_dense_voxel_t (include/lidarslam_amd.h)
@@ -25,6 +25,9 @@ dense_normal_dtype = np.dtype([("normal_x", "<f4"), ("normal_y", "<f4"), ("norma
 # lsa_dense_cell_t and lsa_dense_grid_info_t (include/lidarslam_amd.h)
 dense_cell_dtype = np.dtype([("elevation", "<f4"), ("ground", "<f4"), ("top", "<f4"), ("floor_voxels", "<u4"), ("obstacle_voxels", "<u4")])
 dense_grid_info_dtype = np.dtype([("cx0", "<i4"), ("cy0", "<i4"), ("width", "<i4"), ("height", "<i4"), ("resolution", "<f8"), ("origin_x", "<f8"), ("origin_y", "<f8")])
+
+# lsa_dense_hit_t (include/lidarslam_amd.h): what a ray cast through the map reports
+dense_hit_dtype = np.dtype([("key", "<u8"), ("entry", "<f4"), ("exit", "<f4"), ("depth", "<f4"), ("steps", "<i4"), ("source", "<i4"), ("status", "<i4")])
 
 DENSE_INDEX_RANGE = 1 << 20  # voxel indices lie in [-2^20, 2^20)
 DENSE_NO_NORMAL = 0x7FC00000  # the four floats of a voxel without a normal: this quiet NaN
@@ -40,6 +43,15 @@ class DenseGridParams(C.Structure):
     _fields_ = [
         ("min_height", C.c_double), ("max_height", C.c_double), ("max_miss_ratio", C.c_double), ("window", C.c_double * 4),
         ("cell_leaves", C.c_int32), ("ground_radius", C.c_int32), ("min_obstacle_voxels", C.c_int32), ("min_frames", C.c_int32), ("use_window", C.c_int32),
+    ]
+
+
+class DenseCastParams(C.Structure):
+    """lsa_dense_cast_params_t"""
+
+    _fields_ = [
+        ("max_range", C.c_double), ("extend", C.c_double), ("max_miss_ratio", C.c_double),
+        ("min_frames", C.c_int32), ("use_before", C.c_int32), ("before", C.c_int32), ("reserved", C.c_int32),
     ]
 
 
@@ -72,10 +84,16 @@ def dense_voxel_keys(points, leaf):
     return keys, ok
 
 
-def dense_ray_steps(points, origins, leaf, margin_leaves=2.0, max_range=30.0, stride=1):
+def dense_ray_steps(points, origins, leaf, margin_leaves=2.0, max_range=30.0, stride=1, extend=None, info=None):
     """The walk of DenseMapHost.carve, for all rays at once.  Yields (ray, index): `ray` the indices into `points` of the rays
     that visit a voxel in this round, `index` (len(ray), 3) int64 the voxel each visits.  The first round is every ray's
-    start voxel; a ray of k steps appears in the first k + 1 rounds.  A point that casts no ray never appears."""
+    start voxel; a ray of k steps appears in the first k + 1 rounds.  A point that casts no ray never appears.
+
+    With `extend` (metres, may be +inf or negative) the walk is DenseMapHost.cast's: reach = len + extend in place of len -
+    margin_leaves * leaf, and every round yields (ray, index, t_in, t_out): the step parameter in [0, 1] at which the ray
+    entered the voxel (the tmax of the step that entered it, before tdelta was added; 0 for the start voxel) and at which it
+    leaves it (the smallest tmax among the axes with steps left, 1 when none is left).  `info`, a dict, is given "ray",
+    "len" and "tt" of the rays that are cast before the first round."""
     pts = np.ascontiguousarray(points, POINT_DTYPE)
     n = pts.size
     org = np.ascontiguousarray(origins, np.float32).reshape(-1, 3)
@@ -93,9 +111,9 @@ def dense_ray_steps(points, origins, leaf, margin_leaves=2.0, max_range=30.0, st
     with np.errstate(all="ignore"):
         d = p - o
         length = np.sqrt((d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]) + d[:, 2] * d[:, 2])
-        reach = length - np.float64(margin_leaves) * leaf
+        reach = length - np.float64(margin_leaves) * leaf if extend is None else length + np.float64(extend)
         t = np.where(reach < np.float64(max_range), reach, np.float64(max_range))
-        ok = np.isfinite(o).all(axis=1) & np.isfinite(p).all(axis=1) & (t > 0)
+        ok = np.isfinite(o).all(axis=1) & np.isfinite(p).all(axis=1) & (t > 0) & (length > 0)  # (len 0 and a margin: t <= 0 already)
         e = o + d * (t / length)[:, None]
         f0, f1 = np.floor(o / leaf), np.floor(e / leaf)
         ok &= ((f0 >= -DENSE_INDEX_RANGE) & (f0 < DENSE_INDEX_RANGE) & (f1 >= -DENSE_INDEX_RANGE) & (f1 < DENSE_INDEX_RANGE)).all(axis=1)
@@ -108,26 +126,71 @@ def dense_ray_steps(points, origins, leaf, margin_leaves=2.0, max_range=30.0, st
         step = np.sign(i1 - i)
         tmax = ((i + (step > 0)).astype(np.float64) * leaf - o) / (e - o)
         tdelta = leaf / np.abs(e - o)
-    yield ray, i.copy()
+    if info is not None:
+        info.update(ray=ray.copy(), len=length[at].copy(), tt=t[at].copy())
+    t_in = np.zeros(ray.size)
     while True:
-        go = left.sum(axis=1) > 0
-        if not go.any():
-            return
-        if not go.all():
-            ray, i, left, step, tmax, tdelta = ray[go], i[go], left[go], step[go], tmax[go], tdelta[go]
-        # among the axes with steps left the smallest tmax, the earlier axis on a tie
+        # among the axes with steps left the smallest tmax, the earlier axis on a tie; -1: no step is left
         a = np.full(ray.size, -1)
         best = np.zeros(ray.size)
         for ax in range(3):
             take = (left[:, ax] > 0) & ((a < 0) | (tmax[:, ax] < best))
             a = np.where(take, ax, a)
             best = np.where(take, tmax[:, ax], best)
+        if extend is None:
+            yield ray, i.copy()
+        else:
+            yield ray, i.copy(), t_in.copy(), np.where(a >= 0, best, 1.0)
+        go = a >= 0
+        if not go.any():
+            return
+        if not go.all():
+            ray, i, left, step, tmax, tdelta, a, best = ray[go], i[go], left[go], step[go], tmax[go], tdelta[go], a[go], best[go]
         rows = np.arange(ray.size)
         i[rows, a] += step[rows, a]
         with np.errstate(all="ignore"):
             tmax[rows, a] += tdelta[rows, a]
         left[rows, a] -= 1
-        yield ray, i.copy()
+        t_in = best
+
+
+def _dense_cast_check(leaf, max_range, extend, min_frames, compare=False):
+    """ValueError for what DenseMapHost.cast / .compare refuse (the device: LSA_E_ARG)"""
+    if not (np.isfinite(max_range) and max_range > 0 and np.float64(max_range) / np.float64(leaf) <= 4096.0):
+        raise ValueError("max_range finite, positive and at most 4096 leaves")
+    if np.isnan(extend) or (compare and not (np.isfinite(extend) and extend >= 0)):
+        raise ValueError("the tolerance finite and >= 0" if compare else "extend is NaN")
+    if int(min_frames) < 1:
+        raise ValueError("min_frames >= 1")
+
+
+def _scan_targets_numpy(pose, elevations, n_azimuth):
+    T = np.asarray(pose, np.float64).reshape(4, 4)
+    el = np.asarray(elevations, np.float64).reshape(-1)
+    az = 6.283185307179586476925286766559 * np.arange(int(n_azimuth), dtype=np.float64) / np.float64(int(n_azimuth)) if int(n_azimuth) > 0 else np.zeros(0)
+    v = np.stack([np.cos(el)[:, None] * np.cos(az)[None, :], np.cos(el)[:, None] * np.sin(az)[None, :], np.sin(el)[:, None] * np.ones_like(az)[None, :]], axis=-1).reshape(-1, 3)
+    out = np.stack([((T[k, 0] * v[:, 0] + T[k, 1] * v[:, 1]) + T[k, 2] * v[:, 2]) + T[k, 3] for k in range(3)], axis=1)
+    return T[:3, 3].astype(np.float32).reshape(1, 3), out.astype(np.float32)
+
+
+def scan_targets(pose, elevations, n_azimuth):
+    """(origin (1, 3) float32, targets (n_rings * n_azimuth, 3) float32, ring-major) of a spinning sensor at `pose` (4x4): the
+    origin is the pose's translation narrowed to float, target (r, c) the pose applied to (cos el_r cos az_c, cos el_r sin az_c,
+    sin el_r), az_c = 2 pi c / n_azimuth, in double, narrowed to float.  The floats are lsa_scan_targets' (host only), the one
+    place where a sensor model becomes rays; without the built library, the same statement in numpy (whose cos and sin may
+    differ from the C library's in the last bit)."""
+    el = np.ascontiguousarray(elevations, np.float64).reshape(-1)
+    n_azimuth = int(n_azimuth)
+    if n_azimuth < 0:
+        raise ValueError("n_azimuth >= 0")
+    if not os.path.exists(LIB_PATH):
+        return _scan_targets_numpy(pose, el, n_azimuth)
+    T = pose16(pose)
+    origin, targets = np.zeros((1, 3), np.float32), np.zeros((max(el.size * n_azimuth, 1), 3), np.float32)
+    rc = lib().lsa_scan_targets(ptr(T), ptr(el) if el.size else ptr(np.zeros(1)), el.size, n_azimuth, ptr(origin), ptr(targets))
+    if rc != 0:
+        raise _error("lsa_scan_targets", rc, "bad argument")
+    return origin, targets[: el.size * n_azimuth].copy()
 
 
 def dense_index_keys(index):
@@ -448,7 +511,36 @@ class DenseMapHost:
     window = (x_min, y_min, x_max, y_max) the cells of dense_grid_window_cells, whatever the map holds, so that a window's
     answer is the crop of the whole grid's, to the byte.  resolution = cell_leaves * leaf, origin_x = (double)(cx0 *
     cell_leaves) * leaf; cells are row-major, row 0 is cy0, x fastest.  Nothing depends on the order of the voxels; no state
-    changes.  ValueError for what dense_grid_check refuses, OverflowError above max_cells."""
+    changes.  ValueError for what dense_grid_check refuses, OverflowError above max_cells.
+
+    cast(origins, targets, extend, max_range, min_frames, max_miss_ratio, before): what the map holds along a line.  Origin o
+    and target t are float triples widened to double; everything in double, without contraction.  The geometry is carve's with
+    len + extend in place of len - margin: d = t - o, len = sqrt((dx*dx + dy*dy) + dz*dz), reach = len + extend, tt = reach <
+    max_range ? reach : max_range, e = o + d * (tt / len).  extend may be +inf (the ray runs to max_range, the target is only a
+    direction) or negative.  No ray when a coordinate is not finite, tt is not > 0, len is 0, or a start or end index lies
+    outside [-2^20, 2^20).  The walk is carve's, statement for statement (dense_ray_steps).  A visited voxel counts when it
+    exists, frames >= min_frames, for max_miss_ratio >= 0 misses <= max_miss_ratio * frames (get's predicate) and, with `before`
+    given, first_frame < before -- the map without what that ordinal and later ones created.  The first voxel that counts, in
+    visiting order, is the hit and ends the walk.  One dense_hit_dtype record a ray: key (0 unless status 1); entry =
+    (float)(t_in * tt), t_in the tmax of the step that entered the voxel before tdelta was added, 0 for the start voxel; exit =
+    (float)(t_out * tt), t_out the smallest tmax among the axes with steps left when the voxel is visited, 1 when none is left;
+    depth = (float)((((qx-ox)*dx + (qy-oy)*dy) + (qz-oz)*dz) / len) for the kept point q -- which may lie anywhere in its voxel,
+    so depth need not lie between entry and exit; steps = voxels visited (up to and including the hit, the whole walk for a
+    miss, 0 for no ray); source; status -1 no ray, 0 miss, 1 hit.  Everything but steps and status is 0 unless status is 1.
+    Beside the records the hit voxels' LidarPoints, 32 zero bytes otherwise.
+
+    compare(points, origins, tolerance, ...): one uint8 a point, from the ray of its origin to the point with extend =
+    tolerance (finite, >= 0; default one leaf), decided in double before anything is narrowed: NOT_JUDGED 0 no ray, or len >
+    max_range; UNMAPPED 2 no hit -- nothing that counts lies on the ray up to `tolerance` behind the point; THROUGH_MAP 3 a hit
+    with t_out * tt < len - tolerance -- the ray left a voxel that counts more than the tolerance before it reached the point;
+    CONSISTENT 1 every other hit.  And counts (4,) int64, the number of each.  Two limits of a test by voxels: at tolerance 0 a
+    point exactly on a voxel face may end its walk one voxel short, because o + (t - o) need not be t in double; and at grazing
+    incidence the ray meets occupied voxels of the same surface well before the point, so ground far away reads THROUGH_MAP at
+    a small tolerance.  UNMAPPED is the robust label.
+    Neither depends on the order of the rays, and neither changes any state -- no voxel, record, miss, `rays` or last_frame --
+    but cast_rays, the rays the two have cast since the last clear."""
+
+    NOT_JUDGED, CONSISTENT, UNMAPPED, THROUGH_MAP = 0, 1, 2, 3
 
     def __init__(self, leaf):
         if not (leaf > 0 and np.isfinite(leaf)):
@@ -461,6 +553,7 @@ class DenseMapHost:
         self.skipped = 0
         self.dropped = 0
         self.rays = 0
+        self.cast_rays = 0
         self.pruned = 0
         self.last_frame = None
 
@@ -564,6 +657,73 @@ class DenseMapHost:
         dense_grid_check(cell_leaves, ground_radius, min_height, max_height, min_obstacle_voxels, window)
         pts, vox = self.get(min_frames, max_miss_ratio)
         return dense_grid(pts, vox["key"], self.leaf, cell_leaves, ground_radius, min_height, max_height, min_obstacle_voxels, window, max_cells)
+
+    def _walk_to_hits(self, targets, origins, extend, max_range, min_frames, max_miss_ratio, before):
+        """the walks of cast and compare: per ray status, steps, t_in, t_out, key of the hit, len and tt"""
+        tg = np.ascontiguousarray(targets, np.float32).reshape(-1, 3)
+        org = np.ascontiguousarray(origins, np.float32).reshape(-1, 3)
+        n = tg.shape[0]
+        if org.shape[0] != n and org.shape[0] != 1:
+            raise ValueError("one origin, or one per ray")
+        pts = np.zeros(n, POINT_DTYPE)
+        pts["x"], pts["y"], pts["z"] = tg[:, 0], tg[:, 1], tg[:, 2]
+        w = {"status": np.full(n, -1, np.int32), "steps": np.zeros(n, np.int32), "t_in": np.zeros(n), "t_out": np.zeros(n), "key": np.zeros(n, np.uint64),
+             "len": np.zeros(n), "tt": np.zeros(n)}
+        counting = np.array(sorted(k for k, v in self.voxels.items() if self._passes(v, min_frames, max_miss_ratio) and (before is None or v[3] < int(before))), np.uint64)
+        info = {}
+        done = np.zeros(n, bool)
+        for turn, (ray, index, t_in, t_out) in enumerate(dense_ray_steps(pts, org, self.leaf, max_range=max_range, extend=extend, info=info)):
+            if turn == 0:
+                cast = info["ray"]  # the rays that are cast at all
+                w["status"][cast], w["len"][cast], w["tt"][cast] = 0, info["len"], info["tt"]
+                self.cast_rays += int(cast.size)
+            live = ~done[ray]
+            ray, index, t_in, t_out = ray[live], index[live], t_in[live], t_out[live]
+            if ray.size == 0:
+                break  # every ray that was cast has hit
+            w["steps"][ray] += 1
+            if counting.size:
+                keys = dense_index_keys(index)
+                at = np.minimum(np.searchsorted(counting, keys), counting.size - 1)
+                hit = counting[at] == keys
+                r = ray[hit]
+                w["status"][r], w["t_in"][r], w["t_out"][r], w["key"][r] = 1, t_in[hit], t_out[hit], keys[hit]
+                done[r] = True
+        return w, org.astype(np.float64), tg.astype(np.float64)
+
+    def cast(self, origins, targets, extend=0.0, max_range=30.0, min_frames=1, max_miss_ratio=-1.0, before=None):
+        """(hits (n,) dense_hit_dtype, points (n,) LidarPoints) of the rays from origins ((n, 3) or (1, 3) float32) towards targets
+        ((n, 3) float32); see the class"""
+        _dense_cast_check(self.leaf, max_range, extend, min_frames)
+        w, o, t = self._walk_to_hits(targets, origins, extend, max_range, min_frames, max_miss_ratio, before)
+        n = t.shape[0]
+        hits, points = np.zeros(n, dense_hit_dtype), np.zeros(n, POINT_DTYPE)
+        hits["status"], hits["steps"] = w["status"], w["steps"]
+        for r in np.flatnonzero(w["status"] == 1).tolist():
+            v = self.voxels[int(w["key"][r])]
+            ro = o[r if o.shape[0] == n else 0]
+            d = t[r] - ro
+            q = np.array([v[0]["x"], v[0]["y"], v[0]["z"]], np.float64)
+            points[r] = v[0]
+            hits["key"][r] = w["key"][r]
+            hits["entry"][r] = np.float32(w["t_in"][r] * w["tt"][r])
+            hits["exit"][r] = np.float32(w["t_out"][r] * w["tt"][r])
+            hits["depth"][r] = np.float32((((q[0] - ro[0]) * d[0] + (q[1] - ro[1]) * d[1]) + (q[2] - ro[2]) * d[2]) / w["len"][r])
+            hits["source"][r] = v[6]
+        return hits, points
+
+    def compare(self, points, origins, tolerance=None, max_range=30.0, min_frames=1, max_miss_ratio=-1.0, before=None):
+        """(labels (n,) uint8, counts (4,) int64) of LidarPoints against the map, every point from its origin ((n, 3) or (1, 3)
+        float32); tolerance in metres, None: one leaf; see the class"""
+        tolerance = self.leaf if tolerance is None else float(tolerance)
+        _dense_cast_check(self.leaf, max_range, tolerance, min_frames, compare=True)
+        pts = np.ascontiguousarray(points, POINT_DTYPE)
+        targets = np.stack([pts["x"], pts["y"], pts["z"]], axis=1) if pts.size else np.zeros((0, 3), np.float32)
+        w, _, _ = self._walk_to_hits(targets, origins, tolerance, max_range, min_frames, max_miss_ratio, before)
+        through = w["t_out"] * w["tt"] < w["len"] - np.float64(tolerance)
+        labels = np.where(w["status"] == 0, self.UNMAPPED, np.where(through, self.THROUGH_MAP, self.CONSISTENT))
+        labels = np.where((w["status"] < 0) | (w["len"] > np.float64(max_range)), self.NOT_JUDGED, labels).astype(np.uint8)
+        return labels, np.bincount(labels, minlength=4).astype(np.int64)
 
     def prune(self, min_frames=1, max_miss_ratio=-1.0):
         """removes every voxel get(min_frames, max_miss_ratio) leaves out; returns their number (also added to self.pruned)"""
@@ -775,11 +935,59 @@ class DenseMap:
         p = _grid_params(cell_leaves, ground_radius, min_height, max_height, min_obstacle_voxels, min_frames, max_miss_ratio, window)
         return self._check(self.L.lsa_dense_map_save_grid(self.h, C.byref(p), os.fsencode(prefix)), "lsa_dense_map_save_grid")
 
+    def cast(self, origins, targets, extend=0.0, max_range=30.0, min_frames=1, max_miss_ratio=-1.0, before=None):
+        """(hits (n,) dense_hit_dtype, points (n,) LidarPoints) as DenseMapHost.cast states them, walked on the device: rays from
+        origins ((n, 3) or (1, 3) float32) towards targets ((n, 3) float32).  LsaError with .code E_ARG for what the statement
+        refuses; the map is untouched by the call"""
+        tg = np.ascontiguousarray(targets, np.float32).reshape(-1, 3)
+        org = np.ascontiguousarray(origins, np.float32).reshape(-1, 3)
+        n = tg.shape[0]
+        hits, points = np.zeros(max(n, 1), dense_hit_dtype), np.zeros(max(n, 1), POINT_DTYPE)
+        p = _cast_params(extend, max_range, min_frames, max_miss_ratio, before)
+        self._check(self.L.lsa_dense_map_cast(self.h, ptr(org) if org.size else ptr(np.zeros(3, np.float32)), org.shape[0], ptr(tg) if n else ptr(np.zeros(3, np.float32)), n,
+                                              C.byref(p), ptr(hits), ptr(points)), "lsa_dense_map_cast")
+        return hits[:n].copy(), points[:n].copy()
+
+    def compare_points(self, points, origins, tolerance=None, max_range=30.0, min_frames=1, max_miss_ratio=-1.0, before=None):
+        """(labels (n,) uint8, counts (4,) int64) as DenseMapHost.compare states them: world points of the caller's, every one
+        from its origin ((n, 3) or (1, 3) float32); tolerance None: one leaf"""
+        pts = np.ascontiguousarray(points, POINT_DTYPE)
+        org = np.ascontiguousarray(origins, np.float32).reshape(-1, 3)
+        labels, counts = np.zeros(max(pts.size, 1), np.uint8), np.zeros(4, np.int64)
+        p = _cast_params(self.get_param("LeafSize") if tolerance is None else tolerance, max_range, min_frames, max_miss_ratio, before)
+        self._check(self.L.lsa_dense_map_compare_points(self.h, ptr(pts) if pts.size else ptr(np.zeros(1, POINT_DTYPE)), pts.size,
+                                                        ptr(org) if org.size else ptr(np.zeros(3, np.float32)), org.shape[0], C.byref(p), ptr(labels), ptr(counts)),
+                    "lsa_dense_map_compare_points")
+        return labels[:pts.size].copy(), counts
+
+    def compare_frame(self, H0, H1=None, t0=0.0, t1=0.0, time_offset=0.0, tolerance=None, max_range=30.0, min_frames=1, max_miss_ratio=-1.0, before=None):
+        """compare_points of the context's current frame moved as insert_frame moves it, every point from where the sensor stood
+        at its time (frame_origins_at), fused with the walk: nothing of the frame leaves the device but the labels"""
+        interp = H1 is not None
+        cap = max(int(self.L.lsa_frame_size(self.ctx.h)), 1)
+        labels, counts = np.zeros(cap, np.uint8), np.zeros(4, np.int64)
+        p = _cast_params(self.get_param("LeafSize") if tolerance is None else tolerance, max_range, min_frames, max_miss_ratio, before)
+        n = self._check(
+            self.L.lsa_dense_map_compare_frame(self.h, int(interp), ptr(pose16(H0)), ptr(pose16(H1)) if interp else None, float(t0), float(t1), float(time_offset),
+                                               C.byref(p), ptr(labels), cap, ptr(counts)),
+            "lsa_dense_map_compare_frame",
+        )
+        return labels[:n].copy(), counts
+
     def save_pcd(self, path, fmt=PCD_BINARY, min_frames=1, max_miss_ratio=-1.0):
         """the points of get(min_frames, max_miss_ratio) into a PCD file; returns their number (0 and no file for none)"""
         return self._check(
             self.L.lsa_dense_map_save_pcd_filtered(self.h, os.fsencode(path), int(fmt), int(min_frames), float(max_miss_ratio)), "lsa_dense_map_save_pcd_filtered"
         )
+
+
+def _cast_params(extend, max_range, min_frames, max_miss_ratio, before, use_before=None):
+    """the lsa_dense_cast_params_t of a call (the library refuses what is out of range); before None: every voxel"""
+    p = DenseCastParams()
+    p.max_range, p.extend, p.max_miss_ratio = float(max_range), float(extend), float(max_miss_ratio)
+    p.min_frames, p.before = int(min_frames), 0 if before is None else int(before)
+    p.use_before = (0 if before is None else 1) if use_before is None else int(use_before)
+    return p
 
 
 def _viewpoints(viewpoints):
@@ -979,3 +1187,48 @@ def save_dense_map_grid(slam, prefix, cell_leaves=2, ground_radius=2, min_height
     """the states of dense_map_grid into <prefix>.pgm and <prefix>.yaml; returns the number of cells (0 and no files for none)"""
     p = _grid_params(cell_leaves, ground_radius, min_height, max_height, min_obstacle_voxels, min_frames, max_miss_ratio, window)
     return slam._check(slam.L.lsa_slam_save_dense_map_grid(slam.h, C.byref(p), os.fsencode(prefix)), "lsa_slam_save_dense_map_grid")
+
+
+# ---- rays through the pipeline's map (lsa_slam_cast_dense_map_rays, _render_dense_map_scan, _compare_frame_to_dense_map)
+
+
+def dense_map_cast(slam, origins, targets, extend=0.0, max_range=30.0, min_frames=1, max_miss_ratio=-1.0, before=None):
+    """DenseMap.cast of the pipeline's map: (hits, points).  LsaError (.code E_STATE) while "DenseMap" is 0"""
+    tg = np.ascontiguousarray(targets, np.float32).reshape(-1, 3)
+    org = np.ascontiguousarray(origins, np.float32).reshape(-1, 3)
+    n = tg.shape[0]
+    hits, points = np.zeros(max(n, 1), dense_hit_dtype), np.zeros(max(n, 1), POINT_DTYPE)
+    p = _cast_params(extend, max_range, min_frames, max_miss_ratio, before)
+    slam._check(slam.L.lsa_slam_cast_dense_map_rays(slam.h, ptr(org) if org.size else ptr(np.zeros(3, np.float32)), org.shape[0],
+                                                    ptr(tg) if n else ptr(np.zeros(3, np.float32)), n, C.byref(p), ptr(hits), ptr(points)), "lsa_slam_cast_dense_map_rays")
+    return hits[:n].copy(), points[:n].copy()
+
+
+def dense_map_render_scan(slam, elevations, n_azimuth, pose=None, max_range=30.0, min_frames=1, max_miss_ratio=-1.0, before=None):
+    """hits (n_rings, n_azimuth) dense_hit_dtype: the map as a spinning sensor of these ring elevations (radians) would see it
+    from `pose` (4x4; None: where the sensor stands now, Tworld * BaseToLidarOffset) -- DenseMap.cast of scan_targets with
+    extend = +inf, and nothing more.  hits["entry"] is the range image, status != 1 a ray that met nothing within max_range"""
+    el = np.ascontiguousarray(elevations, np.float64).reshape(-1)
+    n = el.size * int(n_azimuth)
+    hits = np.zeros(max(n, 1), dense_hit_dtype)
+    p = _cast_params(np.inf, max_range, min_frames, max_miss_ratio, before)
+    slam._check(slam.L.lsa_slam_render_dense_map_scan(slam.h, ptr(pose16(pose)) if pose is not None else None, ptr(el) if el.size else ptr(np.zeros(1)), el.size, int(n_azimuth),
+                                                      C.byref(p), ptr(hits)), "lsa_slam_render_dense_map_scan")
+    return hits[:n].reshape(el.size, int(n_azimuth)).copy()
+
+
+def dense_map_compare_frame(slam, tolerance=None, max_range=30.0, min_frames=1, max_miss_ratio=-1.0, before="auto"):
+    """(labels uint8, counts (4,) int64): one label per point of slam.registered_frame(), in its order, as DenseMapHost.compare
+    states them against the pipeline's map -- 2 (UNMAPPED) is a point the map does not know: the car that arrived.  tolerance
+    None: one leaf.  before "auto": when the call that brought the current frame was inserted into the map, its ordinal -- the
+    labels are against the map as it stood before this frame --, otherwise every voxel counts; None: every voxel; an ordinal:
+    only voxels first seen before it.  Computed on the device from the frames it still holds; nothing is added to a frame"""
+    cap = max(slam._n, 1 << 19)  # as Slam.registered_frame
+    labels, counts = np.zeros(cap, np.uint8), np.zeros(4, np.int64)
+    auto = isinstance(before, str)
+    if auto and before != "auto":
+        raise ValueError('before is "auto", None or an ordinal')
+    p = _cast_params(float(slam.get_param("DenseMapLeafSize")) if tolerance is None else tolerance, max_range, min_frames, max_miss_ratio, None if auto else before,
+                     use_before=2 if auto else None)
+    n = slam._check(slam.L.lsa_slam_compare_frame_to_dense_map(slam.h, C.byref(p), ptr(labels), cap, ptr(counts)), "lsa_slam_compare_frame_to_dense_map")
+    return labels[:n].copy(), counts

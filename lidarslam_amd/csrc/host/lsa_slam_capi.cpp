@@ -383,6 +383,26 @@ long long lsa_slam_save_dense_map_grid(lsa_slam* s, const lsa_dense_grid_params_
   return s->core.SaveDenseMapGrid(params, prefix);
 }
 
+int lsa_slam_cast_dense_map_rays(lsa_slam* s, const float* origins_xyz, int n_origins, const float* targets_xyz, int n, const lsa_dense_cast_params_t* params,
+                                 lsa_dense_hit_t* hits, lsa_point_t* points)
+{
+  if (!s) return LSA_E_ARG;
+  return s->core.CastDenseMapRays(origins_xyz, n_origins, targets_xyz, n, params, hits, points);
+}
+
+int lsa_slam_render_dense_map_scan(lsa_slam* s, const double* pose16, const double* elevations_rad, int n_rings, int n_azimuth, const lsa_dense_cast_params_t* params,
+                                   lsa_dense_hit_t* hits)
+{
+  if (!s) return LSA_E_ARG;
+  return s->core.RenderDenseMapScan(pose16, elevations_rad, n_rings, n_azimuth, params, hits);
+}
+
+int lsa_slam_compare_frame_to_dense_map(lsa_slam* s, const lsa_dense_cast_params_t* params, uint8_t* labels, int capacity, long long counts[4])
+{
+  if (!s) return LSA_E_ARG;
+  return s->core.CompareFrameToDenseMap(params, labels, capacity, counts);
+}
+
 int lsa_slam_get_registered_frame_origins(lsa_slam* s, float* xyz, int capacity)
 {
   if (!s || (!xyz && capacity > 0)) return LSA_E_ARG;

@@ -337,6 +337,7 @@ int SlamCore::ProcessCurrentFrame(uint64_t stampUs)
   CurrentStamp = stampUs;
   CurrentTime = StampToSec(stampUs);
   HaveFrame = true;
+  DenseLastOrdinal = -1;  // the current frame changes here: it is in the dense map only once InsertDenseFrame has put it there
   {
     Tick t;
     AheadWorker.Wait();  // it reads the previous frame's keypoint buffers, which the extraction is about to rotate (long done)

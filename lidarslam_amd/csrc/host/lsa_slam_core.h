@@ -303,6 +303,14 @@ public:
   // the floor plan: elevation, ground and the occupancy grid, rasterised from the table as it stands
   long long GetDenseMapGrid(const lsa_dense_grid_params_t* params, lsa_dense_grid_info_t* info, lsa_dense_cell_t* cells, int8_t* state, long long capacity);
   long long SaveDenseMapGrid(const lsa_dense_grid_params_t* params, const std::string& prefix);
+  // rays (DESIGN.md 3.14 "Rays"; lsa_dense_cast.hip): questions along a line, answered from the table as it stands; nothing is
+  // added to a frame.  DenseLastOrdinal: the ordinal under which the call that brought the current frame went into the map, -1
+  // when it did not (mode 2 and no keyframe, a refused insertion, a frame that failed or came while "DenseMap" was 0, a cleared
+  // map): reset where the current frame changes (ProcessCurrentFrame); what use_before == 2 of the compare resolves to
+  int DenseLastOrdinal = -1;
+  int CastDenseMapRays(const float* origins, int nOrigins, const float* targets, int n, const lsa_dense_cast_params_t* params, lsa_dense_hit_t* hits, lsa_point_t* points);
+  int RenderDenseMapScan(const double* pose16, const double* elevations, int nRings, int nAzimuth, const lsa_dense_cast_params_t* params, lsa_dense_hit_t* hits);
+  int CompareFrameToDenseMap(const lsa_dense_cast_params_t* params, uint8_t* labels, int capacity, long long counts[4]);
 
   // ---- state ----
   Pose Tworld, PreviousTworld, Trelative;

@@ -98,6 +98,7 @@ int SlamCore::InsertDenseFrame(bool keyframe, double time)
   }
   if (inserted)
   {
+    DenseLastOrdinal = ordinal;
     DenseFrames++;
     DenseTimes.push_back(time);  // 8 B a frame: which logged pose an applied trajectory corrects this ordinal by
     for (int a = 0; a < 3; ++a) DenseViewpoints.push_back(static_cast<float>(view.m[4 * a + 3]));  // 12 B a frame: what the normals are turned towards
@@ -112,6 +113,7 @@ void SlamCore::DropDenseMap(const char* why)
   if (!Dense) return;
   (void)lsa_dense_map_clear(Dense);
   DenseFrames = 0;
+  DenseLastOrdinal = -1;
   DenseTimes.clear();
   DenseViewpoints.clear();
   DenseClears++;
@@ -349,6 +351,122 @@ long long SlamCore::SaveDenseMapGrid(const lsa_dense_grid_params_t* params, cons
   if (const int rc = MakeDenseMap(); rc < 0) return rc;
   const long long n = lsa_dense_map_save_grid(Dense, params, prefix.c_str());
   return n < 0 ? Fail(static_cast<int>(n), "lsa_dense_map_save_grid") : n;
+}
+
+// ---- rays (lsa_dense_cast.hip): each call behind WaitMaps, on a map that is made empty where no frame has reached it yet
+int SlamCore::CastDenseMapRays(const float* origins, int nOrigins, const float* targets, int n, const lsa_dense_cast_params_t* params, lsa_dense_hit_t* hits, lsa_point_t* points)
+{
+  if (const int rc = DenseReady("CastDenseMapRays"); rc < 0) return rc;
+  if (const int rc = MakeDenseMap(); rc < 0) return rc;
+  const int rc = lsa_dense_map_cast(Dense, origins, nOrigins, targets, n, params, hits, points);
+  return rc < 0 ? Fail(rc, "lsa_dense_map_cast") : rc;
+}
+
+// pose16 == nullptr: where the sensor stands now, Tworld * BaseToLidarOffset
+int SlamCore::RenderDenseMapScan(const double* pose16, const double* elevations, int nRings, int nAzimuth, const lsa_dense_cast_params_t* params, lsa_dense_hit_t* hits)
+{
+  if (const int rc = DenseReady("RenderDenseMapScan"); rc < 0) return rc;
+  if (!elevations || !hits || !params || nRings < 0 || nAzimuth < 0 || static_cast<long long>(nRings) * nAzimuth > (1ll << 30))
+  {
+    LastError = "RenderDenseMapScan: bad argument";
+    return LSA_E_ARG;
+  }
+  if (const int rc = MakeDenseMap(); rc < 0) return rc;
+  const Pose view = Tworld * BaseToLidarOffset;
+  const int n = nRings * nAzimuth;
+  float origin[3];
+  std::vector<float> targets(3 * static_cast<size_t>(std::max(n, 1)));
+  if (const int rc = lsa_scan_targets(pose16 ? pose16 : view.m, elevations, nRings, nAzimuth, origin, targets.data()); rc < 0)
+  {
+    LastError = "RenderDenseMapScan: bad argument";
+    return rc;
+  }
+  const int rc = lsa_dense_map_cast(Dense, origin, 1, targets.data(), n, params, hits, nullptr);
+  return rc < 0 ? Fail(rc, "lsa_dense_map_cast") : rc;
+}
+
+// one label per point of GetRegisteredFrame, in its order: every device frame of the last call with its own offset and time
+// shift under the poses InsertDenseFrame and GetRegisteredFrameOrigins use
+int SlamCore::CompareFrameToDenseMap(const lsa_dense_cast_params_t* params, uint8_t* labels, int capacity, long long counts[4])
+{
+  if (const int rc = DenseReady("CompareFrameToDenseMap"); rc < 0) return rc;
+  if (!labels || !counts || capacity < 0) { LastError = "CompareFrameToDenseMap: bad argument"; return LSA_E_ARG; }
+  lsa_dense_cast_params_t p;
+  if (params) p = *params;
+  else
+  {
+    std::memset(&p, 0, sizeof(p));
+    p.max_range = 30.;
+    p.extend = DenseMapLeafSize;  // the tolerance: one leaf
+    p.max_miss_ratio = -1.;
+    p.min_frames = 1;
+    p.use_before = 2;
+  }
+  if (p.use_before == 2)
+  {
+    // automatic: the map as it stood before the call that brought this frame, when that call went into it
+    p.use_before = DenseLastOrdinal >= 0 ? 1 : 0;
+    p.before = DenseLastOrdinal >= 0 ? DenseLastOrdinal : 0;
+  }
+  if (const int rc = MakeDenseMap(); rc < 0) return rc;
+  long long total = 0;
+  if (HaveFrame)
+  {
+    if (!CurrentFrames.empty())
+      for (const HeldFrame& f : CurrentFrames) total += f.n;
+    else
+      total = std::max(lsa_frame_size(Ctx), 0);
+  }
+  if (total > capacity) { LastError = "CompareFrameToDenseMap: the frame has more points than the labels have room for"; return LSA_E_CAPACITY; }
+  long long sum[4] = {0, 0, 0, 0};
+  if (total == 0)
+  {
+    // (no frame: the parameters are still held to their ranges)
+    const float none[3] = {0.f, 0.f, 0.f};
+    lsa_point_t nothing;
+    std::memset(&nothing, 0, sizeof(nothing));
+    const int rc = lsa_dense_map_compare_points(Dense, &nothing, 0, none, 1, &p, labels, sum);
+    if (rc < 0) return Fail(rc, "lsa_dense_map_compare_points");
+    std::memcpy(counts, sum, sizeof(sum));
+    return 0;
+  }
+  auto compare = [&](const Pose& offset, double timeOffset, uint8_t* out, int room) -> int {
+    long long c[4] = {0, 0, 0, 0};
+    int rc;
+    if (Undistortion)
+    {
+      const Pose H0 = (Tworld * Motion.GetH0()) * offset;
+      const Pose H1 = (Tworld * Motion.GetH1()) * offset;
+      rc = lsa_dense_map_compare_frame(Dense, 1, H0.m, H1.m, Motion.Time0, Motion.Time1, timeOffset, &p, out, room, c);
+    }
+    else
+    {
+      const Pose tf = Tworld * offset;
+      rc = lsa_dense_map_compare_frame(Dense, 0, tf.m, nullptr, 0., 0., timeOffset, &p, out, room, c);
+    }
+    if (rc < 0) return Fail(rc, "lsa_dense_map_compare_frame");
+    for (int l = 0; l < 4; ++l) sum[l] += c[l];
+    return rc;
+  };
+  int at = 0;
+  if (!CurrentFrames.empty())
+  {
+    for (const HeldFrame& f : CurrentFrames)
+    {
+      LSA_TRY(lsa_frame_store_use(Ctx, f.slot));
+      const int got = compare(GetBaseToLidarOffset(f.device), f.timeOffset, labels + at, capacity - at);
+      if (got < 0) return got;
+      at += got;
+    }
+  }
+  else
+  {
+    const int got = compare(BaseToLidarOffset, 0., labels, capacity);
+    if (got < 0) return got;
+    at = got;
+  }
+  std::memcpy(counts, sum, sizeof(sum));
+  return at;
 }
 
 int SlamCore::ClearDenseMap()

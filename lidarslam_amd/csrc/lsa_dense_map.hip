@@ -45,6 +45,8 @@
 //   k_dense_grid_rows / _ground   one thread a cell: the smallest code of the neighbourhood, along the row, then along the column
 //   k_dense_grid_band      every kept voxel against the ground of its cell: atomicAdd on a count, atomicMax on the top code
 //   k_dense_grid_classify  one thread a cell: the 20-byte record and the state
+// The slot, the table, its look-ups, the export's predicate and the walk of a ray are in lsa_dense_table.h, shared with
+// lsa_dense_cast.hip (rays that stop at the first voxel that counts: DenseMapHost.cast / .compare).
 #include <cstring>
 #include <rocprim/device/device_radix_sort.hpp>
 #include <chrono>
@@ -55,6 +57,7 @@
 #include <vector>
 #include "lsa_compact.h"
 #include "lsa_ctx.h"
+#include "lsa_dense_table.h"
 #include "lsa_device_grid_io.h"
 #include "lsa_device_math.h"
 #include "lsa_wave.h"
@@ -66,118 +69,10 @@ namespace lsa
 InterpConst make_interp_const(const double H0[16], const double H1[16], double t0, double t1);  // lsa_transform.hip
 }
 using namespace lsa;
+using namespace lsa::dense;  // the slot, the table and its look-ups, the walk of a ray, the map's host object (lsa_dense_table.h)
 
 namespace
 {
-constexpr u64 kOccupied = 1ull << 63;
-constexpr double kIndexRange = 1048576.;  // 2^20: indices in [-2^20, 2^20)
-constexpr unsigned kMinCapacity = 64, kMaxCapacity = 1u << 30;
-constexpr size_t kDefaultMaxBytes = (size_t)16 << 30;
-constexpr double kMaxRangeLeaves = 4096.;  // "CarveRange" / leaf at most
-
-struct alignas(64) Slot
-{
-  u64 key;
-  u64 cand;
-  float4 a, b;  // the LidarPoint: x y z w | time, intensity, laser / device / label
-  unsigned count, frames;
-  int first, last;
-};
-static_assert(sizeof(Slot) == 64, "a slot is one 64-byte record");
-
-struct Table
-{
-  Slot* slots;
-  int* source;    // [capacity] the ordinal of the call whose point the slot holds
-  unsigned* miss; // [2 * capacity] misses, then miss-frame words; null in a map never carved
-  unsigned mask;  // capacity - 1
-  int stress;     // "ProbeStress": every key's home slot is 0
-};
-// device words of a map: [0] occupied slots, [1] error (a probe sequence ran out), [2] points skipped, [3] voxels the
-// re-projection in flight dropped, [4] rays cast
-enum { kStatOccupied = 0, kStatError = 1, kStatSkipped = 2, kStatDropped = 3, kStatRays = 4, kStatWords = 5 };
-
-// the order-preserving code of an intensity: f2ou, and 0 -- below -inf -- for a NaN
-__device__ __forceinline__ unsigned intensity_code(float v) { return v == v ? f2ou(v) : 0u; }
-
-__device__ __forceinline__ bool voxel_key(const float4& a, double leaf, u64& key)
-{
-  if (!(__builtin_isfinite(a.x) && __builtin_isfinite(a.y) && __builtin_isfinite(a.z))) return false;
-  const double ix = __builtin_floor((double)a.x / leaf), iy = __builtin_floor((double)a.y / leaf), iz = __builtin_floor((double)a.z / leaf);
-  if (!(ix >= -kIndexRange && ix < kIndexRange && iy >= -kIndexRange && iy < kIndexRange && iz >= -kIndexRange && iz < kIndexRange)) return false;
-  key = ((u64)((long long)iz + 1048576ll) << 42) | ((u64)((long long)iy + 1048576ll) << 21) | (u64)((long long)ix + 1048576ll);
-  return true;
-}
-
-__device__ __forceinline__ unsigned home_slot(const Table& t, u64 key)
-{
-  if (t.stress) return 0u;
-  key ^= key >> 33; key *= 0xff51afd7ed558ccdull;
-  key ^= key >> 33; key *= 0xc4ceb9fe1a85ec53ull;
-  key ^= key >> 33;
-  return (unsigned)key & t.mask;
-}
-
-// the slot of `key`, claimed when the table does not hold it; -1 after capacity probes (the caller raises the error word)
-__device__ __forceinline__ int find_or_claim(const Table& t, u64 key, u64* __restrict__ stat)
-{
-  const u64 want = key | kOccupied;
-  unsigned s = home_slot(t, key);
-  for (unsigned probe = 0; probe <= t.mask; ++probe, s = (s + 1u) & t.mask)
-  {
-    u64* kp = &t.slots[s].key;
-    u64 cur = __hip_atomic_load(kp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (cur == 0ull)
-    {
-      cur = atomicCAS(kp, 0ull, want);
-      if (cur == 0ull)
-      {
-        atomicAdd(&stat[kStatOccupied], 1ull);
-        return (int)s;
-      }
-    }
-    if (cur == want) return (int)s;
-  }
-  return -1;
-}
-
-// the slot of `key`, -1 when the table does not hold it: read-only, until the key or an empty slot, capacity probes at most
-__device__ __forceinline__ int find(const Table& t, u64 key)
-{
-  const u64 want = key | kOccupied;
-  unsigned s = home_slot(t, key);
-  for (unsigned probe = 0; probe <= t.mask; ++probe, s = (s + 1u) & t.mask)
-  {
-    const u64 cur = __hip_atomic_load(&t.slots[s].key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (cur == want) return (int)s;
-    if (cur == 0ull) return -1;
-  }
-  return -1;
-}
-
-// what the exports hand out and a prune keeps: frames >= min_frames and, for a ratio >= 0, misses <= ratio * frames
-struct Keep
-{
-  const unsigned* miss;  // null: no voxel has a miss
-  unsigned min_frames;
-  double ratio;
-  __device__ bool operator()(const Slot& S, unsigned i) const
-  {
-    if (S.key == 0ull || S.frames < min_frames) return false;
-    if (!(ratio >= 0.)) return true;
-    return (double)(miss ? miss[i] : 0u) <= ratio * (double)S.frames;
-  }
-};
-
-struct FrameMove
-{
-  int fused;        // 0: the points are world points already
-  int interpolate;
-  InterpConst c;
-  Rigid R;
-  double time_offset;
-};
-
 // launch 1: slot, count, candidate
 __global__ __launch_bounds__(256) void k_dense_claim(const float4* __restrict__ in, int n, const FrameMove m, double leaf, Table t, u64* __restrict__ stat,
                                                      int* __restrict__ slot_of)
@@ -319,66 +214,25 @@ __global__ __launch_bounds__(256) void k_dense_carve(const float4* __restrict__ 
   }
   const double o[3] = {(double)ofx, (double)ofy, (double)ofz};
   const double p[3] = {(double)a.x, (double)a.y, (double)a.z};
-  const double d[3] = {p[0] - o[0], p[1] - o[1], p[2] - o[2]};
-  const double len = __builtin_sqrt((d[0] * d[0] + d[1] * d[1]) + d[2] * d[2]);
-  const double reach = len - c.margin;
-  const double tt = reach < c.range ? reach : c.range;
-  bool ok = __builtin_isfinite(o[0]) && __builtin_isfinite(o[1]) && __builtin_isfinite(o[2]) && __builtin_isfinite(p[0]) && __builtin_isfinite(p[1]) &&
-            __builtin_isfinite(p[2]) && tt > 0.;
-  const double scale = tt / len;
-  double e[3], f0[3], f1[3];
-#pragma unroll
-  for (int k = 0; k < 3; ++k)
-  {
-    e[k] = o[k] + d[k] * scale;
-    f0[k] = __builtin_floor(o[k] / c.leaf);
-    f1[k] = __builtin_floor(e[k] / c.leaf);
-    ok = ok && f0[k] >= -kIndexRange && f0[k] < kIndexRange && f1[k] >= -kIndexRange && f1[k] < kIndexRange;
-  }
+  // the set-up and the step of the walk: dense_ray_begin / _next / _step of lsa_dense_table.h, shared with the casts
+  Ray ray;
+  const bool ok = dense_ray_begin(o, p, -c.margin, c.range, c.leaf, c.max_steps, ray);
   const u64 casting = __ballot(ok);
   if (!ok) return;
   // one add a wavefront
   if ((int)(threadIdx.x & 63) == __ffsll((long long)casting) - 1) atomicAdd(&stat[kStatRays], (u64)__popcll(casting));
-  long long i[3], left[3], step[3];
-  double tmax[3], tdelta[3];
-  long long total = 0;
-#pragma unroll
-  for (int k = 0; k < 3; ++k)
-  {
-    i[k] = (long long)f0[k];
-    const long long i1 = (long long)f1[k];
-    left[k] = i1 > i[k] ? i1 - i[k] : i[k] - i1;
-    step[k] = i1 > i[k] ? 1 : (i1 < i[k] ? -1 : 0);
-    tmax[k] = 0.;
-    tdelta[k] = 0.;
-    if (left[k] > 0)
-    {
-      const double span = e[k] - o[k];
-      tmax[k] = ((double)(i[k] + (step[k] > 0 ? 1 : 0)) * c.leaf - o[k]) / span;
-      tdelta[k] = c.leaf / __builtin_fabs(span);
-    }
-    total += left[k];
-  }
-  if (total > c.max_steps) total = c.max_steps;  // (never: the ray is no longer than the range)
   const unsigned word = (unsigned)c.frame ^ 0x80000000u;
   unsigned* __restrict__ words = t.miss + (size_t)t.mask + 1u;
   for (long long k = 0;; ++k)
   {
-    const u64 key = ((u64)(i[2] + 1048576ll) << 42) | ((u64)(i[1] + 1048576ll) << 21) | (u64)(i[0] + 1048576ll);
-    const int s = find(t, key);
+    const int s = find(t, dense_ray_key(ray));
     // (last_frame is final: k_dense_apply of this ordinal ran before this launch)
     if (s >= 0 && t.slots[s].last != c.frame && atomicMax(&words[s], word) < word) atomicAdd(&t.miss[s], 1u);
-    if (k >= total) break;
-    int ax = -1;
-    double best = 0.;
-#pragma unroll
-    for (int q = 0; q < 3; ++q)
-      if (left[q] > 0 && (ax < 0 || tmax[q] < best)) { ax = q; best = tmax[q]; }
+    if (k >= ray.total) break;
+    double best;
+    const int ax = dense_ray_next(ray, best);
     if (ax < 0) break;  // (never: total is the sum of what is left)
-    // (indexed by a run-time axis, written out: no private array leaves the registers)
-    if (ax == 0) { i[0] += step[0]; tmax[0] += tdelta[0]; left[0] -= 1; }
-    else if (ax == 1) { i[1] += step[1]; tmax[1] += tdelta[1]; left[1] -= 1; }
-    else { i[2] += step[2]; tmax[2] += tdelta[2]; left[2] -= 1; }
+    dense_ray_step(ray, ax);
   }
 }
 
@@ -830,67 +684,8 @@ __global__ __launch_bounds__(256) void k_dense_grid_classify(const Grid g, unsig
 
 }  // namespace
 
-struct lsa_dense_map
-{
-  lsa_ctx* ctx = nullptr;
-  hipStream_t stream = nullptr;  // the context's look-ahead stream
-  double leaf = 0.1;
-  Slot* slots = nullptr;
-  int* source = nullptr;  // [capacity], beside the slots
-  unsigned* miss = nullptr;  // [2 * capacity] misses and miss-frame words, from the first carve on
-  unsigned capacity = 0;
-  unsigned initial_capacity = 1u << 16;
-  size_t max_bytes = kDefaultMaxBytes;
-  int stress = 0;
-  u64* stat = nullptr;        // device, kStatWords
-  u64* host_words = nullptr;  // coherent host memory, 4 words
-  int* slot_of = nullptr;     // [slot_cap] the slot of every point of the call in flight
-  int slot_cap = 0;
-  lsa_point_t* staged = nullptr;  // lsa_dense_map_insert_points: the caller's points on the device
-  int staged_cap = 0;
-  hipEvent_t ev_frame = nullptr;  // the context's stream up to the frame the fused insertion reads
-  // the host's bound of the occupied slots: the last count the device published plus the points inserted since
-  unsigned next_serial = 1, epoch = 1, seen_serial = 0;
-  unsigned known = 0;
-  std::deque<std::pair<unsigned, int>> pending;
-  long long pending_sum = 0;
-  int last_frame = INT32_MIN;
-  int rehashes = 0;
-  // export scratch, kept between exports
-  int* chunks = nullptr; int chunks_cap = 0;
-  int* totals = nullptr;  // device, 2 ints: the total and the compaction's aside slot
-  u64* keys[2] = {nullptr, nullptr}; unsigned* index[2] = {nullptr, nullptr}; int keys_cap = 0;
-  void* sort_tmp = nullptr; size_t sort_tmp_cap = 0;
-  lsa_point_t* out_pts = nullptr; lsa_dense_voxel_t* out_vox = nullptr; int* out_src = nullptr; unsigned* out_miss = nullptr; int out_cap = 0;
-  double export_seconds = 0.;
-  // re-projections (lsa_dense_map_reproject)
-  int reprojections = 0;
-  long long dropped = 0;  // voxels, since the last clear
-  double reproject_seconds = 0.;
-  // free space (lsa_dense_map_carve_*, lsa_dense_map_prune)
-  double carve_margin_leaves = 2., carve_range = 30.;
-  int carve_stride = 1;
-  float* staged_origins = nullptr;  // lsa_dense_map_carve_points: the caller's origins on the device
-  int staged_origins_cap = 0;
-  double carve_seconds = 0.;  // the host's, of the last carve call: what enqueueing it cost
-  long long pruned = 0;       // voxels, since the last clear
-  int prunes = 0;
-  // normals (lsa_dense_map_get_normals): the call's viewpoints and records on the device
-  float* viewpoints = nullptr; int viewpoints_cap = 0;
-  unsigned* out_normals = nullptr; int out_normals_cap = 0;  // 5 words a record
-  double* normal_sums = nullptr; int normal_sums_cap = 0;    // 9 a voxel, between the two launches
-  double normals_seconds = 0.;
-  // the floor plan (lsa_dense_map_get_grid): the rasters, records and states of the last call, kept for the next
-  long long grid_max_cells = 1ll << 24;
-  unsigned char* grid_scratch = nullptr; size_t grid_scratch_cap = 0;
-  int* grid_box = nullptr;  // device, 4 ints
-  double grid_seconds = 0.;
-};
-
 namespace
 {
-Table table_of(const lsa_dense_map* dm) { return Table{dm->slots, dm->source, dm->miss, dm->capacity - 1u, dm->stress}; }
-
 long long occupied_bound(lsa_dense_map* dm)
 {
   const u64 w = __atomic_load_n(&dm->host_words[0], __ATOMIC_ACQUIRE);
@@ -1068,8 +863,10 @@ int carve_device_points(lsa_dense_map* dm, const lsa_point_t* src, int n, const 
   return LSA_OK;
 }
 
+}  // namespace
+
 // waits for the insertions in flight; a probe sequence that ran out is reported here
-int settle(lsa_dense_map* dm, const char* who)
+int lsa::dense::settle(lsa_dense_map* dm, const char* who)
 {
   lsa_ctx* ctx = dm->ctx;
   LSA_HIP(ctx, hipSetDevice(ctx->device));
@@ -1079,6 +876,10 @@ int settle(lsa_dense_map* dm, const char* who)
   return LSA_OK;
 }
 
+double lsa::dense::now_seconds() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+
+namespace
+{
 Keep keep_of(const lsa_dense_map* dm, int min_frames, double max_miss_ratio) { return Keep{dm->miss, (unsigned)std::max(min_frames, 0), max_miss_ratio}; }
 
 // keys and slot indices of the voxels that pass, in slot order, left in dm->keys[0] / index[0]; returns their number.  The
@@ -1336,7 +1137,6 @@ long long grid_raster(lsa_dense_map* dm, const lsa_dense_grid_params_t* p, lsa_d
   return cells;
 }
 
-double now_seconds() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 }  // namespace
 
 extern "C" {
@@ -1376,7 +1176,7 @@ void lsa_dense_map_destroy(lsa_dense_map* dm)
   auto fr = [](void* p) { if (p) (void)hipFree(p); };
   fr(dm->slots); fr(dm->source); fr(dm->miss); fr(dm->staged_origins); fr(dm->out_miss); fr(dm->stat); fr(dm->slot_of); fr(dm->staged); fr(dm->chunks); fr(dm->totals);
   for (int b = 0; b < 2; ++b) { fr(dm->keys[b]); fr(dm->index[b]); }
-  fr(dm->grid_scratch); fr(dm->grid_box);
+  fr(dm->grid_scratch); fr(dm->grid_box); fr(dm->cast_scratch);
   fr(dm->viewpoints); fr(dm->out_normals); fr(dm->normal_sums); fr(dm->sort_tmp); fr(dm->out_pts); fr(dm->out_vox); fr(dm->out_src);
   if (dm->host_words) (void)hipHostFree(dm->host_words);
   if (dm->ev_frame) (void)hipEventDestroy(dm->ev_frame);
@@ -1472,6 +1272,15 @@ double lsa_dense_map_get_param(lsa_dense_map* dm, const char* name)
     u64 rays = 0;
     if (settle(dm, "lsa_dense_map_get_param") != LSA_OK) return -1.;
     if (hipMemcpy(&rays, dm->stat + kStatRays, sizeof(u64), hipMemcpyDeviceToHost) != hipSuccess) return -1.;
+    return (double)rays;
+  }
+  if (n == "CastSeconds") return dm->cast_seconds;
+  if (n == "CastRays")
+  {
+    // the rays of lsa_dense_map_cast and _compare_* since the last clear (lsa_dense_cast.hip): a word of their own, not "Rays"
+    u64 rays = 0;
+    if (settle(dm, "lsa_dense_map_get_param") != LSA_OK) return -1.;
+    if (hipMemcpy(&rays, dm->stat + kStatCastRays, sizeof(u64), hipMemcpyDeviceToHost) != hipSuccess) return -1.;
     return (double)rays;
   }
   return -1.;

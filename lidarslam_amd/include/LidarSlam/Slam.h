@@ -26,6 +26,7 @@
 #include <cstdio>
 #include <cstdint>
 #include <cstring>
+#include <limits>
 #include <map>
 #include <memory>
 #include <set>
@@ -987,6 +988,90 @@ public:
     int n = lsa_slam_get_registered_frame_origins(this->Handle, out.data(), static_cast<int>(out.size() / 3));
     out.resize(3 * static_cast<std::size_t>(std::max(n, 0)));
     this->LastError = n < 0 ? std::string("GetRegisteredFrameOrigins: ") + lsa_slam_last_error(this->Handle) : std::string();
+    return out;
+  }
+  // Rays: what the dense map holds along a line, answered on the device from the table as it stands (nothing is added to a
+  // frame, nothing in the map changes).  A ray runs from an origin towards a target and `extend` metres past it (+inf: to
+  // maxRange, the target only a direction), and stops at the first voxel that counts: seen in minFrames frames, misses <=
+  // maxMissRatio * frames for a ratio >= 0, and -- useBefore 1 -- first seen before the ordinal `before`.  A DenseHit: status
+  // (-1 no ray, 0 miss, 1 hit), the metres along the ray at which it enters and leaves the hit voxel, the voxel's kept point
+  // projected on the ray (depth), the voxels visited, the voxel's key and source ordinal.
+  struct DenseCastParams
+  {
+    double maxRange = 30., extend = 0., maxMissRatio = -1.;
+    int minFrames = 1, useBefore = 0, before = 0;
+    DenseCastParams() {}
+  };
+  struct DenseHit
+  {
+    std::uint64_t key;
+    float entry, exit, depth;
+    std::int32_t steps, source, status;
+  };
+  static lsa_dense_cast_params_t CastParams(const DenseCastParams& params)
+  {
+    lsa_dense_cast_params_t p;
+    std::memset(&p, 0, sizeof(p));
+    p.max_range = params.maxRange; p.extend = params.extend; p.max_miss_ratio = params.maxMissRatio;
+    p.min_frames = params.minFrames; p.use_before = params.useBefore; p.before = params.before;
+    return p;
+  }
+  // origins: xyz of one origin for all rays, or of one per ray; targets: xyz per ray
+  std::vector<DenseHit> CastDenseMapRays(const std::vector<float>& origins, const std::vector<float>& targets, const DenseCastParams& params = DenseCastParams())
+  {
+    static_assert(sizeof(DenseHit) == sizeof(lsa_dense_hit_t), "DenseHit is lsa_dense_hit_t");
+    const lsa_dense_cast_params_t p = CastParams(params);
+    const int n = static_cast<int>(targets.size() / 3);
+    std::vector<DenseHit> out(static_cast<std::size_t>(n));
+    DenseHit none;
+    const int rc = lsa_slam_cast_dense_map_rays(this->Handle, origins.data(), static_cast<int>(origins.size() / 3), targets.data(), n, &p,
+                                                reinterpret_cast<lsa_dense_hit_t*>(n ? out.data() : &none), nullptr);
+    if (rc < 0) out.clear();
+    this->LastError = rc < 0 ? std::string("CastDenseMapRays: ") + lsa_slam_last_error(this->Handle) : std::string();
+    return out;
+  }
+  // a scan of the map as a spinning sensor of these ring elevations (radians) and nAzimuth columns would see it from the current
+  // pose (or from `pose`, row-major 4x4): ring-major, column c at azimuth 2 pi c / nAzimuth; every ray runs to maxRange
+  std::vector<DenseHit> RenderDenseMapScan(const std::vector<double>& elevations, int nAzimuth, DenseCastParams params = DenseCastParams(), const double* pose = nullptr)
+  {
+    params.extend = std::numeric_limits<double>::infinity();
+    const lsa_dense_cast_params_t p = CastParams(params);
+    const std::size_t n = elevations.size() * static_cast<std::size_t>(std::max(nAzimuth, 0));
+    std::vector<DenseHit> out(std::max<std::size_t>(n, 1));
+    const int rc = lsa_slam_render_dense_map_scan(this->Handle, pose, elevations.data(), static_cast<int>(elevations.size()), nAzimuth, &p,
+                                                  reinterpret_cast<lsa_dense_hit_t*>(out.data()));
+    out.resize(rc < 0 ? 0 : n);
+    this->LastError = rc < 0 ? std::string("RenderDenseMapScan: ") + lsa_slam_last_error(this->Handle) : std::string();
+    return out;
+  }
+  // The current frame against the map: one label per point of GetRegisteredFrame(), in its order, from the ray of the point
+  // (from where the sensor stood when it measured it) walked to `tolerance` metres behind the point (negative: one leaf):
+  // DENSE_UNMAPPED nothing that counts lies on the ray -- the point is new to the map: the car that arrived --,
+  // DENSE_CONSISTENT the ray meets the map at the point, DENSE_THROUGH_MAP it left a voxel that counts more than the tolerance
+  // before the point, DENSE_NOT_JUDGED no ray or a point beyond maxRange.  automatic (the default): when this frame is in the
+  // map itself, the map as it stood before it.  Two limits of a test by voxels: at tolerance 0 a point exactly on a voxel face
+  // may end its walk one voxel short, and at grazing incidence far ground reads THROUGH_MAP at a small tolerance; UNMAPPED is
+  // the robust label.  counts: the number of each label.
+  enum DenseLabel : std::uint8_t { DENSE_NOT_JUDGED = 0, DENSE_CONSISTENT = 1, DENSE_UNMAPPED = 2, DENSE_THROUGH_MAP = 3 };
+  std::vector<std::uint8_t> CompareFrameToDenseMap(long long counts[4] = nullptr, double tolerance = -1., DenseCastParams params = DenseCastParams(), bool automatic = true)
+  {
+    params.extend = tolerance < 0. ? this->GetDenseMapLeafSize() : tolerance;
+    lsa_dense_cast_params_t p = CastParams(params);
+    if (automatic) p.use_before = 2;
+    std::vector<std::uint8_t> out(static_cast<std::size_t>(1) << 19);
+    long long c[4] = {0, 0, 0, 0};
+    int n = lsa_slam_compare_frame_to_dense_map(this->Handle, &p, out.data(), static_cast<int>(out.size()), c);
+    // a frame of more points than that (several device frames in one AddFrames call): the call refuses before it touches
+    // anything, and is asked again with more room
+    while (n == LSA_E_CAPACITY && out.size() < (static_cast<std::size_t>(1) << 28))
+    {
+      out.resize(out.size() * 4);
+      n = lsa_slam_compare_frame_to_dense_map(this->Handle, &p, out.data(), static_cast<int>(out.size()), c);
+    }
+    out.resize(static_cast<std::size_t>(std::max(n, 0)));
+    if (counts)
+      for (int l = 0; l < 4; ++l) counts[l] = n < 0 ? 0 : c[l];
+    this->LastError = n < 0 ? std::string("CompareFrameToDenseMap: ") + lsa_slam_last_error(this->Handle) : std::string();
     return out;
   }
 

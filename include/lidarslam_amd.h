@@ -1170,7 +1170,7 @@ int lsa_device_grid_save_pcd(lsa_device_grid* g, const char* path, int format, i
 int lsa_pcd_io_times(const lsa_ctx* ctx, double out[8]);
 
 /* ------------------------------------------------------------------------- */
-/* The dense point-cloud map: registered frames voxel-hashed on the device (lsa_dense_map.hip).  The keypoint
+/* The dense point-cloud map: registered frames voxel-hashed on the device (lsa_dense_*.hip).  The keypoint
  * maps above are the ICP's target; this is the point cloud of the place, one LidarPoint per voxel of `leaf` metres, built
  * from whole registered frames without any of them leaving the device.  The host statement it is held to byte for byte is
  * DenseMapHost (lidarslam_amd/_dense_map.py):
@@ -1263,7 +1263,7 @@ int lsa_dense_map_reserve(lsa_dense_map* dm, long long n); /* room for n more po
 int lsa_dense_map_size(lsa_dense_map* dm);
 long long lsa_dense_map_skipped(lsa_dense_map* dm);
 long long lsa_dense_map_bytes(const lsa_dense_map* dm);
-int lsa_dense_map_get(lsa_dense_map* dm, int min_frames, lsa_point_t* pts, lsa_dense_voxel_t* voxels, int capacity);
+int lsa_dense_map_get(lsa_dense_map* dm, int min_frames, lsa_point_t* pts, lsa_dense_voxel_t* voxels, int capacity); /* every export: LSA_E_CAPACITY without device memory for its scratch (keys, sort, columns) */
 int lsa_dense_map_get_sources(lsa_dense_map* dm, int min_frames, int32_t* out, int capacity);
 int lsa_dense_map_reproject(lsa_dense_map* dm, const double* corrections16, int first_frame, int n, long long* dropped);
 int lsa_pose_corrections(const double* old16, const double* new16, int n, double* out16);

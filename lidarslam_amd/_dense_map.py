@@ -1,6 +1,6 @@
 """The dense point-cloud map: registered frames voxel-hashed on the device (lsa_dense_map_*, lsa_slam_*dense_map*).
 
-DenseMapHost is the numpy statement of what the map computes; the device table (lidarslam_amd/csrc/lsa_dense_map.hip) is
+DenseMapHost is the numpy statement of what the map computes; the device table (lidarslam_amd/csrc/lsa_dense_*.hip) is
 held to it byte for byte, on points, voxel records, sources and misses (free-space carving: DenseMapHost.carve) and on the
 normals computed from the table (DenseMapHost.normals, dense_normals) and on the floor plan rasterised from it
 (DenseMapHost.grid, dense_grid: elevation, ground, and a 2-D occupancy grid of occupied / free / unknown cells).  DenseMap is

@@ -267,7 +267,7 @@ public:
   int GetMap(int k, bool clean, std::vector<lsa_point_t>& out);
   int GetTargetSubMap(int k, std::vector<lsa_point_t>& out);
 
-  // ---- the dense point-cloud map (lsa_slam_dense.cpp; lsa_dense_map.hip) ----
+  // ---- the dense point-cloud map (lsa_slam_dense.cpp; lsa_dense_*.hip) ----
   // "DenseMap": 0 off (nothing whatever changes), 1 every registered frame, 2 keyframes only.  The frame or frames of an
   // AddFrame(s) call go into a voxel hash table on the device at its end, under the poses GetRegisteredFrame would use, all
   // with one ordinal: the count of inserted calls.  Cleared by Reset, ClearMaps and every applied trajectory (the points

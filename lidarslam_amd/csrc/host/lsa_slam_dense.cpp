@@ -1,4 +1,4 @@
-// lsa_slam_dense.cpp -- see lsa_slam_core.h: the pipeline's dense point-cloud map (lsa_dense_map.hip).  The
+// lsa_slam_dense.cpp -- see lsa_slam_core.h: the pipeline's dense point-cloud map (lsa_dense_*.hip).  The
 // registered frame goes into the table at the end of AddFrame without leaving the device; what moves the poses under the
 // points that are already in it clears it -- or, under "DenseMapOnTrajectory" 1 and for an applied trajectory alone,
 // re-projects it: every voxel's point moved by the correction of the frame that measured it.  Under "DenseMapCarve" 1 the rays

@@ -13,7 +13,7 @@
 //   keypoint log AoS lsa_point_t in chunks of 32 MiB, a frame's three types one after the other (lsa_kplog.hip; only with logging on)
 //   descriptors  a ring of slots of rings * sectors + sectors floats, one per logged frame (lsa_place.hip; only once asked for)
 //   pose graph   poses, edges, per-edge block records, block rows D / L / U, the cyclic reduction's levels, PCG vectors (lsa_pose_graph.hip; only once asked for)
-//   dense map    a voxel hash table of 64-byte slots, owned by an lsa_dense_map of the context (lsa_dense_map.hip; only with "DenseMap" on)
+//   dense map    a voxel hash table of 64-byte slots, owned by an lsa_dense_map of the context (lsa_dense_*.hip; only with "DenseMap" on)
 #pragma once
 #include <hip/hip_runtime.h>
 #include <algorithm>
@@ -350,7 +350,7 @@ struct lsa_ctx
   bool map_describe_cull = true;                // lsa_debug_set "map_describe_cull": slices out of a viewpoint's reach are passed over
   // the pose-graph solver's buffers (lsa_pose_graph.hip): made by the first call, grown through the graveyard
   lsa::PgoBuffers* pgo = nullptr;
-  // the dense map's fused insertion (lsa_dense_map.hip) reads a frame's device buffer on the look-ahead stream: ev_dense is
+  // the dense map's fused calls (hold_frame / release_frame of lsa_dense_table.h) read a frame's device buffer on the look-ahead stream: ev_dense is
   // recorded behind the last of them, and whoever writes a frame buffer next waits for it on its stream (frame_writer_guard)
   hipEvent_t ev_dense = nullptr;     // made with the context's first dense map
   bool dense_frame_pending = false;  // a fused insertion has been enqueued (never: nothing is waited for)

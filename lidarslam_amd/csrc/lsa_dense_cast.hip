@@ -15,18 +15,12 @@
 // have neighbouring rays).  The walk's state is the carve's (three axes of index, steps left, direction, tmax, tdelta, all in
 // registers: the run-time axis of a step is written out, never an index into a private array) and two doubles more.
 #include <cmath>
-#include <cstdint>
 #include <cstring>
 #include <limits>
 #include <string>
 #include <vector>
-#include "lsa_ctx.h"
 #include "lsa_dense_table.h"
 
-namespace lsa
-{
-InterpConst make_interp_const(const double H0[16], const double H1[16], double t0, double t1);  // lsa_transform.hip
-}
 using namespace lsa;
 using namespace lsa::dense;
 
@@ -38,7 +32,7 @@ struct Cast
   int n_origins;         // 1 or n
   int n;
   double leaf, extend, range;
-  long long max_steps;  // 3 * (ceil(range / leaf) + 2): no ray has more, whatever it is given
+  long long max_steps;  // ray_max_steps
   Keep keep;            // frames >= min_frames, misses <= ratio * frames
   int use_before, before;
 };
@@ -88,13 +82,6 @@ __device__ __forceinline__ Walked walk_to_hit(const Cast& c, const Table& t, Ray
     dense_ray_step(ray, ax);
     t_in = best;
   }
-}
-
-// one add a wavefront for the lanes with `mine`; every lane of the wavefront that has not returned calls it
-__device__ __forceinline__ void add_once_a_wavefront(u64* word, bool mine)
-{
-  const u64 those = __ballot(mine);
-  if (mine && (int)(threadIdx.x & 63) == __ffsll((long long)those) - 1) atomicAdd(word, (u64)__popcll(those));
 }
 
 __global__ __launch_bounds__(256) void k_dense_cast(const float* __restrict__ targets, const Cast c, Table t, u64* __restrict__ stat, Hit* __restrict__ hits,
@@ -208,8 +195,8 @@ Cast cast_of(const lsa_dense_map* dm, const lsa_dense_cast_params_t* p, int n, c
   c.leaf = dm->leaf;
   c.extend = p->extend;
   c.range = p->max_range;
-  c.max_steps = 3ll * ((long long)std::ceil(p->max_range / dm->leaf) + 2ll);
-  c.keep = Keep{dm->miss, (unsigned)p->min_frames, p->max_miss_ratio};
+  c.max_steps = ray_max_steps(p->max_range, dm->leaf);
+  c.keep = keep_of(dm, p->min_frames, p->max_miss_ratio);  // (min_frames >= 1: check_params)
   c.use_before = p->use_before;
   c.before = p->before;
   return c;
@@ -218,20 +205,7 @@ Cast cast_of(const lsa_dense_map* dm, const lsa_dense_cast_params_t* p, int n, c
 // `bytes` of device scratch for one call; LSA_E_CAPACITY without memory
 int cast_room(lsa_dense_map* dm, size_t bytes, const char* who)
 {
-  lsa_ctx* ctx = dm->ctx;
-  if (bytes <= dm->cast_scratch_cap) return LSA_OK;
-  retire_dev(ctx, dm->cast_scratch);
-  dm->cast_scratch = nullptr;
-  dm->cast_scratch_cap = 0;
-  const size_t want = bytes + bytes / 2;
-  if (hipMalloc((void**)&dm->cast_scratch, want) != hipSuccess)
-  {
-    (void)hipGetLastError();
-    dm->cast_scratch = nullptr;
-    return ctx->fail(LSA_E_CAPACITY, std::string(who) + ": no device memory for " + std::to_string(want) + " bytes of rays; ask for fewer in one call");
-  }
-  dm->cast_scratch_cap = want;
-  return LSA_OK;
+  return room(dm, {{(void**)&dm->cast_scratch, 1}}, &dm->cast_scratch_cap, bytes, 2, who, "rays", "; ask for fewer in one call");
 }
 
 constexpr size_t up16(size_t v) { return (v + 15) & ~(size_t)15; }
@@ -252,8 +226,7 @@ int compare_device_points(lsa_dense_map* dm, const lsa_point_t* src, int n, cons
   LSA_HIP(ctx, hipGetLastError());
   if (m.fused)
   {
-    LSA_HIP(ctx, hipEventRecord(ctx->ev_dense, dm->stream));
-    ctx->dense_frame_pending = true;
+    if (const int rc = release_frame(dm)) return rc;
   }
   u64 words[4] = {0, 0, 0, 0};
   std::vector<uint8_t> got((size_t)n);  // the caller's labels stay untouched unless everything arrives
@@ -350,16 +323,10 @@ int lsa_dense_map_compare_frame(lsa_dense_map* dm, int interpolate, const double
   if (rc) return rc;
   rc = cast_room(dm, (size_t)n, who);
   if (rc) return rc;
-  FrameMove m{};
-  m.fused = 1;
-  m.interpolate = interpolate ? 1 : 0;
-  row_major_to_rt(H0, m.R.R, m.R.t);
-  if (interpolate) m.c = make_interp_const(H0, H1, t0, t1);
-  m.time_offset = time_offset;
-  // as the fused carve: the frame as the context's stream has left it, held by an event its next writer waits for
-  LSA_HIP(ctx, hipEventRecord(dm->ev_frame, ctx->stream));
-  LSA_HIP(ctx, hipStreamWaitEvent(dm->stream, dm->ev_frame, 0));
-  rc = compare_device_points(dm, ctx->frame, n, m, cast_of(dm, params, n, nullptr, 0), dm->cast_scratch, labels, counts);
+  // as the fused carve
+  rc = hold_frame(dm);
+  if (rc) return rc;
+  rc = compare_device_points(dm, ctx->frame, n, frame_move(interpolate, H0, H1, t0, t1, time_offset), cast_of(dm, params, n, nullptr, 0), dm->cast_scratch, labels, counts);
   if (rc) return rc;
   dm->cast_seconds = now_seconds() - started;
   return n;

@@ -290,7 +290,7 @@ static int save_pcd(lsa_device_grid* g, const char* path, int format, int clean)
 }  // extern "C"
 
 // n LidarPoints on the device (what kernels on `gs` left) into a PCD file: the part of a save that comes behind the collection,
-// for the keypoint maps above and the dense map (lsa_dense_map.hip).  The caller has checked path and format and set T[4].
+// for the keypoint maps above and the dense map (lsa_dense_export.hip, lsa_dense_normals.hip).  The caller has checked path and format and set T[4].
 // normals4 (host, may be null): n x 4 floats the writer puts behind every point -- interleaved on the host, the path is not hot.
 int lsa::pcd_save_device_points(lsa_ctx* ctx, hipStream_t gs, const lsa_point_t* pts, int n, const char* path, int format, const float* normals4)
 {

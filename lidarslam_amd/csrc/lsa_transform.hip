@@ -61,7 +61,7 @@ __global__ __launch_bounds__(256) void k_transform_out(const float4* __restrict_
 }
 
 // where the sensor stood when it measured each point: the frame's own origin under the point's pose, float xyz -- the
-// origins of the dense map's fused carve (lsa_dense_map.hip), by the same statement
+// origins of the dense map's fused carve (lsa_dense_carve.hip), by the same statement
 __global__ __launch_bounds__(256) void k_frame_origins(const float4* __restrict__ in, int n, int interpolate, InterpConst c, Rigid R, double time_offset,
                                                        float* __restrict__ out)
 {

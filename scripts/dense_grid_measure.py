@@ -64,7 +64,7 @@ def timed(call):
 
 
 def named_bytes(capacity, voxels, info, radius=2, bounds=True):
-    """the bytes each launch names, as the ProfScopes of lsa_dense_map.hip state them"""
+    """the bytes each launch names, as the ProfScopes of lsa_dense_grid.hip state them"""
     w, h = int(info["width"]), int(info["height"])
     ew, eh, n = w + 2 * radius, h + 2 * radius, w * h
     out = dict(columns=capacity * 64 + voxels * 4, rows_and_ground=(eh * ew + 2 * eh * w + n) * 4, band=capacity * 64 + voxels * 12, classify=n * 41, download=n * 21)

@@ -1,5 +1,5 @@
 """Cases for the dense map's free-space carving (lidarslam_amd/_dense_map.py: DenseMapHost.carve, dense_ray_steps;
-lidarslam_amd/csrc/lsa_dense_map.hip: k_dense_carve).  Needs neither a GPU nor the native library.
+lidarslam_amd/csrc/lsa_dense_carve.hip: k_dense_carve).  Needs neither a GPU nor the native library.
 
 As in tests/dense_map_cases.py the leaf is 0.5 and most coordinates are multiples of 0.125, so that rays start and end on voxel
 corners, edges and faces on purpose.  A ray case is (origin, point, keyword arguments of carve); `walk` is the list of voxels

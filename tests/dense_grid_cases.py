@@ -1,5 +1,5 @@
 """Cases for the dense map's floor plan (lidarslam_amd/_dense_map.py: DenseMapHost.grid, dense_grid;
-lidarslam_amd/csrc/lsa_dense_map.hip: k_dense_grid_*).  Needs neither a GPU nor the native library.
+lidarslam_amd/csrc/lsa_dense_grid.hip: k_dense_grid_*).  Needs neither a GPU nor the native library.
 
 A case is (leaf, steps, queries, device parameters): `steps` build the map as in tests/dense_normals_cases.py and every query
 is a dict of keyword arguments of grid().  The host tests (tests/test_dense_grid_host.py) assert, by hand, what the definition

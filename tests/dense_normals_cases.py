@@ -1,5 +1,5 @@
 """Cases for the dense map's normals (lidarslam_amd/_dense_map.py: DenseMapHost.normals, dense_normals;
-lidarslam_amd/csrc/lsa_dense_map.hip: k_dense_normals).  Needs neither a GPU nor the native library.
+lidarslam_amd/csrc/lsa_dense_normals.hip: k_dense_normals).  Needs neither a GPU nor the native library.
 
 A case is (leaf, steps, queries, device parameters): `steps` build the map -- ("insert", points, frame) and ("carve", points,
 origins, frame), every carve with margin 0 --, and every query is a dict of keyword arguments of normals().  The host tests

@@ -1,5 +1,5 @@
 """Cases for the dense map's re-projection under a corrected trajectory (DenseMapHost.reproject in lidarslam_amd/_dense_map.py;
-lsa_dense_map_reproject in lidarslam_amd/csrc/lsa_dense_map.hip).  Needs neither a GPU nor the native library.
+lsa_dense_map_reproject in lidarslam_amd/csrc/lsa_dense_reproject.hip).  Needs neither a GPU nor the native library.
 
 As in tests/dense_map_cases.py every coordinate is a multiple of 0.125 and the leaf is 0.5; the translations are multiples of
 0.125 too, so that wherever a case must be exact it is exact: a moved coordinate is the sum of two such numbers, and every

@@ -1,4 +1,4 @@
-"""Free-space carving of the dense map on the device (lidarslam_amd/csrc/lsa_dense_map.hip: k_dense_carve, the filtered
+"""Free-space carving of the dense map on the device (lidarslam_amd/csrc/lsa_dense_carve.hip: k_dense_carve, the filtered
 exports, lsa_dense_map_prune) against DenseMapHost, byte for byte on points, voxel records, sources and misses, and on the
 count of rays: the walk's cases, wavefront edges, the scene, long probe sequences, growth, re-projection, the fused frame
 path, the pipeline, files, refusals.  Cases: tests/dense_carve_cases.py."""

@@ -1,4 +1,4 @@
-"""The dense map's floor plan on the device (lidarslam_amd/csrc/lsa_dense_map.hip: k_dense_grid_*) against the host statement
+"""The dense map's floor plan on the device (lidarslam_amd/csrc/lsa_dense_grid.hip: k_dense_grid_*) against the host statement
 (DenseMapHost.grid), on the bytes of the info, of all 20 of every record with its NaNs and of every state: the cases and
 queries of tests/dense_grid_cases.py, long probe sequences and the smallest table, the map after growth, re-projection,
 carving, pruning and a clear, repeated calls, the capacity rule, the cell cap, the pipeline, the files."""

@@ -1,4 +1,4 @@
-"""The dense map's normals on the device (lidarslam_amd/csrc/lsa_dense_map.hip: k_dense_normals) against the host statement
+"""The dense map's normals on the device (lidarslam_amd/csrc/lsa_dense_normals.hip: k_dense_normals) against the host statement
 (DenseMapHost.normals with the oracle's eigen33 as the eigen step), on the bytes of all 20 of every record, the NaN of "no
 normal" included: the cases of tests/dense_normals_cases.py, group and wavefront edges, long probe sequences, the smallest
 table, the map after growth, re-projection, carving, pruning and a clear, refusals, the pipeline, files."""

@@ -1,5 +1,5 @@
-"""The dense map's re-projection on the device (lsa_dense_map_reproject, lsa_dense_map_get_sources in
-lidarslam_amd/csrc/lsa_dense_map.hip) against DenseMapHost.reproject, byte for byte on points, voxel records and sources, at
+"""The dense map's re-projection on the device (lsa_dense_map_reproject in lidarslam_amd/csrc/lsa_dense_reproject.hip,
+lsa_dense_map_get_sources in lsa_dense_export.hip) against DenseMapHost.reproject, byte for byte on points, voxel records and sources, at
 min_frames 1 and 2: every case of tests/dense_reproject_cases.py, sizes, contention on one slot, growth, long probe sequences,
 rotations, refusals, insertion afterwards; and the pipeline under "DenseMapOnTrajectory"."""
 import numpy as np

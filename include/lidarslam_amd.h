@@ -141,9 +141,14 @@ typedef struct lsa_wire_layout_t
  * ring when mapping_len == 0), device_id, time = the record's time offset.  When the time field is not usable
  * (last - first <= 1e-8, :74) the time is built from the azimuth advancement exactly as the node does
  * (SpinningFrameAdvancementEstimator, lidar_conversions/src/Utilities.h:62-114, rpm and timestamp_first_packet
- * as its parameters): per ring that is "the first descent of the advancement and everything after it", found on the
- * ring-bucketed frame on the device (portable arc tangent: the time agrees with the node's to rounding).  The first
- * frame (azimuthal resolution estimate) is converted on the host. */
+ * as its parameters): per ring, in arrival order, a point gets + 1 turn when the ring's last descent of the
+ * advancement (a point below the ring's point right in front of it) lies behind the ring's last NaN advancement (a NaN
+ * x or y: the node stores the NaN and the ring starts afresh) -- without NaN records that is "the first descent and
+ * everything after it".  Both are scanned on the ring-bucketed frame on the device (portable arc tangent: the time
+ * agrees with the node's to rounding; the arc tangent does not tell y = -0.0 from +0.0 at x < 0, where libm gives -pi
+ * and +pi, and the wrap into [0, 1) makes the two advancements agree).  A laser id behind the mapping's end is 0xffff.
+ * The first frame (azimuthal resolution estimate) and a frame with a laser id >= 512, which the bucketing cannot hold,
+ * are converted on the host, with libm. */
 int lsa_upload_wire_frame(lsa_ctx* ctx, const void* records, int n, const lsa_wire_layout_t* layout, const uint16_t* laser_id_mapping,
                           int mapping_len, int device_id, double rpm, int timestamp_first_packet);
 
@@ -178,6 +183,10 @@ int lsa_frame_store_use(lsa_ctx* ctx, int slot);
 
 /* Number of points of the current frame. */
 int lsa_frame_size(const lsa_ctx* ctx);
+/* The current frame as the device holds it: a plain copy on the context's stream, waited for -- every bit as it is
+ * (-0.0, NaN payloads; lsa_transform_frame with the identity keeps neither).  Returns the number of points,
+ * LSA_E_STATE when there is no frame, LSA_E_CAPACITY when capacity is below the frame's size. */
+int lsa_download_frame(lsa_ctx* ctx, lsa_point_t* out, int capacity);
 
 float lsa_get_azimuthal_resolution(const lsa_ctx* ctx);
 void lsa_set_azimuthal_resolution(lsa_ctx* ctx, float rad);

@@ -175,6 +175,12 @@ class Context:
                            C.byref(stamp), C.byref(kept)), "lsa_upload_polydata_frame")
         return stamp.value, kept.value, rc == 1
 
+    def download_frame(self):
+        """lsa_download_frame: the current frame as the device holds it, bit for bit"""
+        out = np.zeros(max(self.L.lsa_frame_size(self.h), 1), POINT_DTYPE)
+        n = self._check(self.L.lsa_download_frame(self.h, ptr(out), out.size), "lsa_download_frame")
+        return out[:n]
+
     def extract_keypoints(self, params=None):
         params = params or ExtractParams()
         counts = np.zeros(3, np.int32)

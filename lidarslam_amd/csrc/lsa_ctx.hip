@@ -398,6 +398,16 @@ int lsa_bind_host_to_device(int device_id)
 }
 
 int lsa_frame_size(const lsa_ctx* ctx) { return ctx ? ctx->frame_n : 0; }
+int lsa_download_frame(lsa_ctx* ctx, lsa_point_t* out, int capacity)
+{
+  if (!ctx || !out) return ctx ? ctx->fail(LSA_E_ARG, "lsa_download_frame: null argument") : LSA_E_ARG;
+  if (!ctx->frame || ctx->frame_n <= 0) return ctx->fail(LSA_E_STATE, "lsa_download_frame: no frame");
+  if (capacity < ctx->frame_n) return ctx->fail(LSA_E_CAPACITY, "lsa_download_frame: capacity < frame size");
+  LSA_HIP(ctx, hipSetDevice(ctx->device));
+  LSA_HIP(ctx, hipMemcpyAsync(out, ctx->frame, (size_t)ctx->frame_n * sizeof(lsa_point_t), hipMemcpyDeviceToHost, ctx->stream));
+  LSA_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return ctx->frame_n;
+}
 float lsa_get_azimuthal_resolution(const lsa_ctx* ctx) { return ctx ? ctx->az_res : 0.f; }
 void lsa_set_azimuthal_resolution(lsa_ctx* ctx, float rad) { if (ctx) ctx->az_res = rad; }
 int lsa_nb_laser_rings(const lsa_ctx* ctx) { return ctx ? ctx->nb_rings_seen : 0; }

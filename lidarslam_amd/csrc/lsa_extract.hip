@@ -225,7 +225,7 @@ __global__ __launch_bounds__(256) void k_invalidate(const float4* __restrict__ x
                                                     ExtractConst c, uint8_t* __restrict__ valid)
 {
   const int j = blockIdx.x * blockDim.x + threadIdx.x;
-  if (j >= n) return;
+  if (j >= n || j >= ring_start[kMaxRings]) return;  // behind the points bucketed (a laser id >= 512 is in none) no slot was filled
   const int r = ring_of[j];
   const int idx = j - ring_start[r];
   const int np = ring_len[r];
@@ -323,7 +323,7 @@ __global__ __launch_bounds__(128) void k_curvature(const float4* __restrict__ xy
                                                    float* __restrict__ o_gap, float* __restrict__ o_sal, float* __restrict__ o_int)
 {
   const int j = blockIdx.x * blockDim.x + threadIdx.x;
-  if (j >= n) return;
+  if (j >= n || j >= ring_start[kMaxRings]) return;  // as in k_invalidate
   float angle = 0.f, gap = 0.f, sal = 0.f, igap = 0.f;
   const int r = ring_of[j];
   const int idx = j - ring_start[r];
@@ -919,37 +919,74 @@ static int extract_frame(lsa_ctx* ctx, const lsa_extract_params_t* params, int c
 }
 
 // ---- SpinningFrameAdvancementEstimator on the device (lidar_conversions/src/Utilities.h:62-114) --------------------
-// The estimator walks the frame in arrival order and keeps, per laser ring, the advancement of the ring's previous point:
-// a point whose advancement (in [0, 1)) is lower than its ring's previous one has passed the turn and gets + 1 -- and
-// from then on so does every later point of that ring (their advancement < 1 <= the stored value).  Per ring that is
-// "the first descent and everything after it": with the frame bucketed by ring (arrival order kept inside a ring) the
-// first descent is one comparison with the ring-major predecessor and a minimum per ring.
-__global__ __launch_bounds__(256) void k_first_wrap(const float4* __restrict__ frame, const uint32_t* __restrict__ orig, const uint16_t* __restrict__ ring_of,
-                                                    const int* __restrict__ ring_start, int n, int* __restrict__ first_wrap)
-{
-  const int p = blockIdx.x * blockDim.x + threadIdx.x;
-  if (p >= n) return;
-  const int ring = ring_of[p];
-  if (p == ring_start[ring]) return;  // the ring's first point compares with 0.0: never lower
-  const float4 b = frame[2 * (size_t)orig[p] + 1], a = frame[2 * (size_t)orig[p - 1] + 1];
-  const double cur = __hiloint2double(__float_as_int(b.y), __float_as_int(b.x)), prev = __hiloint2double(__float_as_int(a.y), __float_as_int(a.x));
-  if (cur < prev) atomicMin(&first_wrap[ring], p - ring_start[ring]);
-}
-__global__ __launch_bounds__(256) void k_time_from_advancement(float4* __restrict__ frame, const uint32_t* __restrict__ orig, const uint16_t* __restrict__ ring_of,
-                                                               const int* __restrict__ ring_start, int n, const int* __restrict__ first_wrap, double rpm,
+// The estimator walks the frame in arrival order and keeps, per laser ring, the value it gave the ring's previous point
+// (0 before the ring's first): a point whose advancement (in [0, 1), or NaN for a NaN x or y) is lower than that value
+// has passed the turn and gets + 1.  The value then stored is >= 1, so every later point of the ring gets + 1 as well --
+// until a NaN advancement: no comparison with a NaN holds, the NaN is what is stored, and the ring starts afresh with
+// the plain value of its next point.  Per ring, in arrival order, with
+//   last_reset    the last point so far whose advancement is NaN,
+//   last_descent  the last point so far whose advancement is below that of the ring's point right in front of it (false
+//                 when either is NaN, and for the ring's first point, which compares with 0),
+// a point gets + 1 exactly when last_descent > last_reset.  With the frame bucketed by ring (arrival order kept inside a
+// ring) both are inclusive running maxima along the ring: one workgroup per ring scans them, 256 points a turn.
+__global__ __launch_bounds__(256) void k_time_from_advancement(float4* __restrict__ frame, const uint32_t* __restrict__ orig,
+                                                               const int* __restrict__ ring_start, const int* __restrict__ ring_len, double rpm,
                                                                int first_packet)
 {
-  const int p = blockIdx.x * blockDim.x + threadIdx.x;
-  if (p >= n) return;
-  const int ring = ring_of[p];
-  float4 b = frame[2 * (size_t)orig[p] + 1];
-  double adv = __hiloint2double(__float_as_int(b.y), __float_as_int(b.x));
-  if (p - ring_start[ring] >= first_wrap[ring]) adv += 1.;
-  const double t = (first_packet ? adv : adv - 1) / rpm * 60.;  // VelodyneToLidarNode.cxx:106
-  const long long tb = __double_as_longlong(t);
-  b.x = __int_as_float((int)(tb & 0xffffffffll));
-  b.y = __int_as_float((int)(tb >> 32));
-  frame[2 * (size_t)orig[p] + 1] = b;
+  __shared__ int wave_desc[4], wave_reset[4];
+  __shared__ double turn_adv[256];
+  const int start = ring_start[blockIdx.x], len = ring_len[blockIdx.x];  // the slots of a ring were all filled by the scatter
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  int run_desc = -1, run_reset = -1;  // over the turns in front of this one
+  double carry = 0.;                  // the advancement of the last point of the turn in front of this one
+  for (int base = 0; base < len; base += 256)
+  {
+    const int k = base + threadIdx.x;
+    float4 b = make_float4(0.f, 0.f, 0.f, 0.f);
+    double adv = 0.;
+    if (k < len)
+    {
+      b = frame[2 * (size_t)orig[start + k] + 1];
+      adv = __hiloint2double(__float_as_int(b.y), __float_as_int(b.x));
+    }
+    turn_adv[threadIdx.x] = adv;
+    __syncthreads();
+    const double before = threadIdx.x > 0 ? turn_adv[threadIdx.x - 1] : carry;
+    carry = turn_adv[255];
+    int desc = -1, reset = -1;
+    if (k < len)
+    {
+      if (adv != adv) reset = k;
+      if (k > 0 && adv < before) desc = k;
+    }
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1)
+    {
+      const int d = __shfl_up(desc, o), r = __shfl_up(reset, o);
+      if (lane >= o) { desc = max(desc, d); reset = max(reset, r); }
+    }
+    if (lane == 63) { wave_desc[wave] = desc; wave_reset[wave] = reset; }
+    __syncthreads();
+    int all_desc = run_desc, all_reset = run_reset;
+    for (int w = 0; w < 4; ++w)
+    {
+      if (w == wave) { desc = max(desc, all_desc); reset = max(reset, all_reset); }
+      all_desc = max(all_desc, wave_desc[w]);
+      all_reset = max(all_reset, wave_reset[w]);
+    }
+    run_desc = all_desc;
+    run_reset = all_reset;
+    __syncthreads();  // wave_desc / wave_reset / turn_adv are rewritten in the next turn
+    if (k < len)
+    {
+      if (desc > reset) adv += 1.;
+      const double t = (first_packet ? adv : adv - 1) / rpm * 60.;  // VelodyneToLidarNode.cxx:106
+      const long long tb = __double_as_longlong(t);
+      b.x = __int_as_float((int)(tb & 0xffffffffll));
+      b.y = __int_as_float((int)(tb >> 32));
+      frame[2 * (size_t)orig[start + k] + 1] = b;
+    }
+  }
 }
 
 }  // extern "C"
@@ -974,11 +1011,9 @@ int time_from_advancement(lsa_ctx* ctx, lsa_point_t* frame, int n, double rpm, i
   hipLaunchKernelGGL(k_ring_scan, dim3(kMaxRings), dim3(64), 0, st, ctx->block_hist, nblocks, ctx->ring_len, meta);
   hipLaunchKernelGGL(k_ring_scatter, dim3(nblocks), dim3(256), 0, st, f4, n, ctx->block_hist, ctx->ring_len, ctx->ring_start, ctx->xyzi, ctx->orig,
                      ctx->ring_of, ctx->valid);
-  int* first_wrap = ctx->ring_counts;  // [kMaxRings] of its 3 x kMaxRings ints
-  LSA_HIP(ctx, hipMemsetAsync(first_wrap, 0x7f, kMaxRings * sizeof(int), st));
-  hipLaunchKernelGGL(k_first_wrap, dim3((n + 255) / 256), dim3(256), 0, st, f4, ctx->orig, ctx->ring_of, ctx->ring_start, n, first_wrap);
-  hipLaunchKernelGGL(k_time_from_advancement, dim3((n + 255) / 256), dim3(256), 0, st, f4, ctx->orig, ctx->ring_of, ctx->ring_start, n, first_wrap, rpm,
-                     first_packet);
+  // a ring's own slots only: behind a laser id the bucketing cannot hold, the slots at the end of the ring-major arrays
+  // were filled by nobody (the frame goes to the host below, whatever time its bucketed points got here)
+  hipLaunchKernelGGL(k_time_from_advancement, dim3(kMaxRings), dim3(256), 0, st, f4, ctx->orig, ctx->ring_start, ctx->ring_len, rpm, first_packet);
   int* hp = reinterpret_cast<int*>(ctx->host_pinned);
   LSA_HIP(ctx, hipMemcpyAsync(hp, ctx->extract_out, 16 * sizeof(int), hipMemcpyDeviceToHost, st));
   LSA_HIP(ctx, hipStreamSynchronize(st));

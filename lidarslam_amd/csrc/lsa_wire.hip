@@ -171,8 +171,9 @@ int lsa_upload_wire_frame(lsa_ctx* ctx, const void* data, int n, const lsa_wire_
   LSA_HIP(ctx, hipStreamSynchronize(ctx->stream));  // the caller's buffer may be pageable and go away
   if (!isTimeValid)
   {
-    // no usable time field: built from the azimuth advancement (a per-ring "first descent" found on the ring-bucketed
-    // frame), on the device; laser ids the bucketing cannot hold go through the host
+    // no usable time field: built from the azimuth advancement (per ring, + 1 behind a descent until a NaN advancement
+    // resets the ring: scanned on the ring-bucketed frame), on the device; laser ids the bucketing cannot hold go through
+    // the host
     rc = time_from_advancement(ctx, ctx->frame_own, n, rpm, timestamp_first_packet);
     if (rc == LSA_E_CAPACITY) return on_host();
     if (rc) return rc;

@@ -416,7 +416,7 @@ def test_wire_format_upload_follows_the_driver_node(O, L):
         for first in (False, True):
             want, valid = O.velodyne_to_lidar(rec, VELODYNE_LAYOUT, None, 0, 600.0, first)
             assert not valid and np.ptp(want["time"]) > 0.05
-            # on the device: per ring "the first descent of the advancement and everything after it" on the ring-bucketed
+            # on the device: per ring "+ 1 behind a descent of the advancement, until a NaN resets the ring" on the ring-bucketed
             # frame; the arc tangent is the portable one, so the time agrees with the node's libm value to rounding
             ctx.upload_wire_frame(rec, VELODYNE_LAYOUT, None, 0, 600.0, first)
             got = ctx.transform_frame(eye)
